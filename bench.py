@@ -26,6 +26,12 @@ cohorts bin-sharded across 8 GPUs, RCCL all-gather of sufficient stats"):
     strong    the same sharding of ONE configs[2] problem (120 091 elements in all): strong scaling, extra curve.
     replicas  every rank its own whole-genome problem, no exchange inside the step.
 Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times the K steps and prints the line (metric, value, unit, ms_per_step, the workload):
+nothing else is measured or checked.  --full adds everything else the bench reports: CPU baselines, per-stage and
+roofline figures sampled inside the loop, 1 000 extra steps behind a short run, the check against a sequential
+evaluation, the weak curve of --mode both, and the aux / e2e / --project-ranks legs.  --dump-outputs DIR writes what
+the last timed step computed as DIR/<name>.npy (see dump_outputs).
 """
 import argparse
 import json
@@ -649,6 +655,36 @@ def aux_rooflines(dev):
     return out
 
 # --------------------------------------------------------------------------------------
+DUMP_BYTES = 48 << 20       # --dump-outputs: all elements up to this size, a fixed sample of them above it
+DUMP_SEED = 20261015
+
+
+def dump_outputs(out_dir, plan, elements):
+    """--dump-outputs: what `plan`'s last run computed, as a caller of dig_element_pipeline receives it -- the statistics planes
+    (engine.ES_PLANES) and MU, SIGMA, R_OBS, FLAG, P [E, C], R_SIZE, ELT_SIZE, P_INDEL [E] -- as out_dir/<name>.npy in float64
+    (the integer outputs exactly), and `element` [n]: the global ids of the rows written.  When all elements would take more
+    than DUMP_BYTES, the rows are a sample drawn with a fixed seed, the same for every run of the same arguments."""
+    import torch
+    from digdriver_amd import engine
+    if plan.records_out:
+        plan.unpack()                                   # the tile-blocked records -> the planes (dig_element_records_unpack)
+    E, C = plan.E, plan.C
+    per_element = 8 * ((len(engine.ES_PLANES) + 5) * C + 4)
+    if E * per_element <= DUMP_BYTES:
+        rows = np.arange(E)
+    else:
+        rows = np.sort(np.random.default_rng(DUMP_SEED).choice(E, DUMP_BYTES // per_element, replace=False))
+    idx = torch.as_tensor(rows, device=plan.dev)
+    out = {name: plan.stats[j].index_select(0, idx) for j, name in enumerate(engine.ES_PLANES)}
+    acc = plan.acc
+    out.update({k: acc[k].index_select(0, idx) for k in ("MU", "SIGMA", "R_OBS", "FLAG", "R_SIZE", "ELT_SIZE", "P_INDEL")})
+    out["P"] = acc["P"][:, 0, :].index_select(0, idx)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), t.cpu().numpy().astype(np.float64))
+    np.save(os.path.join(out_dir, "element.npy"), np.asarray(elements)[rows].astype(np.float64))
+
+
 def _flush_c_stdout():
     try:
         import ctypes
@@ -665,7 +701,7 @@ def parse_args(argv=None):
     ap.add_argument("--bins", type=int, default=288_000)
     ap.add_argument("--elements", type=int, default=120_091)
     ap.add_argument("--cohorts", type=int, default=37)
-    ap.add_argument("--cpu-sample", type=int, default=100_000, help="elements in the CPU-baseline sample (0 = skip)")
+    ap.add_argument("--cpu-sample", type=int, default=100_000, help="with --full: elements in the CPU-baseline sample (0 = skip)")
     ap.add_argument("--seed", type=int, default=3)
     ap.add_argument("--mode", choices=["both", "sharded", "strong", "replicas"], default="both",
                     help="how N > 1 ranks divide the work (see the module docstring); all are configs[2] at N = 1.  both (default): "
@@ -688,15 +724,15 @@ def parse_args(argv=None):
                          "and keeps the faster (developer A/B; the pool's cards differ in which one wins).  No re-layout is part of the timed "
                          "step in any form; same bits")
     ap.add_argument("--aux", type=int, default=1,
-                    help="1: after the timed region (N = 1 only) run short legs of the other SURVEY 8d kernels -- track gather, CNN "
+                    help="with --full, 1: after the timed region (N = 1 only) run short legs of the other SURVEY 8d kernels -- track gather, CNN "
                          "forward, per-base tiles, context counting -- and report them as aux_rooflines; 0: skip")
     ap.add_argument("--e2e", type=int, default=1,
-                    help="1: after the timed region (N = 1 only) write configs[2] as FILES (37 HDF5 maps, element data, 37 mutation "
+                    help="with --full, 1: after the timed region (N = 1 only) write configs[2] as FILES (37 HDF5 maps, element data, 37 mutation "
                          "files) and time the drop-in from files to 37 results.txt, stage by stage (tools/e2e_bench.py; ~40 s, 1.7 GB "
                          "under --e2e-dir); reported as e2e; 0: skip")
     ap.add_argument("--e2e-dir", default=None, help="scratch directory of the e2e leg (default: a fresh directory under the system's temp)")
     ap.add_argument("--project-ranks", type=int, default=0,
-                    help="N > 1 (one GPU only): behind the timed region, build every rank's shard of the strong configs[3] split for 2, 4, ... N "
+                    help="with --full, N > 1 (one GPU only): behind the timed region, build every rank's shard of the strong configs[3] split for 2, 4, ... N "
                          "ranks, time each rank's step on THIS GPU and report the slowest + the world-1 cost of the all-gather call as "
                          "projected_strong_scaling -- a projection, never part of `value` (about a minute of host time per 8 shards)")
     ap.add_argument("--side-lead", type=int, default=0,
@@ -707,6 +743,12 @@ def parse_args(argv=None):
     ap.add_argument("--settle-ms", type=float, default=400.0,
                     help="untimed: the sequential evaluation the loop is checked against is repeated for this long before "
                          "the W warm-up steps (brings the GPU out of its idle power state; 0 = evaluate once)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline figure (see the module docstring); "
+                         "--cpu-sample, --aux, --e2e and --project-ranks take effect with --full only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the outputs of the last timed step as DIR/<name>.npy (float64; rank 0's "
+                         "elements; a fixed, seeded sample of them above %d MB in all)" % (DUMP_BYTES >> 20))
     return ap.parse_args(argv)
 
 
@@ -814,10 +856,12 @@ def main():
     if args.gpus > 1 and world != args.gpus:
         raise SystemExit("--gpus %d but WORLD_SIZE=%d: launch %d ranks (or leave WORLD_SIZE unset: bench.py starts them itself)"
                          % (args.gpus, world, args.gpus))
-    ctx_gpu = gpu_identity() if rank == 0 else {}
+    ctx_gpu = gpu_identity() if rank == 0 and args.full else {}
     # (BENCH_FORCE_BOTH=1: a one-GPU check of the N > 1 control flow -- two workloads timed one after the other in one process)
     modes = [args.mode] if args.mode != "both" else (["strong", "sharded"] if world > 1 or os.environ.get("BENCH_FORCE_BOTH") == "1"
                                                      else ["sharded"])
+    if not args.full:
+        modes = modes[:1]                            # the weak curve beside the strong `value` is a --full figure
     ctx = {"rank": rank, "local_rank": local_rank, "world": world, "gpu_serials": ctx_gpu}
     res = None
     for i, mode in enumerate(modes):
@@ -865,7 +909,7 @@ def run_workload(args, mode, ctx, primary=True):
     E_total = n_elements_global if sharded else args.elements * world
     # CPU baselines first: the all-core one forks workers, which must happen before this process touches the GPU
     cpu_res = (None, None)
-    if world == 1 and args.cpu_sample > 0 and primary:
+    if world == 1 and args.full and args.cpu_sample > 0 and primary:
         cpu_res = (cpu_baseline(w, args.cpu_sample), cpu_baseline_all_cores(w))
     if "dev" not in ctx:
         _lib.require_device()
@@ -910,8 +954,8 @@ def run_workload(args, mode, ctx, primary=True):
     # reduction, squeezed beside the dot kernel, finished 5 us after it: rocprofv3 kernel trace, 0.301 -> 0.290 ms.)
     SIDE_LEAD_STEPS = 3                      # the side stream is enqueued this many steps ahead of the main stream (slack for the all-gather at N > 1)
     # a short run (the driver's --steps 20 is 3.6 ms of GPU time) is followed by an UNTIMED-by-the-driver loop of 1 000 more steps of
-    # the same kind, reported beside it as ms_per_step_1000 (primary workload only)
-    EXTRA_STEPS = 1000 if (args.steps < 100 and primary) else 0
+    # the same kind, reported beside it as ms_per_step_1000 (primary workload only, --full)
+    EXTRA_STEPS = 1000 if (args.full and args.steps < 100 and primary) else 0
     RING = args.steps + args.warmup + EXTRA_STEPS + SIDE_LEAD_STEPS + 2      # one set of scale-factor buffers per step: the side stream never waits
     cj_outs = [(torch.empty(C, dtype=torch.float64, device=dev), torch.empty(C, dtype=torch.float64, device=dev))
                for _ in range(RING)]
@@ -1047,7 +1091,7 @@ def run_workload(args, mode, ctx, primary=True):
     # (Two events around the statistics stage read 148 - 154 us on the common GPUs of the pool where rocprofv3's kernel
     #  trace of the same run says 137: the packets split the call in three and change what the side stream's kernels run
     #  beside -- profiles/r04b_*.)
-    timer_pool = [engine.StageTimer() for _ in range(2 * ((args.steps + args.warmup) // SAMPLE_EVERY + 4) + 1)]
+    timer_pool = [engine.StageTimer() for _ in range(2 * ((args.steps + args.warmup) // SAMPLE_EVERY + 4) + 1)] if args.full else []
     timer_samples = {"dot": [], "statistics": []}
     for e in side_done + main_done + sample_events + slack_events:
         e.record(main_stream)
@@ -1194,7 +1238,7 @@ def run_workload(args, mode, ctx, primary=True):
         pipe.run(seq_cj, seq_cji, stages=7, stream=main_stream)
     torch.cuda.synchronize()
     settle_ms = (time.perf_counter() - t_settle) * 1e3
-    warming[0] = True
+    warming[0] = args.full                           # (a short run brackets its smaller stages on the warm-up steps: --full)
     for _ in range(args.warmup):
         step()
     warming[0] = False
@@ -1206,7 +1250,7 @@ def run_workload(args, mode, ctx, primary=True):
     ev_begin, ev_end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     t0 = time.perf_counter()
     ev_begin.record(main_stream)
-    sampling[0] = True
+    sampling[0] = args.full                          # stage timers and slack events on the sampled steps: --full figures
     trace = [] if os.environ.get("BENCH_TRACE") == "1" else None      # developer switch: host time of every enqueue
     for _ in range(args.steps):
         if trace is not None:
@@ -1229,6 +1273,38 @@ def run_workload(args, mode, ctx, primary=True):
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         dt = float(tmax.item())
     ms_step = ev_begin.elapsed_time(ev_end) / args.steps
+    res = None
+    if rank == 0:
+        units = float(E_total) * C * args.steps
+        res = {
+            "metric": "genomic elements tested/sec (whole node), whole-genome x 37 cohorts",
+            "value": units / dt, "unit": "element-cohort tests/s", "n_gpus": world, "steps": args.steps,
+            "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True,
+            "scaling": "strong" if (mode == "strong" and world > 1) else "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+            "config": {"workload": ("BASELINE configs[2]: whole genome, %d 10-kb bins, %d cohorts batched, %d elements, K=192 "
+                                    "substitution types, mean %.2f bins/element" % (args.bins, C, E_total, nbar)) if world == 1 else
+                                   {"sharded": "BASELINE configs[3]: ONE genome of %d 10-kb bins cut into %d contiguous bin ranges (one per "
+                                               "GPU, + halo), %d cohorts batched, %d elements in all (%d per GPU: the element set grows "
+                                               "with N), all-gather of the per-cohort chunk sums every step",
+                                    "strong": "BASELINE configs[3], strong form: ONE configs[2] problem (%d bins / %d ranks, %d cohorts, %d "
+                                              "elements in all, about %d per GPU), all-gather of the per-cohort chunk sums every step",
+                                    "replicas": "%d-bin genome replicated on each of %d GPUs, %d cohorts, %d elements in all (%d per GPU), "
+                                                "no exchange"}[mode] % (args.bins, world, C, E_total, E_total // world),
+                       "mode": mode, "contexts_on": args.contexts_on,
+                       "scale_factors": "DEVELOPER PROBE (BENCH_NO_SIDE): formed ONCE, not per step -- not a valid bench line" if os.environ.get("BENCH_NO_SIDE") else (
+                                         "kernels of their own on a side stream, several steps ahead" + (" (chunk sums all-gathered over RCCL)" if use_dist and exchange else "")),
+                       "bins": args.bins, "bins_on_rank0": N, "cohorts": C, "elements_total": E_total,
+                       "elements_on_rank0": E, "parallelism": "bins sharded x%d" % world if mode != "replicas" else "replicas x%d" % world},
+            "output_form": output_form,
+            "one_shot": one_shot,
+            "host_enqueue_ms_per_step": host_enqueue_s / args.steps * 1e3,
+            "untimed_settle": {"ms": settle_ms, "sequential_evaluations": n_settle, "two_stream_passes": args.settle_passes,
+                               "what": "the sequential evaluation the loop is checked against, repeated before the warm-up steps"},
+        }
+        if args.dump_outputs and primary:
+            dump_outputs(args.dump_outputs, pipes[(step_no[0] - 1) % PLAN_RING], w["elements"])
+    if not args.full:
+        return res
     ms_step_1000 = None
     if EXTRA_STEPS:
         gc.disable()
@@ -1327,7 +1403,6 @@ def run_workload(args, mode, ctx, primary=True):
         slow_frac = float(int(hdr[2].item()) + int(hdr[3].item())) / (E * C)
 
     if rank == 0:
-        units = float(E_total) * C * args.steps
         b_acc, b_stat = algorithmic_bytes(E, C, nbar)
         b_suff = 9.0 * N_own * C                                 # sufficient statistics: Y_PRED f64 + FLAG u8 per (own bin, cohort)
         # SURVEY 8d's algorithmic bytes, split by the stage that moves them (the three parts add up to b_acc + b_stat):
@@ -1407,25 +1482,7 @@ def run_workload(args, mode, ctx, primary=True):
                 dominant_roof["bracket_note"] = ("avg_launch_ms is the raw event-to-event time of a bracket; a bracket around a one-element "
                                                  "fill kernel takes the figure above, so ~4-6 us of avg_launch_ms are the two event packets "
                                                  "and the dispatch, not the kernel")
-        res = {
-            "metric": "genomic elements tested/sec (whole node), whole-genome x 37 cohorts",
-            "value": units / dt, "unit": "element-cohort tests/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True,
-            "scaling": "strong" if (mode == "strong" and world > 1) else "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
-            "config": {"workload": ("BASELINE configs[2]: whole genome, %d 10-kb bins, %d cohorts batched, %d elements, K=192 "
-                                    "substitution types, mean %.2f bins/element" % (args.bins, C, E_total, nbar)) if world == 1 else
-                                   {"sharded": "BASELINE configs[3]: ONE genome of %d 10-kb bins cut into %d contiguous bin ranges (one per "
-                                               "GPU, + halo), %d cohorts batched, %d elements in all (%d per GPU: the element set grows "
-                                               "with N), all-gather of the per-cohort chunk sums every step",
-                                    "strong": "BASELINE configs[3], strong form: ONE configs[2] problem (%d bins / %d ranks, %d cohorts, %d "
-                                              "elements in all, about %d per GPU), all-gather of the per-cohort chunk sums every step",
-                                    "replicas": "%d-bin genome replicated on each of %d GPUs, %d cohorts, %d elements in all (%d per GPU), "
-                                                "no exchange"}[mode] % (args.bins, world, C, E_total, E_total // world),
-                       "mode": mode, "contexts_on": args.contexts_on,
-                       "scale_factors": "DEVELOPER PROBE (BENCH_NO_SIDE): formed ONCE, not per step -- not a valid bench line" if os.environ.get("BENCH_NO_SIDE") else (
-                                         "kernels of their own on a side stream, several steps ahead" + (" (chunk sums all-gathered over RCCL)" if use_dist and exchange else "")),
-                       "bins": args.bins, "bins_on_rank0": N, "cohorts": C, "elements_total": E_total,
-                       "elements_on_rank0": E, "parallelism": "bins sharded x%d" % world if mode != "replicas" else "replicas x%d" % world},
+        res.update({
             "ms_per_step_1000": ms_step_1000,
             "ms_per_step_1000_note": ("the same step, 1 000 more times after the timed region (own barriers, host clock, max over "
                                       "ranks); NOT part of `value`: the asked %d steps are %.1f ms of GPU time" % (args.steps, dt * 1e3)
@@ -1468,17 +1525,12 @@ def run_workload(args, mode, ctx, primary=True):
                              % (args.contexts_on, SAMPLE_EVERY, "one of the smaller stages on every %d-th timed step" % SAMPLE_EVERY
                                 if not SHORT else "the smaller stages on the warm-up steps (a run this short keeps them out of "
                                                           "its timed steps)", args.steps),
-            "output_form": output_form,
-            "one_shot": one_shot,
             "finite_pvalues": ok, "matches_sequential_evaluation": same, "slow_pair_fraction": slow_frac,
-            "host_enqueue_ms_per_step": host_enqueue_s / args.steps * 1e3,
             "side_stream_slack_us": ({"min": slack_us[0], "median": slack_us[len(slack_us) // 2], "samples": len(slack_us),
                                       "what": "main stream's arrival at the wait for a step's scale factors minus the moment the side "
                                               "stream had them ready (events on both streams, every 8th timed step); negative = the "
                                               "main stream waited"} if slack_us else None),
-            "untimed_settle": {"ms": settle_ms, "sequential_evaluations": n_settle, "two_stream_passes": args.settle_passes,
-                               "what": "the sequential evaluation the loop is checked against, repeated before the warm-up steps"},
-        }
+        })
         if args.aux and world == 1 and primary:
             del td, pipes, seq_plan
             torch.cuda.empty_cache()
