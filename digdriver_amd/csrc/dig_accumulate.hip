@@ -229,15 +229,10 @@ static int launch_acc_v1(const AccArgs& a, hipStream_t stream)
 //   acc_dot_mfma_kernel  the [E x 256] x [256 x C] FP64 product on the matrix cores, quotient and element sizes.
 // =======================================================================================
 typedef double double4_t __attribute__((ext_vector_type(4)));
-#ifndef DIG_MFMA_WAVES
-#define DIG_MFMA_WAVES 12
-#endif
 // waves per workgroup (one workgroup per CU: the table takes <= 96 KB LDS): three per SIMD hide the LDS / HBM waits better
 // than two (127.7 -> 124.2 us per accumulate call); four would cap the kernel at 128 VGPRs and spill
-constexpr int kMfmaWaves = DIG_MFMA_WAVES;
-#ifndef DIG_MFMA_MINBLOCKS
-#define DIG_MFMA_MINBLOCKS 1
-#endif
+constexpr int kMfmaWaves = 12;
+constexpr int kMfmaMinBlocks = 1;
 constexpr int kMfmaSteps = 64;                // 256 K rows / 4
 constexpr int kMfmaChunk = 48;                // cohorts per launch (3 B tiles)
 
@@ -488,7 +483,7 @@ __device__ __forceinline__ void fix_zero_denominators(const double4_t (&den)[NT 
 }
 
 template <int NCLASS, int NT, int NQ>
-__global__ __launch_bounds__(kMfmaWaves * 64, DIG_MFMA_MINBLOCKS) void acc_dot_mfma_kernel(
+__global__ __launch_bounds__(kMfmaWaves * 64, kMfmaMinBlocks) void acc_dot_mfma_kernel(
     const int32_t* __restrict__ rcp, const int32_t* __restrict__ L, const double* __restrict__ tab_g,
     const int32_t* __restrict__ R_SIZE, const int32_t* __restrict__ gene_length, double* __restrict__ P,
     int32_t* __restrict__ ELT_SIZE, double* __restrict__ P_INDEL, int64_t E, int C, int c0, int write_sizes,
@@ -651,10 +646,7 @@ __global__ __launch_bounds__(kMfmaWaves * 64, DIG_MFMA_MINBLOCKS) void acc_dot_m
 // slice 4 t' + (3 - k) instead and takes component 3 - t of slice 3 - u where the '+' strand takes component u of slice t
 // (revcomp(16 t + 4 k + u) = 16 (3 - u) + 4 (3 - k) + (3 - t)).  No context rows cross HBM between two kernels any more.
 // =======================================================================================
-#ifndef DIG_CTX_WAVES
-#define DIG_CTX_WAVES 12
-#endif
-constexpr int kCtxWaves = DIG_CTX_WAVES;
+constexpr int kCtxWaves = 12;
 constexpr int kCtxSteps = 16;                 // 64 context rows / 4
 
 __global__ __launch_bounds__(256) void compact_L_kernel(const int32_t* __restrict__ L, int64_t n64, int32_t* __restrict__ Lc,

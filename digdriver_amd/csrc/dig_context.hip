@@ -229,15 +229,8 @@ constexpr int kC2PadBases = 64;            // bases in front of chromosome data 
 constexpr int kC2BucketShift = 12;         // nint_bucket[b]: first run that ends behind base b << 12
 constexpr int64_t kC2SegQuads = 65534;     // 4-mers per segment: no 16-bit counter can wrap
 
-#ifndef DIG_C2_ABL
-#define DIG_C2_ABL 0       // developer ablation builds (tools/build_variant.sh): 1 no LDS atomics (addresses still formed), 2 no global loads in the scan
-#endif
-#if DIG_C2_ABL & 1
-#define DIG_C2_ADD(addr, val) asm volatile("" ::"v"(addr), "v"(val))
-#else
 #define DIG_C2_ADD(addr, val) \
     __hip_atomic_fetch_add(reinterpret_cast<lds_u32*>(static_cast<uintptr_t>(addr)), (unsigned)(val), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)
-#endif
 
 // the 6-bit code (left base in the low bits) of the window centred at base c
 __device__ __forceinline__ unsigned c2_tri(const uint32_t* __restrict__ w, int64_t c)
@@ -273,11 +266,6 @@ struct C2Step {
 __device__ __forceinline__ C2Step c2_load_step(const uint32_t* __restrict__ words, int64_t S)
 {
     C2Step t;
-#if DIG_C2_ABL & 2
-    for (int g = 0; g < 4; ++g) t.v[g] = make_uint4((uint32_t)S * 2654435761u, (uint32_t)S * 40503u, (uint32_t)S + g, (uint32_t)S ^ 0x9e3779b9u);
-    t.after = (uint32_t)S;
-    return t;
-#endif
     const uint4* p = reinterpret_cast<const uint4*>(words + 16 * S);
 #pragma unroll
     for (int g = 0; g < 4; ++g) t.v[g] = p[g];

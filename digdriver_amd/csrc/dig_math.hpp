@@ -58,13 +58,7 @@ __device__ __forceinline__ double nb_success_prob(double theta, double pi)
 #pragma clang fp contract(off)
     double t = theta * pi;
     double d = t + 1.0;
-#ifdef DIG_FAST_P          // developer A/B: hardware reciprocal + two Newton steps (p within an ulp) instead of the IEEE division
-    double r = __builtin_amdgcn_rcp(d);
-    r = __builtin_fma(__builtin_fma(-d, r, 1.0), r, r);
-    return __builtin_fma(__builtin_fma(-d, r, 1.0), r, r);
-#else
     return 1.0 / d;
-#endif
 }
 
 __device__ __forceinline__ double mul_rn(double a, double b)
@@ -267,12 +261,8 @@ static __device__ __constant__ const double kLogTabRom[128][2] = {
 };
 __shared__ __attribute__((aligned(16))) double g_log_tab[128][2];
 
-__device__ __forceinline__ double fast_log_normal_classic(double x);
 __device__ __forceinline__ double fast_log_normal(double x)
 {
-#ifdef DIG_CLASSIC_LOG
-    return fast_log_normal_classic(x);
-#endif
     const unsigned long long bits = (unsigned long long)__double_as_longlong(x);
     const uint32_t hx = (uint32_t)(bits >> 32);
     const uint32_t tmp = hx - 0x3fe60000u;                     // high word of bits(x) - bits(0.6875) (low word of OFF is 0)
@@ -292,35 +282,6 @@ __device__ __forceinline__ double fast_log_normal(double x)
     const double w = fma(dk, 6.93147180369123816490e-01, t.y);  // exact product (ln2_hi has 32 trailing zero bits)
     return w + fma(dk, 1.90821492927058770002e-10, y);
 }
-
-// Classical form (x = 2^k m, log m = 2 atanh(s) with the degree-14 polynomial in s^2; < 1 ulp, ~40 instructions).
-__device__ __forceinline__ double fast_log_normal_classic(double x)
-{
-    const long long bits = __double_as_longlong(x);
-    int hx = (int)(bits >> 32);
-    int k = (hx >> 20) - 1023;
-    hx &= 0x000fffff;
-    const int i = (hx + 0x95f64) & 0x100000;                   // m >= sqrt(2) -> halve it, k += 1
-    k += i >> 20;
-    const long long mbits = ((long long)(hx | (i ^ 0x3ff00000)) << 32) | (bits & 0xffffffffll);
-    const double f = __longlong_as_double(mbits) - 1.0;
-    const double s = f * recip_nr(2.0 + f);
-    const double z = s * s, w = z * z;
-    double t1 = 1.531383769920937332e-01;
-    t1 = fma_sconst(t1, w, 2.222219843214978396e-01);
-    t1 = fma_sconst(t1, w, 3.999999999940941908e-01);
-    t1 *= w;
-    double t2 = 1.479819860511658591e-01;
-    t2 = fma_sconst(t2, w, 1.818357216161805012e-01);
-    t2 = fma_sconst(t2, w, 2.857142874366239149e-01);
-    t2 = fma_sconst(t2, w, 6.666666666666735130e-01);
-    t2 *= z;
-    const double R = t1 + t2;
-    const double hfsq = 0.5 * f * f;
-    const double dk = (double)k;
-    return dk * 6.93147180369123816490e-01 - ((hfsq - (s * (hfsq + R) + dk * 1.90821492927058770002e-10)) - f);
-}
-
 
 __device__ __forceinline__ double fast_log(double x)
 {

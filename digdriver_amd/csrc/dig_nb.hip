@@ -90,23 +90,13 @@ struct ElementStatsArgs {
     const double2* bin_pack;   // dig_bin_records_pack: {Y_PRED, STD^2} per (bin, cohort), or NULL
     const int32_t* bin_yf;     //                       Y_TRUE | (FLAG != 0) << 31
     int rec;              // DIG_PIPE_RECORDS: out is [ceil(n / 64) * 64][kRecOut] doubles (one record per pair) instead of seven planes
-#ifdef DIG_DEV_ABLATE
-    int ablate;           // developer build only (tools/variant_bench.py): 1 no stores, 2 no recurrence, 4 no bin loop, 8 no arithmetic
-#endif
 };
 
 constexpr int kRecOut = 10;       // DIG_REC_DOUBLES: seven statistics, MU, SIGMA, {R_OBS, FLAG}
 // DIG_PIPE_RECORDS: field f of pair i lives in block i / 64 of 5 rows x 64 lanes x 2 doubles, at row f / 2, lane i % 64
-#ifndef DIG_REC_LAYOUT
-#define DIG_REC_LAYOUT 0
-#endif
 __device__ __forceinline__ int64_t rec_index(int64_t i, int f, int64_t n)
 {
-#if DIG_REC_LAYOUT == 1      // developer A/B: five "pair planes" [5][n_pad][2]
-    return (int64_t)(f >> 1) * (((n + 63) >> 6) << 7) + (i << 1) + (f & 1);
-#else
     return (((i >> 6) * (kRecOut / 2) + (f >> 1)) << 7) + ((i & 63) << 1) + (f & 1);
-#endif
 }
 // where plane `pl` of pair `i` lives (n pairs): the plane form, or field pl of the pair's record
 __device__ __forceinline__ double* out_slot(const ElementStatsArgs& a, int pl, int64_t n, int64_t i)
@@ -120,7 +110,6 @@ constexpr int kWorkHeader = 64;   // dwords reserved in front of the worklist (c
 struct PairRaw {
     double mu, sigma, pi_s, pi_i, mu_i, sigma_i, cj, cji;
     int k_snv, k_smp, k_ind;
-    int64_t q0, q1;   // fused pipeline: CSR range of the pair's element (instead of mu, sigma)
     uint32_t c;       // cohort of the pair
 };
 
@@ -128,20 +117,12 @@ struct PairInputs {
     double alpha, theta, p, exp_snv, alpha_i, theta_i, p_i, exp_ind, k_snv, k_smp, k_ind;
 };
 
-template <bool FUSED_RATES = false>
 __device__ __forceinline__ PairRaw load_raw(const ElementStatsArgs& a, int64_t i, int64_t e, int64_t c)
 {
     PairRaw r;
     r.c = (uint32_t)c;
-    if (FUSED_RATES) {
-        r.q0 = a.ov_ptr[e];
-        r.q1 = a.ov_ptr[e + 1];
-        r.mu = r.sigma = 0.0;
-    } else {
-        r.mu = a.rec ? a.out[rec_index(i, 7, a.E * a.C)] : a.mu[i];
-        r.sigma = a.rec ? a.out[rec_index(i, 8, a.E * a.C)] : a.sigma[i];
-        r.q0 = r.q1 = 0;
-    }
+    r.mu = a.rec ? a.out[rec_index(i, 7, a.E * a.C)] : a.mu[i];
+    r.sigma = a.rec ? a.out[rec_index(i, 8, a.E * a.C)] : a.sigma[i];
     r.pi_s = a.pi_sum[i];
     r.pi_i = a.pi_indel_per_cohort ? a.pi_indel[i] : a.pi_indel[e];
     r.k_snv = a.obs_snv[i];
@@ -154,11 +135,10 @@ __device__ __forceinline__ PairRaw load_raw(const ElementStatsArgs& a, int64_t i
     return r;
 }
 
-template <bool FUSED_RATES = false>
 __device__ __forceinline__ PairRaw load_raw(const ElementStatsArgs& a, int64_t i)
 {
     const int64_t e = a.use_fastdiv ? fastdiv(i, a.divC) : i;   // use_fastdiv == 0 only when C == 1
-    return load_raw<FUSED_RATES>(a, i, e, i - e * a.C);
+    return load_raw(a, i, e, i - e * a.C);
 }
 
 // Input preparation for one (element, cohort) pair, bit-identical to the reference's numpy
@@ -235,20 +215,16 @@ __device__ __forceinline__ unsigned park_flush(unsigned* worklist, const unsigne
     return 0;
 }
 
-// FUSED_RATES (dig_element_pipeline): MU = sum Y_PRED, SIGMA = sqrt(sum STD^2), R_OBS, FLAG of the pair are summed
-// here over the element's bins (same CSR order and IEEE operations as acc_region_kernel, genic_driver_tools.py:262-271)
-// and written out, instead of being read back from a previous kernel: 24 B per pair less HBM traffic each way.
 // The streaming pass writes 80 bytes per pair that nothing reads back soon (the compacted pass revisits 1 % of the pairs):
 // non-temporal stores keep them from displacing the bin tables and the next tiles' inputs in L2 (same-box A/B:
 // 166 -> 157 us for dig_element_stats, 263 -> 256 us for dig_element_pipeline).
-#ifdef DIG_ES_PLAIN_STORES                     // developer A/B: write-back stores instead of streaming ones
-#define DIG_STREAM_STORE(ptr, val) (*(ptr) = (val))
-#else
 #define DIG_STREAM_STORE(ptr, val) __builtin_nontemporal_store((val), (ptr))
-#endif
+// (FUSED_RATES stays in the parameter list so that the instantiations keep their names; the rate sums are formed by
+//  element_stats_stream_fused_kernel below)
 template <bool HAS_INDEL_PARAMS, bool FUSED_RATES = false>
 __global__ __launch_bounds__(kBlock) void element_stats_stream_kernel(ElementStatsArgs a)
 {
+    static_assert(!FUSED_RATES, "the rate sums are formed by element_stats_stream_fused_kernel");
     __shared__ unsigned park_all[kBlock / 64][kParkCap];
     nb_tables_init();
     unsigned* park = park_all[threadIdx.x >> 6];
@@ -271,7 +247,7 @@ __global__ __launch_bounds__(kBlock) void element_stats_stream_kernel(ElementSta
     uint32_t cu = (uint32_t)(iu - eu * a.C);
     auto clamped_load = [&]() {
         const bool past = iu >= n;
-        return load_raw<FUSED_RATES>(a, past ? n - 1 : iu, past ? a.E - 1 : eu, past ? (int64_t)(C32 - 1) : (int64_t)cu);
+        return load_raw(a, past ? n - 1 : iu, past ? a.E - 1 : eu, past ? (int64_t)(C32 - 1) : (int64_t)cu);
     };
     PairRaw nxt = clamped_load();
     unsigned parked = 0;   // wave-uniform
@@ -288,59 +264,12 @@ __global__ __launch_bounds__(kBlock) void element_stats_stream_kernel(ElementSta
             eu += 1;
         }
         nxt = clamped_load();
-        if (FUSED_RATES) {
-            double mu = 0.0, var = 0.0;
-            int robs = 0, flag = 0;
-            const int32_t* oi = a.ov_idx + cur.q0;
-            uint32_t nb = (uint32_t)(cur.q1 - cur.q0);
-#ifdef DIG_DEV_ABLATE
-            if (a.ablate & 4) nb = 0;
-#endif
-            if (a.small_index) {
-                for (uint32_t j = 0; j < nb; ++j) {
-                    const uint32_t o = __umul24((uint32_t)oi[j], C32) + cur.c;   // bin row * C + cohort
-                    const double sd = a.bin_std[o];
-                    mu += a.bin_mu[o];
-                    var += mul_rn(sd, sd);
-                    robs += a.bin_y[o];
-                    flag |= (a.bin_flag[o] != 0);
-                }
-            } else {
-                for (uint32_t j = 0; j < nb; ++j) {
-                    const int64_t o = (int64_t)oi[j] * a.C + cur.c;
-                    const double sd = a.bin_std[o];
-                    mu += a.bin_mu[o];
-                    var += mul_rn(sd, sd);
-                    robs += a.bin_y[o];
-                    flag |= (a.bin_flag[o] != 0);
-                }
-            }
-            cur.mu = mu;
-            cur.sigma = sqrt(var);
-            DIG_STREAM_STORE(&a.mu_w[i], cur.mu);
-            DIG_STREAM_STORE(&a.sigma_w[i], cur.sigma);
-            DIG_STREAM_STORE(&a.r_obs[i], robs);
-            DIG_STREAM_STORE(&a.flag[i], flag);
-        }
-#ifdef DIG_DEV_ABLATE
-        if (a.ablate & 2) cur.k_snv = cur.k_smp = cur.k_ind = 0;
-        if (a.ablate & 8) {
-            const double v = cur.mu + cur.sigma + cur.pi_s + cur.pi_i + (double)(cur.k_snv + cur.k_smp + cur.k_ind) + cur.cj + cur.cji;
-            if (!(a.ablate & 1) || v == 12345.678) {
-                for (int pl = 0; pl < 7; ++pl) DIG_STREAM_STORE(&a.out[pl * n + i], v);
-            }
-            continue;
-        }
-#endif
         const PairInputs q = prepare_pair(cur, HAS_INDEL_PARAMS);
         // (a test the recurrence cannot finish keeps a NEGATIVE value for pass 2: -pmf(k) when the direct form
         //  cancelled, -2 when it was not eligible at all; no p-value is negative)
         double pv_snv, pv_smp, pv_ind, dummy;
         const unsigned d1 = nb_fast2_counts<1>(cur.k_snv, cur.k_smp, true, q.alpha, q.p, pv_snv, pv_smp);
         const unsigned d2 = nb_fast2_counts<1>(cur.k_ind, 0, false, q.alpha_i, q.p_i, pv_ind, dummy);
-#ifdef DIG_DEV_ABLATE
-        if ((a.ablate & 1) && !(pv_snv + pv_smp + pv_ind + q.exp_snv + q.exp_ind + q.theta_i == 12345.678)) continue;
-#endif
         const bool slow = ((d1 != 3u) || (d2 != 1u)) && i_raw < n;
         const unsigned long long m = __ballot(slow);
         if (slow) park[parked + __popcll(m & lanes_below)] = (unsigned)i;
@@ -362,7 +291,7 @@ __global__ __launch_bounds__(kBlock) void element_stats_stream_kernel(ElementSta
 }
 
 // ---- Pass 1 of dig_element_pipeline: fused rates, three-deep software pipeline -----------------------------------------
-// Ablation of the two-stage form above on the bench workload (tools/variant_bench.py): its loads and
+// Ablation of the two-stage form above with the rate sums fused in (a form since removed): its loads and
 // stores alone take 125 us (the practical HBM rate for this read/write mix), its arithmetic alone 89 us of VALU time
 // per SIMD -- and together 165 us, because the rate sums start with two DEPENDENT loads per tile (bin index, then the
 // bin's rates) that are issued after the previous tile's eleven stores: the in-order memory counter makes the wave sit
@@ -376,11 +305,8 @@ __global__ __launch_bounds__(kBlock) void element_stats_stream_kernel(ElementSta
 // order per pair as acc_region_kernel (genic_driver_tools.py:262-271: mu += Y_PRED, var += STD**2 in CSR order).
 // (kPre = 2 since round 3: elements of the element / tile routes overlap one or two 10-kb bins -- 1.3 % of the bench
 //  workload's elements three -- and a third register slot cost more in replayed gathers than the loop costs the few:
-//  142.4 -> 139.9 us, same bits; -DDIG_ES_KPRE=3 restores it)
-#ifndef DIG_ES_KPRE
-#define DIG_ES_KPRE 2
-#endif
-constexpr int kPre = DIG_ES_KPRE;
+//  142.4 -> 139.9 us, same bits)
+constexpr int kPre = 2;
 
 struct StagePtr {            // tile t+2
     int64_t q0, q1;
@@ -416,9 +342,6 @@ struct StageBin {            // tile t+1
 // kQueueCap parked pairs in one workgroup: 6 % of its pairs) overflows into the workgroup's OWN segment of the global
 // worklist (pair indices only), which the same workgroup works off after its queue in the manner of the compacted kernel
 // -- it reads back what its own waves wrote, through its own L1: no other workgroup is involved.  No kernel follows.
-#ifndef DIG_ES_INWAVE
-#define DIG_ES_INWAVE 1
-#endif
 constexpr int kQueueCap = 1024;        // records per workgroup
 constexpr int kRecDoubles = 11;        // [0..2] p-value slots, [3..5] counts, [6] alpha, [7] p, [8] [9] the indel pair, [10] pair index
 __shared__ double g_queue[kQueueCap * kRecDoubles];
@@ -435,54 +358,33 @@ __device__ __forceinline__ void slow_round(const ElementStatsArgs& a, const unsi
                                            unsigned count, bool have_first, unsigned first_item, double (*sp_all)[10],
                                            unsigned* list, int64_t n);
 
-#ifdef DIG_ES_TIMING
-// developer build: first / last clock (100 MHz) of every workgroup of the stream pass (tools/es_balance_probe.py)
-__device__ unsigned long long g_es_t0[1024], g_es_t1[1024], g_es_b0[1024], g_es_b1[1024], g_es_q[1024];
-#endif
-#ifndef DIG_ES_XCD
-#define DIG_ES_XCD 1
-#endif
-#ifndef DIG_ES_CONTIG
-#define DIG_ES_CONTIG 0
-#endif
-#ifndef DIG_ES_ABL
-#define DIG_ES_ABL 0     // developer ablation builds (tools/build_variant.sh): 1 no stores, 2 counts forced to 0, 8 no arithmetic, 16 no bin gathers,
-                         // 32 no CSR / index loads, 64 no stores of the four rate outputs, 128 no stores of the seven planes
-#endif
 // GIVEN = 0: dig_element_pipeline (the rate sums of a pair are formed here from the bin tables and written out); 3: the same
 // from the packed bin records of dig_bin_records_pack (two gathers per bin instead of four);
 // GIVEN = 1 / 2: dig_element_stats (mu / sigma handed in per pair; 2: separate indel parameters) -- the same pipeline,
 // tickets and in-kernel second pass without the CSR and bin stages.
+// (TB and TICKETS stay in the parameter list so that the kernel keeps its name: one 1024-thread workgroup with tickets
+//  is the only form)
 template <int TB, bool TICKETS, int GIVEN = 0, bool REC = false>
 __global__ __launch_bounds__(TB) void element_stats_stream_fused_kernel(ElementStatsArgs a)
 {
-    static_assert(!REC || (TB == 1024 && TICKETS && (GIVEN == 0 || GIVEN == 3)), "record outputs: the pipeline's kernel only");
+    static_assert(TB == 1024 && TICKETS, "one 1024-thread workgroup per CU drawing tile tickets");
+    static_assert(!REC || GIVEN == 0 || GIVEN == 3, "record outputs: the pipeline's kernel only");
     double* const queue = g_queue;
     unsigned* const tests = g_tests;
     constexpr int QCAP = kQueueCap;
-#ifdef DIG_ES_TIMING
-    if (threadIdx.x == 0) g_es_t0[blockIdx.x & 1023] = wall_clock64();
-#endif
     constexpr bool FUSED = GIVEN == 0 || GIVEN == 3;      // rate sums formed here (3: from the packed bin records)
     constexpr bool PACKED = GIVEN == 3;
     __shared__ unsigned park_all[TB / 64][kParkCap];
     __shared__ unsigned s_ticket;
-    if (TICKETS && threadIdx.x == 0) s_ticket = 0;
-#if DIG_ES_INWAVE
-    if (TB == 1024 && TICKETS && threadIdx.x == 0) g_queue_len = g_ovf_len = g_ovf_next = g_n_tests = g_next_test = 0;
-#endif
+    if (threadIdx.x == 0) s_ticket = 0;
+    if (threadIdx.x == 0) g_queue_len = g_ovf_len = g_ovf_next = g_n_tests = g_next_test = 0;
     nb_tables_init();
     unsigned* park = park_all[threadIdx.x >> 6];
     const int64_t n = a.E * a.C;
     const int lane = threadIdx.x & 63;
     const unsigned long long lanes_below = (1ull << lane) - 1ull;
     const int64_t n_tiles = (n + 63) >> 6;
-    const int64_t n_waves = ((int64_t)gridDim.x * TB) >> 6;
     int64_t tile = ((int64_t)blockIdx.x * TB + threadIdx.x) >> 6;
-    if (!TICKETS && tile >= n_tiles) return;
-    const int64_t step_pairs = n_waves * 64;
-    const int64_t step_e = a.use_fastdiv ? fastdiv(step_pairs, a.divC) : step_pairs;
-    const uint32_t step_c = (uint32_t)(step_pairs - step_e * a.C);
     const uint32_t C32 = (uint32_t)a.C;
     int64_t iu = tile * 64 + lane;                    // unclamped flat index of the pair the pointer stage fetches next
     int64_t eu = a.use_fastdiv ? fastdiv(iu, a.divC) : iu;
@@ -491,52 +393,29 @@ __global__ __launch_bounds__(TB) void element_stats_stream_fused_kernel(ElementS
         unsigned t = 0;
         if (lane == 0) t = atomicAdd(&s_ticket, 1u);
         t = (unsigned)__builtin_amdgcn_readfirstlane((int)t);
-#if DIG_ES_CONTIG      // developer A/B: every workgroup walks ONE contiguous range of tiles
-        {
-            const int64_t lo = n_tiles * blockIdx.x / gridDim.x, hi = n_tiles * (blockIdx.x + 1) / gridDim.x;
-            return lo + t < hi ? lo + t : n_tiles;
-        }
-#endif
-#if DIG_ES_XCD
         // Workgroups are dealt round-robin to the 8 XCDs (blockIdx % 8 labels the group that shares an L2).  A tile is 64
         // pairs = 1.7 elements at 37 cohorts, so neighbouring tiles read the same bin rows: the 8 groups take runs of
         // gridDim / 8 consecutive tiles instead of every 8th tile (the grid still sweeps the arrays as one window).
         if ((gridDim.x & 7u) == 0u) return ((int64_t)t * 8 + (blockIdx.x & 7u)) * (gridDim.x >> 3) + (blockIdx.x >> 3);
-#endif
         return (int64_t)t * gridDim.x + blockIdx.x;
     };
-    int64_t tile_ptr = 0;                             // TICKETS: tile the last pointer fetch was for
+    int64_t tile_ptr = 0;                             // tile the last pointer fetch was for
     auto fetch_ptr = [&]() {                          // lanes (and whole tiles) past the end replay the last pair
         StagePtr s;
-        if (TICKETS) {
-            tile_ptr = draw();
-            iu = tile_ptr * 64 + lane;
-            eu = a.use_fastdiv ? fastdiv(min(iu, n - 1), a.divC) : iu;
-            cu = (uint32_t)(min(iu, n - 1) - eu * a.C);
-        }
+        tile_ptr = draw();
+        iu = tile_ptr * 64 + lane;
+        eu = a.use_fastdiv ? fastdiv(min(iu, n - 1), a.divC) : iu;
+        cu = (uint32_t)(min(iu, n - 1) - eu * a.C);
         const bool past = iu >= n;
-        s.ok = TICKETS ? (uint32_t)(tile_ptr < n_tiles) : 1u;
+        s.ok = (uint32_t)(tile_ptr < n_tiles);
         s.i = (uint32_t)(past ? n - 1 : iu);
         s.e = (uint32_t)(past ? a.E - 1 : eu);
         s.c = past ? C32 - 1 : cu;
-#if DIG_ES_ABL & 32
-        s.q0 = s.q1 = 0;
-#else
         if (FUSED) {
             s.q0 = a.ov_ptr[s.e];
             s.q1 = a.ov_ptr[s.e + 1];
         } else
             s.q0 = s.q1 = 0;
-#endif
-        if (!TICKETS) {
-            iu += step_pairs;
-            eu += step_e;
-            cu += step_c;
-            if (cu >= C32) {
-                cu -= C32;
-                eu += 1;
-            }
-        }
         return s;
     };
     // every element's CSR range lies inside [0, nnz); with an empty CSR the index loads replay ov_ptr[0] (= 0: row 0)
@@ -552,11 +431,7 @@ __global__ __launch_bounds__(TB) void element_stats_stream_fused_kernel(ElementS
         if (FUSED) {
 #pragma unroll
             for (int j = 0; j < kPre; ++j)      // unconditional (the memory counter stays exact): bins past the pair's last replay a valid entry
-#if DIG_ES_ABL & 32
-                r.idx[j] = (int)(s.e & 1023u);
-#else
                 r.idx[j] = oi_base[min(s.q0 + j, oi_last)];
-#endif
         } else {
             r.mu = a.mu[s.i];
             r.sg = a.sigma[s.i];
@@ -579,10 +454,6 @@ __global__ __launch_bounds__(TB) void element_stats_stream_fused_kernel(ElementS
     auto fetch_bin = [&](const StageIn& r) {
         StageBin b;
         if (!FUSED) return b;
-#if DIG_ES_ABL & 16
-        for (int j = 0; j < kPre; ++j) { b.mu[j] = 1.0 + r.c; b.sd[j] = 0.5; b.y[j] = 1; b.fl[j] = 0; }
-        return b;
-#endif
 #pragma unroll
         for (int j = 0; j < kPre; ++j) {
             const int64_t o = a.small_index ? (int64_t)(__umul24((uint32_t)r.idx[j], C32) + r.c)
@@ -604,33 +475,31 @@ __global__ __launch_bounds__(TB) void element_stats_stream_fused_kernel(ElementS
         return b;
     };
     // pipeline fill: pointers of the first two tiles, inputs and bin rates of the first
-    if (TICKETS) __syncthreads();        // the counter is zero
+    __syncthreads();                     // the counter is zero
     StagePtr ptr_n = fetch_ptr();
-    if (TICKETS) tile = tile_ptr;        // tickets come out in ascending order: the wave's tiles are tile, tile_n1, tile_ptr
+    tile = tile_ptr;                     // tickets come out in ascending order: the wave's tiles are tile, tile_n1, tile_ptr
     StageIn in_c = fetch_in(ptr_n);
     ptr_n = fetch_ptr();
     int64_t tile_n1 = tile_ptr;
     StageBin bin_c = fetch_bin(in_c);
     unsigned parked = 0;   // wave-uniform
-    // the wave's parked pair indices leave LDS for the global worklist; the in-kernel form keeps one segment per workgroup
+    // the wave's parked pair indices leave LDS for the global worklist, which keeps one segment per workgroup
     // (ceil(tiles per workgroup) x 64 entries: it cannot overflow)
-    const bool own_segment = DIG_ES_INWAVE && TB == 1024 && TICKETS;
-    unsigned* segment = a.worklist + kWorkHeader + (own_segment ? (int64_t)blockIdx.x * (((n_tiles + gridDim.x - 1) / gridDim.x) << 6) : 0);
+    unsigned* segment = a.worklist + kWorkHeader + (int64_t)blockIdx.x * (((n_tiles + gridDim.x - 1) / gridDim.x) << 6);
     auto flush = [&](unsigned count) -> unsigned {
-        if (!own_segment) return park_flush(a.worklist, park, count, lane);
         unsigned base = 0;
         if (lane == 0) base = atomicAdd(&g_ovf_len, count);
         base = (unsigned)__builtin_amdgcn_readfirstlane((int)base);
         for (unsigned j = lane; j < count; j += 64) segment[base + j] = park[j];
         return 0;
     };
-    for (; tile < n_tiles; tile = TICKETS ? tile_n1 : tile + n_waves) {
+    for (; tile < n_tiles; tile = tile_n1) {
         if (parked > (unsigned)(kParkCap - 64)) parked = flush(parked);
         const bool live = tile * 64 + lane < n;
         const StageIn cur = in_c;
         const StageBin bin = bin_c;
         in_c = fetch_in(ptr_n);          // tile t+1: indices + inputs
-        if (TICKETS) tile_n1 = tile_ptr;
+        tile_n1 = tile_ptr;
         ptr_n = fetch_ptr();             // tile t+2: pointers
         const int64_t i = cur.i;
         // rate sums (genic_driver_tools.py:262-271)
@@ -681,23 +550,7 @@ __global__ __launch_bounds__(TB) void element_stats_stream_fused_kernel(ElementS
         }
         w.pi_s = cur.pi_s; w.pi_i = cur.pi_i; w.cj = cur.cj; w.cji = cur.cji;
         w.k_snv = cur.k_snv; w.k_smp = cur.k_smp; w.k_ind = cur.k_ind;
-#if DIG_ES_ABL & 2
-        w.k_snv = w.k_smp = w.k_ind = 0;
-#endif
-#if DIG_ES_ABL & 256                                   // counts capped at 28: what a sorted wave's trip count would cost (timing only)
-#ifndef DIG_ES_CAPK
-#define DIG_ES_CAPK 28
-#endif
-        w.k_snv = min(w.k_snv, DIG_ES_CAPK); w.k_smp = min(w.k_smp, DIG_ES_CAPK);
-#endif
-        w.q0 = w.q1 = 0; w.c = cur.c;
-#if DIG_ES_ABL & 8
-        PairInputs q;
-        q.alpha = q.alpha_i = w.mu; q.p = q.p_i = 0.5; q.exp_snv = w.sigma; q.theta_i = w.pi_s; q.exp_ind = w.pi_i + w.cj + w.cji;
-        q.k_snv = q.k_smp = q.k_ind = 0.0;
-        double pv_snv = (double)w.k_snv, pv_smp = (double)w.k_smp, pv_ind = (double)w.k_ind, pv_mut = 0.25;
-        const bool slow = false;
-#else
+        w.c = cur.c;
         const PairInputs q = prepare_pair(w, GIVEN == 2);
         // (a test the recurrence cannot finish keeps a NEGATIVE value for pass 2: -pmf(k) when the direct form
         //  cancelled, -2 when it was not eligible at all; no p-value is negative)
@@ -707,11 +560,9 @@ __global__ __launch_bounds__(TB) void element_stats_stream_fused_kernel(ElementS
         const bool slow = ((d1 != 3u) || (d2 != 1u)) && live;
         double pv_mut = 0.0;
         if (!slow) pv_mut = fisher_combine_fast(pv_snv, pv_ind);
-#endif
         bin_c = fetch_bin(in_c);         // tile t+1: bin rates (requested BEFORE this tile's stores)
         unsigned long long m = __ballot(slow);
-#if DIG_ES_INWAVE
-        if (TB == 1024 && TICKETS && m) {                   // into the workgroup's queue; what does not fit goes the old way
+        if (m) {                                            // into the workgroup's queue; what does not fit goes the old way
             const unsigned cnt = (unsigned)__popcll(m);
             unsigned qb = 0;
             if (lane == 0) qb = atomicAdd(&g_queue_len, cnt);
@@ -727,29 +578,14 @@ __global__ __launch_bounds__(TB) void element_stats_stream_fused_kernel(ElementS
             }
             m = __ballot(slow && !fits);
         }
-#endif
         if (slow && ((m >> lane) & 1ull)) park[parked + __popcll(m & lanes_below)] = (unsigned)i;
         parked += (unsigned)__popcll(m);
-#if DIG_ES_ABL & 1
-        if (pv_snv + pv_smp + pv_ind + pv_mut + q.exp_snv + q.exp_ind + q.theta_i + w.mu + w.sigma + robs + flag != 12345.678) continue;
-#endif
         if (REC) {
             // tile-blocked records: the tile's block is 5 rows of 64 x 16 bytes; lane l writes its fields (2 j, 2 j + 1) to row j --
             // five store instructions of 1 KB each, one aligned 5 120-byte run per tile, one base address
             const unsigned long long rf = (unsigned long long)(unsigned)robs | ((unsigned long long)(unsigned)flag << 32);
-#if DIG_REC_LAYOUT == 1
-            v2d* g = reinterpret_cast<v2d*>(a.out) + tile * 64 + lane;
-            const int64_t row = ((n + 63) >> 6);              // v2d elements per pair plane / 64
-#define DIG_REC_ROW(j) ((j) * row * 64)
-#else
             v2d* g = reinterpret_cast<v2d*>(a.out + tile * (64 * kRecOut)) + lane;
-#define DIG_REC_ROW(j) ((j) * 64)
-#endif
-#ifdef DIG_REC_PLAIN_STORES                     // developer A/B: write-back stores
-#define DIG_REC_STORE(j, x, y) g[DIG_REC_ROW(j)] = v2d{(x), (y)}
-#else
-#define DIG_REC_STORE(j, x, y) __builtin_nontemporal_store(v2d{(x), (y)}, &g[DIG_REC_ROW(j)])
-#endif
+#define DIG_REC_STORE(j, x, y) __builtin_nontemporal_store(v2d{(x), (y)}, &g[(j) * 64])
             DIG_REC_STORE(0, q.exp_snv, pv_snv);
             DIG_REC_STORE(1, pv_smp, q.theta_i);
             DIG_REC_STORE(2, q.exp_ind, pv_ind);
@@ -757,19 +593,12 @@ __global__ __launch_bounds__(TB) void element_stats_stream_fused_kernel(ElementS
             DIG_REC_STORE(4, w.sigma, __longlong_as_double((long long)rf));
             continue;
         }
-#if !(DIG_ES_ABL & 64)
         if (FUSED) {
             DIG_STREAM_STORE(&a.mu_w[i], w.mu);
             DIG_STREAM_STORE(&a.sigma_w[i], w.sigma);
             DIG_STREAM_STORE(&a.r_obs[i], robs);
             DIG_STREAM_STORE(&a.flag[i], flag);
         }
-#else
-        if (w.mu + w.sigma + robs + flag == 12345.678) DIG_STREAM_STORE(&a.mu_w[i], w.mu);
-#endif
-#if DIG_ES_ABL & 128
-        if (pv_snv + pv_smp + pv_ind + pv_mut + q.exp_snv + q.exp_ind + q.theta_i != 12345.678) continue;
-#endif
         DIG_STREAM_STORE(&a.out[0 * n + i], q.exp_snv);
         DIG_STREAM_STORE(&a.out[1 * n + i], pv_snv);
         DIG_STREAM_STORE(&a.out[2 * n + i], pv_smp);
@@ -779,95 +608,78 @@ __global__ __launch_bounds__(TB) void element_stats_stream_fused_kernel(ElementS
         DIG_STREAM_STORE(&a.out[6 * n + i], pv_mut);
     }
     if (parked) flush(parked);
-#if DIG_ES_INWAVE
-    if (TB == 1024 && TICKETS) {
-#ifdef DIG_ES_TIMING
-        if (lane == 0) {
-            const unsigned long long now = wall_clock64();
-            atomicMin(&g_es_b0[blockIdx.x & 1023], now);
-            atomicMax(&g_es_b1[blockIdx.x & 1023], now);
+    __syncthreads();                                    // every wave of the workgroup is out of tiles: the queue is complete
+    const int total = (int)min(g_queue_len, (unsigned)QCAP);
+    if (threadIdx.x == 0 && total) atomicAdd(&a.worklist[3], (unsigned)total);     // diagnostic: pairs finished here
+    // The queue is taken apart TEST by test, not pair by pair: the workgroups that end last are the ones with the most
+    // records (probe: 14-18 us from the barrier to the end against a median of 8), and with whole pairs dealt to
+    // the waves a wave with sixteen pairs runs three rounds of sixteen quads while its neighbours run two.
+    // (a) one thread per record lists the record's open tests; (b) the waves draw sixteen tests at a time, one quad
+    // each, and put the p-value back into the record; (c) one thread per record combines and writes the four planes.
+    if (total) {
+        const int rec = (int)threadIdx.x;               // TB == kQueueCap
+        double* r = queue + (rec < QCAP ? rec : 0) * kRecDoubles;
+        unsigned open = 0;
+        if (rec < total)
+            open = (__double_as_longlong(r[0]) < 0 ? 1u : 0u) | (__double_as_longlong(r[1]) < 0 ? 2u : 0u) |
+                   (__double_as_longlong(r[2]) < 0 ? 4u : 0u);
+        const unsigned long long b0 = __ballot(open & 1u), b1 = __ballot(open & 2u), b2 = __ballot(open & 4u);
+        const unsigned c0 = (unsigned)__popcll(b0), c1 = (unsigned)__popcll(b1), c2 = (unsigned)__popcll(b2);
+        unsigned tb = 0;
+        if (lane == 0 && c0 + c1 + c2) tb = atomicAdd(&g_n_tests, c0 + c1 + c2);
+        tb = (unsigned)__builtin_amdgcn_readfirstlane((int)tb);
+        if (open & 1u) tests[tb + (unsigned)__popcll(b0 & lanes_below)] = (unsigned)rec * 4u;
+        if (open & 2u) tests[tb + c0 + (unsigned)__popcll(b1 & lanes_below)] = (unsigned)rec * 4u + 1u;
+        if (open & 4u) tests[tb + c0 + c1 + (unsigned)__popcll(b2 & lanes_below)] = (unsigned)rec * 4u + 2u;
+        __syncthreads();
+        const unsigned n_tests = g_n_tests;
+        const int quad = lane >> 2, sub = lane & 3;
+        for (;;) {
+            unsigned t0 = 0;
+            if (lane == 0) t0 = atomicAdd(&g_next_test, 16u);
+            t0 = (unsigned)__builtin_amdgcn_readfirstlane((int)t0);
+            if (t0 >= n_tests) break;
+            const bool active = t0 + (unsigned)quad < n_tests;
+            const unsigned id = tests[active ? t0 + (unsigned)quad : t0];
+            const int role = (int)(id & 3u);
+            double* sp = queue + (id >> 2) * kRecDoubles;
+            const double marker = sp[role];             // -pmf(k), or -2: pmf(k) not known
+            const double pv = nb_midp_upper_quad(sp[3 + role], sp[role == 2 ? 8 : 6], sp[role == 2 ? 9 : 7],
+                                                 marker == -2.0 ? -1.0 : -marker, sub);
+            if (active && sub == 0) sp[role] = pv;      // (nobody else reads this slot before the barrier)
         }
-#endif
-        __syncthreads();                                    // every wave of the workgroup is out of tiles: the queue is complete
-        const int total = (int)min(g_queue_len, (unsigned)QCAP);
-        if (threadIdx.x == 0 && total) atomicAdd(&a.worklist[3], (unsigned)total);     // diagnostic: pairs finished here
-        // The queue is taken apart TEST by test, not pair by pair: the workgroups that end last are the ones with the most
-        // records (probe: 14-18 us from the barrier to the end against a median of 8), and with whole pairs dealt to
-        // the waves a wave with sixteen pairs runs three rounds of sixteen quads while its neighbours run two.
-        // (a) one thread per record lists the record's open tests; (b) the waves draw sixteen tests at a time, one quad
-        // each, and put the p-value back into the record; (c) one thread per record combines and writes the four planes.
-        if (total) {
-            const int rec = (int)threadIdx.x;               // TB == kQueueCap
-            double* r = queue + (rec < QCAP ? rec : 0) * kRecDoubles;
-            unsigned open = 0;
-            if (rec < total)
-                open = (__double_as_longlong(r[0]) < 0 ? 1u : 0u) | (__double_as_longlong(r[1]) < 0 ? 2u : 0u) |
-                       (__double_as_longlong(r[2]) < 0 ? 4u : 0u);
-            const unsigned long long b0 = __ballot(open & 1u), b1 = __ballot(open & 2u), b2 = __ballot(open & 4u);
-            const unsigned c0 = (unsigned)__popcll(b0), c1 = (unsigned)__popcll(b1), c2 = (unsigned)__popcll(b2);
-            unsigned tb = 0;
-            if (lane == 0 && c0 + c1 + c2) tb = atomicAdd(&g_n_tests, c0 + c1 + c2);
-            tb = (unsigned)__builtin_amdgcn_readfirstlane((int)tb);
-            if (open & 1u) tests[tb + (unsigned)__popcll(b0 & lanes_below)] = (unsigned)rec * 4u;
-            if (open & 2u) tests[tb + c0 + (unsigned)__popcll(b1 & lanes_below)] = (unsigned)rec * 4u + 1u;
-            if (open & 4u) tests[tb + c0 + c1 + (unsigned)__popcll(b2 & lanes_below)] = (unsigned)rec * 4u + 2u;
-            __syncthreads();
-            const unsigned n_tests = g_n_tests;
-#ifdef DIG_ES_TIMING
-            if (threadIdx.x == 0) g_es_q[blockIdx.x & 1023] = (unsigned long long)total | ((unsigned long long)n_tests << 32);
-#endif
-            const int quad = lane >> 2, sub = lane & 3;
-            for (;;) {
-                unsigned t0 = 0;
-                if (lane == 0) t0 = atomicAdd(&g_next_test, 16u);
-                t0 = (unsigned)__builtin_amdgcn_readfirstlane((int)t0);
-                if (t0 >= n_tests) break;
-                const bool active = t0 + (unsigned)quad < n_tests;
-                const unsigned id = tests[active ? t0 + (unsigned)quad : t0];
-                const int role = (int)(id & 3u);
-                double* sp = queue + (id >> 2) * kRecDoubles;
-                const double marker = sp[role];             // -pmf(k), or -2: pmf(k) not known
-                const double pv = nb_midp_upper_quad(sp[3 + role], sp[role == 2 ? 8 : 6], sp[role == 2 ? 9 : 7],
-                                                     marker == -2.0 ? -1.0 : -marker, sub);
-                if (active && sub == 0) sp[role] = pv;      // (nobody else reads this slot before the barrier)
-            }
-            __syncthreads();
-            if (rec < total) {
-                const int64_t item = __double_as_longlong(r[10]);
-                const double pv_snv = r[0], pv_smp = r[1], pv_ind = r[2];
-                if (REC) {
-                    a.out[rec_index(item, 1, n)] = pv_snv;
-                    a.out[rec_index(item, 2, n)] = pv_smp;
-                    a.out[rec_index(item, 5, n)] = pv_ind;
-                    a.out[rec_index(item, 6, n)] = fisher_combine_fast(pv_snv, pv_ind);
-                } else {
-                    a.out[1 * n + item] = pv_snv;
-                    a.out[2 * n + item] = pv_smp;
-                    a.out[5 * n + item] = pv_ind;
-                    a.out[6 * n + item] = fisher_combine_fast(pv_snv, pv_ind);
-                }
-            }
-        }
-        const unsigned ovf = g_ovf_len;                     // (final since the barrier above)
-        if (ovf) {
-            // the pairs the queue had no room for: their indices are in this workgroup's segment, their markers in the
-            // planes -- written by this workgroup's waves, all of which have passed the barrier (vmcnt(0) in front of it)
-            __syncthreads();                                // the queue's LDS is free: 80 doubles per wave of it become the pair buffers
-            if (threadIdx.x == 0) atomicAdd(&a.worklist[2], ovf);
-            double (*sp)[10] = reinterpret_cast<double (*)[10]>(queue + (threadIdx.x >> 6) * (kSlowPairsPerWave * 10));
-            for (;;) {
-                unsigned b = 0;
-                if (lane == 0) b = atomicAdd(&g_ovf_next, (unsigned)kSlowPairsPerWave);
-                b = (unsigned)__builtin_amdgcn_readfirstlane((int)b);
-                if (b >= ovf) break;
-                slow_round(a, segment, b, ovf, false, 0u, sp, g_queue_list[threadIdx.x >> 6], n);
+        __syncthreads();
+        if (rec < total) {
+            const int64_t item = __double_as_longlong(r[10]);
+            const double pv_snv = r[0], pv_smp = r[1], pv_ind = r[2];
+            if (REC) {
+                a.out[rec_index(item, 1, n)] = pv_snv;
+                a.out[rec_index(item, 2, n)] = pv_smp;
+                a.out[rec_index(item, 5, n)] = pv_ind;
+                a.out[rec_index(item, 6, n)] = fisher_combine_fast(pv_snv, pv_ind);
+            } else {
+                a.out[1 * n + item] = pv_snv;
+                a.out[2 * n + item] = pv_smp;
+                a.out[5 * n + item] = pv_ind;
+                a.out[6 * n + item] = fisher_combine_fast(pv_snv, pv_ind);
             }
         }
     }
-#endif
-#ifdef DIG_ES_TIMING
-    if (lane == 0) atomicMax(&g_es_t1[blockIdx.x & 1023], (unsigned long long)wall_clock64());
-#endif
+    const unsigned ovf = g_ovf_len;                     // (final since the barrier above)
+    if (ovf) {
+        // the pairs the queue had no room for: their indices are in this workgroup's segment, their markers in the
+        // planes -- written by this workgroup's waves, all of which have passed the barrier (vmcnt(0) in front of it)
+        __syncthreads();                                // the queue's LDS is free: 80 doubles per wave of it become the pair buffers
+        if (threadIdx.x == 0) atomicAdd(&a.worklist[2], ovf);
+        double (*sp)[10] = reinterpret_cast<double (*)[10]>(queue + (threadIdx.x >> 6) * (kSlowPairsPerWave * 10));
+        for (;;) {
+            unsigned b = 0;
+            if (lane == 0) b = atomicAdd(&g_ovf_next, (unsigned)kSlowPairsPerWave);
+            b = (unsigned)__builtin_amdgcn_readfirstlane((int)b);
+            if (b >= ovf) break;
+            slow_round(a, segment, b, ovf, false, 0u, sp, g_queue_list[threadIdx.x >> 6], n);
+        }
+    }
 }
 
 // Pass 2: the compacted slow pairs.  Pass 1 left every test it could not finish NEGATIVE in its p-value plane (counts
@@ -1078,31 +890,6 @@ using namespace dig;
 
 extern "C" {
 
-#ifdef DIG_ES_TIMING
-int dig_debug_es_timing(unsigned long long* out2048)
-{
-    DIG_HIP_TRY(hipDeviceSynchronize());
-    DIG_HIP_TRY(hipMemcpyFromSymbol(out2048, HIP_SYMBOL(dig::g_es_t0), 1024 * sizeof(unsigned long long)));
-    DIG_HIP_TRY(hipMemcpyFromSymbol(out2048 + 1024, HIP_SYMBOL(dig::g_es_t1), 1024 * sizeof(unsigned long long)));
-    static unsigned long long z[1024] = {};
-    DIG_HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(dig::g_es_t1), z, sizeof(z)));
-    // [2048, 3072): first, [3072, 4096): last arrival of a wave at the workgroup's end-of-tiles barrier
-    DIG_HIP_TRY(hipMemcpyFromSymbol(out2048 + 2048, HIP_SYMBOL(dig::g_es_b0), 1024 * sizeof(unsigned long long)));
-    DIG_HIP_TRY(hipMemcpyFromSymbol(out2048 + 3072, HIP_SYMBOL(dig::g_es_b1), 1024 * sizeof(unsigned long long)));
-    DIG_HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(dig::g_es_b1), z, sizeof(z)));
-    static unsigned long long big[1024];
-    for (auto& v : big) v = ~0ull;
-    DIG_HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(dig::g_es_b0), big, sizeof(big)));
-    return DIG_OK;
-}
-int dig_debug_es_queue(unsigned long long* out1024)      // records | open tests << 32 of every workgroup's queue, last launch
-{
-    DIG_HIP_TRY(hipMemcpyFromSymbol(out1024, HIP_SYMBOL(dig::g_es_q), 1024 * sizeof(unsigned long long)));
-    return DIG_OK;
-}
-#endif
-
-
 int dig_nb_midp_upper(const double* k, const double* alpha, const double* p, double* out, int64_t n, void* stream)
 {
     return launch_nb3<OpMidpUpper>(k, alpha, p, out, n, stream);
@@ -1226,18 +1013,6 @@ struct FusedRates {
     int records;               // DIG_PIPE_RECORDS: `out` holds one record of kRecOut doubles per pair
 };
 
-// DIG_ES_FORM / DIG_ES_BLOCKS_PER_CU are developer knobs for A/B runs (tools/variant_bench.py).
-static int stream_form()      // 1 = three-deep pipelined fused kernel (default), 0 = two-stage form
-{
-    const char* e = getenv("DIG_ES_FORM");
-    return e ? atoi(e) : 1;
-}
-static int stream_blocks_per_cu(int dflt)
-{
-    const char* e = getenv("DIG_ES_BLOCKS_PER_CU");
-    return e ? std::max(1, atoi(e)) : dflt;
-}
-
 int element_stats_launch(const double* mu, const double* sigma, const double* mu_indel, const double* sigma_indel,
                          const double* pi_sum, const double* pi_indel, int pi_indel_per_cohort, const int32_t* obs_snv,
                          const int32_t* obs_samples, const int32_t* obs_indel, const double* cj, const double* cj_indel,
@@ -1256,11 +1031,7 @@ int element_stats_launch(const double* mu, const double* sigma, const double* mu
     const int use_fd = (C >= 2);   // exact: E * C * C < 2^64 for any problem that fits in memory
     ElementStatsArgs a{mu, sigma, mu_indel, sigma_indel, pi_sum, pi_indel, obs_snv, obs_samples, obs_indel,
                        cj, cj_indel, out, E, C, pi_indel_per_cohort, wl, make_fastdiv(C), use_fd,
-                       nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr, 0,
-#ifdef DIG_DEV_ABLATE
-                       , 0
-#endif
-    };
+                       nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr, 0};
     if (fused) {
         a.bin_mu = fused->bin_mu; a.bin_std = fused->bin_std; a.bin_y = fused->bin_y; a.bin_flag = fused->bin_flag;
         a.ov_ptr = fused->ov_ptr; a.ov_idx = fused->ov_idx;
@@ -1269,11 +1040,6 @@ int element_stats_launch(const double* mu, const double* sigma, const double* mu
         a.bin_pack = fused->bin_pack; a.bin_yf = fused->bin_yf;
         a.rec = fused->records;
     }
-#ifdef DIG_DEV_ABLATE
-    a.ablate = getenv("DIG_ABLATE") ? atoi(getenv("DIG_ABLATE")) : 0;
-#endif
-    DIG_REQUIRE(!a.rec || (wl && stream_form() == 1 && (!getenv("DIG_ES_TICKETS") || atoi(getenv("DIG_ES_TICKETS")) == 1024)),
-                "DIG_PIPE_RECORDS: only the default form of the statistics kernel writes records");
     if (wl && !worklist_already_zero) DIG_HIP_TRY(hipMemsetAsync(wl, 0, sizeof(unsigned) * kWorkHeader, s));
     bool finished_in_wave = false;
     const int64_t want_blocks = (E * C + kBlock - 1) / kBlock;
@@ -1283,7 +1049,7 @@ int element_stats_launch(const double* mu, const double* sigma, const double* mu
         // Persistent grids: as many workgroups as are resident at once.  The occupancy figures are cached per (device,
         // kernel form): a process may drive several GPUs.
         const int which = fused ? 2 : (mu_indel ? 1 : 0);
-        static int resident[kMaxDevices][4] = {};
+        static int resident[kMaxDevices][2] = {};
         int dev_id = 0;
         DIG_HIP_TRY(hipGetDevice(&dev_id));
         DIG_REQUIRE(dev_id >= 0 && dev_id < kMaxDevices, "device index below 64");
@@ -1296,7 +1062,6 @@ int element_stats_launch(const double* mu, const double* sigma, const double* mu
             }
             return r;
         };
-        static const int form = stream_form(), tickets = getenv("DIG_ES_TICKETS") ? atoi(getenv("DIG_ES_TICKETS")) : 1024;
         static const int given_form = getenv("DIG_ES_GIVEN_FORM") ? atoi(getenv("DIG_ES_GIVEN_FORM")) : 1;
         // the pipelined kernel (one 1024-thread workgroup per CU, tile tickets; it finishes its own parked pairs)
         auto launch_fused = [&](auto kernel) -> int {
@@ -1304,28 +1069,19 @@ int element_stats_launch(const double* mu, const double* sigma, const double* mu
             DIG_LAUNCH_STAGE(DIG_PIPE_STATISTICS, kernel, dim3(grid_for(E * C, 1024, 1)), dim3(1024), 0, s, a);
             return DIG_OK;
         };
-        if (which == 2 && form == 1 && tickets == 1024) {
-            // one 1024-thread workgroup per CU drawing tiles from an LDS counter (default)
+        if (which == 2) {
+            // one 1024-thread workgroup per CU drawing tiles from an LDS counter
             int rc;
             if (a.rec) {
-                DIG_REQUIRE(a.bin_pack && DIG_ES_INWAVE, "DIG_PIPE_RECORDS needs the packed bin records (dig_bin_records_pack)");
+                DIG_REQUIRE(a.bin_pack, "DIG_PIPE_RECORDS needs the packed bin records (dig_bin_records_pack)");
                 rc = launch_fused(element_stats_stream_fused_kernel<1024, true, 3, true>);
             } else if (a.bin_pack)
                 rc = launch_fused(element_stats_stream_fused_kernel<1024, true, 3>);
             else
                 rc = launch_fused(element_stats_stream_fused_kernel<1024, true>);
             if (rc) return rc;
-            finished_in_wave = DIG_ES_INWAVE != 0;
-        } else if (which == 2 && form == 1 && tickets == 256) {
-            const int g = grid_for(E * C, 256, std::min(occupancy(3, element_stats_stream_fused_kernel<256, true>, 256), stream_blocks_per_cu(8)));
-            hipLaunchKernelGGL((element_stats_stream_fused_kernel<256, true>), dim3(g), dim3(256), 0, s, a);
-        } else if (which == 2 && form == 1) {
-            const int g = grid_for(E * C, 256, std::min(occupancy(3, element_stats_stream_fused_kernel<256, false>, 256), stream_blocks_per_cu(8)));
-            hipLaunchKernelGGL((element_stats_stream_fused_kernel<256, false>), dim3(g), dim3(256), 0, s, a);
-        } else if (which == 2) {
-            const int g = grid_for(E * C, kBlock, std::min(occupancy(2, element_stats_stream_kernel<false, true>, kBlock), 5));
-            hipLaunchKernelGGL((element_stats_stream_kernel<false, true>), dim3(g), dim3(kBlock), 0, s, a);
-        } else if (which != 2 && DIG_ES_INWAVE && given_form) {
+            finished_in_wave = true;
+        } else if (given_form) {
             // dig_element_stats on the pipelined kernel of dig_element_pipeline (one 1024-thread workgroup per CU, tickets,
             // second pass inside): DIG_ES_GIVEN_FORM=0 keeps round 1's two-stage kernels + the compacted kernel
             const int rc = which == 1 ? launch_fused(element_stats_stream_fused_kernel<1024, true, 2>)

@@ -98,13 +98,8 @@ __global__ __launch_bounds__(256) void records_unpack_kernel(const double* __res
             o = c * E + e;
         }
         // field f of pair i: block i / 64 (5 rows x 64 lanes x 2 doubles), row f / 2, lane i % 64, half f % 2
-#if defined(DIG_REC_LAYOUT) && DIG_REC_LAYOUT == 1
-        const int64_t plane2 = ((n + 63) >> 6) << 7;
-        auto field = [&](int f) { return rec[(int64_t)(f >> 1) * plane2 + (i << 1) + (f & 1)]; };
-#else
         const double* blk = rec + (i >> 6) * (64 * DIG_REC_DOUBLES) + ((i & 63) << 1);
         auto field = [&](int f) { return blk[((f >> 1) << 7) + (f & 1)]; };
-#endif
         if (out7)
 #pragma unroll
             for (int pl = 0; pl < DIG_ES_NPLANES; ++pl) out7[(int64_t)pl * n + o] = field(pl);

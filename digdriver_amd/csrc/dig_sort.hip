@@ -76,10 +76,7 @@ constexpr int kRangeElems = kRangeTiles * kSortTile;
 // on average with random digits (128 B of keys, 64 B of payloads: the passes over the mantissa's digits are bound by how the
 // memory system takes these runs -- with runs of eight they took 2.4 ms, the passes over the concentrated upper digits 1.3 ms,
 // whatever the occupancy); a range stays 65 536 elements (the histogram and scan kernels do not change)
-#ifndef DIG_SORT_SCAT_WAVES
-#define DIG_SORT_SCAT_WAVES 16
-#endif
-constexpr int kScatWaves = DIG_SORT_SCAT_WAVES, kScatBlock = kScatWaves * 64, kScatTile = kScatBlock * kSortItems;
+constexpr int kScatWaves = 16, kScatBlock = kScatWaves * 64, kScatTile = kScatBlock * kSortItems;
 static_assert(kRangeElems % kScatTile == 0 && kScatBlock >= kSortBins, "whole scatter tiles per range; a thread per digit");
 
 // a barrier that orders LDS only: __syncthreads() also waits for every global load and store of the wave (its fence covers global

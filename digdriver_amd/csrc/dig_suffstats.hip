@@ -135,14 +135,9 @@ struct ChunkTable {
     int n;
 };
 
-#ifndef DIG_SS_NT
-#define DIG_SS_NT 1     // the background kernel's 85 MB stream is read past the caches (non-temporal loads): it evicted bin records the
-#endif                  // statistics kernel re-reads -- step 0.1852 -> 0.1836 ms (records), 0.1969 -> 0.1927 (planes), same box, two runs each
-#if DIG_SS_NT
+// the background kernel's 85 MB stream is read past the caches (non-temporal loads): it evicted bin records the
+// statistics kernel re-reads -- step 0.1852 -> 0.1836 ms (records), 0.1969 -> 0.1927 (planes), same box, two runs each
 #define DIG_SS_LOAD(p) __builtin_nontemporal_load(p)
-#else
-#define DIG_SS_LOAD(p) (*(p))
-#endif
 __global__ __launch_bounds__(kSsBlock) void suffstats_chunk_stage1(const double* __restrict__ bin_mu,
                                                                    const uint8_t* __restrict__ bin_flag, int64_t C,
                                                                    int64_t rows_per_block, ChunkTable tab,

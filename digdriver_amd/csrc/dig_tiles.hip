@@ -237,9 +237,7 @@ typedef double tile_double4 __attribute__((ext_vector_type(4)));
 constexpr int kTmStride = 272;                 // 16-bit counters per histogram row (256 tiles + 16 of padding)
 constexpr int kTmStride32 = kTmStride / 2;
 constexpr int kTmChunk = 48;                   // cohorts per launch
-#ifndef DIG_TM_OCC
-#define DIG_TM_OCC 2                           // workgroups per CU (register budget 256)
-#endif
+constexpr int kTmOcc = 2;                      // workgroups per CU (register budget 256)
 
 // One packed word of a tile's walk: contexts centred on nibbles centre0 .. centre0 + 7 (centre0 = 8 word - 1).  GUARD: the
 // word holds a non-ACGT base or straddles the tile's ends -- the centres that count are one 8-bit mask (inside [lo, hi), no
@@ -314,13 +312,6 @@ __device__ __forceinline__ unsigned tile_base_global(const uint32_t* __restrict_
     return (words[w < n_words ? w : n_words - 1] >> (4 * (int)(g & 7))) & 15u;
 }
 
-#ifdef DIG_TM_TIMING                            // developer build: cycles per phase (wave 0 of every workgroup), tools/tile_variant_bench.py
-__device__ unsigned long long g_tm_prof[8];
-#define TM_MARK(k) do { if (tid == 0) { const unsigned long long now_ = __builtin_readcyclecounter(); tm_acc[k] += now_ - tm_last; tm_last = now_; } } while (0)
-#else
-#define TM_MARK(k) do {} while (0)
-#endif
-
 // MT full 16-cohort tiles (v_mfma_f64_16x16x4), then NQ quads of four cohorts (v_mfma_f64_4x4x4: its four 4x4 blocks take the
 // SAME four cohort rows against four different groups of four tiles, so the B operand is the register of the 16-row form and a
 // quad costs a quarter of a tile): 37 cohorts = 2 tiles + 2 quads pay for 2.5 tiles' worth of matrix time where three tiles
@@ -328,7 +319,7 @@ __device__ unsigned long long g_tm_prof[8];
 // do not depend on the other cohorts of the call.  (A single cohort on the vector ALU -- sixteen FMAs per sixteen tiles --
 // was 1 % faster still but rounds differently: not kept.)
 template <int MT, int NQ = 0>
-__global__ __launch_bounds__(kTileBlock, DIG_TM_OCC) void base_tile_probs_mfma_kernel(
+__global__ __launch_bounds__(kTileBlock, kTmOcc) void base_tile_probs_mfma_kernel(
     const uint32_t* __restrict__ words, int64_t n_words, const int64_t* __restrict__ chrom_off,
     const int64_t* __restrict__ chrom_len, const int32_t* __restrict__ reg_chrom, const int64_t* __restrict__ reg_start,
     const int64_t* __restrict__ reg_end, int64_t R, const double* __restrict__ s_prob, int64_t C, int c0, int binsize, int n_tiles,
@@ -365,9 +356,6 @@ __global__ __launch_bounds__(kTileBlock, DIG_TM_OCC) void base_tile_probs_mfma_k
     __builtin_amdgcn_s_waitcnt(0x0f70);        // vmcnt(0): the A registers are in -- otherwise their first use inside the loop
                                                // waits on the counter, i.e. also for the stores of the previous region
 
-#ifdef DIG_TM_TIMING
-    unsigned long long tm_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tm_last = __builtin_readcyclecounter();
-#endif
     for (int64_t r = blockIdx.x; r < R; r += gridDim.x) {
         const TileRegion reg = tile_region(chrom_off, chrom_len, reg_chrom[r], reg_start[r], reg_end[r]);
         const int64_t tiles_valid = (reg.n_pos + binsize - 1) / binsize;
@@ -388,14 +376,10 @@ __global__ __launch_bounds__(kTileBlock, DIG_TM_OCC) void base_tile_probs_mfma_k
             const int nw = (int)(((ga + n_cov + 1) >> 3) + 1 - w0 + 1);
             stage_words<256>(s_words, words, n_words, w0, nw, tid);
         }
-        TM_MARK(0);
         __syncthreads();
-        TM_MARK(1);
         // ---- per-tile context histograms ----
         tile_histograms(s_words, s_hist32, tid, nv, binsize, n_cov, (int)(ga - g_lds0) + 1);
-        TM_MARK(2);
         __syncthreads();
-        TM_MARK(3);
         // ---- H[ctx] = sum over the tiles: lane = (row of the wave's sixteen, quarter of the row) ----
         {
             const int x = 16 * wave + li;
@@ -429,9 +413,7 @@ __global__ __launch_bounds__(kTileBlock, DIG_TM_OCC) void base_tile_probs_mfma_k
                 }
             }
         }
-        TM_MARK(4);
         __syncthreads();
-        TM_MARK(5);
         // ---- 1 / T[c] (every wave for itself: no exchange), moved into the lane layout of D once per region ----
         double rt[MTA][4], rtq[NQA];
         {
@@ -506,14 +488,8 @@ __global__ __launch_bounds__(kTileBlock, DIG_TM_OCC) void base_tile_probs_mfma_k
                 }
             }
         }
-        TM_MARK(6);
         __syncthreads();
-        TM_MARK(7);
     }
-#ifdef DIG_TM_TIMING
-    if (tid == 0)
-        for (int k = 0; k < 8; ++k) atomicAdd(&g_tm_prof[k], tm_acc[k]);
-#endif
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -681,12 +657,6 @@ __global__ __launch_bounds__(kTsBlock, 1) void base_tile_probs_roles_kernel(
     }
     __syncthreads();
 
-#ifdef DIG_TM_TIMING                            // walker leader: 0 loads issued | 1 zero | 2 walk | 3 sums | 4 words + description | 5 barrier;
-    unsigned long long tm_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tm_last = __builtin_readcyclecounter();      // multiplier leader: 6 product | 7 barrier
-#define TS_MARK(k) do { if (lane == 0 && (wave == 0 || wave == 4)) { const unsigned long long now_ = __builtin_readcyclecounter(); tm_acc[k] += now_ - tm_last; tm_last = now_; } } while (0)
-#else
-#define TS_MARK(k) do {} while (0)
-#endif
     for (int64_t i = 0; i <= n_my; ++i) {
         const int b = (int)(i & 1);
         if (walker) {
@@ -719,19 +689,16 @@ __global__ __launch_bounds__(kTsBlock, 1) void base_tile_probs_roles_kernel(
                     s_nv[b] = nv;
                 }
                 uint32_t* hist = s_hist32[b];
-                TS_MARK(0);
                 {   // zero the columns of this wave's tiles (32 dwords of every row): eight rows per 16-byte store
                     uint4* z = reinterpret_cast<uint4*>(hist + 32 * hw + 4 * (lane & 7)) ;
 #pragma unroll
                     for (int k = 0; k < 8; ++k) z[((lane >> 3) + 8 * k) * (kTmStride32 / 4)] = make_uint4(0u, 0u, 0u, 0u);
                 }
                 __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                TS_MARK(1);
                 const int64_t ga = reg.g0 - 1;
                 const int64_t g_lds0 = (((ga >> 3) + 1) - 1) << 3;
                 tile_histograms(s_words[b], hist, ht, nv, binsize, n_cov, (int)(ga - g_lds0) + 1);
                 __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-                TS_MARK(2);
                 {   // this wave's share of H: lane = histogram row
                     const uint4* rowp = reinterpret_cast<const uint4*>(hist + lane * kTmStride32 + 32 * hw);
                     unsigned sum = 0;                                   // two 16-bit sums side by side
@@ -751,7 +718,6 @@ __global__ __launch_bounds__(kTsBlock, 1) void base_tile_probs_roles_kernel(
                         if (!((a | bb | c) & 12u)) atomicAdd(&s_Hp[b][a + 4 * bb + 16 * c][hw], 1u);
                     }
                 }
-                TS_MARK(3);
                 // the next region's words (the buffer was last read in iteration i - 1)
 #pragma unroll
                 for (int j = 0; j < kTsPer; ++j) {
@@ -763,7 +729,6 @@ __global__ __launch_bounds__(kTsBlock, 1) void base_tile_probs_roles_kernel(
                 raw_chrom = ch3;
                 raw_start = st3;
                 raw_end = en3;
-                TS_MARK(4);
             }
         } else if (i > 0) {
             const int bp = b ^ 1;
@@ -823,16 +788,9 @@ __global__ __launch_bounds__(kTsBlock, 1) void base_tile_probs_roles_kernel(
                 if constexpr (P > 3)
                     if (part == 3) ts_group<MT, NQ, 8u>(A, Aq, hp, o, t < n_tiles, t < nv, rt, rtq, c0, C, lk, cohort_stride);
             }
-            TS_MARK(6);
         }
         __syncthreads();
-        if (walker) TS_MARK(5);
-        else TS_MARK(7);
     }
-#ifdef DIG_TM_TIMING
-    if (lane == 0 && (wave == 0 || wave == 4))
-        for (int k = 0; k < 8; ++k) atomicAdd(&g_tm_prof[k], tm_acc[k]);
-#endif
 }
 
 // =======================================================================================
@@ -911,9 +869,6 @@ __global__ __launch_bounds__(kCtxBlock) void base_tile_probs_ctx_kernel(
     __shared__ double s_part[kCtxBlock / 8][kCtxCoh];
     __shared__ double s_T[kCtxWalkers / 64][kCtxCoh];         // region totals: one partial per wave of the reduction
     const int tid = threadIdx.x, c = tid & 7, walker = tid >> 3;
-#ifdef DIG_TM_TIMING
-    unsigned long long tm_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tm_last = __builtin_readcyclecounter();
-#endif
     const double nan = __longlong_as_double(0x7ff8000000000000LL);
     // Every load of a thread is issued before its first LDS write, and a region's words are requested while the region
     // before it is walked; its description (three loads, then two that depend on the chromosome) is read a region earlier
@@ -979,16 +934,13 @@ __global__ __launch_bounds__(kCtxBlock) void base_tile_probs_ctx_kernel(
                 len1 = chrom_len[raw1.chrom];
                 off1 = chrom_off[raw1.chrom];
             }
-            TM_MARK(0);
             __syncthreads();                          // the previous region's walkers are done with s_code / s_sum (and the table is staged)
-            TM_MARK(1);
 #pragma unroll
             for (int j = 0; j < kCtxWordsPer; ++j) {
                 const int64_t i = tid + (int64_t)j * kCtxBlock;
                 if (i < q.nw) s_words[i] = staged[j];
             }
             __syncthreads();
-            TM_MARK(2);
             // ---- context codes: a thread forms the codes of EIGHT consecutive positions from three words and stores them
             // as one 16-byte piece.  The sixteen nibbles from the first window's leftmost base on are squeezed to sixteen
             // 2-bit fields (five mask-and-fold steps), every (2 W)-bit substring of which IS a code; a window that holds a
@@ -1018,7 +970,6 @@ __global__ __launch_bounds__(kCtxBlock) void base_tile_probs_ctx_kernel(
                 }
             }
             __syncthreads();
-            TM_MARK(3);
             if (r1 < R) {                             // the next region's words travel during this region's walk
                 nxt = ctx_region<U>(raw1, len1, off1, binsize);
                 request(nxt, staged);
@@ -1100,9 +1051,7 @@ __global__ __launch_bounds__(kCtxBlock) void base_tile_probs_ctx_kernel(
                 }
             }
             s_part[walker][c] = mine;
-            TM_MARK(4);
             __syncthreads();
-            TM_MARK(5);
             if (tid < kCtxWalkers) {                  // lane (g, c): walkers 8 g .. 8 g + 7, then the eight g's of the wave
                 const int g = tid >> 3;
                 double v = 0.0;
@@ -1114,7 +1063,6 @@ __global__ __launch_bounds__(kCtxBlock) void base_tile_probs_ctx_kernel(
                 if ((tid & 63) < kCtxCoh) s_T[tid >> 6][tid & 63] = v;
             }
             __syncthreads();
-            TM_MARK(6);
             // ---- pt = sum / total: wave w writes cohort w's plane, a lane = a tile (with a thread = a tile for all eight cohorts
             // 200 of the 512 threads wrote and the rest waited at the next barrier) ----
             if (stash || q.too_long) {
@@ -1167,10 +1115,6 @@ __global__ __launch_bounds__(kCtxBlock) void base_tile_probs_ctx_kernel(
             }
         }
     }
-#ifdef DIG_TM_TIMING
-    if (tid == 0)
-        for (int k = 0; k < 8; ++k) atomicAdd(&g_tm_prof[k], tm_acc[k]);
-#endif
 }
 
 __global__ __launch_bounds__(256) void tile_mut_counts_kernel(const int32_t* __restrict__ pair_mut, const int32_t* __restrict__ pair_reg,
@@ -1198,17 +1142,6 @@ using namespace dig;
 
 extern "C" {
 
-#ifdef DIG_TM_TIMING
-int dig_debug_tile_profile(unsigned long long* out8)
-{
-    DIG_HIP_TRY(hipDeviceSynchronize());
-    DIG_HIP_TRY(hipMemcpyFromSymbol(out8, HIP_SYMBOL(g_tm_prof), 8 * sizeof(unsigned long long)));
-    unsigned long long z[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    DIG_HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(g_tm_prof), z, sizeof(z)));
-    return DIG_OK;
-}
-#endif
-
 int dig_base_tile_probs(const uint32_t* genome_words, int64_t n_words, const int64_t* chrom_off, const int64_t* chrom_len,
                         int n_chrom, const int32_t* reg_chrom, const int64_t* reg_start, const int64_t* reg_end, int64_t R,
                         const double* s_prob, int64_t C, int binsize, int64_t n_tiles, double* pt, int64_t* first_pos,
@@ -1221,11 +1154,7 @@ int dig_base_tile_probs(const uint32_t* genome_words, int64_t n_words, const int
                 "non-null pointers");
     DIG_REQUIRE(C == 0 || n_tiles == 0 || (s_prob && pt), "s_prob and pt");
     DIG_REQUIRE(binsize <= (kTileMaxWords - 1) * 8, "binsize at most 12 280 positions");
-    static const bool classic = []() {
-        const char* e = getenv("DIG_TILES_FORM");        // developer switch: "classic" forces the vector-FMA kernel
-        return e && e[0] == 'c';
-    }();
-    const bool mfma = !classic && binsize >= 2 && n_tiles >= 1 && n_tiles <= kTileBlock && C >= 1 &&
+    const bool mfma = binsize >= 2 && n_tiles >= 1 && n_tiles <= kTileBlock && C >= 1 &&
                       n_tiles * binsize <= (int64_t)(kTileMaxWords - 1) * 8;
     if (mfma) {
         // Which matrix kernel: the two-role one for a chunk of two or more cohort tiles (32 cohorts and up: 1.28 -> 1.22 ms at
@@ -1238,15 +1167,13 @@ int dig_base_tile_probs(const uint32_t* genome_words, int64_t n_words, const int
         }();
         for (int64_t c0 = 0; c0 < C; c0 += kTmChunk) {
             // the chunk's cohorts as full tiles + quads: a remainder of 1 .. 4 is one quad, 5 .. 8 two, 9 and more a (padded) tile.
-            // DIG_TILES_CUT=0 (developer switch): whole tiles only.
-            static const bool cut = !(getenv("DIG_TILES_CUT") && getenv("DIG_TILES_CUT")[0] == '0');
             const int rem = (int)(C - c0 < kTmChunk ? C - c0 : kTmChunk);
             int mt = rem >> 4, nq = 0;
             const int r16 = rem & 15;
-            if (!cut || r16 >= 9) mt += r16 > 0;
+            if (r16 >= 9) mt += 1;
             else nq = (r16 + 3) >> 2;
             const bool one_role = forced ? forced == 1 : mt < 2;
-            const int grid = one_role ? grid_for(R * kTileBlock, kTileBlock, DIG_TM_OCC) : grid_for(R * kTsBlock, kTsBlock, 1);
+            const int grid = one_role ? grid_for(R * kTileBlock, kTileBlock, kTmOcc) : grid_for(R * kTsBlock, kTsBlock, 1);
             auto go = [&](auto kern, auto kern_roles) {
                 if (one_role)
                     hipLaunchKernelGGL(kern, dim3(grid), dim3(kTileBlock), 0, (hipStream_t)stream, genome_words, n_words, chrom_off,

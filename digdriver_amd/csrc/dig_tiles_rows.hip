@@ -34,13 +34,6 @@
 
 namespace dig {
 
-#ifdef DIG_TM_TIMING                            // developer build: cycles per phase (first and last wave of every workgroup), tools/penta_bench.py
-__device__ unsigned long long g_rw_prof[8];
-#define RW_MARK(k) do { if (lane == 0 && (wave == 0 || wave == n_waves - 1)) { const unsigned long long now_ = __builtin_readcyclecounter(); rw_acc[k] += now_ - rw_last; rw_last = now_; } } while (0)
-#else
-#define RW_MARK(k) do {} while (0)
-#endif
-
 constexpr int kRwMaxPos = 10240;                       // positions of a region whose bases are staged
 constexpr int kRwEntries = (kRwMaxPos + 7 + 4 + 15) / 16 + 3;       // 16-base entries {bases, flags}; + 2 read past the end (a window = three words), + 1 spare
 constexpr int kRwLds = 163840;                         // bytes of LDS per CU
@@ -137,7 +130,8 @@ __device__ __forceinline__ int rw_slot(int lane, bool permute)
     return q | (lane & 32);
 }
 
-// U: bases on either side; LW: lanes of a walker (cohorts of the pass = 2 LW); TP: positions per trip
+// U: bases on either side; LW: lanes of a walker (cohorts of the pass = 2 LW); TP: positions per trip; PERMUTE: the lane order of
+// rw_slot (always launched with it; the parameter keeps the kernel's name)
 template <int U, int LW, int TP, bool PERMUTE>
 __global__ __launch_bounds__(1024) void base_tile_probs_rows_kernel(
     const uint32_t* __restrict__ words, int64_t n_words, const int64_t* __restrict__ chrom_off,
@@ -241,9 +235,6 @@ __global__ __launch_bounds__(1024) void base_tile_probs_rows_kernel(
     load_raw(blockIdx.x + 2 * G, chrom1, start1, end1);
     __syncthreads();                                    // table and the first region's bases are in LDS
 
-#ifdef DIG_TM_TIMING
-    unsigned long long rw_acc[4] = {0, 0, 0, 0}, rw_last = __builtin_readcyclecounter();
-#endif
     int rk = 0;                                         // regions this workgroup has walked
     for (int64_t r = blockIdx.x; r < R; r += G, ++rk) {
         const RwRegion q = cur;
@@ -307,13 +298,6 @@ __global__ __launch_bounds__(1024) void base_tile_probs_rows_kernel(
                 auto read_row = [&](uint32_t x) {                             // x: the field of a position at the row bits
                     uint32_t off;                                               // (the compiler turns the | of disjoint bits into an add
                     asm("v_and_or_b32 %0, %1, %2, %3" : "=v"(off) : "v"(x), "v"(amask), "v"(abase));       //  and then has no fused form)
-#if defined(DIG_RW_ABL) && DIG_RW_ABL == 1         // timing builds: every walker reads row 0 / paired walkers rows of different parity / of the same parity
-                    off = abase;
-#elif defined(DIG_RW_ABL) && DIG_RW_ABL == 2
-                    off = (off & ~(1u << kRowLog)) | (((unsigned)(slot / LW) & 1u) << kRowLog);
-#elif defined(DIG_RW_ABL) && DIG_RW_ABL == 3
-                    off = off & ~(1u << kRowLog);
-#endif
                     return *reinterpret_cast<const double2*>(reinterpret_cast<const char*>(s_all) + off);
                 };
                 // the row of position i of a trip whose bases sit at bits 63 - 2 j of (hi, lo) (32-bit windows: hi only)
@@ -378,9 +362,7 @@ __global__ __launch_bounds__(1024) void base_tile_probs_rows_kernel(
         };
         if (s_hasn[rk & 1]) walk(std::true_type{});
         else walk(std::false_type{});
-        RW_MARK(0);
         __syncthreads();                                // sums complete; nobody reads the staged bases any more
-        RW_MARK(1);
         // ---- the next region's bases -> LDS; the words of the region after it are requested (they travel during the output
         // phase and the next walk) ----
         cur = nxt;
@@ -395,11 +377,7 @@ __global__ __launch_bounds__(1024) void base_tile_probs_rows_kernel(
         // (a wave takes a cohort: its total by a lane-strided sum and a DPP reduction -- a butterfly of ds_bpermute would be six
         //  dependent LDS round trips --, the quotient as a multiplication by 1 / total, as in the trinucleotide matrix kernels)
         // (a lane's four sums -- tiles lane, lane + 64, ... : the sum buffer holds at most 202 -- are read once, all in flight)
-#if defined(DIG_RW_OUT_ABL) && DIG_RW_OUT_ABL == 2
-        if (false) {
-#else
         if (!q.deferred) {
-#endif
             const bool whole = tiles_valid == (int)n_tiles;     // (the usual case: every tile asked for exists and none beyond)
             for (int co = wave; co < cc; co += n_waves) {
                 double sv[4];
@@ -413,10 +391,6 @@ __global__ __launch_bounds__(1024) void base_tile_probs_rows_kernel(
                 for (int k = 0; k < 4; ++k) part += lane + 64 * k < tiles_valid ? sv[k] : 0.0;
                 const double inv = 1.0 / rw_wave_sum(part);
                 double* plane = pt + ((int64_t)(c0 + co) * R + r) * n_tiles + lane;
-#if defined(DIG_RW_OUT_ABL) && DIG_RW_OUT_ABL == 1         // timing builds: the output phase without its stores / without the whole phase
-                if (sv[0] * inv == 12345.678) plane[0] = inv;
-                continue;
-#endif
                 if (whole) {
 #pragma unroll
                     for (int k = 0; k < 4; ++k)
@@ -431,29 +405,19 @@ __global__ __launch_bounds__(1024) void base_tile_probs_rows_kernel(
                 }
             }
         }
-        RW_MARK(2);
         __syncthreads();                                // the sum buffer is free, the next region's bases are in LDS
-        RW_MARK(3);
     }
-#ifdef DIG_TM_TIMING
-    if (lane == 0 && (wave == 0 || wave == n_waves - 1))
-        for (int k = 0; k < 4; ++k) atomicAdd(&g_rw_prof[k + (wave == 0 ? 0 : 4)], rw_acc[k]);
-#endif
 }
 
 template <int U, int LW, int TP>
-static void launch_rows(bool permute, int grid, int block, hipStream_t stream, const uint32_t* words, int64_t n_words,
+static void launch_rows(int grid, int block, hipStream_t stream, const uint32_t* words, int64_t n_words,
                         const int64_t* chrom_off, const int64_t* chrom_len, const int32_t* reg_chrom, const int64_t* reg_start,
                         const int64_t* reg_end, int64_t R, const double* s_prob, int c0, int cc, int binsize, int64_t n_tiles, double* pt,
                         int64_t* first_pos, int32_t* n_valid, int write_meta)
 {
     const unsigned bin_magic = binsize >= 2 ? (unsigned)(((1ull << 32) + (unsigned)binsize - 1) / (unsigned)binsize) : 0u;
-    if (permute)
-        hipLaunchKernelGGL((base_tile_probs_rows_kernel<U, LW, TP, true>), dim3(grid), dim3(block), 0, stream, words, n_words, chrom_off,
-                           chrom_len, reg_chrom, reg_start, reg_end, R, s_prob, c0, cc, binsize, bin_magic, n_tiles, pt, first_pos, n_valid, write_meta);
-    else
-        hipLaunchKernelGGL((base_tile_probs_rows_kernel<U, LW, TP, false>), dim3(grid), dim3(block), 0, stream, words, n_words, chrom_off,
-                           chrom_len, reg_chrom, reg_start, reg_end, R, s_prob, c0, cc, binsize, bin_magic, n_tiles, pt, first_pos, n_valid, write_meta);
+    hipLaunchKernelGGL((base_tile_probs_rows_kernel<U, LW, TP, true>), dim3(grid), dim3(block), 0, stream, words, n_words, chrom_off,
+                       chrom_len, reg_chrom, reg_start, reg_end, R, s_prob, c0, cc, binsize, bin_magic, n_tiles, pt, first_pos, n_valid, write_meta);
 }
 
 // The passes of one call: sixteen cohorts while more than eight are left, then one pass of eight (4-lane walkers) or four
@@ -463,8 +427,6 @@ int launch_tile_probs_rows(const uint32_t* words, int64_t n_words, const int64_t
                            int64_t C, int n_up, int binsize, int64_t n_tiles, double* pt, int64_t* first_pos, int32_t* n_valid,
                            hipStream_t stream)
 {
-    static const bool permute = !(getenv("DIG_ROWS_PERMUTE") && getenv("DIG_ROWS_PERMUTE")[0] == '0');      // developer switch (A/B)
-    static const int forced_waves = getenv("DIG_ROWS_WAVES") ? atoi(getenv("DIG_ROWS_WAVES")) : 0;
     // positions per trip: the one that wastes the fewest slots of a tile's last trip (ties: the longer trip)
     int tp = 12;
     {
@@ -475,8 +437,6 @@ int launch_tile_probs_rows(const uint32_t* words, int64_t n_words, const int64_t
             if (best < 0 || waste < best) best = waste, tp = cand[k];
         }
     }
-    static const int forced_tp = getenv("DIG_ROWS_TP") ? atoi(getenv("DIG_ROWS_TP")) : 0;      // developer switch (A/B)
-    if (forced_tp == 25 || forced_tp == 12 || forced_tp == 10 || forced_tp == 8) tp = forced_tp;
     const int grid = grid_for(R * 1024, 1024, 1);
     int c0 = 0;
     bool first = true;
@@ -484,26 +444,21 @@ int launch_tile_probs_rows(const uint32_t* words, int64_t n_words, const int64_t
         const int left = (int)(C - c0);
         const int lw = left > 8 ? 8 : (left > 4 ? 4 : 2);
         const int cc = left < 2 * lw ? left : 2 * lw;
-        // waves per workgroup
-        int n_waves = 16;
-        if (forced_waves >= 6 && forced_waves <= 16) {
-            n_waves = forced_waves;
-        } else {
-            n_waves = 16;       // (tiles are dealt by tickets: more waves hide more latency, and a wave = a cohort in the output phase)
-        }
+        // waves per workgroup (tiles are dealt by tickets: more waves hide more latency, and a wave = a cohort in the output phase)
+        const int n_waves = 16;
         auto go = [&](auto u_c, auto lw_c) {
             constexpr int UU = decltype(u_c)::value, LL = decltype(lw_c)::value;
             if (tp == 25)
-                launch_rows<UU, LL, 25>(permute, grid, 64 * n_waves, stream, words, n_words, chrom_off, chrom_len, reg_chrom, reg_start, reg_end,
+                launch_rows<UU, LL, 25>(grid, 64 * n_waves, stream, words, n_words, chrom_off, chrom_len, reg_chrom, reg_start, reg_end,
                                         R, s_prob, c0, cc, binsize, n_tiles, pt, first_pos, n_valid, first ? 1 : 0);
             else if (tp == 12)
-                launch_rows<UU, LL, 12>(permute, grid, 64 * n_waves, stream, words, n_words, chrom_off, chrom_len, reg_chrom, reg_start, reg_end,
+                launch_rows<UU, LL, 12>(grid, 64 * n_waves, stream, words, n_words, chrom_off, chrom_len, reg_chrom, reg_start, reg_end,
                                         R, s_prob, c0, cc, binsize, n_tiles, pt, first_pos, n_valid, first ? 1 : 0);
             else if (tp == 10)
-                launch_rows<UU, LL, 10>(permute, grid, 64 * n_waves, stream, words, n_words, chrom_off, chrom_len, reg_chrom, reg_start, reg_end,
+                launch_rows<UU, LL, 10>(grid, 64 * n_waves, stream, words, n_words, chrom_off, chrom_len, reg_chrom, reg_start, reg_end,
                                         R, s_prob, c0, cc, binsize, n_tiles, pt, first_pos, n_valid, first ? 1 : 0);
             else
-                launch_rows<UU, LL, 8>(permute, grid, 64 * n_waves, stream, words, n_words, chrom_off, chrom_len, reg_chrom, reg_start, reg_end,
+                launch_rows<UU, LL, 8>(grid, 64 * n_waves, stream, words, n_words, chrom_off, chrom_len, reg_chrom, reg_start, reg_end,
                                        R, s_prob, c0, cc, binsize, n_tiles, pt, first_pos, n_valid, first ? 1 : 0);
         };
         auto go_u = [&](auto lw_c) {
@@ -523,13 +478,3 @@ int launch_tile_probs_rows(const uint32_t* words, int64_t n_words, const int64_t
 
 }  // namespace dig
 
-#ifdef DIG_TM_TIMING
-extern "C" int dig_debug_rows_profile(unsigned long long* out8)
-{
-    DIG_HIP_TRY(hipDeviceSynchronize());
-    DIG_HIP_TRY(hipMemcpyFromSymbol(out8, HIP_SYMBOL(dig::g_rw_prof), 8 * sizeof(unsigned long long)));
-    unsigned long long z[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    DIG_HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(dig::g_rw_prof), z, sizeof(z)));
-    return DIG_OK;
-}
-#endif
