@@ -1064,71 +1064,6 @@ int dig_accumulate_elements(const double* bin_mu, const double* bin_std, const i
                              workspace_bytes, stream, 1, nullptr, 0, 3);
 }
 
-int dig_accumulate_elements_host(const double* bin_mu, const double* bin_std, const int32_t* bin_y,
-                                 const uint8_t* bin_flag, const int32_t* bin_ctx, const int64_t* ov_ptr,
-                                 const int32_t* ov_idx, const int32_t* L, int n_class, const uint8_t* strand_minus,
-                                 const int32_t* gene_length, const double* d_pr, double* MU, double* SIGMA,
-                                 int32_t* R_OBS, int32_t* FLAG, double* P, int32_t* R_SIZE, int32_t* ELT_SIZE,
-                                 double* P_INDEL, int64_t N, int64_t E, int64_t C, int device)
-{
-    DIG_REQUIRE(N >= 0 && E >= 0 && C >= 0, "N, E, C >= 0");
-    DIG_REQUIRE(n_class == 1 || n_class == 4, "n_class must be 1 (elements) or 4 (genes)");
-    if (E == 0 || C == 0) return DIG_OK;
-    DIG_REQUIRE(bin_mu && bin_std && bin_y && bin_flag && bin_ctx && ov_ptr && ov_idx && L && strand_minus && d_pr,
-                "non-null inputs");
-    DIG_REQUIRE(MU && SIGMA && R_OBS && FLAG && P && R_SIZE && ELT_SIZE && P_INDEL, "non-null outputs");
-    DIG_HIP_TRY(hipSetDevice(device));
-    const int64_t nnz = ov_ptr[E];
-    DIG_REQUIRE(nnz >= 0, "ov_ptr[E] >= 0");
-    for (int64_t q = 0; q < nnz; ++q) DIG_REQUIRE(ov_idx[q] >= 0 && ov_idx[q] < N, "ov_idx within [0, N)");
-    const size_t nNC = (size_t)N * C, nEC = (size_t)E * C;
-    DevBuf d_mu, d_sd, d_y, d_fl, d_ctx, d_ptr, d_idx, d_L, d_st, d_gl, d_dpr;
-    DevBuf o_mu, o_sg, o_ro, o_fl, o_p, o_rs, o_es, o_pi;
-#define UP(buf, src, bytes)                       \
-    DIG_HIP_TRY(buf.alloc(bytes));                \
-    DIG_HIP_TRY(hipMemcpy(buf.p, src, bytes, hipMemcpyHostToDevice))
-    UP(d_mu, bin_mu, nNC * 8);
-    UP(d_sd, bin_std, nNC * 8);
-    UP(d_y, bin_y, nNC * 4);
-    UP(d_fl, bin_flag, nNC);
-    UP(d_ctx, bin_ctx, (size_t)N * 64 * 4);
-    UP(d_ptr, ov_ptr, (size_t)(E + 1) * 8);
-    UP(d_idx, ov_idx, (size_t)nnz * 4);
-    UP(d_L, L, (size_t)E * n_class * 192 * 4);
-    UP(d_st, strand_minus, (size_t)E);
-    if (gene_length) { UP(d_gl, gene_length, (size_t)E * 4); }
-    UP(d_dpr, d_pr, (size_t)C * 192 * 8);
-#undef UP
-    DIG_HIP_TRY(o_mu.alloc(nEC * 8));
-    DIG_HIP_TRY(o_sg.alloc(nEC * 8));
-    DIG_HIP_TRY(o_ro.alloc(nEC * 4));
-    DIG_HIP_TRY(o_fl.alloc(nEC * 4));
-    DIG_HIP_TRY(o_p.alloc(nEC * n_class * 8));
-    DIG_HIP_TRY(o_rs.alloc((size_t)E * 4));
-    DIG_HIP_TRY(o_es.alloc((size_t)E * 4));
-    DIG_HIP_TRY(o_pi.alloc((size_t)E * 8));
-    DevBuf d_ws;
-    const int64_t wsb = dig_accumulate_workspace(E, C);
-    DIG_HIP_TRY(d_ws.alloc((size_t)wsb));
-    int rc = dig_accumulate_elements(d_mu.as<double>(), d_sd.as<double>(), d_y.as<int32_t>(), d_fl.as<uint8_t>(),
-                                     d_ctx.as<int32_t>(), d_ptr.as<int64_t>(), d_idx.as<int32_t>(), d_L.as<int32_t>(),
-                                     n_class, d_st.as<uint8_t>(), gene_length ? d_gl.as<int32_t>() : nullptr,
-                                     d_dpr.as<double>(), o_mu.as<double>(), o_sg.as<double>(), o_ro.as<int32_t>(),
-                                     o_fl.as<int32_t>(), o_p.as<double>(), o_rs.as<int32_t>(), o_es.as<int32_t>(),
-                                     o_pi.as<double>(), N, E, C, d_ws.p, wsb, nullptr);
-    if (rc) return rc;
-    DIG_HIP_TRY(hipDeviceSynchronize());
-    DIG_HIP_TRY(hipMemcpy(MU, o_mu.p, nEC * 8, hipMemcpyDeviceToHost));
-    DIG_HIP_TRY(hipMemcpy(SIGMA, o_sg.p, nEC * 8, hipMemcpyDeviceToHost));
-    DIG_HIP_TRY(hipMemcpy(R_OBS, o_ro.p, nEC * 4, hipMemcpyDeviceToHost));
-    DIG_HIP_TRY(hipMemcpy(FLAG, o_fl.p, nEC * 4, hipMemcpyDeviceToHost));
-    DIG_HIP_TRY(hipMemcpy(P, o_p.p, nEC * n_class * 8, hipMemcpyDeviceToHost));
-    DIG_HIP_TRY(hipMemcpy(R_SIZE, o_rs.p, (size_t)E * 4, hipMemcpyDeviceToHost));
-    DIG_HIP_TRY(hipMemcpy(ELT_SIZE, o_es.p, (size_t)E * 4, hipMemcpyDeviceToHost));
-    DIG_HIP_TRY(hipMemcpy(P_INDEL, o_pi.p, (size_t)E * 8, hipMemcpyDeviceToHost));
-    return DIG_OK;
-}
-
 // Host-side integer index construction (genic_driver_tools.py:275-283).
 int dig_ideal_overlaps_host(const int32_t* elt_chrom, const int64_t* blk_ptr, const int64_t* blk_start,
                             const int64_t* blk_end, int64_t E, int64_t window, const int32_t* bin_chrom,

@@ -30,21 +30,6 @@ int set_error(int code, const char* fmt, ...);
 // number of CUs of the current device (cached per device)
 int cu_count();
 
-// RAII device buffer used only by the *_host twins
-struct DevBuf {
-    void* p = nullptr;
-    ~DevBuf()
-    {
-        if (p) (void)hipFree(p);
-    }
-    hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 1); }
-    template <typename T>
-    T* as()
-    {
-        return static_cast<T*>(p);
-    }
-};
-
 // i / C with a host-computed magic multiplier: e = hi64(i * ceil(2^64 / C)), exact while
 // i * C < 2^64 (the per-pair int64 division the flat [E, C] index would otherwise need costs
 // more than a whole recurrence step).

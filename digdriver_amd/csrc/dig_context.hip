@@ -496,44 +496,6 @@ int dig_count_contexts(const uint32_t* genome_words, int64_t n_words, const int6
     return DIG_OK;
 }
 
-int dig_count_contexts_host(const uint32_t* genome_words, int64_t n_words, const int64_t* chrom_off,
-                            const int64_t* chrom_len, int n_chrom, const int32_t* reg_chrom, const int64_t* reg_start,
-                            const int64_t* reg_end, const uint8_t* reg_minus, int64_t R, int32_t* out, int device)
-{
-    DIG_REQUIRE(R >= 0 && n_words >= 2 && n_chrom >= 0, "R >= 0, n_words >= 2 (pad words), n_chrom >= 0");
-    if (R == 0) return DIG_OK;
-    DIG_REQUIRE(genome_words && chrom_off && chrom_len && reg_chrom && reg_start && reg_end && reg_minus && out,
-                "non-null pointers");
-    for (int64_t r = 0; r < R; ++r) {
-        DIG_REQUIRE(reg_chrom[r] >= 0 && reg_chrom[r] < n_chrom, "region chromosome index within [0, n_chrom)");
-        DIG_REQUIRE(reg_start[r] >= 0 && reg_end[r] >= 0, "non-negative coordinates");
-    }
-    for (int c = 0; c < n_chrom; ++c)
-        DIG_REQUIRE((chrom_off[c] & 7) == 0 && chrom_off[c] + chrom_len[c] <= (n_words - 2) * 8,
-                    "chromosomes word-aligned and inside the genome array");
-    DIG_HIP_TRY(hipSetDevice(device));
-    DevBuf dw, doff, dlen, dc, ds, de, dm, dout;
-#define UP(buf, src, bytes)        \
-    DIG_HIP_TRY(buf.alloc(bytes)); \
-    DIG_HIP_TRY(hipMemcpy(buf.p, src, bytes, hipMemcpyHostToDevice))
-    UP(dw, genome_words, (size_t)n_words * 4);
-    UP(doff, chrom_off, (size_t)std::max(n_chrom, 1) * 8);
-    UP(dlen, chrom_len, (size_t)std::max(n_chrom, 1) * 8);
-    UP(dc, reg_chrom, (size_t)R * 4);
-    UP(ds, reg_start, (size_t)R * 8);
-    UP(de, reg_end, (size_t)R * 8);
-    UP(dm, reg_minus, (size_t)R);
-#undef UP
-    DIG_HIP_TRY(dout.alloc((size_t)R * 64 * 4));
-    int rc = dig_count_contexts(dw.as<uint32_t>(), n_words, doff.as<int64_t>(), dlen.as<int64_t>(), n_chrom,
-                                dc.as<int32_t>(), ds.as<int64_t>(), de.as<int64_t>(), dm.as<uint8_t>(), R,
-                                dout.as<int32_t>(), nullptr);
-    if (rc) return rc;
-    DIG_HIP_TRY(hipDeviceSynchronize());
-    DIG_HIP_TRY(hipMemcpy(out, dout.p, (size_t)R * 64 * 4, hipMemcpyDeviceToHost));
-    return DIG_OK;
-}
-
 int dig_count_contexts2(const uint32_t* words2, int64_t n_words2, const int64_t* nint_start, const int64_t* nint_end, int64_t n_int,
                         const int32_t* nint_bucket, int64_t n_buckets, const int64_t* chrom_off, const int64_t* chrom_len, int n_chrom,
                         const int32_t* reg_chrom, const int64_t* reg_start, const int64_t* reg_end, const uint8_t* reg_minus, int64_t R,
@@ -550,49 +512,5 @@ int dig_count_contexts2(const uint32_t* words2, int64_t n_words2, const int64_t*
     DIG_HIP_TRY(hipGetLastError());
     return DIG_OK;
 }
-
-int dig_count_contexts2_host(const uint32_t* words2, int64_t n_words2, const int64_t* nint_start, const int64_t* nint_end, int64_t n_int,
-                             const int32_t* nint_bucket, int64_t n_buckets, const int64_t* chrom_off, const int64_t* chrom_len,
-                             int n_chrom, const int32_t* reg_chrom, const int64_t* reg_start, const int64_t* reg_end,
-                             const uint8_t* reg_minus, int64_t R, int32_t* out, int device)
-{
-    DIG_REQUIRE(R >= 0 && n_words2 >= 28 && n_chrom >= 0 && n_int >= 0, "R, n_int, n_chrom >= 0, n_words2 >= 28 (pad words)");
-    if (R == 0) return DIG_OK;
-    DIG_REQUIRE(words2 && chrom_off && chrom_len && reg_chrom && reg_start && reg_end && reg_minus && out, "non-null pointers");
-    DIG_REQUIRE(n_int == 0 || (nint_start && nint_end && nint_bucket && n_buckets >= 1), "interval list with its bucket index");
-    for (int64_t r = 0; r < R; ++r) {
-        DIG_REQUIRE(reg_chrom[r] >= 0 && reg_chrom[r] < n_chrom, "region chromosome index within [0, n_chrom)");
-        DIG_REQUIRE(reg_start[r] >= 0 && reg_end[r] >= 0, "non-negative coordinates");
-    }
-    for (int c = 0; c < n_chrom; ++c)
-        DIG_REQUIRE(chrom_off[c] >= 0 && chrom_off[c] + chrom_len[c] + 64 <= (n_words2 - 24) * 16, "chromosomes inside the genome array");
-    for (int64_t j = 0; j < n_int; ++j)
-        DIG_REQUIRE(nint_start[j] < nint_end[j] && (j == 0 || nint_end[j - 1] < nint_start[j]), "intervals sorted, disjoint, not touching");
-    DIG_HIP_TRY(hipSetDevice(device));
-    DevBuf dw, dns, dne, dnb, doff, dlen, dc, ds, de, dm, dout;
-#define UP(buf, src, bytes)        \
-    DIG_HIP_TRY(buf.alloc(bytes)); \
-    if ((bytes) > 0) DIG_HIP_TRY(hipMemcpy(buf.p, src, bytes, hipMemcpyHostToDevice))
-    UP(dw, words2, (size_t)n_words2 * 4);
-    UP(dns, nint_start, (size_t)n_int * 8);
-    UP(dne, nint_end, (size_t)n_int * 8);
-    UP(dnb, nint_bucket, (size_t)(n_int ? n_buckets : 0) * 4);
-    UP(doff, chrom_off, (size_t)std::max(n_chrom, 1) * 8);
-    UP(dlen, chrom_len, (size_t)std::max(n_chrom, 1) * 8);
-    UP(dc, reg_chrom, (size_t)R * 4);
-    UP(ds, reg_start, (size_t)R * 8);
-    UP(de, reg_end, (size_t)R * 8);
-    UP(dm, reg_minus, (size_t)R);
-#undef UP
-    DIG_HIP_TRY(dout.alloc((size_t)R * 64 * 4));
-    int rc = dig_count_contexts2(dw.as<uint32_t>(), n_words2, dns.as<int64_t>(), dne.as<int64_t>(), n_int, dnb.as<int32_t>(), n_buckets,
-                                 doff.as<int64_t>(), dlen.as<int64_t>(), n_chrom, dc.as<int32_t>(), ds.as<int64_t>(), de.as<int64_t>(),
-                                 dm.as<uint8_t>(), R, dout.as<int32_t>(), nullptr);
-    if (rc) return rc;
-    DIG_HIP_TRY(hipDeviceSynchronize());
-    DIG_HIP_TRY(hipMemcpy(out, dout.p, (size_t)R * 64 * 4, hipMemcpyDeviceToHost));
-    return DIG_OK;
-}
-
 
 }  // extern "C"

@@ -391,17 +391,6 @@ static int launch_gather(const void* x, int64_t n_total, int64_t L, int64_t T, c
     return DIG_OK;
 }
 
-static size_t dtype_size(int dt)
-{
-    switch (dt) {
-        case DIG_F32: return 4;
-        case DIG_F64: return 8;
-        case DIG_I16: return 2;
-        case DIG_BF16: return 2;
-        default: return 0;
-    }
-}
-
 }  // namespace dig
 
 using namespace dig;
@@ -429,36 +418,6 @@ int dig_gather_bins(const void* x_data, int src_dtype, int64_t N, int64_t L, int
     if (src_dtype == DIG_F64) GO(double, __hip_bfloat16);
     GO(int16_t, __hip_bfloat16);
 #undef GO
-}
-
-int dig_gather_bins_host(const void* x_data, int src_dtype, int64_t N, int64_t L, int64_t T, const int64_t* bin_rows,
-                         int64_t B, const int32_t* tracks, int64_t T_sel, void* out, int out_dtype, int transpose_out,
-                         int device)
-{
-    DIG_REQUIRE(N >= 0 && L > 0 && T > 0 && B >= 0 && T_sel >= 0, "sizes");
-    if (B == 0 || T_sel == 0) return DIG_OK;
-    DIG_REQUIRE(x_data && bin_rows && out, "non-null pointers");
-    DIG_REQUIRE(tracks || T_sel == T, "tracks == NULL selects all tracks: T_sel must equal T");
-    const size_t ss = dtype_size(src_dtype), ds = dtype_size(out_dtype);
-    DIG_REQUIRE(ss && ds, "known dtypes");
-    for (int64_t b = 0; b < B; ++b) DIG_REQUIRE(bin_rows[b] >= 0 && bin_rows[b] < N, "bin_rows within [0, N)");
-    for (int64_t t = 0; tracks && t < T_sel; ++t) DIG_REQUIRE(tracks[t] >= 0 && tracks[t] < T, "tracks within [0, T)");
-    DIG_HIP_TRY(hipSetDevice(device));
-    DevBuf dx, dr, dt, dout;
-    const size_t xb = (size_t)N * L * T * ss, ob = (size_t)B * L * T_sel * ds;
-    DIG_HIP_TRY(dx.alloc(xb));
-    DIG_HIP_TRY(dr.alloc((size_t)B * 8));
-    if (tracks) DIG_HIP_TRY(dt.alloc((size_t)T_sel * 4));
-    DIG_HIP_TRY(dout.alloc(ob));
-    DIG_HIP_TRY(hipMemcpy(dx.p, x_data, xb, hipMemcpyHostToDevice));
-    DIG_HIP_TRY(hipMemcpy(dr.p, bin_rows, (size_t)B * 8, hipMemcpyHostToDevice));
-    if (tracks) DIG_HIP_TRY(hipMemcpy(dt.p, tracks, (size_t)T_sel * 4, hipMemcpyHostToDevice));
-    int rc = dig_gather_bins(dx.p, src_dtype, N, L, T, dr.as<int64_t>(), B, tracks ? dt.as<int32_t>() : nullptr, T_sel, dout.p, out_dtype,
-                             transpose_out, nullptr);
-    if (rc) return rc;
-    DIG_HIP_TRY(hipDeviceSynchronize());
-    DIG_HIP_TRY(hipMemcpy(out, dout.p, ob, hipMemcpyDeviceToHost));
-    return DIG_OK;
 }
 
 }  // extern "C"

@@ -121,43 +121,6 @@ int dig_gene_stats(const double* mu, const double* sigma, const double* mu_indel
     return gene_stats_launch(a, (hipStream_t)stream);
 }
 
-int dig_gene_stats_host(const double* mu, const double* sigma, const double* mu_indel, const double* sigma_indel, const double* pi,
-                        int n_pi, const double* pi_indel, int pi_indel_per_cohort, const int32_t* obs, const int32_t* n_samp,
-                        const double* cj, const double* t_indel, int with_indel, double* out, int64_t G, int64_t C, int device)
-{
-    DIG_REQUIRE(G >= 0 && C >= 0, "G, C >= 0");
-    DIG_REQUIRE(n_pi == 4 || n_pi == 6, "n_pi: 4 or 6");
-    if (G == 0 || C == 0) return DIG_OK;
-    DIG_REQUIRE(mu && sigma && pi && obs && n_samp && cj && out, "non-null pointers");
-    DIG_REQUIRE(!with_indel || (pi_indel && t_indel), "pi_indel and t_indel for the indel block");
-    DIG_HIP_TRY(hipSetDevice(device));
-    const size_t nGC = (size_t)G * C;
-    DevBuf dmu, dsg, dmi, dsi, dpi, dpii, dob, dns, dcj, dti, dout;
-#define UP(buf, src, bytes)                                                    \
-    DIG_HIP_TRY(buf.alloc(bytes));                                             \
-    if (src) DIG_HIP_TRY(hipMemcpy(buf.p, src, bytes, hipMemcpyHostToDevice))
-    UP(dmu, mu, nGC * 8);
-    UP(dsg, sigma, nGC * 8);
-    UP(dmi, mu_indel, nGC * 8);
-    UP(dsi, sigma_indel, nGC * 8);
-    UP(dpi, pi, nGC * n_pi * 8);
-    UP(dpii, pi_indel, (pi_indel_per_cohort ? nGC : (size_t)G) * 8);
-    UP(dob, obs, nGC * 5 * 4);
-    UP(dns, n_samp, nGC * 6 * 4);
-    UP(dcj, cj, (size_t)C * 8);
-    UP(dti, t_indel, (size_t)C * 8);
-#undef UP
-    DIG_HIP_TRY(dout.alloc(nGC * 22 * 8));
-    int rc = dig_gene_stats(dmu.as<double>(), dsg.as<double>(), mu_indel ? dmi.as<double>() : nullptr,
-                            sigma_indel ? dsi.as<double>() : nullptr, dpi.as<double>(), n_pi, pi_indel ? dpii.as<double>() : nullptr,
-                            pi_indel_per_cohort, dob.as<int32_t>(), dns.as<int32_t>(), dcj.as<double>(),
-                            t_indel ? dti.as<double>() : nullptr, with_indel, dout.as<double>(), G, C, nullptr);
-    if (rc) return rc;
-    DIG_HIP_TRY(hipDeviceSynchronize());
-    DIG_HIP_TRY(hipMemcpy(out, dout.p, nGC * 22 * 8, hipMemcpyDeviceToHost));
-    return DIG_OK;
-}
-
 int64_t dig_accumulate_workspace(int64_t E, int64_t C);
 
 int dig_gene_pipeline(const double* bin_mu, const double* bin_std, const int32_t* bin_y, const uint8_t* bin_flag,

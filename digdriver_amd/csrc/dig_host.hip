@@ -1,8 +1,9 @@
-// dig_host.hip -- `_host` twins of the entry points whose device forms live in dig_pipeline.hip, dig_tiles.hip and
-// dig_join.hip (one twin per entry point).  A twin takes host pointers, stages them through device buffers
-// of its own, runs the device entry point on the null stream and copies the results back: the PCIe-inclusive path for
-// callers without device memory of their own (small problems, tests, the reference-side binding of INTEGRATION.md).
-#include <utility>
+// dig_host.hip -- the `_host` twins of the device entry points (one twin per entry point).  A twin takes host
+// pointers, checks its arguments, stages them through device buffers of its own, runs the device entry point on the null
+// stream and copies the results back: the PCIe-inclusive path for callers without device memory of their own (small problems,
+// tests, the torch-free command lines, the reference-side binding of INTEGRATION.md).  The twins hold no arithmetic; the
+// kernels and their device entry points live in the other translation units.
+#include <algorithm>
 #include <vector>
 
 #include "dig_common.hpp"
@@ -11,37 +12,295 @@ using namespace dig;
 
 namespace {
 
-struct Stage {                 // host <-> device staging of one call
-    std::vector<std::pair<DevBuf*, std::pair<void*, size_t>>> outs;
-    int up(DevBuf& b, const void* src, size_t bytes)
+// The device side of one twin call.  The constructor selects the device; in() / out() / scratch() allocate a buffer the
+// destructor frees (one byte at least, so an empty array still has an address) and in() copies its source up.  The first
+// failing HIP call is recorded and the staging steps after it are skipped; staged() reports it (DIG_EHIP), and call() checks
+// it before it runs the device entry point, then synchronises and copies every out() back.  Counts are elements of T; the
+// _bytes forms serve run-time dtypes.
+class Staging {
+public:
+    explicit Staging(int device) { check(hipSetDevice(device), "hipSetDevice"); }
+    ~Staging()
     {
-        DIG_HIP_TRY(b.alloc(bytes));
-        if (src && bytes) DIG_HIP_TRY(hipMemcpy(b.p, src, bytes, hipMemcpyHostToDevice));
+        for (void* p : bufs_) (void)hipFree(p);
+    }
+    Staging(const Staging&) = delete;
+    Staging& operator=(const Staging&) = delete;
+
+    // a device copy of src[0, count); NULL for a NULL src (an optional input)
+    template <typename T>
+    const T* in(const T* src, size_t count)
+    {
+        return static_cast<const T*>(in_bytes(src, count * sizeof(T)));
+    }
+    // a device array of count elements that call() copies to dst
+    template <typename T>
+    T* out(T* dst, size_t count)
+    {
+        return static_cast<T*>(out_bytes(dst, count * sizeof(T)));
+    }
+    const void* in_bytes(const void* src, size_t bytes)
+    {
+        if (!src) return nullptr;
+        void* d = alloc(bytes);
+        if (d && bytes) check(hipMemcpy(d, src, bytes, hipMemcpyHostToDevice), "hipMemcpy (host to device)");
+        return d;
+    }
+    void* out_bytes(void* dst, size_t bytes)
+    {
+        void* d = alloc(bytes);
+        outs_.push_back({dst, d, bytes});
+        return d;
+    }
+    void* scratch(size_t bytes) { return alloc(bytes); }
+
+    int staged() const
+    {
+        if (err_ != hipSuccess) return set_error(DIG_EHIP, "%s failed: %s", what_, hipGetErrorString(err_));
         return DIG_OK;
     }
-    int out(DevBuf& b, void* dst, size_t bytes)
+    template <typename Fn, typename... Args>
+    int call(Fn fn, Args... args)
     {
-        DIG_HIP_TRY(b.alloc(bytes));
-        outs.push_back({&b, {dst, bytes}});
-        return DIG_OK;
-    }
-    int down()
-    {
+        if (int rc = staged()) return rc;
+        if (int rc = fn(args...)) return rc;
         DIG_HIP_TRY(hipDeviceSynchronize());
-        for (auto& o : outs)
-            if (o.second.second) DIG_HIP_TRY(hipMemcpy(o.second.first, o.first->p, o.second.second, hipMemcpyDeviceToHost));
+        for (const Out& o : outs_)
+            if (o.bytes) DIG_HIP_TRY(hipMemcpy(o.dst, o.src, o.bytes, hipMemcpyDeviceToHost));
         return DIG_OK;
     }
+
+private:
+    struct Out {
+        void* dst;
+        const void* src;
+        size_t bytes;
+    };
+    void* alloc(size_t bytes)
+    {
+        void* p = nullptr;
+        if (err_ == hipSuccess && check(hipMalloc(&p, bytes ? bytes : 1), "hipMalloc")) bufs_.push_back(p);
+        return p;
+    }
+    bool check(hipError_t e, const char* what)
+    {
+        if (e != hipSuccess && err_ == hipSuccess) err_ = e, what_ = what;
+        return e == hipSuccess;
+    }
+    std::vector<void*> bufs_;
+    std::vector<Out> outs_;
+    hipError_t err_ = hipSuccess;
+    const char* what_ = "";
 };
-#define DIG_TRY(expr)            \
-    do {                         \
-        int _rc = (expr);        \
-        if (_rc) return _rc;     \
-    } while (0)
+
+using Nb3Fn = int (*)(const double*, const double*, const double*, double*, int64_t, void*);
+
+int nb3_host(Nb3Fn fn, const double* k, const double* alpha, const double* p, double* out, int64_t n, int device)
+{
+    if (n == 0) return DIG_OK;
+    if (!k || !alpha || !p || !out || n < 0) return set_error(DIG_EINVAL, "nb3_host: null pointer or negative n");
+    Staging st(device);
+    return st.call(fn, st.in(k, n), st.in(alpha, n), st.in(p, n), st.out(out, n), n, nullptr);
+}
+
+size_t dtype_size(int dt)
+{
+    switch (dt) {
+        case DIG_F32: return 4;
+        case DIG_F64: return 8;
+        case DIG_I16: return 2;
+        case DIG_BF16: return 2;
+        default: return 0;
+    }
+}
 
 }  // namespace
 
 extern "C" {
+
+int dig_nb_midp_upper_host(const double* k, const double* alpha, const double* p, double* out, int64_t n, int device)
+{
+    return nb3_host(dig_nb_midp_upper, k, alpha, p, out, n, device);
+}
+int dig_nb_exact_host(const double* k, const double* alpha, const double* p, double* out, int64_t n, int device)
+{
+    return nb3_host(dig_nb_exact, k, alpha, p, out, n, device);
+}
+int dig_nb_greater_host(const double* k, const double* alpha, const double* p, double* out, int64_t n, int device)
+{
+    return nb3_host(dig_nb_greater, k, alpha, p, out, n, device);
+}
+int dig_nb_midp_twosided_host(const double* k, const double* alpha, const double* p, double* out, int64_t n, int device)
+{
+    return nb3_host(dig_nb_midp_twosided, k, alpha, p, out, n, device);
+}
+
+int dig_fisher_host(const double* p1, const double* p2, double* out, int64_t n, int device)
+{
+    if (n == 0) return DIG_OK;
+    DIG_REQUIRE(p1 && p2 && out && n > 0, "non-null pointers, n >= 0");
+    Staging st(device);
+    return st.call(dig_fisher, st.in(p1, n), st.in(p2, n), st.out(out, n), n, nullptr);
+}
+
+int dig_normal_params_to_gamma_host(const double* mu, const double* sigma, double* alpha, double* theta, int64_t n, int device)
+{
+    if (n == 0) return DIG_OK;
+    DIG_REQUIRE(mu && sigma && alpha && theta && n > 0, "non-null pointers, n >= 0");
+    Staging st(device);
+    return st.call(dig_normal_params_to_gamma, st.in(mu, n), st.in(sigma, n), st.out(alpha, n), st.out(theta, n), n, nullptr);
+}
+
+int dig_element_stats_host(const double* mu, const double* sigma, const double* mu_indel, const double* sigma_indel,
+                           const double* pi_sum, const double* pi_indel, int pi_indel_per_cohort, const int32_t* obs_snv,
+                           const int32_t* obs_samples, const int32_t* obs_indel, const double* cj, const double* cj_indel, double* out,
+                           int64_t E, int64_t C, int device)
+{
+    DIG_REQUIRE(E >= 0 && C >= 0, "E, C >= 0");
+    if (E == 0 || C == 0) return DIG_OK;
+    DIG_REQUIRE(mu && sigma && pi_sum && pi_indel && obs_snv && obs_samples && obs_indel && cj && cj_indel && out,
+                "non-null pointers");
+    DIG_REQUIRE(!mu_indel || sigma_indel, "sigma_indel with mu_indel");
+    const size_t n = (size_t)E * C;
+    const int64_t wsb = dig_element_stats_workspace(E, C);
+    Staging st(device);
+    return st.call(dig_element_stats, st.in(mu, n), st.in(sigma, n), st.in(mu_indel, n), mu_indel ? st.in(sigma_indel, n) : nullptr,
+                   st.in(pi_sum, n), st.in(pi_indel, pi_indel_per_cohort ? n : (size_t)E), pi_indel_per_cohort, st.in(obs_snv, n),
+                   st.in(obs_samples, n), st.in(obs_indel, n), st.in(cj, C), st.in(cj_indel, C), st.out(out, n * DIG_ES_NPLANES),
+                   E, C, wsb > 0 ? st.scratch((size_t)wsb) : nullptr, wsb, nullptr);
+}
+
+int dig_tiled_nb_test_host(const double* pt, int pt_per_cohort, const int32_t* k, const double* mu, const double* sigma,
+                           double* pval, double* exp_out, int64_t C, int64_t n_bins, int64_t n_tiles, int device)
+{
+    DIG_REQUIRE(C >= 0 && n_bins >= 0 && n_tiles >= 0, "non-negative sizes");
+    const size_t n = (size_t)C * n_bins * n_tiles;
+    if (n == 0) return DIG_OK;
+    DIG_REQUIRE(pt && k && mu && sigma && pval && exp_out, "non-null pointers");
+    const size_t ncb = (size_t)C * n_bins;
+    Staging st(device);
+    return st.call(dig_tiled_nb_test, st.in(pt, pt_per_cohort ? n : (size_t)n_bins * n_tiles), pt_per_cohort, st.in(k, n),
+                   st.in(mu, ncb), st.in(sigma, ncb), st.out(pval, n), st.out(exp_out, n), C, n_bins, n_tiles, nullptr);
+}
+
+int dig_accumulate_elements_host(const double* bin_mu, const double* bin_std, const int32_t* bin_y, const uint8_t* bin_flag,
+                                 const int32_t* bin_ctx, const int64_t* ov_ptr, const int32_t* ov_idx, const int32_t* L, int n_class,
+                                 const uint8_t* strand_minus, const int32_t* gene_length, const double* d_pr, double* MU,
+                                 double* SIGMA, int32_t* R_OBS, int32_t* FLAG, double* P, int32_t* R_SIZE, int32_t* ELT_SIZE,
+                                 double* P_INDEL, int64_t N, int64_t E, int64_t C, int device)
+{
+    DIG_REQUIRE(N >= 0 && E >= 0 && C >= 0, "N, E, C >= 0");
+    DIG_REQUIRE(n_class == 1 || n_class == 4, "n_class must be 1 (elements) or 4 (genes)");
+    if (E == 0 || C == 0) return DIG_OK;
+    DIG_REQUIRE(bin_mu && bin_std && bin_y && bin_flag && bin_ctx && ov_ptr && ov_idx && L && strand_minus && d_pr,
+                "non-null inputs");
+    DIG_REQUIRE(MU && SIGMA && R_OBS && FLAG && P && R_SIZE && ELT_SIZE && P_INDEL, "non-null outputs");
+    const int64_t nnz = ov_ptr[E];
+    DIG_REQUIRE(nnz >= 0, "ov_ptr[E] >= 0");
+    for (int64_t q = 0; q < nnz; ++q) DIG_REQUIRE(ov_idx[q] >= 0 && ov_idx[q] < N, "ov_idx within [0, N)");
+    const size_t nNC = (size_t)N * C, nEC = (size_t)E * C;
+    const int64_t wsb = dig_accumulate_workspace(E, C);
+    Staging st(device);
+    return st.call(dig_accumulate_elements, st.in(bin_mu, nNC), st.in(bin_std, nNC), st.in(bin_y, nNC), st.in(bin_flag, nNC),
+                   st.in(bin_ctx, (size_t)N * 64), st.in(ov_ptr, (size_t)E + 1), st.in(ov_idx, (size_t)nnz),
+                   st.in(L, (size_t)E * n_class * 192), n_class, st.in(strand_minus, E), st.in(gene_length, E),
+                   st.in(d_pr, (size_t)C * 192), st.out(MU, nEC), st.out(SIGMA, nEC), st.out(R_OBS, nEC), st.out(FLAG, nEC),
+                   st.out(P, nEC * n_class), st.out(R_SIZE, E), st.out(ELT_SIZE, E), st.out(P_INDEL, E), N, E, C,
+                   st.scratch((size_t)wsb), wsb, nullptr);
+}
+
+int dig_gene_stats_host(const double* mu, const double* sigma, const double* mu_indel, const double* sigma_indel, const double* pi,
+                        int n_pi, const double* pi_indel, int pi_indel_per_cohort, const int32_t* obs, const int32_t* n_samp,
+                        const double* cj, const double* t_indel, int with_indel, double* out, int64_t G, int64_t C, int device)
+{
+    DIG_REQUIRE(G >= 0 && C >= 0, "G, C >= 0");
+    DIG_REQUIRE(n_pi == 4 || n_pi == 6, "n_pi: 4 or 6");
+    if (G == 0 || C == 0) return DIG_OK;
+    DIG_REQUIRE(mu && sigma && pi && obs && n_samp && cj && out, "non-null pointers");
+    DIG_REQUIRE(!with_indel || (pi_indel && t_indel), "pi_indel and t_indel for the indel block");
+    const size_t nGC = (size_t)G * C;
+    Staging st(device);
+    return st.call(dig_gene_stats, st.in(mu, nGC), st.in(sigma, nGC), st.in(mu_indel, nGC), st.in(sigma_indel, nGC),
+                   st.in(pi, nGC * n_pi), n_pi, st.in(pi_indel, pi_indel_per_cohort ? nGC : (size_t)G), pi_indel_per_cohort,
+                   st.in(obs, nGC * 5), st.in(n_samp, nGC * 6), st.in(cj, C), st.in(t_indel, C), with_indel, st.out(out, nGC * 22),
+                   G, C, nullptr);
+}
+
+int dig_scale_suffstats_host(const double* bin_mu, const uint8_t* bin_flag, int64_t N, int64_t C, double* out_sum, int device)
+{
+    DIG_REQUIRE(N >= 0 && C >= 0, "N, C >= 0");
+    if (C == 0) return DIG_OK;
+    DIG_REQUIRE(out_sum, "non-null output");
+    const size_t n = (size_t)N * C;
+    DIG_REQUIRE(n == 0 || (bin_mu && bin_flag), "non-null inputs");
+    const int64_t wsb = dig_scale_suffstats_workspace(N, C);
+    Staging st(device);
+    return st.call(dig_scale_suffstats, st.in(bin_mu, n), st.in(bin_flag, n), N, C, st.out(out_sum, C), st.scratch((size_t)wsb), wsb,
+                   nullptr);
+}
+
+int dig_gather_bins_host(const void* x_data, int src_dtype, int64_t N, int64_t L, int64_t T, const int64_t* bin_rows, int64_t B,
+                         const int32_t* tracks, int64_t T_sel, void* out, int out_dtype, int transpose_out, int device)
+{
+    DIG_REQUIRE(N >= 0 && L > 0 && T > 0 && B >= 0 && T_sel >= 0, "sizes");
+    if (B == 0 || T_sel == 0) return DIG_OK;
+    DIG_REQUIRE(x_data && bin_rows && out, "non-null pointers");
+    DIG_REQUIRE(tracks || T_sel == T, "tracks == NULL selects all tracks: T_sel must equal T");
+    const size_t ss = dtype_size(src_dtype), ds = dtype_size(out_dtype);
+    DIG_REQUIRE(ss && ds, "known dtypes");
+    for (int64_t b = 0; b < B; ++b) DIG_REQUIRE(bin_rows[b] >= 0 && bin_rows[b] < N, "bin_rows within [0, N)");
+    for (int64_t t = 0; tracks && t < T_sel; ++t) DIG_REQUIRE(tracks[t] >= 0 && tracks[t] < T, "tracks within [0, T)");
+    Staging st(device);
+    return st.call(dig_gather_bins, st.in_bytes(x_data, (size_t)N * L * T * ss), src_dtype, N, L, T, st.in(bin_rows, B), B,
+                   st.in(tracks, T_sel), T_sel, st.out_bytes(out, (size_t)B * L * T_sel * ds), out_dtype, transpose_out, nullptr);
+}
+
+int dig_count_contexts_host(const uint32_t* genome_words, int64_t n_words, const int64_t* chrom_off, const int64_t* chrom_len,
+                            int n_chrom, const int32_t* reg_chrom, const int64_t* reg_start, const int64_t* reg_end,
+                            const uint8_t* reg_minus, int64_t R, int32_t* out, int device)
+{
+    DIG_REQUIRE(R >= 0 && n_words >= 2 && n_chrom >= 0, "R >= 0, n_words >= 2 (pad words), n_chrom >= 0");
+    if (R == 0) return DIG_OK;
+    DIG_REQUIRE(genome_words && chrom_off && chrom_len && reg_chrom && reg_start && reg_end && reg_minus && out,
+                "non-null pointers");
+    for (int64_t r = 0; r < R; ++r) {
+        DIG_REQUIRE(reg_chrom[r] >= 0 && reg_chrom[r] < n_chrom, "region chromosome index within [0, n_chrom)");
+        DIG_REQUIRE(reg_start[r] >= 0 && reg_end[r] >= 0, "non-negative coordinates");
+    }
+    for (int c = 0; c < n_chrom; ++c)
+        DIG_REQUIRE((chrom_off[c] & 7) == 0 && chrom_off[c] + chrom_len[c] <= (n_words - 2) * 8,
+                    "chromosomes word-aligned and inside the genome array");
+    const size_t nc = std::max(n_chrom, 1);
+    Staging st(device);
+    return st.call(dig_count_contexts, st.in(genome_words, n_words), n_words, st.in(chrom_off, nc), st.in(chrom_len, nc), n_chrom,
+                   st.in(reg_chrom, R), st.in(reg_start, R), st.in(reg_end, R), st.in(reg_minus, R), R, st.out(out, (size_t)R * 64),
+                   nullptr);
+}
+
+int dig_count_contexts2_host(const uint32_t* words2, int64_t n_words2, const int64_t* nint_start, const int64_t* nint_end, int64_t n_int,
+                             const int32_t* nint_bucket, int64_t n_buckets, const int64_t* chrom_off, const int64_t* chrom_len,
+                             int n_chrom, const int32_t* reg_chrom, const int64_t* reg_start, const int64_t* reg_end,
+                             const uint8_t* reg_minus, int64_t R, int32_t* out, int device)
+{
+    DIG_REQUIRE(R >= 0 && n_words2 >= 28 && n_chrom >= 0 && n_int >= 0, "R, n_int, n_chrom >= 0, n_words2 >= 28 (pad words)");
+    if (R == 0) return DIG_OK;
+    DIG_REQUIRE(words2 && chrom_off && chrom_len && reg_chrom && reg_start && reg_end && reg_minus && out, "non-null pointers");
+    DIG_REQUIRE(n_int == 0 || (nint_start && nint_end && nint_bucket && n_buckets >= 1), "interval list with its bucket index");
+    for (int64_t r = 0; r < R; ++r) {
+        DIG_REQUIRE(reg_chrom[r] >= 0 && reg_chrom[r] < n_chrom, "region chromosome index within [0, n_chrom)");
+        DIG_REQUIRE(reg_start[r] >= 0 && reg_end[r] >= 0, "non-negative coordinates");
+    }
+    for (int c = 0; c < n_chrom; ++c)
+        DIG_REQUIRE(chrom_off[c] >= 0 && chrom_off[c] + chrom_len[c] + 64 <= (n_words2 - 24) * 16, "chromosomes inside the genome array");
+    for (int64_t j = 0; j < n_int; ++j)
+        DIG_REQUIRE(nint_start[j] < nint_end[j] && (j == 0 || nint_end[j - 1] < nint_start[j]), "intervals sorted, disjoint, not touching");
+    const size_t nc = std::max(n_chrom, 1);
+    Staging st(device);
+    return st.call(dig_count_contexts2, st.in(words2, n_words2), n_words2, st.in(nint_start, n_int), st.in(nint_end, n_int), n_int,
+                   st.in(nint_bucket, n_int ? n_buckets : 0), n_buckets, st.in(chrom_off, nc), st.in(chrom_len, nc), n_chrom,
+                   st.in(reg_chrom, R), st.in(reg_start, R), st.in(reg_end, R), st.in(reg_minus, R), R, st.out(out, (size_t)R * 64),
+                   nullptr);
+}
 
 int dig_element_pipeline_host(const double* bin_mu, const double* bin_std, const int32_t* bin_y, const uint8_t* bin_flag,
                               const int32_t* bin_ctx, const int64_t* ov_ptr, const int32_t* ov_idx, const int32_t* L,
@@ -57,52 +316,53 @@ int dig_element_pipeline_host(const double* bin_mu, const double* bin_std, const
                 "non-null accumulation inputs");
     DIG_REQUIRE(obs_snv && obs_samples && obs_indel && cj && cj_indel, "non-null statistics inputs");
     DIG_REQUIRE(MU && SIGMA && R_OBS && FLAG && P && R_SIZE && ELT_SIZE && P_INDEL && out, "non-null outputs");
-    DIG_HIP_TRY(hipSetDevice(device));
     const int64_t nnz = ov_ptr[E];
     DIG_REQUIRE(nnz >= 0, "ov_ptr[E] >= 0");
     for (int64_t q = 0; q < nnz; ++q) DIG_REQUIRE(ov_idx[q] >= 0 && ov_idx[q] < N, "ov_idx within [0, N)");
-    const size_t nNC = (size_t)N * C, nEC = (size_t)E * C;
-    Stage st;
-    DevBuf d_mu, d_sd, d_y, d_fl, d_ctx, d_ptr, d_idx, d_L, d_sm, d_gl, d_dpr, d_o1, d_o2, d_o3, d_cj, d_cji;
-    DevBuf o_mu, o_sg, o_ro, o_fg, o_p, o_rs, o_es, o_pi, o_out, d_ws;
-    DIG_TRY(st.up(d_mu, bin_mu, nNC * 8));
-    DIG_TRY(st.up(d_sd, bin_std, nNC * 8));
-    DIG_TRY(st.up(d_y, bin_y, nNC * 4));
-    DIG_TRY(st.up(d_fl, bin_flag, nNC));
-    DIG_TRY(st.up(d_ctx, bin_ctx, (size_t)N * 64 * 4));
-    DIG_TRY(st.up(d_ptr, ov_ptr, (size_t)(E + 1) * 8));
-    DIG_TRY(st.up(d_idx, ov_idx, (size_t)(nnz > 0 ? nnz : 1) * 4));
-    DIG_TRY(st.up(d_L, L, (size_t)E * 192 * 4));
-    DIG_TRY(st.up(d_sm, strand_minus, (size_t)E));
-    if (gene_length) DIG_TRY(st.up(d_gl, gene_length, (size_t)E * 4));
-    DIG_TRY(st.up(d_dpr, d_pr, (size_t)C * 192 * 8));
-    DIG_TRY(st.up(d_o1, obs_snv, nEC * 4));
-    DIG_TRY(st.up(d_o2, obs_samples, nEC * 4));
-    DIG_TRY(st.up(d_o3, obs_indel, nEC * 4));
-    DIG_TRY(st.up(d_cj, cj, (size_t)C * 8));
-    DIG_TRY(st.up(d_cji, cj_indel, (size_t)C * 8));
-    DIG_TRY(st.out(o_mu, MU, nEC * 8));
-    DIG_TRY(st.out(o_sg, SIGMA, nEC * 8));
-    DIG_TRY(st.out(o_ro, R_OBS, nEC * 4));
-    DIG_TRY(st.out(o_fg, FLAG, nEC * 4));
-    DIG_TRY(st.out(o_p, P, nEC * 8));
-    DIG_TRY(st.out(o_rs, R_SIZE, (size_t)E * 4));
-    DIG_TRY(st.out(o_es, ELT_SIZE, (size_t)E * 4));
-    DIG_TRY(st.out(o_pi, P_INDEL, (size_t)E * 8));
-    DIG_TRY(st.out(o_out, out, nEC * 7 * 8));
     const int64_t wsb = dig_element_pipeline_workspace(E, C);
     DIG_REQUIRE(wsb > 0, "E * C must stay below 2^32 - 1");
-    DIG_HIP_TRY(d_ws.alloc((size_t)wsb));
+    const size_t nNC = (size_t)N * C, nEC = (size_t)E * C;
+    Staging st(device);
+    const int32_t* dL = st.in(L, (size_t)E * 192);
+    void* ws = st.scratch((size_t)wsb);
     int compact = 0;
-    if (N >= 1) DIG_TRY(dig_element_pipeline_prepare(d_L.as<int32_t>(), E, C, d_ws.p, wsb, &compact, nullptr));
-    DIG_TRY(dig_element_pipeline(d_mu.as<double>(), d_sd.as<double>(), d_y.as<int32_t>(), d_fl.as<uint8_t>(), d_ctx.as<int32_t>(),
-                                 d_ptr.as<int64_t>(), d_idx.as<int32_t>(), d_L.as<int32_t>(), d_sm.as<uint8_t>(),
-                                 gene_length ? d_gl.as<int32_t>() : nullptr, d_dpr.as<double>(), d_o1.as<int32_t>(),
-                                 d_o2.as<int32_t>(), d_o3.as<int32_t>(), d_cj.as<double>(), d_cji.as<double>(), o_mu.as<double>(),
-                                 o_sg.as<double>(), o_ro.as<int32_t>(), o_fg.as<int32_t>(), o_p.as<double>(), o_rs.as<int32_t>(),
-                                 o_es.as<int32_t>(), o_pi.as<double>(), o_out.as<double>(), N, E, C, nullptr,
-                                 DIG_PIPE_ALL | (compact ? DIG_PIPE_COMPACT_L : 0), d_ws.p, wsb, nullptr));
-    return st.down();
+    if (N >= 1) {
+        if (int rc = st.staged()) return rc;
+        if (int rc = dig_element_pipeline_prepare(dL, E, C, ws, wsb, &compact, nullptr)) return rc;
+    }
+    return st.call(dig_element_pipeline, st.in(bin_mu, nNC), st.in(bin_std, nNC), st.in(bin_y, nNC), st.in(bin_flag, nNC),
+                   st.in(bin_ctx, (size_t)N * 64), st.in(ov_ptr, (size_t)E + 1), st.in(ov_idx, (size_t)(nnz > 0 ? nnz : 1)), dL,
+                   st.in(strand_minus, E), st.in(gene_length, E), st.in(d_pr, (size_t)C * 192), st.in(obs_snv, nEC),
+                   st.in(obs_samples, nEC), st.in(obs_indel, nEC), st.in(cj, C), st.in(cj_indel, C), st.out(MU, nEC),
+                   st.out(SIGMA, nEC), st.out(R_OBS, nEC), st.out(FLAG, nEC), st.out(P, nEC), st.out(R_SIZE, E), st.out(ELT_SIZE, E),
+                   st.out(P_INDEL, E), st.out(out, nEC * 7), N, E, C, nullptr, DIG_PIPE_ALL | (compact ? DIG_PIPE_COMPACT_L : 0),
+                   ws, wsb, nullptr);
+}
+
+int dig_gene_pipeline_host(const double* bin_mu, const double* bin_std, const int32_t* bin_y, const uint8_t* bin_flag,
+                           const int32_t* bin_ctx, const int64_t* ov_ptr, const int32_t* ov_idx, const int32_t* L,
+                           const uint8_t* strand_minus, const int32_t* gene_length, const double* d_pr, const int32_t* obs,
+                           const int32_t* n_samp, const double* cj, const double* t_indel, int with_indel, double* MU, double* SIGMA,
+                           int32_t* R_OBS, int32_t* FLAG, double* P, int32_t* R_SIZE, int32_t* ELT_SIZE, double* P_INDEL, double* out,
+                           int64_t N, int64_t G, int64_t C, int device)
+{
+    DIG_REQUIRE(N >= 0 && G >= 0 && C >= 0, "N, G, C >= 0");
+    if (G == 0 || C == 0) return DIG_OK;
+    DIG_REQUIRE(bin_mu && bin_std && bin_y && bin_flag && bin_ctx && ov_ptr && ov_idx && L && strand_minus && d_pr, "non-null accumulation inputs");
+    DIG_REQUIRE(obs && n_samp && cj && (!with_indel || t_indel), "non-null statistics inputs");
+    DIG_REQUIRE(MU && SIGMA && R_OBS && FLAG && P && R_SIZE && ELT_SIZE && P_INDEL && out, "non-null outputs");
+    const int64_t nnz = ov_ptr[G];
+    DIG_REQUIRE(nnz >= 0, "ov_ptr[G] >= 0");
+    for (int64_t q = 0; q < nnz; ++q) DIG_REQUIRE(ov_idx[q] >= 0 && ov_idx[q] < N, "ov_idx within [0, N)");
+    const size_t nNC = (size_t)N * C, nGC = (size_t)G * C;
+    const int64_t wsb = dig_accumulate_workspace(G, C);
+    Staging st(device);
+    return st.call(dig_gene_pipeline, st.in(bin_mu, nNC), st.in(bin_std, nNC), st.in(bin_y, nNC), st.in(bin_flag, nNC),
+                   st.in(bin_ctx, (size_t)N * 64), st.in(ov_ptr, (size_t)G + 1), st.in(ov_idx, (size_t)(nnz > 0 ? nnz : 1)),
+                   st.in(L, (size_t)G * 4 * 192), st.in(strand_minus, G), st.in(gene_length, G), st.in(d_pr, (size_t)C * 192),
+                   st.in(obs, nGC * 5), st.in(n_samp, nGC * 6), st.in(cj, C), st.in(t_indel, C), with_indel, st.out(MU, nGC),
+                   st.out(SIGMA, nGC), st.out(R_OBS, nGC), st.out(FLAG, nGC), st.out(P, nGC * 4), st.out(R_SIZE, G),
+                   st.out(ELT_SIZE, G), st.out(P_INDEL, G), st.out(out, nGC * 22), N, G, C, st.scratch((size_t)wsb), wsb, nullptr);
 }
 
 int dig_base_tile_probs_host(const uint32_t* genome_words, int64_t n_words, const int64_t* chrom_off, const int64_t* chrom_len,
@@ -114,97 +374,10 @@ int dig_base_tile_probs_host(const uint32_t* genome_words, int64_t n_words, cons
     if (R == 0) return DIG_OK;
     DIG_REQUIRE(genome_words && chrom_off && chrom_len && reg_chrom && reg_start && reg_end && first_pos && n_valid, "non-null pointers");
     DIG_REQUIRE(C == 0 || n_tiles == 0 || (s_prob && pt), "s_prob and pt");
-    DIG_HIP_TRY(hipSetDevice(device));
-    Stage st;
-    DevBuf dw, doff, dlen, dc, ds, de, dsp, opt, ofp, onv;
-    DIG_TRY(st.up(dw, genome_words, (size_t)n_words * 4));
-    DIG_TRY(st.up(doff, chrom_off, (size_t)n_chrom * 8));
-    DIG_TRY(st.up(dlen, chrom_len, (size_t)n_chrom * 8));
-    DIG_TRY(st.up(dc, reg_chrom, (size_t)R * 4));
-    DIG_TRY(st.up(ds, reg_start, (size_t)R * 8));
-    DIG_TRY(st.up(de, reg_end, (size_t)R * 8));
-    DIG_TRY(st.up(dsp, s_prob, (size_t)C * 64 * 8));
-    DIG_TRY(st.out(opt, pt, (size_t)C * R * n_tiles * 8));
-    DIG_TRY(st.out(ofp, first_pos, (size_t)R * 8));
-    DIG_TRY(st.out(onv, n_valid, (size_t)R * 4));
-    DIG_TRY(dig_base_tile_probs(dw.as<uint32_t>(), n_words, doff.as<int64_t>(), dlen.as<int64_t>(), n_chrom, dc.as<int32_t>(),
-                                ds.as<int64_t>(), de.as<int64_t>(), R, dsp.as<double>(), C, binsize, n_tiles, opt.as<double>(),
-                                ofp.as<int64_t>(), onv.as<int32_t>(), nullptr));
-    return st.down();
-}
-
-int dig_tile_mut_counts_host(const int32_t* pair_mut, const int32_t* pair_reg, int64_t n_pairs, const int64_t* mut_start,
-                             int64_t n_mut, const int32_t* mut_cohort, const int64_t* first_pos, const int32_t* n_valid,
-                             int binsize, int64_t n_tiles, int64_t R, int64_t C, int32_t* k, int device)
-{
-    DIG_REQUIRE(n_pairs >= 0 && n_mut >= 0 && binsize >= 1 && n_tiles >= 0 && R >= 0 && C >= 0, "non-negative sizes, binsize >= 1");
-    const size_t n = (size_t)C * R * n_tiles;
-    if (n == 0) return DIG_OK;
-    DIG_REQUIRE(k && first_pos && n_valid, "non-null outputs / region tables");
-    DIG_REQUIRE(n_pairs == 0 || (pair_mut && pair_reg && mut_start && mut_cohort), "non-null pair / mutation arrays");
-    for (int64_t i = 0; i < n_pairs; ++i)
-        DIG_REQUIRE(pair_mut[i] >= 0 && pair_mut[i] < n_mut && pair_reg[i] >= 0 && pair_reg[i] < R, "pairs inside the mutation / region tables");
-    DIG_HIP_TRY(hipSetDevice(device));
-    Stage st;
-    DevBuf dpm, dpr, dms, dmc, dfp, dnv, ok;
-    DIG_TRY(st.up(dpm, pair_mut, (size_t)n_pairs * 4));
-    DIG_TRY(st.up(dpr, pair_reg, (size_t)n_pairs * 4));
-    DIG_TRY(st.up(dms, mut_start, (size_t)n_mut * 8));
-    DIG_TRY(st.up(dmc, mut_cohort, (size_t)n_mut * 4));
-    DIG_TRY(st.up(dfp, first_pos, (size_t)R * 8));
-    DIG_TRY(st.up(dnv, n_valid, (size_t)R * 4));
-    DIG_TRY(st.out(ok, k, n * 4));
-    DIG_TRY(dig_tile_mut_counts(dpm.as<int32_t>(), dpr.as<int32_t>(), n_pairs, dms.as<int64_t>(), dmc.as<int32_t>(), dfp.as<int64_t>(),
-                                dnv.as<int32_t>(), binsize, n_tiles, R, C, ok.as<int32_t>(), nullptr));
-    return st.down();
-}
-
-int dig_overlap_join_count_host(const int64_t* blk_start_key, const int64_t* blk_runmax_key, const int64_t* blk_end, int64_t n_blk,
-                                const int64_t* mut_chrom, const int64_t* mut_start, const int64_t* mut_end, int64_t n_mut,
-                                int32_t* counts, int device)
-{
-    DIG_REQUIRE(n_blk >= 0 && n_mut >= 0, "sizes >= 0");
-    if (n_mut == 0) return DIG_OK;
-    DIG_REQUIRE(mut_chrom && mut_start && mut_end && counts, "non-null mutation arrays");
-    DIG_REQUIRE(n_blk == 0 || (blk_start_key && blk_runmax_key && blk_end), "non-null block arrays");
-    DIG_HIP_TRY(hipSetDevice(device));
-    Stage st;
-    DevBuf b1, b2, b3, m1, m2, m3, oc;
-    DIG_TRY(st.up(b1, blk_start_key, (size_t)n_blk * 8));
-    DIG_TRY(st.up(b2, blk_runmax_key, (size_t)n_blk * 8));
-    DIG_TRY(st.up(b3, blk_end, (size_t)n_blk * 8));
-    DIG_TRY(st.up(m1, mut_chrom, (size_t)n_mut * 8));
-    DIG_TRY(st.up(m2, mut_start, (size_t)n_mut * 8));
-    DIG_TRY(st.up(m3, mut_end, (size_t)n_mut * 8));
-    DIG_TRY(st.out(oc, counts, (size_t)n_mut * 4));
-    DIG_TRY(dig_overlap_join_count(b1.as<int64_t>(), b2.as<int64_t>(), b3.as<int64_t>(), n_blk, m1.as<int64_t>(), m2.as<int64_t>(),
-                                   m3.as<int64_t>(), n_mut, oc.as<int32_t>(), nullptr));
-    return st.down();
-}
-
-int dig_overlap_join_fill_host(const int64_t* blk_start_key, const int64_t* blk_runmax_key, const int64_t* blk_end, int64_t n_blk,
-                               const int64_t* mut_chrom, const int64_t* mut_start, const int64_t* mut_end, int64_t n_mut,
-                               const int64_t* offsets, int64_t n_pairs, int32_t* pair_mut, int32_t* pair_blk, int device)
-{
-    DIG_REQUIRE(n_blk >= 0 && n_mut >= 0 && n_pairs >= 0, "sizes >= 0");
-    if (n_mut == 0 || n_blk == 0 || n_pairs == 0) return DIG_OK;
-    DIG_REQUIRE(mut_chrom && mut_start && mut_end && offsets && pair_mut && pair_blk, "non-null arrays");
-    DIG_REQUIRE(blk_start_key && blk_runmax_key && blk_end, "non-null block arrays");
-    DIG_HIP_TRY(hipSetDevice(device));
-    Stage st;
-    DevBuf b1, b2, b3, m1, m2, m3, off, o1, o2;
-    DIG_TRY(st.up(b1, blk_start_key, (size_t)n_blk * 8));
-    DIG_TRY(st.up(b2, blk_runmax_key, (size_t)n_blk * 8));
-    DIG_TRY(st.up(b3, blk_end, (size_t)n_blk * 8));
-    DIG_TRY(st.up(m1, mut_chrom, (size_t)n_mut * 8));
-    DIG_TRY(st.up(m2, mut_start, (size_t)n_mut * 8));
-    DIG_TRY(st.up(m3, mut_end, (size_t)n_mut * 8));
-    DIG_TRY(st.up(off, offsets, (size_t)n_mut * 8));
-    DIG_TRY(st.out(o1, pair_mut, (size_t)n_pairs * 4));
-    DIG_TRY(st.out(o2, pair_blk, (size_t)n_pairs * 4));
-    DIG_TRY(dig_overlap_join_fill(b1.as<int64_t>(), b2.as<int64_t>(), b3.as<int64_t>(), n_blk, m1.as<int64_t>(), m2.as<int64_t>(),
-                                  m3.as<int64_t>(), n_mut, off.as<int64_t>(), o1.as<int32_t>(), o2.as<int32_t>(), nullptr));
-    return st.down();
+    Staging st(device);
+    return st.call(dig_base_tile_probs, st.in(genome_words, n_words), n_words, st.in(chrom_off, n_chrom), st.in(chrom_len, n_chrom),
+                   n_chrom, st.in(reg_chrom, R), st.in(reg_start, R), st.in(reg_end, R), R, st.in(s_prob, (size_t)C * 64), C, binsize,
+                   n_tiles, st.out(pt, (size_t)C * R * n_tiles), st.out(first_pos, R), st.out(n_valid, R), nullptr);
 }
 
 int dig_base_tile_probs_ctx_host(const uint32_t* genome_words, int64_t n_words, const int64_t* chrom_off, const int64_t* chrom_len,
@@ -222,79 +395,56 @@ int dig_base_tile_probs_ctx_host(const uint32_t* genome_words, int64_t n_words, 
         DIG_REQUIRE(n_up == 1 || reg_end[r] - reg_start[r] <= 16384, "a region of the general-context form holds at most 16 384 positions");
         DIG_REQUIRE(n_up == 1 || reg_start[r] == 0 || reg_start[r] >= n_up, "a region that starts inside (0, n_up) would fetch from a negative position");
     }
-    DIG_HIP_TRY(hipSetDevice(device));
-    const int64_t K = n_up == 1 ? 64 : 1024;
-    Stage st;
-    DevBuf dw, doff, dlen, dc, ds, de, dsp, opt, ofp, onv;
-    DIG_TRY(st.up(dw, genome_words, (size_t)n_words * 4));
-    DIG_TRY(st.up(doff, chrom_off, (size_t)n_chrom * 8));
-    DIG_TRY(st.up(dlen, chrom_len, (size_t)n_chrom * 8));
-    DIG_TRY(st.up(dc, reg_chrom, (size_t)R * 4));
-    DIG_TRY(st.up(ds, reg_start, (size_t)R * 8));
-    DIG_TRY(st.up(de, reg_end, (size_t)R * 8));
-    DIG_TRY(st.up(dsp, s_prob, (size_t)C * K * 8));
-    DIG_TRY(st.out(opt, pt, (size_t)C * R * n_tiles * 8));
-    DIG_TRY(st.out(ofp, first_pos, (size_t)R * 8));
-    DIG_TRY(st.out(onv, n_valid, (size_t)R * 4));
-    DIG_TRY(dig_base_tile_probs_ctx(dw.as<uint32_t>(), n_words, doff.as<int64_t>(), dlen.as<int64_t>(), n_chrom, dc.as<int32_t>(),
-                                    ds.as<int64_t>(), de.as<int64_t>(), R, dsp.as<double>(), C, n_up, binsize, n_tiles,
-                                    opt.as<double>(), ofp.as<int64_t>(), onv.as<int32_t>(), nullptr));
-    return st.down();
+    const size_t nsp = (size_t)C * (n_up == 1 ? 64 : 1024);
+    Staging st(device);
+    // the context kernels load the table of every cohort even when n_tiles == 0 (s_prob may be NULL then)
+    const double* d_sp = s_prob ? st.in(s_prob, nsp) : static_cast<const double*>(st.scratch(nsp * sizeof(double)));
+    return st.call(dig_base_tile_probs_ctx, st.in(genome_words, n_words), n_words, st.in(chrom_off, n_chrom),
+                   st.in(chrom_len, n_chrom), n_chrom, st.in(reg_chrom, R), st.in(reg_start, R), st.in(reg_end, R), R, d_sp, C, n_up,
+                   binsize, n_tiles, st.out(pt, (size_t)C * R * n_tiles), st.out(first_pos, R), st.out(n_valid, R), nullptr);
 }
 
-int dig_gene_pipeline_host(const double* bin_mu, const double* bin_std, const int32_t* bin_y, const uint8_t* bin_flag,
-                           const int32_t* bin_ctx, const int64_t* ov_ptr, const int32_t* ov_idx, const int32_t* L,
-                           const uint8_t* strand_minus, const int32_t* gene_length, const double* d_pr, const int32_t* obs,
-                           const int32_t* n_samp, const double* cj, const double* t_indel, int with_indel, double* MU, double* SIGMA,
-                           int32_t* R_OBS, int32_t* FLAG, double* P, int32_t* R_SIZE, int32_t* ELT_SIZE, double* P_INDEL, double* out,
-                           int64_t N, int64_t G, int64_t C, int device)
+int dig_tile_mut_counts_host(const int32_t* pair_mut, const int32_t* pair_reg, int64_t n_pairs, const int64_t* mut_start,
+                             int64_t n_mut, const int32_t* mut_cohort, const int64_t* first_pos, const int32_t* n_valid,
+                             int binsize, int64_t n_tiles, int64_t R, int64_t C, int32_t* k, int device)
 {
-    DIG_REQUIRE(N >= 0 && G >= 0 && C >= 0, "N, G, C >= 0");
-    if (G == 0 || C == 0) return DIG_OK;
-    DIG_REQUIRE(bin_mu && bin_std && bin_y && bin_flag && bin_ctx && ov_ptr && ov_idx && L && strand_minus && d_pr, "non-null accumulation inputs");
-    DIG_REQUIRE(obs && n_samp && cj && (!with_indel || t_indel), "non-null statistics inputs");
-    DIG_REQUIRE(MU && SIGMA && R_OBS && FLAG && P && R_SIZE && ELT_SIZE && P_INDEL && out, "non-null outputs");
-    DIG_HIP_TRY(hipSetDevice(device));
-    const int64_t nnz = ov_ptr[G];
-    DIG_REQUIRE(nnz >= 0, "ov_ptr[G] >= 0");
-    for (int64_t q = 0; q < nnz; ++q) DIG_REQUIRE(ov_idx[q] >= 0 && ov_idx[q] < N, "ov_idx within [0, N)");
-    const size_t nNC = (size_t)N * C, nGC = (size_t)G * C;
-    Stage st;
-    DevBuf d_mu, d_sd, d_y, d_fl, d_ctx, d_ptr, d_idx, d_L, d_sm, d_gl, d_dpr, d_ob, d_ns, d_cj, d_ti;
-    DevBuf o_mu, o_sg, o_ro, o_fg, o_p, o_rs, o_es, o_pi, o_out, d_ws;
-    DIG_TRY(st.up(d_mu, bin_mu, nNC * 8));
-    DIG_TRY(st.up(d_sd, bin_std, nNC * 8));
-    DIG_TRY(st.up(d_y, bin_y, nNC * 4));
-    DIG_TRY(st.up(d_fl, bin_flag, nNC));
-    DIG_TRY(st.up(d_ctx, bin_ctx, (size_t)N * 64 * 4));
-    DIG_TRY(st.up(d_ptr, ov_ptr, (size_t)(G + 1) * 8));
-    DIG_TRY(st.up(d_idx, ov_idx, (size_t)(nnz > 0 ? nnz : 1) * 4));
-    DIG_TRY(st.up(d_L, L, (size_t)G * 4 * 192 * 4));
-    DIG_TRY(st.up(d_sm, strand_minus, (size_t)G));
-    if (gene_length) DIG_TRY(st.up(d_gl, gene_length, (size_t)G * 4));
-    DIG_TRY(st.up(d_dpr, d_pr, (size_t)C * 192 * 8));
-    DIG_TRY(st.up(d_ob, obs, nGC * 5 * 4));
-    DIG_TRY(st.up(d_ns, n_samp, nGC * 6 * 4));
-    DIG_TRY(st.up(d_cj, cj, (size_t)C * 8));
-    if (t_indel) DIG_TRY(st.up(d_ti, t_indel, (size_t)C * 8));
-    DIG_TRY(st.out(o_mu, MU, nGC * 8));
-    DIG_TRY(st.out(o_sg, SIGMA, nGC * 8));
-    DIG_TRY(st.out(o_ro, R_OBS, nGC * 4));
-    DIG_TRY(st.out(o_fg, FLAG, nGC * 4));
-    DIG_TRY(st.out(o_p, P, nGC * 4 * 8));
-    DIG_TRY(st.out(o_rs, R_SIZE, (size_t)G * 4));
-    DIG_TRY(st.out(o_es, ELT_SIZE, (size_t)G * 4));
-    DIG_TRY(st.out(o_pi, P_INDEL, (size_t)G * 8));
-    DIG_TRY(st.out(o_out, out, nGC * 22 * 8));
-    const int64_t wsb = dig_accumulate_workspace(G, C);
-    DIG_HIP_TRY(d_ws.alloc((size_t)wsb));
-    DIG_TRY(dig_gene_pipeline(d_mu.as<double>(), d_sd.as<double>(), d_y.as<int32_t>(), d_fl.as<uint8_t>(), d_ctx.as<int32_t>(),
-                              d_ptr.as<int64_t>(), d_idx.as<int32_t>(), d_L.as<int32_t>(), d_sm.as<uint8_t>(),
-                              gene_length ? d_gl.as<int32_t>() : nullptr, d_dpr.as<double>(), d_ob.as<int32_t>(), d_ns.as<int32_t>(),
-                              d_cj.as<double>(), t_indel ? d_ti.as<double>() : nullptr, with_indel, o_mu.as<double>(), o_sg.as<double>(),
-                              o_ro.as<int32_t>(), o_fg.as<int32_t>(), o_p.as<double>(), o_rs.as<int32_t>(), o_es.as<int32_t>(),
-                              o_pi.as<double>(), o_out.as<double>(), N, G, C, d_ws.p, wsb, nullptr));
-    return st.down();
+    DIG_REQUIRE(n_pairs >= 0 && n_mut >= 0 && binsize >= 1 && n_tiles >= 0 && R >= 0 && C >= 0, "non-negative sizes, binsize >= 1");
+    const size_t n = (size_t)C * R * n_tiles;
+    if (n == 0) return DIG_OK;
+    DIG_REQUIRE(k && first_pos && n_valid, "non-null outputs / region tables");
+    DIG_REQUIRE(n_pairs == 0 || (pair_mut && pair_reg && mut_start && mut_cohort), "non-null pair / mutation arrays");
+    for (int64_t i = 0; i < n_pairs; ++i)
+        DIG_REQUIRE(pair_mut[i] >= 0 && pair_mut[i] < n_mut && pair_reg[i] >= 0 && pair_reg[i] < R, "pairs inside the mutation / region tables");
+    Staging st(device);
+    return st.call(dig_tile_mut_counts, st.in(pair_mut, n_pairs), st.in(pair_reg, n_pairs), n_pairs, st.in(mut_start, n_mut),
+                   st.in(mut_cohort, n_mut), st.in(first_pos, R), st.in(n_valid, R), binsize, n_tiles, R, C, st.out(k, n), nullptr);
+}
+
+int dig_overlap_join_count_host(const int64_t* blk_start_key, const int64_t* blk_runmax_key, const int64_t* blk_end, int64_t n_blk,
+                                const int64_t* mut_chrom, const int64_t* mut_start, const int64_t* mut_end, int64_t n_mut,
+                                int32_t* counts, int device)
+{
+    DIG_REQUIRE(n_blk >= 0 && n_mut >= 0, "sizes >= 0");
+    if (n_mut == 0) return DIG_OK;
+    DIG_REQUIRE(mut_chrom && mut_start && mut_end && counts, "non-null mutation arrays");
+    DIG_REQUIRE(n_blk == 0 || (blk_start_key && blk_runmax_key && blk_end), "non-null block arrays");
+    Staging st(device);
+    return st.call(dig_overlap_join_count, st.in(blk_start_key, n_blk), st.in(blk_runmax_key, n_blk), st.in(blk_end, n_blk), n_blk,
+                   st.in(mut_chrom, n_mut), st.in(mut_start, n_mut), st.in(mut_end, n_mut), n_mut, st.out(counts, n_mut), nullptr);
+}
+
+int dig_overlap_join_fill_host(const int64_t* blk_start_key, const int64_t* blk_runmax_key, const int64_t* blk_end, int64_t n_blk,
+                               const int64_t* mut_chrom, const int64_t* mut_start, const int64_t* mut_end, int64_t n_mut,
+                               const int64_t* offsets, int64_t n_pairs, int32_t* pair_mut, int32_t* pair_blk, int device)
+{
+    DIG_REQUIRE(n_blk >= 0 && n_mut >= 0 && n_pairs >= 0, "sizes >= 0");
+    if (n_mut == 0 || n_blk == 0 || n_pairs == 0) return DIG_OK;
+    DIG_REQUIRE(mut_chrom && mut_start && mut_end && offsets && pair_mut && pair_blk, "non-null arrays");
+    DIG_REQUIRE(blk_start_key && blk_runmax_key && blk_end, "non-null block arrays");
+    Staging st(device);
+    return st.call(dig_overlap_join_fill, st.in(blk_start_key, n_blk), st.in(blk_runmax_key, n_blk), st.in(blk_end, n_blk), n_blk,
+                   st.in(mut_chrom, n_mut), st.in(mut_start, n_mut), st.in(mut_end, n_mut), n_mut, st.in(offsets, n_mut),
+                   st.out(pair_mut, n_pairs), st.out(pair_blk, n_pairs), nullptr);
 }
 
 }  // extern "C"

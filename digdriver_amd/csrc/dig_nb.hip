@@ -862,28 +862,6 @@ static int launch_nb3(const double* k, const double* alpha, const double* p, dou
     return DIG_OK;
 }
 
-template <typename Op>
-static int host_nb3(const double* k, const double* alpha, const double* p, double* out, int64_t n, int device)
-{
-    if (n == 0) return DIG_OK;
-    if (!k || !alpha || !p || !out || n < 0) return set_error(DIG_EINVAL, "nb3_host: null pointer or negative n");
-    DIG_HIP_TRY(hipSetDevice(device));
-    DevBuf dk, da, dp, dout;
-    const size_t bytes = (size_t)n * sizeof(double);
-    DIG_HIP_TRY(dk.alloc(bytes));
-    DIG_HIP_TRY(da.alloc(bytes));
-    DIG_HIP_TRY(dp.alloc(bytes));
-    DIG_HIP_TRY(dout.alloc(bytes));
-    DIG_HIP_TRY(hipMemcpy(dk.p, k, bytes, hipMemcpyHostToDevice));
-    DIG_HIP_TRY(hipMemcpy(da.p, alpha, bytes, hipMemcpyHostToDevice));
-    DIG_HIP_TRY(hipMemcpy(dp.p, p, bytes, hipMemcpyHostToDevice));
-    int rc = launch_nb3<Op>(dk.as<double>(), da.as<double>(), dp.as<double>(), dout.as<double>(), n, nullptr);
-    if (rc) return rc;
-    DIG_HIP_TRY(hipDeviceSynchronize());
-    DIG_HIP_TRY(hipMemcpy(out, dout.p, bytes, hipMemcpyDeviceToHost));
-    return DIG_OK;
-}
-
 }  // namespace dig
 
 using namespace dig;
@@ -894,34 +872,17 @@ int dig_nb_midp_upper(const double* k, const double* alpha, const double* p, dou
 {
     return launch_nb3<OpMidpUpper>(k, alpha, p, out, n, stream);
 }
-int dig_nb_midp_upper_host(const double* k, const double* alpha, const double* p, double* out, int64_t n, int device)
-{
-    return host_nb3<OpMidpUpper>(k, alpha, p, out, n, device);
-}
 int dig_nb_exact(const double* k, const double* alpha, const double* p, double* out, int64_t n, void* stream)
 {
     return launch_nb3<OpExact>(k, alpha, p, out, n, stream);
-}
-int dig_nb_exact_host(const double* k, const double* alpha, const double* p, double* out, int64_t n, int device)
-{
-    return host_nb3<OpExact>(k, alpha, p, out, n, device);
 }
 int dig_nb_greater(const double* k, const double* alpha, const double* p, double* out, int64_t n, void* stream)
 {
     return launch_nb3<OpGreater>(k, alpha, p, out, n, stream);
 }
-int dig_nb_greater_host(const double* k, const double* alpha, const double* p, double* out, int64_t n, int device)
-{
-    return host_nb3<OpGreater>(k, alpha, p, out, n, device);
-}
 int dig_nb_midp_twosided(const double* k, const double* alpha, const double* p, double* out, int64_t n, void* stream)
 {
     return launch_nb3<OpMidpTwo>(k, alpha, p, out, n, stream);
-}
-int dig_nb_midp_twosided_host(const double* k, const double* alpha, const double* p, double* out, int64_t n,
-                              int device)
-{
-    return host_nb3<OpMidpTwo>(k, alpha, p, out, n, device);
 }
 
 int dig_fisher(const double* p1, const double* p2, double* out, int64_t n, void* stream)
@@ -933,25 +894,6 @@ int dig_fisher(const double* p1, const double* p2, double* out, int64_t n, void*
     return DIG_OK;
 }
 
-int dig_fisher_host(const double* p1, const double* p2, double* out, int64_t n, int device)
-{
-    if (n == 0) return DIG_OK;
-    DIG_REQUIRE(p1 && p2 && out && n > 0, "non-null pointers, n >= 0");
-    DIG_HIP_TRY(hipSetDevice(device));
-    DevBuf d1, d2, dout;
-    const size_t bytes = (size_t)n * sizeof(double);
-    DIG_HIP_TRY(d1.alloc(bytes));
-    DIG_HIP_TRY(d2.alloc(bytes));
-    DIG_HIP_TRY(dout.alloc(bytes));
-    DIG_HIP_TRY(hipMemcpy(d1.p, p1, bytes, hipMemcpyHostToDevice));
-    DIG_HIP_TRY(hipMemcpy(d2.p, p2, bytes, hipMemcpyHostToDevice));
-    int rc = dig_fisher(d1.as<double>(), d2.as<double>(), dout.as<double>(), n, nullptr);
-    if (rc) return rc;
-    DIG_HIP_TRY(hipDeviceSynchronize());
-    DIG_HIP_TRY(hipMemcpy(out, dout.p, bytes, hipMemcpyDeviceToHost));
-    return DIG_OK;
-}
-
 int dig_normal_params_to_gamma(const double* mu, const double* sigma, double* alpha, double* theta, int64_t n,
                                void* stream)
 {
@@ -960,28 +902,6 @@ int dig_normal_params_to_gamma(const double* mu, const double* sigma, double* al
     hipLaunchKernelGGL(gamma_kernel, dim3(grid_for(n, kBlock)), dim3(kBlock), 0, (hipStream_t)stream, mu, sigma, alpha,
                        theta, n);
     DIG_HIP_TRY(hipGetLastError());
-    return DIG_OK;
-}
-
-int dig_normal_params_to_gamma_host(const double* mu, const double* sigma, double* alpha, double* theta, int64_t n,
-                                    int device)
-{
-    if (n == 0) return DIG_OK;
-    DIG_REQUIRE(mu && sigma && alpha && theta && n > 0, "non-null pointers, n >= 0");
-    DIG_HIP_TRY(hipSetDevice(device));
-    DevBuf dm, ds, da, dt;
-    const size_t bytes = (size_t)n * sizeof(double);
-    DIG_HIP_TRY(dm.alloc(bytes));
-    DIG_HIP_TRY(ds.alloc(bytes));
-    DIG_HIP_TRY(da.alloc(bytes));
-    DIG_HIP_TRY(dt.alloc(bytes));
-    DIG_HIP_TRY(hipMemcpy(dm.p, mu, bytes, hipMemcpyHostToDevice));
-    DIG_HIP_TRY(hipMemcpy(ds.p, sigma, bytes, hipMemcpyHostToDevice));
-    int rc = dig_normal_params_to_gamma(dm.as<double>(), ds.as<double>(), da.as<double>(), dt.as<double>(), n, nullptr);
-    if (rc) return rc;
-    DIG_HIP_TRY(hipDeviceSynchronize());
-    DIG_HIP_TRY(hipMemcpy(alpha, da.p, bytes, hipMemcpyDeviceToHost));
-    DIG_HIP_TRY(hipMemcpy(theta, dt.p, bytes, hipMemcpyDeviceToHost));
     return DIG_OK;
 }
 
@@ -1144,60 +1064,6 @@ int dig_element_stats(const double* mu, const double* sigma, const double* mu_in
                                 obs_samples, obs_indel, cj, cj_indel, out, E, C, workspace, workspace_bytes, stream, nullptr, 0);
 }
 
-int dig_element_stats_host(const double* mu, const double* sigma, const double* mu_indel, const double* sigma_indel,
-                           const double* pi_sum, const double* pi_indel, int pi_indel_per_cohort,
-                           const int32_t* obs_snv, const int32_t* obs_samples, const int32_t* obs_indel,
-                           const double* cj, const double* cj_indel, double* out, int64_t E, int64_t C, int device)
-{
-    DIG_REQUIRE(E >= 0 && C >= 0, "E, C >= 0");
-    if (E == 0 || C == 0) return DIG_OK;
-    DIG_REQUIRE(mu && sigma && pi_sum && pi_indel && obs_snv && obs_samples && obs_indel && cj && cj_indel && out,
-                "non-null pointers");
-    DIG_HIP_TRY(hipSetDevice(device));
-    const size_t n = (size_t)E * (size_t)C;
-    const size_t nd = n * sizeof(double), ni = n * sizeof(int32_t);
-    const size_t npi = (pi_indel_per_cohort ? n : (size_t)E) * sizeof(double);
-    DevBuf dmu, dsg, dmui, dsgi, dps, dpi, dk1, dk2, dk3, dcj, dcji, dout;
-    DIG_HIP_TRY(dmu.alloc(nd));
-    DIG_HIP_TRY(dsg.alloc(nd));
-    DIG_HIP_TRY(dps.alloc(nd));
-    DIG_HIP_TRY(dpi.alloc(npi));
-    DIG_HIP_TRY(dk1.alloc(ni));
-    DIG_HIP_TRY(dk2.alloc(ni));
-    DIG_HIP_TRY(dk3.alloc(ni));
-    DIG_HIP_TRY(dcj.alloc((size_t)C * sizeof(double)));
-    DIG_HIP_TRY(dcji.alloc((size_t)C * sizeof(double)));
-    DIG_HIP_TRY(dout.alloc(nd * DIG_ES_NPLANES));
-    DIG_HIP_TRY(hipMemcpy(dmu.p, mu, nd, hipMemcpyHostToDevice));
-    DIG_HIP_TRY(hipMemcpy(dsg.p, sigma, nd, hipMemcpyHostToDevice));
-    if (mu_indel) {
-        DIG_REQUIRE(sigma_indel, "sigma_indel with mu_indel");
-        DIG_HIP_TRY(dmui.alloc(nd));
-        DIG_HIP_TRY(dsgi.alloc(nd));
-        DIG_HIP_TRY(hipMemcpy(dmui.p, mu_indel, nd, hipMemcpyHostToDevice));
-        DIG_HIP_TRY(hipMemcpy(dsgi.p, sigma_indel, nd, hipMemcpyHostToDevice));
-    }
-    DIG_HIP_TRY(hipMemcpy(dps.p, pi_sum, nd, hipMemcpyHostToDevice));
-    DIG_HIP_TRY(hipMemcpy(dpi.p, pi_indel, npi, hipMemcpyHostToDevice));
-    DIG_HIP_TRY(hipMemcpy(dk1.p, obs_snv, ni, hipMemcpyHostToDevice));
-    DIG_HIP_TRY(hipMemcpy(dk2.p, obs_samples, ni, hipMemcpyHostToDevice));
-    DIG_HIP_TRY(hipMemcpy(dk3.p, obs_indel, ni, hipMemcpyHostToDevice));
-    DIG_HIP_TRY(hipMemcpy(dcj.p, cj, (size_t)C * sizeof(double), hipMemcpyHostToDevice));
-    DIG_HIP_TRY(hipMemcpy(dcji.p, cj_indel, (size_t)C * sizeof(double), hipMemcpyHostToDevice));
-    DevBuf dws;
-    const int64_t wsb = dig_element_stats_workspace(E, C);
-    if (wsb > 0) DIG_HIP_TRY(dws.alloc((size_t)wsb));
-    int rc = dig_element_stats(dmu.as<double>(), dsg.as<double>(), mu_indel ? dmui.as<double>() : nullptr,
-                               mu_indel ? dsgi.as<double>() : nullptr, dps.as<double>(), dpi.as<double>(),
-                               pi_indel_per_cohort, dk1.as<int32_t>(), dk2.as<int32_t>(), dk3.as<int32_t>(),
-                               dcj.as<double>(), dcji.as<double>(), dout.as<double>(), E, C, wsb > 0 ? dws.p : nullptr,
-                               wsb, nullptr);
-    if (rc) return rc;
-    DIG_HIP_TRY(hipDeviceSynchronize());
-    DIG_HIP_TRY(hipMemcpy(out, dout.p, nd * DIG_ES_NPLANES, hipMemcpyDeviceToHost));
-    return DIG_OK;
-}
-
 int dig_tiled_nb_test(const double* pt, int pt_per_cohort, const int32_t* k, const double* mu, const double* sigma,
                       double* pval, double* exp_out, int64_t C, int64_t n_bins, int64_t n_tiles, void* stream)
 {
@@ -1214,37 +1080,6 @@ int dig_tiled_nb_test(const double* pt, int pt_per_cohort, const int32_t* k, con
         hipLaunchKernelGGL(tiled_nb_generic_kernel, dim3(grid_for(n, kBlock)), dim3(kBlock), 0, (hipStream_t)stream, pt,
                            pt_per_cohort, k, mu, sigma, pval, exp_out, C, n_bins, n_tiles);
     DIG_HIP_TRY(hipGetLastError());
-    return DIG_OK;
-}
-
-int dig_tiled_nb_test_host(const double* pt, int pt_per_cohort, const int32_t* k, const double* mu,
-                           const double* sigma, double* pval, double* exp_out, int64_t C, int64_t n_bins,
-                           int64_t n_tiles, int device)
-{
-    DIG_REQUIRE(C >= 0 && n_bins >= 0 && n_tiles >= 0, "non-negative sizes");
-    const size_t n = (size_t)C * n_bins * n_tiles;
-    if (n == 0) return DIG_OK;
-    DIG_REQUIRE(pt && k && mu && sigma && pval && exp_out, "non-null pointers");
-    DIG_HIP_TRY(hipSetDevice(device));
-    const size_t npt = (pt_per_cohort ? n : (size_t)n_bins * n_tiles) * sizeof(double);
-    const size_t ncb = (size_t)C * n_bins * sizeof(double);
-    DevBuf dpt, dk, dmu, dsg, dpv, dex;
-    DIG_HIP_TRY(dpt.alloc(npt));
-    DIG_HIP_TRY(dk.alloc(n * sizeof(int32_t)));
-    DIG_HIP_TRY(dmu.alloc(ncb));
-    DIG_HIP_TRY(dsg.alloc(ncb));
-    DIG_HIP_TRY(dpv.alloc(n * sizeof(double)));
-    DIG_HIP_TRY(dex.alloc(n * sizeof(double)));
-    DIG_HIP_TRY(hipMemcpy(dpt.p, pt, npt, hipMemcpyHostToDevice));
-    DIG_HIP_TRY(hipMemcpy(dk.p, k, n * sizeof(int32_t), hipMemcpyHostToDevice));
-    DIG_HIP_TRY(hipMemcpy(dmu.p, mu, ncb, hipMemcpyHostToDevice));
-    DIG_HIP_TRY(hipMemcpy(dsg.p, sigma, ncb, hipMemcpyHostToDevice));
-    int rc = dig_tiled_nb_test(dpt.as<double>(), pt_per_cohort, dk.as<int32_t>(), dmu.as<double>(), dsg.as<double>(),
-                               dpv.as<double>(), dex.as<double>(), C, n_bins, n_tiles, nullptr);
-    if (rc) return rc;
-    DIG_HIP_TRY(hipDeviceSynchronize());
-    DIG_HIP_TRY(hipMemcpy(pval, dpv.p, n * sizeof(double), hipMemcpyDeviceToHost));
-    DIG_HIP_TRY(hipMemcpy(exp_out, dex.p, n * sizeof(double), hipMemcpyDeviceToHost));
     return DIG_OK;
 }
 

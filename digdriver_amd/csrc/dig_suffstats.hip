@@ -373,30 +373,4 @@ int dig_scale_factors_chunked(const double* chunk_sums, int n_chunks, const doub
     return DIG_OK;
 }
 
-int dig_scale_suffstats_host(const double* bin_mu, const uint8_t* bin_flag, int64_t N, int64_t C, double* out_sum,
-                             int device)
-{
-    DIG_REQUIRE(N >= 0 && C >= 0, "N, C >= 0");
-    if (C == 0) return DIG_OK;
-    DIG_REQUIRE(out_sum, "non-null output");
-    DIG_HIP_TRY(hipSetDevice(device));
-    DevBuf dmu, dfl, dws, dout;
-    const size_t n = (size_t)N * C;
-    DIG_HIP_TRY(dmu.alloc(n * 8));
-    DIG_HIP_TRY(dfl.alloc(n));
-    DIG_HIP_TRY(dws.alloc((size_t)dig_scale_suffstats_workspace(N, C)));
-    DIG_HIP_TRY(dout.alloc((size_t)C * 8));
-    if (n) {
-        DIG_REQUIRE(bin_mu && bin_flag, "non-null inputs");
-        DIG_HIP_TRY(hipMemcpy(dmu.p, bin_mu, n * 8, hipMemcpyHostToDevice));
-        DIG_HIP_TRY(hipMemcpy(dfl.p, bin_flag, n, hipMemcpyHostToDevice));
-    }
-    int rc = dig_scale_suffstats(dmu.as<double>(), dfl.as<uint8_t>(), N, C, dout.as<double>(), dws.p,
-                                 dig_scale_suffstats_workspace(N, C), nullptr);
-    if (rc) return rc;
-    DIG_HIP_TRY(hipDeviceSynchronize());
-    DIG_HIP_TRY(hipMemcpy(out_sum, dout.p, (size_t)C * 8, hipMemcpyDeviceToHost));
-    return DIG_OK;
-}
-
 }  // extern "C"

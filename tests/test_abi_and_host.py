@@ -1,6 +1,7 @@
 """CPU-only checks: the C-ABI library loads and exports every symbol include/dig_hip.h declares,
 host-side index construction matches the reference goldens, and the product path fails loudly
 (no CPU fallback) when no GPU is present."""
+import ctypes
 import json
 import os
 import re
@@ -98,6 +99,55 @@ def test_bad_arguments_are_reported_through_dig_last_error():
                                           None, None, None, None, None, None, None, 1, 1, 1, 0)
     assert rc == -1
     assert "n_class" in _lib.last_error()
+
+
+def test_every_host_twin_checks_its_arguments_before_touching_the_device():
+    """Each `_host` twin refuses one bad argument (a negative size, a missing pointer, or host data out of range) with
+    DIG_EINVAL and its own message, before any HIP call: no device is needed to see it."""
+    lib = _lib.load()
+    i32 = lambda *v: np.array(v, np.int32)
+    i64 = lambda *v: np.array(v, np.int64)
+    buf = np.zeros(4096)                                   # any non-null pointer; the checks fail before it is read
+    cases = [  # (twin, {argument index: value}, message fragment)
+        ("dig_nb_midp_upper_host", {4: -1}, "nb3_host: null pointer or negative n"),
+        ("dig_nb_exact_host", {4: -1}, "nb3_host: null pointer or negative n"),
+        ("dig_nb_greater_host", {4: -1}, "nb3_host: null pointer or negative n"),
+        ("dig_nb_midp_twosided_host", {4: 3}, "nb3_host: null pointer or negative n"),
+        ("dig_fisher_host", {3: 3}, "non-null pointers, n >= 0"),
+        ("dig_normal_params_to_gamma_host", {4: -1}, "non-null pointers, n >= 0"),
+        ("dig_element_stats_host", {13: -1, 14: 2}, "E, C >= 0"),
+        ("dig_element_stats_host", {**{i: buf for i in range(13) if i != 6}, 3: None, 13: 2, 14: 2}, "sigma_indel with mu_indel"),
+        ("dig_tiled_nb_test_host", {7: 1, 8: 1, 9: 1}, "non-null pointers"),
+        ("dig_accumulate_elements_host", {8: 1, 20: -1}, "N, E, C >= 0"),
+        ("dig_accumulate_elements_host", {**{i: buf for i in range(20)}, 5: i64(0, 1), 6: i32(5), 8: 1, 20: 4, 21: 1, 22: 1},
+         "ov_idx within [0, N)"),
+        ("dig_gene_stats_host", {5: 4, 14: -1}, "G, C >= 0"),
+        ("dig_scale_suffstats_host", {2: 5, 3: 2, 4: buf}, "non-null inputs"),
+        ("dig_gather_bins_host", {2: 1, 3: 0, 4: 1}, "sizes"),
+        ("dig_gather_bins_host", {0: buf, 2: 2, 3: 1, 4: 1, 5: i64(7), 6: 1, 8: 1, 9: buf}, "bin_rows within [0, N)"),
+        ("dig_count_contexts_host", {1: 4, 9: -1}, "R >= 0, n_words >= 2 (pad words), n_chrom >= 0"),
+        ("dig_count_contexts_host", {**{i: buf for i in (0, 2, 3, 6, 7, 8, 10)}, 1: 4, 4: 1, 5: i32(1), 9: 1},
+         "region chromosome index within [0, n_chrom)"),
+        ("dig_count_contexts2_host", {1: 27, 14: 1}, "R, n_int, n_chrom >= 0, n_words2 >= 28 (pad words)"),
+        ("dig_element_pipeline_host", {25: 1, 26: -1, 27: 1}, "N, E, C >= 0"),
+        ("dig_gene_pipeline_host", {25: 1, 26: 1, 27: 1}, "non-null accumulation inputs"),
+        ("dig_base_tile_probs_host", {1: 1, 8: 1}, "non-negative sizes, n_words >= 2 (pad words)"),
+        ("dig_base_tile_probs_ctx_host", {1: 4, 8: 1, 11: 3}, "n_up = n_down = 1 or 2"),
+        ("dig_tile_mut_counts_host", {8: 0, 9: 1, 10: 1, 11: 1}, "non-negative sizes, binsize >= 1"),
+        ("dig_tile_mut_counts_host", {**{i: buf for i in (3, 5, 6, 7, 12)}, 0: i32(0), 1: i32(3), 2: 1, 4: 1, 8: 1, 9: 1, 10: 2, 11: 1},
+         "pairs inside the mutation / region tables"),
+        ("dig_overlap_join_count_host", {7: -1}, "sizes >= 0"),
+        ("dig_overlap_join_fill_host", {3: 1, 7: 1, 9: -1}, "sizes >= 0"),
+    ]
+    for name, over, fragment in cases:
+        args = [None if t is ctypes.c_void_p else 0 for t in _lib._SIGNATURES[name]]
+        for i, v in over.items():
+            args[i] = _lib.host_ptr(v) if isinstance(v, np.ndarray) else v
+        rc = getattr(lib, name)(*args)
+        msg = _lib.last_error()
+        assert rc == -1, (name, rc, msg)
+        assert fragment in msg, (name, msg)
+        assert fragment.startswith("nb3_host") or name in msg, (name, msg)
 
 
 def test_native_result_writer_writes_the_bytes_pandas_writes(tmp_path):

@@ -1135,6 +1135,107 @@ def test_host_twins_of_pipeline_tiles_and_join(torch_dev):
         assert np.array_equal(out_h[j], st_g[name].cpu().numpy(), equal_nan=True), name
 
 
+def _twin_agrees_with_device(dev, name, args, ws_bytes=None):
+    """`name`_host on the numpy arrays of `args` and `name` on device copies of them (None stays NULL, scalars pass as they
+    are, a workspace of ws_bytes goes in front of the stream): every array comes back with the same bits.  Returns the
+    host twin's arrays."""
+    import torch
+    from digdriver_amd import _lib
+    is_arr = lambda a: isinstance(a, np.ndarray)
+    host = [a.copy() if is_arr(a) else a for a in args]
+    _lib.call(name + "_host", *[_lib.host_ptr(a) if is_arr(a) else a for a in host], 0)
+    devs = [torch.as_tensor(a, device=dev) if is_arr(a) else a for a in args]
+    ws = [] if ws_bytes is None else [torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev), ws_bytes]
+    _lib.call(name, *[_lib.dev_ptr(t) if isinstance(t, torch.Tensor) else t for t in devs + ws], _lib.stream_ptr())
+    torch.cuda.synchronize()
+    for j, (h, d) in enumerate(zip(host, devs)):
+        if is_arr(h):
+            assert np.array_equal(h, d.cpu().numpy(), equal_nan=True), (name, j)
+    return host
+
+
+def test_staged_host_twins_match_their_device_entry_points(torch_dev):
+    """The `_host` twins not covered above against their device entry points on small inputs, bit for bit, through their
+    optional inputs: the NB tails, Fisher, gamma; accumulation with one and four classes, with and without gene_length;
+    element statistics with and without indel parameters, pi_indel per element and per cohort; gene statistics with and
+    without the indel block; tiled tests with a shared and a per-cohort pt; scale sums with N > 0 and N == 0; gathers with
+    and without a track list; both context-count forms on genomes with and without runs of N."""
+    from bench import make_workload
+    from digdriver_amd import _lib, engine
+    from digdriver_amd.data_tools.genome import PackedGenome
+    agree = lambda name, *args, ws=None: _twin_agrees_with_device(torch_dev, name, list(args), ws)
+    rng = np.random.default_rng(12)
+    nan = lambda *shape: np.full(shape, np.nan)
+    neg = lambda *shape: np.full(shape, -7, np.int32)
+    # ---- elementwise ----
+    n = 3001
+    k, alpha, p = rng.poisson(4.0, n).astype(np.float64), rng.gamma(2.0, 3.0, n), rng.uniform(0.05, 0.95, n)
+    for tail in ("dig_nb_midp_upper", "dig_nb_exact", "dig_nb_greater", "dig_nb_midp_twosided"):
+        agree(tail, k, alpha, p, nan(n), n)
+    agree("dig_fisher", rng.uniform(1e-9, 1.0, n), rng.uniform(1e-9, 1.0, n), nan(n), n)
+    agree("dig_normal_params_to_gamma", rng.gamma(3.0, 2.0, n), rng.uniform(0.1, 5.0, n), nan(n), nan(n), n)
+    # ---- accumulation ----
+    E, C, N = 300, 3, 400
+    w = make_workload(n_bins=N, n_elements=E, n_cohorts=C, seed=13)
+    c = lambda key, dt: np.ascontiguousarray(w[key], dtype=dt)
+    bins = [c("bin_mu", np.float64), c("bin_std", np.float64), c("bin_y", np.int32), c("bin_flag", np.uint8), c("bin_ctx", np.int32),
+            c("ov_ptr", np.int64), c("ov_idx", np.int32)]
+    L4 = np.repeat(rng.poisson(5.0, (E, 4, 64)), 3, axis=2).astype(np.int32)
+    glen = rng.integers(300, 9000, E).astype(np.int32)
+    acc = {}
+    for n_class, L in ((1, c("L", np.int32)), (4, L4)):
+        for gl in (None, glen):
+            res = agree("dig_accumulate_elements", *bins, L, n_class, c("strand_minus", np.uint8), gl, c("d_pr", np.float64),
+                        nan(E, C), nan(E, C), neg(E, C), neg(E, C), nan(E, n_class, C), neg(E), neg(E), nan(E), N, E, C,
+                        ws=_lib.workspace_bytes("accumulate", E, C))
+            acc[n_class, gl is not None] = res[12:20]
+    # ---- element statistics ----
+    MU, SIGMA, _, _, P, _, _, P_INDEL = acc[1, False]
+    obs = [c("obs_snv", np.int32), c("obs_samples", np.int32), c("obs_indel", np.int32), c("cj", np.float64), c("cj_indel", np.float64)]
+    pi_cohort = np.ascontiguousarray(P_INDEL[:, None] * rng.uniform(0.5, 2.0, (E, C)))
+    for mu_i, sg_i in ((None, None), (MU * 0.3, SIGMA * 0.5)):
+        for per_cohort, pi_i in ((0, P_INDEL), (1, pi_cohort)):
+            agree("dig_element_stats", MU, SIGMA, mu_i, sg_i, np.ascontiguousarray(P[:, 0, :]), pi_i, per_cohort, *obs, nan(7, E, C), E, C,
+                  ws=_lib.workspace_bytes("element_stats", E, C))
+    # ---- gene statistics ----
+    MUg, SIGMAg, _, _, Pg, _, _, PIg = acc[4, True]
+    obs5, ns6 = rng.poisson(3.0, (E, 5, C)).astype(np.int32), rng.poisson(2.0, (E, 6, C)).astype(np.int32)
+    ti = rng.uniform(0.05, 0.3, C)
+    agree("dig_gene_stats", MUg, SIGMAg, None, None, Pg, 4, PIg, 0, obs5, ns6, obs[3], ti, 1, nan(22, E, C), E, C)
+    agree("dig_gene_stats", MUg, SIGMAg, MUg * 0.3, SIGMAg * 0.5, Pg, 4, PIg, 0, obs5, ns6, obs[3], ti, 1, nan(22, E, C), E, C)
+    agree("dig_gene_stats", MUg, SIGMAg, None, None, Pg, 4, None, 0, obs5, ns6, obs[3], None, 0, nan(22, E, C), E, C)
+    # ---- tiled tests ----
+    nb, nt = 40, 20
+    kt = rng.poisson(1.0, (C, nb, nt)).astype(np.int32)
+    mut = rng.uniform(5.0, 40.0, (C, nb))
+    sgt = mut * rng.uniform(0.2, 0.8, (C, nb))
+    for per_cohort, pt in ((0, rng.dirichlet(np.ones(nt), nb)), (1, rng.dirichlet(np.ones(nt), (C, nb)))):
+        agree("dig_tiled_nb_test", pt, per_cohort, kt, mut, sgt, nan(C, nb, nt), nan(C, nb, nt), C, nb, nt)
+    # ---- scale sums ----
+    agree("dig_scale_suffstats", bins[0], bins[3], N, C, nan(C), ws=_lib.workspace_bytes("suffstats", N, C))
+    agree("dig_scale_suffstats", None, None, 0, C, nan(C), ws=_lib.workspace_bytes("suffstats", 0, C))
+    # ---- gathers ----
+    Nx, Lx, Tx, B = 50, 7, 6, 33
+    rows = rng.integers(0, Nx, B).astype(np.int64)
+    agree("dig_gather_bins", rng.normal(size=(Nx, Lx, Tx)), 1, Nx, Lx, Tx, rows, B, np.array([5, 0, 3], np.int32), 3,
+          np.full((B, Lx, 3), np.nan, np.float32), 0, 0)                                  # f64 -> f32, three tracks
+    agree("dig_gather_bins", rng.integers(-3000, 3000, (Nx, Lx, Tx)).astype(np.int16), 2, Nx, Lx, Tx, rows, B, None, Tx,
+          np.zeros((B, Tx, Lx), np.int16), 3, 1)                                          # i16 -> bf16, every track, transposed
+    # ---- context counts: n_int == 0 and n_int > 0 ----
+    for p_n, n1, n2 in ((0.0, 6000, 2000), (0.05, 6007, 2003)):      # whole words of ACGT: no run of other letters, no padding
+        seqs = {"c1": "".join(rng.choice(list("ACGTN"), n1, p=[(1 - p_n) / 4] * 4 + [p_n])), "c2": "".join(rng.choice(list("ACGT"), n2))}
+        genome = PackedGenome.from_sequences(seqs)
+        assert (genome.two_bit()[1].size > 0) == (p_n > 0)
+        chroms = ["c1"] * 40 + ["c2"] * 10
+        starts = np.array([int(rng.integers(0, len(seqs[ch]))) for ch in chroms], np.int64)
+        ends = np.minimum(starts + rng.integers(0, 700, len(chroms)), [len(seqs[ch]) for ch in chroms])
+        minus = rng.uniform(size=len(chroms)) < 0.5
+        for form in ("2bit", "4bit"):
+            dv = engine.count_contexts(genome, chroms, starts, ends, minus, device=0, form=form).cpu().numpy()
+            assert np.array_equal(engine.count_contexts(genome, chroms, starts, ends, minus, on_device=False, form=form), dv), form
+            assert dv.sum() > 0
+
+
 def test_gene_pipeline_all_cohorts_against_oracle(torch_dev):
     """dig_gene_pipeline: genic_model's accumulation (four class columns of L, P_INDEL = GENE_LENGTH / R_SIZE) + the gene
     statistics block (six classes x count / sample tests, indel test, Fisher on TRUNC + INDEL) for G genes x C cohorts in one
