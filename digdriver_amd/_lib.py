@@ -78,6 +78,14 @@ _SIGNATURES = {
     "dig_count_contexts_host": [_vp, _i64, _vp, _vp, _int, _vp, _vp, _vp, _vp, _i64, _vp, _int],
     "dig_count_contexts2": [_vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _int, _vp, _vp, _vp, _vp, _i64, _vp, _vp],
     "dig_count_contexts2_host": [_vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _int, _vp, _vp, _vp, _vp, _i64, _vp, _int],
+    "dig_mutation_contexts": [_vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _int, _vp, _vp, _vp, _i64, _int, _int, _int, _vp, _vp, _vp,
+                              _i64, _vp],
+    "dig_mutation_contexts_host": [_vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _int, _vp, _vp, _vp, _i64, _int, _int, _int, _vp,
+                                   _vp, _int],
+    "dig_mutctx_file_parse_host": [ctypes.c_char_p, _vp, _vp, _vp],
+    "dig_mutctx_file_fetch_host": [_vp, _vp, _vp, _vp],
+    "dig_mutctx_file_write_host": [_vp, ctypes.c_char_p, _vp, _vp, _vp, _vp, _int, _int],
+    "dig_mutctx_file_free_host": [_vp],
     "dig_write_tsv_host": [ctypes.c_char_p, ctypes.c_char_p, _vp, _vp, _i64, _int, _vp, _vp, _int],
     "dig_mutation_file_parse_host": [ctypes.c_char_p, _vp, _vp, _vp, _vp],
     "dig_mutation_file_fetch_host": [_vp] * 9,
@@ -122,6 +130,7 @@ _SIZE_QUERIES = {
     "dig_element_records_bytes": [_i64, _i64],
     "dig_bh_workspace": [_i64, _i64],
     "dig_bh_ragged_workspace": [_vp, _i64],
+    "dig_mutation_contexts_workspace": [_i64],
 }
 
 ABI_VERSION = 12         # include/dig_hip.h: DIG_ABI_VERSION

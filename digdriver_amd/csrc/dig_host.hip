@@ -302,6 +302,31 @@ int dig_count_contexts2_host(const uint32_t* words2, int64_t n_words2, const int
                    nullptr);
 }
 
+int dig_mutation_contexts_host(const uint32_t* words2, int64_t n_words2, const int64_t* nint_start, const int64_t* nint_end, int64_t n_int,
+                               const int32_t* nint_bucket, int64_t n_buckets, const int64_t* chrom_off, const int64_t* chrom_len,
+                               int n_chrom, const int32_t* row_chrom, const int64_t* row_start, const uint8_t* row_ref, int64_t n_rows,
+                               int n_up, int n_down, int collapse, uint8_t* status, uint32_t* context, int device)
+{
+    DIG_REQUIRE(n_rows >= 0 && n_rows <= INT32_MAX, "0 <= n_rows < 2^31");
+    DIG_REQUIRE(n_up >= 0 && n_down >= 0 && n_up + n_down + 1 <= 16, "n_up, n_down >= 0 and n_up + n_down + 1 <= 16");
+    DIG_REQUIRE(n_words2 >= 28 && n_chrom >= 0 && n_int >= 0, "n_int, n_chrom >= 0, n_words2 >= 28 (pad words)");
+    if (n_rows == 0) return DIG_OK;
+    DIG_REQUIRE(words2 && chrom_off && chrom_len && row_chrom && row_start && row_ref && status && context, "non-null pointers");
+    DIG_REQUIRE(n_int == 0 || (nint_start && nint_end && nint_bucket && n_buckets >= 1), "interval list with its bucket index");
+    for (int64_t r = 0; r < n_rows; ++r) DIG_REQUIRE(row_chrom[r] >= 0 && row_chrom[r] < n_chrom, "row chromosome index within [0, n_chrom)");
+    for (int c = 0; c < n_chrom; ++c)
+        DIG_REQUIRE(chrom_off[c] >= 0 && chrom_off[c] + chrom_len[c] + 64 <= (n_words2 - 24) * 16, "chromosomes inside the genome array");
+    for (int64_t j = 0; j < n_int; ++j)
+        DIG_REQUIRE(nint_start[j] < nint_end[j] && (j == 0 || nint_end[j - 1] < nint_start[j]), "intervals sorted, disjoint, not touching");
+    const size_t nc = std::max(n_chrom, 1);
+    const int64_t ws = dig_mutation_contexts_workspace(n_rows);
+    Staging st(device);
+    return st.call(dig_mutation_contexts, st.in(words2, n_words2), n_words2, st.in(nint_start, n_int), st.in(nint_end, n_int), n_int,
+                   st.in(nint_bucket, n_int ? n_buckets : 0), n_buckets, st.in(chrom_off, nc), st.in(chrom_len, nc), n_chrom,
+                   st.in(row_chrom, n_rows), st.in(row_start, n_rows), st.in(row_ref, n_rows), n_rows, n_up, n_down, collapse,
+                   st.out(status, n_rows), st.out(context, n_rows), st.scratch(ws), ws, nullptr);
+}
+
 int dig_element_pipeline_host(const double* bin_mu, const double* bin_std, const int32_t* bin_y, const uint8_t* bin_flag,
                               const int32_t* bin_ctx, const int64_t* ov_ptr, const int32_t* ov_idx, const int32_t* L,
                               const uint8_t* strand_minus, const int32_t* gene_length, const double* d_pr,

@@ -294,6 +294,17 @@ inline int64_t autosome(std::string_view s)      // "1" .. "22" -> 1 .. 22, else
     return -1;
 }
 
+// the spellings of "missing" that pandas.read_csv turns into NaN by default
+inline bool is_na_token(std::string_view s)
+{
+    static const std::string_view kNa[] = {"", "#N/A", "#N/A N/A", "#NA", "-1.#IND", "-1.#QNAN", "-NaN", "-nan", "1.#IND", "1.#QNAN",
+                                           "<NA>", "N/A", "NA", "NULL", "NaN", "None", "n/a", "nan", "null"};
+    if (s.size() > 8) return false;
+    for (const std::string_view na : kNa)
+        if (s == na) return true;
+    return false;
+}
+
 }  // namespace
 
 extern "C" {
@@ -365,12 +376,9 @@ int dig_mutation_file_parse_host(const char* path, void** handle, int64_t* n_row
     if (n_fields != 8 && n_fields != 10 && n_fields != 11) return DIG_OK;
     // pandas.read_csv turns these spellings of "missing" into NaN (and the reference's groupby then drops such samples): a file
     // with one of them in a label column goes the Python path, which reads it with pandas
-    static const char* const kNa[] = {"", "#N/A", "#N/A N/A", "#NA", "-1.#IND", "-1.#QNAN", "-NaN", "-nan", "1.#IND", "1.#QNAN", "<NA>",
-                                      "N/A", "NA", "NULL", "NaN", "None", "n/a", "nan", "null"};
     for (const Interner* in : {&ref, &alt, &samp, &gene, &annot})
         for (const std::string_view lab : in->labels)
-            for (const char* na : kNa)
-                if (lab == std::string_view(na)) return DIG_OK;
+            if (is_na_token(lab)) return DIG_OK;
     int64_t indel_id = -1;
     {
         auto it = annot.ids.find(std::string_view("INDEL"));
@@ -510,6 +518,240 @@ int dig_mutation_file_flags_host(void* handle, int64_t* first_row, int64_t* firs
 int dig_mutation_file_free_host(void* handle)
 {
     delete static_cast<MutFile*>(handle);
+    return DIG_OK;
+}
+
+}  // extern "C"
+
+// =======================================================================================
+// Raw mutation calls -> the annotated ten-column file (addMutationContext; host code only).
+//
+// DigPreprocess.py addMutationContext reads an 8-column file with pandas (read_mutation_file: autosomes "1" .. "22" only, INDEL
+// rows de-duplicated on CHROM START END REF ALT GENE and put behind the others), splits off the rows whose ANNOT contains
+// "INDEL", groups the rest by CHROM, gives them MUT_TYPE and CONTEXT (sequence_tools.py:130-222) and writes the frame with
+// to_csv(sep="\t", index=False, header=False).  For a file pandas would echo byte for byte -- no NaN spelling, quote, CR, NUL or
+// non-ASCII byte, exactly 8 fields per line, no empty line, START / END integers in canonical form -- the same bytes come from
+// here: parse hands the grouped SNV rows to the context kernel, write puts each kept row out as its input fields, MUT_TYPE and
+// CONTEXT (indel rows: the first seven fields, "INDEL", their ANNOT as MUT_TYPE, "."), stably sorted by (CHROM, START, END)
+// when there is an indel.  Any other file reports *n_snv = -1 and no handle: the caller takes the pandas path.
+// =======================================================================================
+#include <unordered_set>
+
+namespace {
+
+struct CtxRow {
+    int64_t pos;          // the line's first byte
+    int64_t start, end;
+    uint32_t len;         // bytes of the line without its newline
+    int16_t chrom;
+    uint8_t ref;          // the REF code of dig_mutctx_file_fetch_host
+};
+
+struct CtxFile {
+    std::string buf;
+    std::vector<CtxRow> rows;
+    std::vector<uint32_t> snv, indel;        // rows of the two branches, SNV rows grouped by CHROM
+};
+
+inline bool canonical_i64(std::string_view s, int64_t& out)    // what int(...) then str(...) gives back unchanged
+{
+    if (s.empty() || s.size() > 18) return false;
+    const size_t i = s[0] == '-' ? 1 : 0;
+    if (i == s.size() || (s[i] == '0' && (s.size() > i + 1 || i == 1))) return false;
+    return parse_i64(s, out);
+}
+
+inline int split8(std::string_view line, std::string_view* f)    // number of tab-separated fields; the first 8 in f
+{
+    int n = 0;
+    size_t a = 0;
+    for (;;) {
+        const size_t t = line.find('\t', a);
+        const size_t e = t == std::string_view::npos ? line.size() : t;
+        if (n < 8) f[n] = line.substr(a, e - a);
+        ++n;
+        if (t == std::string_view::npos) return n;
+        a = t + 1;
+    }
+}
+
+}  // namespace
+
+extern "C" {
+
+int dig_mutctx_file_parse_host(const char* path, void** handle, int64_t* n_snv, int64_t* n_indel)
+{
+    DIG_REQUIRE(path && handle && n_snv && n_indel, "non-null arguments");
+    *handle = nullptr;
+    *n_snv = -1;
+    *n_indel = 0;
+    std::unique_ptr<CtxFile> m(new CtxFile());
+    {
+        FILE* f = fopen(path, "rb");
+        if (!f) return dig::set_error(DIG_EINVAL, "dig_mutctx_file_parse_host: cannot open %s", path);
+        fseek(f, 0, SEEK_END);
+        const long sz = ftell(f);
+        fseek(f, 0, SEEK_SET);
+        m->buf.resize(sz > 0 ? (size_t)sz : 0);
+        const size_t got = m->buf.empty() ? 0 : fread(&m->buf[0], 1, m->buf.size(), f);
+        fclose(f);
+        if (got != m->buf.size()) return dig::set_error(DIG_EINVAL, "dig_mutctx_file_parse_host: short read of %s", path);
+    }
+    const std::string& buf = m->buf;
+    for (const char c : buf)                                         // gzip, quoting, CR, NUL, non-ASCII: the pandas path
+        if (c == '"' || c == '\r' || c == '\0' || (unsigned char)c >= 0x80) return DIG_OK;
+    if (buf.empty()) return DIG_OK;
+    std::vector<uint32_t> plain, indel_exact;                        // read_mutation_file's two parts (get_unique_indels)
+    std::unordered_set<std::string> seen;                            // INDEL keys: CHROM START END REF ALT GENE
+    std::vector<std::string_view> annot;
+    size_t p = 0;
+    while (p < buf.size()) {
+        size_t nl = buf.find('\n', p);
+        if (nl == std::string::npos) nl = buf.size();
+        const std::string_view line(buf.data() + p, nl - p);
+        if (line.empty() || line.size() >= ((size_t)1 << 32)) return DIG_OK;
+        std::string_view f[8];
+        if (split8(line, f) != 8) return DIG_OK;
+        for (const std::string_view& x : f)
+            if (is_na_token(x)) return DIG_OK;
+        CtxRow r;
+        if (!canonical_i64(f[1], r.start) || !canonical_i64(f[2], r.end)) return DIG_OK;
+        r.pos = (int64_t)p;
+        r.len = (uint32_t)line.size();
+        r.chrom = (int16_t)autosome(f[0]);
+        r.ref = 255;                                                 // REF of more than one letter: never matches
+        if (f[3].size() == 1) {                                      // ACGT -> 0-3, another letter as itself (the caller checks it)
+            const char c = f[3][0];
+            r.ref = c == 'A' ? 0 : c == 'C' ? 1 : c == 'G' ? 2 : c == 'T' ? 3 : (uint8_t)c > 4 ? (uint8_t)c : 255;
+        }
+        p = nl + 1;
+        if (r.chrom < 0 || f[0].size() > 2) continue;                // CHROM exactly "1" .. "22"
+        if (m->rows.size() >= (size_t)INT32_MAX) return DIG_OK;
+        const uint32_t id = (uint32_t)m->rows.size();
+        m->rows.push_back(r);
+        annot.push_back(f[7]);
+        if (f[7] == "INDEL") {
+            std::string key(line.data(), (size_t)(f[4].data() + f[4].size() - line.data()));
+            key.push_back('\t');
+            key.append(f[6].data(), f[6].size());
+            if (seen.insert(std::move(key)).second) indel_exact.push_back(id);
+        } else {
+            plain.push_back(id);
+        }
+    }
+    // add_context_to_mutations: ANNOT containing "INDEL" -> the indel branch; the rest grouped by CHROM, file order inside
+    std::vector<uint32_t> snv;
+    for (const auto* part : {&plain, &indel_exact})
+        for (const uint32_t id : *part) (annot[id].find("INDEL") != std::string_view::npos ? m->indel : snv).push_back(id);
+    size_t first[24] = {0};                                          // a counting sort by CHROM (stable)
+    for (const uint32_t id : snv) ++first[m->rows[id].chrom + 1];
+    for (int c = 1; c < 24; ++c) first[c] += first[c - 1];
+    m->snv.resize(snv.size());
+    for (const uint32_t id : snv) m->snv[first[m->rows[id].chrom]++] = id;
+    *n_snv = (int64_t)m->snv.size();
+    *n_indel = (int64_t)m->indel.size();
+    *handle = m.release();
+    return DIG_OK;
+}
+
+int dig_mutctx_file_fetch_host(void* handle, int32_t* chrom, int64_t* start, uint8_t* ref)
+{
+    DIG_REQUIRE(handle, "a handle of dig_mutctx_file_parse_host");
+    const CtxFile* m = static_cast<const CtxFile*>(handle);
+    DIG_REQUIRE(m->snv.empty() || (chrom && start && ref), "non-null arrays of n_snv elements");
+    for (size_t k = 0; k < m->snv.size(); ++k) {
+        const CtxRow& r = m->rows[m->snv[k]];
+        chrom[k] = r.chrom;
+        start[k] = r.start;
+        ref[k] = r.ref;
+    }
+    return DIG_OK;
+}
+
+int dig_mutctx_file_write_host(void* handle, const char* path, const uint8_t* status, const uint32_t* context, const char* host_text,
+                               const int64_t* host_off, int n_up, int n_down)
+{
+    DIG_REQUIRE(handle && path, "a handle of dig_mutctx_file_parse_host and a path");
+    DIG_REQUIRE(n_up >= 0 && n_down >= 0 && n_up + n_down + 1 <= 16, "n_up, n_down >= 0 and n_up + n_down + 1 <= 16");
+    const CtxFile* m = static_cast<const CtxFile*>(handle);
+    const size_t ns = m->snv.size();
+    DIG_REQUIRE(ns == 0 || (status && context), "status and context arrays of n_snv elements");
+    // the output rows: kept SNV rows (group order), then the indel branch; each with its context text
+    struct Out {
+        int64_t start, end;   // the sort key with chrom
+        int64_t ctx;          // offset into host_text, or -1 - (k: context[k] is the code)
+        uint32_t row;
+        int16_t chrom;
+        int16_t ctx_len;      // -1: an indel row
+    };
+    std::vector<Out> out;
+    out.reserve(ns + m->indel.size());
+    int64_t h = 0;
+    for (size_t k = 0; k < ns; ++k) {
+        if (status[k] == DIG_MC_KEPT) {
+            const CtxRow& r = m->rows[m->snv[k]];
+            out.push_back(Out{r.start, r.end, -1 - (int64_t)k, m->snv[k], r.chrom, (int16_t)(n_up + n_down + 1)});
+        } else if (status[k] == DIG_MC_HOST) {
+            DIG_REQUIRE(host_text && host_off, "the host-resolved contexts of the DIG_MC_HOST rows");
+            const int64_t a = host_off[h], b = host_off[h + 1];
+            ++h;
+            DIG_REQUIRE(b - a <= 16, "host contexts of at most 16 letters");
+            const CtxRow& r = m->rows[m->snv[k]];
+            if (b > a) out.push_back(Out{r.start, r.end, a, m->snv[k], r.chrom, (int16_t)(b - a)});
+        }
+    }
+    for (const uint32_t id : m->indel) out.push_back(Out{m->rows[id].start, m->rows[id].end, 0, id, m->rows[id].chrom, -1});
+    if (!m->indel.empty())
+        std::stable_sort(out.begin(), out.end(), [](const Out& x, const Out& y) {
+            if (x.chrom != y.chrom) return x.chrom < y.chrom;
+            if (x.start != y.start) return x.start < y.start;
+            return x.end < y.end;
+        });
+    FILE* f = fopen(path, "wb");
+    if (!f) return dig::set_error(DIG_EINVAL, "dig_mutctx_file_write_host: cannot open %s for writing", path);
+    std::string text;
+    text.reserve((size_t)1 << 24);
+    bool ok = true;
+    static const char kBase[4] = {'A', 'C', 'G', 'T'};
+    for (const Out& o : out) {
+        const CtxRow& r = m->rows[o.row];
+        const std::string_view line(m->buf.data() + r.pos, r.len);
+        std::string_view fl[8];
+        split8(line, fl);
+        if (o.ctx_len < 0) {                                         // CHROM .. GENE, "INDEL", ANNOT as MUT_TYPE, "."
+            text.append(line.data(), (size_t)(fl[7].data() - line.data()));
+            text.append("INDEL\t");
+            text.append(fl[7].data(), fl[7].size());
+            text.append("\t.\n");
+        } else {
+            text.append(line.data(), line.size());
+            text.push_back('\t');
+            text.append(fl[3].data(), fl[3].size());
+            text.push_back('>');
+            text.append(fl[4].data(), fl[4].size());
+            text.push_back('\t');
+            if (o.ctx < 0) {
+                const uint32_t code = context[-1 - o.ctx];
+                for (int k = 0; k < o.ctx_len; ++k) text.push_back(kBase[(code >> (2 * k)) & 3u]);
+            } else {
+                text.append(host_text + o.ctx, (size_t)o.ctx_len);
+            }
+            text.push_back('\n');
+        }
+        if (text.size() >= ((size_t)1 << 24)) {
+            ok = ok && fwrite(text.data(), 1, text.size(), f) == text.size();
+            text.clear();
+        }
+    }
+    ok = ok && fwrite(text.data(), 1, text.size(), f) == text.size();
+    ok = (fclose(f) == 0) && ok;
+    if (!ok) return dig::set_error(DIG_EINVAL, "dig_mutctx_file_write_host: short write to %s", path);
+    return DIG_OK;
+}
+
+int dig_mutctx_file_free_host(void* handle)
+{
+    delete static_cast<CtxFile*>(handle);
     return DIG_OK;
 }
 

@@ -4,6 +4,9 @@ The reference reads sequence through pysam.FastaFile per region (sequence_tools.
 Here the FASTA is parsed once into the 4-bit layout of include/dig_hip.h (A=0 C=1 G=2 T=3, anything else 4; eight
 bases per 32-bit word, base 0 in the low nibble; chromosomes word-aligned; one all-N pad word at either end), cached
 as an .npz next to the FASTA if the directory is writable, and uploaded to HBM once (hg19: 1.55 GB).
+Both packed forms store every letter other than ACGT as one code; the positions and upper-case letters of those other than
+ACGTN (IUPAC codes such as R, M) are kept in a small side table, so that letters() gives back the sequence as
+fasta.fetch(...).upper() does.
 """
 import gzip
 import os
@@ -14,15 +17,25 @@ _CODE = np.full(256, 4, np.uint8)
 for _i, _ch in enumerate("ACGT"):
     _CODE[ord(_ch)] = _i
     _CODE[ord(_ch.lower())] = _i
+_OTHER = np.ones(256, bool)                   # letters other than ACGTN, either case
+for _ch in "ACGTNacgtn":
+    _OTHER[ord(_ch)] = False
+_UPPER = np.arange(256, dtype=np.uint8)
+_UPPER[ord("a"):ord("z") + 1] -= 32
+_LETTER = np.frombuffer(b"ACGTN", np.uint8)
 
 
 class PackedGenome:
-    def __init__(self, names, offsets, lengths, words):
+    def __init__(self, names, offsets, lengths, words, other_pos=None, other_letter=None):
         self.names = list(names)
         self.index = {n: i for i, n in enumerate(self.names)}
         self.offsets = np.asarray(offsets, np.int64)     # in bases, counted from word 1, multiples of 8
         self.lengths = np.asarray(lengths, np.int64)
         self.words = np.ascontiguousarray(words, np.uint32)
+        # the side table: sorted positions (offset + position) and upper-case letters of everything other than ACGTN; None for a
+        # genome built without it (slab())
+        self.other_pos = None if other_pos is None else np.asarray(other_pos, np.int64)
+        self.other_letter = None if other_letter is None else np.asarray(other_letter, np.uint8)
         self._dev = {}
 
     # ---- construction ----------------------------------------------------------------------
@@ -36,24 +49,30 @@ class PackedGenome:
             lengths.append(len(s))
             total += (len(s) + 7) // 8 * 8
         nib = np.full(total + 16, 4, np.uint8)            # + one pad word (8 nibbles) at either end
+        other_pos, other_letter = [], []
         for n, o in zip(names, offsets):
             s = seqs[n]
             b = np.frombuffer(s.encode() if isinstance(s, str) else bytes(s), np.uint8)
             nib[8 + o: 8 + o + len(b)] = _CODE[b]
+            k = np.flatnonzero(_OTHER[b])
+            other_pos.append(o + k)
+            other_letter.append(_UPPER[b[k]])
         n8 = nib.reshape(-1, 8).astype(np.uint32)
         words = np.zeros(n8.shape[0], np.uint32)
         for k in range(8):
             words |= n8[:, k] << np.uint32(4 * k)
-        return cls(names, offsets, lengths, words)
+        return cls(names, offsets, lengths, words, np.concatenate(other_pos or [np.zeros(0, np.int64)]).astype(np.int64),
+                   np.concatenate(other_letter or [np.zeros(0, np.uint8)]))
 
     @classmethod
     def from_fasta(cls, f_fasta, cache=True):
         f_cache = f_fasta + ".dig4.npz"
         if cache and os.path.exists(f_cache) and os.path.getmtime(f_cache) >= os.path.getmtime(f_fasta):
             d = np.load(f_cache, allow_pickle=False)
-            g = cls([str(n) for n in d["names"]], d["offsets"], d["lengths"], d["words"])
-            g._cache2 = f_fasta + ".dig2.npz"
-            return g
+            if "other_pos" in d.files:                    # (a cache written before the side table existed is repacked)
+                g = cls([str(n) for n in d["names"]], d["offsets"], d["lengths"], d["words"], d["other_pos"], d["other_letter"])
+                g._cache2 = f_fasta + ".dig2.npz"
+                return g
         seqs, name, parts = {}, None, []
         opener = gzip.open if f_fasta.endswith(".gz") else open
         with opener(f_fasta, "rb") as f:
@@ -69,7 +88,8 @@ class PackedGenome:
         g = cls.from_sequences(seqs)
         if cache:
             try:
-                np.savez(f_cache, names=np.array(g.names), offsets=g.offsets, lengths=g.lengths, words=g.words)
+                np.savez(f_cache, names=np.array(g.names), offsets=g.offsets, lengths=g.lengths, words=g.words,
+                         other_pos=g.other_pos, other_letter=g.other_letter)
                 g._cache2 = f_fasta + ".dig2.npz"
                 if os.path.exists(g._cache2):
                     os.remove(g._cache2)                  # (a 2-bit cache of an older FASTA)
@@ -92,6 +112,24 @@ class PackedGenome:
             else:
                 raise KeyError("chromosome %r is not in the genome" % c)
         return out
+
+    def letters(self, chrom, start, stop):
+        """Upper-case letters of positions start .. stop - 1 of chromosome index `chrom` (bytes): what fasta.fetch(...).upper()
+        gives for them -- ACGT from the packed words, the side table's letter or N for the other code."""
+        if self.other_pos is None:
+            raise ValueError("this PackedGenome has no table of letters other than ACGTN (built by slab()?)")
+        start, stop = int(start), max(int(start), int(stop))
+        if start < 0 or stop > int(self.lengths[chrom]):
+            raise ValueError("positions %d .. %d outside chromosome %s" % (start, stop, self.names[chrom]))
+        b = np.arange(start, stop, dtype=np.int64) + int(self.offsets[chrom]) + 8        # nibble index of the 4-bit array
+        nib = (self.words[b >> 3] >> ((b & 7) * 4).astype(np.uint32)) & np.uint32(15)
+        out = _LETTER[np.minimum(nib, 4)].copy()
+        g = b - 8
+        j = np.searchsorted(self.other_pos, g)
+        hit = (j < self.other_pos.size) & (self.other_pos[np.minimum(j, max(self.other_pos.size - 1, 0))] == g) \
+            if self.other_pos.size else np.zeros(g.size, bool)
+        out[hit] = self.other_letter[j[hit]]
+        return out.tobytes()
 
     def slab(self, chroms, starts, ends, margin_words=1):
         """The part of the genome a set of regions needs -- one rank's bin range of the per-base route (the reference

@@ -714,6 +714,65 @@ def count_contexts(genome, chroms, starts, ends, minus=None, device=0, on_device
     return out
 
 
+MC_KEPT, MC_MISMATCH, MC_DROPPED, MC_HOST = 0, 1, 2, 3          # include/dig_hip.h DIG_MC_*
+_REF_CODE = {"A": 0, "C": 1, "G": 2, "T": 3}
+
+
+def mutation_contexts(genome, chroms, starts, refs, n_up=2, n_down=2, collapse=False, device=0, on_device=True):
+    """Per-row match test, run rule and context window of mutation_contexts_by_chrom (sequence_tools.py:130-177) over a
+    PackedGenome, rows in group order (dig_mutation_contexts).  refs: the REF values (anything but one upper-case ACGT letter
+    never matches).  Returns (status u8 [R] -- MC_KEPT / MC_MISMATCH / MC_DROPPED / MC_HOST --, context [R]: the window at 2 bits
+    per base, base k in bits 2 k, 2 k + 1; int32 bits on the device, uint32 on the host).  on_device=True keeps the genome
+    resident in HBM and returns device tensors; False goes through the host twin.  A START outside its chromosome raises
+    ValueError (the reference indexes past the end of the chromosome string)."""
+    import pandas as pd
+    codes, uniq = pd.factorize(np.asarray(chroms))                # (one lookup per distinct label)
+    ci = genome.chrom_index(list(uniq))[codes] if len(codes) else np.zeros(0, np.int32)
+    R = len(ci)
+    st = _lib.as_host(starts, np.int64).ravel()
+    if isinstance(refs, np.ndarray) and refs.dtype == np.uint8:   # codes already (0-3, a single other letter as its byte, 255)
+        rc = _lib.as_host(refs, np.uint8).copy().ravel()
+    else:
+        one = pd.Series(np.asarray(refs, dtype=object))
+        one = one.where(one.map(lambda r: isinstance(r, str) and len(r) == 1 and 4 < ord(r) < 255), "")
+        rc = one.map(_REF_CODE).fillna(one.map(lambda r: ord(r) if r else 255)).to_numpy(np.uint8)
+    # a REF of one letter other than ACGT matches where the genome holds that letter (an N, an IUPAC code): the match is
+    # decided here from the letter table (the 2-bit form does not know it) and passed on as code 4
+    other = np.flatnonzero((rc > 3) & (rc < 255))
+    for k in other:
+        hit = 0 <= st[k] < genome.lengths[ci[k]] and genome.letters(ci[k], st[k], st[k] + 1) == bytes([rc[k]])
+        rc[k] = 4 if hit else 255
+    assert len(st) == len(rc) == R
+    n_up, n_down = int(n_up), int(n_down)
+    if n_up < 0 or n_down < 0 or n_up + n_down + 1 > 16:
+        raise ValueError("n_up, n_down >= 0 and n_up + n_down + 1 <= 16 (a context of at most 16 bases)")
+    if R and ((st < 0).any() or (st >= genome.lengths[ci]).any()):
+        bad = int(np.flatnonzero((st < 0) | (st >= genome.lengths[ci]))[0])
+        raise ValueError("START %d is outside chromosome %s (length %d)" % (st[bad], genome.names[ci[bad]], genome.lengths[ci[bad]]))
+    if on_device:
+        import torch
+        dev = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
+        status = torch.empty(R, dtype=torch.uint8, device=dev)
+        context = torch.empty(R, dtype=torch.int32, device=dev)
+        ws = torch.empty(max(_lib.load().dig_mutation_contexts_workspace(R), 1), dtype=torch.uint8, device=dev)
+        t = lambda a: torch.as_tensor(a, device=dev)
+        p = _lib.dev_ptr
+        with torch.cuda.device(dev):
+            w2, ns, ne, bk, off, ln = genome.on_device2(dev)
+            rci, rst, rrf = t(ci), t(st), t(rc)
+            _lib.call("dig_mutation_contexts", p(w2), w2.numel(), p(ns) if ns.numel() else None, p(ne) if ns.numel() else None,
+                      ns.numel(), p(bk) if ns.numel() else None, bk.numel(), p(off), p(ln), len(genome.names), p(rci), p(rst), p(rrf),
+                      R, n_up, n_down, int(bool(collapse)), p(status), p(context), p(ws), ws.numel(), _lib.stream_ptr())
+        return status, context
+    status, context = np.empty(R, np.uint8), np.empty(R, np.uint32)
+    h = _lib.host_ptr
+    w2, ns, ne, bk = genome.two_bit()
+    _lib.call("dig_mutation_contexts_host", h(w2), w2.size, h(ns) if ns.size else None, h(ne) if ns.size else None, ns.size,
+              h(bk) if ns.size else None, bk.size, h(genome.offsets), h(genome.lengths), len(genome.names), h(ci), h(st), h(rc), R,
+              n_up, n_down, int(bool(collapse)), h(status), h(context), device if isinstance(device, int) else 0)
+    return status, context
+
+
 def tiled_nb_test(pt, k, mu, sigma, device=0):
     """Per-tile exact NB test (nb_model.py:141-178).  pt f64 [n_bins, n_tiles] or [C, n_bins, n_tiles];
     k i32 [C, n_bins, n_tiles]; mu, sigma f64 [C, n_bins].  Returns (pval, exp) [C, n_bins, n_tiles]."""

@@ -297,3 +297,180 @@ def preprocess_sites(f_sites, f_nonc_data, f_pretrained, save_key, window):
         mapfile.write_array(f_nonc_data, base + 'blk_start', np.array(bs, np.int64))
         mapfile.write_array(f_nonc_data, base + 'blk_end', np.array(be, np.int64))
         mapfile.write_array(f_nonc_data, base + 'L', np.stack(Ls) if Ls else np.zeros((0, 192), np.int32))
+
+
+# ---------------------------------------------------------------------------------------------
+# sequence context of mutations (DigPreprocess.py addMutationContext; reference: a Python loop per row over a whole
+# chromosome string, one pool worker per chromosome, sequence_tools.py:130-222) -- dig_mutation_contexts on the GPU
+# ---------------------------------------------------------------------------------------------
+_BASES = np.frombuffer(b'ACGT', np.uint8)
+_COMP_BYTES = bytes.maketrans(b'NTCGA', b'NAGCT')
+
+
+def _on_device(on_device):
+    from .. import _lib
+    return (not _lib.TORCH_FREE) if on_device is None else bool(on_device)
+
+
+def _host_window(genome, ci, start, n_up, n_down, collapse):
+    """The context of one row whose window the kernel left to the host (a letter other than ACGT, a chromosome end): the
+    reference's seq[START - n_up : START + n_down + 1] with Python slice semantics, then seq_to_context."""
+    a, b, _ = slice(start - n_up, start + n_down + 1).indices(int(genome.lengths[ci]))
+    w = genome.letters(ci, a, b) if b > a else b''
+    if b'N' in w:
+        return ''
+    if collapse:
+        if len(w) <= n_up:
+            raise ValueError("START %d of %s: with collapse=True the reference indexes past its %d-letter window (IndexError)"
+                             % (start, genome.names[ci], len(w)))
+        if w[n_up:n_up + 1] in (b'G', b'A'):
+            w = w[::-1].translate(_COMP_BYTES)
+    return w.decode('ascii')
+
+
+def _kernel_rows(genome, chroms, starts, refs, n_up, n_down, collapse, on_device):
+    """engine.mutation_contexts on host arrays: (status, code, host, host_ctx) -- host: the rows the kernel left to the host
+    (MC_HOST), host_ctx: their contexts."""
+    from .. import engine
+    status, code = engine.mutation_contexts(genome, chroms, starts, refs, n_up=n_up, n_down=n_down, collapse=collapse,
+                                            on_device=on_device)
+    if on_device:
+        status, code = status.cpu().numpy(), code.cpu().numpy().view(np.uint32)
+    host = np.flatnonzero(status == engine.MC_HOST)
+    host_ctx = []
+    if host.size:
+        ci = genome.chrom_index(np.asarray(chroms)[host])
+        st = np.asarray(starts, np.int64)[host]
+        host_ctx = [_host_window(genome, int(c), int(s), n_up, n_down, collapse) for c, s in zip(ci, st)]
+    return status, code, host, host_ctx
+
+
+def _row_contexts(genome, chroms, starts, refs, n_up, n_down, collapse, on_device):
+    """(status, contexts): the kernel's status per row and the CONTEXT strings ('' for a dropped row), rows in group order."""
+    from .. import engine
+    status, code, host, host_ctx = _kernel_rows(genome, chroms, starts, refs, n_up, n_down, collapse, on_device)
+    W = n_up + n_down + 1
+    ctx = np.full(len(status), '', dtype=object)
+    kept = np.flatnonzero(status == engine.MC_KEPT)
+    if kept.size:
+        letters = _BASES[(code[kept, None] >> (2 * np.arange(W, dtype=np.uint32))) & np.uint32(3)]
+        ctx[kept] = np.ascontiguousarray(letters).view('S%d' % W).ravel().astype('U%d' % W)
+    if host.size:
+        ctx[host] = host_ctx
+    return status, ctx
+
+
+def _mut_types(ref, alt, collapse):
+    """type_mutation over columns: REF>ALT, both complemented letter by letter when REF is G or A (collapse)."""
+    ref, alt = ref.astype(str), alt.astype(str)
+    if collapse:
+        flip = ref.isin(['G', 'A'])
+        table = str.maketrans('NTCGA', 'NAGCT')
+        ref, alt = ref.where(~flip, ref.str.translate(table)), alt.where(~flip, alt.str.translate(table))
+    return (ref + '>' + alt).to_numpy(dtype=object)
+
+
+def mutation_contexts_by_chrom(f_fasta, df, n_up=2, n_down=2, collapse=False, on_device=None):
+    """sequence_tools.py:130-177: MUT_TYPE and CONTEXT columns appended to `df` (rows of the chromosome of its first row, in
+    order), rows without a context dropped.  f_fasta: a FASTA path or a PackedGenome.  on_device: None = the device form
+    unless the process declared itself torch-free (_lib.TORCH_FREE)."""
+    genome = load_genome(f_fasta)
+    CHROM = str(df.CHROM.iloc[0])
+    if not CHROM.startswith('chr'):
+        CHROM = "chr{}".format(CHROM)
+    _, ctx = _row_contexts(genome, [CHROM] * len(df), df.START.to_numpy(np.int64), df.REF.to_numpy(), n_up, n_down, collapse,
+                           _on_device(on_device))
+    df.insert(df.shape[1], 'MUT_TYPE', _mut_types(df.REF, df.ALT, collapse))
+    df.insert(df.shape[1], 'CONTEXT', ctx)
+    return df[df.CONTEXT != ""]
+
+
+def add_context_to_mutations(f_fasta, df_mut, n_up=2, n_down=2, N_proc=1, collapse=False, on_device=None):
+    """sequence_tools.py:179-222: SNV rows (ANNOT not containing INDEL) get MUT_TYPE and CONTEXT chromosome by chromosome
+    (CHROM ascending, order kept inside), indel rows ANNOT 'INDEL', their ANNOT as MUT_TYPE and CONTEXT '.'; with any indel the
+    frame is sorted by (CHROM, START, END).  All chromosomes go through one kernel call; N_proc is accepted and unused.
+    No row in either branch: ValueError (the reference fails with UnboundLocalError)."""
+    is_indel = df_mut.ANNOT.str.contains('INDEL')
+    df_indel = df_mut[is_indel]
+    df_mut = df_mut[~is_indel]
+    if len(df_mut) == 0 and len(df_indel) == 0:
+        raise ValueError("add_context_to_mutations: no mutation left to annotate")
+    if len(df_mut) > 0:
+        codes, uniq = pd.factorize(df_mut.CHROM, sort=True)       # groupby('CHROM') order, rows in order inside a group
+        keep = np.array(['MT' not in str(u) for u in uniq], bool)
+        order = np.argsort(codes, kind='stable')
+        order = order[keep[codes[order]]]
+        if order.size == 0:
+            raise ValueError("add_context_to_mutations: no chromosome left to annotate")
+        df = df_mut.iloc[order].copy()
+        chroms = np.array(['chr{}'.format(u) if not str(u).startswith('chr') else str(u) for u in uniq], dtype=object)[codes[order]]
+        _, ctx = _row_contexts(load_genome(f_fasta), chroms, df.START.to_numpy(np.int64), df.REF.to_numpy(), n_up, n_down, collapse,
+                               _on_device(on_device))
+        df.insert(df.shape[1], 'MUT_TYPE', _mut_types(df.REF, df.ALT, collapse))
+        df.insert(df.shape[1], 'CONTEXT', ctx)
+        df_out = df[df.CONTEXT != ""]
+    if len(df_indel) > 0:
+        print('Adding context to indels')
+        df_indel = df_indel.rename({'ANNOT': 'MUT_TYPE'}, axis=1)
+        df_indel.insert(df_indel.shape[1] - 1, 'ANNOT', 'INDEL')
+        df_indel.insert(df_indel.shape[1], 'CONTEXT', '.')
+        if len(df_mut) > 0:
+            df_out = pd.concat([df_out, df_indel]).sort_values(['CHROM', 'START', 'END'])
+        else:
+            df_out = df_indel.sort_values(['CHROM', 'START', 'END'])
+    return df_out
+
+
+def write_mutation_contexts(f_mut, f_fasta, f_out, n_up=1, n_down=1, native=True, on_device=None, timings=None):
+    """DigPreprocess.py addMutationContext (:75-100): the 8-column file f_mut annotated with MUT_TYPE and CONTEXT, written to
+    f_out (a trailing .gz is dropped; the output is not compressed).  A file pandas would echo unchanged goes through the native
+    reader / writer (dig_mutctx_file_*_host) when `native`; anything else through read_mutation_file, add_context_to_mutations
+    and to_csv -- the same bytes.  Returns the path taken ('native' or 'pandas'); `timings` (a dict) receives the seconds of the
+    parse, kernel and write steps."""
+    import ctypes
+    import time
+    from .. import _lib
+
+    if f_out.endswith('.gz'):
+        f_out = f_out[:-3]
+    width = mutation_tools._first_row_width(f_mut)
+    if width != 8:
+        raise ValueError("addMutationContext reads the 8-column mutation file CHROM START END REF ALT SAMPLE GENE ANNOT; "
+                         "{} has {} columns".format(f_mut, width))
+    timings = {} if timings is None else timings
+    dev = _on_device(on_device)
+    genome = load_genome(f_fasta)
+    t0 = time.perf_counter()
+    handle, n_snv, n_indel = ctypes.c_void_p(), ctypes.c_int64(-1), ctypes.c_int64(0)
+    if native:
+        _lib.call("dig_mutctx_file_parse_host", f_mut.encode(), ctypes.byref(handle), ctypes.byref(n_snv), ctypes.byref(n_indel))
+    if n_snv.value < 0:
+        df_mut = mutation_tools.read_mutation_file(f_mut, drop_duplicates=False)
+        timings['parse'] = time.perf_counter() - t0
+        t0 = time.perf_counter()
+        df_out = add_context_to_mutations(genome, df_mut, n_up=n_up, n_down=n_down, collapse=False, on_device=dev)
+        timings['kernel'] = time.perf_counter() - t0
+        t0 = time.perf_counter()
+        df_out.to_csv(f_out, sep="\t", index=False, header=False)
+        timings['write'] = time.perf_counter() - t0
+        return 'pandas'
+    try:
+        n = n_snv.value
+        if n == 0 and n_indel.value == 0:
+            raise ValueError("add_context_to_mutations: no mutation left to annotate")
+        chrom, start, ref = np.empty(n, np.int32), np.empty(n, np.int64), np.empty(n, np.uint8)
+        _lib.call("dig_mutctx_file_fetch_host", handle, _lib.host_ptr(chrom), _lib.host_ptr(start), _lib.host_ptr(ref))
+        timings['parse'] = time.perf_counter() - t0
+        t0 = time.perf_counter()
+        status, code, _, host_ctx = _kernel_rows(genome, chrom, start, ref, n_up, n_down, False, dev)
+        host_text = ''.join(host_ctx).encode('ascii')
+        host_off = np.zeros(len(host_ctx) + 1, np.int64)
+        np.cumsum([len(h) for h in host_ctx], out=host_off[1:])
+        timings['kernel'] = time.perf_counter() - t0
+        t0 = time.perf_counter()
+        _lib.call("dig_mutctx_file_write_host", handle, f_out.encode(), _lib.host_ptr(status), _lib.host_ptr(code),
+                  host_text, _lib.host_ptr(host_off), int(n_up), int(n_down))
+        timings['write'] = time.perf_counter() - t0
+    finally:
+        _lib.call("dig_mutctx_file_free_host", handle)
+    return 'native'

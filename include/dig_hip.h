@@ -409,6 +409,37 @@ int dig_count_contexts2_host(const uint32_t *words2, int64_t n_words2, const int
                              const int64_t *chrom_len, int n_chrom, const int32_t *reg_chrom, const int64_t *reg_start,
                              const int64_t *reg_end, const uint8_t *reg_minus, int64_t R, int32_t *out, int device);
 
+/* ---- sequence context of mutations (DigPreprocess.py addMutationContext) ------------------------------ *
+ * mutation_contexts_by_chrom (sequence_model/sequence_tools.py:130-177) for rows in group order (chromosome-grouped; a run is a
+ * maximal block of consecutive rows with the same chromosome and START), over the 2-bit genome of dig_count_contexts2 (words2,
+ * the run list and its bucket index, chrom_off / chrom_len exactly as there):
+ *   row_chrom i32 [n_rows] within [0, n_chrom); row_start i64 [n_rows] (0-based centre); row_ref u8 [n_rows]: 0-3 for a REF of one
+ *       upper-case letter A C G T, 4 for a REF the caller found equal to a genome letter other than ACGT (such a row's window
+ *       touches a non-ACGT run: DIG_MC_HOST), anything else never matches;
+ *   window = bases START - n_up .. START + n_down, n_up, n_down >= 0, n_up + n_down + 1 <= 16;
+ *   status u8 [n_rows]: DIG_MC_KEPT, DIG_MC_MISMATCH (seq[START] != REF), DIG_MC_DROPPED (it matches, an earlier row of its run
+ *       does not), DIG_MC_HOST (it and its run match, but the window touches a letter other than ACGT, starts before the
+ *       chromosome or is cut short at its end: the caller takes the letters from the FASTA); a START outside [0, chrom_len) is
+ *       reported as DIG_MC_HOST with nothing read (the caller rejects it);
+ *   context u32 [n_rows] (DIG_MC_KEPT rows): the window at 2 bits per base (A=0 C=1 G=2 T=3), window base k in bits 2 k, 2 k + 1;
+ *       collapse != 0: reverse-complemented when the centre is A or G;
+ *   workspace: dig_mutation_contexts_workspace(n_rows) bytes.  n_rows < 2^31. */
+#define DIG_MC_KEPT 0
+#define DIG_MC_MISMATCH 1
+#define DIG_MC_DROPPED 2
+#define DIG_MC_HOST 3
+int64_t dig_mutation_contexts_workspace(int64_t n_rows);
+int dig_mutation_contexts(const uint32_t *words2, int64_t n_words2, const int64_t *nint_start, const int64_t *nint_end,
+                          int64_t n_int, const int32_t *nint_bucket, int64_t n_buckets, const int64_t *chrom_off,
+                          const int64_t *chrom_len, int n_chrom, const int32_t *row_chrom, const int64_t *row_start,
+                          const uint8_t *row_ref, int64_t n_rows, int n_up, int n_down, int collapse, uint8_t *status,
+                          uint32_t *context, void *workspace, int64_t workspace_bytes, void *stream);
+int dig_mutation_contexts_host(const uint32_t *words2, int64_t n_words2, const int64_t *nint_start, const int64_t *nint_end,
+                               int64_t n_int, const int32_t *nint_bucket, int64_t n_buckets, const int64_t *chrom_off,
+                               const int64_t *chrom_len, int n_chrom, const int32_t *row_chrom, const int64_t *row_start,
+                               const uint8_t *row_ref, int64_t n_rows, int n_up, int n_down, int collapse, uint8_t *status,
+                               uint32_t *context, int device);
+
 /* ---- result files (ABI 6; host code only) ------------------------------------------------- *
  * The text DataFrame.to_csv(path, header=True, index=True, sep="\t") writes for a frame (DigDriver.py:115-118): `header`
  * (a complete first line, no newline), then n_rows rows  label TAB col_0 TAB ... col_{n_cols-1}.
@@ -438,6 +469,25 @@ int dig_mutation_file_fetch_host(void *handle, int64_t *chrom, int64_t *start, i
  * genome-mode scale factors (calc_scale_factor_efficient, transfer_tools.py:129-159) count flagged rows: no sort on the device. */
 int dig_mutation_file_flags_host(void *handle, int64_t *first_row, int64_t *first_indel);
 int dig_mutation_file_free_host(void *handle);
+
+/* ---- raw mutation calls -> annotated file (addMutationContext, DigPreprocess.py:75-100; host code only) ---------- *
+ * For an 8-column file (CHROM START END REF ALT SAMPLE GENE ANNOT) that pandas would echo unchanged -- no NaN spelling, quote,
+ * CR, NUL or non-ASCII byte, 8 fields on every line, no empty line, START / END canonical integers -- what read_mutation_file +
+ * add_context_to_mutations + to_csv(sep="\t", index=False, header=False) write:
+ * parse: *n_snv = rows of the SNV branch (CHROM exactly "1" .. "22", ANNOT not containing "INDEL", grouped by CHROM, file order
+ *   inside), *n_indel = rows of the indel branch (after the de-duplication of ANNOT == "INDEL" rows on CHROM START END REF ALT
+ *   GENE); *n_snv = -1 and no handle for any other file (the caller takes the pandas path).
+ * fetch: the SNV rows' CHROM (1 .. 22), START and REF code: 0-3 for one upper-case ACGT letter, the byte itself for one
+ *   other letter (the caller compares it with the genome: 4 or 255 for dig_mutation_contexts), 255 otherwise.
+ * write: status / context of dig_mutation_contexts for the n_snv rows; host_text / host_off [n_host + 1]: the contexts of the
+ *   DIG_MC_HOST rows, in row order (an empty one drops the row).  Kept SNV rows get MUT_TYPE = REF>ALT and CONTEXT; indel rows
+ *   ANNOT "INDEL", their ANNOT as MUT_TYPE and CONTEXT "."; with any indel row the output is stably sorted by (CHROM, START, END).
+ * free: releases the handle (NULL allowed). */
+int dig_mutctx_file_parse_host(const char *path, void **handle, int64_t *n_snv, int64_t *n_indel);
+int dig_mutctx_file_fetch_host(void *handle, int32_t *chrom, int64_t *start, uint8_t *ref);
+int dig_mutctx_file_write_host(void *handle, const char *path, const uint8_t *status, const uint32_t *context,
+                               const char *host_text, const int64_t *host_off, int n_up, int n_down);
+int dig_mutctx_file_free_host(void *handle);
 
 /* ---- Benjamini-Hochberg q-values (nb_model.get_q_vals, nb_model.py:340-342 = statsmodels fdrcorrection, method 'indep') ---- *
  * For `rows` lists of n p-values each, every list ALREADY in ascending order (the caller sorts: torch.sort / rocPRIM; row r at

@@ -1,16 +1,19 @@
 #!/usr/bin/env python
 """DigPreprocess.py -- sequence-context preprocessing on MI355X.
 
-The sub-commands of the reference's scripts/DigPreprocess.py that feed the burden-test path with context counts
-(the annotation sub-commands need bedtools / R and are out of scope):
+The sub-commands of the reference's scripts/DigPreprocess.py that feed the burden-test path with context counts and
+annotated mutation files (addMutationFunction and annotMutationFile need bedtools / R and are out of scope, DESIGN.md
+section 7; addMutationContext needs only the FASTA):
 
     countGenomeContext        window context counts of a genome          (DigPreprocess.py:19-73)
+    addMutationContext        MUT_TYPE and CONTEXT columns of a mutation file (:75-100)
     initialize_f_data         start an element-data container            (:147-153)
     preprocess_element_model  per-element L counts from bed12 + FASTA    (:129-145)
     preprocess_tiled          L counts of a tiled genome                 (:155-164)
 
 Same positional arguments and option names.  Sequence is read once into a 4-bit packed array (cached next to the
-FASTA) and counted by dig_count_contexts instead of per-region pysam fetches.
+FASTA) and counted by dig_count_contexts instead of per-region pysam fetches; the mutation contexts come from
+dig_mutation_contexts over the same genome.
 """
 import argparse
 import os
@@ -49,6 +52,21 @@ def count_genome_context(args):
         mapfile.write_frame(args.fout, 'all_window_genome_counts', df)
         mapfile.write_array(args.fout, 'idx', idx.astype(np.int32))
         mapfile.write_attrs(args.fout, n_up=1, n_down=1, collapse=0)
+
+
+def add_mutation_context(args):
+    # torch-free: the `_host` twin path, as the single-cohort DigDriver commands
+    from digdriver_amd import _lib
+    _lib.TORCH_FREE = True
+    if args.up < 0 or args.down < 0 or args.up + args.down + 1 > 16:
+        raise SystemExit("--up and --down must be >= 0 with up + down + 1 <= 16.")
+    print('Reading in mutation file')
+    fout = args.fout[:-3] if args.fout.endswith('.gz') else args.fout
+    try:
+        sequence_tools.write_mutation_contexts(args.fmut, args.fasta, fout, n_up=args.up, n_down=args.down, on_device=False)
+    except ValueError as exc:
+        raise SystemExit("addMutationContext: %s" % exc)
+    print('Saved annotated mutation file: {}'.format(fout))
 
 
 def initialize_data(args):
@@ -93,6 +111,15 @@ def parse_args(text=None):
     a.add_argument('--map-thresh', type=float, default=0.5, help='unused')
     a.set_defaults(func=count_genome_context)
 
+    b = sub.add_parser('addMutationContext', help='annotate a mutation file with MUT_TYPE and sequence CONTEXT')
+    b.add_argument('fmut', type=str, help='8-column mutation file: CHROM START END REF ALT SAMPLE GENE ANNOT (plain or gzip)')
+    b.add_argument('fasta', type=str, help='reference genome FASTA')
+    b.add_argument('fout', type=str, help='output file name (a trailing .gz is dropped; not compressed)')
+    b.add_argument('--up', type=int, default=1, help='bases upstream of the mutation in the context (1)')
+    b.add_argument('--down', type=int, default=1, help='bases downstream of the mutation in the context (1)')
+    b.add_argument('--n-procs', type=int, default=1, help='accepted for compatibility')
+    b.set_defaults(func=add_mutation_context)
+
     e = sub.add_parser('preprocess_element_model', help='per-element context counts from a bed12 file')
     e.add_argument('f_element_data', help='element-data container (see initialize_f_data)')
     e.add_argument('f_pretrained', help='any pretrained map (kept for compatibility)')
@@ -125,3 +152,5 @@ def parse_args(text=None):
 if __name__ == "__main__":
     cli = parse_args()
     cli.func(cli)
+    if os.environ.get("DIG_CLI_ASSERT_NO_TORCH") == "1" and cli.func is add_mutation_context:
+        assert "torch" not in sys.modules, "a torch-free sub-command imported torch"         # (tests: the claim above)
