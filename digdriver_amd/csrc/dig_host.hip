@@ -302,6 +302,32 @@ int dig_count_contexts2_host(const uint32_t* words2, int64_t n_words2, const int
                    nullptr);
 }
 
+int dig_count_contexts5_host(const uint32_t* words2, int64_t n_words2, const int64_t* nint_start, const int64_t* nint_end, int64_t n_int,
+                             const int32_t* nint_bucket, int64_t n_buckets, const int64_t* chrom_off, const int64_t* chrom_len,
+                             int n_chrom, const int32_t* reg_chrom, const int64_t* reg_start, const int64_t* reg_end,
+                             const uint8_t* reg_minus, int64_t R, int32_t* out, int device)
+{
+    DIG_REQUIRE(R >= 0 && n_words2 >= 28 && n_chrom >= 0 && n_int >= 0, "R, n_int, n_chrom >= 0, n_words2 >= 28 (pad words)");
+    if (R == 0) return DIG_OK;
+    DIG_REQUIRE(words2 && chrom_off && chrom_len && reg_chrom && reg_start && reg_end && reg_minus && out, "non-null pointers");
+    DIG_REQUIRE(n_int == 0 || (nint_start && nint_end && nint_bucket && n_buckets >= 1), "interval list with its bucket index");
+    for (int64_t r = 0; r < R; ++r) {
+        DIG_REQUIRE(reg_chrom[r] >= 0 && reg_chrom[r] < n_chrom, "region chromosome index within [0, n_chrom)");
+        DIG_REQUIRE(reg_start[r] >= 0 && reg_end[r] >= 0, "non-negative coordinates");
+        DIG_REQUIRE(reg_start[r] == 0 || reg_start[r] >= 2, "START 0 or >= 2 (the fetch would start before the chromosome)");
+    }
+    for (int c = 0; c < n_chrom; ++c)
+        DIG_REQUIRE(chrom_off[c] >= 0 && chrom_off[c] + chrom_len[c] + 64 <= (n_words2 - 24) * 16, "chromosomes inside the genome array");
+    for (int64_t j = 0; j < n_int; ++j)
+        DIG_REQUIRE(nint_start[j] < nint_end[j] && (j == 0 || nint_end[j - 1] < nint_start[j]), "intervals sorted, disjoint, not touching");
+    const size_t nc = std::max(n_chrom, 1);
+    Staging st(device);
+    return st.call(dig_count_contexts5, st.in(words2, n_words2), n_words2, st.in(nint_start, n_int), st.in(nint_end, n_int), n_int,
+                   st.in(nint_bucket, n_int ? n_buckets : 0), n_buckets, st.in(chrom_off, nc), st.in(chrom_len, nc), n_chrom,
+                   st.in(reg_chrom, R), st.in(reg_start, R), st.in(reg_end, R), st.in(reg_minus, R), R, st.out(out, (size_t)R * 1024),
+                   nullptr);
+}
+
 int dig_mutation_contexts_host(const uint32_t* words2, int64_t n_words2, const int64_t* nint_start, const int64_t* nint_end, int64_t n_int,
                                const int32_t* nint_bucket, int64_t n_buckets, const int64_t* chrom_off, const int64_t* chrom_len,
                                int n_chrom, const int32_t* row_chrom, const int64_t* row_start, const uint8_t* row_ref, int64_t n_rows,

@@ -669,12 +669,18 @@ def gather_bins(x_data, bin_rows, tracks=None, out_dtype="f32", transpose=False,
     return out
 
 
-def count_contexts(genome, chroms, starts, ends, minus=None, device=0, on_device=True, form="2bit"):
-    """Trinucleotide context counts [R, 64] of regions of a PackedGenome (sequence_tools.py:65-99,527-566).
+def count_contexts(genome, chroms, starts, ends, minus=None, device=0, on_device=True, form="2bit", n_up=1, n_down=1):
+    """Context counts of regions of a PackedGenome (sequence_tools.py:65-99,527-566): [R, 64] trinucleotide counts for
+    (n_up, n_down) = (1, 1), [R, 1024] penta-nucleotide counts for (2, 2) (dig_count_contexts5; columns in
+    mk_context_sequences(2, 2) order; a START of 1 raises ValueError, the reference's fetch would start at -1).
     on_device=True keeps the genome resident in HBM (uploaded on first use) and returns a device tensor; False goes
     through the host twin (uploads the genome for this call; small genomes / tests).
-    form: "2bit" (dig_count_contexts2: the genome at 2 bits per base + the list of non-ACGT runs; what everything uses) or
-    "4bit" (dig_count_contexts, the first form; kept as a cross-check) -- the same counts."""
+    form (trinucleotides only): "2bit" (dig_count_contexts2: the genome at 2 bits per base + the list of non-ACGT runs;
+    what everything uses) or "4bit" (dig_count_contexts, the first form; kept as a cross-check) -- the same counts."""
+    if (n_up, n_down) not in ((1, 1), (2, 2)):
+        raise NotImplementedError("context counting handles (n_up, n_down) = (1, 1) (trinucleotides) and (2, 2) "
+                                  "(penta-nucleotides); got (%s, %s)" % (n_up, n_down))
+    penta = (n_up, n_down) == (2, 2)
     ci = genome.chrom_index(chroms)
     R = len(ci)
     st, en = _lib.as_host(starts, np.int64).ravel(), _lib.as_host(ends, np.int64).ravel()
@@ -682,31 +688,39 @@ def count_contexts(genome, chroms, starts, ends, minus=None, device=0, on_device
     assert len(st) == len(en) == len(mi) == R and form in ("2bit", "4bit")
     if (st < 0).any() or (en < 0).any():
         raise ValueError("negative region coordinates")
+    if penta:
+        if form != "2bit":
+            raise ValueError("penta-nucleotide counts come from the 2-bit form only")
+        if ((st > 0) & (st < n_up)).any():
+            bad = int(np.flatnonzero((st > 0) & (st < n_up))[0])
+            raise ValueError("START %d of region %d: the reference fetches from START - %d, before the chromosome start"
+                             % (st[bad], bad, n_up))
+    K = 1024 if penta else 64
     if on_device:
         import torch
         dev = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
         t = lambda a: torch.as_tensor(a, device=dev)
-        out = torch.empty((R, 64), dtype=torch.int32, device=dev)
+        out = torch.empty((R, K), dtype=torch.int32, device=dev)
         rc, rs, re_, rm = t(ci), t(st), t(en), t(mi)
         p = _lib.dev_ptr
         with torch.cuda.device(dev):
             if form == "2bit":
                 w2, ns, ne, bk, off, ln = genome.on_device2(dev)
-                _lib.call("dig_count_contexts2", p(w2), w2.numel(), p(ns) if ns.numel() else None, p(ne) if ns.numel() else None,
-                          ns.numel(), p(bk) if ns.numel() else None, bk.numel(), p(off), p(ln), len(genome.names), p(rc), p(rs),
+                _lib.call("dig_count_contexts5" if penta else "dig_count_contexts2", p(w2), w2.numel(), p(ns) if ns.numel() else None,
+                          p(ne) if ns.numel() else None, ns.numel(), p(bk) if ns.numel() else None, bk.numel(), p(off), p(ln), len(genome.names), p(rc), p(rs),
                           p(re_), p(rm), R, p(out), _lib.stream_ptr())
             else:
                 words, off, ln = genome.on_device(dev)
                 _lib.call("dig_count_contexts", p(words), words.numel(), p(off), p(ln), len(genome.names), p(rc), p(rs), p(re_),
                           p(rm), R, p(out), _lib.stream_ptr())
         return out
-    out = np.empty((R, 64), np.int32)
+    out = np.empty((R, K), np.int32)
     h = _lib.host_ptr
     dv = device if isinstance(device, int) else 0
     if form == "2bit":
         w2, ns, ne, bk = genome.two_bit()
-        _lib.call("dig_count_contexts2_host", h(w2), w2.size, h(ns) if ns.size else None, h(ne) if ns.size else None, ns.size,
-                  h(bk) if ns.size else None, bk.size, h(genome.offsets), h(genome.lengths), len(genome.names), h(ci), h(st), h(en),
+        _lib.call("dig_count_contexts5_host" if penta else "dig_count_contexts2_host", h(w2), w2.size, h(ns) if ns.size else None,
+                  h(ne) if ns.size else None, ns.size, h(bk) if ns.size else None, bk.size, h(genome.offsets), h(genome.lengths), len(genome.names), h(ci), h(st), h(en),
                   h(mi), R, h(out), dv)
     else:
         _lib.call("dig_count_contexts_host", h(genome.words), genome.words.size, h(genome.offsets), h(genome.lengths),

@@ -5,7 +5,8 @@ Mirror of the parts of DIGDriver/sequence_model/sequence_tools.py that the hot p
 count_sequence_context :67-80, mk_mutation_context :232-262, mk_trans_idx :282-289,
 train_sequence_model + mutation_freq_conditional :321-373).  The live path is the 192-type / 64-context
 model (collapse=False everywhere, DigPreprocess.py:47,91); collapse=True (96 types) is kept for
-completeness.
+completeness.  Genome context counts also come in the reference's default penta-nucleotide form (n_up = n_down = 2:
+1 024 contexts, 3 072 substitution types), which trains the per-base route's default S_prob.
 """
 import itertools as it
 
@@ -106,8 +107,9 @@ def sequence_model_counts(df_mut_white, n_up=1, n_down=1):
 
 
 def train_sequence_model(regions, df_mut, genome_counts, n_up=1, n_down=1, key_prefix=None, counts=None):
-    """sequence_tools.py:321-354 -> (df_freq_mut [192: MUT_TYPE, CONTEXT, COUNT, FREQ], df_freq_context [64: FREQ]).
-    `counts` lets a caller pass pre-reduced 192-vector counts (multi-GPU / multi-shard path)."""
+    """sequence_tools.py:321-354 -> (df_freq_mut [192: MUT_TYPE, CONTEXT, COUNT, FREQ], df_freq_context [64: FREQ]); with
+    n_up = n_down = 2, 3 072 and 1 024 rows.  `counts` lets a caller pass pre-reduced counts in the model's row order
+    (multi-GPU / multi-shard path)."""
     if counts is None:
         df_bed = pd.DataFrame(regions, columns=['CHROM', 'START', 'END'])
         white = mutation_tools.restrict_mutations_by_bed(df_mut, df_bed, unique=True, remove_X=False)
@@ -135,47 +137,50 @@ def load_genome(f_fasta):
     return _GENOMES[f_fasta]
 
 
-def _require_trinuc(n_up, n_down, collapse):
-    if (n_up, n_down) != (1, 1):
-        raise NotImplementedError("the GPU context counter handles trinucleotides (n_up = n_down = 1), the only configuration "
-                                  "the driver path uses (onthefly_tools.py:70-71,120)")
+def _require_supported(n_up, n_down):
+    if (n_up, n_down) not in ((1, 1), (2, 2)):
+        raise NotImplementedError("the GPU context counter handles (n_up, n_down) = (1, 1) (trinucleotides, what the driver "
+                                  "path uses: onthefly_tools.py:70-71,120) and (2, 2) (penta-nucleotides, the per-base model); "
+                                  "got (%s, %s)" % (n_up, n_down))
 
 
 def count_contexts_by_regions(f_fasta, chrom_lst, start_lst, end_lst, n_up=2, n_down=2, collapse=False):
-    """sequence_tools.py:82-99: frame [regions x 64 contexts] (columns in mk_context_sequences order, index
-    "{CHROM}:{START}-{END}") -- one dig_count_contexts2 launch for all regions; collapse=True: the 32 pyrimidine-centred
-    contexts.  `f_fasta`: path or PackedGenome."""
+    """sequence_tools.py:82-99: frame [regions x 4^(n_up + 1 + n_down) contexts] (columns in mk_context_sequences order, index
+    "{CHROM}:{START}-{END}") -- one dig_count_contexts2 (trinucleotides) or dig_count_contexts5 (penta-nucleotides) launch for
+    all regions; collapse=True: the pyrimidine-centred half of the contexts.  `f_fasta`: path or PackedGenome."""
     from .. import engine
-    _require_trinuc(n_up, n_down, collapse)
+    _require_supported(n_up, n_down)
     genome = f_fasta if hasattr(f_fasta, "words") else load_genome(f_fasta)
-    cnt = engine.count_contexts(genome, list(chrom_lst), np.asarray(start_lst, np.int64), np.asarray(end_lst, np.int64))
+    cnt = engine.count_contexts(genome, list(chrom_lst), np.asarray(start_lst, np.int64), np.asarray(end_lst, np.int64),
+                                n_up=n_up, n_down=n_down)
     idx = ["{}:{}-{}".format(c, s, e) for c, s, e in zip(chrom_lst, start_lst, end_lst)]
     cnt = cnt.cpu().numpy().astype(np.int64)
-    ctx64 = list(mk_context_sequences(1, 1).keys())
+    ctx = list(mk_context_sequences(n_up, n_down).keys())
     if not collapse:
-        return pd.DataFrame(cnt, index=idx, columns=ctx64)
+        return pd.DataFrame(cnt, index=idx, columns=ctx)
     # collapse=True (the K = 96 model): a window centred on A or G counts as its reverse complement (seq_to_context,
-    # sequence_tools.py:42-55): the 32 pyrimidine-centred columns, each the sum of a context and its reverse complement
-    pos = {c: i for i, c in enumerate(ctx64)}
-    ctx32 = list(mk_context_sequences(1, 1, collapse=True).keys())
-    cols = np.array([pos[c] for c in ctx32]), np.array([pos[reverse_complement(c)] for c in ctx32])
-    return pd.DataFrame(cnt[:, cols[0]] + cnt[:, cols[1]], index=idx, columns=ctx32)
+    # sequence_tools.py:42-55): the pyrimidine-centred columns, each the sum of a context and its reverse complement
+    pos = {c: i for i, c in enumerate(ctx)}
+    half = list(mk_context_sequences(n_up, n_down, collapse=True).keys())
+    cols = np.array([pos[c] for c in half]), np.array([pos[reverse_complement(c)] for c in half])
+    return pd.DataFrame(cnt[:, cols[0]] + cnt[:, cols[1]], index=idx, columns=half)
 
 
 def nonc_elt_context_count(regions, trans_idx, f_fasta, n_up=1, n_down=1):
     """sequence_tools.py:527-566: `regions` = (chrom, start, end, strand) tuples; '-' / -1 strand regions count the
-    reverse-complemented sequence; result [regions x 192] with the sorted substitution keys as columns, every
-    substitution column holding the count of its context; index "chr{chrom}:{start}-{end}"."""
+    reverse-complemented sequence; result [regions x substitutions] (192 for trinucleotides, 3 072 for penta-nucleotides)
+    with the sorted substitution keys as columns, every substitution column holding the count of its context; index
+    "chr{chrom}:{start}-{end}"."""
     from .. import engine
-    _require_trinuc(n_up, n_down, False)
+    _require_supported(n_up, n_down)
     genome = f_fasta if hasattr(f_fasta, "words") else load_genome(f_fasta)
     chroms = ['chr' + str(r[0]) for r in regions]
     starts = np.array([r[1] for r in regions], np.int64)
     ends = np.array([r[2] for r in regions], np.int64)
     minus = np.array([(r[3] == '-' or r[3] == -1) for r in regions], bool)
-    cnt = engine.count_contexts(genome, chroms, starts, ends, minus).cpu().numpy().astype(np.float64)
+    cnt = engine.count_contexts(genome, chroms, starts, ends, minus, n_up=n_up, n_down=n_down).cpu().numpy().astype(np.float64)
     keys = sorted(set(trans_idx))
-    ctx = list(mk_context_sequences(1, 1).keys())
+    ctx = list(mk_context_sequences(n_up, n_down).keys())
     pos = {c: i for i, c in enumerate(ctx)}
     cols = np.array([pos[k.split('>')[0]] for k in keys])
     idx = ["{}:{}-{}".format(c, s, e) for c, s, e in zip(chroms, starts, ends)]
@@ -184,8 +189,11 @@ def nonc_elt_context_count(regions, trans_idx, f_fasta, n_up=1, n_down=1):
 
 def precount_region_contexts_parallel(f_nonc_bed, f_fasta, n_procs, window, sub_elts=True, n_up=1, n_down=1):
     """sequence_tools.py:481-525: context counts of every block of a bed12 (sub_elts) or of every bed row, rows with a
-    repeated index removed.  n_procs is accepted for compatibility (one launch does all regions)."""
+    repeated index removed.  n_procs is accepted for compatibility (one launch does all regions).  As in the reference, the
+    counts are trinucleotide ones (192 columns, what preprocess_nonc reads) whatever n_up / n_down say: it builds the
+    (1, 1) substitution index and does not pass n_up / n_down on."""
     from ..data_tools import mutation_tools
+    _require_supported(n_up, n_down)
     trans_idx = mk_trans_idx(n_up=1, n_down=1, collapse=False)
     df = pd.read_csv(f_nonc_bed, sep='\t', header=None, names=None, low_memory=False, dtype={0: str})
     if sub_elts:
@@ -199,7 +207,7 @@ def precount_region_contexts_parallel(f_nonc_bed, f_fasta, n_procs, window, sub_
         if 'chr' in str(chrom.iloc[0]):
             chrom = chrom.map(lambda x: x.lstrip('chr'))
         regions = list(zip(chrom, df[1], df[2], df[5]))
-    results = nonc_elt_context_count(regions, trans_idx, f_fasta, n_up=n_up, n_down=n_down)
+    results = nonc_elt_context_count(regions, trans_idx, f_fasta)
     return results.loc[~results.index.duplicated()]
 
 

@@ -409,6 +409,23 @@ int dig_count_contexts2_host(const uint32_t *words2, int64_t n_words2, const int
                              const int64_t *chrom_len, int n_chrom, const int32_t *reg_chrom, const int64_t *reg_start,
                              const int64_t *reg_end, const uint8_t *reg_minus, int64_t R, int32_t *out, int device);
 
+/* Penta-nucleotide counts (n_up = n_down = 2) from the 2-bit genome of dig_count_contexts2 (same words2, run list, bucket
+ * index, chromosome and region arrays):
+ *   centres of region r run over [s, e) with s = 2 if START == 0 else START, e = min(END, chrom_len - 2) (the reference's
+ *       fetch widened by two bases on either side, truncated at the chromosome end); an empty range gives a row of zeros;
+ *       0 < START < 2 is refused (the _host twin returns DIG_EINVAL; the reference's fetch would start before base 0);
+ *   a window holding any letter other than ACGT is skipped; reg_minus[r] != 0 counts the reverse-complemented sequence;
+ *   out i32 [R, 1024], 16-byte aligned, context index 256 b0 + 64 b1 + 16 b2 + 4 b3 + b4 (= itertools.product('ACGT',
+ *       repeat=5) order).  Counters are 32-bit: a region may be a whole chromosome. */
+int dig_count_contexts5(const uint32_t *words2, int64_t n_words2, const int64_t *nint_start, const int64_t *nint_end,
+                        int64_t n_int, const int32_t *nint_bucket, int64_t n_buckets, const int64_t *chrom_off,
+                        const int64_t *chrom_len, int n_chrom, const int32_t *reg_chrom, const int64_t *reg_start,
+                        const int64_t *reg_end, const uint8_t *reg_minus, int64_t R, int32_t *out, void *stream);
+int dig_count_contexts5_host(const uint32_t *words2, int64_t n_words2, const int64_t *nint_start, const int64_t *nint_end,
+                             int64_t n_int, const int32_t *nint_bucket, int64_t n_buckets, const int64_t *chrom_off,
+                             const int64_t *chrom_len, int n_chrom, const int32_t *reg_chrom, const int64_t *reg_start,
+                             const int64_t *reg_end, const uint8_t *reg_minus, int64_t R, int32_t *out, int device);
+
 /* ---- sequence context of mutations (DigPreprocess.py addMutationContext) ------------------------------ *
  * mutation_contexts_by_chrom (sequence_model/sequence_tools.py:130-177) for rows in group order (chromosome-grouped; a run is a
  * maximal block of consecutive rows with the same chromosome and START), over the 2-bit genome of dig_count_contexts2 (words2,

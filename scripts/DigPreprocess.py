@@ -5,14 +5,14 @@ The sub-commands of the reference's scripts/DigPreprocess.py that feed the burde
 annotated mutation files (addMutationFunction and annotMutationFile need bedtools / R and are out of scope, DESIGN.md
 section 7; addMutationContext needs only the FASTA):
 
-    countGenomeContext        window context counts of a genome          (DigPreprocess.py:19-73)
+    countGenomeContext        window context counts of a genome, --up/--down 1 or 2 (DigPreprocess.py:19-73)
     addMutationContext        MUT_TYPE and CONTEXT columns of a mutation file (:75-100)
     initialize_f_data         start an element-data container            (:147-153)
     preprocess_element_model  per-element L counts from bed12 + FASTA    (:129-145)
     preprocess_tiled          L counts of a tiled genome                 (:155-164)
 
 Same positional arguments and option names.  Sequence is read once into a 4-bit packed array (cached next to the
-FASTA) and counted by dig_count_contexts instead of per-region pysam fetches; the mutation contexts come from
+FASTA) and counted by dig_count_contexts2 / dig_count_contexts5 instead of per-region pysam fetches; the mutation contexts come from
 dig_mutation_contexts over the same genome.
 """
 import argparse
@@ -31,8 +31,8 @@ from digdriver_amd.sequence_model import sequence_tools                    # noq
 def count_genome_context(args):
     if bool(args.h5) == bool(args.bed):
         raise SystemExit("Exactly one of --h5 or --bed must be supplied.")
-    if (args.up, args.down) != (1, 1):
-        raise SystemExit("This build counts trinucleotide contexts (--up 1 --down 1).")
+    if (args.up, args.down) not in ((1, 1), (2, 2)):
+        raise SystemExit("This build counts trinucleotide (--up 1 --down 1) or penta-nucleotide (--up 2 --down 2) contexts.")
     if args.map_file:
         raise SystemExit("--map-file needs the bigWig reader of the reference's preprocessing stack (out of scope).")
     if args.h5:
@@ -44,14 +44,14 @@ def count_genome_context(args):
         df_bed[0] = df_bed[0].astype(int)
     df_bed = df_bed.sort_values(by=[0, 1])
     print('Counting nucleotide contexts in {} regions'.format(len(df_bed)))
-    df = sequence_tools.count_contexts_in_bed(args.fasta, df_bed, n_up=1, n_down=1)
+    df = sequence_tools.count_contexts_in_bed(args.fasta, df_bed, n_up=args.up, n_down=args.down)
     idx = df_bed.iloc[:, 0:3].values
     print('Saving context counts to {}'.format(args.fout))
     with mapfile.batch(args.fout):
         mapfile.write_frame(args.fout, 'genome_counts', df.sum(axis=0).to_frame('COUNT'))
         mapfile.write_frame(args.fout, 'all_window_genome_counts', df)
         mapfile.write_array(args.fout, 'idx', idx.astype(np.int32))
-        mapfile.write_attrs(args.fout, n_up=1, n_down=1, collapse=0)
+        mapfile.write_attrs(args.fout, n_up=args.up, n_down=args.down, collapse=0)
 
 
 def add_mutation_context(args):
@@ -99,7 +99,7 @@ def preprocess_tiled(args):
 def parse_args(text=None):
     parser = argparse.ArgumentParser(description='Sequence-context preprocessing for the burden-test path (MI355X build).')
     sub = parser.add_subparsers()
-    a = sub.add_parser('countGenomeContext', help='trinucleotide context counts of genome windows')
+    a = sub.add_parser('countGenomeContext', help='tri- or penta-nucleotide context counts of genome windows')
     a.add_argument('fasta', type=str, help='reference genome FASTA')
     a.add_argument('fout', type=str, help='container to write')
     a.add_argument('--h5', type=str, default='', help='container holding the windows as `idx`')
