@@ -72,6 +72,12 @@ int launch_tile_probs_rows(const uint32_t* words, int64_t n_words, const int64_t
                            int64_t C, int n_up, int binsize, int64_t n_tiles, double* pt, int64_t* first_pos, int32_t* n_valid,
                            hipStream_t stream);
 
+// The 2-bit genome of dig_count_contexts2 (include/dig_hip.h): array base = kGenome2PadBases + chrom_off + position, 16 bases
+// per word; the bucket index of the non-ACGT run list holds, per 2^kGenome2BucketShift array bases, the first run that ends
+// behind the bucket's first base.
+constexpr int kGenome2PadBases = 64;
+constexpr int kGenome2BucketShift = 12;
+
 inline int grid_for(int64_t n, int block, int max_blocks_per_cu = 8)
 {
     int64_t want = (n + block - 1) / block;

@@ -353,6 +353,57 @@ int dig_mutation_contexts_host(const uint32_t* words2, int64_t n_words2, const i
                    st.out(status, n_rows), st.out(context, n_rows), st.scratch(ws), ws, nullptr);
 }
 
+int dig_mutation_function_host(const uint32_t* words2, int64_t n_words2, const int64_t* nint_start, const int64_t* nint_end, int64_t n_int,
+                               const int32_t* nint_bucket, int64_t n_buckets, const int64_t* chrom_off, const int64_t* chrom_len,
+                               int n_chrom, const int32_t* gene_chrom, const uint8_t* gene_minus, const int64_t* blk_ptr,
+                               const int64_t* blk_start, const int64_t* blk_end, const int64_t* cds_off, const int64_t* spl_ptr,
+                               const int64_t* spl_pos, int64_t n_genes, const int32_t* pair_gene, const int64_t* pair_start,
+                               const int64_t* pair_end, const uint8_t* pair_kind, const uint8_t* pair_ref, const uint8_t* pair_alt,
+                               int64_t n_pairs, uint8_t* impact, uint8_t* status, int32_t* n_cds, int32_t* cds_min, int32_t* cds_max,
+                               int device)
+{
+    DIG_REQUIRE(n_pairs >= 0 && n_genes >= 0, "n_pairs, n_genes >= 0");
+    DIG_REQUIRE(n_words2 >= 28 && n_chrom >= 0 && n_int >= 0, "n_int, n_chrom >= 0, n_words2 >= 28 (pad words)");
+    if (n_pairs == 0) return DIG_OK;
+    DIG_REQUIRE(words2 && chrom_off && chrom_len && blk_ptr && spl_ptr, "non-null genome arrays, blk_ptr, spl_ptr");
+    DIG_REQUIRE(n_int == 0 || (nint_start && nint_end && nint_bucket && n_buckets >= 1), "interval list with its bucket index");
+    DIG_REQUIRE(pair_gene && pair_start && pair_end && pair_kind && pair_ref && pair_alt, "non-null pair arrays");
+    DIG_REQUIRE(impact && status && n_cds && cds_min && cds_max, "non-null outputs");
+    const int64_t n_blk = blk_ptr[n_genes], n_spl = spl_ptr[n_genes];
+    DIG_REQUIRE(blk_ptr[0] == 0 && spl_ptr[0] == 0 && n_blk >= 0 && n_spl >= 0, "blk_ptr, spl_ptr start at 0");
+    DIG_REQUIRE(n_genes == 0 || (gene_chrom && gene_minus), "non-null gene_chrom, gene_minus");
+    DIG_REQUIRE(n_blk == 0 || (blk_start && blk_end && cds_off), "non-null block arrays");
+    DIG_REQUIRE(n_spl == 0 || spl_pos, "non-null spl_pos");
+    for (int c = 0; c < n_chrom; ++c)
+        DIG_REQUIRE(chrom_off[c] >= 0 && chrom_off[c] + chrom_len[c] + 64 <= (n_words2 - 24) * 16, "chromosomes inside the genome array");
+    for (int64_t j = 0; j < n_int; ++j)
+        DIG_REQUIRE(nint_start[j] < nint_end[j] && (j == 0 || nint_end[j - 1] < nint_start[j]), "intervals sorted, disjoint, not touching");
+    for (int64_t g = 0; g < n_genes; ++g) {
+        DIG_REQUIRE(gene_chrom[g] >= 0 && gene_chrom[g] < n_chrom, "gene chromosome index within [0, n_chrom)");
+        DIG_REQUIRE(blk_ptr[g] <= blk_ptr[g + 1] && spl_ptr[g] <= spl_ptr[g + 1], "blk_ptr, spl_ptr non-decreasing");
+        int64_t len = 0;
+        for (int64_t b = blk_ptr[g]; b < blk_ptr[g + 1]; ++b) {
+            DIG_REQUIRE(blk_start[b] >= 1 && blk_start[b] <= blk_end[b] && blk_end[b] <= chrom_len[gene_chrom[g]],
+                        "CDS blocks 1-based, closed, inside the chromosome");
+            DIG_REQUIRE(b == blk_ptr[g] || blk_end[b - 1] < blk_start[b], "CDS blocks of a gene ascending and disjoint");
+            DIG_REQUIRE(cds_off[b] == len, "cds_off: the CDS length in front of the block");
+            len += blk_end[b] - blk_start[b] + 1;
+        }
+        DIG_REQUIRE(len % 3 == 0 && len <= INT32_MAX, "CDS length a multiple of 3 below 2^31");
+        for (int64_t q = spl_ptr[g] + 1; q < spl_ptr[g + 1]; ++q) DIG_REQUIRE(spl_pos[q - 1] < spl_pos[q], "splice positions of a gene ascending");
+    }
+    for (int64_t i = 0; i < n_pairs; ++i) DIG_REQUIRE(pair_gene[i] >= 0 && pair_gene[i] < n_genes, "pair gene index within [0, n_genes)");
+    const size_t nc = std::max(n_chrom, 1), ng = (size_t)n_genes;
+    Staging st(device);
+    return st.call(dig_mutation_function, st.in(words2, n_words2), n_words2, st.in(nint_start, n_int), st.in(nint_end, n_int), n_int,
+                   st.in(nint_bucket, n_int ? n_buckets : 0), n_buckets, st.in(chrom_off, nc), st.in(chrom_len, nc), n_chrom,
+                   st.in(gene_chrom, ng), st.in(gene_minus, ng), st.in(blk_ptr, ng + 1), st.in(blk_start, n_blk), st.in(blk_end, n_blk),
+                   st.in(cds_off, n_blk), st.in(spl_ptr, ng + 1), st.in(spl_pos, n_spl), n_genes, st.in(pair_gene, n_pairs),
+                   st.in(pair_start, n_pairs), st.in(pair_end, n_pairs), st.in(pair_kind, n_pairs), st.in(pair_ref, n_pairs),
+                   st.in(pair_alt, n_pairs), n_pairs, st.out(impact, n_pairs), st.out(status, n_pairs), st.out(n_cds, n_pairs),
+                   st.out(cds_min, n_pairs), st.out(cds_max, n_pairs), nullptr);
+}
+
 int dig_element_pipeline_host(const double* bin_mu, const double* bin_std, const int32_t* bin_y, const uint8_t* bin_flag,
                               const int32_t* bin_ctx, const int64_t* ov_ptr, const int32_t* ov_idx, const int32_t* L,
                               const uint8_t* strand_minus, const int32_t* gene_length, const double* d_pr,

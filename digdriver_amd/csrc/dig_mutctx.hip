@@ -23,8 +23,8 @@
 namespace dig {
 
 constexpr int kMcBlock = 256;
-constexpr int kMcPadBases = 64;           // the 2-bit layout of dig_count_contexts2
-constexpr int kMcBucketShift = 12;
+constexpr int kMcPadBases = kGenome2PadBases;           // the 2-bit layout of dig_count_contexts2 (dig_common.hpp)
+constexpr int kMcBucketShift = kGenome2BucketShift;
 constexpr unsigned kMcMatch = 1u, kMcHead = 2u, kMcNeedsHost = 4u;
 
 __device__ __forceinline__ uint64_t mc_upto(int lane)           // lanes 0 .. lane

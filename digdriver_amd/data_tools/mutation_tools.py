@@ -385,3 +385,224 @@ def tabulate_nonc_mutations_at_sites(f_sites, f_mut, return_sites=False):
 def tabulate_sites_in_element(f_sites, f_mut):
     """mutation_tools.py:279-283"""
     return tabulate_nonc_mutations_at_sites(f_sites, f_mut).set_index('ELT')[['OBS_SAMPLES', 'OBS_SNV']]
+
+
+# ---------------------------------------------------------------------------------------------
+# genic function of mutations (DigPreprocess.py addMutationFunction; reference: scripts/mutationFunction.R, which needs R,
+# Bioconductor and dNdScv's refcds_hg19.rda) -- the gene table from a bed12 of coding exons, the CDS letters from the FASTA,
+# the interval join by dig_overlap_join_* and the per-(mutation, gene) work by dig_mutation_function
+# ---------------------------------------------------------------------------------------------
+_MF_LABEL = ('Synonymous', 'Missense', 'Nonsense', 'Stop_loss', 'Essential_Splice')
+_MF_CODE = "KNKNTTTTRSRSIIMI" "QHQHPPPPRRRRLLLL" "EDEDAAAAGGGGVVVV" "*Y*YSSSS*CWCLFLF"     # codon 16 b0 + 4 b1 + b2, A C G T = 0 1 2 3
+_MF_COMP = {'A': 'T', 'C': 'G', 'G': 'C', 'T': 'A'}
+
+
+def read_raw_mutations(f_mut):
+    """Steps 1-3 of the annotation rule: the raw call file (no header; tab separated when its first line holds a tab, else
+    whitespace separated; 5 columns CHROM POS REF ALT SAMPLE, or 6 and more CHROM START END REF ALT SAMPLE ... with pos = START + 1,
+    plain or gzip) -> frame CHROM, pos, REF, ALT, SAMPLE, start, end (1-based closed) in file order, without REF == ALT rows, rows with an
+    empty field and later copies of (SAMPLE, CHROM, pos, REF, ALT)."""
+    opener = gzip.open if f_mut.endswith('.gz') else open
+    with opener(f_mut, 'rt') as handle:
+        first = handle.readline()
+    sep = "\t" if "\t" in first else r"\s+"
+    width = len(first.rstrip("\r\n").split("\t") if sep == "\t" else first.split())
+    if width < 5:
+        raise ValueError("{}: {} columns; a raw mutation file has 5 (CHROM POS REF ALT SAMPLE) or 6 and more "
+                         "(CHROM START END REF ALT SAMPLE ...)".format(f_mut, width))
+    raw = pd.read_csv(f_mut, sep=sep, header=None, names=list(range(width)), dtype=str, keep_default_na=False, na_filter=False,
+                      engine="c" if sep == "\t" else "python", skip_blank_lines=True)
+    cols = [0, 1, 2, 3, 4] if width == 5 else [0, 1, 3, 4, 5]
+    df = raw[cols].fillna('')                                           # (a row shorter than the first one: its missing fields are empty)
+    df.columns = ['CHROM', 'pos', 'REF', 'ALT', 'SAMPLE']
+    for c in df.columns:
+        df[c] = df[c].str.strip()
+    df = df[(df != '').all(axis=1) & (df.REF != df.ALT)]
+    try:
+        df = df.assign(pos=df.pos.astype(np.int64) + (0 if width == 5 else 1))
+    except ValueError as exc:
+        raise ValueError("{}: a position that is not an integer ({})".format(f_mut, exc))
+    df = df.drop_duplicates(['SAMPLE', 'CHROM', 'pos', 'REF', 'ALT']).reset_index(drop=True)
+    shift = (df.REF.str[:1] == df.ALT.str[:1]) & (df.REF.str.len() > df.ALT.str.len())     # a deletion written from the base in front
+    return df.assign(start=df.pos + shift.astype(np.int64), end=df.pos + df.REF.str.len().astype(np.int64) - 1)
+
+
+def _gene_range_join(r_chrom, r_start, r_end, m_chrom, m_start, m_end, on_device):
+    """(mutation row, range row) pairs of the closed overlap of mutations and gene ranges (both 1-based closed, same chromosome
+    label; ranges sorted by (chrom, start)): dig_overlap_join_count / _fill, the device form or the `_host` twins."""
+    from .. import _lib
+    labels = {lab: i + 1 for i, lab in enumerate(dict.fromkeys(r_chrom.tolist()))}
+    rc = np.array([labels[c] for c in r_chrom.tolist()], np.int64)
+    codes, uniq = pd.factorize(m_chrom)
+    mc = np.array([labels.get(u, 0) for u in uniq], np.int64)[codes] if len(codes) else np.zeros(0, np.int64)
+    rs, re_ = np.asarray(r_start, np.int64) - 1, np.asarray(r_end, np.int64)                # half-open, 0-based
+    ms, me = _lib.as_host(np.asarray(m_start, np.int64) - 1, np.int64), _lib.as_host(m_end, np.int64)
+    if len(rs) == 0 or len(ms) == 0:
+        return np.zeros(0, np.int64), np.zeros(0, np.int64)
+    if on_device:
+        import torch
+        from . import tabulate_gpu
+        dev = torch.device("cuda", 0)
+        blocks = tabulate_gpu.ElementBlocks(rc, rs, re_, np.arange(len(rs)), len(rs), dev)   # (the ranges are sorted already: order kept)
+        t = lambda a: torch.as_tensor(a, device=dev)
+        pm, pb = tabulate_gpu.overlap_pairs(blocks, t(mc), t(ms), t(me))
+        return pm.cpu().numpy().astype(np.int64), pb.cpu().numpy().astype(np.int64)
+    runmax = np.empty_like(re_)
+    for c in np.unique(rc):
+        sel = rc == c
+        runmax[sel] = np.maximum.accumulate(re_[sel])
+    keys = [_lib.as_host(a, np.int64) for a in ((rc << 40) | rs, (rc << 40) | runmax, re_)]
+    h = _lib.host_ptr
+    counts = np.zeros(len(ms), np.int32)
+    _lib.call("dig_overlap_join_count_host", h(keys[0]), h(keys[1]), h(keys[2]), len(rs), h(mc), h(ms), h(me), len(ms), h(counts), 0)
+    offsets = np.cumsum(counts, dtype=np.int64) - counts
+    total = int(counts.sum(dtype=np.int64))
+    pm, pb = np.zeros(max(total, 1), np.int32), np.zeros(max(total, 1), np.int32)
+    if total:
+        _lib.call("dig_overlap_join_fill_host", h(keys[0]), h(keys[1]), h(keys[2]), len(rs), h(mc), h(ms), h(me), len(ms), h(offsets),
+                  total, h(pm), h(pb), 0)
+    return pm[:total].astype(np.int64), pb[:total].astype(np.int64)
+
+
+def _snv_function_from_letters(genome, genes, gene_chrom, g, pos, ref, alt):
+    """(impact, wrong_ref) of one SNV pair the kernel left to the host (DIG_MF_HOST: the base or its codon holds a letter other
+    than ACGT), from PackedGenome's letters: a codon with such a letter translates to X, as seqinr::translate does."""
+    ci = int(gene_chrom[g])
+    letter = lambda p: genome.letters(ci, p - 1, p).decode('ascii')
+    minus = bool(genes.minus[g])
+    wrong = letter(pos) != ref
+    spl = genes.spl_pos[genes.spl_ptr[g]:genes.spl_ptr[g + 1]]
+    if (spl == pos).any():
+        return 4, wrong
+    b0, b1 = int(genes.blk_ptr[g]), int(genes.blk_ptr[g + 1])
+    b = b0 + int(np.searchsorted(genes.blk_start[b0:b1], pos, side='right')) - 1
+    f = int(genes.cds_off[b] + pos - genes.blk_start[b])                 # 0-based, genome order
+    n = int(genes.cds_len[g])
+    pos_ind = n - f if minus else f + 1
+    k = (pos_ind + 2) // 3
+    old = []
+    for t in range(3 * k - 2, 3 * k + 1):                                # the codon's CDS indices, transcript direction
+        ft = n - t if minus else t - 1
+        bt = b0 + int(np.searchsorted(genes.cds_off[b0:b1], ft, side='right')) - 1
+        c = letter(int(genes.blk_start[bt] + ft - genes.cds_off[bt]))
+        old.append(_MF_COMP.get(c, 'N') if minus else c)
+    new = list(old)
+    new[pos_ind - 3 * (k - 1) - 1] = _MF_COMP[alt] if minus else alt
+    aa = lambda cod: _MF_CODE[16 * "ACGT".index(cod[0]) + 4 * "ACGT".index(cod[1]) + "ACGT".index(cod[2])] \
+        if all(x in "ACGT" for x in cod) else 'X'
+    old_aa, new_aa = aa(old), aa(new)
+    impact = 0 if new_aa == old_aa else 2 if new_aa == '*' else 1 if old_aa != '*' else 3
+    return impact, wrong
+
+
+def classify_pairs_on_gpu(genome, genes, gene_chrom, pair_gene, pair_start, pair_end, pair_kind, pair_ref, pair_alt, on_device=False):
+    """The classifier of annotate_mutation_function: engine.mutation_function on the pairs, the DIG_MF_HOST pairs finished from
+    the genome's letters -> host arrays (impact, wrong_ref, n_cds, cds_min, cds_max)."""
+    from .. import engine
+    out = engine.mutation_function(genome, genes, gene_chrom, pair_gene, pair_start, pair_end, pair_kind, pair_ref, pair_alt,
+                                   on_device=on_device)
+    impact, status, n_cds, cds_min, cds_max = [a.cpu().numpy() if on_device else a for a in out]
+    if (status == engine.MF_OUTSIDE).any():
+        raise ValueError("a (mutation, gene) pair of the join lies outside the gene's ranges")
+    wrong = status == engine.MF_WRONG_REF
+    impact = impact.copy()
+    for i in np.flatnonzero(status == engine.MF_HOST):
+        impact[i], wrong[i] = _snv_function_from_letters(genome, genes, gene_chrom, int(pair_gene[i]), int(pair_start[i]),
+                                                         "ACGT"[pair_ref[i]], "ACGT"[pair_alt[i]])
+    return impact, wrong, n_cds, cds_min, cds_max
+
+
+def annotate_mutation_function(f_mut, f_out, genes, genome, splice_offsets=None, on_device=None, join=None, classify=None):
+    """scripts/mutationFunction.R: the raw call file f_mut annotated with GENE and ANNOT, written to f_out as CHROM START END REF
+    ALT SAMPLE GENE ANNOT (tab separated, no header, START 0-based, integers).  genes: a bed12 file of coding exons or a GeneSet;
+    genome: a FASTA path or a PackedGenome.  A mutation outside every gene range (CDS blocks and essential-splice positions) gets
+    GENE "." and Noncoding / Noncoding_INDEL; every other one a row per gene it touches: an SNV (REF and ALT each one of ACGT)
+    Synonymous / Missense / Nonsense / Stop_loss / Essential_Splice, anything else cds_INDEL or INDEL_{min}_{max}_{ins|del}{frshift|
+    inframe} / INDEL_{min}_{max}_mnv with the range of CDS indices it covers.  SNV pairs whose REF is not the genome's base are
+    left out: 10 % or more of the coding SNV pairs raise ValueError, fewer print a warning.  Rows are sorted (stably, from the
+    order coding SNVs, noncoding SNVs, coding others, noncoding others) by (CHROM as bytes, START, END).
+    join / classify: the two GPU steps as functions (default: dig_overlap_join_* and dig_mutation_function; `on_device` None = the
+    device forms unless the process declared itself torch-free) -- join(r_chrom, r_start, r_end, m_chrom, m_start, m_end) ->
+    (mutation row, range row) pairs; classify(genome, genes, gene_chrom, gene, start, end, kind, ref, alt) -> (impact, wrong_ref,
+    n_cds, cds_min, cds_max).  Returns a dict of row counts."""
+    from .. import _lib
+    from ..sequence_model import sequence_tools
+    from . import gene_annotation
+    dev = (not _lib.TORCH_FREE) if on_device is None else bool(on_device)
+    if join is None:
+        join = lambda *a: _gene_range_join(*a, on_device=dev)
+    if classify is None:
+        classify = lambda *a: classify_pairs_on_gpu(*a, on_device=dev)
+    if not isinstance(genes, gene_annotation.GeneSet):
+        genes = gene_annotation.load_cds_bed12(genes, splice_offsets=splice_offsets)
+    if genome is not None and not hasattr(genome, 'chrom_index'):
+        genome = sequence_tools.load_genome(genome)
+    gene_chrom = None
+    if genome is not None:
+        genes, gene_chrom = genes.on_genome(genome)
+    df = read_raw_mutations(f_mut)
+    M = len(df)
+    ref, alt = df.REF.to_numpy(dtype=object), df.ALT.to_numpy(dtype=object)
+    is_snv = (df.REF.isin(list("ACGT")) & df.ALT.isin(list("ACGT"))).to_numpy()
+    start, end = df.start.to_numpy(np.int64), df.end.to_numpy(np.int64)
+
+    r_chrom, r_start, r_end, r_gene = genes.ranges()
+    pm, pr = join(r_chrom, r_start, r_end, df.CHROM.to_numpy(dtype=object), start, end)
+    pair = np.unique(np.stack([np.asarray(pm, np.int64), r_gene[np.asarray(pr, np.int64)]], axis=1), axis=0) if len(pm) \
+        else np.zeros((0, 2), np.int64)                                   # distinct (mutation, gene), mutation-major, genes ascending
+    pmut, pgene = pair[:, 0], pair[:, 1]
+    coding = np.zeros(M, bool)
+    coding[pmut] = True
+
+    code = {c: i for i, c in enumerate("ACGT")}
+    bare_ref = df.REF.str.replace('-', '', regex=False).str.len().to_numpy()
+    bare_alt = df.ALT.str.replace('-', '', regex=False).str.len().to_numpy()
+    kind = np.where(is_snv, 0, np.where(bare_ref < bare_alt, 1, 2)).astype(np.uint8)
+    snv_code = lambda col: np.array([code.get(x, 0) for x in col.tolist()], np.uint8)
+    p_ref, p_alt = snv_code(ref[pmut]), snv_code(alt[pmut])
+    impact, wrong, n_cds, cds_min, cds_max = classify(genome, genes, gene_chrom, pgene.astype(np.int32), start[pmut], end[pmut],
+                                                      kind[pmut], p_ref, p_alt) if len(pmut) else \
+        (np.zeros(0, np.uint8), np.zeros(0, bool), np.zeros(0, np.int32), np.zeros(0, np.int32), np.zeros(0, np.int32))
+    impact, wrong = np.asarray(impact), np.asarray(wrong, bool)
+    p_snv = is_snv[pmut]
+    n_coding_snv, n_wrong = int(p_snv.sum()), int((wrong & p_snv).sum())
+    if n_wrong:
+        text = "{} ({:.2g}%) mutations have a wrong reference base".format(n_wrong, 100.0 * n_wrong / n_coding_snv)
+        if 10 * n_wrong >= n_coding_snv:
+            raise ValueError(text + ": wrong assembly? Confirm that the mutations and the FASTA are of the same assembly and species.")
+        print("WARNING: " + text + " and were left out.")
+
+    annot = np.empty(len(pmut), dtype=object)
+    label = np.array(_MF_LABEL, dtype=object)
+    if (impact[p_snv & ~wrong] > 4).any():
+        raise ValueError("the classifier left {} SNV pairs without an effect class".format(int((impact[p_snv & ~wrong] > 4).sum())))
+    annot[p_snv] = label[np.minimum(impact[p_snv], 4)]                  # (wrong-REF pairs are left out below, whatever their class)
+    other = np.flatnonzero(~p_snv)
+    if other.size:
+        k, n = kind[pmut[other]], np.asarray(n_cds)[other]
+        what = np.where(bare_ref[pmut[other]] < bare_alt[pmut[other]], 'ins', np.where(bare_ref[pmut[other]] > bare_alt[pmut[other]], 'del', 'mnv'))
+        tail = np.where(what == 'mnv', '', np.where(n % 3 == 0, 'inframe', 'frshift'))
+        annot[other] = ["cds_INDEL" if c == 0 else "INDEL_%d_%d_%s%s" % (a, b, w, t)
+                        for c, a, b, w, t in zip(n.tolist(), np.asarray(cds_min)[other].tolist(), np.asarray(cds_max)[other].tolist(),
+                                                 what.tolist(), tail.tolist())]
+    names = np.array(genes.names, dtype=object)
+    keep_snv = p_snv & ~wrong
+    # the reference's row order in front of its sort: coding SNVs, noncoding SNVs, coding others, noncoding others
+    rows = np.concatenate([pmut[keep_snv], np.flatnonzero(~coding & is_snv), pmut[~p_snv], np.flatnonzero(~coding & ~is_snv)])
+    nc_snv, nc_other = int((~coding & is_snv).sum()), int((~coding & ~is_snv).sum())
+    gene_col = np.concatenate([names[pgene[keep_snv]], np.full(nc_snv, '.', dtype=object), names[pgene[~p_snv]],
+                               np.full(nc_other, '.', dtype=object)])
+    annot_col = np.concatenate([annot[keep_snv], np.full(nc_snv, 'Noncoding', dtype=object), annot[~p_snv],
+                                np.full(nc_other, 'Noncoding_INDEL', dtype=object)])
+    chrom = df.CHROM.to_numpy(dtype=object)[rows]
+    _, chrom_rank = np.unique(np.array([c.encode() for c in chrom.tolist()], dtype=object), return_inverse=True) if len(rows) \
+        else (None, np.zeros(0, np.int64))
+    order = np.lexsort((end[rows], start[rows] - 1, chrom_rank))          # (lexsort is stable)
+    rows = rows[order]
+    out = pd.DataFrame({'CHROM': chrom[order], 'START': start[rows] - 1, 'END': end[rows], 'REF': ref[rows], 'ALT': alt[rows],
+                        'SAMPLE': df.SAMPLE.to_numpy(dtype=object)[rows], 'GENE': gene_col[order], 'ANNOT': annot_col[order]})
+    out.to_csv(f_out, sep="\t", index=False, header=False)
+    if len(out) > M:
+        print("WARNING: {} mutation entries were duplicated because they overlap multiple genes.".format(len(out) - M))
+    return dict(n_mutations=M, n_rows=len(out), coding_snv=int(keep_snv.sum()), noncoding_snv=nc_snv, coding_other=int((~p_snv).sum()),
+                noncoding_other=nc_other, wrong_ref=n_wrong)

@@ -787,6 +787,64 @@ def mutation_contexts(genome, chroms, starts, refs, n_up=2, n_down=2, collapse=F
     return status, context
 
 
+MF_KIND_SNV, MF_KIND_INS, MF_KIND_OTHER = 0, 1, 2               # include/dig_hip.h DIG_MF_*
+MF_SYN, MF_MIS, MF_NONS, MF_STOP_LOSS, MF_SPLICE, MF_NONE = 0, 1, 2, 3, 4, 255
+MF_OK, MF_WRONG_REF, MF_HOST, MF_OUTSIDE = 0, 1, 2, 3
+
+
+def mutation_function(genome, genes, gene_chrom, pair_gene, pair_start, pair_end, pair_kind, pair_ref, pair_alt, device=0,
+                      on_device=True):
+    """Genic function of (mutation, gene) pairs (scripts/mutationFunction.R; dig_mutation_function) over a PackedGenome.
+    genes: a gene_annotation.GeneSet; gene_chrom: the genome's chromosome index of every gene (GeneSet.on_genome).  Pairs: gene
+    index, 1-based closed start / end, kind (MF_KIND_*), REF / ALT codes 0-3 on the + strand (SNVs; ignored otherwise).
+    Returns (impact u8, status u8, n_cds i32, cds_min i32, cds_max i32): MF_SYN ... MF_SPLICE / MF_NONE and MF_OK / MF_WRONG_REF /
+    MF_HOST / MF_OUTSIDE as include/dig_hip.h describes them.  on_device=True takes numpy arrays or tensors, keeps the genome
+    resident in HBM and returns device tensors; False goes through the host twin on numpy arrays."""
+    G = len(genes)
+    gch = _lib.as_host(gene_chrom, np.int32).ravel()
+    assert len(gch) == G
+    if G and ((gch < 0).any() or (gch >= len(genome.names)).any()):
+        raise ValueError("gene chromosome index outside the genome")
+    last = genes.blk_end[genes.blk_ptr[1:] - 1] if G else np.zeros(0, np.int64)
+    if G and ((genes.blk_start < 1).any() or (last > genome.lengths[gch]).any()):
+        raise ValueError("a gene's CDS blocks reach outside its chromosome")
+    if G and (genes.cds_len % 3).any():
+        raise ValueError("a gene's CDS length is not a multiple of 3")
+    table = (gch, genes.minus, genes.blk_ptr, genes.blk_start, genes.blk_end, genes.cds_off, genes.spl_ptr, genes.spl_pos)
+    dtypes = (np.int32, np.int64, np.int64, np.uint8, np.uint8, np.uint8)
+    if on_device:
+        import torch
+        dev = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
+        tdt = (torch.int32, torch.int64, torch.int64, torch.uint8, torch.uint8, torch.uint8)
+        pairs = [torch.as_tensor(a, dtype=d, device=dev).contiguous().ravel()
+                 for a, d in zip((pair_gene, pair_start, pair_end, pair_kind, pair_ref, pair_alt), tdt)]
+        n = pairs[0].numel()
+        assert all(a.numel() == n for a in pairs)
+        if n and (int(pairs[0].min()) < 0 or int(pairs[0].max()) >= G):
+            raise ValueError("pair gene index outside the gene table")
+        impact, status = (torch.empty(n, dtype=torch.uint8, device=dev) for _ in range(2))
+        n_cds, cds_min, cds_max = (torch.empty(n, dtype=torch.int32, device=dev) for _ in range(3))
+        p = _lib.dev_ptr
+        with torch.cuda.device(dev):
+            w2, ns, ne, bk, off, ln = genome.on_device2(dev)
+            tab = [torch.as_tensor(a, device=dev) for a in table]
+            _lib.call("dig_mutation_function", p(w2), w2.numel(), p(ns) if ns.numel() else None, p(ne) if ns.numel() else None,
+                      ns.numel(), p(bk) if ns.numel() else None, bk.numel(), p(off), p(ln), len(genome.names), *[p(a) for a in tab], G,
+                      *[p(a) for a in pairs], n, p(impact), p(status), p(n_cds), p(cds_min), p(cds_max), _lib.stream_ptr())
+        return impact, status, n_cds, cds_min, cds_max
+    pairs = [_lib.as_host(a, d).ravel() for a, d in zip((pair_gene, pair_start, pair_end, pair_kind, pair_ref, pair_alt), dtypes)]
+    n = len(pairs[0])
+    assert all(len(a) == n for a in pairs)
+    impact, status = np.empty(n, np.uint8), np.empty(n, np.uint8)
+    n_cds, cds_min, cds_max = np.empty(n, np.int32), np.empty(n, np.int32), np.empty(n, np.int32)
+    h = _lib.host_ptr
+    w2, ns, ne, bk = genome.two_bit()
+    _lib.call("dig_mutation_function_host", h(w2), w2.size, h(ns) if ns.size else None, h(ne) if ns.size else None, ns.size,
+              h(bk) if ns.size else None, bk.size, h(genome.offsets), h(genome.lengths), len(genome.names), *[h(a) for a in table], G,
+              *[h(a) for a in pairs], n, h(impact), h(status), h(n_cds), h(cds_min), h(cds_max), device if isinstance(device, int) else 0)
+    return impact, status, n_cds, cds_min, cds_max
+
+
 def tiled_nb_test(pt, k, mu, sigma, device=0):
     """Per-tile exact NB test (nb_model.py:141-178).  pt f64 [n_bins, n_tiles] or [C, n_bins, n_tiles];
     k i32 [C, n_bins, n_tiles]; mu, sigma f64 [C, n_bins].  Returns (pval, exp) [C, n_bins, n_tiles]."""

@@ -457,6 +457,60 @@ int dig_mutation_contexts_host(const uint32_t *words2, int64_t n_words2, const i
                                const uint8_t *row_ref, int64_t n_rows, int n_up, int n_down, int collapse, uint8_t *status,
                                uint32_t *context, int device);
 
+/* ---- genic function of mutations (DigPreprocess.py addMutationFunction; scripts/mutationFunction.R) ---- *
+ * One work item is one (mutation, gene) pair of the interval join of the mutations with the genes' CDS blocks and
+ * essential-splice positions, over the 2-bit genome of dig_count_contexts2 (words2, the run list and its bucket index,
+ * chrom_off / chrom_len exactly as there).  All genome positions are 1-BASED and intervals closed.
+ * Gene table (n_genes genes):
+ *   gene_chrom i32 within [0, n_chrom); gene_minus u8 (1: the gene lies on the - strand);
+ *   blk_ptr i64 [n_genes + 1], blk_start / blk_end i64 [blk_ptr[n_genes]]: the CDS blocks of gene g, ascending and disjoint;
+ *   cds_off i64 per block: the CDS length in front of the block in genome order (the CDS length of a gene is a multiple of 3);
+ *   spl_ptr i64 [n_genes + 1], spl_pos i64 [spl_ptr[n_genes]]: the essential-splice positions of gene g, ascending.
+ * Pairs: pair_gene i32, pair_start / pair_end i64, pair_kind u8 (DIG_MF_KIND_*); SNVs: pair_ref / pair_alt u8, the codes 0-3
+ *   (A C G T) of REF and ALT on the + strand (anything else in pair_ref never matches; pair_alt is taken modulo 4).
+ * Outputs per pair:
+ *   SNV (pos = pair_start): impact = DIG_MF_SPLICE when pos is a splice position of the gene; otherwise pos_ind, the 1-based index
+ *     of pos in the CDS read in transcript direction, its codon (CDS positions 3 ceil(pos_ind / 3) - 2 .. 3 ceil(pos_ind / 3), which
+ *     may lie in up to three blocks; complemented for a - gene) and the codon with ALT in place go through the standard genetic
+ *     code: same amino acid DIG_MF_SYN, else new stop DIG_MF_NONS, else old not stop DIG_MF_MIS, else DIG_MF_STOP_LOSS.
+ *     n_cds = 1, cds_min = cds_max = pos_ind (n_cds = 0 for a splice position).
+ *     status: DIG_MF_OK; DIG_MF_WRONG_REF (the genome base at pos is not REF; impact is still that of ALT on the genome's codon);
+ *     DIG_MF_HOST (pos or a base of the codon is a letter other than ACGT: impact = DIG_MF_NONE, the caller finishes the pair
+ *     from the letters);
+ *     DIG_MF_OUTSIDE (pos is neither in a CDS block nor a splice position of the gene, or the gene index is out of range).
+ *   other kinds: impact = DIG_MF_NONE, status = DIG_MF_OK; n_cds, cds_min, cds_max = count, minimum and maximum of the CDS
+ *     indices (transcript direction) of the positions pair_start .. pair_end (DIG_MF_KIND_INS: pair_start - 1 .. pair_end) that lie
+ *     in the gene's CDS blocks; no genome read.  n_cds = 0 (cds_min = cds_max = 0) when no position does. */
+#define DIG_MF_KIND_SNV 0
+#define DIG_MF_KIND_INS 1
+#define DIG_MF_KIND_OTHER 2
+#define DIG_MF_SYN 0
+#define DIG_MF_MIS 1
+#define DIG_MF_NONS 2
+#define DIG_MF_STOP_LOSS 3
+#define DIG_MF_SPLICE 4
+#define DIG_MF_NONE 255
+#define DIG_MF_OK 0
+#define DIG_MF_WRONG_REF 1
+#define DIG_MF_HOST 2
+#define DIG_MF_OUTSIDE 3
+int dig_mutation_function(const uint32_t *words2, int64_t n_words2, const int64_t *nint_start, const int64_t *nint_end,
+                          int64_t n_int, const int32_t *nint_bucket, int64_t n_buckets, const int64_t *chrom_off,
+                          const int64_t *chrom_len, int n_chrom, const int32_t *gene_chrom, const uint8_t *gene_minus,
+                          const int64_t *blk_ptr, const int64_t *blk_start, const int64_t *blk_end, const int64_t *cds_off,
+                          const int64_t *spl_ptr, const int64_t *spl_pos, int64_t n_genes, const int32_t *pair_gene,
+                          const int64_t *pair_start, const int64_t *pair_end, const uint8_t *pair_kind, const uint8_t *pair_ref,
+                          const uint8_t *pair_alt, int64_t n_pairs, uint8_t *impact, uint8_t *status, int32_t *n_cds,
+                          int32_t *cds_min, int32_t *cds_max, void *stream);
+int dig_mutation_function_host(const uint32_t *words2, int64_t n_words2, const int64_t *nint_start, const int64_t *nint_end,
+                               int64_t n_int, const int32_t *nint_bucket, int64_t n_buckets, const int64_t *chrom_off,
+                               const int64_t *chrom_len, int n_chrom, const int32_t *gene_chrom, const uint8_t *gene_minus,
+                               const int64_t *blk_ptr, const int64_t *blk_start, const int64_t *blk_end, const int64_t *cds_off,
+                               const int64_t *spl_ptr, const int64_t *spl_pos, int64_t n_genes, const int32_t *pair_gene,
+                               const int64_t *pair_start, const int64_t *pair_end, const uint8_t *pair_kind,
+                               const uint8_t *pair_ref, const uint8_t *pair_alt, int64_t n_pairs, uint8_t *impact, uint8_t *status,
+                               int32_t *n_cds, int32_t *cds_min, int32_t *cds_max, int device);
+
 /* ---- result files (ABI 6; host code only) ------------------------------------------------- *
  * The text DataFrame.to_csv(path, header=True, index=True, sep="\t") writes for a frame (DigDriver.py:115-118): `header`
  * (a complete first line, no newline), then n_rows rows  label TAB col_0 TAB ... col_{n_cols-1}.

@@ -2,18 +2,20 @@
 """DigPreprocess.py -- sequence-context preprocessing on MI355X.
 
 The sub-commands of the reference's scripts/DigPreprocess.py that feed the burden-test path with context counts and
-annotated mutation files (addMutationFunction and annotMutationFile need bedtools / R and are out of scope, DESIGN.md
-section 7; addMutationContext needs only the FASTA):
+annotated mutation files.  The reference's addMutationFunction shells out to an R script that needs Bioconductor and dNdScv's
+refcds_hg19.rda; here the gene table comes from a bed12 file of coding exons (--cds-bed) and the CDS letters from the FASTA:
 
     countGenomeContext        window context counts of a genome, --up/--down 1 or 2 (DigPreprocess.py:19-73)
+    addMutationFunction       GENE and ANNOT columns of a raw call file (:102-109, scripts/mutationFunction.R)
     addMutationContext        MUT_TYPE and CONTEXT columns of a mutation file (:75-100)
+    annotMutationFile         addMutationFunction, then addMutationContext (:111-117)
     initialize_f_data         start an element-data container            (:147-153)
     preprocess_element_model  per-element L counts from bed12 + FASTA    (:129-145)
     preprocess_tiled          L counts of a tiled genome                 (:155-164)
 
 Same positional arguments and option names.  Sequence is read once into a 4-bit packed array (cached next to the
 FASTA) and counted by dig_count_contexts2 / dig_count_contexts5 instead of per-region pysam fetches; the mutation contexts come from
-dig_mutation_contexts over the same genome.
+dig_mutation_contexts and the genic function from dig_mutation_function over the same genome.
 """
 import argparse
 import os
@@ -69,6 +71,41 @@ def add_mutation_context(args):
     print('Saved annotated mutation file: {}'.format(fout))
 
 
+def _mutation_function(args, fout):
+    from digdriver_amd.data_tools import mutation_tools
+    try:
+        counts = mutation_tools.annotate_mutation_function(args.fmut, fout, args.cds_bed, args.fasta, on_device=False)
+    except (ValueError, KeyError) as exc:
+        raise SystemExit("addMutationFunction: %s" % exc)
+    print("\t{coding_snv}\tcoding SNVs\n\t{noncoding_snv}\tnoncoding SNVs\n\t{coding_other}\tcoding INDELs\n"
+          "\t{noncoding_other}\tnoncoding INDELs".format(**counts))
+
+
+def add_mutation_function(args):
+    # torch-free, as addMutationContext
+    from digdriver_amd import _lib
+    _lib.TORCH_FREE = True
+    fout = args.fout[:-3] if args.fout.endswith('.gz') else args.fout
+    _mutation_function(args, fout)
+    print('Saved annotated mutation file: {}'.format(fout))
+
+
+def annot_mutation_file(args):
+    from digdriver_amd import _lib
+    _lib.TORCH_FREE = True
+    if args.up < 0 or args.down < 0 or args.up + args.down + 1 > 16:
+        raise SystemExit("--up and --down must be >= 0 with up + down + 1 <= 16.")
+    fout = args.fout[:-3] if args.fout.endswith('.gz') else args.fout
+    print('Adding mutation function')
+    _mutation_function(args, fout)
+    print('Adding mutation context')
+    try:                                               # (load_genome keeps the packed genome of `fasta`: one pack for both steps)
+        sequence_tools.write_mutation_contexts(fout, args.fasta, fout, n_up=args.up, n_down=args.down, on_device=False)
+    except ValueError as exc:
+        raise SystemExit("annotMutationFile: %s" % exc)
+    print('Saved annotated mutation file: {}'.format(fout))
+
+
 def initialize_data(args):
     idx = mapfile.read_array(args.f_genome_counts, 'idx')
     if not mapfile.has_key(args.f_genome_counts, 'all_window_genome_counts'):
@@ -120,6 +157,26 @@ def parse_args(text=None):
     b.add_argument('--n-procs', type=int, default=1, help='accepted for compatibility')
     b.set_defaults(func=add_mutation_context)
 
+    cds_help = ('bed12 file of the coding exons of every gene (strand in column 6, CDS blocks in columns 10-12), e.g. the '
+                "reference's DIGDriver/data/genes.MARTINCORENA.bed; required: it and the FASTA replace the refcds_hg19.rda the "
+                "reference's R script loads")
+    c = sub.add_parser('addMutationFunction', help='annotate a raw call file with GENE and the genic function ANNOT')
+    c.add_argument('fmut', type=str, help='raw calls, no header: CHROM POS REF ALT SAMPLE, or CHROM START END REF ALT SAMPLE ...')
+    c.add_argument('fout', type=str, help='output file name (a trailing .gz is dropped; not compressed)')
+    c.add_argument('--cds-bed', type=str, required=True, help=cds_help)
+    c.add_argument('--fasta', type=str, required=True, help='reference genome FASTA (the CDS letters are read from it)')
+    c.set_defaults(func=add_mutation_function)
+
+    d = sub.add_parser('annotMutationFile', help='addMutationFunction followed by addMutationContext')
+    d.add_argument('fmut', type=str, help='raw calls, no header: CHROM POS REF ALT SAMPLE, or CHROM START END REF ALT SAMPLE ...')
+    d.add_argument('fasta', type=str, help='reference genome FASTA')
+    d.add_argument('fout', type=str, help='output file name (a trailing .gz is dropped; not compressed)')
+    d.add_argument('--cds-bed', type=str, required=True, help=cds_help)
+    d.add_argument('--up', type=int, default=1, help='bases upstream of the mutation in the context (1)')
+    d.add_argument('--down', type=int, default=1, help='bases downstream of the mutation in the context (1)')
+    d.add_argument('--n-procs', type=int, default=1, help='accepted for compatibility')
+    d.set_defaults(func=annot_mutation_file)
+
     e = sub.add_parser('preprocess_element_model', help='per-element context counts from a bed12 file')
     e.add_argument('f_element_data', help='element-data container (see initialize_f_data)')
     e.add_argument('f_pretrained', help='any pretrained map (kept for compatibility)')
@@ -152,5 +209,6 @@ def parse_args(text=None):
 if __name__ == "__main__":
     cli = parse_args()
     cli.func(cli)
-    if os.environ.get("DIG_CLI_ASSERT_NO_TORCH") == "1" and cli.func is add_mutation_context:
+    if os.environ.get("DIG_CLI_ASSERT_NO_TORCH") == "1" and cli.func in (add_mutation_context, add_mutation_function,
+                                                                            annot_mutation_file):
         assert "torch" not in sys.modules, "a torch-free sub-command imported torch"         # (tests: the claim above)
