@@ -1,8 +1,8 @@
 // dig_codon.hpp -- the device functions of the genic annotation that the per-gene counts of possible substitutions need as
-// well: (gene, CDS index) -> genome position, one base of the 2-bit genome, and the effect class of a codon change under the
-// standard genetic code.
+// well: (gene, CDS index) -> genome position and the effect class of a codon change under the standard genetic code (one
+// base of the 2-bit genome: genome2_base, dig_genome2.hpp).
 #pragma once
-#include "dig_common.hpp"
+#include "dig_genome2.hpp"
 
 namespace dig {
 
@@ -32,33 +32,6 @@ __device__ __forceinline__ int64_t cds_to_genome(const GeneCds& g, int64_t idx)
     const int64_t f = (g.minus ? g.len - idx : idx - 1);             // 0-based, genome order
     const int64_t b = codon_last_le(g.cds_off, g.b0, g.b1, f);       // cds_off[b0] == 0: b >= b0
     return g.blk_start[b] + (f - g.cds_off[b]);
-}
-
-// The 2-bit genome of dig_count_contexts2 with its list of non-ACGT runs and the list's bucket index (dig_common.hpp).
-struct Genome2 {
-    const uint32_t* __restrict__ words;
-    const int64_t* __restrict__ nint_start;
-    const int64_t* __restrict__ nint_end;
-    int64_t n_int;
-    const int32_t* __restrict__ nint_bucket;
-    int64_t n_buckets;
-};
-
-// code 0-3 of position p (1-based) of a chromosome at array offset `off` (pad included) of length `len`; 4 for a letter other
-// than ACGT or a position outside the chromosome (nothing is read then)
-__device__ __forceinline__ unsigned genome2_base(const Genome2& G, int64_t off, int64_t len, int64_t p)
-{
-    if (p < 1 || p > len) return 4u;
-    const int64_t g = off + p - 1;
-    const unsigned code = (G.words[g >> 4] >> (2 * (int)(g & 15))) & 3u;
-    if (G.n_int > 0) {
-        int64_t b = g >> kGenome2BucketShift;
-        if (b >= G.n_buckets) b = G.n_buckets - 1;
-        int64_t j = G.nint_bucket[b];
-        while (j < G.n_int && G.nint_end[j] <= g) ++j;
-        if (j < G.n_int && G.nint_start[j] <= g) return 4u;
-    }
-    return code;
 }
 
 // amino acid of a codon on the coding strand, codon = 16 b0 + 4 b1 + b2 with A C G T = 0 1 2 3 (the standard code, '*' = stop)

@@ -22,10 +22,12 @@ int set_error(int code, const char* fmt, ...);
                                     __FILE__, __LINE__);                                               \
     } while (0)
 
-#define DIG_REQUIRE(cond, msg)                                                                  \
+// (fn: the entry point's name, for a check that a helper makes on its behalf)
+#define DIG_REQUIRE_IN(fn, cond, msg)                                                           \
     do {                                                                                        \
-        if (!(cond)) return ::dig::set_error(DIG_EINVAL, "%s: requirement failed: %s", __func__, msg); \
+        if (!(cond)) return ::dig::set_error(DIG_EINVAL, "%s: requirement failed: %s", fn, msg); \
     } while (0)
+#define DIG_REQUIRE(cond, msg) DIG_REQUIRE_IN(__func__, cond, msg)
 
 // number of CUs of the current device (cached per device)
 int cu_count();
@@ -71,12 +73,6 @@ int launch_tile_probs_rows(const uint32_t* words, int64_t n_words, const int64_t
                            const int32_t* reg_chrom, const int64_t* reg_start, const int64_t* reg_end, int64_t R, const double* s_prob,
                            int64_t C, int n_up, int binsize, int64_t n_tiles, double* pt, int64_t* first_pos, int32_t* n_valid,
                            hipStream_t stream);
-
-// The 2-bit genome of dig_count_contexts2 (include/dig_hip.h): array base = kGenome2PadBases + chrom_off + position, 16 bases
-// per word; the bucket index of the non-ACGT run list holds, per 2^kGenome2BucketShift array bases, the first run that ends
-// behind the bucket's first base.
-constexpr int kGenome2PadBases = 64;
-constexpr int kGenome2BucketShift = 12;
 
 inline int grid_for(int64_t n, int block, int max_blocks_per_cu = 8)
 {

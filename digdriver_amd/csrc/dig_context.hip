@@ -30,7 +30,7 @@
 // shared-histogram word-per-lane form took 1.37 ms.  What bounds it now is instruction issue (about 8 lane-operations
 // per position all told): 16 or 32 copies, 5 to 10 resident workgroups per CU and removing the LDS update altogether
 // all land within 10 %.
-#include "dig_common.hpp"
+#include "dig_genome2.hpp"
 
 namespace dig {
 
@@ -225,20 +225,10 @@ __global__ __launch_bounds__(kCtxBlock, DIG_CTX_WAVES_PER_SIMD) void context_cou
 //   * a region of more than 131 068 bases is counted in segments (a counter holds 65 535).
 // =====================================================================================================================
 constexpr int kC2Block = 256;
-constexpr int kC2PadBases = 64;            // bases in front of chromosome data (one 4-word group); >= 24 pad words behind (a lane reads whole 16-word steps)
-constexpr int kC2BucketShift = 12;         // nint_bucket[b]: first run that ends behind base b << 12
 constexpr int64_t kC2SegQuads = 65534;     // 4-mers per segment: no 16-bit counter can wrap
 
 #define DIG_C2_ADD(addr, val) \
     __hip_atomic_fetch_add(reinterpret_cast<lds_u32*>(static_cast<uintptr_t>(addr)), (unsigned)(val), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)
-
-// the 6-bit code (left base in the low bits) of the window centred at base c
-__device__ __forceinline__ unsigned c2_tri(const uint32_t* __restrict__ w, int64_t c)
-{
-    const int64_t q = c - 1;
-    const uint64_t x = (uint64_t)w[q >> 4] | ((uint64_t)w[(q >> 4) + 1] << 32);
-    return (unsigned)(x >> (2 * (int)(q & 15))) & 63u;
-}
 
 __device__ __forceinline__ int c2_code_to_ctx(unsigned m)            // code (left base low) -> context index 16 L + 4 C + R
 {
@@ -316,11 +306,10 @@ __device__ __forceinline__ void c2_count_group_checked(const C2Group& g, unsigne
 // Layout: two 64 KB arrays per workgroup, one per pair of waves; row b (4-mer b) = 256 bytes = 2 waves x 32 dwords; lane l
 // of a wave owns 16 bits of dword l mod 32 of its wave's half row (low half: lanes 0-31, high half: lanes 32-63).
 __global__ __launch_bounds__(kC2Block, 1) void context_count2_kernel(
-    const uint32_t* __restrict__ words, const int64_t* __restrict__ nint_start, const int64_t* __restrict__ nint_end, int64_t n_int,
-    const int32_t* __restrict__ nint_bucket, int64_t n_buckets, const int64_t* __restrict__ chrom_off,
-    const int64_t* __restrict__ chrom_len, const int32_t* __restrict__ reg_chrom, const int64_t* __restrict__ reg_start,
-    const int64_t* __restrict__ reg_end, const uint8_t* __restrict__ reg_minus, int64_t R, int32_t* __restrict__ out)
+    Genome2 G, const int32_t* __restrict__ reg_chrom, const int64_t* __restrict__ reg_start, const int64_t* __restrict__ reg_end,
+    const uint8_t* __restrict__ reg_minus, int64_t R, int32_t* __restrict__ out)
 {
+    const uint32_t* __restrict__ words = G.words;
     __shared__ alignas(65536) uint32_t hist[2][256 * 64];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     char* half_row0 = reinterpret_cast<char*>(hist[wave >> 1]) + 128 * (wave & 1);        // the wave's 128 bytes of row 0
@@ -345,28 +334,24 @@ __global__ __launch_bounds__(kC2Block, 1) void context_count2_kernel(
         if (have) {
             const int ch = reg_chrom[r];
             minus = reg_minus[r];
-            const int64_t len = chrom_len[ch], off = chrom_off[ch] + kC2PadBases;
+            const int64_t len = G.chrom_len[ch], off = G.chrom_off[ch] + kGenome2PadBases;
             int64_t s = reg_start[r], e = reg_end[r];
             if (s == 0) s = 1;                                   // fetch_sequence :25-26
             if (e > len - 1) e = len - 1;                        // the fetch is truncated: the last centre is len - 2
             gs = off + s;
             ge = off + e;                                        // centres [gs, ge) in array bases
             if (ge < gs) ge = gs;
-            if (n_int > 0 && ge > gs) {                          // first non-ACGT run that overlaps the widened region
-                const int64_t x0 = gs - 1, x1 = ge + 1;
-                int64_t b = x0 >> kC2BucketShift;
-                if (b >= n_buckets) b = n_buckets - 1;
-                int64_t jj = nint_bucket[b];
-                while (jj < n_int && nint_end[jj] <= x0) ++jj;
-                if (jj < n_int && nint_start[jj] < x1) jf = jj;
+            if (G.n_int > 0 && ge > gs) {                        // first non-ACGT run that overlaps the widened region
+                const int64_t jj = genome2_first_run(G, gs - 1);
+                if (jj < G.n_int && G.nint_start[jj] < ge + 1) jf = jj;
             }
         }
         const int64_t a = gs & ~(int64_t)1;                      // first even base >= gs - 1
         const int64_t n4 = ge > gs ? (ge - 1 - a) >> 1 : 0;      // 4-mers at a, a + 2, ...: centres a + 1 .. a + 2 n4
         // the centre in front of the first pair and the one behind the last
         int head_code = -1, tail_code = -1;
-        if (ge > gs && a == gs) head_code = (int)c2_tri(words, gs);
-        if (ge > gs && ((ge - 1 - a) & 1)) tail_code = (int)c2_tri(words, ge - 1);
+        if (ge > gs && a == gs) head_code = (int)genome2_context<1>(words, gs);
+        if (ge > gs && ((ge - 1 - a) & 1)) tail_code = (int)genome2_context<1>(words, ge - 1);
         uint32_t T[64];                                          // context totals by CODE (left base in the low bits)
 #pragma unroll
         for (int m = 0; m < 64; ++m) T[m] = 0u;
@@ -445,30 +430,14 @@ __global__ __launch_bounds__(kC2Block, 1) void context_count2_kernel(
                 *reinterpret_cast<int4*>(row + 4 * c4) = make_int4(v[0], v[1], v[2], v[3]);
             }
             // ---- centres whose window touches a non-ACGT run: taken back in the lane's own row ----
+            // (a run's interior counts as AAA, code 0; its edge centres are looked up)
             if (jf >= 0) {
-                const int64_t x1 = ge + 1;
                 auto take = [&](unsigned code, int32_t n) {
                     int ctx = c2_code_to_ctx(code);
                     if (minus) ctx = revcomp_ctx64(ctx);
                     row[ctx] -= n;
                 };
-                for (int64_t j = jf; j < n_int; ++j) {
-                    const int64_t ns = nint_start[j], ne = nint_end[j];
-                    if (ns >= x1) break;                         // the list is sorted: nothing further can overlap
-                    const int64_t prev_end = j > 0 ? nint_end[j - 1] : -1;      // centres up to prev_end belong to run j - 1
-                    int64_t lo = ns - 1 > gs ? ns - 1 : gs;
-                    if (prev_end + 1 > lo) lo = prev_end + 1;
-                    const int64_t hi = ne + 1 < ge ? ne + 1 : ge;
-                    if (hi <= lo) continue;
-                    // interior: all three bases inside the run -> stored as AAA (code 0)
-                    const int64_t i0 = lo > ns + 1 ? lo : ns + 1, i1 = hi < ne - 1 ? hi : ne - 1;
-                    if (i1 > i0) take(0u, (int32_t)(i1 - i0));
-                    const int64_t l1 = hi < ns + 1 ? hi : ns + 1;               // left edge centres [lo, l1)
-                    int64_t e0 = ne - 1 > ns + 1 ? ne - 1 : ns + 1;             // right edge centres [e0, hi)
-                    if (e0 < lo) e0 = lo;
-                    for (int64_t c = lo; c < l1; ++c) take(c2_tri(words, c), 1);
-                    for (int64_t c = e0; c < hi; ++c) take(c2_tri(words, c), 1);
-                }
+                genome2_take_back<1>(G, jf, 1, gs, ge, [&](int64_t n) { take(0u, (int32_t)n); }, [&](unsigned code) { take(code, 1); });
             }
         }
     }
@@ -501,14 +470,14 @@ int dig_count_contexts2(const uint32_t* words2, int64_t n_words2, const int64_t*
                         const int32_t* reg_chrom, const int64_t* reg_start, const int64_t* reg_end, const uint8_t* reg_minus, int64_t R,
                         int32_t* out, void* stream)
 {
-    DIG_REQUIRE(R >= 0 && n_words2 >= 28 && n_chrom >= 0 && n_int >= 0, "R, n_int, n_chrom >= 0, n_words2 >= 28 (pad words)");
+    const Genome2 G = {words2, n_words2, nint_start, nint_end, n_int, nint_bucket, n_buckets, chrom_off, chrom_len, n_chrom};
+    if (int rc = genome2_check(__func__, G, R, true)) return rc;
     if (R == 0) return DIG_OK;
     DIG_REQUIRE(words2 && chrom_off && chrom_len && reg_chrom && reg_start && reg_end && reg_minus && out, "non-null pointers");
-    DIG_REQUIRE(n_int == 0 || (nint_start && nint_end && nint_bucket && n_buckets >= 1), "interval list with its bucket index");
     DIG_REQUIRE(((uintptr_t)words2 & 15) == 0, "words2 16-byte aligned");
     const int grid = grid_for(R, kC2Block, 1);          // one lane per region, one workgroup (128 KB of LDS) per CU
-    hipLaunchKernelGGL(context_count2_kernel, dim3(grid), dim3(kC2Block), 0, (hipStream_t)stream, words2, nint_start, nint_end, n_int,
-                       nint_bucket, n_buckets, chrom_off, chrom_len, reg_chrom, reg_start, reg_end, reg_minus, R, out);
+    hipLaunchKernelGGL(context_count2_kernel, dim3(grid), dim3(kC2Block), 0, (hipStream_t)stream, G, reg_chrom, reg_start,
+                       reg_end, reg_minus, R, out);
     DIG_HIP_TRY(hipGetLastError());
     return DIG_OK;
 }

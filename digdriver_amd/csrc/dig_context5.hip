@@ -21,26 +21,16 @@
 //     edge centres on either side looked up; a region whose windows all lie inside one run is not scanned at all;
 //   * the output stage reads bin code(ctx) for context ctx (ctx = 256 b0 + 64 b1 + 16 b2 + 4 b3 + b4, code = the same
 //     digits in reverse order); a '-' strand region reads bin 1023 - ctx, which is code(revcomp(ctx)).
-#include "dig_common.hpp"
+#include "dig_genome2.hpp"
 
 namespace dig {
 
 constexpr int kC5Block = 256;               // four waves, one region per wave at a time
-constexpr int kC5PadBases = 64;             // bases in front of chromosome data in words2 (dig_count_contexts2)
-constexpr int kC5BucketShift = 12;          // nint_bucket[b]: first run that ends behind array base b << 12
 
 typedef __attribute__((address_space(3))) unsigned lds5_u32;
 
 #define DIG_C5_ADD(addr, val) \
     __hip_atomic_fetch_add(reinterpret_cast<lds5_u32*>(static_cast<uintptr_t>(addr)), (unsigned)(val), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)
-
-// the 10-bit code (base c - 2 in the low bits) of the window centred at array base c
-__device__ __forceinline__ unsigned c5_code(const uint32_t* __restrict__ w, int64_t c)
-{
-    const int64_t q = c - 2;
-    const uint64_t x = (uint64_t)w[q >> 4] | ((uint64_t)w[(q >> 4) + 1] << 32);
-    return (unsigned)(x >> (2 * (int)(q & 15))) & 1023u;
-}
 
 // the centres k = lo .. hi - 1 of word w (array bases 16 w + k); prev / cur / next = words w - 1, w, w + 1; hist_addr = LDS
 // byte address of the wave's 4 KB-aligned histogram.  kFull: all 16 centres, no range test.
@@ -64,11 +54,11 @@ __device__ __forceinline__ int c5_rev_digits(int ctx)      // the five base-4 di
 }
 
 __global__ __launch_bounds__(kC5Block) void context_count5_kernel(
-    const uint32_t* __restrict__ words, const int64_t* __restrict__ nint_start, const int64_t* __restrict__ nint_end, int64_t n_int,
-    const int32_t* __restrict__ nint_bucket, int64_t n_buckets, const int64_t* __restrict__ chrom_off,
-    const int64_t* __restrict__ chrom_len, const int32_t* __restrict__ reg_chrom, const int64_t* __restrict__ reg_start,
-    const int64_t* __restrict__ reg_end, const uint8_t* __restrict__ reg_minus, int64_t R, int32_t* __restrict__ out)
+    Genome2 G, const int32_t* __restrict__ reg_chrom, const int64_t* __restrict__ reg_start, const int64_t* __restrict__ reg_end,
+    const uint8_t* __restrict__ reg_minus, int64_t R, int32_t* __restrict__ out)
 {
+    const uint32_t* __restrict__ words = G.words;
+    const int64_t n_int = G.n_int;
     __shared__ alignas(4096) uint32_t hist_all[kC5Block / 64][1024];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     uint32_t* hist = hist_all[wave];
@@ -81,7 +71,7 @@ __global__ __launch_bounds__(kC5Block) void context_count5_kernel(
     for (int64_t r = (int64_t)blockIdx.x * (kC5Block / 64) + wave; r < R; r += nwaves) {
         const int ch = reg_chrom[r];
         const int minus = reg_minus[r];
-        const int64_t len = chrom_len[ch], off = chrom_off[ch] + kC5PadBases;
+        const int64_t len = G.chrom_len[ch], off = G.chrom_off[ch] + kGenome2PadBases;
         int64_t s = reg_start[r], e = reg_end[r];
         if (s < 2) s = 2;                                   // START == 0 -> 2 (fetch_sequence :25-26); the callers refuse 0 < START < 2
         if (e > len - 2) e = len - 2;                       // the fetch is truncated: the last centre is len - 3
@@ -90,12 +80,8 @@ __global__ __launch_bounds__(kC5Block) void context_count5_kernel(
         int64_t jf = n_int;                                 // first run that overlaps the widened region [gs - 2, ge + 2)
         if (scan && n_int > 0) {
             const int64_t x0 = gs - 2, x1 = ge + 2;
-            int64_t b = x0 >> kC5BucketShift;
-            if (b >= n_buckets) b = n_buckets - 1;
-            int64_t j = nint_bucket[b];
-            while (j < n_int && nint_end[j] <= x0) ++j;
-            jf = j;
-            if (j < n_int && nint_start[j] <= x0 && nint_end[j] >= x1) scan = false;    // every window lies inside one run
+            jf = genome2_first_run(G, x0);
+            if (jf < n_int && G.nint_start[jf] <= x0 && G.nint_end[jf] >= x1) scan = false;    // every window lies inside one run
         }
         if (scan) {
             // word pairs v (words 2 v, 2 v + 1) from the pair of the first centre to the pair of the last
@@ -134,35 +120,9 @@ __global__ __launch_bounds__(kC5Block) void context_count5_kernel(
                 v = vn;
             }
             // ---- centres whose window touches a non-ACGT run: taken back, one run per lane ----
-            if (jf < n_int) {
-                const int64_t x1 = ge + 2;
-                for (int64_t j0 = jf; j0 < n_int; j0 += 64) {
-                    const int64_t j = j0 + lane;
-                    int64_t ns = x1, ne = x1;
-                    if (j < n_int) {
-                        ns = nint_start[j];
-                        ne = nint_end[j];
-                    }
-                    if (ns < x1) {
-                        // centres [lo, hi) see run j and no earlier run (the sets of two runs overlap when they are
-                        // fewer than four bases apart: such a centre belongs to the earlier run)
-                        int64_t lo = ns - 2 > gs ? ns - 2 : gs;
-                        if (j > 0 && nint_end[j - 1] + 2 > lo) lo = nint_end[j - 1] + 2;
-                        const int64_t hi = ne + 2 < ge ? ne + 2 : ge;
-                        if (hi > lo) {
-                            // interior: all five bases inside the run -> stored as AAAAA (code 0)
-                            const int64_t i0 = lo > ns + 2 ? lo : ns + 2, i1 = hi < ne - 2 ? hi : ne - 2;
-                            if (i1 > i0) DIG_C5_ADD(hist_addr, 0u - (unsigned)(i1 - i0));
-                            const int64_t l1 = hi < ns + 2 ? hi : ns + 2;                // left edge centres [lo, l1)
-                            int64_t e0 = ne - 2 > ns + 2 ? ne - 2 : ns + 2;              // right edge centres [e0, hi)
-                            if (e0 < lo) e0 = lo;
-                            for (int64_t c = lo; c < l1; ++c) DIG_C5_ADD(hist_addr + 4u * c5_code(words, c), 0xffffffffu);
-                            for (int64_t c = e0; c < hi; ++c) DIG_C5_ADD(hist_addr + 4u * c5_code(words, c), 0xffffffffu);
-                        }
-                    }
-                    if (__any(ns >= x1)) break;                              // the list is sorted: nothing further overlaps
-                }
-            }
+            // (a run's interior counts as AAAAA, code 0; its edge centres are looked up)
+            genome2_take_back<2>(G, jf + lane, 64, gs, ge, [&](int64_t n) { DIG_C5_ADD(hist_addr, 0u - (unsigned)n); },
+                                 [&](unsigned code) { DIG_C5_ADD(hist_addr + 4u * code, 0xffffffffu); });
         }
         // (one wave owns this histogram: LDS operations of a wave complete in order, no barrier needed)
         __builtin_amdgcn_wave_barrier();
@@ -193,14 +153,14 @@ int dig_count_contexts5(const uint32_t* words2, int64_t n_words2, const int64_t*
                         const int32_t* reg_chrom, const int64_t* reg_start, const int64_t* reg_end, const uint8_t* reg_minus, int64_t R,
                         int32_t* out, void* stream)
 {
-    DIG_REQUIRE(R >= 0 && n_words2 >= 28 && n_chrom >= 0 && n_int >= 0, "R, n_int, n_chrom >= 0, n_words2 >= 28 (pad words)");
+    const Genome2 G = {words2, n_words2, nint_start, nint_end, n_int, nint_bucket, n_buckets, chrom_off, chrom_len, n_chrom};
+    if (int rc = genome2_check(__func__, G, R, true)) return rc;
     if (R == 0) return DIG_OK;
     DIG_REQUIRE(words2 && chrom_off && chrom_len && reg_chrom && reg_start && reg_end && reg_minus && out, "non-null pointers");
-    DIG_REQUIRE(n_int == 0 || (nint_start && nint_end && nint_bucket && n_buckets >= 1), "interval list with its bucket index");
     DIG_REQUIRE(((uintptr_t)words2 & 15) == 0 && ((uintptr_t)out & 15) == 0, "words2 and out 16-byte aligned");
     const int grid = grid_for(R * 64, kC5Block, 8);     // one wave per region, 16 KB of LDS per workgroup
-    hipLaunchKernelGGL(context_count5_kernel, dim3(grid), dim3(kC5Block), 0, (hipStream_t)stream, words2, nint_start, nint_end, n_int,
-                       nint_bucket, n_buckets, chrom_off, chrom_len, reg_chrom, reg_start, reg_end, reg_minus, R, out);
+    hipLaunchKernelGGL(context_count5_kernel, dim3(grid), dim3(kC5Block), 0, (hipStream_t)stream, G, reg_chrom, reg_start,
+                       reg_end, reg_minus, R, out);
     DIG_HIP_TRY(hipGetLastError());
     return DIG_OK;
 }

@@ -6,7 +6,7 @@
 #include <algorithm>
 #include <vector>
 
-#include "dig_common.hpp"
+#include "dig_genome2.hpp"
 
 using namespace dig;
 
@@ -101,6 +101,26 @@ int nb3_host(Nb3Fn fn, const double* k, const double* alpha, const double* p, do
     if (!k || !alpha || !p || !out || n < 0) return set_error(DIG_EINVAL, "nb3_host: null pointer or negative n");
     Staging st(device);
     return st.call(fn, st.in(k, n), st.in(alpha, n), st.in(p, n), st.out(out, n), n, nullptr);
+}
+
+// the region table of the context-counting twins (`fn`: the twin's name, which the message begins with)
+int check_regions(const char* fn, const int32_t* reg_chrom, const int64_t* reg_start, const int64_t* reg_end, int64_t R, int n_chrom)
+{
+    for (int64_t r = 0; r < R; ++r) {
+        DIG_REQUIRE_IN(fn, reg_chrom[r] >= 0 && reg_chrom[r] < n_chrom, "region chromosome index within [0, n_chrom)");
+        DIG_REQUIRE_IN(fn, reg_start[r] >= 0 && reg_end[r] >= 0, "non-negative coordinates");
+    }
+    return DIG_OK;
+}
+
+// st.call(fn, the ten genome arguments of H staged on the device, args...): the twins of the 2-bit genome's entry points
+template <typename Fn, typename... Args>
+int call_genome2(Staging& st, Fn fn, const Genome2& H, Args... args)
+{
+    const size_t nc = std::max(H.n_chrom, 1);
+    return st.call(fn, st.in(H.words, H.n_words), H.n_words, st.in(H.nint_start, H.n_int), st.in(H.nint_end, H.n_int), H.n_int,
+                   st.in(H.nint_bucket, H.n_int ? H.n_buckets : 0), H.n_buckets, st.in(H.chrom_off, nc), st.in(H.chrom_len, nc),
+                   H.n_chrom, args...);
 }
 
 size_t dtype_size(int dt)
@@ -263,10 +283,7 @@ int dig_count_contexts_host(const uint32_t* genome_words, int64_t n_words, const
     if (R == 0) return DIG_OK;
     DIG_REQUIRE(genome_words && chrom_off && chrom_len && reg_chrom && reg_start && reg_end && reg_minus && out,
                 "non-null pointers");
-    for (int64_t r = 0; r < R; ++r) {
-        DIG_REQUIRE(reg_chrom[r] >= 0 && reg_chrom[r] < n_chrom, "region chromosome index within [0, n_chrom)");
-        DIG_REQUIRE(reg_start[r] >= 0 && reg_end[r] >= 0, "non-negative coordinates");
-    }
+    if (int rc = check_regions(__func__, reg_chrom, reg_start, reg_end, R, n_chrom)) return rc;
     for (int c = 0; c < n_chrom; ++c)
         DIG_REQUIRE((chrom_off[c] & 7) == 0 && chrom_off[c] + chrom_len[c] <= (n_words - 2) * 8,
                     "chromosomes word-aligned and inside the genome array");
@@ -282,24 +299,15 @@ int dig_count_contexts2_host(const uint32_t* words2, int64_t n_words2, const int
                              int n_chrom, const int32_t* reg_chrom, const int64_t* reg_start, const int64_t* reg_end,
                              const uint8_t* reg_minus, int64_t R, int32_t* out, int device)
 {
-    DIG_REQUIRE(R >= 0 && n_words2 >= 28 && n_chrom >= 0 && n_int >= 0, "R, n_int, n_chrom >= 0, n_words2 >= 28 (pad words)");
+    const Genome2 H = {words2, n_words2, nint_start, nint_end, n_int, nint_bucket, n_buckets, chrom_off, chrom_len, n_chrom};
+    if (int rc = genome2_check(__func__, H, R, true)) return rc;
     if (R == 0) return DIG_OK;
     DIG_REQUIRE(words2 && chrom_off && chrom_len && reg_chrom && reg_start && reg_end && reg_minus && out, "non-null pointers");
-    DIG_REQUIRE(n_int == 0 || (nint_start && nint_end && nint_bucket && n_buckets >= 1), "interval list with its bucket index");
-    for (int64_t r = 0; r < R; ++r) {
-        DIG_REQUIRE(reg_chrom[r] >= 0 && reg_chrom[r] < n_chrom, "region chromosome index within [0, n_chrom)");
-        DIG_REQUIRE(reg_start[r] >= 0 && reg_end[r] >= 0, "non-negative coordinates");
-    }
-    for (int c = 0; c < n_chrom; ++c)
-        DIG_REQUIRE(chrom_off[c] >= 0 && chrom_off[c] + chrom_len[c] + 64 <= (n_words2 - 24) * 16, "chromosomes inside the genome array");
-    for (int64_t j = 0; j < n_int; ++j)
-        DIG_REQUIRE(nint_start[j] < nint_end[j] && (j == 0 || nint_end[j - 1] < nint_start[j]), "intervals sorted, disjoint, not touching");
-    const size_t nc = std::max(n_chrom, 1);
+    if (int rc = check_regions(__func__, reg_chrom, reg_start, reg_end, R, n_chrom)) return rc;
+    if (int rc = genome2_check_host(__func__, H)) return rc;
     Staging st(device);
-    return st.call(dig_count_contexts2, st.in(words2, n_words2), n_words2, st.in(nint_start, n_int), st.in(nint_end, n_int), n_int,
-                   st.in(nint_bucket, n_int ? n_buckets : 0), n_buckets, st.in(chrom_off, nc), st.in(chrom_len, nc), n_chrom,
-                   st.in(reg_chrom, R), st.in(reg_start, R), st.in(reg_end, R), st.in(reg_minus, R), R, st.out(out, (size_t)R * 64),
-                   nullptr);
+    return call_genome2(st, dig_count_contexts2, H, st.in(reg_chrom, R), st.in(reg_start, R), st.in(reg_end, R), st.in(reg_minus, R), R,
+                        st.out(out, (size_t)R * 64), nullptr);
 }
 
 int dig_count_contexts5_host(const uint32_t* words2, int64_t n_words2, const int64_t* nint_start, const int64_t* nint_end, int64_t n_int,
@@ -307,25 +315,17 @@ int dig_count_contexts5_host(const uint32_t* words2, int64_t n_words2, const int
                              int n_chrom, const int32_t* reg_chrom, const int64_t* reg_start, const int64_t* reg_end,
                              const uint8_t* reg_minus, int64_t R, int32_t* out, int device)
 {
-    DIG_REQUIRE(R >= 0 && n_words2 >= 28 && n_chrom >= 0 && n_int >= 0, "R, n_int, n_chrom >= 0, n_words2 >= 28 (pad words)");
+    const Genome2 H = {words2, n_words2, nint_start, nint_end, n_int, nint_bucket, n_buckets, chrom_off, chrom_len, n_chrom};
+    if (int rc = genome2_check(__func__, H, R, true)) return rc;
     if (R == 0) return DIG_OK;
     DIG_REQUIRE(words2 && chrom_off && chrom_len && reg_chrom && reg_start && reg_end && reg_minus && out, "non-null pointers");
-    DIG_REQUIRE(n_int == 0 || (nint_start && nint_end && nint_bucket && n_buckets >= 1), "interval list with its bucket index");
-    for (int64_t r = 0; r < R; ++r) {
-        DIG_REQUIRE(reg_chrom[r] >= 0 && reg_chrom[r] < n_chrom, "region chromosome index within [0, n_chrom)");
-        DIG_REQUIRE(reg_start[r] >= 0 && reg_end[r] >= 0, "non-negative coordinates");
+    if (int rc = check_regions(__func__, reg_chrom, reg_start, reg_end, R, n_chrom)) return rc;
+    for (int64_t r = 0; r < R; ++r)
         DIG_REQUIRE(reg_start[r] == 0 || reg_start[r] >= 2, "START 0 or >= 2 (the fetch would start before the chromosome)");
-    }
-    for (int c = 0; c < n_chrom; ++c)
-        DIG_REQUIRE(chrom_off[c] >= 0 && chrom_off[c] + chrom_len[c] + 64 <= (n_words2 - 24) * 16, "chromosomes inside the genome array");
-    for (int64_t j = 0; j < n_int; ++j)
-        DIG_REQUIRE(nint_start[j] < nint_end[j] && (j == 0 || nint_end[j - 1] < nint_start[j]), "intervals sorted, disjoint, not touching");
-    const size_t nc = std::max(n_chrom, 1);
+    if (int rc = genome2_check_host(__func__, H)) return rc;
     Staging st(device);
-    return st.call(dig_count_contexts5, st.in(words2, n_words2), n_words2, st.in(nint_start, n_int), st.in(nint_end, n_int), n_int,
-                   st.in(nint_bucket, n_int ? n_buckets : 0), n_buckets, st.in(chrom_off, nc), st.in(chrom_len, nc), n_chrom,
-                   st.in(reg_chrom, R), st.in(reg_start, R), st.in(reg_end, R), st.in(reg_minus, R), R, st.out(out, (size_t)R * 1024),
-                   nullptr);
+    return call_genome2(st, dig_count_contexts5, H, st.in(reg_chrom, R), st.in(reg_start, R), st.in(reg_end, R), st.in(reg_minus, R), R,
+                        st.out(out, (size_t)R * 1024), nullptr);
 }
 
 int dig_mutation_contexts_host(const uint32_t* words2, int64_t n_words2, const int64_t* nint_start, const int64_t* nint_end, int64_t n_int,
@@ -335,22 +335,16 @@ int dig_mutation_contexts_host(const uint32_t* words2, int64_t n_words2, const i
 {
     DIG_REQUIRE(n_rows >= 0 && n_rows <= INT32_MAX, "0 <= n_rows < 2^31");
     DIG_REQUIRE(n_up >= 0 && n_down >= 0 && n_up + n_down + 1 <= 16, "n_up, n_down >= 0 and n_up + n_down + 1 <= 16");
-    DIG_REQUIRE(n_words2 >= 28 && n_chrom >= 0 && n_int >= 0, "n_int, n_chrom >= 0, n_words2 >= 28 (pad words)");
+    const Genome2 H = {words2, n_words2, nint_start, nint_end, n_int, nint_bucket, n_buckets, chrom_off, chrom_len, n_chrom};
+    if (int rc = genome2_check(__func__, H, n_rows)) return rc;
     if (n_rows == 0) return DIG_OK;
     DIG_REQUIRE(words2 && chrom_off && chrom_len && row_chrom && row_start && row_ref && status && context, "non-null pointers");
-    DIG_REQUIRE(n_int == 0 || (nint_start && nint_end && nint_bucket && n_buckets >= 1), "interval list with its bucket index");
     for (int64_t r = 0; r < n_rows; ++r) DIG_REQUIRE(row_chrom[r] >= 0 && row_chrom[r] < n_chrom, "row chromosome index within [0, n_chrom)");
-    for (int c = 0; c < n_chrom; ++c)
-        DIG_REQUIRE(chrom_off[c] >= 0 && chrom_off[c] + chrom_len[c] + 64 <= (n_words2 - 24) * 16, "chromosomes inside the genome array");
-    for (int64_t j = 0; j < n_int; ++j)
-        DIG_REQUIRE(nint_start[j] < nint_end[j] && (j == 0 || nint_end[j - 1] < nint_start[j]), "intervals sorted, disjoint, not touching");
-    const size_t nc = std::max(n_chrom, 1);
+    if (int rc = genome2_check_host(__func__, H)) return rc;
     const int64_t ws = dig_mutation_contexts_workspace(n_rows);
     Staging st(device);
-    return st.call(dig_mutation_contexts, st.in(words2, n_words2), n_words2, st.in(nint_start, n_int), st.in(nint_end, n_int), n_int,
-                   st.in(nint_bucket, n_int ? n_buckets : 0), n_buckets, st.in(chrom_off, nc), st.in(chrom_len, nc), n_chrom,
-                   st.in(row_chrom, n_rows), st.in(row_start, n_rows), st.in(row_ref, n_rows), n_rows, n_up, n_down, collapse,
-                   st.out(status, n_rows), st.out(context, n_rows), st.scratch(ws), ws, nullptr);
+    return call_genome2(st, dig_mutation_contexts, H, st.in(row_chrom, n_rows), st.in(row_start, n_rows), st.in(row_ref, n_rows), n_rows,
+                        n_up, n_down, collapse, st.out(status, n_rows), st.out(context, n_rows), st.scratch(ws), ws, nullptr);
 }
 
 int dig_mutation_function_host(const uint32_t* words2, int64_t n_words2, const int64_t* nint_start, const int64_t* nint_end, int64_t n_int,
@@ -363,10 +357,10 @@ int dig_mutation_function_host(const uint32_t* words2, int64_t n_words2, const i
                                int device)
 {
     DIG_REQUIRE(n_pairs >= 0 && n_genes >= 0, "n_pairs, n_genes >= 0");
-    DIG_REQUIRE(n_words2 >= 28 && n_chrom >= 0 && n_int >= 0, "n_int, n_chrom >= 0, n_words2 >= 28 (pad words)");
+    const Genome2 H = {words2, n_words2, nint_start, nint_end, n_int, nint_bucket, n_buckets, chrom_off, chrom_len, n_chrom};
+    if (int rc = genome2_check(__func__, H, n_pairs)) return rc;
     if (n_pairs == 0) return DIG_OK;
     DIG_REQUIRE(words2 && chrom_off && chrom_len && blk_ptr && spl_ptr, "non-null genome arrays, blk_ptr, spl_ptr");
-    DIG_REQUIRE(n_int == 0 || (nint_start && nint_end && nint_bucket && n_buckets >= 1), "interval list with its bucket index");
     DIG_REQUIRE(pair_gene && pair_start && pair_end && pair_kind && pair_ref && pair_alt, "non-null pair arrays");
     DIG_REQUIRE(impact && status && n_cds && cds_min && cds_max, "non-null outputs");
     const int64_t n_blk = blk_ptr[n_genes], n_spl = spl_ptr[n_genes];
@@ -374,10 +368,7 @@ int dig_mutation_function_host(const uint32_t* words2, int64_t n_words2, const i
     DIG_REQUIRE(n_genes == 0 || (gene_chrom && gene_minus), "non-null gene_chrom, gene_minus");
     DIG_REQUIRE(n_blk == 0 || (blk_start && blk_end && cds_off), "non-null block arrays");
     DIG_REQUIRE(n_spl == 0 || spl_pos, "non-null spl_pos");
-    for (int c = 0; c < n_chrom; ++c)
-        DIG_REQUIRE(chrom_off[c] >= 0 && chrom_off[c] + chrom_len[c] + 64 <= (n_words2 - 24) * 16, "chromosomes inside the genome array");
-    for (int64_t j = 0; j < n_int; ++j)
-        DIG_REQUIRE(nint_start[j] < nint_end[j] && (j == 0 || nint_end[j - 1] < nint_start[j]), "intervals sorted, disjoint, not touching");
+    if (int rc = genome2_check_host(__func__, H)) return rc;
     for (int64_t g = 0; g < n_genes; ++g) {
         DIG_REQUIRE(gene_chrom[g] >= 0 && gene_chrom[g] < n_chrom, "gene chromosome index within [0, n_chrom)");
         DIG_REQUIRE(blk_ptr[g] <= blk_ptr[g + 1] && spl_ptr[g] <= spl_ptr[g + 1], "blk_ptr, spl_ptr non-decreasing");
@@ -393,15 +384,13 @@ int dig_mutation_function_host(const uint32_t* words2, int64_t n_words2, const i
         for (int64_t q = spl_ptr[g] + 1; q < spl_ptr[g + 1]; ++q) DIG_REQUIRE(spl_pos[q - 1] < spl_pos[q], "splice positions of a gene ascending");
     }
     for (int64_t i = 0; i < n_pairs; ++i) DIG_REQUIRE(pair_gene[i] >= 0 && pair_gene[i] < n_genes, "pair gene index within [0, n_genes)");
-    const size_t nc = std::max(n_chrom, 1), ng = (size_t)n_genes;
+    const size_t ng = (size_t)n_genes;
     Staging st(device);
-    return st.call(dig_mutation_function, st.in(words2, n_words2), n_words2, st.in(nint_start, n_int), st.in(nint_end, n_int), n_int,
-                   st.in(nint_bucket, n_int ? n_buckets : 0), n_buckets, st.in(chrom_off, nc), st.in(chrom_len, nc), n_chrom,
-                   st.in(gene_chrom, ng), st.in(gene_minus, ng), st.in(blk_ptr, ng + 1), st.in(blk_start, n_blk), st.in(blk_end, n_blk),
-                   st.in(cds_off, n_blk), st.in(spl_ptr, ng + 1), st.in(spl_pos, n_spl), n_genes, st.in(pair_gene, n_pairs),
-                   st.in(pair_start, n_pairs), st.in(pair_end, n_pairs), st.in(pair_kind, n_pairs), st.in(pair_ref, n_pairs),
-                   st.in(pair_alt, n_pairs), n_pairs, st.out(impact, n_pairs), st.out(status, n_pairs), st.out(n_cds, n_pairs),
-                   st.out(cds_min, n_pairs), st.out(cds_max, n_pairs), nullptr);
+    return call_genome2(st, dig_mutation_function, H, st.in(gene_chrom, ng), st.in(gene_minus, ng), st.in(blk_ptr, ng + 1),
+                        st.in(blk_start, n_blk), st.in(blk_end, n_blk), st.in(cds_off, n_blk), st.in(spl_ptr, ng + 1),
+                        st.in(spl_pos, n_spl), n_genes, st.in(pair_gene, n_pairs), st.in(pair_start, n_pairs), st.in(pair_end, n_pairs),
+                        st.in(pair_kind, n_pairs), st.in(pair_ref, n_pairs), st.in(pair_alt, n_pairs), n_pairs, st.out(impact, n_pairs),
+                        st.out(status, n_pairs), st.out(n_cds, n_pairs), st.out(cds_min, n_pairs), st.out(cds_max, n_pairs), nullptr);
 }
 
 int dig_element_pipeline_host(const double* bin_mu, const double* bin_std, const int32_t* bin_y, const uint8_t* bin_flag,

@@ -18,13 +18,11 @@
 // Rows whose window touches a non-ACGT run (the 2-bit form stores N, R, M, ... all as A), starts before the chromosome or is cut
 // short at its end are left to the host (DIG_MC_HOST), which knows the letters; their match test is still exact here, since
 // the centre base's run membership is looked up.  The work is one short gather per row: latency-bound.
-#include "dig_common.hpp"
+#include "dig_genome2.hpp"
 
 namespace dig {
 
 constexpr int kMcBlock = 256;
-constexpr int kMcPadBases = kGenome2PadBases;           // the 2-bit layout of dig_count_contexts2 (dig_common.hpp)
-constexpr int kMcBucketShift = kGenome2BucketShift;
 constexpr unsigned kMcMatch = 1u, kMcHead = 2u, kMcNeedsHost = 4u;
 
 __device__ __forceinline__ uint64_t mc_upto(int lane)           // lanes 0 .. lane
@@ -38,11 +36,9 @@ __device__ __forceinline__ int64_t mc_last(uint64_t mask, int64_t base)      // 
 }
 
 __global__ __launch_bounds__(kMcBlock) void mutctx_lookup_kernel(
-    const uint32_t* __restrict__ words, const int64_t* __restrict__ nint_start, const int64_t* __restrict__ nint_end, int64_t n_int,
-    const int32_t* __restrict__ nint_bucket, int64_t n_buckets, const int64_t* __restrict__ chrom_off,
-    const int64_t* __restrict__ chrom_len, const int32_t* __restrict__ row_chrom, const int64_t* __restrict__ row_start,
-    const uint8_t* __restrict__ row_ref, int64_t N, int n_up, int n_down, int collapse, uint8_t* __restrict__ status,
-    uint32_t* __restrict__ context, int32_t* __restrict__ wave_last)
+    Genome2 G, const int32_t* __restrict__ row_chrom, const int64_t* __restrict__ row_start, const uint8_t* __restrict__ row_ref,
+    int64_t N, int n_up, int n_down, int collapse, uint8_t* __restrict__ status, uint32_t* __restrict__ context,
+    int32_t* __restrict__ wave_last)
 {
     const int64_t i = (int64_t)blockIdx.x * kMcBlock + threadIdx.x;
     const int lane = threadIdx.x & 63;
@@ -53,38 +49,31 @@ __global__ __launch_bounds__(kMcBlock) void mutctx_lookup_kernel(
         const int ch = row_chrom[i];
         const int64_t s = row_start[i];
         head = i == 0 || row_chrom[i - 1] != ch || row_start[i - 1] != s;
-        const int64_t len = chrom_len[ch];
+        const int64_t len = G.chrom_len[ch];
         if (s < 0 || s >= len) {
             host = true;                                             // the caller rejects these; nothing is read
         } else {
             const int W = n_up + n_down + 1;
-            const int64_t off = kMcPadBases + chrom_off[ch];
+            const int64_t off = kGenome2PadBases + G.chrom_off[ch];
             const int64_t g = off + s;                               // the centre in array bases
             host = s < n_up || s + n_down + 1 > len;
             const int64_t lo = max(g - n_up, off), hi = min(g + n_down + 1, off + len);      // the window inside the chromosome
             bool centre_other = false;
-            if (n_int > 0) {                                         // the runs of non-ACGT letters that touch [lo, hi)
-                int64_t b = lo >> kMcBucketShift;
-                if (b >= n_buckets) b = n_buckets - 1;
-                int64_t j = nint_bucket[b];
-                while (j < n_int && nint_end[j] <= lo) ++j;
-                for (; j < n_int && nint_start[j] < hi; ++j) {
+            if (G.n_int > 0) {                                       // the runs of non-ACGT letters that touch [lo, hi)
+                for (int64_t j = genome2_first_run(G, lo); j < G.n_int && G.nint_start[j] < hi; ++j) {
                     host = true;
-                    centre_other |= nint_start[j] <= g && g < nint_end[j];
+                    centre_other |= G.nint_start[j] <= g && g < G.nint_end[j];
                 }
             }
-            const unsigned centre = (words[g >> 4] >> (2 * (int)(g & 15))) & 3u;
+            const unsigned centre = genome2_code(G.words, g);
             const unsigned ref = row_ref[i];
             match = ref == 4u || (ref < 4u && !centre_other && centre == ref);       // 4: the caller matched a non-ACGT letter
             if (!host) {
-                const int64_t q = g - n_up;
-                const uint64_t x = (uint64_t)words[q >> 4] | ((uint64_t)words[(q >> 4) + 1] << 32);
-                const uint32_t mask = W == 16 ? 0xffffffffu : ((1u << (2 * W)) - 1u);
-                code = (uint32_t)(x >> (2 * (int)(q & 15))) & mask;  // base k of the window in bits 2 k, 2 k + 1
+                code = genome2_window(G.words, g - n_up, W);         // base k of the window in bits 2 k, 2 k + 1
                 if (collapse && (centre == 0u || centre == 2u)) {    // A / G centre: the reverse complement
                     uint32_t r = __builtin_bitreverse32(code);
                     r = ((r >> 1) & 0x55555555u) | ((r & 0x55555555u) << 1);
-                    code = (r >> (32 - 2 * W)) ^ mask;
+                    code = (r >> (32 - 2 * W)) ^ genome2_mask(W);
                 }
             }
         }
@@ -159,17 +148,16 @@ int dig_mutation_contexts(const uint32_t* words2, int64_t n_words2, const int64_
 {
     DIG_REQUIRE(n_rows >= 0 && n_rows <= INT32_MAX, "0 <= n_rows < 2^31");
     DIG_REQUIRE(n_up >= 0 && n_down >= 0 && n_up + n_down + 1 <= 16, "n_up, n_down >= 0 and n_up + n_down + 1 <= 16");
-    DIG_REQUIRE(n_words2 >= 28 && n_chrom >= 0 && n_int >= 0, "n_int, n_chrom >= 0, n_words2 >= 28 (pad words)");
+    const Genome2 G = {words2, n_words2, nint_start, nint_end, n_int, nint_bucket, n_buckets, chrom_off, chrom_len, n_chrom};
+    if (int rc = genome2_check(__func__, G, n_rows)) return rc;
     if (n_rows == 0) return DIG_OK;
     DIG_REQUIRE(words2 && chrom_off && chrom_len && row_chrom && row_start && row_ref && status && context && workspace,
                 "non-null pointers");
-    DIG_REQUIRE(n_int == 0 || (nint_start && nint_end && nint_bucket && n_buckets >= 1), "interval list with its bucket index");
     DIG_REQUIRE(workspace_bytes >= dig_mutation_contexts_workspace(n_rows), "workspace of dig_mutation_contexts_workspace bytes");
     const int grid = (int)((n_rows + kMcBlock - 1) / kMcBlock);
     int32_t* wave_last = static_cast<int32_t*>(workspace);
-    hipLaunchKernelGGL(mutctx_lookup_kernel, dim3(grid), dim3(kMcBlock), 0, (hipStream_t)stream, words2, nint_start, nint_end, n_int,
-                       nint_bucket, n_buckets, chrom_off, chrom_len, row_chrom, row_start, row_ref, n_rows, n_up, n_down, collapse,
-                       status, context, wave_last);
+    hipLaunchKernelGGL(mutctx_lookup_kernel, dim3(grid), dim3(kMcBlock), 0, (hipStream_t)stream, G, row_chrom, row_start, row_ref,
+                       n_rows, n_up, n_down, collapse, status, context, wave_last);
     DIG_HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(mutctx_resolve_kernel, dim3(grid), dim3(kMcBlock), 0, (hipStream_t)stream, wave_last, n_rows, status);
     DIG_HIP_TRY(hipGetLastError());

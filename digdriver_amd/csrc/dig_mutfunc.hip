@@ -17,8 +17,7 @@ namespace dig {
 
 constexpr int kMfBlock = 256;
 __global__ __launch_bounds__(kMfBlock) void mutation_function_kernel(
-    Genome2 G, const int64_t* __restrict__ chrom_off, const int64_t* __restrict__ chrom_len, int n_chrom,
-    const int32_t* __restrict__ gene_chrom, const uint8_t* __restrict__ gene_minus, const int64_t* __restrict__ blk_ptr,
+    Genome2 G, const int32_t* __restrict__ gene_chrom, const uint8_t* __restrict__ gene_minus, const int64_t* __restrict__ blk_ptr,
     const int64_t* __restrict__ blk_start, const int64_t* __restrict__ blk_end, const int64_t* __restrict__ cds_off,
     const int64_t* __restrict__ spl_ptr, const int64_t* __restrict__ spl_pos, int64_t n_genes,
     const int32_t* __restrict__ pair_gene, const int64_t* __restrict__ pair_start, const int64_t* __restrict__ pair_end,
@@ -41,8 +40,8 @@ __global__ __launch_bounds__(kMfBlock) void mutation_function_kernel(
             const int64_t len = cds_off[b1 - 1] + blk_end[b1 - 1] - blk_start[b1 - 1] + 1;
             if (kind == DIG_MF_KIND_SNV) {
                 const int ch = gene_chrom[gi];
-                const bool ch_ok = ch >= 0 && ch < n_chrom;
-                const int64_t off = ch_ok ? kGenome2PadBases + chrom_off[ch] : 0, clen = ch_ok ? chrom_len[ch] : 0;
+                const bool ch_ok = ch >= 0 && ch < G.n_chrom;
+                const int64_t off = ch_ok ? kGenome2PadBases + G.chrom_off[ch] : 0, clen = ch_ok ? G.chrom_len[ch] : 0;
                 const unsigned ref = pair_ref[i], alt = pair_alt[i] & 3u;
                 const int64_t q0 = spl_ptr[gi], q1 = spl_ptr[gi + 1];
                 const int64_t q = codon_last_le(spl_pos, q0, q1, s);
@@ -125,17 +124,16 @@ int dig_mutation_function(const uint32_t* words2, int64_t n_words2, const int64_
                           int32_t* n_cds, int32_t* cds_min, int32_t* cds_max, void* stream)
 {
     DIG_REQUIRE(n_pairs >= 0 && n_genes >= 0, "n_pairs, n_genes >= 0");
-    DIG_REQUIRE(n_words2 >= 28 && n_chrom >= 0 && n_int >= 0, "n_int, n_chrom >= 0, n_words2 >= 28 (pad words)");
+    const Genome2 G = {words2, n_words2, nint_start, nint_end, n_int, nint_bucket, n_buckets, chrom_off, chrom_len, n_chrom};
+    if (int rc = genome2_check(__func__, G, n_pairs)) return rc;
     if (n_pairs == 0) return DIG_OK;
     DIG_REQUIRE(words2 && chrom_off && chrom_len, "non-null genome arrays");
-    DIG_REQUIRE(n_int == 0 || (nint_start && nint_end && nint_bucket && n_buckets >= 1), "interval list with its bucket index");
     DIG_REQUIRE(n_genes == 0 || (gene_chrom && gene_minus && blk_start && blk_end && cds_off), "non-null gene table");
     DIG_REQUIRE(blk_ptr && spl_ptr, "non-null blk_ptr, spl_ptr (n_genes + 1 entries)");
     DIG_REQUIRE(pair_gene && pair_start && pair_end && pair_kind && pair_ref && pair_alt, "non-null pair arrays");
     DIG_REQUIRE(impact && status && n_cds && cds_min && cds_max, "non-null outputs");
-    const Genome2 G = {words2, nint_start, nint_end, n_int, nint_bucket, n_buckets};
     hipLaunchKernelGGL(mutation_function_kernel, dim3(grid_for(n_pairs, kMfBlock)), dim3(kMfBlock), 0, (hipStream_t)stream, G,
-                       chrom_off, chrom_len, n_chrom, gene_chrom, gene_minus, blk_ptr, blk_start, blk_end, cds_off, spl_ptr, spl_pos,
+                       gene_chrom, gene_minus, blk_ptr, blk_start, blk_end, cds_off, spl_ptr, spl_pos,
                        n_genes, pair_gene, pair_start, pair_end, pair_kind, pair_ref, pair_alt, n_pairs, impact, status, n_cds,
                        cds_min, cds_max);
     DIG_HIP_TRY(hipGetLastError());

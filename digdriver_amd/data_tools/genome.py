@@ -164,8 +164,8 @@ class PackedGenome:
         return PackedGenome(self.names, offsets, new_len, np.concatenate(pieces)), shift
 
     # ---- the 2-bit form (dig_count_contexts2, include/dig_hip.h) ------------------------------------------
-    PAD2_BASES = 64            # bases in front of the chromosome data of the 2-bit array
-    BUCKET_SHIFT = 12
+    PAD2_BASES = 64            # bases in front of the chromosome data of the 2-bit array: kGenome2PadBases and
+    BUCKET_SHIFT = 12          # kGenome2BucketShift of csrc/dig_genome2.hpp, where the kernels' side of the layout lives
 
     def two_bit(self, cache_path=None):
         """(words2, nint_start, nint_end, nint_bucket): the genome at 2 bits per base (every letter other than ACGT stored as
@@ -241,6 +241,18 @@ class PackedGenome:
             self._dev[key] = (torch.as_tensor(w2.view(np.int32), device=dev), torch.as_tensor(ns, device=dev), torch.as_tensor(ne, device=dev),
                               torch.as_tensor(bk, device=dev), torch.as_tensor(self.offsets, device=dev), torch.as_tensor(self.lengths, device=dev))
         return self._dev[key]
+
+    def genome2_args(self, device=None):
+        """The ten leading arguments of every entry point that reads the 2-bit form (words2, n_words2, nint_start, nint_end,
+        n_int, nint_bucket, n_buckets, chrom_off, chrom_len, n_chrom): device pointers into on_device2(device), or with
+        device=None host pointers for a `_host` twin.  An empty run list is passed as NULL pointers."""
+        from .. import _lib
+        if device is None:
+            p, (w2, ns, ne, bk), off, ln = _lib.host_ptr, self.two_bit(), self.offsets, self.lengths
+        else:
+            p, (w2, ns, ne, bk, off, ln) = _lib.dev_ptr, self.on_device2(device)
+        q = p if len(ns) else lambda a: None
+        return [p(w2), len(w2), q(ns), q(ne), len(ns), q(bk), len(bk), p(off), p(ln), len(self.names)]
 
     def on_device(self, device):
         import torch

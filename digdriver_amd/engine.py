@@ -705,9 +705,7 @@ def count_contexts(genome, chroms, starts, ends, minus=None, device=0, on_device
         p = _lib.dev_ptr
         with torch.cuda.device(dev):
             if form == "2bit":
-                w2, ns, ne, bk, off, ln = genome.on_device2(dev)
-                _lib.call("dig_count_contexts5" if penta else "dig_count_contexts2", p(w2), w2.numel(), p(ns) if ns.numel() else None,
-                          p(ne) if ns.numel() else None, ns.numel(), p(bk) if ns.numel() else None, bk.numel(), p(off), p(ln), len(genome.names), p(rc), p(rs),
+                _lib.call("dig_count_contexts5" if penta else "dig_count_contexts2", *genome.genome2_args(dev), p(rc), p(rs),
                           p(re_), p(rm), R, p(out), _lib.stream_ptr())
             else:
                 words, off, ln = genome.on_device(dev)
@@ -718,9 +716,7 @@ def count_contexts(genome, chroms, starts, ends, minus=None, device=0, on_device
     h = _lib.host_ptr
     dv = device if isinstance(device, int) else 0
     if form == "2bit":
-        w2, ns, ne, bk = genome.two_bit()
-        _lib.call("dig_count_contexts5_host" if penta else "dig_count_contexts2_host", h(w2), w2.size, h(ns) if ns.size else None,
-                  h(ne) if ns.size else None, ns.size, h(bk) if ns.size else None, bk.size, h(genome.offsets), h(genome.lengths), len(genome.names), h(ci), h(st), h(en),
+        _lib.call("dig_count_contexts5_host" if penta else "dig_count_contexts2_host", *genome.genome2_args(), h(ci), h(st), h(en),
                   h(mi), R, h(out), dv)
     else:
         _lib.call("dig_count_contexts_host", h(genome.words), genome.words.size, h(genome.offsets), h(genome.lengths),
@@ -772,18 +768,14 @@ def mutation_contexts(genome, chroms, starts, refs, n_up=2, n_down=2, collapse=F
         t = lambda a: torch.as_tensor(a, device=dev)
         p = _lib.dev_ptr
         with torch.cuda.device(dev):
-            w2, ns, ne, bk, off, ln = genome.on_device2(dev)
             rci, rst, rrf = t(ci), t(st), t(rc)
-            _lib.call("dig_mutation_contexts", p(w2), w2.numel(), p(ns) if ns.numel() else None, p(ne) if ns.numel() else None,
-                      ns.numel(), p(bk) if ns.numel() else None, bk.numel(), p(off), p(ln), len(genome.names), p(rci), p(rst), p(rrf),
-                      R, n_up, n_down, int(bool(collapse)), p(status), p(context), p(ws), ws.numel(), _lib.stream_ptr())
+            _lib.call("dig_mutation_contexts", *genome.genome2_args(dev), p(rci), p(rst), p(rrf), R, n_up, n_down,
+                      int(bool(collapse)), p(status), p(context), p(ws), ws.numel(), _lib.stream_ptr())
         return status, context
     status, context = np.empty(R, np.uint8), np.empty(R, np.uint32)
     h = _lib.host_ptr
-    w2, ns, ne, bk = genome.two_bit()
-    _lib.call("dig_mutation_contexts_host", h(w2), w2.size, h(ns) if ns.size else None, h(ne) if ns.size else None, ns.size,
-              h(bk) if ns.size else None, bk.size, h(genome.offsets), h(genome.lengths), len(genome.names), h(ci), h(st), h(rc), R,
-              n_up, n_down, int(bool(collapse)), h(status), h(context), device if isinstance(device, int) else 0)
+    _lib.call("dig_mutation_contexts_host", *genome.genome2_args(), h(ci), h(st), h(rc), R, n_up, n_down, int(bool(collapse)),
+              h(status), h(context), device if isinstance(device, int) else 0)
     return status, context
 
 
@@ -826,11 +818,9 @@ def mutation_function(genome, genes, gene_chrom, pair_gene, pair_start, pair_end
         n_cds, cds_min, cds_max = (torch.empty(n, dtype=torch.int32, device=dev) for _ in range(3))
         p = _lib.dev_ptr
         with torch.cuda.device(dev):
-            w2, ns, ne, bk, off, ln = genome.on_device2(dev)
             tab = [torch.as_tensor(a, device=dev) for a in table]
-            _lib.call("dig_mutation_function", p(w2), w2.numel(), p(ns) if ns.numel() else None, p(ne) if ns.numel() else None,
-                      ns.numel(), p(bk) if ns.numel() else None, bk.numel(), p(off), p(ln), len(genome.names), *[p(a) for a in tab], G,
-                      *[p(a) for a in pairs], n, p(impact), p(status), p(n_cds), p(cds_min), p(cds_max), _lib.stream_ptr())
+            _lib.call("dig_mutation_function", *genome.genome2_args(dev), *[p(a) for a in tab], G, *[p(a) for a in pairs], n,
+                      p(impact), p(status), p(n_cds), p(cds_min), p(cds_max), _lib.stream_ptr())
         return impact, status, n_cds, cds_min, cds_max
     pairs = [_lib.as_host(a, d).ravel() for a, d in zip((pair_gene, pair_start, pair_end, pair_kind, pair_ref, pair_alt), dtypes)]
     n = len(pairs[0])
@@ -838,10 +828,8 @@ def mutation_function(genome, genes, gene_chrom, pair_gene, pair_start, pair_end
     impact, status = np.empty(n, np.uint8), np.empty(n, np.uint8)
     n_cds, cds_min, cds_max = np.empty(n, np.int32), np.empty(n, np.int32), np.empty(n, np.int32)
     h = _lib.host_ptr
-    w2, ns, ne, bk = genome.two_bit()
-    _lib.call("dig_mutation_function_host", h(w2), w2.size, h(ns) if ns.size else None, h(ne) if ns.size else None, ns.size,
-              h(bk) if ns.size else None, bk.size, h(genome.offsets), h(genome.lengths), len(genome.names), *[h(a) for a in table], G,
-              *[h(a) for a in pairs], n, h(impact), h(status), h(n_cds), h(cds_min), h(cds_max), device if isinstance(device, int) else 0)
+    _lib.call("dig_mutation_function_host", *genome.genome2_args(), *[h(a) for a in table], G, *[h(a) for a in pairs], n,
+              h(impact), h(status), h(n_cds), h(cds_min), h(cds_max), device if isinstance(device, int) else 0)
     return impact, status, n_cds, cds_min, cds_max
 
 

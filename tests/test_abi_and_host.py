@@ -37,6 +37,16 @@ def test_library_abi_version_matches_header_and_binding():
     assert declared == _lib.ABI_VERSION == _lib.load().dig_abi_version()
 
 
+def test_two_bit_layout_constants_of_the_packer_match_the_kernels_header():
+    """PackedGenome.two_bit writes the layout that csrc/dig_genome2.hpp reads: the pad in front and the bucket size agree."""
+    from digdriver_amd.data_tools.genome import PackedGenome
+    hpp = open(os.path.join(ROOT, "digdriver_amd", "csrc", "dig_genome2.hpp")).read()
+    const = {k: int(v) for k, v in re.findall(r"^constexpr int (kGenome2\w+) = (\d+);", hpp, flags=re.M)}
+    assert const["kGenome2PadBases"] == PackedGenome.PAD2_BASES
+    assert const["kGenome2BucketShift"] == PackedGenome.BUCKET_SHIFT
+    assert const["kGenome2BasesPerWord"] == 16 and const["kGenome2PadWordsBehind"] == 24     # two_bit: 4 + ceil(total / 16) + 24 words
+
+
 def test_product_never_imports_oracle_or_scipy():
     """The product path must not route through the oracle or any CPU implementation."""
     pkg = os.path.join(ROOT, "digdriver_amd")

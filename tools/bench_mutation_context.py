@@ -21,26 +21,12 @@ import time
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
+from bench_penta_contexts import synthetic_seqs                # noqa: E402
 from digdriver_amd import engine                               # noqa: E402
 from digdriver_amd.data_tools.genome import PackedGenome       # noqa: E402
 from digdriver_amd.sequence_model import sequence_tools as st  # noqa: E402
-
-HG19 = [249250621, 243199373, 198022430, 191154276, 180915260, 171115067, 159138663, 146364022, 141213431, 135534747, 135006516,
-        133851895, 115169878, 107349540, 102531392, 90354753, 81195210, 78077248, 59128983, 63025520, 48129895, 51304566]
-
-
-def synthetic_seqs(total_mb, rng):
-    scale = total_mb * 1e6 / sum(HG19)
-    seqs = {}
-    for i, n in enumerate(HG19):
-        n = max(int(n * scale), 1000)
-        s = np.frombuffer(b"ACGT", np.uint8)[rng.integers(0, 4, n, dtype=np.uint8)].copy()
-        for a in rng.integers(0, n - 5000, max(n // 1000000, 1)):
-            s[a:a + int(rng.integers(100, 5000))] = ord("N")
-        seqs["chr%d" % (i + 1)] = s.tobytes()
-    return seqs
-
 
 def make_rows(g, n_rows, rng):
     lengths = g.lengths[[g.index["chr%d" % c] for c in range(1, 23)]]
@@ -58,7 +44,7 @@ def time_kernel(g, chrom, start, ref):
     torch.cuda.synchronize()
     # the timed window: both launches only (the rows are already on the device)
     from digdriver_amd import _lib
-    w2, ns, ne, bk, off, ln = g.on_device2(dev)
+    genome = g.genome2_args(dev)
     ci = torch.as_tensor(g.chrom_index(list(range(1, 23)))[chrom - 1], device=dev)
     s_d, r_d = torch.as_tensor(start, device=dev), torch.as_tensor(ref, device=dev)
     R = len(chrom)
@@ -70,8 +56,8 @@ def time_kernel(g, chrom, start, ref):
     for _ in range(13):
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
-        _lib.call("dig_mutation_contexts", p(w2), w2.numel(), p(ns), p(ne), ns.numel(), p(bk), bk.numel(), p(off), p(ln),
-                  len(g.names), p(ci), p(s_d), p(r_d), R, 1, 1, 0, p(status), p(ctx), p(ws), ws.numel(), _lib.stream_ptr())
+        _lib.call("dig_mutation_contexts", *genome, p(ci), p(s_d), p(r_d), R, 1, 1, 0, p(status), p(ctx), p(ws), ws.numel(),
+                  _lib.stream_ptr())
         e1.record()
         torch.cuda.synchronize()
         times.append(e0.elapsed_time(e1))
@@ -108,7 +94,7 @@ def main():
     rng = np.random.default_rng(0)
     res = dict(rows=a.rows)
     t0 = time.perf_counter()
-    g = PackedGenome.from_fasta(a.fasta) if a.fasta else PackedGenome.from_sequences(synthetic_seqs(a.genome_mb, rng))
+    g = PackedGenome.from_fasta(a.fasta) if a.fasta else PackedGenome.from_sequences(synthetic_seqs(a.genome_mb, rng, centromere=False))
     g.two_bit()
     res.update(genome=a.fasta or "synthetic", genome_bases=int(g.lengths.sum()), pack_s=round(time.perf_counter() - t0, 1))
     chrom, start = make_rows(g, a.rows, rng)
@@ -118,7 +104,7 @@ def main():
     del g
     if not a.skip_cli:
         with tempfile.TemporaryDirectory() as tmp:
-            seqs = synthetic_seqs(a.cli_genome_mb, rng)
+            seqs = synthetic_seqs(a.cli_genome_mb, rng, centromere=False)
             fa = os.path.join(tmp, "g.fa")
             with open(fa, "wb") as f:
                 for n, s in seqs.items():

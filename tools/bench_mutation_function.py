@@ -85,7 +85,7 @@ def main():
     genes, gch = synthetic_genes(g, a.genes, rng).on_genome(g)
     t = lambda x: torch.as_tensor(x, device=dev)
     p = _lib.dev_ptr
-    w2, ns, ne, bk, off, ln = g.on_device2(dev)
+    genome = g.genome2_args(dev)
     tab = [t(x) for x in (gch, genes.minus, genes.blk_ptr, genes.blk_start, genes.blk_end, genes.cds_off, genes.spl_ptr, genes.spl_pos)]
     r_chrom, r_start, r_end, r_gene = genes.ranges()
     blocks = tabulate_gpu.ElementBlocks(g.chrom_index(r_chrom).astype(np.int64) + 1, r_start - 1, r_end, np.arange(len(r_start)), len(r_start), dev)
@@ -104,8 +104,7 @@ def main():
         n_cds, cmin, cmax = (torch.empty(n, dtype=torch.int32, device=dev) for _ in range(3))
 
         def launch():
-            _lib.call("dig_mutation_function", p(w2), w2.numel(), p(ns), p(ne), ns.numel(), p(bk), bk.numel(), p(off), p(ln), len(g.names),
-                      *[p(x) for x in tab], len(genes), p(pg), p(ps), p(ps), p(kind), p(ref), p(alt), n, p(impact), p(status), p(n_cds),
+            _lib.call("dig_mutation_function", *genome, *[p(x) for x in tab], len(genes), p(pg), p(ps), p(ps), p(kind), p(ref), p(alt), n, p(impact), p(status), p(n_cds),
                       p(cmin), p(cmax), _lib.stream_ptr())
 
         key = "%gM" % millions
