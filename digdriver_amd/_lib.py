@@ -87,6 +87,8 @@ _SIGNATURES = {
     "dig_mutation_function": [_vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _int] + [_vp] * 8 + [_i64] + [_vp] * 6 + [_i64] + [_vp] * 6,
     "dig_mutation_function_host": [_vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _int] + [_vp] * 8 + [_i64] + [_vp] * 6 + [_i64] +
                                   [_vp] * 5 + [_int],
+    "dig_gene_site_counts": [_vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _int] + [_vp] * 8 + [_i64] + [_vp] * 4,
+    "dig_gene_site_counts_host": [_vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _int] + [_vp] * 8 + [_i64] + [_vp] * 3 + [_int],
     "dig_mutctx_file_parse_host": [ctypes.c_char_p, _vp, _vp, _vp],
     "dig_mutctx_file_fetch_host": [_vp, _vp, _vp, _vp],
     "dig_mutctx_file_write_host": [_vp, ctypes.c_char_p, _vp, _vp, _vp, _vp, _int, _int],

@@ -123,6 +123,28 @@ int call_genome2(Staging& st, Fn fn, const Genome2& H, Args... args)
                    H.n_chrom, args...);
 }
 
+// the gene table of the genic twins, once its pointers are known to be non-null
+int check_gene_table(const char* fn, const int32_t* gene_chrom, const int64_t* blk_ptr, const int64_t* blk_start, const int64_t* blk_end,
+                     const int64_t* cds_off, const int64_t* spl_ptr, const int64_t* spl_pos, int64_t n_genes, const int64_t* chrom_len,
+                     int n_chrom)
+{
+    for (int64_t g = 0; g < n_genes; ++g) {
+        DIG_REQUIRE_IN(fn, gene_chrom[g] >= 0 && gene_chrom[g] < n_chrom, "gene chromosome index within [0, n_chrom)");
+        DIG_REQUIRE_IN(fn, blk_ptr[g] <= blk_ptr[g + 1] && spl_ptr[g] <= spl_ptr[g + 1], "blk_ptr, spl_ptr non-decreasing");
+        int64_t len = 0;
+        for (int64_t b = blk_ptr[g]; b < blk_ptr[g + 1]; ++b) {
+            DIG_REQUIRE_IN(fn, blk_start[b] >= 1 && blk_start[b] <= blk_end[b] && blk_end[b] <= chrom_len[gene_chrom[g]],
+                       "CDS blocks 1-based, closed, inside the chromosome");
+            DIG_REQUIRE_IN(fn, b == blk_ptr[g] || blk_end[b - 1] < blk_start[b], "CDS blocks of a gene ascending and disjoint");
+            DIG_REQUIRE_IN(fn, cds_off[b] == len, "cds_off: the CDS length in front of the block");
+            len += blk_end[b] - blk_start[b] + 1;
+        }
+        DIG_REQUIRE_IN(fn, len % 3 == 0 && len <= INT32_MAX, "CDS length a multiple of 3 below 2^31");
+        for (int64_t q = spl_ptr[g] + 1; q < spl_ptr[g + 1]; ++q) DIG_REQUIRE_IN(fn, spl_pos[q - 1] < spl_pos[q], "splice positions of a gene ascending");
+    }
+    return DIG_OK;
+}
+
 size_t dtype_size(int dt)
 {
     switch (dt) {
@@ -369,20 +391,8 @@ int dig_mutation_function_host(const uint32_t* words2, int64_t n_words2, const i
     DIG_REQUIRE(n_blk == 0 || (blk_start && blk_end && cds_off), "non-null block arrays");
     DIG_REQUIRE(n_spl == 0 || spl_pos, "non-null spl_pos");
     if (int rc = genome2_check_host(__func__, H)) return rc;
-    for (int64_t g = 0; g < n_genes; ++g) {
-        DIG_REQUIRE(gene_chrom[g] >= 0 && gene_chrom[g] < n_chrom, "gene chromosome index within [0, n_chrom)");
-        DIG_REQUIRE(blk_ptr[g] <= blk_ptr[g + 1] && spl_ptr[g] <= spl_ptr[g + 1], "blk_ptr, spl_ptr non-decreasing");
-        int64_t len = 0;
-        for (int64_t b = blk_ptr[g]; b < blk_ptr[g + 1]; ++b) {
-            DIG_REQUIRE(blk_start[b] >= 1 && blk_start[b] <= blk_end[b] && blk_end[b] <= chrom_len[gene_chrom[g]],
-                        "CDS blocks 1-based, closed, inside the chromosome");
-            DIG_REQUIRE(b == blk_ptr[g] || blk_end[b - 1] < blk_start[b], "CDS blocks of a gene ascending and disjoint");
-            DIG_REQUIRE(cds_off[b] == len, "cds_off: the CDS length in front of the block");
-            len += blk_end[b] - blk_start[b] + 1;
-        }
-        DIG_REQUIRE(len % 3 == 0 && len <= INT32_MAX, "CDS length a multiple of 3 below 2^31");
-        for (int64_t q = spl_ptr[g] + 1; q < spl_ptr[g + 1]; ++q) DIG_REQUIRE(spl_pos[q - 1] < spl_pos[q], "splice positions of a gene ascending");
-    }
+    if (int rc = check_gene_table(__func__, gene_chrom, blk_ptr, blk_start, blk_end, cds_off, spl_ptr, spl_pos, n_genes, chrom_len, n_chrom))
+        return rc;
     for (int64_t i = 0; i < n_pairs; ++i) DIG_REQUIRE(pair_gene[i] >= 0 && pair_gene[i] < n_genes, "pair gene index within [0, n_genes)");
     const size_t ng = (size_t)n_genes;
     Staging st(device);
@@ -391,6 +401,33 @@ int dig_mutation_function_host(const uint32_t* words2, int64_t n_words2, const i
                         st.in(spl_pos, n_spl), n_genes, st.in(pair_gene, n_pairs), st.in(pair_start, n_pairs), st.in(pair_end, n_pairs),
                         st.in(pair_kind, n_pairs), st.in(pair_ref, n_pairs), st.in(pair_alt, n_pairs), n_pairs, st.out(impact, n_pairs),
                         st.out(status, n_pairs), st.out(n_cds, n_pairs), st.out(cds_min, n_pairs), st.out(cds_max, n_pairs), nullptr);
+}
+
+int dig_gene_site_counts_host(const uint32_t* words2, int64_t n_words2, const int64_t* nint_start, const int64_t* nint_end, int64_t n_int,
+                              const int32_t* nint_bucket, int64_t n_buckets, const int64_t* chrom_off, const int64_t* chrom_len,
+                              int n_chrom, const int32_t* gene_chrom, const uint8_t* gene_minus, const int64_t* blk_ptr,
+                              const int64_t* blk_start, const int64_t* blk_end, const int64_t* cds_off, const int64_t* spl_ptr,
+                              const int64_t* spl_pos, int64_t n_genes, int32_t* L, int32_t* n_stop_loss, uint8_t* status, int device)
+{
+    DIG_REQUIRE(n_genes >= 0, "n_genes >= 0");
+    const Genome2 H = {words2, n_words2, nint_start, nint_end, n_int, nint_bucket, n_buckets, chrom_off, chrom_len, n_chrom};
+    if (int rc = genome2_check(__func__, H, n_genes)) return rc;
+    if (n_genes == 0) return DIG_OK;
+    DIG_REQUIRE(words2 && chrom_off && chrom_len && blk_ptr && spl_ptr, "non-null genome arrays, blk_ptr, spl_ptr");
+    DIG_REQUIRE(gene_chrom && gene_minus, "non-null gene_chrom, gene_minus");
+    DIG_REQUIRE(L && n_stop_loss && status, "non-null outputs");
+    const int64_t n_blk = blk_ptr[n_genes], n_spl = spl_ptr[n_genes];
+    DIG_REQUIRE(blk_ptr[0] == 0 && spl_ptr[0] == 0 && n_blk >= 0 && n_spl >= 0, "blk_ptr, spl_ptr start at 0");
+    DIG_REQUIRE(n_blk == 0 || (blk_start && blk_end && cds_off), "non-null block arrays");
+    DIG_REQUIRE(n_spl == 0 || spl_pos, "non-null spl_pos");
+    if (int rc = genome2_check_host(__func__, H)) return rc;
+    if (int rc = check_gene_table(__func__, gene_chrom, blk_ptr, blk_start, blk_end, cds_off, spl_ptr, spl_pos, n_genes, chrom_len, n_chrom))
+        return rc;
+    const size_t ng = (size_t)n_genes;
+    Staging st(device);
+    return call_genome2(st, dig_gene_site_counts, H, st.in(gene_chrom, ng), st.in(gene_minus, ng), st.in(blk_ptr, ng + 1),
+                        st.in(blk_start, n_blk), st.in(blk_end, n_blk), st.in(cds_off, n_blk), st.in(spl_ptr, ng + 1),
+                        st.in(spl_pos, n_spl), n_genes, st.out(L, ng * 4 * 192), st.out(n_stop_loss, ng), st.out(status, ng), nullptr);
 }
 
 int dig_element_pipeline_host(const double* bin_mu, const double* bin_std, const int32_t* bin_y, const uint8_t* bin_flag,

@@ -833,6 +833,106 @@ def mutation_function(genome, genes, gene_chrom, pair_gene, pair_start, pair_end
     return impact, status, n_cds, cds_min, cds_max
 
 
+GS_OK, GS_HOST = 0, 1                                            # include/dig_hip.h DIG_GS_*
+_GS_CODE = "KNKNTTTTRSRSIIMIQHQHPPPPRRRRLLLLEDEDAAAAGGGGVVVV*Y*YSSSS*CWCLFLF"      # codon 16 b0 + 4 b1 + b2, A C G T = 0 .. 3
+_GS_COMP = bytes.maketrans(b"ACGT", b"TGCA")
+
+
+def _gene_sites_from_letters(genome, genes, gene_chrom, g):
+    """(L [4, 192], n_stop_loss) of one gene the kernel left to the host (DIG_GS_HOST), from PackedGenome's letters: a site whose
+    trinucleotide holds a letter other than ACGT (or is cut off by the chromosome end) is skipped, as seq_to_context returning
+    nothing skips it in si_by_regions (sequence_tools.py:416-417); a codon with such a letter translates to X, as for
+    addMutationFunction."""
+    ci, minus = int(gene_chrom[g]), bool(genes.minus[g])
+    clen = int(genome.lengths[ci])
+    b0, b1 = int(genes.blk_ptr[g]), int(genes.blk_ptr[g + 1])
+    pos = np.concatenate([np.arange(s, e + 1) for s, e in zip(genes.blk_start[b0:b1], genes.blk_end[b0:b1])] or [np.zeros(0, np.int64)])
+    if minus:
+        pos = pos[::-1]
+    spl = genes.spl_pos[genes.spl_ptr[g]:genes.spl_ptr[g + 1]]
+    L, n_stop_loss = np.zeros((4, 192), np.int32), 0
+    code = {c: i for i, c in enumerate(b"ACGT")}
+
+    def context(p):                                                  # (X, Y, Z) in transcript direction, or None
+        if p - 1 < 1 or p + 1 > clen:
+            return None
+        w = genome.letters(ci, p - 2, p + 1)
+        w = w[::-1].translate(_GS_COMP) if minus else w
+        return tuple(code[c] for c in w) if all(c in code for c in w) else None
+
+    def amino(codon):
+        return _GS_CODE[16 * codon[0] + 4 * codon[1] + codon[2]] if None not in codon else 'X'
+
+    for k in range(len(pos) // 3):
+        letters = [genome.letters(ci, int(p) - 1, int(p)) for p in pos[3 * k:3 * k + 3]]
+        codon = [code.get((c.translate(_GS_COMP) if minus else c)[0]) for c in letters]
+        for at in range(3):
+            ctx = context(int(pos[3 * k + at]))
+            if ctx is None:
+                continue
+            for a in range(4):
+                if a == ctx[1]:
+                    continue
+                changed = codon[:at] + [a] + codon[at + 1:]
+                old_aa, new_aa = amino(codon), amino(changed)
+                col = 3 * (16 * ctx[0] + 4 * ctx[1] + ctx[2]) + a - (a > ctx[1])
+                if new_aa == old_aa:
+                    L[0, col] += 1
+                elif new_aa == '*':
+                    L[2, col] += 1
+                elif old_aa != '*':
+                    L[1, col] += 1
+                else:
+                    n_stop_loss += 1
+    for p in spl:
+        ctx = context(int(p))
+        if ctx is not None:
+            c0 = 3 * (16 * ctx[0] + 4 * ctx[1] + ctx[2])
+            L[3, c0:c0 + 3] += 1
+    return L, n_stop_loss
+
+
+def gene_site_counts(genome, genes, gene_chrom, device=0, on_device=True, return_status=False):
+    """The possible single-base substitutions of every gene by effect class and substitution type (dig_gene_site_counts; the L of
+    the gene container) over a PackedGenome.  genes: a gene_annotation.GeneSet; gene_chrom: the genome's chromosome index of every
+    gene (GeneSet.on_genome).  Returns host arrays (L i32 [G, 4, 192] -- classes silent, missense, nonsense, essential splice;
+    columns in the order of the sorted substitution index --, n_stop_loss i32 [G]); the genes the kernel left to the host (a letter
+    other than ACGT in their CDS, splice positions or flanks) are finished from the genome's letters.  on_device=True keeps the
+    genome resident in HBM; False goes through the host twin and needs no torch.  return_status: also the kernel's status per gene
+    (GS_OK / GS_HOST)."""
+    G = len(genes)
+    gch = _lib.as_host(gene_chrom, np.int32).ravel()
+    assert len(gch) == G
+    if G and ((gch < 0).any() or (gch >= len(genome.names)).any()):
+        raise ValueError("gene chromosome index outside the genome")
+    last = genes.blk_end[genes.blk_ptr[1:] - 1] if G else np.zeros(0, np.int64)
+    if G and ((genes.blk_start < 1).any() or (last > genome.lengths[gch]).any()):
+        raise ValueError("a gene's CDS blocks reach outside its chromosome")
+    if G and (genes.cds_len % 3).any():
+        raise ValueError("a gene's CDS length is not a multiple of 3")
+    table = (gch, genes.minus, genes.blk_ptr, genes.blk_start, genes.blk_end, genes.cds_off, genes.spl_ptr, genes.spl_pos)
+    if on_device:
+        import torch
+        dev = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
+        L = torch.empty((G, 4, 192), dtype=torch.int32, device=dev)
+        nsl = torch.empty(G, dtype=torch.int32, device=dev)
+        status = torch.empty(G, dtype=torch.uint8, device=dev)
+        p = _lib.dev_ptr
+        with torch.cuda.device(dev):
+            tab = [torch.as_tensor(a, device=dev) for a in table]
+            _lib.call("dig_gene_site_counts", *genome.genome2_args(dev), *[p(a) for a in tab], G, p(L), p(nsl), p(status),
+                      _lib.stream_ptr())
+        L, nsl, status = L.cpu().numpy(), nsl.cpu().numpy(), status.cpu().numpy()
+    else:
+        L, nsl, status = np.empty((G, 4, 192), np.int32), np.empty(G, np.int32), np.empty(G, np.uint8)
+        h = _lib.host_ptr
+        _lib.call("dig_gene_site_counts_host", *genome.genome2_args(), *[h(a) for a in table], G, h(L), h(nsl), h(status),
+                  device if isinstance(device, int) else 0)
+    for g in np.flatnonzero(status == GS_HOST):
+        L[g], nsl[g] = _gene_sites_from_letters(genome, genes, gch, int(g))
+    return (L, nsl, status) if return_status else (L, nsl)
+
+
 def tiled_nb_test(pt, k, mu, sigma, device=0):
     """Per-tile exact NB test (nb_model.py:141-178).  pt f64 [n_bins, n_tiles] or [C, n_bins, n_tiles];
     k i32 [C, n_bins, n_tiles]; mu, sigma f64 [C, n_bins].  Returns (pval, exp) [C, n_bins, n_tiles]."""

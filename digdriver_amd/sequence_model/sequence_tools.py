@@ -308,6 +308,138 @@ def preprocess_sites(f_sites, f_nonc_data, f_pretrained, save_key, window):
 
 
 # ---------------------------------------------------------------------------------------------
+# the gene container from a bed12 of coding exons + FASTA, and the window counts of the genes (DigPreprocess.py
+# preprocess_genic_model; reference: L_data from refcds_hg19.rda, si_count_* as a Python loop per base, sequence_tools.py:375-449)
+# ---------------------------------------------------------------------------------------------
+def _region_counts(genome, chroms, starts, ends, minus, on_device):
+    from .. import engine
+    cnt = engine.count_contexts(genome, chroms, starts, ends, minus, on_device=on_device)
+    return (cnt.cpu().numpy() if on_device else cnt).astype(np.int64)
+
+
+def _context_columns(trans_idx):
+    """(sorted substitution keys, for each the column of its context among mk_context_sequences(1, 1))."""
+    keys = sorted(set(str(k) for k in trans_idx))
+    pos = {c: i for i, c in enumerate(mk_context_sequences(1, 1))}
+    return keys, np.array([pos[k.split('>')[0]] for k in keys], np.int64)
+
+
+def si_by_regions(f_fasta, trans_idx, regions, strand=1, n_up=1, n_down=1, normed=True, on_device=None, count=None):
+    """sequence_tools.py:396-425: for regions "chrom:start-end" the number of positions at which each substitution of trans_idx can
+    happen -- the count of its trinucleotide in the regions (each fetched with one base on either side, cut off at the contig's
+    ends; windows with an N skipped), on the reverse-complemented sequence for strand -1 / '-'.  One-column frame indexed by the
+    sorted substitution keys.  count(genome, chroms, starts, ends, minus) -> [R, 64] replaces dig_count_contexts2."""
+    if (n_up, n_down) != (1, 1):
+        raise NotImplementedError("si_by_regions counts trinucleotides (n_up = n_down = 1)")
+    genome = load_genome(f_fasta)
+    chroms = [r.split(':')[0] for r in regions]
+    starts = np.array([int(r.split(':')[1].split('-')[0]) for r in regions], np.int64)
+    ends = np.array([int(r.split('-')[1]) for r in regions], np.int64)
+    minus = np.full(len(regions), strand == -1 or strand == '-', bool)
+    count = count or (lambda *a: _region_counts(*a, _on_device(on_device)))
+    cnt = np.asarray(count(genome, chroms, starts, ends, minus), np.int64).reshape(-1, 64).sum(axis=0)
+    keys, cols = _context_columns(trans_idx)
+    return pd.DataFrame(cnt[cols], index=keys)
+
+
+def si_count_pretrain(gene_lst, f_genic, f_fasta, window, on_device=None, count=None):
+    """sequence_tools.py:375-393: frame [genes x 192 sorted substitutions] of the context counts of the windows each gene of
+    gene_lst overlaps (get_ideal_overlaps of its CDS blocks), on the gene's strand; every substitution column holds its context's
+    count.  The genes come from window_{w}/genes/ of f_genic (preprocess_genic).  All genes at once: the distinct windows are
+    counted by one dig_count_contexts2 launch on the + strand (a - gene reads the reverse-complemented contexts) and summed per
+    gene."""
+    from .. import engine
+    from ..io import mapfile
+    base = 'window_{}/genes/'.format(window)
+    names = mapfile.read_array(f_genic, base + 'names').astype(str)
+    pos = {n: i for i, n in enumerate(names)}
+    sel = np.array([pos[g] for g in gene_lst], np.int64)
+    chrom_str = mapfile.read_array(f_genic, base + 'chrom_str').astype(str)[sel]
+    strand = mapfile.read_array(f_genic, base + 'strand').astype(str)[sel]
+    blk_ptr = mapfile.read_array(f_genic, base + 'blk_ptr').astype(np.int64)
+    bs, be = (mapfile.read_array(f_genic, base + k).astype(np.int64) for k in ('blk_start', 'blk_end'))
+    cnt_blk = (blk_ptr[1:] - blk_ptr[:-1])[sel]
+    ptr = np.concatenate([[0], np.cumsum(cnt_blk)]).astype(np.int64)
+    take = np.repeat(blk_ptr[sel] - ptr[:-1], cnt_blk) + np.arange(int(ptr[-1]), dtype=np.int64)
+    bs, be = bs[take], be[take]
+    if mapfile.has_key(f_genic, 'substitution_idx'):
+        trans_idx = mapfile.read_array(f_genic, 'substitution_idx').astype(str)
+    else:
+        trans_idx = mk_trans_idx(n_up=1, n_down=1, collapse=False)
+    keys, cols = _context_columns(trans_idx)
+    out = np.zeros((len(sel), 64), np.int64)
+    if len(sel) and len(bs):
+        labels, code = np.unique(chrom_str, return_inverse=True)
+        owner = np.repeat(np.arange(len(sel)), cnt_blk)
+        # the table of every window a block can touch: per contig 0, w, ... beyond the last block's end
+        top = np.zeros(len(labels), np.int64)
+        np.maximum.at(top, code[owner], be)
+        n_bins = top // window + 2
+        bin_chrom = np.repeat(np.arange(len(labels), dtype=np.int32), n_bins)
+        bin_start = np.concatenate([np.arange(n, dtype=np.int64) * window for n in n_bins])
+        ov_ptr, ov_idx = engine.ideal_overlaps(code.astype(np.int32), ptr, bs, be, window, bin_chrom, bin_start)
+        used, inv = np.unique(ov_idx, return_inverse=True)
+        genome = load_genome(f_fasta)
+        count = count or (lambda *a: _region_counts(*a, _on_device(on_device)))
+        chroms = ['chr{}'.format(labels[c]) for c in bin_chrom[used]]
+        cnt = np.asarray(count(genome, chroms, bin_start[used], bin_start[used] + window, np.zeros(len(used), bool)), np.int64)
+        has = np.diff(ov_ptr) > 0
+        out[has] = np.add.reduceat(cnt[inv], ov_ptr[:-1][has], axis=0)
+        ctx = list(mk_context_sequences(1, 1))
+        rc = np.array([ctx.index(reverse_complement(c)) for c in ctx], np.int64)
+        flip = (strand == '-') | (strand == '-1')
+        out[flip] = out[flip][:, rc]
+    return pd.DataFrame(out[:, cols], index=list(gene_lst), columns=keys)
+
+
+def si_count_parallel(f_genic, f_fasta, window, n_procs=1, on_device=None, count=None):
+    """sequence_tools.py:428-449 for every gene of the container; n_procs is accepted for compatibility (one launch)."""
+    from ..io import mapfile
+    names = mapfile.read_array(f_genic, 'window_{}/genes/names'.format(window)).astype(str)
+    return si_count_pretrain(list(names), f_genic, f_fasta, window, on_device=on_device, count=count)
+
+
+def preprocess_genic(f_cds_bed, f_fasta, f_genic, window, on_device=None, counts=None):
+    """The gene container of genicModel / geneDriver from a bed12 of coding exons and a FASTA: under window_{w}/genes/ of f_genic
+    the arrays genic_model reads -- names, chrom (i32), chrom_str, strand, blk_ptr, blk_start, blk_end (the GeneSet's 1-based closed
+    CDS blocks) and L i32 [G, 4, 192], the possible substitutions of every gene by class (silent, missense, nonsense, essential
+    splice) and sorted substitution type (dig_gene_site_counts) -- plus n_stop_loss.  The reference takes L (L_data) from dNdScv's
+    refcds_hg19.rda and has no code that makes it.  Genes on X / Y are kept (chrom 23 / 24; genic_model skips them by chrom_str),
+    genes on any other non-numeric contig are dropped with a printed count.  f_cds_bed: a bed12 file or a GeneSet; f_fasta: a
+    path or a PackedGenome.  counts(genome, genes, gene_chrom) -> (L, n_stop_loss) replaces the kernel.  Returns the GeneSet
+    written."""
+    from .. import engine
+    from ..data_tools import gene_annotation
+    from ..io import mapfile
+    genes = f_cds_bed if isinstance(f_cds_bed, gene_annotation.GeneSet) else gene_annotation.load_cds_bed12(f_cds_bed)
+    genome = load_genome(f_fasta)
+    genes, gene_chrom = genes.on_genome(genome)
+    label = np.array([c[3:] if c.startswith('chr') else c for c in genes.chrom.astype(str)], dtype=object)
+    sex = {'X': 23, 'Y': 24}
+    keep = np.array([c.isdigit() or c in sex for c in label], bool)
+    if not keep.all():
+        print("Dropping {} genes on contigs other than the numbered ones, X and Y: {}".format(
+            int((~keep).sum()), ", ".join(sorted(set(label[~keep].tolist())))))
+        genes, gene_chrom, label = genes.subset(keep), gene_chrom[keep], label[keep]
+    dev = _on_device(on_device)
+    counts = counts or (lambda *a: engine.gene_site_counts(*a, on_device=dev))
+    L, n_stop_loss = counts(genome, genes, gene_chrom)
+    L = np.ascontiguousarray(L, np.int32).reshape(len(genes), 4, 192)
+    base = 'window_{}/genes/'.format(window)
+    with mapfile.batch(f_genic):
+        mapfile.write_array(f_genic, base + 'names', np.array(genes.names, dtype=str))
+        mapfile.write_array(f_genic, base + 'chrom', np.array([sex[c] if c in sex else int(c) for c in label], np.int32))
+        mapfile.write_array(f_genic, base + 'chrom_str', label.astype(str))
+        mapfile.write_array(f_genic, base + 'strand', np.where(genes.minus != 0, '-', '+').astype(str))
+        mapfile.write_array(f_genic, base + 'blk_ptr', genes.blk_ptr)
+        mapfile.write_array(f_genic, base + 'blk_start', genes.blk_start)
+        mapfile.write_array(f_genic, base + 'blk_end', genes.blk_end)
+        mapfile.write_array(f_genic, base + 'L', L)
+        mapfile.write_array(f_genic, base + 'n_stop_loss', np.ascontiguousarray(n_stop_loss, np.int32))
+    return genes
+
+
+# ---------------------------------------------------------------------------------------------
 # sequence context of mutations (DigPreprocess.py addMutationContext; reference: a Python loop per row over a whole
 # chromosome string, one pool worker per chromosome, sequence_tools.py:130-222) -- dig_mutation_contexts on the GPU
 # ---------------------------------------------------------------------------------------------

@@ -511,6 +511,35 @@ int dig_mutation_function_host(const uint32_t *words2, int64_t n_words2, const i
                                const uint8_t *pair_ref, const uint8_t *pair_alt, int64_t n_pairs, uint8_t *impact, uint8_t *status,
                                int32_t *n_cds, int32_t *cds_min, int32_t *cds_max, int device);
 
+/* ---- possible substitutions of genes (DigPreprocess.py preprocess_genic_model --cds-bed: the L of the gene container) ---- *
+ * For every gene of the gene table of dig_mutation_function (same ten genome arguments, same eight gene-table arguments, no
+ * pairs) the number of possible single-base substitutions by effect class and substitution type:
+ *   L i32 [n_genes, 4, 192]: class 0 silent, 1 missense, 2 nonsense, 3 essential splice (the rows of the reference's L_data,
+ *       genic_driver_tools.py:110-123).  Every CDS base p (CDS index 1 .. len in transcript direction) and each of its three
+ *       alternates is classified on its codon as dig_mutation_function classifies an SNV; DIG_MF_SYN / _MIS / _NONS add one to class
+ *       0 / 1 / 2, DIG_MF_STOP_LOSS to none (it is counted in n_stop_loss).  Every splice position adds its three alternates to
+ *       class 3.
+ *   type: the genome's bases p - 1, p, p + 1 (at an exon edge a flank is an intron base) in transcript direction -- reverse-
+ *       complemented for a - gene, the alternate complemented -- as X Y Z -> X a Z with A C G T = 0 .. 3: column
+ *       3 (16 X + 4 Y + Z) + rank of a among the three bases other than Y (the sorted substitution index, mk_trans_idx).
+ *   n_stop_loss i32 [n_genes]; status u8 [n_genes]: DIG_GS_OK, or DIG_GS_HOST for a gene in which a base read (a CDS or splice
+ *       position or a flank) is a letter other than ACGT or lies outside the chromosome: its L row and n_stop_loss are zero and
+ *       the caller finishes it from the letters.  Every output row is written (nothing to zero beforehand). */
+#define DIG_GS_OK 0
+#define DIG_GS_HOST 1
+int dig_gene_site_counts(const uint32_t *words2, int64_t n_words2, const int64_t *nint_start, const int64_t *nint_end,
+                         int64_t n_int, const int32_t *nint_bucket, int64_t n_buckets, const int64_t *chrom_off,
+                         const int64_t *chrom_len, int n_chrom, const int32_t *gene_chrom, const uint8_t *gene_minus,
+                         const int64_t *blk_ptr, const int64_t *blk_start, const int64_t *blk_end, const int64_t *cds_off,
+                         const int64_t *spl_ptr, const int64_t *spl_pos, int64_t n_genes, int32_t *L, int32_t *n_stop_loss,
+                         uint8_t *status, void *stream);
+int dig_gene_site_counts_host(const uint32_t *words2, int64_t n_words2, const int64_t *nint_start, const int64_t *nint_end,
+                              int64_t n_int, const int32_t *nint_bucket, int64_t n_buckets, const int64_t *chrom_off,
+                              const int64_t *chrom_len, int n_chrom, const int32_t *gene_chrom, const uint8_t *gene_minus,
+                              const int64_t *blk_ptr, const int64_t *blk_start, const int64_t *blk_end, const int64_t *cds_off,
+                              const int64_t *spl_ptr, const int64_t *spl_pos, int64_t n_genes, int32_t *L, int32_t *n_stop_loss,
+                              uint8_t *status, int device);
+
 /* ---- result files (ABI 6; host code only) ------------------------------------------------- *
  * The text DataFrame.to_csv(path, header=True, index=True, sep="\t") writes for a frame (DigDriver.py:115-118): `header`
  * (a complete first line, no newline), then n_rows rows  label TAB col_0 TAB ... col_{n_cols-1}.

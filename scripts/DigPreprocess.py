@@ -10,12 +10,15 @@ refcds_hg19.rda; here the gene table comes from a bed12 file of coding exons (--
     addMutationContext        MUT_TYPE and CONTEXT columns of a mutation file (:75-100)
     annotMutationFile         addMutationFunction, then addMutationContext (:111-117)
     initialize_f_data         start an element-data container            (:147-153)
+    preprocess_genic_model    the gene container from bed12 + FASTA (--cds-bed) and the genes' window counts (:119-127)
     preprocess_element_model  per-element L counts from bed12 + FASTA    (:129-145)
     preprocess_tiled          L counts of a tiled genome                 (:155-164)
 
 Same positional arguments and option names.  Sequence is read once into a 4-bit packed array (cached next to the
 FASTA) and counted by dig_count_contexts2 / dig_count_contexts5 instead of per-region pysam fetches; the mutation contexts come from
-dig_mutation_contexts and the genic function from dig_mutation_function over the same genome.
+dig_mutation_contexts and the genic function from dig_mutation_function over the same genome.  preprocess_genic_model --cds-bed
+builds what the reference takes from refcds_hg19.rda and has no code for: the gene container (window_{w}/genes/ with L, the
+possible substitutions of every gene by class and type, from dig_gene_site_counts) that DigPretrain.py genicModel reads.
 """
 import argparse
 import os
@@ -113,6 +116,28 @@ def initialize_data(args):
     sequence_tools.initialize_nonc_data(args.f_annot_data, args.f_genome_counts, int(idx[0, 2] - idx[0, 1]))
 
 
+def preprocess_cds_contexts(args):
+    # torch-free, as addMutationFunction
+    from digdriver_amd import _lib
+    _lib.TORCH_FREE = True
+    key = 'window_{}'.format(args.window)
+    if args.cds_bed:
+        print('Building the gene container from {}'.format(args.cds_bed))
+        try:
+            genes = sequence_tools.preprocess_genic(args.cds_bed, args.f_fasta, args.f_genic, args.window, on_device=False)
+        except (ValueError, KeyError) as exc:
+            raise SystemExit("preprocess_genic_model: %s" % exc)
+        print('Saved {} genes under {}/genes of {}'.format(len(genes), key, args.f_genic))
+    elif not mapfile.has_key(args.f_genic, key + '/genes/names'):
+        raise SystemExit("f_genic does not hold {}/genes: pass --cds-bed (a bed12 file of coding exons) to build it.".format(key))
+    if not (mapfile.has_key(args.f_genic, key + '/full_window_si_index') and mapfile.has_key(args.f_genic, key + '/full_window_si_values')):
+        print("Note: {} does not hold {}/full_window_si_index and full_window_si_values, which genicModel reads: start the "
+              "container with initialize_f_data.".format(args.f_genic, key))
+    results = sequence_tools.si_count_parallel(args.f_genic, args.f_fasta, args.window, args.N_procs, on_device=False)
+    mapfile.write_frame(args.out_file, args.out_key, results)
+    print('Saved window context counts of {} genes to {}:{}'.format(len(results), args.out_file, args.out_key))
+
+
 def preprocess_nonc_contexts(args):
     if args.f_sites:
         print("preprocessing sites data")
@@ -177,6 +202,18 @@ def parse_args(text=None):
     d.add_argument('--n-procs', type=int, default=1, help='accepted for compatibility')
     d.set_defaults(func=annot_mutation_file)
 
+    c1 = sub.add_parser('preprocess_genic_model', help='the gene container (with --cds-bed) and the context counts of the windows '
+                                                      'each gene overlaps')
+    c1.add_argument('f_genic', help='gene-data container (see initialize_f_data)')
+    c1.add_argument('f_fasta', help='reference genome FASTA (hg19)')
+    c1.add_argument('out_file', help='container to save the window counts to')
+    c1.add_argument('--out-key', default='cds/window_10kb', help='key of the saved frame')
+    c1.add_argument('--n-procs', default=1, type=int, dest='N_procs', help='accepted for compatibility')
+    c1.add_argument('--window', type=int, default=10000, help='window size in bp')
+    c1.add_argument('--cds-bed', type=str, default='', help='build window_{w}/genes of f_genic first, from this ' + cds_help[0].lower() +
+                    cds_help[1:cds_help.index('; required')])
+    c1.set_defaults(func=preprocess_cds_contexts)
+
     e = sub.add_parser('preprocess_element_model', help='per-element context counts from a bed12 file')
     e.add_argument('f_element_data', help='element-data container (see initialize_f_data)')
     e.add_argument('f_pretrained', help='any pretrained map (kept for compatibility)')
@@ -210,5 +247,5 @@ if __name__ == "__main__":
     cli = parse_args()
     cli.func(cli)
     if os.environ.get("DIG_CLI_ASSERT_NO_TORCH") == "1" and cli.func in (add_mutation_context, add_mutation_function,
-                                                                            annot_mutation_file):
+                                                                            annot_mutation_file, preprocess_cds_contexts):
         assert "torch" not in sys.modules, "a torch-free sub-command imported torch"         # (tests: the claim above)
