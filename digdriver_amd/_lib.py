@@ -206,12 +206,15 @@ def last_error():
     return load().dig_last_error().decode("utf-8", "replace")
 
 
-def call(name, *args):
-    """Invoke an entry point; non-zero status -> DigHipError(dig_last_error())."""
-    lib = load()
-    rc = getattr(lib, name)(*args)
+def check(name, rc):
+    """Status of entry point `name`: non-zero -> DigHipError(dig_last_error())."""
     if rc != 0:
         raise DigHipError("%s failed (%d): %s" % (name, rc, last_error()))
+
+
+def call(name, *args):
+    """Invoke an entry point and check its status."""
+    check(name, getattr(load(), name)(*args))
 
 
 def workspace_bytes(kind, E, C):

@@ -12,30 +12,20 @@ element at a time:
     tiled_nb_test        <- nb_model.apply_nb_to_region arithmetic (nb_model.py:141-178)
 
 Every function takes either torch CUDA tensors (device entry points, enqueued on
-torch's current stream, zero copies) or numpy arrays (``*_host`` twins).  PyTorch is
-used only for device memory and streams.
+torch's current stream, zero copies) or numpy arrays (``*_host`` twins); each is written
+once on the backend pair of _marshal.py.  PyTorch is used only for device memory and streams.
 """
 import numpy as np
 
 from . import _lib
+from ._marshal import backend_of, backend_on, device_backend, is_cuda, resolve_device
 
 ES_PLANES = _lib.ES_PLANES
 GS_PLANES = _lib.GS_PLANES
 
 
-def _is_cuda(x):
-    return type(x).__module__.startswith("torch") and getattr(x, "is_cuda", False)
-
-
 def _t(x, dtype, device):
-    _lib._need_torch()
-    import torch
-    if x is None:
-        return None
-    t = torch.as_tensor(x, device=device)
-    if t.dtype != dtype:
-        t = t.to(dtype)
-    return t.contiguous()
+    return device_backend(device).arr(x, dtype)
 
 
 _WS_CACHE = {}
@@ -63,6 +53,32 @@ def _workspace(kind, E, C, dev, private=False):
     return ws, need
 
 
+def _shared_workspace(be, kind, E, C, use=True):
+    """The `workspace=` of be.call for a one-shot launch: the cached buffer on the device (NULL with use=False), nothing on the host."""
+    return _workspace(kind, E, C, be.dev) if be.is_device and use else (None, 0)
+
+
+def _cols(a):
+    """A table for one cohort given as a vector -> [n, 1]."""
+    return a[:, None] if a.ndim == 1 else a
+
+
+def _per_cohort(be, x, C):
+    """f64 [C] (None stays None); a single value stands for every cohort."""
+    x = be.arr(x, "f64", (-1,))
+    if x is not None and x.shape[0] == 1 and C != 1:
+        x = x.repeat(C)
+    assert x is None or x.shape[0] == C
+    return x
+
+
+def _rates(be, mu, sigma, mu_indel, sigma_indel):
+    """mu, sigma (and the optional indel pair) as f64 [n, C]; returns them and (n, C)."""
+    mu = _cols(be.arr(mu, "f64"))
+    n, C = mu.shape
+    return mu, be.arr(sigma, "f64", (n, C)), be.arr(mu_indel, "f64", (n, C)), be.arr(sigma_indel, "f64", (n, C)), n, C
+
+
 # ---------------------------------------------------------------------------
 def element_stats(mu, sigma, pi_sum, pi_indel, obs_snv, obs_samples, obs_indel, cj, cj_indel,
                   mu_indel=None, sigma_indel=None, device=0, out=None, use_workspace=True):
@@ -72,100 +88,50 @@ def element_stats(mu, sigma, pi_sum, pi_indel, obs_snv, obs_samples, obs_indel, 
     cj, cj_indel : f64 [C].  Returns a dict plane-name -> [E, C] array/tensor (views of one
     [7, E, C] buffer).  CUDA tensors in -> CUDA tensors out.
     """
-    if _is_cuda(mu):
-        import torch
-        dev = mu.device
-        f64, i32 = torch.float64, torch.int32
-        mu, sigma, pi_sum = (_t(v, f64, dev) for v in (mu, sigma, pi_sum))
-        E, C = mu.shape
-        pi_indel = _t(pi_indel, f64, dev)
-        per_cohort = int(pi_indel.dim() == 2)
-        obs_snv, obs_samples, obs_indel = (_t(v, i32, dev) for v in (obs_snv, obs_samples, obs_indel))
-        cj, cj_indel = _t(cj, f64, dev).reshape(-1), _t(cj_indel, f64, dev).reshape(-1)
-        assert cj.numel() == C and cj_indel.numel() == C
-        mu_indel, sigma_indel = _t(mu_indel, f64, dev), _t(sigma_indel, f64, dev)
-        if out is None:
-            out = torch.empty((len(ES_PLANES), E, C), dtype=f64, device=dev)
-        ws, wsb = _workspace("element_stats", E, C, dev) if use_workspace else (None, 0)
-        with torch.cuda.device(dev):
-            _lib.call("dig_element_stats", _lib.dev_ptr(mu), _lib.dev_ptr(sigma), _lib.dev_ptr(mu_indel),
-                      _lib.dev_ptr(sigma_indel), _lib.dev_ptr(pi_sum), _lib.dev_ptr(pi_indel), per_cohort,
-                      _lib.dev_ptr(obs_snv), _lib.dev_ptr(obs_samples), _lib.dev_ptr(obs_indel), _lib.dev_ptr(cj),
-                      _lib.dev_ptr(cj_indel), _lib.dev_ptr(out), E, C, _lib.dev_ptr(ws), wsb, _lib.stream_ptr())
-        return {name: out[i] for i, name in enumerate(ES_PLANES)}
-    mu = _lib.as_host(mu, np.float64)
-    if mu.ndim == 1:
-        mu = mu[:, None]
-    E, C = mu.shape
-    sigma = _lib.as_host(sigma, np.float64).reshape(E, C)
-    pi_sum = _lib.as_host(pi_sum, np.float64).reshape(E, C)
-    pi_indel = _lib.as_host(pi_indel, np.float64)
+    be = backend_of(mu, device=device)
+    mu, sigma, mu_indel, sigma_indel, E, C = _rates(be, mu, sigma, mu_indel, sigma_indel)
+    pi_sum = be.arr(pi_sum, "f64", (E, C))
+    pi_indel = be.arr(pi_indel, "f64")
     per_cohort = int(pi_indel.ndim == 2)
     assert pi_indel.shape == ((E, C) if per_cohort else (E,))
-    obs = [_lib.as_host(v, np.int32).reshape(E, C) for v in (obs_snv, obs_samples, obs_indel)]
-    cj = _lib.as_host(np.broadcast_to(np.asarray(cj, np.float64).reshape(-1), (C,)), np.float64)
-    cj_indel = _lib.as_host(np.broadcast_to(np.asarray(cj_indel, np.float64).reshape(-1), (C,)), np.float64)
-    mi = None if mu_indel is None else _lib.as_host(mu_indel, np.float64).reshape(E, C)
-    si = None if sigma_indel is None else _lib.as_host(sigma_indel, np.float64).reshape(E, C)
-    res = np.empty((len(ES_PLANES), E, C), np.float64)
-    _lib.call("dig_element_stats_host", _lib.host_ptr(mu), _lib.host_ptr(sigma), _lib.host_ptr(mi), _lib.host_ptr(si),
-              _lib.host_ptr(pi_sum), _lib.host_ptr(pi_indel), per_cohort, _lib.host_ptr(obs[0]), _lib.host_ptr(obs[1]),
-              _lib.host_ptr(obs[2]), _lib.host_ptr(cj), _lib.host_ptr(cj_indel), _lib.host_ptr(res), E, C, device)
-    return {name: res[i] for i, name in enumerate(ES_PLANES)}
+    obs = [be.arr(v, "i32", (E, C)) for v in (obs_snv, obs_samples, obs_indel)]
+    cj, cj_indel = _per_cohort(be, cj, C), _per_cohort(be, cj_indel, C)
+    if out is None:
+        out = be.empty((len(ES_PLANES), E, C), "f64")
+    p = be.ptr
+    be.call("dig_element_stats", p(mu), p(sigma), p(mu_indel), p(sigma_indel), p(pi_sum), p(pi_indel), per_cohort, p(obs[0]),
+            p(obs[1]), p(obs[2]), p(cj), p(cj_indel), p(out), E, C,
+            workspace=_shared_workspace(be, "element_stats", E, C, use_workspace))
+    return {name: out[i] for i, name in enumerate(ES_PLANES)}
 
 
 # ---------------------------------------------------------------------------
+def _gene_observations(be, obs, n_samp, cj, t_indel, G, C):
+    """obs i32 [G, 5, C], n_samp i32 [G, 6, C], cj and t_indel (or None) f64 [C]."""
+    return be.arr(obs, "i32", (G, 5, C)), be.arr(n_samp, "i32", (G, 6, C)), _per_cohort(be, cj, C), _per_cohort(be, t_indel, C)
+
+
 def gene_stats(mu, sigma, pi, pi_indel, obs, n_samp, cj, t_indel=None, mu_indel=None, sigma_indel=None, device=0, out=None):
     """The gene route's statistics block (transfer_tools.py:331-340,394-456,554-583,709-729,860-861) for G genes x C cohorts
     in ONE launch (dig_gene_stats).  mu, sigma f64 [G, C]; pi f64 [G, 6 or 4, C]; pi_indel [G] or [G, C]; obs i32 [G, 5, C]
     (SYN, MIS, NONS, SPL, INDEL); n_samp i32 [G, 6, C]; cj [C]; t_indel [C] or None (no indel block: those planes are NaN).
     Returns dict plane name -> [G, C] (views of one [22, G, C] buffer); CUDA tensors in -> CUDA tensors out."""
-    with_indel = int(t_indel is not None)
-    if _is_cuda(mu):
-        import torch
-        dev = mu.device
-        f64, i32 = torch.float64, torch.int32
-        mu, sigma, pi = _t(mu, f64, dev), _t(sigma, f64, dev), _t(pi, f64, dev)
-        G, C = mu.shape
-        n_pi = pi.shape[1]
-        assert pi.shape == (G, n_pi, C) and n_pi in (4, 6)
-        pi_indel = _t(pi_indel, f64, dev)
-        per_cohort = int(pi_indel is not None and pi_indel.dim() == 2)
-        obs, n_samp = _t(obs, i32, dev), _t(n_samp, i32, dev)
-        assert obs.shape == (G, 5, C) and n_samp.shape == (G, 6, C)
-        cj, t_indel = _t(cj, f64, dev).reshape(-1), (None if t_indel is None else _t(t_indel, f64, dev).reshape(-1))
-        mu_indel, sigma_indel = _t(mu_indel, f64, dev), _t(sigma_indel, f64, dev)
-        if out is None:
-            out = torch.empty((len(GS_PLANES), G, C), dtype=f64, device=dev)
-        p = _lib.dev_ptr
-        with torch.cuda.device(dev):
-            _lib.call("dig_gene_stats", p(mu), p(sigma), p(mu_indel), p(sigma_indel), p(pi), n_pi, p(pi_indel), per_cohort, p(obs),
-                      p(n_samp), p(cj), p(t_indel), with_indel, p(out), G, C, _lib.stream_ptr())
-        return {name: out[i] for i, name in enumerate(GS_PLANES)}
-    mu = _lib.as_host(mu, np.float64)
-    if mu.ndim == 1:
-        mu = mu[:, None]
-    G, C = mu.shape
-    sigma = _lib.as_host(sigma, np.float64).reshape(G, C)
-    pi = _lib.as_host(pi, np.float64)
+    be = backend_of(mu, device=device)
+    mu, sigma, mu_indel, sigma_indel, G, C = _rates(be, mu, sigma, mu_indel, sigma_indel)
+    pi = be.arr(pi, "f64")
     if pi.ndim == 2:
         pi = pi[:, :, None]
-    pi = np.ascontiguousarray(pi)
     n_pi = pi.shape[1]
     assert pi.shape == (G, n_pi, C) and n_pi in (4, 6)
-    pi_indel = None if pi_indel is None else _lib.as_host(pi_indel, np.float64)
+    pi_indel = be.arr(pi_indel, "f64")
     per_cohort = int(pi_indel is not None and pi_indel.ndim == 2)
-    obs = np.ascontiguousarray(_lib.as_host(obs, np.int32).reshape(G, 5, C))
-    n_samp = np.ascontiguousarray(_lib.as_host(n_samp, np.int32).reshape(G, 6, C))
-    cj = _lib.as_host(np.broadcast_to(np.asarray(cj, np.float64).reshape(-1), (C,)), np.float64)
-    ti = None if t_indel is None else _lib.as_host(np.broadcast_to(np.asarray(t_indel, np.float64).reshape(-1), (C,)), np.float64)
-    mi = None if mu_indel is None else _lib.as_host(mu_indel, np.float64).reshape(G, C)
-    si = None if sigma_indel is None else _lib.as_host(sigma_indel, np.float64).reshape(G, C)
-    res = np.empty((len(GS_PLANES), G, C), np.float64)
-    h = _lib.host_ptr
-    _lib.call("dig_gene_stats_host", h(mu), h(sigma), h(mi), h(si), h(pi), n_pi, h(pi_indel), per_cohort, h(obs), h(n_samp), h(cj),
-              h(ti), with_indel, h(res), G, C, device)
-    return {name: res[i] for i, name in enumerate(GS_PLANES)}
+    obs, n_samp, cj, ti = _gene_observations(be, obs, n_samp, cj, t_indel, G, C)
+    if out is None:
+        out = be.empty((len(GS_PLANES), G, C), "f64")
+    p = be.ptr
+    be.call("dig_gene_stats", p(mu), p(sigma), p(mu_indel), p(sigma_indel), p(pi), n_pi, p(pi_indel), per_cohort, p(obs), p(n_samp),
+            p(cj), p(ti), int(ti is not None), p(out), G, C)
+    return {name: out[i] for i, name in enumerate(GS_PLANES)}
 
 
 def gene_pipeline(bin_mu, bin_std, bin_y, bin_flag, bin_ctx, ov_ptr, ov_idx, L, strand_minus, gene_length, d_pr, obs, n_samp, cj,
@@ -173,55 +139,30 @@ def gene_pipeline(bin_mu, bin_std, bin_y, bin_flag, bin_ctx, ov_ptr, ov_idx, L, 
     """genic_model (genic_driver_tools.py:31-203) + the gene statistics block as one call on device tensors
     (dig_gene_pipeline): L i32 [G, 4, 192] (silent, missense, nonsense, splice columns), gene_length i32 [G].
     Returns (accumulate dict with P [G, 4, C], dict of the 22 statistics planes)."""
-    import torch
-    dev = bin_mu.device
-    f64, i32, i64, u8 = torch.float64, torch.int32, torch.int64, torch.uint8
-    bin_mu, bin_std = _t(bin_mu, f64, dev), _t(bin_std, f64, dev)
-    N, C = bin_mu.shape
-    bin_y, bin_flag, bin_ctx = _t(bin_y, i32, dev), _t(bin_flag, u8, dev), _t(bin_ctx, i32, dev)
-    ov_ptr, ov_idx, L = _t(ov_ptr, i64, dev), _t(ov_idx, i32, dev), _t(L, i32, dev)
-    G = L.shape[0]
-    assert L.shape == (G, 4, 192) and ov_ptr.numel() == G + 1
-    strand_minus, gene_length, d_pr = _t(strand_minus, u8, dev), _t(gene_length, i32, dev), _t(d_pr, f64, dev)
-    obs, n_samp = _t(obs, i32, dev), _t(n_samp, i32, dev)
-    assert obs.shape == (G, 5, C) and n_samp.shape == (G, 6, C)
-    cj = _t(cj, f64, dev).reshape(-1)
-    ti = None if t_indel is None else _t(t_indel, f64, dev).reshape(-1)
-    o = alloc_accumulate_outputs(G, C, 4, dev)
-    out = torch.empty((len(GS_PLANES), G, C), dtype=f64, device=dev)
-    ws, wsb = _workspace("accumulate", G, C, dev)
-    p = _lib.dev_ptr
-    with torch.cuda.device(dev):
-        _lib.call("dig_gene_pipeline", p(bin_mu), p(bin_std), p(bin_y), p(bin_flag), p(bin_ctx), p(ov_ptr), p(ov_idx), p(L),
-                  p(strand_minus), p(gene_length), p(d_pr), p(obs), p(n_samp), p(cj), p(ti), int(ti is not None), p(o["MU"]),
-                  p(o["SIGMA"]), p(o["R_OBS"]), p(o["FLAG"]), p(o["P"]), p(o["R_SIZE"]), p(o["ELT_SIZE"]), p(o["P_INDEL"]), p(out),
-                  N, G, C, p(ws), wsb, _lib.stream_ptr())
+    be = device_backend(bin_mu.device)
+    tabs, (N, G, C, n_class) = _bin_tables(be, bin_mu, bin_std, bin_y, bin_flag, bin_ctx, ov_ptr, ov_idx, L, strand_minus,
+                                           gene_length, d_pr)
+    assert n_class == 4
+    obs, n_samp, cj, ti = _gene_observations(be, obs, n_samp, cj, t_indel, G, C)
+    o = _accumulate_outputs(be, G, C, 4)
+    out = be.empty((len(GS_PLANES), G, C), "f64")
+    p = be.ptr
+    be.call("dig_gene_pipeline", *[p(x) for x in tabs], p(obs), p(n_samp), p(cj), p(ti), int(ti is not None),
+            *[p(o[k]) for k in _ACC_OUTPUTS], p(out), N, G, C, workspace=_shared_workspace(be, "accumulate", G, C))
     return o, {name: out[i] for i, name in enumerate(GS_PLANES)}
 
 
 # ---------------------------------------------------------------------------
 def scale_suffstats(bin_mu, bin_flag, device=0, out=None):
     """Per-cohort sum of Y_PRED over unflagged bins (transfer_tools.py:148-156): [N, C] -> [C]."""
-    if _is_cuda(bin_mu):
-        import torch
-        dev = bin_mu.device
-        bin_mu, bin_flag = _t(bin_mu, torch.float64, dev), _t(bin_flag, torch.uint8, dev)
-        N, C = bin_mu.shape
-        if out is None:
-            out = torch.empty(C, dtype=torch.float64, device=dev)
-        ws, wsb = _workspace("suffstats", N, C, dev)
-        with torch.cuda.device(dev):
-            _lib.call("dig_scale_suffstats", _lib.dev_ptr(bin_mu), _lib.dev_ptr(bin_flag), N, C, _lib.dev_ptr(out),
-                      _lib.dev_ptr(ws), wsb, _lib.stream_ptr())
-        return out
-    bin_mu = _lib.as_host(bin_mu, np.float64)
-    if bin_mu.ndim == 1:
-        bin_mu = bin_mu[:, None]
+    be = backend_of(bin_mu, device=device)
+    bin_mu = _cols(be.arr(bin_mu, "f64"))
     N, C = bin_mu.shape
-    bin_flag = _lib.as_host(bin_flag, np.uint8).reshape(N, C)
-    res = np.empty(C)
-    _lib.call("dig_scale_suffstats_host", _lib.host_ptr(bin_mu), _lib.host_ptr(bin_flag), N, C, _lib.host_ptr(res), device)
-    return res
+    bin_flag = be.arr(bin_flag, "u8", (N, C))
+    if out is None:
+        out = be.empty(C, "f64")
+    be.call("dig_scale_suffstats", be.ptr(bin_mu), be.ptr(bin_flag), N, C, be.ptr(out), workspace=_shared_workspace(be, "suffstats", N, C))
+    return out
 
 
 def scale_factors_local(bin_mu, bin_flag, n_snv_obs, n_ind_obs, out=None):
@@ -229,9 +170,9 @@ def scale_factors_local(bin_mu, bin_flag, n_snv_obs, n_ind_obs, out=None):
     kernels (dig_scale_factors_local).  Returns (cj, cj_indel, exp_sum) device tensors."""
     import torch
     dev = bin_mu.device
-    bin_mu, bin_flag = _t(bin_mu, torch.float64, dev), _t(bin_flag, torch.uint8, dev)
+    bin_mu, bin_flag = _t(bin_mu, "f64", dev), _t(bin_flag, "u8", dev)
     N, C = bin_mu.shape
-    n_snv_obs, n_ind_obs = _t(n_snv_obs, torch.float64, dev), _t(n_ind_obs, torch.float64, dev)
+    n_snv_obs, n_ind_obs = _t(n_snv_obs, "f64", dev), _t(n_ind_obs, "f64", dev)
     if out is None:
         out = tuple(torch.empty(C, dtype=torch.float64, device=dev) for _ in range(3))
     ws, wsb = _workspace("suffstats", N, C, dev)
@@ -247,7 +188,7 @@ def scale_factors_from_parts(parts, out=None):
     (rank-ordered sums + division in one kernel; transfer_tools.py:153-154)."""
     import torch
     dev = parts.device
-    parts = _t(parts, torch.float64, dev)
+    parts = _t(parts, "f64", dev)
     world, three, C = parts.shape
     assert three == 3
     if out is None:
@@ -278,14 +219,38 @@ def ideal_overlaps(elt_chrom, blk_ptr, blk_start, blk_end, window, bin_chrom, bi
     return ov_ptr, ov_idx[:int(ov_ptr[E])]
 
 
+_ACC_OUTPUTS = ("MU", "SIGMA", "R_OBS", "FLAG", "P", "R_SIZE", "ELT_SIZE", "P_INDEL")       # in the library's argument order
+
+
+def _accumulate_outputs(be, E, C, n_class):
+    return dict(MU=be.empty((E, C), "f64"), SIGMA=be.empty((E, C), "f64"), R_OBS=be.empty((E, C), "i32"),
+                FLAG=be.empty((E, C), "i32"), P=be.empty((E, n_class, C), "f64"), R_SIZE=be.empty(E, "i32"),
+                ELT_SIZE=be.empty(E, "i32"), P_INDEL=be.empty(E, "f64"))
+
+
 def alloc_accumulate_outputs(E, C, n_class, dev):
     """Output tensors of accumulate_elements (reusable across calls through `out=`)."""
-    import torch
-    f64, i32 = torch.float64, torch.int32
-    return dict(MU=torch.empty((E, C), dtype=f64, device=dev), SIGMA=torch.empty((E, C), dtype=f64, device=dev),
-                R_OBS=torch.empty((E, C), dtype=i32, device=dev), FLAG=torch.empty((E, C), dtype=i32, device=dev),
-                P=torch.empty((E, n_class, C), dtype=f64, device=dev), R_SIZE=torch.empty(E, dtype=i32, device=dev),
-                ELT_SIZE=torch.empty(E, dtype=i32, device=dev), P_INDEL=torch.empty(E, dtype=f64, device=dev))
+    return _accumulate_outputs(device_backend(dev), E, C, n_class)
+
+
+def _bin_tables(be, bin_mu, bin_std, bin_y, bin_flag, bin_ctx, ov_ptr, ov_idx, L, strand_minus, gene_length, d_pr):
+    """The bin tables, the overlap CSR and the element table every accumulation takes, normalised: bin_mu, bin_std f64 [N, C];
+    bin_y i32 [N, C]; bin_flag u8 [N, C]; bin_ctx i32 [N, 64]; ov_ptr i64 [E + 1]; ov_idx i32; L i32 [E, n_class, 192] (an
+    [E, 192] table is one class); strand_minus u8 [E]; gene_length i32 [E] or None; d_pr f64 [C, 192].
+    Returns (the eleven arrays in that order, (N, E, C, n_class))."""
+    bin_mu = _cols(be.arr(bin_mu, "f64"))
+    N, C = bin_mu.shape
+    L = be.arr(L, "i32")
+    if L.ndim == 2:
+        L = L[:, None, :]
+    E, n_class, K = L.shape
+    ov_ptr, ov_idx = be.arr(ov_ptr, "i64"), be.arr(ov_idx, "i32")
+    assert K == 192 and ov_ptr.shape[0] == E + 1
+    if not be.is_device and ov_idx.shape[0] == 0:               # (the staging helper of the host twins copies at least one entry)
+        ov_idx = be.arr([0], "i32")
+    return [bin_mu, be.arr(bin_std, "f64", (N, C)), be.arr(bin_y, "i32", (N, C)), be.arr(bin_flag, "u8", (N, C)),
+            be.arr(bin_ctx, "i32", (N, 64)), ov_ptr, ov_idx, L, be.arr(strand_minus, "u8"), be.arr(gene_length, "i32"),
+            be.arr(d_pr, "f64", (C, 192))], (N, E, C, n_class)
 
 
 def accumulate_elements(bin_mu, bin_std, bin_y, bin_flag, bin_ctx, ov_ptr, ov_idx, L, strand_minus, d_pr,
@@ -294,69 +259,17 @@ def accumulate_elements(bin_mu, bin_std, bin_y, bin_flag, bin_ctx, ov_ptr, ov_id
 
     Returns dict(MU, SIGMA [E,C] f64; R_OBS, FLAG [E,C] i32; P [E,n_class,C] f64;
                  R_SIZE, ELT_SIZE [E] i32; P_INDEL [E] f64)."""
-    if _is_cuda(bin_mu):
-        import torch
-        dev = bin_mu.device
-        f64, i32, i64, u8 = torch.float64, torch.int32, torch.int64, torch.uint8
-        bin_mu, bin_std = _t(bin_mu, f64, dev), _t(bin_std, f64, dev)
-        N, C = bin_mu.shape
-        bin_y, bin_flag, bin_ctx = _t(bin_y, i32, dev), _t(bin_flag, u8, dev), _t(bin_ctx, i32, dev)
-        ov_ptr, ov_idx = _t(ov_ptr, i64, dev), _t(ov_idx, i32, dev)
-        L = _t(L, i32, dev)
-        if L.dim() == 2:
-            L = L[:, None, :]
-        E, n_class, K = L.shape
-        assert K == 192 and bin_ctx.shape == (N, 64) and ov_ptr.numel() == E + 1
-        strand_minus = _t(strand_minus, u8, dev)
-        gene_length = _t(gene_length, i32, dev)
-        d_pr = _t(d_pr, f64, dev)
-        assert d_pr.shape == (C, 192)
-        o = out if out is not None else alloc_accumulate_outputs(E, C, n_class, dev)
-        ws, wsb = _workspace("accumulate", E, C, dev) if use_workspace else (None, 0)
-        with torch.cuda.device(dev):
-            _lib.call("dig_accumulate_elements", _lib.dev_ptr(bin_mu), _lib.dev_ptr(bin_std), _lib.dev_ptr(bin_y),
-                      _lib.dev_ptr(bin_flag), _lib.dev_ptr(bin_ctx), _lib.dev_ptr(ov_ptr), _lib.dev_ptr(ov_idx),
-                      _lib.dev_ptr(L), n_class, _lib.dev_ptr(strand_minus), _lib.dev_ptr(gene_length), _lib.dev_ptr(d_pr),
-                      _lib.dev_ptr(o["MU"]), _lib.dev_ptr(o["SIGMA"]), _lib.dev_ptr(o["R_OBS"]), _lib.dev_ptr(o["FLAG"]),
-                      _lib.dev_ptr(o["P"]), _lib.dev_ptr(o["R_SIZE"]), _lib.dev_ptr(o["ELT_SIZE"]),
-                      _lib.dev_ptr(o["P_INDEL"]), N, E, C, _lib.dev_ptr(ws), wsb, _lib.stream_ptr())
-        return o
-    bin_mu = _lib.as_host(bin_mu, np.float64)
-    if bin_mu.ndim == 1:
-        bin_mu = bin_mu[:, None]
-    N, C = bin_mu.shape
-    bin_std = _lib.as_host(bin_std, np.float64).reshape(N, C)
-    bin_y = _lib.as_host(bin_y, np.int32).reshape(N, C)
-    bin_flag = _lib.as_host(bin_flag, np.uint8).reshape(N, C)
-    bin_ctx = _lib.as_host(bin_ctx, np.int32).reshape(N, 64)
-    ov_ptr, ov_idx = _lib.as_host(ov_ptr, np.int64), _lib.as_host(ov_idx, np.int32)
-    L = _lib.as_host(L, np.int32)
-    if L.ndim == 2:
-        L = L[:, None, :]
-    L = np.ascontiguousarray(L)
-    E, n_class, K = L.shape
-    assert K == 192 and len(ov_ptr) == E + 1
-    strand_minus = _lib.as_host(strand_minus, np.uint8)
-    gl = None if gene_length is None else _lib.as_host(gene_length, np.int32)
-    d_pr = _lib.as_host(d_pr, np.float64).reshape(C, 192)
-    o = dict(MU=np.empty((E, C)), SIGMA=np.empty((E, C)), R_OBS=np.empty((E, C), np.int32),
-             FLAG=np.empty((E, C), np.int32), P=np.empty((E, n_class, C)), R_SIZE=np.empty(E, np.int32),
-             ELT_SIZE=np.empty(E, np.int32), P_INDEL=np.empty(E))
-    if len(ov_idx) == 0:
-        ov_idx = np.zeros(1, np.int32)
-    _lib.call("dig_accumulate_elements_host", _lib.host_ptr(bin_mu), _lib.host_ptr(bin_std), _lib.host_ptr(bin_y),
-              _lib.host_ptr(bin_flag), _lib.host_ptr(bin_ctx), _lib.host_ptr(ov_ptr), _lib.host_ptr(ov_idx),
-              _lib.host_ptr(L), n_class, _lib.host_ptr(strand_minus), _lib.host_ptr(gl), _lib.host_ptr(d_pr),
-              _lib.host_ptr(o["MU"]), _lib.host_ptr(o["SIGMA"]), _lib.host_ptr(o["R_OBS"]), _lib.host_ptr(o["FLAG"]),
-              _lib.host_ptr(o["P"]), _lib.host_ptr(o["R_SIZE"]), _lib.host_ptr(o["ELT_SIZE"]), _lib.host_ptr(o["P_INDEL"]),
-              N, E, C, device)
+    be = backend_of(bin_mu, device=device)
+    tabs, (N, E, C, n_class) = _bin_tables(be, bin_mu, bin_std, bin_y, bin_flag, bin_ctx, ov_ptr, ov_idx, L, strand_minus,
+                                           gene_length, d_pr)
+    o = out if out is not None else _accumulate_outputs(be, E, C, n_class)
+    p = [be.ptr(x) for x in tabs]
+    be.call("dig_accumulate_elements", *p[:8], n_class, *p[8:], *[be.ptr(o[k]) for k in _ACC_OUTPUTS], N, E, C,
+            workspace=_shared_workspace(be, "accumulate", E, C, use_workspace))
     return o
 
 
 # ---------------------------------------------------------------------------
-_NP_DT = {np.dtype(np.float32): _lib.DIG_F32, np.dtype(np.float64): _lib.DIG_F64, np.dtype(np.int16): _lib.DIG_I16}
-
-
 def element_pipeline(bin_mu, bin_std, bin_y, bin_flag, bin_ctx, ov_ptr, ov_idx, L, strand_minus, d_pr, obs_snv,
                      obs_samples, obs_indel, cj, cj_indel, gene_length=None, out_acc=None, out_stats=None, stages=7, compact=False):
     """accumulate_elements (n_class = 1) + element_stats as one operation on device tensors (dig_element_pipeline):
@@ -364,38 +277,26 @@ def element_pipeline(bin_mu, bin_std, bin_y, bin_flag, bin_ctx, ov_ptr, ov_idx, 
     stages: bit mask 1 = context kernel, 2 = dot kernel, 4 = statistics (7 = all); separate calls must keep that order.
     compact="auto": check L for the three-fold context repetition first (one more pass over L and a stream synchronisation,
     see PipelinePlan) and run the 64-context form when it holds; a loop over the same element set should keep a PipelinePlan."""
-    import torch
     if compact:
         plan = PipelinePlan(bin_mu, bin_std, bin_y, bin_flag, bin_ctx, ov_ptr, ov_idx, L, strand_minus, d_pr, obs_snv, obs_samples,
                             obs_indel, out_acc=out_acc, out_stats=out_stats, gene_length=gene_length, compact=compact,
                             pack_bins=False)               # (one call: packing the tables would cost more than it saves)
-        return plan.run(_t(cj, torch.float64, plan.dev), _t(cj_indel, torch.float64, plan.dev), stages=stages)
-    dev = bin_mu.device
-    f64, i32, i64, u8 = torch.float64, torch.int32, torch.int64, torch.uint8
-    bin_mu, bin_std = _t(bin_mu, f64, dev), _t(bin_std, f64, dev)
-    N, C = bin_mu.shape
-    bin_y, bin_flag, bin_ctx = _t(bin_y, i32, dev), _t(bin_flag, u8, dev), _t(bin_ctx, i32, dev)
-    ov_ptr, ov_idx = _t(ov_ptr, i64, dev), _t(ov_idx, i32, dev)
-    L = _t(L, i32, dev)
-    if L.dim() == 2:
-        L = L[:, None, :]
-    E, n_class, K = L.shape
-    assert n_class == 1 and K == 192 and bin_ctx.shape == (N, 64) and ov_ptr.numel() == E + 1
-    strand_minus, gene_length, d_pr = _t(strand_minus, u8, dev), _t(gene_length, i32, dev), _t(d_pr, f64, dev)
-    obs = [_t(x, i32, dev) for x in (obs_snv, obs_samples, obs_indel)]
+        return plan.run(_t(cj, "f64", plan.dev), _t(cj_indel, "f64", plan.dev), stages=stages)
+    be = device_backend(bin_mu.device)
+    tabs, (N, E, C, n_class) = _bin_tables(be, bin_mu, bin_std, bin_y, bin_flag, bin_ctx, ov_ptr, ov_idx, L, strand_minus,
+                                           gene_length, d_pr)
+    assert n_class == 1
+    obs = [be.arr(x, "i32") for x in (obs_snv, obs_samples, obs_indel)]
     assert all(x.shape == (E, C) for x in obs)
-    cj, cj_indel = _t(cj, f64, dev), _t(cj_indel, f64, dev)
-    o = out_acc if out_acc is not None else alloc_accumulate_outputs(E, C, 1, dev)
-    st = out_stats if out_stats is not None else torch.empty((len(ES_PLANES), E, C), dtype=f64, device=dev)
-    ws, wsb = _workspace("pipeline", E, C, dev)
-    if ws is None:
+    cj, cj_indel = be.arr(cj, "f64"), be.arr(cj_indel, "f64")
+    o = out_acc if out_acc is not None else _accumulate_outputs(be, E, C, 1)
+    st = out_stats if out_stats is not None else be.empty((len(ES_PLANES), E, C), "f64")
+    ws = _shared_workspace(be, "pipeline", E, C)
+    if ws[0] is None:
         raise _lib.DigHipError("dig_element_pipeline: problem too large for the fused path (E * C >= 2^32 - 1)")
-    p = _lib.dev_ptr
-    with torch.cuda.device(dev):
-        _lib.call("dig_element_pipeline", p(bin_mu), p(bin_std), p(bin_y), p(bin_flag), p(bin_ctx), p(ov_ptr), p(ov_idx),
-                  p(L), p(strand_minus), p(gene_length), p(d_pr), p(obs[0]), p(obs[1]), p(obs[2]), p(cj), p(cj_indel),
-                  p(o["MU"]), p(o["SIGMA"]), p(o["R_OBS"]), p(o["FLAG"]), p(o["P"]), p(o["R_SIZE"]), p(o["ELT_SIZE"]),
-                  p(o["P_INDEL"]), p(st), N, E, C, None, int(stages), p(ws), wsb, _lib.stream_ptr())
+    p = be.ptr
+    be.call("dig_element_pipeline", *[p(x) for x in tabs], *[p(x) for x in obs], p(cj), p(cj_indel), *[p(o[k]) for k in _ACC_OUTPUTS],
+            p(st), N, E, C, None, int(stages), workspace=ws)
     return o, st
 
 
@@ -457,21 +358,16 @@ class PipelinePlan:
         import ctypes
         import torch
         dev = bin_mu.device
-        f64, i32, i64, u8 = torch.float64, torch.int32, torch.int64, torch.uint8
-        L = _t(L, i32, dev)
-        if L.dim() == 2:
-            L = L[:, None, :]
-        self.keep = [_t(bin_mu, f64, dev), _t(bin_std, f64, dev), _t(bin_y, i32, dev), _t(bin_flag, u8, dev),
-                     _t(bin_ctx, i32, dev), _t(ov_ptr, i64, dev), _t(ov_idx, i32, dev), L, _t(strand_minus, u8, dev),
-                     _t(gene_length, i32, dev), _t(d_pr, f64, dev), _t(obs_snv, i32, dev), _t(obs_samples, i32, dev),
-                     _t(obs_indel, i32, dev)]
-        self.N, self.C = self.keep[0].shape
-        self.E, n_class, K = L.shape
-        assert n_class == 1 and K == 192 and self.keep[4].shape == (self.N, 64) and self.keep[5].numel() == self.E + 1
+        be = device_backend(dev)
+        tabs, (self.N, self.E, self.C, n_class) = _bin_tables(be, bin_mu, bin_std, bin_y, bin_flag, bin_ctx, ov_ptr, ov_idx, L,
+                                                              strand_minus, gene_length, d_pr)
+        assert n_class == 1
+        L = tabs[7]
+        self.keep = tabs + [be.arr(x, "i32") for x in (obs_snv, obs_samples, obs_indel)]
         assert all(x.shape == (self.E, self.C) for x in self.keep[11:14])
         self.dev = dev
-        self.acc = out_acc if out_acc is not None else alloc_accumulate_outputs(self.E, self.C, 1, dev)
-        self.stats = out_stats if out_stats is not None else torch.empty((len(ES_PLANES), self.E, self.C), dtype=f64, device=dev)
+        self.acc = out_acc if out_acc is not None else _accumulate_outputs(be, self.E, self.C, 1)
+        self.stats = out_stats if out_stats is not None else be.empty((len(ES_PLANES), self.E, self.C), "f64")
         if workspace is not None:
             # A caller-owned buffer (uint8, at least dig_element_pipeline_workspace bytes).  NOT plain scratch: a compact plan
             # keeps its [E, 64] copy of L and the repetition flag in it from construction on (dig_element_pipeline_prepare), so
@@ -506,7 +402,7 @@ class PipelinePlan:
             if self.records is None:
                 raise ValueError("records_out needs the packed bin records (pack_bins)")
             nrec = (self.E * self.C + 63) // 64 * 64
-            self.out_records = torch.empty((nrec // 64, _lib.DIG_REC_DOUBLES // 2, 64, 2), dtype=f64, device=dev)
+            self.out_records = torch.empty((nrec // 64, _lib.DIG_REC_DOUBLES // 2, 64, 2), dtype=torch.float64, device=dev)
             assert self.out_records.data_ptr() % 256 == 0
         self._tail = [p(o["MU"]), p(o["SIGMA"]), p(o["R_OBS"]), p(o["FLAG"]), p(o["P"]), p(o["R_SIZE"]), p(o["ELT_SIZE"]),
                       p(o["P_INDEL"]), p(self.out_records if self.records_out else self.stats), self.N, self.E, self.C,
@@ -559,8 +455,7 @@ class PipelinePlan:
         """Enqueue the pipeline (or one of its stages) on `stream` (default: torch's current stream)."""
         rc = self._fn(*self._head, _lib.dev_ptr(cj), _lib.dev_ptr(cj_indel), *self._tail, int(stages) | self._flags, self._ws,
                       self.wsb, _lib.stream_ptr(stream))
-        if rc != 0:
-            raise _lib.DigHipError("dig_element_pipeline failed (%d): %s" % (rc, _lib.last_error()))
+        _lib.check("dig_element_pipeline", rc)
         return self.acc, self.stats
 
 
@@ -597,8 +492,8 @@ class ScaleFactorPlan:
     def __init__(self, bin_mu, bin_flag, n_snv_obs, n_ind_obs):
         import torch
         dev = bin_mu.device
-        self.keep = [_t(bin_mu, torch.float64, dev), _t(bin_flag, torch.uint8, dev), _t(n_snv_obs, torch.float64, dev),
-                     _t(n_ind_obs, torch.float64, dev)]
+        self.keep = [_t(bin_mu, "f64", dev), _t(bin_flag, "u8", dev), _t(n_snv_obs, "f64", dev),
+                     _t(n_ind_obs, "f64", dev)]
         self.N, self.C = self.keep[0].shape
         self.ws, self.wsb = _workspace("suffstats", self.N, self.C, dev, private=True)
         p = _lib.dev_ptr
@@ -609,8 +504,7 @@ class ScaleFactorPlan:
     def run(self, out_sum, cj, cj_indel, stream=None):
         rc = self._fn(*self._args, _lib.dev_ptr(out_sum), _lib.dev_ptr(cj), _lib.dev_ptr(cj_indel), self._ws, self.wsb,
                       _lib.stream_ptr(stream))
-        if rc != 0:
-            raise _lib.DigHipError("dig_scale_factors_local failed (%d): %s" % (rc, _lib.last_error()))
+        _lib.check("dig_scale_factors_local", rc)
 
     def run_sharded(self, part, cj, cj_indel, group=None):
         """Bins sharded over ranks: this shard's sums into part[0] (dig_scale_suffstats), all-gather of the [3, C]
@@ -621,8 +515,7 @@ class ScaleFactorPlan:
         lib = _lib.load()
         sp = _lib.stream_ptr()
         rc = lib.dig_scale_suffstats(self._args[0], self._args[1], self.N, self.C, _lib.dev_ptr(part[0]), self._ws, self.wsb, sp)
-        if rc != 0:
-            raise _lib.DigHipError("dig_scale_suffstats failed (%d): %s" % (rc, _lib.last_error()))
+        _lib.check("dig_scale_suffstats", rc)
         from . import parallel
         world = dist.get_world_size(group) if dist.is_available() and dist.is_initialized() else 1
         parts = part
@@ -632,40 +525,30 @@ class ScaleFactorPlan:
             dist.all_gather_into_tensor(self._parts, part, group=group)
             parts = self._parts
         rc = lib.dig_scale_factors(_lib.dev_ptr(parts), world, self.C, _lib.dev_ptr(cj), _lib.dev_ptr(cj_indel), sp)
-        if rc != 0:
-            raise _lib.DigHipError("dig_scale_factors failed (%d): %s" % (rc, _lib.last_error()))
+        _lib.check("dig_scale_factors", rc)
+
+
+_DIG_SRC = {"float32": _lib.DIG_F32, "float64": _lib.DIG_F64, "int16": _lib.DIG_I16}         # by numpy's and torch's dtype name
+_DIG_DST = {"f32": _lib.DIG_F32, "bf16": _lib.DIG_BF16}
 
 
 def gather_bins(x_data, bin_rows, tracks=None, out_dtype="f32", transpose=False, device=0):
     """x_data[bin_rows, :, tracks] as float32 (or bf16) -- mut_dataset.py:76-81 for a batch.
     transpose=True returns channels-first [B, T_sel, L] (cnn_predictors.py:131)."""
-    if _is_cuda(x_data):
-        import torch
-        dev = x_data.device
-        tmap = {torch.float32: _lib.DIG_F32, torch.float64: _lib.DIG_F64, torch.int16: _lib.DIG_I16}
-        assert x_data.dtype in tmap and x_data.is_contiguous() and x_data.dim() == 3
-        N, L, T = x_data.shape
-        rows = _t(bin_rows, torch.int64, dev)
-        tr = None if tracks is None else _t(tracks, torch.int32, dev)      # NULL = all tracks (contiguous block copy)
-        B, Ts = rows.numel(), T if tr is None else tr.numel()
-        odt = torch.float32 if out_dtype == "f32" else torch.bfloat16
-        out = torch.empty((B, Ts, L) if transpose else (B, L, Ts), dtype=odt, device=dev)
-        with torch.cuda.device(dev):
-            _lib.call("dig_gather_bins", _lib.dev_ptr(x_data), tmap[x_data.dtype], N, L, T, _lib.dev_ptr(rows), B,
-                      _lib.dev_ptr(tr), Ts, _lib.dev_ptr(out), _lib.DIG_F32 if out_dtype == "f32" else _lib.DIG_BF16,
-                      int(transpose), _lib.stream_ptr())
-        return out
-    x = np.ascontiguousarray(x_data)
-    assert x.dtype in _NP_DT and x.ndim == 3
+    be = backend_of(x_data, device=device)
+    x = be.arr(x_data)
+    src = str(x.dtype).rpartition(".")[2]                                 # "float32" of numpy's float32 and of torch.float32
+    assert src in _DIG_SRC and x.ndim == 3
     N, L, T = x.shape
-    rows = _lib.as_host(bin_rows, np.int64).ravel()
-    tr = None if tracks is None else _lib.as_host(tracks, np.int32).ravel()
-    B, Ts = len(rows), T if tr is None else len(tr)
-    if out_dtype != "f32":
+    rows = be.arr(bin_rows, "i64", (-1,))
+    tr = be.arr(tracks, "i32", (-1,))                                     # NULL = all tracks (contiguous block copy)
+    B, Ts = rows.shape[0], T if tr is None else tr.shape[0]
+    if out_dtype != "f32" and not be.is_device:
         raise ValueError("host path returns float32 only")
-    out = np.empty((B, Ts, L) if transpose else (B, L, Ts), np.float32)
-    _lib.call("dig_gather_bins_host", _lib.host_ptr(x), _NP_DT[x.dtype], N, L, T, _lib.host_ptr(rows), B,
-              _lib.host_ptr(tr), Ts, _lib.host_ptr(out), _lib.DIG_F32, int(transpose), device)
+    dst = "f32" if out_dtype == "f32" else "bf16"
+    out = be.empty((B, Ts, L) if transpose else (B, L, Ts), dst)
+    be.call("dig_gather_bins", be.ptr(x), _DIG_SRC[src], N, L, T, be.ptr(rows), B, be.ptr(tr), Ts, be.ptr(out), _DIG_DST[dst],
+            int(transpose))
     return out
 
 
@@ -695,32 +578,16 @@ def count_contexts(genome, chroms, starts, ends, minus=None, device=0, on_device
             bad = int(np.flatnonzero((st > 0) & (st < n_up))[0])
             raise ValueError("START %d of region %d: the reference fetches from START - %d, before the chromosome start"
                              % (st[bad], bad, n_up))
-    K = 1024 if penta else 64
-    if on_device:
-        import torch
-        dev = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
-        t = lambda a: torch.as_tensor(a, device=dev)
-        out = torch.empty((R, K), dtype=torch.int32, device=dev)
-        rc, rs, re_, rm = t(ci), t(st), t(en), t(mi)
-        p = _lib.dev_ptr
-        with torch.cuda.device(dev):
-            if form == "2bit":
-                _lib.call("dig_count_contexts5" if penta else "dig_count_contexts2", *genome.genome2_args(dev), p(rc), p(rs),
-                          p(re_), p(rm), R, p(out), _lib.stream_ptr())
-            else:
-                words, off, ln = genome.on_device(dev)
-                _lib.call("dig_count_contexts", p(words), words.numel(), p(off), p(ln), len(genome.names), p(rc), p(rs), p(re_),
-                          p(rm), R, p(out), _lib.stream_ptr())
-        return out
-    out = np.empty((R, K), np.int32)
-    h = _lib.host_ptr
-    dv = device if isinstance(device, int) else 0
+    be = backend_on(device, on_device)
+    p = be.ptr
+    out = be.empty((R, 1024 if penta else 64), "i32")
+    regions = [be.arr(a) for a in (ci, st, en, mi)]
     if form == "2bit":
-        _lib.call("dig_count_contexts5_host" if penta else "dig_count_contexts2_host", *genome.genome2_args(), h(ci), h(st), h(en),
-                  h(mi), R, h(out), dv)
+        name, head = "dig_count_contexts5" if penta else "dig_count_contexts2", genome.genome2_args(be.dev)
     else:
-        _lib.call("dig_count_contexts_host", h(genome.words), genome.words.size, h(genome.offsets), h(genome.lengths),
-                  len(genome.names), h(ci), h(st), h(en), h(mi), R, h(out), dv)
+        words, off, ln = genome.on_device(be.dev) if be.is_device else (genome.words, genome.offsets, genome.lengths)
+        name, head = "dig_count_contexts", [p(words), words.shape[0], p(off), p(ln), len(genome.names)]
+    be.call(name, *head, *[p(a) for a in regions], R, p(out))
     return out
 
 
@@ -759,23 +626,13 @@ def mutation_contexts(genome, chroms, starts, refs, n_up=2, n_down=2, collapse=F
     if R and ((st < 0).any() or (st >= genome.lengths[ci]).any()):
         bad = int(np.flatnonzero((st < 0) | (st >= genome.lengths[ci]))[0])
         raise ValueError("START %d is outside chromosome %s (length %d)" % (st[bad], genome.names[ci[bad]], genome.lengths[ci[bad]]))
-    if on_device:
-        import torch
-        dev = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
-        status = torch.empty(R, dtype=torch.uint8, device=dev)
-        context = torch.empty(R, dtype=torch.int32, device=dev)
-        ws = torch.empty(max(_lib.load().dig_mutation_contexts_workspace(R), 1), dtype=torch.uint8, device=dev)
-        t = lambda a: torch.as_tensor(a, device=dev)
-        p = _lib.dev_ptr
-        with torch.cuda.device(dev):
-            rci, rst, rrf = t(ci), t(st), t(rc)
-            _lib.call("dig_mutation_contexts", *genome.genome2_args(dev), p(rci), p(rst), p(rrf), R, n_up, n_down,
-                      int(bool(collapse)), p(status), p(context), p(ws), ws.numel(), _lib.stream_ptr())
-        return status, context
-    status, context = np.empty(R, np.uint8), np.empty(R, np.uint32)
-    h = _lib.host_ptr
-    _lib.call("dig_mutation_contexts_host", *genome.genome2_args(), h(ci), h(st), h(rc), R, n_up, n_down, int(bool(collapse)),
-              h(status), h(context), device if isinstance(device, int) else 0)
+    be = backend_on(device, on_device)
+    p = be.ptr
+    status, context = be.empty(R, "u8"), be.empty(R, "i32" if be.is_device else "u32")
+    n_ws = max(int(_lib.load().dig_mutation_contexts_workspace(R)), 1) if be.is_device else 0
+    rows = [be.arr(a) for a in (ci, st, rc)]
+    be.call("dig_mutation_contexts", *genome.genome2_args(be.dev), *[p(a) for a in rows], R, n_up, n_down, int(bool(collapse)),
+            p(status), p(context), workspace=(be.empty(n_ws, "u8") if be.is_device else None, n_ws))
     return status, context
 
 
@@ -784,14 +641,10 @@ MF_SYN, MF_MIS, MF_NONS, MF_STOP_LOSS, MF_SPLICE, MF_NONE = 0, 1, 2, 3, 4, 255
 MF_OK, MF_WRONG_REF, MF_HOST, MF_OUTSIDE = 0, 1, 2, 3
 
 
-def mutation_function(genome, genes, gene_chrom, pair_gene, pair_start, pair_end, pair_kind, pair_ref, pair_alt, device=0,
-                      on_device=True):
-    """Genic function of (mutation, gene) pairs (scripts/mutationFunction.R; dig_mutation_function) over a PackedGenome.
-    genes: a gene_annotation.GeneSet; gene_chrom: the genome's chromosome index of every gene (GeneSet.on_genome).  Pairs: gene
-    index, 1-based closed start / end, kind (MF_KIND_*), REF / ALT codes 0-3 on the + strand (SNVs; ignored otherwise).
-    Returns (impact u8, status u8, n_cds i32, cds_min i32, cds_max i32): MF_SYN ... MF_SPLICE / MF_NONE and MF_OK / MF_WRONG_REF /
-    MF_HOST / MF_OUTSIDE as include/dig_hip.h describes them.  on_device=True takes numpy arrays or tensors, keeps the genome
-    resident in HBM and returns device tensors; False goes through the host twin on numpy arrays."""
+def gene_table(be, genome, genes, gene_chrom):
+    """The gene-table arguments of dig_mutation_function / dig_gene_site_counts on backend `be`: checks the GeneSet against the
+    genome (ValueError) and returns (the eight arrays gene_chrom i32, minus u8, blk_ptr, blk_start, blk_end, cds_off, spl_ptr,
+    spl_pos i64 in the library's order, gene_chrom as a host array)."""
     G = len(genes)
     gch = _lib.as_host(gene_chrom, np.int32).ravel()
     assert len(gch) == G
@@ -803,34 +656,32 @@ def mutation_function(genome, genes, gene_chrom, pair_gene, pair_start, pair_end
     if G and (genes.cds_len % 3).any():
         raise ValueError("a gene's CDS length is not a multiple of 3")
     table = (gch, genes.minus, genes.blk_ptr, genes.blk_start, genes.blk_end, genes.cds_off, genes.spl_ptr, genes.spl_pos)
-    dtypes = (np.int32, np.int64, np.int64, np.uint8, np.uint8, np.uint8)
-    if on_device:
-        import torch
-        dev = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
-        tdt = (torch.int32, torch.int64, torch.int64, torch.uint8, torch.uint8, torch.uint8)
-        pairs = [torch.as_tensor(a, dtype=d, device=dev).contiguous().ravel()
-                 for a, d in zip((pair_gene, pair_start, pair_end, pair_kind, pair_ref, pair_alt), tdt)]
-        n = pairs[0].numel()
-        assert all(a.numel() == n for a in pairs)
-        if n and (int(pairs[0].min()) < 0 or int(pairs[0].max()) >= G):
-            raise ValueError("pair gene index outside the gene table")
-        impact, status = (torch.empty(n, dtype=torch.uint8, device=dev) for _ in range(2))
-        n_cds, cds_min, cds_max = (torch.empty(n, dtype=torch.int32, device=dev) for _ in range(3))
-        p = _lib.dev_ptr
-        with torch.cuda.device(dev):
-            tab = [torch.as_tensor(a, device=dev) for a in table]
-            _lib.call("dig_mutation_function", *genome.genome2_args(dev), *[p(a) for a in tab], G, *[p(a) for a in pairs], n,
-                      p(impact), p(status), p(n_cds), p(cds_min), p(cds_max), _lib.stream_ptr())
-        return impact, status, n_cds, cds_min, cds_max
-    pairs = [_lib.as_host(a, d).ravel() for a, d in zip((pair_gene, pair_start, pair_end, pair_kind, pair_ref, pair_alt), dtypes)]
-    n = len(pairs[0])
-    assert all(len(a) == n for a in pairs)
-    impact, status = np.empty(n, np.uint8), np.empty(n, np.uint8)
-    n_cds, cds_min, cds_max = np.empty(n, np.int32), np.empty(n, np.int32), np.empty(n, np.int32)
-    h = _lib.host_ptr
-    _lib.call("dig_mutation_function_host", *genome.genome2_args(), *[h(a) for a in table], G, *[h(a) for a in pairs], n,
-              h(impact), h(status), h(n_cds), h(cds_min), h(cds_max), device if isinstance(device, int) else 0)
-    return impact, status, n_cds, cds_min, cds_max
+    return [be.arr(a, dt) for a, dt in zip(table, ("i32", "u8", "i64", "i64", "i64", "i64", "i64", "i64"))], gch
+
+
+def mutation_function(genome, genes, gene_chrom, pair_gene, pair_start, pair_end, pair_kind, pair_ref, pair_alt, device=0,
+                      on_device=True):
+    """Genic function of (mutation, gene) pairs (scripts/mutationFunction.R; dig_mutation_function) over a PackedGenome.
+    genes: a gene_annotation.GeneSet; gene_chrom: the genome's chromosome index of every gene (GeneSet.on_genome).  Pairs: gene
+    index, 1-based closed start / end, kind (MF_KIND_*), REF / ALT codes 0-3 on the + strand (SNVs; ignored otherwise).
+    Returns (impact u8, status u8, n_cds i32, cds_min i32, cds_max i32): MF_SYN ... MF_SPLICE / MF_NONE and MF_OK / MF_WRONG_REF /
+    MF_HOST / MF_OUTSIDE as include/dig_hip.h describes them.  on_device=True takes numpy arrays or tensors, keeps the genome
+    resident in HBM and returns device tensors; False goes through the host twin on numpy arrays."""
+    be = backend_on(device, on_device)
+    G = len(genes)
+    tab, _ = gene_table(be, genome, genes, gene_chrom)
+    pairs = [be.arr(a, dt, (-1,)) for a, dt in zip((pair_gene, pair_start, pair_end, pair_kind, pair_ref, pair_alt),
+                                                   ("i32", "i64", "i64", "u8", "u8", "u8"))]
+    n = pairs[0].shape[0]
+    assert all(a.shape[0] == n for a in pairs)
+    # (device tensors are checked here; the host twin checks its own arrays inside the library)
+    if be.is_device and n and (int(pairs[0].min()) < 0 or int(pairs[0].max()) >= G):
+        raise ValueError("pair gene index outside the gene table")
+    outs = [be.empty(n, dt) for dt in ("u8", "u8", "i32", "i32", "i32")]           # impact, status, n_cds, cds_min, cds_max
+    p = be.ptr
+    be.call("dig_mutation_function", *genome.genome2_args(be.dev), *[p(a) for a in tab], G, *[p(a) for a in pairs], n,
+            *[p(a) for a in outs])
+    return tuple(outs)
 
 
 GS_OK, GS_HOST = 0, 1                                            # include/dig_hip.h DIG_GS_*
@@ -900,34 +751,13 @@ def gene_site_counts(genome, genes, gene_chrom, device=0, on_device=True, return
     other than ACGT in their CDS, splice positions or flanks) are finished from the genome's letters.  on_device=True keeps the
     genome resident in HBM; False goes through the host twin and needs no torch.  return_status: also the kernel's status per gene
     (GS_OK / GS_HOST)."""
+    be = backend_on(device, on_device)
     G = len(genes)
-    gch = _lib.as_host(gene_chrom, np.int32).ravel()
-    assert len(gch) == G
-    if G and ((gch < 0).any() or (gch >= len(genome.names)).any()):
-        raise ValueError("gene chromosome index outside the genome")
-    last = genes.blk_end[genes.blk_ptr[1:] - 1] if G else np.zeros(0, np.int64)
-    if G and ((genes.blk_start < 1).any() or (last > genome.lengths[gch]).any()):
-        raise ValueError("a gene's CDS blocks reach outside its chromosome")
-    if G and (genes.cds_len % 3).any():
-        raise ValueError("a gene's CDS length is not a multiple of 3")
-    table = (gch, genes.minus, genes.blk_ptr, genes.blk_start, genes.blk_end, genes.cds_off, genes.spl_ptr, genes.spl_pos)
-    if on_device:
-        import torch
-        dev = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
-        L = torch.empty((G, 4, 192), dtype=torch.int32, device=dev)
-        nsl = torch.empty(G, dtype=torch.int32, device=dev)
-        status = torch.empty(G, dtype=torch.uint8, device=dev)
-        p = _lib.dev_ptr
-        with torch.cuda.device(dev):
-            tab = [torch.as_tensor(a, device=dev) for a in table]
-            _lib.call("dig_gene_site_counts", *genome.genome2_args(dev), *[p(a) for a in tab], G, p(L), p(nsl), p(status),
-                      _lib.stream_ptr())
-        L, nsl, status = L.cpu().numpy(), nsl.cpu().numpy(), status.cpu().numpy()
-    else:
-        L, nsl, status = np.empty((G, 4, 192), np.int32), np.empty(G, np.int32), np.empty(G, np.uint8)
-        h = _lib.host_ptr
-        _lib.call("dig_gene_site_counts_host", *genome.genome2_args(), *[h(a) for a in table], G, h(L), h(nsl), h(status),
-                  device if isinstance(device, int) else 0)
+    tab, gch = gene_table(be, genome, genes, gene_chrom)
+    outs = [be.empty((G, 4, 192), "i32"), be.empty(G, "i32"), be.empty(G, "u8")]
+    p = be.ptr
+    be.call("dig_gene_site_counts", *genome.genome2_args(be.dev), *[p(a) for a in tab], G, *[p(a) for a in outs])
+    L, nsl, status = (a.cpu().numpy() if be.is_device else a for a in outs)
     for g in np.flatnonzero(status == GS_HOST):
         L[g], nsl[g] = _gene_sites_from_letters(genome, genes, gch, int(g))
     return (L, nsl, status) if return_status else (L, nsl)
@@ -936,26 +766,14 @@ def gene_site_counts(genome, genes, gene_chrom, device=0, on_device=True, return
 def tiled_nb_test(pt, k, mu, sigma, device=0):
     """Per-tile exact NB test (nb_model.py:141-178).  pt f64 [n_bins, n_tiles] or [C, n_bins, n_tiles];
     k i32 [C, n_bins, n_tiles]; mu, sigma f64 [C, n_bins].  Returns (pval, exp) [C, n_bins, n_tiles]."""
-    if _is_cuda(k):
-        import torch
-        dev = k.device
-        k = _t(k, torch.int32, dev)
-        C, nb, nt = k.shape
-        pt = _t(pt, torch.float64, dev)
-        mu, sigma = _t(mu, torch.float64, dev).reshape(C, nb), _t(sigma, torch.float64, dev).reshape(C, nb)
-        pval = torch.empty((C, nb, nt), dtype=torch.float64, device=dev)
-        ex = torch.empty_like(pval)
-        with torch.cuda.device(dev):
-            _lib.call("dig_tiled_nb_test", _lib.dev_ptr(pt), int(pt.dim() == 3), _lib.dev_ptr(k), _lib.dev_ptr(mu),
-                      _lib.dev_ptr(sigma), _lib.dev_ptr(pval), _lib.dev_ptr(ex), C, nb, nt, _lib.stream_ptr())
-        return pval, ex
-    k = _lib.as_host(k, np.int32)
+    be = backend_of(k, device=device)
+    k = be.arr(k, "i32")
     C, nb, nt = k.shape
-    pt = _lib.as_host(pt, np.float64)
-    mu, sigma = _lib.as_host(mu, np.float64).reshape(C, nb), _lib.as_host(sigma, np.float64).reshape(C, nb)
-    pval, ex = np.empty((C, nb, nt)), np.empty((C, nb, nt))
-    _lib.call("dig_tiled_nb_test_host", _lib.host_ptr(pt), int(pt.ndim == 3), _lib.host_ptr(k), _lib.host_ptr(mu),
-              _lib.host_ptr(sigma), _lib.host_ptr(pval), _lib.host_ptr(ex), C, nb, nt, device)
+    pt = be.arr(pt, "f64")
+    mu, sigma = be.arr(mu, "f64", (C, nb)), be.arr(sigma, "f64", (C, nb))
+    pval, ex = be.empty((C, nb, nt), "f64"), be.empty((C, nb, nt), "f64")
+    p = be.ptr
+    be.call("dig_tiled_nb_test", p(pt), int(pt.ndim == 3), p(k), p(mu), p(sigma), p(pval), p(ex), C, nb, nt)
     return pval, ex
 
 
@@ -983,7 +801,7 @@ def base_tile_probs(genome, chroms, starts, ends, s_prob, binsize, n_tiles=None,
     Returns device tensors (pt [C, R, n_tiles], first_pos [R], n_valid [R]); n_tiles defaults to what the longest region
     needs."""
     import torch
-    dev = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
+    dev = resolve_device(device)
     ci = genome.chrom_index(chroms)
     R = len(ci)
     st, en = _lib.as_host(starts, np.int64).ravel(), _lib.as_host(ends, np.int64).ravel()
@@ -992,7 +810,7 @@ def base_tile_probs(genome, chroms, starts, ends, s_prob, binsize, n_tiles=None,
     binsize = int(binsize)
     if n_tiles is None:
         n_tiles = int(max(1, -(-int((en - st).max() if R else 1) // binsize)))
-    s_prob = _t(s_prob, torch.float64, dev)
+    s_prob = _t(s_prob, "f64", dev)
     assert s_prob.dim() == 2 and s_prob.shape[1] in (64, 1024), "s_prob must be [C, 64] (trinucleotide) or [C, 1024] (penta-nucleotide)"
     C = s_prob.shape[0]
     n_up = 1 if s_prob.shape[1] == 64 else 2
@@ -1022,10 +840,10 @@ def tile_mut_counts(genome, chroms, starts, ends, first_pos, n_valid, mut_chrom,
     ci = genome.chrom_index(chroms)
     blocks = tabulate_gpu.ElementBlocks(ci, _lib.as_host(starts, np.int64).ravel(), _lib.as_host(ends, np.int64).ravel(),
                                         np.arange(R), R, dev)
-    mc = torch.as_tensor(genome.chrom_index(list(np.asarray(mut_chrom).astype(str))) if not _is_cuda(mut_chrom) else mut_chrom,
+    mc = torch.as_tensor(genome.chrom_index(list(np.asarray(mut_chrom).astype(str))) if not is_cuda(mut_chrom) else mut_chrom,
                          device=dev).to(torch.int64)
-    ms, me = _t(mut_start, torch.int64, dev), _t(mut_end, torch.int64, dev)
-    co = _t(mut_cohort, torch.int32, dev)
+    ms, me = _t(mut_start, "i64", dev), _t(mut_end, "i64", dev)
+    co = _t(mut_cohort, "i32", dev)
     pm, pb = tabulate_gpu.overlap_pairs(blocks, mc, ms, me)
     pr = blocks.elt[pb.long()].to(torch.int32).contiguous()          # block row -> region index
     k = torch.empty((int(C), R, int(n_tiles)), dtype=torch.int32, device=dev)
@@ -1067,7 +885,7 @@ class ChunkedScaleFactorPlan:
         import torch
         import torch.distributed as dist
         dev = bin_mu.device
-        self.mu, self.flag = _t(bin_mu, torch.float64, dev), _t(bin_flag, torch.uint8, dev)
+        self.mu, self.flag = _t(bin_mu, "f64", dev), _t(bin_flag, "u8", dev)
         self.masked = None
         if premask:
             self.masked = torch.empty_like(self.mu)
@@ -1085,8 +903,8 @@ class ChunkedScaleFactorPlan:
         self.ws = torch.empty(max(self.wsb, 8), dtype=torch.uint8, device=dev)
         # what a rank contributes: its chunk sums [n_own, C] followed by its observed counts [2, C]
         self.part = torch.zeros((self.n_own + 2, self.C), dtype=torch.float64, device=dev)
-        self.part[self.n_own] = _t(n_snv_obs, torch.float64, dev)
-        self.part[self.n_own + 1] = _t(n_ind_obs, torch.float64, dev)
+        self.part[self.n_own] = _t(n_snv_obs, "f64", dev)
+        self.part[self.n_own + 1] = _t(n_ind_obs, "f64", dev)
         # the exchange step: with more than one rank, or when parallel.FORCE_COLLECTIVES sends a world of one through RCCL too
         from . import parallel
         self.exchange = self.world == self.dist_world and parallel.collectives_on(group)
@@ -1108,8 +926,7 @@ class ChunkedScaleFactorPlan:
         mu, flag = (self.masked, None) if self.masked is not None else (self.mu, self.flag)
         rc = self._lib.dig_scale_suffstats_chunked(p(mu), p(flag), self.C, _lib.host_ptr(self.chunk_rows), self.n_own,
                                                    p(self.part), p(self.ws), self.wsb, _lib.stream_ptr(stream))
-        if rc != 0:
-            raise _lib.DigHipError("dig_scale_suffstats_chunked failed (%d): %s" % (rc, _lib.last_error()))
+        _lib.check("dig_scale_suffstats_chunked", rc)
         return self.part
 
     def _on(self, stream):
@@ -1132,8 +949,7 @@ class ChunkedScaleFactorPlan:
         rc = self._lib.dig_scale_factors_chunked(p(sums), self.n_total, p(obs), self.world, self.C,
                                                  p(out_sum) if out_sum is not None else None, p(cj), p(cj_indel),
                                                  _lib.stream_ptr(stream))
-        if rc != 0:
-            raise _lib.DigHipError("dig_scale_factors_chunked failed (%d): %s" % (rc, _lib.last_error()))
+        _lib.check("dig_scale_factors_chunked", rc)
 
     def run(self, cj, cj_indel, out_sum=None, stream=None):
         """Enqueue on `stream` (default: torch's current stream).  With a process group the all-gather and the copies that

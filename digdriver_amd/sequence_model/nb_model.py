@@ -8,11 +8,7 @@ on torch's current stream).  There is no CPU fallback.
 """
 import numpy as np
 
-from .. import _lib
-
-
-def _is_cuda_tensor(x):
-    return type(x).__module__.startswith("torch") and getattr(x, "is_cuda", False)
+from .._marshal import backend_of
 
 
 def _series_like(*xs):
@@ -22,58 +18,33 @@ def _series_like(*xs):
     return None
 
 
-def _vec3(name, k, alpha, p, device=0):
-    if any(_is_cuda_tensor(x) for x in (k, alpha, p)):
-        import torch
-        dev = next(x.device for x in (k, alpha, p) if _is_cuda_tensor(x))
-        k, alpha, p = torch.broadcast_tensors(*[torch.as_tensor(x, dtype=torch.float64, device=dev) for x in (k, alpha, p)])
-        k, alpha, p = k.contiguous(), alpha.contiguous(), p.contiguous()
-        out = torch.empty_like(k)
-        with torch.cuda.device(dev):
-            _lib.call(name, _lib.dev_ptr(k), _lib.dev_ptr(alpha), _lib.dev_ptr(p), _lib.dev_ptr(out), k.numel(),
-                      _lib.stream_ptr())
-        return out
-    ser = _series_like(k, alpha, p)
-    kb, ab, pb = np.broadcast_arrays(np.asarray(k, dtype=np.float64), np.asarray(alpha, dtype=np.float64),
-                                     np.asarray(p, dtype=np.float64))
-    shape = kb.shape
-    kc, ac, pc = (_lib.as_host(v, np.float64).ravel() for v in (kb, ab, pb))
-    out = np.empty(kc.shape, np.float64)
-    _lib.call(name + "_host", _lib.host_ptr(kc), _lib.host_ptr(ac), _lib.host_ptr(pc), _lib.host_ptr(out), kc.size,
-              device)
-    out = out.reshape(shape)
+def _elementwise(name, ins, n_out, device):
+    """Entry point `name` over the broadcast of `ins` (float64), n_out results of that shape.  Device tensors in -> device tensors
+    out; on the host a Series among the inputs gives Series, scalars give floats."""
+    be = backend_of(*ins, device=device)
+    xs = be.broadcast(ins, "f64")
+    shape = tuple(xs[0].shape)
+    outs = [be.empty(shape, "f64") for _ in range(n_out)]
+    n = 1
+    for s in shape:
+        n *= s
+    be.call(name, *[be.ptr(x) for x in xs], *[be.ptr(o) for o in outs], n)
+    if be.is_device:
+        return outs
+    ser = _series_like(*ins)
     if ser is not None:
         import pandas as pd
-        return pd.Series(out, index=ser.index)
-    return out if shape else float(out)
+        return [pd.Series(o, index=ser.index) for o in outs]
+    return outs if shape else [float(o) for o in outs]
+
+
+def _vec3(name, k, alpha, p, device=0):
+    return _elementwise(name, (k, alpha, p), 1, device)[0]
 
 
 def normal_params_to_gamma(mu, sigma, device=0):
     """nb_model.py:237-241 -- alpha = mu**2 / sigma**2, theta = sigma**2 / mu."""
-    if _is_cuda_tensor(mu) or _is_cuda_tensor(sigma):
-        import torch
-        dev = mu.device if _is_cuda_tensor(mu) else sigma.device
-        mu, sigma = torch.broadcast_tensors(*[torch.as_tensor(x, dtype=torch.float64, device=dev) for x in (mu, sigma)])
-        mu, sigma = mu.contiguous(), sigma.contiguous()
-        alpha, theta = torch.empty_like(mu), torch.empty_like(mu)
-        with torch.cuda.device(dev):
-            _lib.call("dig_normal_params_to_gamma", _lib.dev_ptr(mu), _lib.dev_ptr(sigma), _lib.dev_ptr(alpha),
-                      _lib.dev_ptr(theta), mu.numel(), _lib.stream_ptr())
-        return alpha, theta
-    ser = _series_like(mu, sigma)
-    mb, sb = np.broadcast_arrays(np.asarray(mu, dtype=np.float64), np.asarray(sigma, dtype=np.float64))
-    shape = mb.shape
-    mc, sc = _lib.as_host(mb, np.float64).ravel(), _lib.as_host(sb, np.float64).ravel()
-    alpha, theta = np.empty(mc.shape), np.empty(mc.shape)
-    _lib.call("dig_normal_params_to_gamma_host", _lib.host_ptr(mc), _lib.host_ptr(sc), _lib.host_ptr(alpha),
-              _lib.host_ptr(theta), mc.size, device)
-    alpha, theta = alpha.reshape(shape), theta.reshape(shape)
-    if ser is not None:
-        import pandas as pd
-        return pd.Series(alpha, index=ser.index), pd.Series(theta, index=ser.index)
-    if not shape:
-        return float(alpha), float(theta)
-    return alpha, theta
+    return tuple(_elementwise("dig_normal_params_to_gamma", (mu, sigma), 2, device))
 
 
 def nb_pvalue_greater_midp(k, alpha, p, device=0):
@@ -103,26 +74,7 @@ def nb_pvalue_midp(k, alpha, p, mu=None, device=0):
 
 def fisher_combine(p1, p2, device=0):
     """chi2.sf(-2 (ln p1 + ln p2), df=4) (transfer_tools.py:860-861,1086-1087)."""
-    if _is_cuda_tensor(p1) or _is_cuda_tensor(p2):
-        import torch
-        dev = p1.device if _is_cuda_tensor(p1) else p2.device
-        p1, p2 = torch.broadcast_tensors(*[torch.as_tensor(x, dtype=torch.float64, device=dev) for x in (p1, p2)])
-        p1, p2 = p1.contiguous(), p2.contiguous()
-        out = torch.empty_like(p1)
-        with torch.cuda.device(dev):
-            _lib.call("dig_fisher", _lib.dev_ptr(p1), _lib.dev_ptr(p2), _lib.dev_ptr(out), p1.numel(), _lib.stream_ptr())
-        return out
-    ser = _series_like(p1, p2)
-    a, b = np.broadcast_arrays(np.asarray(p1, dtype=np.float64), np.asarray(p2, dtype=np.float64))
-    shape = a.shape
-    ac, bc = _lib.as_host(a, np.float64).ravel(), _lib.as_host(b, np.float64).ravel()
-    out = np.empty(ac.shape)
-    _lib.call("dig_fisher_host", _lib.host_ptr(ac), _lib.host_ptr(bc), _lib.host_ptr(out), ac.size, device)
-    out = out.reshape(shape)
-    if ser is not None:
-        import pandas as pd
-        return pd.Series(out, index=ser.index)
-    return out if shape else float(out)
+    return _elementwise("dig_fisher", (p1, p2), 1, device)[0]
 
 
 # ---------------------------------------------------------------------------------------------

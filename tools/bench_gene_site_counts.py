@@ -25,6 +25,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from bench_mutation_function import synthetic_genes, timed        # noqa: E402
 from bench_penta_contexts import synthetic_seqs                   # noqa: E402
 from digdriver_amd import _lib, engine                            # noqa: E402
+from digdriver_amd._marshal import device_backend                # noqa: E402
 from digdriver_amd.data_tools.genome import PackedGenome          # noqa: E402
 
 
@@ -48,7 +49,7 @@ def main():
     t = lambda x: torch.as_tensor(x, device=dev)
     p = _lib.dev_ptr
     genome = g.genome2_args(dev)
-    tab = [t(x) for x in (gch, genes.minus, genes.blk_ptr, genes.blk_start, genes.blk_end, genes.cds_off, genes.spl_ptr, genes.spl_pos)]
+    tab, _ = engine.gene_table(device_backend(dev), g, genes, gch)
     L = torch.empty((G, 4, 192), dtype=torch.int32, device=dev)
     nsl, status = torch.empty(G, dtype=torch.int32, device=dev), torch.empty(G, dtype=torch.uint8, device=dev)
 

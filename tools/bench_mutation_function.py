@@ -24,7 +24,8 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 from bench_penta_contexts import synthetic_seqs                 # noqa: E402
-from digdriver_amd import _lib                                  # noqa: E402
+from digdriver_amd import _lib, engine                          # noqa: E402
+from digdriver_amd._marshal import device_backend              # noqa: E402
 from digdriver_amd.data_tools import gene_annotation            # noqa: E402
 from digdriver_amd.data_tools.genome import PackedGenome        # noqa: E402
 
@@ -86,7 +87,7 @@ def main():
     t = lambda x: torch.as_tensor(x, device=dev)
     p = _lib.dev_ptr
     genome = g.genome2_args(dev)
-    tab = [t(x) for x in (gch, genes.minus, genes.blk_ptr, genes.blk_start, genes.blk_end, genes.cds_off, genes.spl_ptr, genes.spl_pos)]
+    tab, _ = engine.gene_table(device_backend(dev), g, genes, gch)
     r_chrom, r_start, r_end, r_gene = genes.ranges()
     blocks = tabulate_gpu.ElementBlocks(g.chrom_index(r_chrom).astype(np.int64) + 1, r_start - 1, r_end, np.arange(len(r_start)), len(r_start), dev)
     size = genes.blk_end - genes.blk_start + 1
