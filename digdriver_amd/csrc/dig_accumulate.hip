@@ -234,22 +234,7 @@ typedef double double4_t __attribute__((ext_vector_type(4)));
 constexpr int kMfmaWaves = 12;
 constexpr int kMfmaMinBlocks = 1;
 constexpr int kMfmaSteps = 64;                // 256 K rows / 4
-constexpr int kMfmaChunk = 48;                // cohorts per launch (3 B tiles)
-
-// How the (at most 48) cohort columns of a chunk are cut: full 16-column tiles for v_mfma_f64_16x16x4, and, when what is
-// left over is 1..8 columns, one or two QUADS of four columns for v_mfma_f64_4x4x4 (four 4x4 blocks = the same sixteen
-// elements; a quad costs a quarter of a tile's matrix-pipe time, so 37 cohorts pay for 40 columns instead of 48).
-struct ChunkCut {
-    int nt, nq;      // full tiles, tail quads
-};
-__host__ __device__ inline ChunkCut chunk_cut(int C, int chunk)
-{
-    const int rem = C - chunk * 48 < 48 ? C - chunk * 48 : 48;
-    const int full = rem >> 4, r = rem & 15;
-    if (r == 0) return {full, 0};
-    if (r <= 8) return {full, (r + 3) >> 2};
-    return {full + 1, 0};
-}
+constexpr int kMfmaChunk = kCutChunk;         // cohorts per launch (3 B tiles)
 
 // tab[chunk][step = 4 t + u][nt][lane] = T[kappa = 16 t + 4 (lane / 16) + u][chunk * 48 + nt * 16 + lane % 16],
 // T = per-context sums (kappa < 64, d_pr[c][3 ctx .. 3 ctx + 2] summed as (a + b) + c) then d_pr[c][kappa - 64].
@@ -915,25 +900,14 @@ static int launch_dot_mfma(const AccWorkspace& w, const int32_t* L, const int32_
         const ChunkCut cut = chunk_cut((int)C, ch);
         const size_t lds = (size_t)kMfmaSteps * (cut.nt + (cut.nq > 0)) * 64 * sizeof(double);
         const double* tab = w.tab + (int64_t)ch * kMfmaSteps * 3 * 64;
-        auto go = [&](auto kern) -> int {
+        const int rc = dispatch_cut(cut, [&](auto nt, auto nq) -> int {
+            auto kern = acc_dot_mfma_kernel<NCLASS, nt.value, nq.value>;
             DIG_HIP_TRY(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
             DIG_LAUNCH_STAGE(DIG_PIPE_DOT, kern, dim3(grid), dim3(kMfmaWaves * 64), lds, stream, w.rcp, L, tab, R_SIZE, gene_length, P,
                                ELT_SIZE, P_INDEL, E, (int)C, c0, (int)(ch == 0), d_pr);
             DIG_HIP_TRY(hipGetLastError());
             return DIG_OK;
-        };
-        int rc;
-        switch (cut.nt * 3 + cut.nq) {
-        case 9: rc = go(acc_dot_mfma_kernel<NCLASS, 3, 0>); break;
-        case 6: rc = go(acc_dot_mfma_kernel<NCLASS, 2, 0>); break;
-        case 7: rc = go(acc_dot_mfma_kernel<NCLASS, 2, 1>); break;
-        case 8: rc = go(acc_dot_mfma_kernel<NCLASS, 2, 2>); break;
-        case 3: rc = go(acc_dot_mfma_kernel<NCLASS, 1, 0>); break;
-        case 4: rc = go(acc_dot_mfma_kernel<NCLASS, 1, 1>); break;
-        case 5: rc = go(acc_dot_mfma_kernel<NCLASS, 1, 2>); break;
-        case 1: rc = go(acc_dot_mfma_kernel<NCLASS, 0, 1>); break;
-        default: rc = go(acc_dot_mfma_kernel<NCLASS, 0, 2>); break;
-        }
+        });
         if (rc) return rc;
     }
     return DIG_OK;
@@ -1014,25 +988,14 @@ int accumulate_compact_launch(const int32_t* bin_ctx, const int64_t* ov_ptr, con
     const int n48 = (int)((C + kMfmaChunk - 1) / kMfmaChunk);
     for (int ch = 0; ch < n48; ++ch) {
         const ChunkCut cut = chunk_cut((int)C, ch);
-        auto go = [&](auto kern) -> int {
+        const int rc = dispatch_cut(cut, [&](auto nt, auto nq) -> int {
+            auto kern = acc_dot_ctx_kernel<nt.value, nq.value>;
             DIG_LAUNCH_STAGE(DIG_PIPE_DOT, kern, dim3(grid), dim3(kCtxWaves * 64), 0, (hipStream_t)stream, bin_ctx, ov_ptr, ov_idx, strand_minus,
                                Lc, d_pr, gene_length, P, R_SIZE, ELT_SIZE, P_INDEL, E, (int)C, ch * kMfmaChunk, (int)(ch == 0),
                                ch == 0 ? zero_dwords : nullptr, n_zero);
             DIG_HIP_TRY(hipGetLastError());
             return DIG_OK;
-        };
-        int rc;
-        switch (cut.nt * 3 + cut.nq) {
-        case 9: rc = go(acc_dot_ctx_kernel<3, 0>); break;
-        case 6: rc = go(acc_dot_ctx_kernel<2, 0>); break;
-        case 7: rc = go(acc_dot_ctx_kernel<2, 1>); break;
-        case 8: rc = go(acc_dot_ctx_kernel<2, 2>); break;
-        case 3: rc = go(acc_dot_ctx_kernel<1, 0>); break;
-        case 4: rc = go(acc_dot_ctx_kernel<1, 1>); break;
-        case 5: rc = go(acc_dot_ctx_kernel<1, 2>); break;
-        case 1: rc = go(acc_dot_ctx_kernel<0, 1>); break;
-        default: rc = go(acc_dot_ctx_kernel<0, 2>); break;
-        }
+        });
         if (rc) return rc;
     }
     return DIG_OK;

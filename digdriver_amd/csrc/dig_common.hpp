@@ -6,6 +6,7 @@
 #include <stdio.h>
 
 #include <string>
+#include <type_traits>
 
 #include "../../include/dig_hip.h"
 
@@ -67,19 +68,50 @@ void disarm_stage_timers();                    // end of a dig_element_pipeline 
             hipLaunchKernelGGL(kernel, grid, block, lds, stream, __VA_ARGS__);                                           \
     } while (0)
 
-// dig_tiles_rows.hip: the row walk of the tile probabilities, one launch per cohort pass; regions it does not take are left with
-// n_valid = -2 for the general kernel (dig_tiles.hip)
-int launch_tile_probs_rows(const uint32_t* words, int64_t n_words, const int64_t* chrom_off, const int64_t* chrom_len,
-                           const int32_t* reg_chrom, const int64_t* reg_start, const int64_t* reg_end, int64_t R, const double* s_prob,
-                           int64_t C, int n_up, int binsize, int64_t n_tiles, double* pt, int64_t* first_pos, int32_t* n_valid,
-                           hipStream_t stream);
-
 inline int grid_for(int64_t n, int block, int max_blocks_per_cu = 8)
 {
     int64_t want = (n + block - 1) / block;
     int64_t cap = (int64_t)cu_count() * max_blocks_per_cu;
     if (want < 1) want = 1;
     return (int)(want < cap ? want : cap);
+}
+
+// How the (at most 48) cohort columns of a chunk are cut: full 16-column tiles for v_mfma_f64_16x16x4, and, when what is
+// left over is 1..8 columns, one or two QUADS of four columns for v_mfma_f64_4x4x4 (four 4x4 blocks = the same sixteen
+// elements; a quad costs a quarter of a tile's matrix-pipe time, so 37 cohorts pay for 40 columns instead of 48).
+// (the dot kernels of dig_accumulate.hip and the matrix kernels of dig_tiles.hip)
+constexpr int kCutChunk = 48;                 // cohorts per chunk
+struct ChunkCut {
+    int nt, nq;      // full tiles, tail quads
+};
+__host__ __device__ inline ChunkCut chunk_cut(int C, int chunk)
+{
+    const int rem = C - chunk * kCutChunk < kCutChunk ? C - chunk * kCutChunk : kCutChunk;
+    const int full = rem >> 4, r = rem & 15;
+    if (r == 0) return {full, 0};
+    if (r <= 8) return {full, (r + 3) >> 2};
+    return {full + 1, 0};
+}
+// f(std::integral_constant<int, NT>{}, std::integral_constant<int, NQ>{}) -> int for the nine cuts a chunk with a cohort in
+// it can have; any other pair is refused
+template <class F>
+inline int dispatch_cut(ChunkCut cut, F&& f)
+{
+#define DIG_CUT_CASE(NT, NQ) \
+    case NT * 3 + NQ: return f(std::integral_constant<int, NT>{}, std::integral_constant<int, NQ>{})
+    switch (cut.nq >= 0 && cut.nq <= 2 ? cut.nt * 3 + cut.nq : -1) {
+        DIG_CUT_CASE(0, 1);
+        DIG_CUT_CASE(0, 2);
+        DIG_CUT_CASE(1, 0);
+        DIG_CUT_CASE(1, 1);
+        DIG_CUT_CASE(1, 2);
+        DIG_CUT_CASE(2, 0);
+        DIG_CUT_CASE(2, 1);
+        DIG_CUT_CASE(2, 2);
+        DIG_CUT_CASE(3, 0);
+    default: return set_error(DIG_EINVAL, "dispatch_cut: no kernel for %d tiles + %d quads", cut.nt, cut.nq);
+    }
+#undef DIG_CUT_CASE
 }
 
 }  // namespace dig

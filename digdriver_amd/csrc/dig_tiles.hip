@@ -23,62 +23,41 @@
 //
 // dig_tile_mut_counts: k[c][region][tile] from the (mutation, region) pairs of dig_overlap_join_*: one atomic add per
 // pair whose START lies inside the region's positions.
-#include <type_traits>
-
-#include "dig_common.hpp"
+//
+// Four kernels here (base_tile_probs_kernel: the plain fallback; base_tile_probs_mfma_kernel and base_tile_probs_roles_kernel:
+// the matrix forms; base_tile_probs_ctx_kernel: general contexts), the row walk in dig_tiles_rows.hip.  What they share lives in
+// dig_tiles.hpp: a region's positions (region_positions), the packed-word window of a base range (word_window, load_word) and
+// its staging (stage_load / stage_store), the nibble squeezes, the matrix kernels' cohort operands, and on the host the argument
+// block (TileArgs: launch, check_tile_args) and the DIG_TILES_FORM switch.  The cut of a cohort chunk into tiles and quads
+// (chunk_cut, dispatch_cut) is the dot kernels' (dig_accumulate.hip) as well: dig_common.hpp.
+#include "dig_tiles.hpp"
 
 namespace dig {
 
 constexpr int kTileBlock = 256;
 constexpr int kTileCohorts = 20;          // cohort accumulators per sweep of the histogram column (37 cohorts: 20 + 17); even
 constexpr int kTileMaxWords = 1536;       // packed words staged per pass: 12 288 bases (a 10-kb bin and its neighbours)
+constexpr int kTilePer = (kTileMaxWords + 2 + kTileBlock - 1) / kTileBlock;      // of them per thread
+constexpr int64_t kTilePassPos = (int64_t)(kTileMaxWords - 1) * 8;                 // positions whose windows a pass covers
 
-struct TileRegion {
-    int64_t first;      // first position (chromosome coordinates)
-    int64_t n_pos;      // number of positions
-    int64_t g0;         // global base index of position `first` (counted from word 1 of the genome array)
-};
-
-// fetch_sequence (sequence_tools.py:21-29) with n_up = n_down = 1: START == 0 becomes 1; the widened fetch is cut at
-// the chromosome end, so the last position with a full window is chrom_len - 2.
+// The trinucleotide kernels' region: n_up = n_down = 1.
 __device__ __forceinline__ TileRegion tile_region(const int64_t* chrom_off, const int64_t* chrom_len, int chrom, int64_t start,
                                                   int64_t end)
 {
-    TileRegion t;
-    const int64_t len = chrom_len[chrom];
-    t.first = start == 0 ? 1 : start;
-    const int64_t stop = end < len - 1 ? end : len - 1;       // one past the last position
-    t.n_pos = stop > t.first ? stop - t.first : 0;
-    t.g0 = chrom_off[chrom] + t.first;
-    return t;
+    return region_positions(1, chrom_len[chrom], chrom_off[chrom], start, end);
 }
 
-// Stage nw <= kTileMaxWords + 2 packed words (from array word w0 on, clamped to the trailing pad word) into LDS: all loads of a
-// thread are issued before its first LDS write -- the plain loop `s_words[i] = words[...]` waits for every load in turn (one
-// memory round trip per 256 words instead of one per region).
-template <int BLOCK>
-__device__ __forceinline__ void stage_words(uint32_t* s_words, const uint32_t* __restrict__ words, int64_t n_words, int64_t w0,
-                                            int64_t nw, int tid)
+// The staged window of n positions from global base g on: their bases and one neighbour on either side.
+constexpr int kTileMarginWords = 0;       // nothing is read past the last window (the walk's word ahead is clamped where it reads)
+__device__ __forceinline__ WordWindow tile_window(int64_t g, int64_t n)
 {
-    constexpr int kPer = (1538 + BLOCK - 1) / BLOCK;       // kTileMaxWords + 2
-    uint32_t tmp[kPer];
-#pragma unroll
-    for (int j = 0; j < kPer; ++j) {
-        const int64_t i = tid + (int64_t)j * BLOCK;
-        tmp[j] = i < nw ? words[(w0 + i < n_words ? w0 + i : n_words - 1)] : 0u;
-    }
-#pragma unroll
-    for (int j = 0; j < kPer; ++j) {
-        const int64_t i = tid + (int64_t)j * BLOCK;
-        if (i < nw) s_words[i] = tmp[j];
-    }
+    WordWindow v = word_window(g - 1, n + 2);
+    v.nw += kTileMarginWords;
+    return v;
 }
-
-// 4-bit code of global base g (word 0 of the array is the leading pad word)
-__device__ __forceinline__ unsigned tile_base(const uint32_t* s_words, int64_t g, int64_t g_lds0)
+__device__ __forceinline__ void tile_stage(uint32_t* s_words, const uint32_t* __restrict__ words, int64_t n_words, const WordWindow& v, int tid)
 {
-    const int64_t r = g - g_lds0;                               // base index inside the staged words
-    return (s_words[r >> 3] >> (4 * (int)(r & 7))) & 15u;
+    stage_words<kTilePer, kTileBlock>(s_words, words, n_words, v.w0, v.nw, tid);
 }
 
 template <bool SINGLE>
@@ -105,15 +84,12 @@ __global__ __launch_bounds__(kTileBlock) void base_tile_probs_kernel(
         // ---- region histogram H over ALL positions (passes of kTileMaxWords words when the region is longer) ----
         if (tid < 64) s_H[tid] = 0;
         __syncthreads();
-        const int64_t pos_per_pass = (int64_t)(kTileMaxWords - 1) * 8;
-        for (int64_t p0 = 0; p0 < reg.n_pos; p0 += pos_per_pass) {
-            const int64_t np = reg.n_pos - p0 < pos_per_pass ? reg.n_pos - p0 : pos_per_pass;
-            const int64_t ga = reg.g0 + p0 - 1;                 // leftmost base needed (left neighbour of the first position)
-            const int64_t w0 = (ga >> 3) + 1;                   // array word holding it (array word = genome word + 1)
-            const int64_t nw = ((ga + np + 1) >> 3) + 1 - w0 + 1;
-            stage_words<256>(s_words, words, n_words, w0, nw, tid);
+        for (int64_t p0 = 0; p0 < reg.n_pos; p0 += kTilePassPos) {
+            const int64_t np = reg.n_pos - p0 < kTilePassPos ? reg.n_pos - p0 : kTilePassPos;
+            const WordWindow win = tile_window(reg.g0 + p0, np);
+            tile_stage(s_words, words, n_words, win, tid);
             __syncthreads();
-            const int64_t g_lds0 = (w0 - 1) << 3;
+            const int64_t g_lds0 = win.g_lds0;
             for (int64_t j = tid; j < np; j += kTileBlock) {
                 const int64_t g = reg.g0 + p0 + j;
                 const unsigned a = tile_base(s_words, g - 1, g_lds0), b = tile_base(s_words, g, g_lds0), c = tile_base(s_words, g + 1, g_lds0);
@@ -133,16 +109,14 @@ __global__ __launch_bounds__(kTileBlock) void base_tile_probs_kernel(
             if (!SINGLE)
                 for (int x = 0; x < 64; ++x) s_hist[x][tid] = 0;
             // 256 tiles span 256 * binsize positions: staged in passes of whole tiles when that exceeds the buffer
-            const int64_t pos_pass = (int64_t)(kTileMaxWords - 1) * 8 / binsize * binsize;
+            const int64_t pos_pass = kTilePassPos / binsize * binsize;
             for (int64_t q0 = 0; q0 < np; q0 += pos_pass) {
                 const int64_t nq = np - q0 < pos_pass ? np - q0 : pos_pass;
-                const int64_t ga = reg.g0 + pa + q0 - 1;
-                const int64_t w0 = (ga >> 3) + 1;
-                const int64_t nw = ((ga + nq + 1) >> 3) + 1 - w0 + 1;
+                const WordWindow win = tile_window(reg.g0 + pa + q0, nq);
                 __syncthreads();
-                stage_words<256>(s_words, words, n_words, w0, nw, tid);
+                tile_stage(s_words, words, n_words, win, tid);
                 __syncthreads();
-                const int64_t g_lds0 = (w0 - 1) << 3;
+                const int64_t g_lds0 = win.g_lds0;
                 const int64_t tp = (int64_t)tid * binsize - q0;          // first position of this lane's tile inside the pass
                 if (live && tp >= 0 && tp < nq) {
                     int64_t cnt = binsize;
@@ -236,7 +210,7 @@ __global__ __launch_bounds__(kTileBlock) void base_tile_probs_kernel(
 typedef double tile_double4 __attribute__((ext_vector_type(4)));
 constexpr int kTmStride = 272;                 // 16-bit counters per histogram row (256 tiles + 16 of padding)
 constexpr int kTmStride32 = kTmStride / 2;
-constexpr int kTmChunk = 48;                   // cohorts per launch
+constexpr int kTmChunk = kCutChunk;            // cohorts per launch
 constexpr int kTmOcc = 2;                      // workgroups per CU (register budget 256)
 
 // One packed word of a tile's walk: contexts centred on nibbles centre0 .. centre0 + 7 (centre0 = 8 word - 1).  GUARD: the
@@ -246,19 +220,11 @@ template <bool GUARD>
 __device__ __forceinline__ void tile_word(unsigned w, unsigned& carry, unsigned& icarry, int centre0, int lo, int hi,
                                           unsigned* col, unsigned inc)
 {
-    unsigned x = w & 0x33333333u;                                  // 2-bit bases, squeezed: base n at bits 2 n
-    x = (x | (x >> 2)) & 0x0F0F0F0Fu;
-    x = (x | (x >> 4)) & 0x00FF00FFu;
-    x = (x | (x >> 8)) & 0xFFFFu;
-    const unsigned win = (x << 4) | carry;                         // the two bases before the word, then its eight
+    const unsigned win = (squeeze_bases(w) << 4) | carry;          // the two bases before the word, then its eight
     carry = win >> 16;
     unsigned okm = 0xFFu;
     if (GUARD) {
-        unsigned f = ((w >> 2) | (w >> 3)) & 0x11111111u;          // non-ACGT flags, squeezed: base n at bit n
-        f = (f | (f >> 3)) & 0x03030303u;
-        f = (f | (f >> 6)) & 0x000F000Fu;
-        f = (f | (f >> 12)) & 0xFFu;
-        const unsigned iwin = (f << 2) | icarry;                   // bit n + 2: base n of the word; bits n .. n + 2: the window of centre n
+        const unsigned iwin = (nonacgt_flags(w) << 2) | icarry;                  // bit n + 2: base n of the word; bits n .. n + 2: the window of centre n
         icarry = iwin >> 8;
         const int a = lo - centre0, b = hi - centre0;              // centres a .. b - 1 of the word lie inside the tile
         const unsigned below_b = b >= 8 ? 0xFFu : (b <= 0 ? 0u : (1u << b) - 1u);
@@ -305,13 +271,6 @@ __device__ __forceinline__ void tile_histograms(const uint32_t* s_words, uint32_
     }
 }
 
-// 4-bit code of global base g straight from the packed array (array word = genome word + 1; clamped to the trailing pad word)
-__device__ __forceinline__ unsigned tile_base_global(const uint32_t* __restrict__ words, int64_t n_words, int64_t g)
-{
-    const int64_t w = (g >> 3) + 1;
-    return (words[w < n_words ? w : n_words - 1] >> (4 * (int)(g & 7))) & 15u;
-}
-
 // MT full 16-cohort tiles (v_mfma_f64_16x16x4), then NQ quads of four cohorts (v_mfma_f64_4x4x4: its four 4x4 blocks take the
 // SAME four cohort rows against four different groups of four tiles, so the B operand is the register of the 16-row form and a
 // quad costs a quarter of a tile): 37 cohorts = 2 tiles + 2 quads pay for 2.5 tiles' worth of matrix time where three tiles
@@ -335,21 +294,7 @@ __global__ __launch_bounds__(kTileBlock, kTmOcc) void base_tile_probs_mfma_kerne
 
     constexpr int MTA = MT > 0 ? MT : 1, NQA = NQ > 0 ? NQ : 1;
     double A[MTA][16], Aq[NQA][16];
-#pragma unroll
-    for (int ks = 0; ks < 16; ++ks) {
-        const int row = 4 * ks + lk;                                    // histogram row = b0 + 4 b1 + 16 b2 (walk order) ...
-        const int ctx = ((row & 3) << 4) | (row & 12) | (row >> 4);     // ... of context 16 b0 + 4 b1 + b2
-#pragma unroll
-        for (int m = 0; m < MT; ++m) {
-            const int64_t c = c0 + 16 * m + li;
-            A[m][ks] = c < C ? s_prob[c * 64 + ctx] : 0.0;
-        }
-#pragma unroll
-        for (int q = 0; q < NQ; ++q) {                                  // A[i][k] of every block b: lane 16 k + 4 b + i
-            const int64_t c = c0 + 16 * MT + 4 * q + (lane & 3);
-            Aq[q][ks] = c < C ? s_prob[c * 64 + ctx] : 0.0;
-        }
-    }
+    load_cohort_operands<MT, NQ>(A, Aq, s_prob, c0, C, lane, true);
     const int n_groups = (n_tiles + 15) >> 4;
     const int64_t cohort_stride = R * n_tiles;                 // elements between two cohorts of pt
     const int64_t tiled = (int64_t)n_tiles * binsize;
@@ -369,16 +314,11 @@ __global__ __launch_bounds__(kTileBlock, kTmOcc) void base_tile_probs_mfma_kerne
             uint4* z = reinterpret_cast<uint4*>(s_hist32);
             for (int i = tid; i < 64 * kTmStride32 / 4; i += kTileBlock) z[i] = make_uint4(0u, 0u, 0u, 0u);
         }
-        const int64_t ga = reg.g0 - 1;                      // left neighbour of the first position
-        const int64_t w0 = (ga >> 3) + 1;
-        const int64_t g_lds0 = (w0 - 1) << 3;
-        {
-            const int nw = (int)(((ga + n_cov + 1) >> 3) + 1 - w0 + 1);
-            stage_words<256>(s_words, words, n_words, w0, nw, tid);
-        }
+        const WordWindow win = tile_window(reg.g0, n_cov);
+        tile_stage(s_words, words, n_words, win, tid);
         __syncthreads();
         // ---- per-tile context histograms ----
-        tile_histograms(s_words, s_hist32, tid, nv, binsize, n_cov, (int)(ga - g_lds0) + 1);
+        tile_histograms(s_words, s_hist32, tid, nv, binsize, n_cov, (int)(reg.g0 - win.g_lds0));
         __syncthreads();
         // ---- H[ctx] = sum over the tiles: lane = (row of the wave's sixteen, quarter of the row) ----
         {
@@ -396,16 +336,13 @@ __global__ __launch_bounds__(kTileBlock, kTmOcc) void base_tile_probs_mfma_kerne
         }
         if (reg.n_pos > n_cov) {                              // positions behind the last tile count for the normalisation only
             __syncthreads();
-            const int64_t pos_per_pass = (int64_t)(kTileMaxWords - 1) * 8;
-            for (int64_t p0 = n_cov; p0 < reg.n_pos; p0 += pos_per_pass) {
-                const int64_t np = reg.n_pos - p0 < pos_per_pass ? reg.n_pos - p0 : pos_per_pass;
-                const int64_t gb = reg.g0 + p0 - 1;
-                const int64_t wb0 = (gb >> 3) + 1;
-                const int64_t nw = ((gb + np + 1) >> 3) + 1 - wb0 + 1;
+            for (int64_t p0 = n_cov; p0 < reg.n_pos; p0 += kTilePassPos) {
+                const int64_t np = reg.n_pos - p0 < kTilePassPos ? reg.n_pos - p0 : kTilePassPos;
+                const WordWindow wb = tile_window(reg.g0 + p0, np);
                 __syncthreads();
-                stage_words<256>(s_words, words, n_words, wb0, nw, tid);
+                tile_stage(s_words, words, n_words, wb, tid);
                 __syncthreads();
-                const int64_t gl = (wb0 - 1) << 3;
+                const int64_t gl = wb.g_lds0;
                 for (int64_t j = tid; j < np; j += kTileBlock) {
                     const int64_t g = reg.g0 + p0 + j;
                     const unsigned a = tile_base(s_words, g - 1, gl), b = tile_base(s_words, g, gl), c = tile_base(s_words, g + 1, gl);
@@ -513,23 +450,12 @@ __global__ __launch_bounds__(kTileBlock, kTmOcc) void base_tile_probs_mfma_kerne
 //     (13 groups x (2 tiles + 2 quads): 8.5 / 8.5 / 8 / 7.5 tile-times instead of 10 / 7.5 / 7.5 / 7.5).
 // Same bits as the kernel above (same chains, same order; tests/test_gpu_tiles.py compares the two forms).
 constexpr int kTsBlock = 512;
-constexpr int kTsPer = (kTileMaxWords + 2 + 255) / 256;         // packed words a walker thread carries for the next region
 
 __device__ __forceinline__ double count_as_double(unsigned n)   // n < 2^20, exact, integer instructions only
 {
     const unsigned f = __float_as_uint((float)n);
     const unsigned hi = n ? (f >> 3) + 0x38000000u : 0u;        // exponent 127 -> 1023; the 20 mantissa bits in use fit the high word
     return __hiloint2double((int)hi, 0);
-}
-
-__device__ __forceinline__ TileRegion tile_region_of(int64_t len, int64_t off, int64_t start, int64_t end)
-{
-    TileRegion t;
-    t.first = start == 0 ? 1 : start;
-    const int64_t stop = end < len - 1 ? end : len - 1;
-    t.n_pos = stop > t.first ? stop - t.first : 0;
-    t.g0 = off + t.first;
-    return t;
 }
 
 // One tile group: the chains named by MASK (bit m = cohort tile m, bit MT = the quads) share the converted histogram values.
@@ -614,21 +540,7 @@ __global__ __launch_bounds__(kTsBlock, 1) void base_tile_probs_roles_kernel(
     const int64_t tiled = (int64_t)n_tiles * binsize;
 
     double A[MTA][16], Aq[NQA][16];
-#pragma unroll
-    for (int ks = 0; ks < 16; ++ks) {
-        const int row = 4 * ks + lk;                                    // histogram row = b0 + 4 b1 + 16 b2 (walk order) ...
-        const int ctx = ((row & 3) << 4) | (row & 12) | (row >> 4);     // ... of context 16 b0 + 4 b1 + b2
-#pragma unroll
-        for (int m = 0; m < MTA; ++m) {
-            const int64_t c = c0 + 16 * m + li;
-            A[m][ks] = (!walker && m < MT && c < C) ? s_prob[c * 64 + ctx] : 0.0;
-        }
-#pragma unroll
-        for (int q = 0; q < NQA; ++q) {
-            const int64_t c = c0 + 16 * MT + 4 * q + (lane & 3);
-            Aq[q][ks] = (!walker && q < NQ && c < C) ? s_prob[c * 64 + ctx] : 0.0;
-        }
-    }
+    load_cohort_operands<MT, NQ>(A, Aq, s_prob, c0, C, lane, !walker);
 
     // ---- walker state: region i (d_cur), i + 1 (d_nxt: its words travel during the walk of i), i + 2 (raw: chromosome, start, end) ----
     const int ht = tid - 256, hw = wave - 4;
@@ -636,24 +548,16 @@ __global__ __launch_bounds__(kTsBlock, 1) void base_tile_probs_roles_kernel(
     TileRegion d_cur = {0, 0, 0}, d_nxt = {0, 0, 0};
     int raw_chrom = 0;
     int64_t raw_start = 0, raw_end = 0;
-    auto words_of = [&](const TileRegion& d, int64_t& w0, int& nw, int& n_cov) {
-        n_cov = (int)(d.n_pos < tiled ? d.n_pos : tiled);
-        const int64_t ga = d.g0 - 1;
-        w0 = (ga >> 3) + 1;
-        nw = (int)(((ga + n_cov + 1) >> 3) + 1 - w0 + 1);
-    };
+    auto window_of = [&](const TileRegion& d) { return tile_window(d.g0, (int)(d.n_pos < tiled ? d.n_pos : tiled)); };     // of its tiled positions
     if (walker && n_my > 0) {
         const int64_t r0 = region_index(0), r1 = region_index(1), r2 = region_index(2);
         const int ch0 = reg_chrom[r0], ch1 = reg_chrom[r1];
-        d_cur = tile_region_of(chrom_len[ch0], chrom_off[ch0], reg_start[r0], reg_end[r0]);
-        d_nxt = tile_region_of(chrom_len[ch1], chrom_off[ch1], reg_start[r1], reg_end[r1]);
+        d_cur = tile_region(chrom_off, chrom_len, ch0, reg_start[r0], reg_end[r0]);
+        d_nxt = tile_region(chrom_off, chrom_len, ch1, reg_start[r1], reg_end[r1]);
         raw_chrom = reg_chrom[r2];
         raw_start = reg_start[r2];
         raw_end = reg_end[r2];
-        int64_t w0;
-        int nw, n_cov;
-        words_of(d_cur, w0, nw, n_cov);
-        stage_words<256>(s_words[0], words, n_words, w0, nw, ht);
+        tile_stage(s_words[0], words, n_words, window_of(d_cur), ht);
     }
     __syncthreads();
 
@@ -663,16 +567,10 @@ __global__ __launch_bounds__(kTsBlock, 1) void base_tile_probs_roles_kernel(
             if (i < n_my) {
                 const int64_t r = blockIdx.x + i * gridDim.x;
                 // the next region's packed words: loads now, LDS writes behind the walk
-                uint32_t wreg[kTsPer];
-                int64_t w0n;
-                int nwn, n_cov_n;
-                words_of(d_nxt, w0n, nwn, n_cov_n);
-                if (i + 1 >= n_my) nwn = 0;
-#pragma unroll
-                for (int j = 0; j < kTsPer; ++j) {
-                    const int64_t k = ht + (int64_t)j * 256;
-                    wreg[j] = k < nwn ? __builtin_nontemporal_load(&words[(w0n + k < n_words ? w0n + k : n_words - 1)]) : 0u;
-                }
+                uint32_t wreg[kTilePer];
+                WordWindow wn = window_of(d_nxt);
+                if (i + 1 >= n_my) wn.nw = 0;
+                stage_load<kTilePer, kTileBlock, true>(wreg, words, n_words, wn.w0, wn.nw, ht);
                 // the description of region i + 2 (its chromosome's row) and the raw row of region i + 3
                 const int64_t len2 = chrom_len[raw_chrom], off2 = chrom_off[raw_chrom];
                 const int64_t r3 = region_index(i + 3);
@@ -695,9 +593,7 @@ __global__ __launch_bounds__(kTsBlock, 1) void base_tile_probs_roles_kernel(
                     for (int k = 0; k < 8; ++k) z[((lane >> 3) + 8 * k) * (kTmStride32 / 4)] = make_uint4(0u, 0u, 0u, 0u);
                 }
                 __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                const int64_t ga = reg.g0 - 1;
-                const int64_t g_lds0 = (((ga >> 3) + 1) - 1) << 3;
-                tile_histograms(s_words[b], hist, ht, nv, binsize, n_cov, (int)(ga - g_lds0) + 1);
+                tile_histograms(s_words[b], hist, ht, nv, binsize, n_cov, (int)(reg.g0 - tile_window(reg.g0, n_cov).g_lds0));
                 __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
                 {   // this wave's share of H: lane = histogram row
                     const uint4* rowp = reinterpret_cast<const uint4*>(hist + lane * kTmStride32 + 32 * hw);
@@ -719,13 +615,9 @@ __global__ __launch_bounds__(kTsBlock, 1) void base_tile_probs_roles_kernel(
                     }
                 }
                 // the next region's words (the buffer was last read in iteration i - 1)
-#pragma unroll
-                for (int j = 0; j < kTsPer; ++j) {
-                    const int k = ht + j * 256;
-                    if (k < nwn) s_words[b ^ 1][k] = wreg[j];
-                }
+                stage_store<kTilePer, kTileBlock>(s_words[b ^ 1], wreg, wn.nw, ht);
                 d_cur = d_nxt;
-                d_nxt = tile_region_of(len2, off2, raw_start, raw_end);
+                d_nxt = region_positions(1, len2, off2, raw_start, raw_end);
                 raw_chrom = ch3;
                 raw_start = st3;
                 raw_end = en3;
@@ -829,24 +721,22 @@ struct CtxRaw {                           // a region as handed in
     int chrom;
     int64_t start, end;
 };
-struct CtxRegion {                        // wave-uniform description of a region
-    int64_t first, n_pos, g0, tiles_valid, w0, nw;
+struct CtxRegion : TileRegion {           // wave-uniform description of a region
+    int64_t tiles_valid, w0, nw;
     bool too_long;
 };
+constexpr int kCtxMarginWords = 2;        // the code loop forms eight positions from three words, whatever is left of the region
 
 template <int U>
 __device__ __forceinline__ CtxRegion ctx_region(const CtxRaw& a, int64_t len, int64_t off, int binsize)
 {
     CtxRegion q;
-    q.first = a.start == 0 ? U : a.start;
-    const int64_t stop = a.end < len - U ? a.end : len - U;
-    q.n_pos = stop > q.first ? stop - q.first : 0;
-    q.g0 = off + q.first;
+    static_cast<TileRegion&>(q) = region_positions(U, len, off, a.start, a.end);
     q.tiles_valid = (q.n_pos + binsize - 1) / binsize;
     q.too_long = q.n_pos > kCtxMaxPos;
-    const int64_t ga0 = q.g0 - U;                     // leftmost base of the first window
-    q.w0 = (ga0 >> 3) + 1;                            // array word = genome word + 1 (leading pad word)
-    q.nw = (q.n_pos > 0 && !q.too_long) ? ((ga0 + q.n_pos + 2 * U - 1) >> 3) + 1 - q.w0 + 3 : 0;
+    const WordWindow v = word_window(q.g0 - U, q.n_pos + 2 * U);      // from the leftmost base of the first window on
+    q.w0 = v.w0;
+    q.nw = (q.n_pos > 0 && !q.too_long) ? v.nw + kCtxMarginWords : 0;
     return q;
 }
 
@@ -875,11 +765,7 @@ __global__ __launch_bounds__(kCtxBlock) void base_tile_probs_ctx_kernel(
     // still.  (A load per position inside the code loop was a memory round trip per iteration: 20 us per region and pass, the
     // whole of the first build's 14.7 ms; words fetched when the region is reached: 2 us of every 11.)
     auto request = [&](const CtxRegion& q, uint32_t (&tmp)[kCtxWordsPer]) {
-#pragma unroll
-        for (int j = 0; j < kCtxWordsPer; ++j) {
-            const int64_t i = tid + (int64_t)j * kCtxBlock;
-            tmp[j] = i < q.nw ? words[(q.w0 + i < n_words ? q.w0 + i : n_words - 1)] : 0u;
-        }
+        stage_load<kCtxWordsPer, kCtxBlock>(tmp, words, n_words, q.w0, q.nw, tid);
     };
     auto raw_of = [&](int64_t r) {
         CtxRaw a{0, 0, 0};
@@ -935,11 +821,7 @@ __global__ __launch_bounds__(kCtxBlock) void base_tile_probs_ctx_kernel(
                 off1 = chrom_off[raw1.chrom];
             }
             __syncthreads();                          // the previous region's walkers are done with s_code / s_sum (and the table is staged)
-#pragma unroll
-            for (int j = 0; j < kCtxWordsPer; ++j) {
-                const int64_t i = tid + (int64_t)j * kCtxBlock;
-                if (i < q.nw) s_words[i] = staged[j];
-            }
+            stage_store<kCtxWordsPer, kCtxBlock>(s_words, staged, q.nw, tid);
             __syncthreads();
             // ---- context codes: a thread forms the codes of EIGHT consecutive positions from three words and stores them
             // as one 16-byte piece.  The sixteen nibbles from the first window's leftmost base on are squeezed to sixteen
@@ -1147,64 +1029,36 @@ int dig_base_tile_probs(const uint32_t* genome_words, int64_t n_words, const int
                         const double* s_prob, int64_t C, int binsize, int64_t n_tiles, double* pt, int64_t* first_pos,
                         int32_t* n_valid, void* stream)
 {
-    DIG_REQUIRE(R >= 0 && C >= 0 && n_words >= 2 && n_chrom >= 0 && n_tiles >= 0, "non-negative sizes, n_words >= 2 (pad words)");
-    DIG_REQUIRE(binsize >= 1, "binsize >= 1");
+    const TileArgs a{genome_words, n_words, chrom_off, chrom_len, reg_chrom, reg_start, reg_end, R, s_prob, C, binsize, n_tiles,
+                     pt, first_pos, n_valid, (hipStream_t)stream};
+    if (const int rc = check_tile_args(__func__, a, n_chrom)) return rc;
     if (R == 0) return DIG_OK;
-    DIG_REQUIRE(genome_words && chrom_off && chrom_len && reg_chrom && reg_start && reg_end && first_pos && n_valid,
-                "non-null pointers");
-    DIG_REQUIRE(C == 0 || n_tiles == 0 || (s_prob && pt), "s_prob and pt");
-    DIG_REQUIRE(binsize <= (kTileMaxWords - 1) * 8, "binsize at most 12 280 positions");
-    const bool mfma = binsize >= 2 && n_tiles >= 1 && n_tiles <= kTileBlock && C >= 1 &&
-                      n_tiles * binsize <= (int64_t)(kTileMaxWords - 1) * 8;
+    DIG_REQUIRE(binsize <= kTilePassPos, "binsize at most 12 280 positions");
+    const bool mfma = binsize >= 2 && n_tiles >= 1 && n_tiles <= kTileBlock && C >= 1 && n_tiles * binsize <= kTilePassPos;
     if (mfma) {
         // Which matrix kernel: the two-role one for a chunk of two or more cohort tiles (32 cohorts and up: 1.28 -> 1.22 ms at
         // 37, 1.41 -> 1.34 at 48), the one-role one below that (its two workgroups per CU walk twice as fast when the product
-        // is short: 0.93 against 0.95 ms at 21 cohorts, 0.60 against 0.69 at 5).  DIG_TILES_FORM = "one-role" / "two-role"
-        // (developer switch) forces either.
-        static const int forced = []() {
-            const char* e = getenv("DIG_TILES_FORM");
-            return e && e[0] == 'o' ? 1 : (e && e[0] == 't' ? 2 : 0);
-        }();
+        // is short: 0.93 against 0.95 ms at 21 cohorts, 0.60 against 0.69 at 5), unless DIG_TILES_FORM forces either.
+        const TilesForm form = tiles_form();
         for (int64_t c0 = 0; c0 < C; c0 += kTmChunk) {
-            // the chunk's cohorts as full tiles + quads: a remainder of 1 .. 4 is one quad, 5 .. 8 two, 9 and more a (padded) tile.
-            const int rem = (int)(C - c0 < kTmChunk ? C - c0 : kTmChunk);
-            int mt = rem >> 4, nq = 0;
-            const int r16 = rem & 15;
-            if (r16 >= 9) mt += 1;
-            else nq = (r16 + 3) >> 2;
-            const bool one_role = forced ? forced == 1 : mt < 2;
-            const int grid = one_role ? grid_for(R * kTileBlock, kTileBlock, kTmOcc) : grid_for(R * kTsBlock, kTsBlock, 1);
-            auto go = [&](auto kern, auto kern_roles) {
+            const ChunkCut cut = chunk_cut((int)C, (int)(c0 / kTmChunk));
+            const bool one_role = form == TilesForm::kOneRole || (form != TilesForm::kTwoRole && cut.nt < 2);
+            const int rc = dispatch_cut(cut, [&](auto nt, auto nq) {
                 if (one_role)
-                    hipLaunchKernelGGL(kern, dim3(grid), dim3(kTileBlock), 0, (hipStream_t)stream, genome_words, n_words, chrom_off,
-                                       chrom_len, reg_chrom, reg_start, reg_end, R, s_prob, C, (int)c0, binsize, (int)n_tiles, pt,
-                                       first_pos, n_valid);
+                    a.launch(base_tile_probs_mfma_kernel<nt.value, nq.value>, grid_for(R * kTileBlock, kTileBlock, kTmOcc), kTileBlock, C,
+                             (int)c0, binsize, (int)n_tiles)();
                 else
-                    hipLaunchKernelGGL(kern_roles, dim3(grid), dim3(kTsBlock), 0, (hipStream_t)stream, genome_words, n_words,
-                                       chrom_off, chrom_len, reg_chrom, reg_start, reg_end, R, s_prob, C, (int)c0, binsize,
-                                       (int)n_tiles, pt, first_pos, n_valid);
-            };
-            auto pick = [&](auto mt_c) {
-                constexpr int M = decltype(mt_c)::value;
-                if (nq == 2) go(base_tile_probs_mfma_kernel<M, 2>, base_tile_probs_roles_kernel<M, 2>);
-                else if (nq == 1) go(base_tile_probs_mfma_kernel<M, 1>, base_tile_probs_roles_kernel<M, 1>);
-                else if constexpr (M > 0) go(base_tile_probs_mfma_kernel<M, 0>, base_tile_probs_roles_kernel<M, 0>);
-            };
-            if (mt == 3) go(base_tile_probs_mfma_kernel<3, 0>, base_tile_probs_roles_kernel<3, 0>);
-            else if (mt == 2) pick(std::integral_constant<int, 2>{});
-            else if (mt == 1) pick(std::integral_constant<int, 1>{});
-            else pick(std::integral_constant<int, 0>{});
+                    a.launch(base_tile_probs_roles_kernel<nt.value, nq.value>, grid_for(R * kTsBlock, kTsBlock, 1), kTsBlock, C, (int)c0,
+                             binsize, (int)n_tiles)();
+                return DIG_OK;
+            });
+            if (rc) return rc;
         }
-        DIG_HIP_TRY(hipGetLastError());
-        return DIG_OK;
+    } else {
+        const int grid = grid_for(R * kTileBlock, kTileBlock, 4);
+        if (binsize == 1) a.launch(base_tile_probs_kernel<true>, grid, kTileBlock, C, binsize, n_tiles)();
+        else a.launch(base_tile_probs_kernel<false>, grid, kTileBlock, C, binsize, n_tiles)();
     }
-    const int grid = grid_for(R * kTileBlock, kTileBlock, 4);
-    if (binsize == 1)
-        hipLaunchKernelGGL((base_tile_probs_kernel<true>), dim3(grid), dim3(kTileBlock), 0, (hipStream_t)stream, genome_words, n_words,
-                           chrom_off, chrom_len, reg_chrom, reg_start, reg_end, R, s_prob, C, binsize, n_tiles, pt, first_pos, n_valid);
-    else
-        hipLaunchKernelGGL((base_tile_probs_kernel<false>), dim3(grid), dim3(kTileBlock), 0, (hipStream_t)stream, genome_words, n_words,
-                           chrom_off, chrom_len, reg_chrom, reg_start, reg_end, R, s_prob, C, binsize, n_tiles, pt, first_pos, n_valid);
     DIG_HIP_TRY(hipGetLastError());
     return DIG_OK;
 }
@@ -1215,38 +1069,23 @@ int dig_base_tile_probs_ctx(const uint32_t* genome_words, int64_t n_words, const
                             int32_t* n_valid, void* stream)
 {
     DIG_REQUIRE(n_up == 1 || n_up == 2, "n_up = n_down = 1 (trinucleotide) or 2 (penta-nucleotide)");
-    // developer switches: DIG_TILES_FORM = "general": the general kernel for every region, n_up = 1 too; "rows": the row walk for
-    // n_up = 1 too (both cross-check the trinucleotide kernels)
-    static const int form = []() {
-        const char* e = getenv("DIG_TILES_FORM");
-        return e && e[0] == 'g' ? 1 : (e && e[0] == 'r' ? 2 : 0);
-    }();
-    if (n_up == 1 && form == 0)
+    const TilesForm form = tiles_form();
+    if (n_up == 1 && form != TilesForm::kGeneral && form != TilesForm::kRows)
         return dig_base_tile_probs(genome_words, n_words, chrom_off, chrom_len, n_chrom, reg_chrom, reg_start, reg_end, R, s_prob, C,
                                    binsize, n_tiles, pt, first_pos, n_valid, stream);
-    DIG_REQUIRE(R >= 0 && C >= 0 && n_words >= 2 && n_chrom >= 0 && n_tiles >= 0, "non-negative sizes, n_words >= 2 (pad words)");
-    DIG_REQUIRE(binsize >= 1, "binsize >= 1");
+    const TileArgs a{genome_words, n_words, chrom_off, chrom_len, reg_chrom, reg_start, reg_end, R, s_prob, C, binsize, n_tiles,
+                     pt, first_pos, n_valid, (hipStream_t)stream};
+    if (const int rc = check_tile_args(__func__, a, n_chrom)) return rc;
     if (R == 0) return DIG_OK;
-    DIG_REQUIRE(genome_words && chrom_off && chrom_len && reg_chrom && reg_start && reg_end && first_pos && n_valid, "non-null pointers");
-    DIG_REQUIRE(C == 0 || n_tiles == 0 || (s_prob && pt), "s_prob and pt");
     // The row walk (dig_tiles_rows.hip) takes every region its LDS budget covers and marks the others n_valid = -2; the general
     // kernel behind it takes those (a region of more than kCtxMaxPos positions is not evaluated -- n_valid -1, pt NaN; the host
     // wrappers, which know the coordinates, refuse such regions before the launch).
-    const int only_deferred = form == 1 ? 0 : 1;
-    if (only_deferred) {
-        const int rc = launch_tile_probs_rows(genome_words, n_words, chrom_off, chrom_len, reg_chrom, reg_start, reg_end, R, s_prob, C, n_up,
-                                              binsize, n_tiles, pt, first_pos, n_valid, (hipStream_t)stream);
-        if (rc != DIG_OK) return rc;
-    }
+    const int only_deferred = form == TilesForm::kGeneral ? 0 : 1;
+    if (only_deferred)
+        if (const int rc = launch_tile_probs_rows(a, n_up)) return rc;
     const int grid = grid_for(R * kCtxBlock, kCtxBlock, 1);
-    if (n_up == 1)
-        hipLaunchKernelGGL((base_tile_probs_ctx_kernel<1>), dim3(grid), dim3(kCtxBlock), 0, (hipStream_t)stream, genome_words, n_words,
-                           chrom_off, chrom_len, reg_chrom, reg_start, reg_end, R, s_prob, C, binsize, n_tiles, pt, first_pos, n_valid,
-                           only_deferred);
-    else
-        hipLaunchKernelGGL((base_tile_probs_ctx_kernel<2>), dim3(grid), dim3(kCtxBlock), 0, (hipStream_t)stream, genome_words, n_words,
-                           chrom_off, chrom_len, reg_chrom, reg_start, reg_end, R, s_prob, C, binsize, n_tiles, pt, first_pos, n_valid,
-                           only_deferred);
+    if (n_up == 1) a.launch(base_tile_probs_ctx_kernel<1>, grid, kCtxBlock, C, binsize, n_tiles)(only_deferred);
+    else a.launch(base_tile_probs_ctx_kernel<2>, grid, kCtxBlock, C, binsize, n_tiles)(only_deferred);
     DIG_HIP_TRY(hipGetLastError());
     return DIG_OK;
 }

@@ -26,20 +26,19 @@
 // Sum order: a tile's positions in order (as the general kernel); the region total = the tile sums added lane-strided, then a
 // butterfly: pt differs from the general kernel's by an ulp of the total (1e-16 relative), from the reference's
 // normalise-then-sum by a few ulp (tests: 1e-12).
-#include <stdlib.h>
-
-#include <type_traits>
-
-#include "dig_common.hpp"
+// A region's positions, the packed-word window, the clamped word load, the nibble squeezes and the host-side argument block
+// and launch helper are those of the other tile kernels: dig_tiles.hpp.
+#include "dig_tiles.hpp"
 
 namespace dig {
 
 constexpr int kRwMaxPos = 10240;                       // positions of a region whose bases are staged
-constexpr int kRwEntries = (kRwMaxPos + 7 + 4 + 15) / 16 + 3;       // 16-base entries {bases, flags}; + 2 read past the end (a window = three words), + 1 spare
+constexpr int kRwMarginEntries = 2;                    // a window is read as three entries from any of the region's on: two past the last
+constexpr int kRwEntries = (kRwMaxPos + 7 + 4 + 15) / 16 + kRwMarginEntries + 1;       // 16-base entries {bases, flags}; + 1 spare
 constexpr int kRwLds = 163840;                         // bytes of LDS per CU
 
-struct RwRegion {                                      // wave-uniform description of a region
-    int64_t first, n_pos, g0, tiles_valid, w0;
+struct RwRegion : TileRegion {                         // wave-uniform description of a region
+    int64_t tiles_valid, w0;
     int ne, sh0;
     bool deferred;
 };
@@ -49,10 +48,7 @@ __device__ __forceinline__ RwRegion rw_region(int chrom, int64_t start, int64_t 
                                               int cap_tiles)
 {
     RwRegion q;
-    q.first = start == 0 ? U : start;
-    const int64_t stop = end < len - U ? end : len - U;
-    q.n_pos = stop > q.first ? stop - q.first : 0;
-    q.g0 = off + q.first;
+    static_cast<TileRegion&>(q) = region_positions(U, len, off, start, end);
     // tiles of the region, without a 64-bit division (a hundred and fifty scalar instructions per wave and region on the CU's one
     // scalar unit): bin_magic = ceil(2^32 / binsize), exact while (n_pos + binsize) binsize < 2^32; only regions that fit matter
     q.tiles_valid = 0;
@@ -62,9 +58,10 @@ __device__ __forceinline__ RwRegion rw_region(int chrom, int64_t start, int64_t 
     }
     q.deferred = q.n_pos > kRwMaxPos || q.tiles_valid > cap_tiles;
     const int64_t ga0 = q.g0 - U;                      // leftmost base of the first window
-    q.w0 = (ga0 >> 3) + 1;                             // array word = genome word + 1 (leading pad word)
-    q.sh0 = (int)(ga0 & 7);
-    q.ne = (q.n_pos > 0 && !q.deferred) ? (int)((q.sh0 + q.n_pos + 2 * U - 1) >> 4) + 3 : 0;
+    const WordWindow v = word_window(ga0, q.n_pos + 2 * U);
+    q.w0 = v.w0;
+    q.sh0 = v.sh;
+    q.ne = (q.n_pos > 0 && !q.deferred) ? (int)((v.sh + q.n_pos + 2 * U - 1) >> 4) + 1 + kRwMarginEntries : 0;      // an entry = two words from w0 on
     return q;
 }
 
@@ -72,21 +69,9 @@ __device__ __forceinline__ RwRegion rw_region(int chrom, int64_t start, int64_t 
 // bits of a base exchanged (v_bfrev); flags: bit 31 - k set when base k is not A, C, G or T}
 __device__ __forceinline__ uint2 rw_entry(uint32_t wa, uint32_t wb)
 {
-    auto squeeze = [](uint32_t w) {
-        uint32_t x = w & 0x33333333u;
-        x = (x | (x >> 2)) & 0x0F0F0F0Fu;
-        x = (x | (x >> 4)) & 0x00FF00FFu;
-        return (x | (x >> 8)) & 0xFFFFu;
-    };
-    auto flags = [](uint32_t w) {
-        uint32_t f = ((w >> 2) | (w >> 3)) & 0x11111111u;
-        f = (f | (f >> 3)) & 0x03030303u;
-        f = (f | (f >> 6)) & 0x000F000Fu;
-        return (f | (f >> 12)) & 0xFFu;
-    };
-    const uint32_t z = squeeze(wa) | (squeeze(wb) << 16);
+    const uint32_t z = squeeze_bases(wa) | (squeeze_bases(wb) << 16);
     uint32_t f = 0u;
-    if ((wa | wb) & 0xCCCCCCCCu) f = __builtin_bitreverse32(flags(wa) | (flags(wb) << 8));       // (rare: most words skip it)
+    if ((wa | wb) & 0xCCCCCCCCu) f = __builtin_bitreverse32(nonacgt_flags(wa) | (nonacgt_flags(wb) << 8));       // (rare: most words skip it)
     return make_uint2(__builtin_bitreverse32(z), f);
 }
 
@@ -201,8 +186,8 @@ __global__ __launch_bounds__(1024) void base_tile_probs_rows_kernel(
             wq[2 * j] = 0u, wq[2 * j + 1] = 0u;
             if (e < q.ne) {
                 const int64_t i = q.w0 + 2 * (int64_t)e;
-                wq[2 * j] = words[i < n_words ? i : n_words - 1];
-                wq[2 * j + 1] = words[i + 1 < n_words ? i + 1 : n_words - 1];
+                wq[2 * j] = load_word(words, n_words, i);
+                wq[2 * j + 1] = load_word(words, n_words, i + 1);
             }
         }
     };
@@ -409,24 +394,11 @@ __global__ __launch_bounds__(1024) void base_tile_probs_rows_kernel(
     }
 }
 
-template <int U, int LW, int TP>
-static void launch_rows(int grid, int block, hipStream_t stream, const uint32_t* words, int64_t n_words,
-                        const int64_t* chrom_off, const int64_t* chrom_len, const int32_t* reg_chrom, const int64_t* reg_start,
-                        const int64_t* reg_end, int64_t R, const double* s_prob, int c0, int cc, int binsize, int64_t n_tiles, double* pt,
-                        int64_t* first_pos, int32_t* n_valid, int write_meta)
-{
-    const unsigned bin_magic = binsize >= 2 ? (unsigned)(((1ull << 32) + (unsigned)binsize - 1) / (unsigned)binsize) : 0u;
-    hipLaunchKernelGGL((base_tile_probs_rows_kernel<U, LW, TP, true>), dim3(grid), dim3(block), 0, stream, words, n_words, chrom_off,
-                       chrom_len, reg_chrom, reg_start, reg_end, R, s_prob, c0, cc, binsize, bin_magic, n_tiles, pt, first_pos, n_valid, write_meta);
-}
-
 // The passes of one call: sixteen cohorts while more than eight are left, then one pass of eight (4-lane walkers) or four
 // (2-lane walkers).  Every pass is a launch of its own (its table is staged once per workgroup).
-int launch_tile_probs_rows(const uint32_t* words, int64_t n_words, const int64_t* chrom_off, const int64_t* chrom_len,
-                           const int32_t* reg_chrom, const int64_t* reg_start, const int64_t* reg_end, int64_t R, const double* s_prob,
-                           int64_t C, int n_up, int binsize, int64_t n_tiles, double* pt, int64_t* first_pos, int32_t* n_valid,
-                           hipStream_t stream)
+int launch_tile_probs_rows(const TileArgs& a, int n_up)
 {
+    const int binsize = a.binsize;
     // positions per trip: the one that wastes the fewest slots of a tile's last trip (ties: the longer trip)
     int tp = 12;
     {
@@ -437,37 +409,24 @@ int launch_tile_probs_rows(const uint32_t* words, int64_t n_words, const int64_t
             if (best < 0 || waste < best) best = waste, tp = cand[k];
         }
     }
-    const int grid = grid_for(R * 1024, 1024, 1);
+    const unsigned bin_magic = binsize >= 2 ? (unsigned)(((1ull << 32) + (unsigned)binsize - 1) / (unsigned)binsize) : 0u;
+    const int grid = grid_for(a.R * 1024, 1024, 1);
+    // waves per workgroup (tiles are dealt by tickets: more waves hide more latency, and a wave = a cohort in the output phase)
+    const int n_waves = 16;
     int c0 = 0;
     bool first = true;
-    while (c0 < C || first) {
-        const int left = (int)(C - c0);
+    while (c0 < a.C || first) {
+        const int left = (int)(a.C - c0);
         const int lw = left > 8 ? 8 : (left > 4 ? 4 : 2);
         const int cc = left < 2 * lw ? left : 2 * lw;
-        // waves per workgroup (tiles are dealt by tickets: more waves hide more latency, and a wave = a cohort in the output phase)
-        const int n_waves = 16;
-        auto go = [&](auto u_c, auto lw_c) {
-            constexpr int UU = decltype(u_c)::value, LL = decltype(lw_c)::value;
-            if (tp == 25)
-                launch_rows<UU, LL, 25>(grid, 64 * n_waves, stream, words, n_words, chrom_off, chrom_len, reg_chrom, reg_start, reg_end,
-                                        R, s_prob, c0, cc, binsize, n_tiles, pt, first_pos, n_valid, first ? 1 : 0);
-            else if (tp == 12)
-                launch_rows<UU, LL, 12>(grid, 64 * n_waves, stream, words, n_words, chrom_off, chrom_len, reg_chrom, reg_start, reg_end,
-                                        R, s_prob, c0, cc, binsize, n_tiles, pt, first_pos, n_valid, first ? 1 : 0);
-            else if (tp == 10)
-                launch_rows<UU, LL, 10>(grid, 64 * n_waves, stream, words, n_words, chrom_off, chrom_len, reg_chrom, reg_start, reg_end,
-                                        R, s_prob, c0, cc, binsize, n_tiles, pt, first_pos, n_valid, first ? 1 : 0);
-            else
-                launch_rows<UU, LL, 8>(grid, 64 * n_waves, stream, words, n_words, chrom_off, chrom_len, reg_chrom, reg_start, reg_end,
-                                       R, s_prob, c0, cc, binsize, n_tiles, pt, first_pos, n_valid, first ? 1 : 0);
-        };
-        auto go_u = [&](auto lw_c) {
-            if (n_up == 2) go(std::integral_constant<int, 2>{}, lw_c);
-            else go(std::integral_constant<int, 1>{}, lw_c);
-        };
-        if (lw == 8) go_u(std::integral_constant<int, 8>{});
-        else if (lw == 4) go_u(std::integral_constant<int, 4>{});
-        else go_u(std::integral_constant<int, 2>{});
+        dispatch_const<1, 2>(n_up, [&](auto u) {
+            dispatch_const<8, 4, 2>(lw, [&](auto l) {
+                dispatch_const<25, 12, 10, 8>(tp, [&](auto t) {
+                    a.launch(base_tile_probs_rows_kernel<u.value, l.value, t.value, true>, grid, 64 * n_waves, c0, cc, binsize, bin_magic,
+                             a.n_tiles)(first ? 1 : 0);
+                });
+            });
+        });
         c0 += cc;
         first = false;
         if (cc == 0) break;

@@ -341,13 +341,12 @@ def test_accumulate_tiled_and_genic_golden(torch_dev):
     assert np.array_equal(r["FLAG"][:, 0], v[:, col["FLAG"]].astype(np.int32))
 
 
-@pytest.mark.parametrize("C", [1, 5, 12, 20, 33, 37, 48, 64, 70, 104])
-def test_accumulate_vs_oracle_multi_cohort(torch_dev, C):
+def _accumulate_vs_oracle(torch_dev, C, E):
     import torch
     from bench import make_workload
     from digdriver_amd import engine
     from oracle import dig_oracle as O
-    w = make_workload(n_bins=900, n_elements=700, n_cohorts=C, seed=11 + C)
+    w = make_workload(n_bins=900, n_elements=E, n_cohorts=C, seed=11 + C)
     # a few ragged cases: an element with no overlapped bin and one with many
     w["ov_ptr"] = w["ov_ptr"].copy()
     td = {k: torch.as_tensor(v, device=torch_dev) for k, v in w.items() if isinstance(v, np.ndarray)}
@@ -373,6 +372,35 @@ def test_accumulate_vs_oracle_multi_cohort(torch_dev, C):
                                       w["ov_idx"], w["L"], w["strand_minus"], w["d_pr"])
     for name in got:
         assert np.array_equal(host[name], got[name].cpu().numpy(), equal_nan=True), name
+    return w, td, got, want
+
+
+@pytest.mark.parametrize("C", [1, 5, 12, 20, 33, 37, 48, 64, 70, 104])
+def test_accumulate_vs_oracle_multi_cohort(torch_dev, C):
+    _accumulate_vs_oracle(torch_dev, C, 700)
+
+
+@pytest.mark.parametrize("C", [1, 4, 5, 8, 9, 16, 17, 21, 24, 25, 32, 33, 37, 40, 41, 48, 49, 85])
+def test_accumulate_and_compact_pipeline_at_every_cohort_cut(torch_dev, C):
+    """All nine (tiles, quads) cuts of a 48-cohort chunk, and two chunks, through both dot kernels: dig_accumulate_elements
+    (acc_dot_mfma_kernel) as above, and the compact pipeline (acc_dot_ctx_kernel) against it with the comparison of
+    test_compact_pipeline_against_general_form_and_oracle.  E = 33: two full 16-row tiles and one row."""
+    import torch
+    from digdriver_amd import engine
+    w, td, got, want = _accumulate_vs_oracle(torch_dev, C, 33)
+    plan = engine.PipelinePlan(td["bin_mu"], td["bin_std"], td["bin_y"], td["bin_flag"], td["bin_ctx"], td["ov_ptr"], td["ov_idx"],
+                               td["L"], td["strand_minus"], td["d_pr"], td["obs_snv"], td["obs_samples"], td["obs_indel"])
+    assert plan.compact, "make_workload repeats every context count three times"
+    acc_c, _ = plan.run(td["cj"], td["cj_indel"])
+    torch.cuda.synchronize()
+    for k in ("MU", "SIGMA", "R_OBS", "FLAG", "R_SIZE", "ELT_SIZE", "P_INDEL"):
+        assert torch.equal(torch.nan_to_num(got[k].double(), nan=-7.0), torch.nan_to_num(acc_c[k].double(), nan=-7.0)), k
+    pg, pc = got["P"].cpu().numpy(), acc_c["P"].cpu().numpy()
+    assert (np.isnan(pg) == np.isnan(pc)).all()
+    ok = np.isfinite(pg)
+    assert np.array_equal(pc[~ok & ~np.isnan(pg)], pg[~ok & ~np.isnan(pg)])
+    assert (np.abs(pc[ok] / pg[ok] - 1) <= 1e-13).all()
+    rel_close(pc, want["P"], 1e-11)
 
 
 def test_scale_suffstats(torch_dev):
