@@ -20,6 +20,10 @@ DIG_REC_DOUBLES, DIG_REC_MU, DIG_REC_SIGMA, DIG_REC_ROBS_FLAG = 10, 7, 8, 9
 GENE_CLASSES = ("SYN", "MIS", "NONS", "SPL", "TRUNC", "NONSYN")
 GS_PLANES = tuple("EXP_" + c for c in GENE_CLASSES) + tuple("PVAL_%s_BURDEN" % c for c in GENE_CLASSES) + \
     tuple("PVAL_%s_BURDEN_SAMPLE" % c for c in GENE_CLASSES) + ("THETA_INDEL", "EXP_INDEL", "PVAL_INDEL_BURDEN", "PVAL_MUT_BURDEN")
+SEL_PLANES = ("T_SYN", "MRFOLD") + tuple("EXP_%s_ML" % c for c in GENE_CLASSES) + \
+    tuple("PVAL_%s_BURDEN_DNDS" % c for c in GENE_CLASSES) + tuple("PVAL_%s_SEL_NB" % c for c in ("SYN", "MIS", "TRUNC", "NONSYN")) + \
+    tuple("PVAL_%s_SEL_PG" % c for c in ("SYN", "MIS", "NONS", "NONSYN")) + tuple("SEL_" + c for c in GENE_CLASSES) + \
+    tuple("PVAL_%s_SEL" % c for c in GENE_CLASSES)
 ES_PLANES = ("EXP_SNV", "PVAL_SNV_BURDEN", "PVAL_SAMPLE_BURDEN", "THETA_INDEL", "EXP_INDEL",
              "PVAL_INDEL_BURDEN", "PVAL_MUT_BURDEN")
 
@@ -72,6 +76,8 @@ _SIGNATURES = {
     "dig_element_pipeline_host": [_vp] * 25 + [_i64, _i64, _i64, _int],
     "dig_gene_stats": [_vp, _vp, _vp, _vp, _vp, _int, _vp, _int, _vp, _vp, _vp, _vp, _int, _vp, _i64, _i64, _vp],
     "dig_gene_stats_host": [_vp, _vp, _vp, _vp, _vp, _int, _vp, _int, _vp, _vp, _vp, _vp, _int, _vp, _i64, _i64, _int],
+    "dig_gene_selection": [_vp, _vp, _vp, _int, _vp, _vp, _i64, _i64, _vp],
+    "dig_gene_selection_host": [_vp, _vp, _vp, _int, _vp, _vp, _i64, _i64, _int],
     "dig_gene_pipeline": [_vp] * 15 + [_int] + [_vp] * 9 + [_i64, _i64, _i64, _vp, _i64, _vp],
     "dig_gene_pipeline_host": [_vp] * 15 + [_int] + [_vp] * 9 + [_i64, _i64, _i64, _int],
     "dig_count_contexts": [_vp, _i64, _vp, _vp, _int, _vp, _vp, _vp, _vp, _i64, _vp, _vp],

@@ -268,6 +268,19 @@ int dig_gene_stats_host(const double* mu, const double* sigma, const double* mu_
                    G, C, nullptr);
 }
 
+int dig_gene_selection_host(const double* alpha, const double* theta, const double* pi, int n_pi, const int32_t* obs, double* out,
+                            int64_t G, int64_t C, int device)
+{
+    DIG_REQUIRE(G >= 0 && C >= 0, "G, C >= 0");
+    DIG_REQUIRE(n_pi == 4 || n_pi == 6, "n_pi: 4 or 6");
+    if (G == 0 || C == 0) return DIG_OK;
+    DIG_REQUIRE(alpha && theta && pi && obs && out, "non-null pointers");
+    const size_t nGC = (size_t)G * C;
+    Staging st(device);
+    return st.call(dig_gene_selection, st.in(alpha, nGC), st.in(theta, nGC), st.in(pi, nGC * n_pi), n_pi, st.in(obs, nGC * 5),
+                   st.out(out, nGC * DIG_SEL_NPLANES), G, C, nullptr);
+}
+
 int dig_scale_suffstats_host(const double* bin_mu, const uint8_t* bin_flag, int64_t N, int64_t C, double* out_sum, int device)
 {
     DIG_REQUIRE(N >= 0 && C >= 0, "N, C >= 0");

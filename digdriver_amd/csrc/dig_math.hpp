@@ -1087,6 +1087,22 @@ __device__ __forceinline__ double fisher_combine(double p1, double p2)
     return exp(-h) * (1.0 + h);
 }
 
+// scipy.stats.chi2.sf(x, df) for df = 1 and 2 (the likelihood-ratio tests of the gene route's selection block):
+// erfc(sqrt(x / 2)) and exp(-x / 2); x < 0 -> 1 as scipy, NaN -> NaN, +inf -> 0.
+__device__ __forceinline__ double chi2_sf1(double x)
+{
+    if (isnan(x)) return dnan();
+    if (x < 0.0) return 1.0;
+    return erfc(sqrt(0.5 * x));
+}
+
+__device__ __forceinline__ double chi2_sf2(double x)
+{
+    if (isnan(x)) return dnan();
+    if (x < 0.0) return 1.0;
+    return exp(-0.5 * x);
+}
+
 __device__ __forceinline__ double fisher_combine_fast(double p1, double p2)
 {
     const double q = p1 * p2;

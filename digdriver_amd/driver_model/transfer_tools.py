@@ -353,6 +353,97 @@ def combine_snv_indel(df_model, snv_col):
     return df_model
 
 
+# ---------------------------------------------------------------------------------------------
+# dN/dS correction and selection tests of the gene route (one launch each: dig_gene_selection)
+# ---------------------------------------------------------------------------------------------
+_SEL_NB_CLASSES = ('SYN', 'MIS', 'TRUNC', 'NONSYN')
+_SEL_PG_CLASSES = ('SYN', 'MIS', 'NONS', 'NONSYN')
+
+
+def _selection_planes(df_model):
+    """The 34 planes of engine.gene_selection (SEL_PLANES) for the frame's ALPHA, THETA, Pi_* and OBS_* columns, as vectors.
+    A missing column is a KeyError, before anything reaches the device."""
+    alpha, theta = _f64(df_model, 'ALPHA'), _f64(df_model, 'THETA')
+    pi = np.stack([_f64(df_model, 'Pi_' + c) for c in GENE_CLASSES], axis=1)
+    counts = [df_model['OBS_' + c].values for c in ('SYN', 'MIS', 'NONS', 'SPL')]
+    obs = np.stack(counts + [np.zeros(len(df_model))], axis=1).astype(np.int32)[:, :, None]
+    planes = engine.gene_selection(alpha, theta, pi, obs)
+    return {name: plane[:, 0] for name, plane in planes.items()}
+
+
+def _take(df_model, planes, names):
+    for name in names:
+        df_model[name] = planes[name]
+    return df_model
+
+
+def _expected_muts_dnds_columns(df_model, planes):
+    df_model = gene_expected_muts_nb(df_model)                                   # :367-372
+    return _take(df_model, planes, ['T_SYN', 'MRFOLD'] + ['EXP_%s_ML' % c for c in GENE_CLASSES])
+
+
+def gene_expected_muts_dnds(df_model):
+    """transfer_tools.py:363-392: EXP_c, the maximum-likelihood neutral rate T_SYN from the synonymous count (_mle_t), the
+    correction factor MRFOLD (_mrfold_factor) and the corrected expectations EXP_c_ML."""
+    return _expected_muts_dnds_columns(df_model, _selection_planes(df_model))
+
+
+def gene_pvalue_burden_dnds(df_model):
+    """transfer_tools.py:617-655: the six burden tests at the corrected expectations."""
+    return _take(df_model, _selection_planes(df_model), ['PVAL_%s_BURDEN_DNDS' % c for c in GENE_CLASSES])
+
+
+def gene_pvalue_sel_nb(df_model):
+    """transfer_tools.py:657-676: likelihood-ratio selection tests under the NB model (_llr_test_nb)."""
+    return _take(df_model, _selection_planes(df_model), ['PVAL_%s_SEL_NB' % c for c in _SEL_NB_CLASSES])
+
+
+def gene_pvalue_sel_gamma(df_model):
+    """transfer_tools.py:749-765: the Gamma-Poisson variant (_llr_test_gamma_poiss)."""
+    return _take(df_model, _selection_planes(df_model), ['PVAL_%s_SEL_PG' % c for c in _SEL_PG_CLASSES])
+
+
+def selection_coefficient(df_model, mut_type, pvalue=True):
+    """transfer_tools.py:1280-1292: observed over expected mutations of one class, SEL_<mut_type>, and the p-value of its
+    likelihood ratio, PVAL_<mut_type>_SEL."""
+    if mut_type not in GENE_CLASSES:
+        raise KeyError('OBS_{}'.format(mut_type))
+    names = ['SEL_' + mut_type] + (['PVAL_%s_SEL' % mut_type] if pvalue else [])
+    return _take(df_model, _selection_planes(df_model), names)
+
+
+def gene_selection_block(df_model, burden_dnds=True, sel=True):
+    """gene_expected_muts_dnds, gene_pvalue_burden_dnds and gene_pvalue_sel_nb as ONE launch: the same columns in the same
+    order, the same bits."""
+    planes = _selection_planes(df_model)
+    df_model = _expected_muts_dnds_columns(df_model, planes)
+    if burden_dnds:
+        _say("\tCalculating dnds-adjusted burden p-values")
+        df_model = _take(df_model, planes, ['PVAL_%s_BURDEN_DNDS' % c for c in GENE_CLASSES])
+    if sel:
+        _say("\tCalculating selection p-values")
+        df_model = _take(df_model, planes, ['PVAL_%s_SEL_NB' % c for c in _SEL_NB_CLASSES])
+    return df_model
+
+
+def _gene_selection_columns(df_model, selection, fused):
+    """The selection step of run_gene_model (the reference's commented-out sequence, :833-853); selection: None or
+    (burden_dnds, sel)."""
+    if selection is None:
+        return df_model
+    burden_dnds, sel = selection
+    if fused:
+        return gene_selection_block(df_model, burden_dnds=burden_dnds, sel=sel)
+    df_model = gene_expected_muts_dnds(df_model)
+    if burden_dnds:
+        _say("\tCalculating dnds-adjusted burden p-values")
+        df_model = gene_pvalue_burden_dnds(df_model)
+    if sel:
+        _say("\tCalculating selection p-values")
+        df_model = gene_pvalue_sel_nb(df_model)
+    return df_model
+
+
 def element_statistics_block(df_model, cj, cj_indel, skip_pvals=False):
     """The statistics block of run_element_region_model (transfer_tools.py:1069-1094) as ONE fused launch
     (dig_element_stats): EXP_SNV, both SNV tests and -- when the cohort has indels -- the indel test and the
@@ -375,12 +466,13 @@ def element_statistics_block(df_model, cj, cj_indel, skip_pvals=False):
     return df_model
 
 
-def gene_statistics_block(df_model, cj, indel=True, all_cosmic=None):
+def gene_statistics_block(df_model, cj, indel=True, all_cosmic=None, selection=None):
     """The statistics of the gene route -- gene_expected_muts_nb, gene_pvalue_burden_nb, gene_pvalue_burden_nb_by_sample,
     gene_pvalue_indel and the Fisher combination (transfer_tools.py:331-340,394-456,554-583,709-729,860-861) -- as ONE
     launch (dig_gene_stats) instead of four.  `df_model` comes from transfer_gene_model(..., cj) and `cj` is that same
     factor: the kernel forms theta = sigma^2 / mu * cj from MU / SIGMA with the IEEE operations that made the frame's
-    THETA column.  Same columns in the same order as the column-by-column route."""
+    THETA column.  Same columns in the same order as the column-by-column route.  selection: None or (burden_dnds, sel), the
+    columns of gene_selection_block between the burden and the indel columns (a second launch)."""
     with_indel = bool(indel and df_model.OBS_INDEL.sum() != 0)
     t_indel = None
     if with_indel:
@@ -398,6 +490,7 @@ def gene_statistics_block(df_model, cj, indel=True, all_cosmic=None):
     for pattern in ('PVAL_%s_BURDEN', 'PVAL_%s_BURDEN_SAMPLE'):
         for c in GENE_CLASSES:
             df_model[pattern % c] = planes[pattern % c][:, 0]
+    df_model = _gene_selection_columns(df_model, selection, fused=True)
     if with_indel:
         _say("\tCalculating indel burden p-values")
         for name in ('THETA_INDEL', 'EXP_INDEL', 'PVAL_INDEL_BURDEN', 'PVAL_MUT_BURDEN'):
@@ -405,18 +498,19 @@ def gene_statistics_block(df_model, cj, indel=True, all_cosmic=None):
     return df_model
 
 
-def _gene_statistics(df_model, burden=True, indel=True, all_cosmic=None, announce=True, fused_cj=None):
+def _gene_statistics(df_model, burden=True, indel=True, all_cosmic=None, announce=True, fused_cj=None, selection=None):
     """fused_cj: the cohort factor the frame was transferred with -> the one-launch form (gene_statistics_block); None: the
     reference's column-by-column sequence.  Same results (tests/test_gpu_host_mirror.py)."""
     if fused_cj is not None and burden:
         if announce:
             _say("\tCalculating burden p-values")
-        return gene_statistics_block(df_model, fused_cj, indel=indel, all_cosmic=all_cosmic)
+        return gene_statistics_block(df_model, fused_cj, indel=indel, all_cosmic=all_cosmic, selection=selection)
     df_model = gene_expected_muts_nb(df_model)
     if burden:
         if announce:
             _say("\tCalculating burden p-values")
         df_model = gene_pvalue_burden_nb_by_sample(gene_pvalue_burden_nb(df_model))
+    df_model = _gene_selection_columns(df_model, selection, fused=fused_cj is not None)
     if indel and df_model.OBS_INDEL.sum() != 0:
         _say("\tCalculating indel burden p-values")
         df_model = combine_snv_indel(gene_pvalue_indel(df_model, all_cosmic=all_cosmic), 'PVAL_TRUNC_BURDEN')
@@ -428,9 +522,12 @@ def _gene_statistics(df_model, burden=True, indel=True, all_cosmic=None, announc
 # ---------------------------------------------------------------------------------------------
 def run_gene_model(f_mut, f_h5_genemodel, scale_by_sample=False, pval_burden_nb=True, pval_burden_dnds=True,
                    pval_sel=True, max_muts_per_sample=3e9, max_muts_per_gene_per_sample=3e9, scale_factor=None,
-                   scale_by_expectation=True, cgc_genes=False, all_cosmic=None, fused=False):
+                   scale_by_expectation=True, cgc_genes=False, all_cosmic=None, fused=False, selection=False):
     """transfer_tools.py:789-874.  `fused=True` computes the whole statistics block with the single dig_gene_stats launch
-    (gene_statistics_block) instead of the reference's column-by-column sequence; same columns, same values."""
+    (gene_statistics_block) instead of the reference's column-by-column sequence; same columns, same values.
+    `selection=True` adds the step the reference's driver has commented out (:833-853): T_SYN, MRFOLD and EXP_*_ML, then
+    PVAL_*_BURDEN_DNDS if pval_burden_dnds and PVAL_*_SEL_NB if pval_sel, between the burden and the indel columns (the
+    reference has no live caller for them: its functions are the specification).  Without it the two flags do nothing."""
     run = CohortRun(f_mut, f_h5_genemodel)
     model, rows = run.gene_model(), run.coding_rows()
     if cgc_genes:
@@ -447,7 +544,8 @@ def run_gene_model(f_mut, f_h5_genemodel, scale_by_sample=False, pval_burden_nb=
         cj = run.ratio_scale(rows, 'sample' if scale_by_sample else 'exome')
     _say("\tScaling factor is: {}".format(cj))
     return _gene_statistics(transfer_gene_model(rows, counts, model, cj), burden=pval_burden_nb, all_cosmic=all_cosmic,
-                            fused_cj=cj if fused else None)
+                            fused_cj=cj if fused else None,
+                            selection=(bool(pval_burden_dnds), bool(pval_sel)) if selection else None)
 
 
 def run_target_model(f_mut, f_h5_genemodel, scale_by_sample=False, panel="MSK_341", max_muts_per_sample=3e9,

@@ -22,6 +22,7 @@ from ._marshal import backend_of, backend_on, device_backend, is_cuda, resolve_d
 
 ES_PLANES = _lib.ES_PLANES
 GS_PLANES = _lib.GS_PLANES
+SEL_PLANES = _lib.SEL_PLANES
 
 
 def _t(x, dtype, device):
@@ -132,6 +133,28 @@ def gene_stats(mu, sigma, pi, pi_indel, obs, n_samp, cj, t_indel=None, mu_indel=
     be.call("dig_gene_stats", p(mu), p(sigma), p(mu_indel), p(sigma_indel), p(pi), n_pi, p(pi_indel), per_cohort, p(obs), p(n_samp),
             p(cj), p(ti), int(ti is not None), p(out), G, C)
     return {name: out[i] for i, name in enumerate(GS_PLANES)}
+
+
+def gene_selection(alpha, theta, pi, obs, device=0, out=None):
+    """The gene route's dN/dS correction and selection tests (transfer_tools.py:363-392,617-676,749-765,1172-1292) for G genes x
+    C cohorts in ONE launch (dig_gene_selection).  alpha, theta f64 [G, C] (the frame's ALPHA and THETA: THETA already scaled);
+    pi f64 [G, 6 or 4, C] ([G, n_pi] for one cohort); obs i32 [G, 5, C] (SYN, MIS, NONS, SPL, INDEL; INDEL unused).
+    Returns dict plane name -> [G, C] (views of one [34, G, C] buffer, SEL_PLANES); CUDA tensors in -> CUDA tensors out."""
+    be = backend_of(alpha, device=device)
+    alpha = _cols(be.arr(alpha, "f64"))
+    G, C = alpha.shape
+    theta = be.arr(theta, "f64", (G, C))
+    pi = be.arr(pi, "f64")
+    if pi.ndim == 2:
+        pi = pi[:, :, None]
+    n_pi = pi.shape[1]
+    assert pi.shape == (G, n_pi, C) and n_pi in (4, 6)
+    obs = be.arr(obs, "i32", (G, 5, C))
+    if out is None:
+        out = be.empty((len(SEL_PLANES), G, C), "f64")
+    p = be.ptr
+    be.call("dig_gene_selection", p(alpha), p(theta), p(pi), n_pi, p(obs), p(out), G, C)
+    return {name: out[i] for i, name in enumerate(SEL_PLANES)}
 
 
 def gene_pipeline(bin_mu, bin_std, bin_y, bin_flag, bin_ctx, ov_ptr, ov_idx, L, strand_minus, gene_length, d_pr, obs, n_samp, cj,

@@ -286,6 +286,28 @@ int dig_gene_pipeline_host(const double *bin_mu, const double *bin_std, const in
                            double *SIGMA, int32_t *R_OBS, int32_t *FLAG, double *P, int32_t *R_SIZE, int32_t *ELT_SIZE,
                            double *P_INDEL, double *out, int64_t N, int64_t G, int64_t C, int device);
 
+/* ---- the gene route's dN/dS correction and selection tests as one launch (additive: the ABI version stays) --- *
+ * gene_expected_muts_dnds :363-392 (_mle_t, _mrfold_factor :1264-1277), gene_pvalue_burden_dnds :617-655, gene_pvalue_sel_nb
+ * :657-676 (_llr_test_nb :1172-1213), gene_pvalue_sel_gamma :749-765 (_llr_test_gamma_poiss :1215-1252) and
+ * selection_coefficient :1280-1292 of driver_model/transfer_tools.py, for G genes x C cohorts; classes as dig_gene_stats.
+ *   alpha, theta f64 [G, C]: the frame's ALPHA and THETA columns (THETA already scaled by the cohort factor);
+ *   pi f64 [G, n_pi, C], n_pi = 6 or 4 as dig_gene_stats; obs i32 [G, 5, C] = OBS_SYN, MIS, NONS, SPL, INDEL (INDEL unused).
+ *   out f64 [DIG_SEL_NPLANES = 34, G, C]:
+ *      0- 1  T_SYN, MRFOLD                     T_SYN = _mle_t(OBS_SYN, 1, ALPHA, THETA Pi_SYN), MRFOLD = max(1e-10, T_SYN / EXP_SYN)
+ *      2- 7  EXP_c_ML                          c = SYN, MIS, NONS, SPL, TRUNC, NONSYN: EXP_c MRFOLD
+ *      8-13  PVAL_c_BURDEN_DNDS                mid-p burden test at 1 / (EXP_c_ML / ALPHA + 1)
+ *     14-17  PVAL_{SYN,MIS,TRUNC,NONSYN}_SEL_NB   likelihood-ratio tests under the NB model (df 1, 1, 1, 2)
+ *     18-21  PVAL_{SYN,MIS,NONS,NONSYN}_SEL_PG    the same under the Gamma-Poisson model
+ *     22-27  SEL_c                             (OBS_c + 1e-16) / (EXP_c + 1e-16)
+ *     28-33  PVAL_c_SEL                        df 1 likelihood ratio between THETA Pi_c and THETA Pi_c SEL_c
+ *   Both maxima are Python's max(a, b) (a unless b > a): a NaN T_SYN / EXP_SYN gives MRFOLD = 1e-10.  Otherwise NaN in, NaN out,
+ *   and NaN wherever the reference's sums of log-likelihoods hold -inf on both sides. */
+#define DIG_SEL_NPLANES 34
+int dig_gene_selection(const double *alpha, const double *theta, const double *pi, int n_pi, const int32_t *obs, double *out,
+                       int64_t G, int64_t C, void *stream);
+int dig_gene_selection_host(const double *alpha, const double *theta, const double *pi, int n_pi, const int32_t *obs, double *out,
+                            int64_t G, int64_t C, int device);
+
 /* ---- sufficient statistics in canonical chunks (bin-sharded runs) --------------------------- *
  * Same quantity as dig_scale_suffstats / dig_scale_factors, defined so that it does not depend on the sharding: the bins
  * are cut into K canonical chunks of the GLOBAL grid (boundaries floor(N j / K)); a rank computes the chunk sums of the

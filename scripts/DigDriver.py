@@ -40,7 +40,7 @@ def cmd_gene(args):
         args.fmut, args.model, scale_by_sample=args.scale_by_samples, pval_burden_nb=args.pval_burden,
         max_muts_per_sample=args.max_muts_per_sample, max_muts_per_gene_per_sample=args.max_muts_per_gene_per_sample,
         scale_factor=args.scale_factor_manual, scale_by_expectation=args.scale_by_expectation, cgc_genes=args.cgc_genes,
-        fused=True)
+        fused=True, selection=args.selection, pval_burden_dnds=args.pval_burden_dnds, pval_sel=args.pval_sel)
     write_results(res, args)
 
 
@@ -134,6 +134,12 @@ def parse_args(text=None):
     g.add_argument('--cgc-genes', choices=CGC_SETS, default=False, help='restrict to a Cancer Gene Census set')
     g.add_argument('--no-pval-burden', dest='pval_burden', action='store_false', default=True,
                    help='skip the burden p-values')
+    g.add_argument('--selection', action='store_true', default=False,
+                   help='add the dN/dS-corrected expectations, their burden p-values and the selection p-values')
+    g.add_argument('--no-pval-burden-dnds', dest='pval_burden_dnds', action='store_false', default=True,
+                   help='with --selection: skip the dN/dS-corrected burden p-values')
+    g.add_argument('--no-pval-sel', dest='pval_sel', action='store_false', default=True,
+                   help='with --selection: skip the selection p-values')
     g.set_defaults(func=cmd_gene)
 
     t = _common(sub.add_parser('targetDriver', help='test the genes of a targeted sequencing panel'), False)
