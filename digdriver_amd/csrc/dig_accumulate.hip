@@ -648,8 +648,10 @@ __global__ __launch_bounds__(256) void compact_L_kernel(const int32_t* __restric
     if (__any(bad) && (threadIdx.x & 63) == 0) atomicOr(mismatch, 1);
 }
 
+// At most 160 vector registers (amdgpu_num_vgpr counts in units of two on the unified register file of gfx90a and later: 80 -> 160),
+// no scratch in any instantiation: three waves per SIMD leave room for one 32-register wave of the scale factors' background kernels.
 template <int NT, int NQ>
-__global__ __launch_bounds__(kCtxWaves * 64) void acc_dot_ctx_kernel(
+__global__ __launch_bounds__(kCtxWaves * 64) __attribute__((amdgpu_waves_per_eu(3, 3), amdgpu_num_vgpr(80))) void acc_dot_ctx_kernel(
     const int32_t* __restrict__ bin_ctx, const int64_t* __restrict__ ov_ptr, const int32_t* __restrict__ ov_idx,
     const uint8_t* __restrict__ strand_minus, const int32_t* __restrict__ Lc, const double* __restrict__ d_pr,
     const int32_t* __restrict__ gene_length, double* __restrict__ P, int32_t* __restrict__ R_SIZE,
@@ -665,7 +667,9 @@ __global__ __launch_bounds__(kCtxWaves * 64) void acc_dot_ctx_kernel(
     if (threadIdx.x < kChunkCohorts) g_cohort_bad[threadIdx.x] = 0u;
     __syncthreads();
 
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    // (the wave index through readfirstlane: the tile walk, the tile's first element and every base address derived from them
+    //  are then scalar, and a lane keeps 32-bit offsets only)
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int i = lane & 15, kq = lane >> 4;
     const int toff = 4 * kq + (lane & 3);     // B[k][j] of every block of a quad: lane 16 k + 4 b + j
     const int64_t n_tiles = (E + 15) >> 4;
@@ -686,15 +690,21 @@ __global__ __launch_bounds__(kCtxWaves * 64) void acc_dot_ctx_kernel(
     const int32_t* oi_base = nnz > 0 ? ov_idx : reinterpret_cast<const int32_t*>(ov_ptr);
     const int64_t oi_last = nnz > 0 ? nnz - 1 : 0;
 
-    struct Bounds { int64_t q0, row; int cnt, minus; };
+    // (kept across tiles per lane: the CSR start and one word with the bin count and, in bit 31, the '-' strand; the element's
+    //  row is the tile's scalar first row + a lane offset formed again where it is needed)
+    struct Bounds { int64_t q0; int cm; };
     struct Idx { int i0, i1; };
     struct Rows { int4 a[4], b[4], l[4]; };
+    auto first_row = [&](int64_t tile_) { return min(tile_, n_tiles - 1) * 16; };             // scalar; <= E - 1
+    auto row_off = [&](int64_t row0) { return (unsigned)min(i, (int)min(E - 1 - row0, (int64_t)15)); };
     auto load_bounds = [&](int64_t tile_) {          // tiles / rows past the end replay the last row (never stored)
         Bounds r;
-        r.row = min(min(tile_, n_tiles - 1) * 16 + i, E - 1);
-        r.q0 = ov_ptr[r.row];
-        r.cnt = (int)(ov_ptr[r.row + 1] - r.q0);
-        r.minus = strand_minus[r.row];
+        const int64_t row0 = first_row(tile_);
+        const unsigned ro = row_off(row0);
+        const int64_t* op = ov_ptr + row0;
+        r.q0 = op[ro];
+        const int cnt = (int)(op[ro + 1] - r.q0);
+        r.cm = max(cnt, 0) | ((strand_minus + row0)[ro] ? (int)0x80000000u : 0);
         return r;
     };
     auto load_idx = [&](const Bounds& b) {           // unconditional: bins an element does not have replay a valid entry
@@ -703,18 +713,20 @@ __global__ __launch_bounds__(kCtxWaves * 64) void acc_dot_ctx_kernel(
         x.i1 = oi_base[min(b.q0 + 1, oi_last)];
         return x;
     };
-    auto load_rows = [&](const Bounds& b, const Idx& x) {
+    auto load_rows = [&](int64_t tile_, const Bounds& b, const Idx& x) {
         Rows r;
-        const int kk = b.minus ? 3 - kq : kq;
+        const int kk = b.cm < 0 ? 3 - kq : kq;
         const int4* r0 = ctx4 + (int64_t)x.i0 * 16 + kk;
         const int4* r1 = ctx4 + (int64_t)x.i1 * 16 + kk;
-        const int4* rl = L4 + b.row * 16 + kq;
+        const int64_t row0 = first_row(tile_);
+        const int4* rl = L4 + row0 * 16;
+        const unsigned lo = row_off(row0) * 16u + (unsigned)kq;
 #pragma unroll
         for (int t = 0; t < 4; ++t) r.a[t] = r0[4 * t];
 #pragma unroll
         for (int t = 0; t < 4; ++t) r.b[t] = r1[4 * t];
 #pragma unroll
-        for (int t = 0; t < 4; ++t) r.l[t] = rl[4 * t];
+        for (int t = 0; t < 4; ++t) r.l[t] = rl[lo + 4u * t];
         return r;
     };
 
@@ -750,7 +762,7 @@ __global__ __launch_bounds__(kCtxWaves * 64) void acc_dot_ctx_kernel(
             if (idx < kTotal) tab[idx] = (d0[j] + d1[j]) + d2[j];
         }
     }
-    Rows r_c = load_rows(b_c, x_c);
+    Rows r_c = load_rows(tile, b_c, x_c);
     __syncthreads();
     if (tile >= t_end) return;
 
@@ -759,13 +771,15 @@ __global__ __launch_bounds__(kCtxWaves * 64) void acc_dot_ctx_kernel(
         int opaque_zero;
         asm volatile("s_mov_b32 %0, 0" : "=s"(opaque_zero));
         const double* tabw = tab + opaque_zero;
-        const int64_t e0 = tile * 16;
+        const int64_t e0 = tile * 16;                            // (scalar)
         const Bounds b_nn = load_bounds(tile + 2 * stride);      // tile t+2: CSR bounds
         const Idx x_n = load_idx(b_n);                           // tile t+1: first two bin indices
+        const int cnt = b_c.cm & 0x7fffffff;
+        const bool minus = b_c.cm < 0;
         // region counts of the element: sum of its bins' context rows (sequence_tools.py:630-631), integers
         int rcv[4][4], lv[4][4];
         {
-            const int m0 = b_c.cnt > 0 ? -1 : 0, m1 = b_c.cnt > 1 ? -1 : 0;
+            const int m0 = cnt > 0 ? -1 : 0, m1 = cnt > 1 ? -1 : 0;
 #pragma unroll
             for (int t = 0; t < 4; ++t) {
                 rcv[t][0] = (r_c.a[t].x & m0) + (r_c.b[t].x & m1);
@@ -775,14 +789,42 @@ __global__ __launch_bounds__(kCtxWaves * 64) void acc_dot_ctx_kernel(
                 lv[t][0] = r_c.l[t].x; lv[t][1] = r_c.l[t].y; lv[t][2] = r_c.l[t].z; lv[t][3] = r_c.l[t].w;
             }
         }
-        if (__any(b_c.cnt > 2)) {                                // elements over more than two bins (multi-block, gene-sized)
-            const int kk = b_c.minus ? 3 - kq : kq;
-            for (int j = 2; j < b_c.cnt; ++j) {
+        if (__any(cnt > 2)) {                                    // elements over more than two bins (multi-block, gene-sized)
+            const int kk = minus ? 3 - kq : kq;
+            for (int j = 2; j < cnt; ++j) {
                 const int4* r = ctx4 + (int64_t)ov_idx[b_c.q0 + j] * 16 + kk;
 #pragma unroll
                 for (int t = 0; t < 4; ++t) {
                     const int4 v = r[4 * t];
                     rcv[t][0] += v.x; rcv[t][1] += v.y; rcv[t][2] += v.z; rcv[t][3] += v.w;
+                }
+            }
+        }
+        // the sizes first: integer sums of what the lane holds now, written before the matrix steps so that they are not
+        // carried through them (only the "some L == 0" flag is)
+        int lzero = 0;
+        {
+            int rsum = 0, lsum = 0;
+#pragma unroll
+            for (int t = 0; t < 4; ++t) {
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    rsum += rcv[t][u];
+                    lsum += lv[t][u];
+                    lzero |= lv[t][u] == 0;
+                }
+            }
+            if (write_sizes) {
+                rsum += __shfl_xor(rsum, 16, 64);
+                rsum += __shfl_xor(rsum, 32, 64);
+                lsum += __shfl_xor(lsum, 16, 64);
+                lsum += __shfl_xor(lsum, 32, 64);
+                const unsigned io = (unsigned)(i + opaque_zero);          // (formed here: not a 64-bit address per array kept across tiles)
+                if (kq == 0 && e0 + i < E) {
+                    (R_SIZE + e0)[io] = rsum;                                        // genic_driver_tools.py:375
+                    (ELT_SIZE + e0)[io] = lsum;                                      // :380 (sum(L) / 3 with L = 3 x repeated)
+                    const double numer = gene_length ? (double)(gene_length + e0)[io] : (double)lsum;
+                    (P_INDEL + e0)[io] = numer / (double)rsum;                       // :381 / :159
                 }
             }
         }
@@ -792,8 +834,6 @@ __global__ __launch_bounds__(kCtxWaves * 64) void acc_dot_ctx_kernel(
         for (int nt = 0; nt < NTA; ++nt) den[nt] = num[nt] = double4_t{0.0, 0.0, 0.0, 0.0};
 #pragma unroll
         for (int q = 0; q < NQA; ++q) denq[q] = numq[q] = 0.0;
-        int rsum = 0, lsum = 0, lzero = 0;
-        const bool minus = b_c.minus != 0;
         auto steps = [&](auto T0) {
             constexpr int t0 = decltype(T0)::value;
 #pragma unroll
@@ -801,9 +841,6 @@ __global__ __launch_bounds__(kCtxWaves * 64) void acc_dot_ctx_kernel(
 #pragma unroll
                 for (int u = 0; u < 4; ++u) {
                     const int vr = minus ? rcv[3 - u][3 - t] : rcv[t][u];
-                    rsum += rcv[t][u];
-                    lsum += lv[t][u];
-                    lzero |= lv[t][u] == 0;
                     const double Ar = (double)vr, Al = (double)lv[t][u];
                     const double* b = tabw + ((4 * t + u) * SL) * 64 + lane;
 #pragma unroll
@@ -825,41 +862,33 @@ __global__ __launch_bounds__(kCtxWaves * 64) void acc_dot_ctx_kernel(
             }
         };
         steps(std::integral_constant<int, 0>{});
-        r_c = load_rows(b_n, x_n);                               // tile t+1: context rows + L (indices have arrived meanwhile)
+        r_c = load_rows(tile + stride, b_n, x_n);                // tile t+1: context rows + L (indices have arrived meanwhile)
         steps(std::integral_constant<int, 2>{});
         fix_zero_denominators<NT, NQ>(den, denq, num, numq, lzero, lane);
+        // P[e, c] of the tile: the tile's scalar base + a lane's 32-bit offset (at most 16 C + C elements)
+        // (offsets formed per tile from an opaque copy of C: hoisted out of the loop they are ten 64-bit addresses per lane)
+        double* Pt = P + e0 * C;
+        const int Cz = C + opaque_zero;
+        const int n_e = (int)min(E - e0, (int64_t)16);           // elements of the tile that exist
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-            const int64_t e = e0 + 4 * r + kq;                   // D[i][j]: lane 16 (i % 4) + j, register i / 4
-            if (e < E) {
+            const int el = 4 * r + kq;                           // D[i][j]: lane 16 (i % 4) + j, register i / 4
+            if (el < n_e) {
 #pragma unroll
                 for (int nt = 0; nt < NT; ++nt) {
                     const int c = c0 + nt * 16 + i;
-                    if (c < C) P[e * C + c] = num[nt][r] / den[nt][r];
+                    if (c < C) Pt[(unsigned)(el * Cz + c)] = num[nt][r] / den[nt][r];
                 }
             }
         }
         if constexpr (NQ > 0) {
-            const int64_t e = e0 + 4 * ((lane >> 2) & 3) + kq;   // D[i][j] of block b: lane 16 i + 4 b + j
-            if (e < E) {
+            const int el = 4 * ((lane >> 2) & 3) + kq;           // D[i][j] of block b: lane 16 i + 4 b + j
+            if (el < n_e) {
 #pragma unroll
                 for (int q = 0; q < NQ; ++q) {
                     const int c = c0 + NT * 16 + 4 * q + (lane & 3);
-                    if (c < C) P[e * C + c] = numq[q] / denq[q];
+                    if (c < C) Pt[(unsigned)(el * Cz + c)] = numq[q] / denq[q];
                 }
-            }
-        }
-        if (write_sizes) {
-            rsum += __shfl_xor(rsum, 16, 64);
-            rsum += __shfl_xor(rsum, 32, 64);
-            lsum += __shfl_xor(lsum, 16, 64);
-            lsum += __shfl_xor(lsum, 32, 64);
-            const int64_t e = e0 + i;
-            if (kq == 0 && e < E) {
-                R_SIZE[e] = rsum;                                                    // genic_driver_tools.py:375
-                ELT_SIZE[e] = lsum;                                                  // :380 (sum(L) / 3 with L = 3 x repeated)
-                const double numer = gene_length ? (double)gene_length[e] : (double)lsum;
-                P_INDEL[e] = numer / (double)rsum;                                   // :381 / :159
             }
         }
         b_c = b_n;
@@ -989,6 +1018,8 @@ int accumulate_compact_launch(const int32_t* bin_ctx, const int64_t* ov_ptr, con
     for (int ch = 0; ch < n48; ++ch) {
         const ChunkCut cut = chunk_cut((int)C, ch);
         const int rc = dispatch_cut(cut, [&](auto nt, auto nq) -> int {
+            // register budget of a SIMD while this kernel runs: 3 waves x 160 (every instantiation; amdgpu_num_vgpr on the kernel) + one
+            // 32-register wave of the scale factors' background kernels (dig_suffstats.hip) = 512
             auto kern = acc_dot_ctx_kernel<nt.value, nq.value>;
             DIG_LAUNCH_STAGE(DIG_PIPE_DOT, kern, dim3(grid), dim3(kCtxWaves * 64), 0, (hipStream_t)stream, bin_ctx, ov_ptr, ov_idx, strand_minus,
                                Lc, d_pr, gene_length, P, R_SIZE, ELT_SIZE, P_INDEL, E, (int)C, ch * kMfmaChunk, (int)(ch == 0),

@@ -138,7 +138,12 @@ struct ChunkTable {
 // the background kernel's 85 MB stream is read past the caches (non-temporal loads): it evicted bin records the
 // statistics kernel re-reads -- step 0.1852 -> 0.1836 ms (records), 0.1969 -> 0.1927 (planes), same box, two runs each
 #define DIG_SS_LOAD(p) __builtin_nontemporal_load(p)
-__global__ __launch_bounds__(kSsBlock) void suffstats_chunk_stage1(const double* __restrict__ bin_mu,
+// The three kernels of the chunked form are BACKGROUND kernels (see suffstats_chunk_stage1): at most 32 vector registers each, so
+// that a wave of theirs fits beside either big kernel of the step.  (amdgpu_num_vgpr counts in units of two registers on the
+// unified register file of gfx90a and later: 16 -> 32.)
+#define DIG_SS_BACKGROUND __attribute__((amdgpu_num_vgpr(16)))
+constexpr int kSsUnroll = 8;                       // row loads in flight per thread
+__global__ __launch_bounds__(kSsBlock) DIG_SS_BACKGROUND void suffstats_chunk_stage1(const double* __restrict__ bin_mu,
                                                                    const uint8_t* __restrict__ bin_flag, int64_t C,
                                                                    int64_t rows_per_block, ChunkTable tab,
                                                                    double* __restrict__ partial)
@@ -153,9 +158,12 @@ __global__ __launch_bounds__(kSsBlock) void suffstats_chunk_stage1(const double*
     const int col = tid % (int)C, rg = tid / (int)C;
     // A BACKGROUND kernel: in the burden-test loop it runs on a side stream beside the statistics kernel, whose one
     // 1024-thread workgroup per CU leaves 32 of the 512 vector registers of a SIMD lane, one wave slot and a few KB of LDS
-    // free.  With <= 32 VGPRs (four loads in flight per thread, 32-bit element offsets from the block's base) a workgroup of
-    // this kernel fits into exactly that, so its 96 MB stream no longer waits for -- or holds up -- the big kernels
-    // (round 3: 20 us of the step, tools/loop_probe.py).  Same additions in the same order per thread as before.
+    // free, and beside the contexts + dot kernel, whose three waves per SIMD hold 3 x 160 of the 512 (acc_dot_ctx_kernel).
+    // With <= 32 VGPRs (eight loads in flight per thread, 32-bit element offsets from the block's base) a workgroup of
+    // this kernel fits into exactly that, so its 85 MB stream neither waits for nor holds up either big kernel
+    // (round 3: 20 us of the step, tools/loop_probe.py).  Same additions in the same order per thread as before.  Its waves
+    // issue at the lowest priority: under the big kernels' waves, not beside them.
+    __builtin_amdgcn_s_setprio(0);
     double acc = 0.0;
     if (rg < rpp) {
         const double* mu0 = bin_mu + r_begin * C;
@@ -165,27 +173,27 @@ __global__ __launch_bounds__(kSsBlock) void suffstats_chunk_stage1(const double*
         int r = rg;
         unsigned o = (unsigned)(rg * (int)C + col);
         if (bin_flag) {
-            for (; r + 3 * rpp < n_rows; r += 4 * rpp, o += 4u * (unsigned)stride) {
-                double v[4];
-                uint8_t f[4];
+            for (; r + (kSsUnroll - 1) * rpp < n_rows; r += kSsUnroll * rpp, o += (unsigned)kSsUnroll * (unsigned)stride) {
+                double v[kSsUnroll];
+                uint8_t f[kSsUnroll];
 #pragma unroll
-                for (int q = 0; q < 4; ++q) {
+                for (int q = 0; q < kSsUnroll; ++q) {
                     v[q] = mu0[o + (unsigned)(q * stride)];
                     f[q] = fl0[o + (unsigned)(q * stride)];
                 }
 #pragma unroll
-                for (int q = 0; q < 4; ++q) acc += f[q] ? 0.0 : v[q];
+                for (int q = 0; q < kSsUnroll; ++q) acc += f[q] ? 0.0 : v[q];
             }
             for (; r < n_rows; r += rpp, o += (unsigned)stride) acc += fl0[o] ? 0.0 : mu0[o];
         } else {
             // bin_flag == NULL: the caller's table holds +0.0 where a bin is flagged (a plan-time copy: 8 instead of 9 bytes per
             // (bin, cohort) and step) -- the same additions, the same bits
-            for (; r + 3 * rpp < n_rows; r += 4 * rpp, o += 4u * (unsigned)stride) {
-                double v[4];
+            for (; r + (kSsUnroll - 1) * rpp < n_rows; r += kSsUnroll * rpp, o += (unsigned)kSsUnroll * (unsigned)stride) {
+                double v[kSsUnroll];
 #pragma unroll
-                for (int q = 0; q < 4; ++q) v[q] = DIG_SS_LOAD(&mu0[o + (unsigned)(q * stride)]);
+                for (int q = 0; q < kSsUnroll; ++q) v[q] = DIG_SS_LOAD(&mu0[o + (unsigned)(q * stride)]);
 #pragma unroll
-                for (int q = 0; q < 4; ++q) acc += v[q];
+                for (int q = 0; q < kSsUnroll; ++q) acc += v[q];
             }
             for (; r < n_rows; r += rpp, o += (unsigned)stride) acc += DIG_SS_LOAD(&mu0[o]);
         }
@@ -200,7 +208,7 @@ __global__ __launch_bounds__(kSsBlock) void suffstats_chunk_stage1(const double*
 }
 
 // one workgroup per chunk: thread c adds the chunk's workgroup partials first to last
-__global__ __launch_bounds__(kSsBlock) void suffstats_chunk_stage2(const double* __restrict__ partial, int64_t C, ChunkTable tab,
+__global__ __launch_bounds__(kSsBlock) DIG_SS_BACKGROUND void suffstats_chunk_stage2(const double* __restrict__ partial, int64_t C, ChunkTable tab,
                                                                    double* __restrict__ out_chunks)
 {
     const int j = blockIdx.x;
@@ -212,7 +220,7 @@ __global__ __launch_bounds__(kSsBlock) void suffstats_chunk_stage2(const double*
 }
 
 // cj[c] = (sum over ranks of obs_snv) / (sum over ALL chunks, first to last); obs [world, 2, C] hold integer counts.
-__global__ void scale_factors_chunked_kernel(const double* __restrict__ chunk_sums, int n_chunks, const double* __restrict__ obs,
+__global__ DIG_SS_BACKGROUND void scale_factors_chunked_kernel(const double* __restrict__ chunk_sums, int n_chunks, const double* __restrict__ obs,
                                              int world, int C, double* __restrict__ out_sum, double* __restrict__ cj,
                                              double* __restrict__ cj_indel)
 {
