@@ -1,6 +1,8 @@
 #!/usr/bin/env python
 """Randomised stress of the elementwise NB entry points (host mirror sequence_model.nb_model) against the oracle over a wide
-parameter range (developer tool): mid-p upper, greater, exact, two-sided mid-p, Fisher."""
+parameter range (developer tool): mid-p upper, greater, exact, two-sided mid-p, Fisher.  Its directed counterpart is
+tests/golden/nb_routes_golden.npz (tests/test_gpu_nb_routes.py): rows placed ON the switch points of the dispatch, against an
+80-digit reference at 1e-7; this sweep finds what nobody thought of placing, against scipy at its own accuracy."""
 import os
 import sys
 
