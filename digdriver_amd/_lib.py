@@ -78,6 +78,10 @@ _SIGNATURES = {
     "dig_gene_stats_host": [_vp, _vp, _vp, _vp, _vp, _int, _vp, _int, _vp, _vp, _vp, _vp, _int, _vp, _i64, _i64, _int],
     "dig_gene_selection": [_vp, _vp, _vp, _int, _vp, _vp, _i64, _i64, _vp],
     "dig_gene_selection_host": [_vp, _vp, _vp, _int, _vp, _vp, _i64, _i64, _int],
+    "dig_gene_row_keys": [_vp] * 5 + [_i64] * 4 + [_vp, _vp, _vp],
+    "dig_gene_row_keys_host": [_vp] * 5 + [_i64] * 4 + [_vp, _vp, _int],
+    "dig_gene_counts": [_vp, _i64, _vp, _i64, ctypes.c_double, ctypes.c_double, _i64, _i64, _i64] + [_vp] * 7,
+    "dig_gene_counts_host": [_vp, _i64, _vp, _i64, ctypes.c_double, ctypes.c_double, _i64, _i64, _i64] + [_vp] * 5 + [_int],
     "dig_gene_pipeline": [_vp] * 15 + [_int] + [_vp] * 9 + [_i64, _i64, _i64, _vp, _i64, _vp],
     "dig_gene_pipeline_host": [_vp] * 15 + [_int] + [_vp] * 9 + [_i64, _i64, _i64, _int],
     "dig_count_contexts": [_vp, _i64, _vp, _vp, _int, _vp, _vp, _vp, _vp, _i64, _vp, _vp],

@@ -33,6 +33,10 @@ int set_error(int code, const char* fmt, ...);
 // number of CUs of the current device (cached per device)
 int cu_count();
 
+// dig_genecounts.hip: the bits of the global-sample field of a gene-count key; DIG_EINVAL (in the name of entry point `fn`) when
+// (cohort (G + 2) + gene, global sample, class) does not fit 63 bits
+int gene_key_layout(const char* fn, int64_t G, int64_t C, int64_t n_samples, int* sample_bits);
+
 // i / C with a host-computed magic multiplier: e = hi64(i * ceil(2^64 / C)), exact while
 // i * C < 2^64 (the per-pair int64 division the flat [E, C] index would otherwise need costs
 // more than a whole recurrence step).

@@ -281,6 +281,45 @@ int dig_gene_selection_host(const double* alpha, const double* theta, const doub
                    st.out(out, nGC * DIG_SEL_NPLANES), G, C, nullptr);
 }
 
+int dig_gene_row_keys_host(const int32_t* gene, const int32_t* sample, const uint8_t* annot, const int32_t* cohort,
+                           const int64_t* sample_off, int64_t n, int64_t G, int64_t C, int64_t n_samples, int64_t* keys,
+                           int32_t* sample_total, int device)
+{
+    DIG_REQUIRE(n >= 0 && G >= 0 && C >= 1 && n_samples >= 0, "n, G, n_samples >= 0, C >= 1");
+    DIG_REQUIRE(sample_off && (n == 0 || (gene && sample && annot && cohort && keys)) && (n_samples == 0 || sample_total),
+                "non-null pointers");
+    int sb = 0;
+    if (int rc = gene_key_layout(__func__, G, C, n_samples, &sb)) return rc;
+    DIG_REQUIRE(sample_off[0] == 0 && sample_off[C] == n_samples, "sample_off: 0 first, the sample count last");
+    for (int64_t c = 0; c < C; ++c) DIG_REQUIRE(sample_off[c] <= sample_off[c + 1], "sample_off non-decreasing");
+    for (int64_t i = 0; i < n; ++i) {
+        DIG_REQUIRE(cohort[i] >= 0 && cohort[i] < C, "cohort within [0, C)");
+        DIG_REQUIRE(gene[i] >= 0 && gene[i] <= G + 1, "gene id within [0, G + 1]");
+        DIG_REQUIRE(annot[i] <= 5, "annotation class within [0, 5]");
+        DIG_REQUIRE(sample[i] >= 0 && sample_off[cohort[i]] + sample[i] < sample_off[cohort[i] + 1], "sample id within its cohort");
+    }
+    Staging st(device);
+    return st.call(dig_gene_row_keys, st.in(gene, n), st.in(sample, n), st.in(annot, n), st.in(cohort, n), st.in(sample_off, C + 1), n,
+                   G, C, n_samples, st.out(keys, n), st.out(sample_total, n_samples), nullptr);
+}
+
+int dig_gene_counts_host(const int64_t* keys_sorted, int64_t n, const int32_t* sample_total, int64_t n_samples,
+                         double max_muts_per_sample, double max_muts_per_gene_per_sample, int64_t tp53, int64_t G, int64_t C,
+                         int32_t* obs, int32_t* n_samp, int32_t* extra, int64_t* n_syn, uint8_t* blacklisted, int device)
+{
+    DIG_REQUIRE(n >= 0 && G >= 0 && C >= 1 && n_samples >= 0, "n, G, n_samples >= 0, C >= 1");
+    DIG_REQUIRE(n_syn && (n == 0 || keys_sorted) && (G == 0 || (obs && n_samp && extra)) && (n_samples == 0 || (sample_total && blacklisted)),
+                "non-null pointers");
+    int sb = 0;
+    if (int rc = gene_key_layout(__func__, G, C, n_samples, &sb)) return rc;
+    for (int64_t i = 1; i < n; ++i) DIG_REQUIRE(keys_sorted[i - 1] <= keys_sorted[i], "keys ascending (the caller sorts)");
+    const size_t GC = (size_t)G * C;
+    Staging st(device);
+    return st.call(dig_gene_counts, st.in(keys_sorted, n), n, st.in(sample_total, n_samples), n_samples, max_muts_per_sample,
+                   max_muts_per_gene_per_sample, tp53, G, C, st.out(obs, GC * 5), st.out(n_samp, GC * 6), st.out(extra, GC * 2),
+                   st.out(n_syn, C), st.out(blacklisted, n_samples), static_cast<int32_t*>(st.scratch(GC * 5 * sizeof(int32_t))), nullptr);
+}
+
 int dig_scale_suffstats_host(const double* bin_mu, const uint8_t* bin_flag, int64_t N, int64_t C, double* out_sum, int device)
 {
     DIG_REQUIRE(N >= 0 && C >= 0, "N, C >= 0");

@@ -151,6 +151,56 @@ def dedup_flags(uid, sample, gene, indel):
     return first_row, first_indel
 
 
+GENE_ROW_CLASSES = {'Synonymous': 0, 'Missense': 1, 'Nonsense': 2, 'Essential_Splice': 3, 'INDEL': 4}     # anything else: 5
+_INDEL_KEY = ['CHROM', 'START', 'END', 'REF', 'ALT', 'GENE']
+
+
+def encode_gene_rows(f_mut, gene_index, cohort_id=0, keep=None):
+    """The coding rows of a cohort file as engine.gene_counts takes them: the rows of transfer_tools.read_mutations_cds --
+    read_mutation_file(drop_duplicates=False, drop_sex=True) with GENE != '.', i.e. autosomes only, SNV duplicates kept, an INDEL row
+    kept only when no earlier INDEL row of the file has the same (CHROM, START, END, REF, ALT, GENE) (get_unique_indels,
+    mutation_tools.py:111-117) -- as integer arrays.  That indel rule is NOT dedup_flags' first_indel, which sits behind
+    drop_duplicate_mutations and loses a row when one sample carries an indel under two gene labels; the flag is formed here, by a
+    lexsort as dedup_flags forms its own.
+    gene_index: the gene model's index (G labels).  keep: a set of gene labels; rows of other genes are left out (run_gene_model's
+    cgc_genes).  Returns dict(gene i32: the label's place in gene_index, G for a gene outside it, G + 1 for TP53 when gene_index
+    has no TP53; sample i32: dense ids in order of first appearance; annot u8: GENE_ROW_CLASSES, 5 for any other label; cohort i32;
+    sample_names).  ValueError for a file without a coding row, and for a coding row without a SAMPLE label."""
+    import pandas as pd
+    rows = mutation_tools.read_mutation_file(f_mut, drop_duplicates=False, drop_sex=True, unique_indels=False)
+    if 'GENE' not in rows.columns or 'ANNOT' not in rows.columns:
+        raise ValueError("{}: no GENE / ANNOT columns (an annotated mutation file has 8 or more)".format(f_mut))
+    rows = rows.loc[rows.GENE != '.']
+    if len(rows) == 0:
+        raise ValueError("{}: no coding row (a row with a gene label on an autosome)".format(f_mut))
+    indel = (rows.ANNOT == 'INDEL').values
+    if indel.any():
+        cols = [pd.factorize(rows[c].values[indel])[0] for c in _INDEL_KEY]
+        at = np.flatnonzero(indel)
+        order = np.lexsort([at] + cols[::-1])
+        new = np.ones(len(at), bool)
+        for col in cols:
+            new[1:] &= col[order][1:] == col[order][:-1]
+        new[1:] = ~new[1:]
+        drop = np.zeros(len(rows), bool)
+        drop[at[order[~new]]] = True
+        rows = rows.loc[~drop]
+    if keep is not None:
+        rows = rows.loc[rows.GENE.isin(keep)]
+    if rows.SAMPLE.isna().any():
+        raise ValueError("{}: a coding row without a SAMPLE label".format(f_mut))
+    labels = list(gene_index)
+    G = len(labels)
+    place = {name: i for i, name in enumerate(labels)}
+    codes, uniq = pd.factorize(rows.GENE.values)
+    lookup = np.array([place.get(u, G + 1 if u == 'TP53' else G) for u in uniq] + [G], np.int32)       # (a missing label: code -1)
+    sample, sample_names = pd.factorize(rows.SAMPLE.values)
+    annot = rows.ANNOT.map(GENE_ROW_CLASSES).fillna(5).to_numpy(np.uint8)
+    n = len(rows)
+    return dict(gene=lookup[codes], sample=sample.astype(np.int32), annot=annot, cohort=np.full(n, int(cohort_id), np.int32),
+                sample_names=list(sample_names))
+
+
 def _encode_mutation_file_native(path, cohort_id):
     """encode_mutation_file through the library's parser (dig_mutation_file_*_host, include/dig_hip.h): the same arrays, no
     interpreter lock held while a file is parsed -- 37 files side by side: 0.83 s -> 0.1 s on the 256 cores of the GPU box.

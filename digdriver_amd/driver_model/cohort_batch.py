@@ -11,6 +11,11 @@ arithmetic is a batch along the cohort axis:
 
 and the result is one frame per cohort with the reference's column names, identical to what the per-cohort route
 gives (tests/test_gpu_cohort_batch.py).
+
+geneDriver (transfer_tools.run_gene_model, transfer_tools.py:789-874) is batched the same way -- run_gene_cohorts: C gene models
+with one gene index, the coding rows of C cohorts counted by engine.gene_counts (dig_gene_row_keys + a key sort +
+dig_gene_counts), then ONE dig_gene_stats launch and, when asked for, ONE dig_gene_selection launch over [G, C]
+(tests/test_gpu_gene_cohorts.py).
 """
 import numpy as np
 import pandas as pd
@@ -19,6 +24,7 @@ from .. import engine
 from ..data_tools import tabulate_gpu
 from ..io import mapfile
 from ..sequence_model import genic_driver_tools, nb_model
+from . import transfer_tools
 
 _MUT_COLS10 = ['CHROM', 'START', 'END', 'REF', 'ALT', 'SAMPLE', 'GENE', 'ANNOT', 'MUT_TYPE', 'CONTEXT']
 
@@ -350,3 +356,170 @@ def write_results(frames, outdir, prefixes, workers=None):
         with ThreadPoolExecutor(max_workers=workers) as pool:
             list(pool.map(one, jobs[1:]))
     return paths
+
+
+# ---------------------------------------------------------------------------------------------
+# geneDriver for many cohorts
+# ---------------------------------------------------------------------------------------------
+def _read_gene_models(f_genemodels):
+    """The C gene models as load_pretrained_model leaves them, without its per-map device calls: the frames are read and checked
+    first (one gene index: ValueError naming the first map that differs), then the Gamma parameters of all of them are ONE
+    element-wise call over [G, C] (the same bits).  Returns (the frames with _GENE_COLS_LEFT columns, dict name -> f64 [G, C])."""
+    tt = transfer_tools
+    raw = []
+    for f in f_genemodels:
+        m = mapfile.read_frame(f, 'genic_model')
+        m = m.set_index(m.GENE).rename(columns=tt._GENE_RENAME)
+        m['Pi_NONSYN'] = m.Pi_MIS + m.Pi_TRUNC
+        if raw and not m.index.equals(raw[0].index):
+            raise ValueError("{}: its gene model's gene index differs from that of {} (run_gene_cohorts needs one gene index for all "
+                             "maps)".format(f, list(f_genemodels)[0]))
+        raw.append(m)
+    stack = lambda col: np.ascontiguousarray(np.stack([m[col].values for m in raw], axis=1), dtype=np.float64)
+    planes = {col: stack(col) for col in ['MU', 'SIGMA', 'MU_INDEL', 'SIGMA_INDEL', 'Pi_INDEL'] + ['Pi_' + c for c in tt.GENE_CLASSES]}
+    planes['ALPHA'], planes['THETA'] = nb_model.normal_params_to_gamma(planes['MU'], planes['SIGMA'])
+    planes['ALPHA_INDEL'], planes['THETA_INDEL'] = nb_model.normal_params_to_gamma(planes['MU_INDEL'], planes['SIGMA_INDEL'])
+    frames = []
+    for c, m in enumerate(raw):
+        for col in ('ALPHA', 'THETA', 'ALPHA_INDEL', 'THETA_INDEL'):
+            m[col] = planes[col][:, c]
+        frames.append(m[tt._GENE_COLS_LEFT])
+    return frames, planes
+
+
+def run_gene_cohorts(f_muts, f_genemodels, scale_by_sample=False, pval_burden_nb=True, pval_burden_dnds=True, pval_sel=True,
+                     max_muts_per_sample=3e9, max_muts_per_gene_per_sample=3e9, scale_factors=None, scale_by_expectation=True,
+                     cgc_genes=False, all_cosmic=None, selection=False, device=0, on_frame=None):
+    """geneDriver for C cohorts in one pass: one frame per cohort, with the columns, the column order and the dtypes of
+    transfer_tools.run_gene_model(f_muts[c], f_genemodels[c], fused=True, ...) and the same keywords (scale_factors: an array [C]
+    in place of scale_factor).  The gene models must share one gene index.  The sample and exome ratios (scale_by_sample, or
+    neither scale_by_expectation nor scale_factors) need the maps' N_MUT_CDS bookkeeping and are not batched: NotImplementedError,
+    before any device work.
+    The observed counts, N_SAMP_*, the hypermutator filter and the synonymous row count come from engine.gene_counts over the
+    rows of tabulate_gpu.encode_gene_rows; the scale factor's and the indel rate's denominators are the serial route's own pandas
+    expressions over a cohort's model (G values each: the same bits); the statistics are one engine.gene_stats launch and, with
+    selection=True, one engine.gene_selection launch over [G, C].
+    on_frame(c, frame): called as soon as cohort c's frame exists."""
+    import torch
+    tt = transfer_tools
+    C = len(f_muts)
+    assert C > 0 and len(f_genemodels) == C
+    if scale_by_sample or not (scale_by_expectation or scale_factors is not None):
+        raise NotImplementedError("run_gene_cohorts scales by the expected synonymous count (scale_by_expectation) or by given "
+                                  "scale_factors; the sample and exome ratios are run_gene_model's")
+    if scale_factors is not None and not scale_by_expectation:
+        scale_factors = np.asarray(scale_factors, float).reshape(C)
+    models, planes = _read_gene_models(f_genemodels)
+    keep = None
+    if cgc_genes:
+        keep = set(tt.gene_panel(cgc_genes))
+        inside = models[0].index.isin(keep)
+        models = [m.loc[inside] for m in models]
+        planes = {k: np.ascontiguousarray(v[inside]) for k, v in planes.items()}
+    index = models[0].index
+    G = len(index)
+    dev = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
+
+    rows = [tabulate_gpu.encode_gene_rows(f, index, c, keep=keep) for c, f in enumerate(f_muts)]
+    offsets = np.concatenate([[0], np.cumsum([len(r["sample_names"]) for r in rows])]).astype(np.int64)
+    tp53 = int(index.get_loc('TP53')) if 'TP53' in index else G + 1
+    up = lambda k: torch.as_tensor(np.concatenate([r[k] for r in rows]), device=dev)
+    counts = engine.gene_counts(up("gene"), up("sample"), up("annot"), up("cohort"), offsets, G, C, tp53,
+                                max_muts_per_sample=max_muts_per_sample, max_muts_per_gene_per_sample=max_muts_per_gene_per_sample)
+    by_cohort = lambda x: x.transpose(-1, -2).contiguous().cpu().numpy()                     # [..., G, C] -> [..., C, G]
+    obs_h = counts["obs"].permute(2, 1, 0).contiguous().cpu().numpy().astype(np.int64)       # [C, 5, G]
+    n_samp_h = counts["n_samp"].permute(2, 1, 0).contiguous().cpu().numpy().astype(np.int64)
+    n_samp_indel, n_pairs = by_cohort(counts["n_samp_indel"]).astype(np.int64), by_cohort(counts["n_pairs"])
+    n_syn = counts["n_syn"].cpu().numpy()
+
+    # scale factors (transfer_tools.py:809-823) and the uniform indel rate (:709-721), a cohort at a time over G values
+    if scale_by_expectation:
+        print('scaling by expected synonymous mutations (excluding TP53)')
+        cj = np.empty(C)
+        for c, m in enumerate(models):
+            background = m.loc[m.index != 'TP53']
+            cj[c] = int(n_syn[c]) / (background.MU * background.Pi_SYN).sum()
+    else:
+        cj = scale_factors
+    theta = planes['THETA'] * 1.0 * cj[None, :]                          # (_attach_counts scales by 1.0, transfer_gene_model by cj)
+    has_indel = obs_h[:, 4, :].sum(axis=1) != 0
+    if not pval_burden_nb and has_indel.any():
+        raise KeyError('PVAL_TRUNC_BURDEN')                              # (what the serial route's Fisher step says without the burden tests)
+    t_indel = np.ones(C)
+    if has_indel.any():
+        null = ~index.isin(tt.cosmic_null_set(all_cosmic))
+        for c in np.flatnonzero(has_indel):
+            m = models[c].loc[null]
+            t_indel[c] = pd.Series(obs_h[c, 4][null]).sum() / (m.Pi_INDEL * m.ALPHA_INDEL * m.THETA_INDEL).sum()
+
+    print('Calculating statistics')
+    t = lambda a: torch.as_tensor(np.ascontiguousarray(a), device=dev)
+    pi = np.stack([planes['Pi_' + c] for c in tt.GENE_CLASSES], axis=1)                       # [G, 6, C]
+    S = {}
+    if pval_burden_nb:
+        st = engine.gene_stats(t(planes['MU']), t(planes['SIGMA']), t(pi), t(planes['Pi_INDEL']), counts["obs"], counts["n_samp"], t(cj),
+                               t(t_indel), mu_indel=t(planes['MU_INDEL']), sigma_indel=t(planes['SIGMA_INDEL']))
+        S.update({k: by_cohort(v) for k, v in st.items()})
+    if selection:
+        sel = engine.gene_selection(t(planes['ALPHA']), t(theta), t(pi), counts["obs"])
+        S.update({k: by_cohort(v) for k, v in sel.items()})
+
+    frames = []
+    obs_names = ('OBS_SYN', 'OBS_MIS', 'OBS_NONS', 'OBS_SPL', 'OBS_INDEL')
+    for c, m in enumerate(models):
+        d = {col: m[col].values for col in tt._GENE_COLS_LEFT}
+        d['THETA'] = np.ascontiguousarray(theta[:, c])
+        # a model gene without a row in the cohort's count table makes the serial route's left join fill with NaN: float columns
+        kind = np.int64 if (n_pairs[c] > 0).all() else np.float64
+        for q, name in enumerate(obs_names):
+            d[name] = obs_h[c, q].astype(kind)
+        d['OBS_TRUNC'] = d['OBS_NONS'] + d['OBS_SPL']
+        d['OBS_NONSYN'] = d['OBS_MIS'] + d['OBS_TRUNC']
+        for q, cls in enumerate(tt.GENE_CLASSES):
+            d['N_SAMP_' + cls] = n_samp_h[c, q]
+        d['N_SAMP_INDEL'] = n_samp_indel[c]
+        rate = m.ALPHA.values * d['THETA']
+        for q, cls in enumerate(tt.GENE_CLASSES):                          # gene_expected_muts_nb: the serial route's own products
+            d['EXP_' + cls] = S['EXP_' + cls][c] if pval_burden_nb and not selection else rate * m['Pi_' + cls].values
+        if pval_burden_nb:
+            for pattern in ('PVAL_%s_BURDEN', 'PVAL_%s_BURDEN_SAMPLE'):
+                for cls in tt.GENE_CLASSES:
+                    d[pattern % cls] = S[pattern % cls][c]
+        if selection:
+            names = ['T_SYN', 'MRFOLD'] + ['EXP_%s_ML' % cls for cls in tt.GENE_CLASSES]
+            if pval_burden_dnds:
+                names += ['PVAL_%s_BURDEN_DNDS' % cls for cls in tt.GENE_CLASSES]
+            if pval_sel:
+                names += ['PVAL_%s_SEL_NB' % cls for cls in tt._SEL_NB_CLASSES]
+            for name in names:
+                d[name] = S[name][c]
+        if has_indel[c]:                                                   # (pval_burden_nb holds here)
+            for name in ('THETA_INDEL', 'EXP_INDEL', 'PVAL_INDEL_BURDEN', 'PVAL_MUT_BURDEN'):
+                d[name] = S[name][c]
+        print("\tScaling factor of cohort {} is: {}".format(c, cj[c]))
+        frames.append(pd.DataFrame(d, index=index))
+        if on_frame is not None:
+            on_frame(c, frames[-1])
+    return frames
+
+
+def run_and_write_gene_cohorts(f_muts, f_genemodels, outdir, prefixes, write_threads=None, **kw):
+    """run_gene_cohorts + <outdir>/<prefix>.results.txt per cohort through the native writer, as `DigDriver.py geneDriver` writes
+    it (mapfile.write_results_tsv of the frame as it is: the bytes of frame.to_csv), each file by a worker thread while the frames
+    of the cohorts after it are assembled.  Returns (frames, paths); the files are complete when the call returns."""
+    import os
+    from concurrent.futures import ThreadPoolExecutor
+    os.makedirs(outdir, exist_ok=True)
+    C = len(f_muts)
+    assert len(prefixes) == C
+    paths = [os.path.join(outdir, pfx + '.results.txt') for pfx in prefixes]
+    cores = os.cpu_count() or 1
+    threads = int(write_threads) if write_threads else max(1, min(8, cores // max(C, 1)))
+    pending = []
+    with ThreadPoolExecutor(max_workers=max(1, min(C, cores))) as pool:
+        frames = run_gene_cohorts(f_muts, f_genemodels,
+                                  on_frame=lambda c, frame: pending.append(pool.submit(mapfile.write_results_tsv, frame, paths[c], threads)),
+                                  **kw)
+        for f in pending:
+            f.result()
+    return frames, paths

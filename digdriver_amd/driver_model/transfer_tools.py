@@ -31,6 +31,8 @@ _INDEL_RATE_COLS = [c + '_INDEL' for c in _RATE_COLS]
 _GENE_COLS_LEFT = (['CHROM', 'GENE_LENGTH', 'R_SIZE', 'R_OBS', 'R_INDEL'] + _RATE_COLS + _INDEL_RATE_COLS + ['FLAG']
                    + ['Pi_' + c for c in GENE_CLASSES] + ['Pi_INDEL'])
 _ELT_COLS_LEFT = ['ELT_SIZE', 'FLAG', 'R_SIZE', 'R_OBS', 'R_INDEL'] + _RATE_COLS + _INDEL_RATE_COLS + ['Pi_SUM', 'Pi_INDEL']
+_GENE_RENAME = {'P_SILENT': 'Pi_SYN', 'P_MIS': 'Pi_MIS', 'P_NONS': 'Pi_NONS', 'P_SPLICE': 'Pi_SPL', 'P_TRUNC': 'Pi_TRUNC',
+                'P_INDEL': 'Pi_INDEL'}                        # the gene model's stored column names -> the drivers'
 _COSMIC_EXTRA = ['CDKN2A.p14arf', 'CDKN2A.p16INK4a']          # added to the CGC panel wherever the reference uses it
 
 # ---------------------------------------------------------------------------------------------
@@ -97,8 +99,7 @@ def load_pretrained_model(h5, key='genic_model', restrict_cols=True):
     has_indel = is_gene or 'P_INDEL' in model.columns
     model = model.set_index(model.GENE if is_gene else model.ELT)
     if is_gene:
-        model = model.rename(columns={'P_SILENT': 'Pi_SYN', 'P_MIS': 'Pi_MIS', 'P_NONS': 'Pi_NONS', 'P_SPLICE': 'Pi_SPL',
-                                      'P_TRUNC': 'Pi_TRUNC', 'P_INDEL': 'Pi_INDEL'})
+        model = model.rename(columns=_GENE_RENAME)
         model['Pi_NONSYN'] = model.Pi_MIS + model.Pi_TRUNC
     else:
         model = model.rename(columns={'P_SUM': 'Pi_SUM', 'P_INDEL': 'Pi_INDEL'})

@@ -157,6 +157,47 @@ def gene_selection(alpha, theta, pi, obs, device=0, out=None):
     return {name: out[i] for i, name in enumerate(SEL_PLANES)}
 
 
+def gene_counts(gene, sample, annot, cohort, sample_offsets, G, C, tp53, max_muts_per_sample=3e9, max_muts_per_gene_per_sample=3e9,
+                device=0):
+    """The gene route's integer bookkeeping for the coding rows of C cohorts against one gene index of G rows
+    (filter_hypermut_samples, mutations_per_gene, the N_SAMP_* columns of transfer_gene_model and the synonymous row count of the
+    scale factor; mutation_tools.py:293-304,329-361, transfer_tools.py:196-270,809-823): dig_gene_row_keys, a key sort,
+    dig_gene_counts.  Rows as tabulate_gpu.encode_gene_rows gives them: gene i32 (0 .. G - 1, G = outside the model, G + 1 = TP53
+    when the model has none), sample i32 (dense per cohort), annot u8 (0 SYN, 1 MIS, 2 NONS, 3 SPL, 4 INDEL, 5 other), cohort i32;
+    sample_offsets [C + 1] = a cohort's first global sample; tp53: TP53's gene id.
+    Returns dict(obs i32 [G, 5, C] (SYN, MIS, NONS, SPL, INDEL) and n_samp i32 [G, 6, C] as gene_stats takes them, n_syn i64 [C],
+    blacklisted u8 per global sample, n_samp_indel i32 [G, C], n_pairs i32 [G, C]: (gene, sample) pairs with a row of any class).
+    CUDA tensors in -> CUDA tensors out."""
+    be = backend_of(gene, sample, annot, cohort, device=device)
+    gene, sample, cohort = (be.arr(x, "i32", (-1,)) for x in (gene, sample, cohort))
+    annot = be.arr(annot, "u8", (-1,))
+    n = gene.shape[0]
+    assert sample.shape[0] == annot.shape[0] == cohort.shape[0] == n
+    G, C = int(G), int(C)
+    off_host = np.ascontiguousarray(np.asarray(sample_offsets.cpu() if is_cuda(sample_offsets) else sample_offsets), dtype=np.int64).ravel()
+    if len(off_host) != C + 1 or off_host[0] != 0 or (np.diff(off_host) < 0).any():
+        raise ValueError("sample_offsets: C + 1 non-decreasing entries, 0 first")
+    S = int(off_host[-1])
+    off = be.arr(off_host, "i64")
+    if be.is_device and n:
+        # (device tensors are checked here; the host twin checks its own arrays inside the library)
+        per_row = (off[1:] - off[:-1])[cohort.clamp(0, C - 1).long()]
+        bad = (cohort < 0) | (cohort >= C) | (gene < 0) | (gene > G + 1) | (annot > 5) | (sample < 0) | (sample >= per_row)
+        if bool(bad.any()):
+            raise ValueError("a row outside the tables: cohort within [0, C), gene within [0, G + 1], annot within [0, 5], sample "
+                             "within its cohort")
+    p = be.ptr
+    keys, total = be.empty(n, "i64"), be.empty(S, "i32")
+    be.call("dig_gene_row_keys", p(gene), p(sample), p(annot), p(cohort), p(off), n, G, C, S, p(keys), p(total))
+    keys = keys.sort()[0] if be.is_device else np.sort(keys)               # the caller sorts (plumbing, as for dig_bh_qvalues_sorted)
+    obs, n_samp, extra = be.empty((G, 5, C), "i32"), be.empty((G, 6, C), "i32"), be.empty((G, 2, C), "i32")
+    n_syn, black = be.empty(C, "i64"), be.empty(S, "u8")
+    scratch = [p(be.empty((G, 5, C), "i32"))] if be.is_device else []      # (the host twin stages its own)
+    be.call("dig_gene_counts", p(keys), n, p(total), S, float(max_muts_per_sample), float(max_muts_per_gene_per_sample), int(tp53),
+            G, C, p(obs), p(n_samp), p(extra), p(n_syn), p(black), *scratch)
+    return dict(obs=obs, n_samp=n_samp, n_syn=n_syn, blacklisted=black, n_samp_indel=extra[:, 0], n_pairs=extra[:, 1])
+
+
 def gene_pipeline(bin_mu, bin_std, bin_y, bin_flag, bin_ctx, ov_ptr, ov_idx, L, strand_minus, gene_length, d_pr, obs, n_samp, cj,
                   t_indel=None):
     """genic_model (genic_driver_tools.py:31-203) + the gene statistics block as one call on device tensors

@@ -308,6 +308,39 @@ int dig_gene_selection(const double *alpha, const double *theta, const double *p
 int dig_gene_selection_host(const double *alpha, const double *theta, const double *pi, int n_pi, const int32_t *obs, double *out,
                             int64_t G, int64_t C, int device);
 
+/* ---- the gene route's observed counts for many cohorts (additive: the ABI version stays) ---------------------- *
+ * filter_hypermut_samples + mutations_per_gene (mutation_tools.py:293-304,329-361), the N_SAMP_* columns of transfer_gene_model
+ * (transfer_tools.py:196-270) and the synonymous row count of the scale factor (:809-823) for the coding rows of C cohorts against
+ * one gene index of G rows.  A row is (gene id, sample id dense per cohort, class, cohort): gene 0 .. G - 1 = the model's rows, G =
+ * a gene outside the model, G + 1 = TP53 when the model has no TP53 row; class 0 Synonymous, 1 Missense, 2 Nonsense,
+ * 3 Essential_Splice, 4 INDEL, 5 anything else.  sample_off i64 [C + 1]: a cohort's first global sample (0 first, n_samples last).
+ *   dig_gene_row_keys: keys i64 [n], key = (cohort (G + 2) + gene) << (sb + 3) | global sample << 3 | class with sb the bits of
+ *     n_samples - 1 (DIG_EINVAL when the fields do not fit 63 bits), and sample_total i32 [n_samples] = rows per sample.  A row
+ *     outside the tables gets key -1 and is counted nowhere (the host twin refuses it).
+ *   The caller sorts the keys ascending (as for dig_bh_qvalues_sorted).
+ *   dig_gene_counts, from the sorted keys: a sample with sample_total > max_muts_per_sample (a double, the reference's `>`) is
+ *     blacklisted [n_samples] u8 and none of its rows count.  Of the others:
+ *       obs i32 [G, 5, C]     rows per (gene, class 0 .. 4, cohort), each (gene, sample, class) group clipped to
+ *                             max_muts_per_gene_per_sample as the reference clips: summed as numbers, then cast to int
+ *       n_samp i32 [G, 6, C]  distinct (gene, sample) pairs with a row of class SYN, MIS, NONS, SPL, TRUNC = {NONS, SPL}, NONSYN =
+ *                             {MIS, NONS, SPL} (unclipped); the layouts dig_gene_stats reads
+ *       extra i32 [G, 2, C]   the same for INDEL (N_SAMP_INDEL), and for a row of any class (a gene with 0 here has no row in the
+ *                             reference's count table: its merge turns the cohort's OBS_* columns into floats)
+ *       n_syn i64 [C]         class-0 rows of every gene but `tp53` (a gene id; G + 1 when the model has no TP53), genes outside
+ *                             the model included, unclipped
+ *     scratch: i32 [G, 5, C] of device memory.  Every output is zeroed by the call; integer atomics, so order-independent. */
+int dig_gene_row_keys(const int32_t *gene, const int32_t *sample, const uint8_t *annot, const int32_t *cohort, const int64_t *sample_off,
+                      int64_t n, int64_t G, int64_t C, int64_t n_samples, int64_t *keys, int32_t *sample_total, void *stream);
+int dig_gene_row_keys_host(const int32_t *gene, const int32_t *sample, const uint8_t *annot, const int32_t *cohort,
+                           const int64_t *sample_off, int64_t n, int64_t G, int64_t C, int64_t n_samples, int64_t *keys,
+                           int32_t *sample_total, int device);
+int dig_gene_counts(const int64_t *keys_sorted, int64_t n, const int32_t *sample_total, int64_t n_samples, double max_muts_per_sample,
+                    double max_muts_per_gene_per_sample, int64_t tp53, int64_t G, int64_t C, int32_t *obs, int32_t *n_samp,
+                    int32_t *extra, int64_t *n_syn, uint8_t *blacklisted, int32_t *scratch, void *stream);
+int dig_gene_counts_host(const int64_t *keys_sorted, int64_t n, const int32_t *sample_total, int64_t n_samples,
+                         double max_muts_per_sample, double max_muts_per_gene_per_sample, int64_t tp53, int64_t G, int64_t C,
+                         int32_t *obs, int32_t *n_samp, int32_t *extra, int64_t *n_syn, uint8_t *blacklisted, int device);
+
 /* ---- sufficient statistics in canonical chunks (bin-sharded runs) --------------------------- *
  * Same quantity as dig_scale_suffstats / dig_scale_factors, defined so that it does not depend on the sharding: the bins
  * are cut into K canonical chunks of the GLOBAL grid (boundaries floor(N j / K)); a rank computes the chunk sums of the
