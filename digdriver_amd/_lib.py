@@ -82,6 +82,12 @@ _SIGNATURES = {
     "dig_gene_row_keys_host": [_vp] * 5 + [_i64] * 4 + [_vp, _vp, _int],
     "dig_gene_counts": [_vp, _i64, _vp, _i64, ctypes.c_double, ctypes.c_double, _i64, _i64, _i64] + [_vp] * 7,
     "dig_gene_counts_host": [_vp, _i64, _vp, _i64, ctypes.c_double, ctypes.c_double, _i64, _i64, _i64] + [_vp] * 5 + [_int],
+    "dig_window_pair_keys": [_vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp] + [_i64] * 4 + [_vp, _vp],
+    "dig_window_pair_keys_host": [_vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp] + [_i64] * 4 + [_vp, _int],
+    "dig_window_sample_hits": [_vp] + [_i64] * 4 + [_vp, _vp],
+    "dig_window_sample_hits_host": [_vp] + [_i64] * 4 + [_vp, _int],
+    "dig_window_objectives": [_vp, _i64, _vp, _vp] + [_i64] * 4 + [_vp, _vp, _vp],
+    "dig_window_objectives_host": [_vp, _i64, _vp, _vp] + [_i64] * 4 + [_vp, _int],
     "dig_gene_pipeline": [_vp] * 15 + [_int] + [_vp] * 9 + [_i64, _i64, _i64, _vp, _i64, _vp],
     "dig_gene_pipeline_host": [_vp] * 15 + [_int] + [_vp] * 9 + [_i64, _i64, _i64, _int],
     "dig_count_contexts": [_vp, _i64, _vp, _vp, _int, _vp, _vp, _vp, _vp, _i64, _vp, _vp],

@@ -320,6 +320,58 @@ int dig_gene_counts_host(const int64_t* keys_sorted, int64_t n, const int32_t* s
                    st.out(n_syn, C), st.out(blacklisted, n_samples), static_cast<int32_t*>(st.scratch(GC * 5 * sizeof(int32_t))), nullptr);
 }
 
+int dig_window_pair_keys_host(const int32_t* pair_row, const int32_t* pair_blk, int64_t n_pairs, const int32_t* blk_window, int64_t n_blk,
+                              const int32_t* row_sample, const int32_t* row_uid, const uint8_t* row_indel, int64_t n_rows,
+                              int64_t n_samples, int64_t N, int64_t n_uid, int64_t* keys, int device)
+{
+    DIG_REQUIRE(n_pairs >= 0 && n_blk >= 0 && n_rows >= 0, "n_pairs, n_blk, n_rows >= 0");
+    WindowKeyLayout lay;
+    if (int rc = window_key_layout(__func__, n_samples, N, n_uid, &lay)) return rc;
+    DIG_REQUIRE(n_pairs == 0 || (pair_row && pair_blk && keys), "non-null pair arrays");
+    DIG_REQUIRE(n_rows == 0 || (row_sample && row_uid && row_indel), "non-null row arrays");
+    for (int64_t b = 0; blk_window && b < n_blk; ++b) DIG_REQUIRE(blk_window[b] >= 0 && blk_window[b] < N, "window within [0, N)");
+    DIG_REQUIRE(blk_window || n_blk <= N, "without blk_window the block row is the window: n_blk <= N");
+    for (int64_t r = 0; r < n_rows; ++r) {
+        DIG_REQUIRE(row_sample[r] >= 0 && row_sample[r] < n_samples, "global sample within [0, n_samples)");
+        DIG_REQUIRE(row_uid[r] >= 0 && row_uid[r] < n_uid, "mutation id within [0, n_uid)");
+    }
+    for (int64_t i = 0; i < n_pairs; ++i)
+        DIG_REQUIRE(pair_row[i] >= 0 && pair_row[i] < n_rows && pair_blk[i] >= 0 && pair_blk[i] < n_blk, "a pair within the tables");
+    Staging st(device);
+    return st.call(dig_window_pair_keys, st.in(pair_row, n_pairs), st.in(pair_blk, n_pairs), n_pairs, st.in(blk_window, n_blk), n_blk,
+                   st.in(row_sample, n_rows), st.in(row_uid, n_rows), st.in(row_indel, n_rows), n_rows, n_samples, N, n_uid,
+                   st.out(keys, n_pairs), nullptr);
+}
+
+int dig_window_sample_hits_host(const int64_t* keys_sorted, int64_t n_pairs, int64_t n_samples, int64_t N, int64_t n_uid, int32_t* hits,
+                                int device)
+{
+    DIG_REQUIRE(n_pairs >= 0, "n_pairs >= 0");
+    WindowKeyLayout lay;
+    if (int rc = window_key_layout(__func__, n_samples, N, n_uid, &lay)) return rc;
+    DIG_REQUIRE((n_pairs == 0 || keys_sorted) && (n_samples == 0 || hits), "non-null pointers");
+    for (int64_t i = 1; i < n_pairs; ++i) DIG_REQUIRE(keys_sorted[i - 1] <= keys_sorted[i], "keys ascending (the caller sorts)");
+    Staging st(device);
+    return st.call(dig_window_sample_hits, st.in(keys_sorted, n_pairs), n_pairs, n_samples, N, n_uid, st.out(hits, n_samples), nullptr);
+}
+
+int dig_window_objectives_host(const int64_t* keys_sorted, int64_t n_pairs, const uint8_t* keep, const int64_t* sample_off,
+                               int64_t n_samples, int64_t N, int64_t C, int64_t n_uid, double* labels, int device)
+{
+    DIG_REQUIRE(n_pairs >= 0 && C >= 1, "n_pairs >= 0, C >= 1");
+    WindowKeyLayout lay;
+    if (int rc = window_key_layout(__func__, n_samples, N, n_uid, &lay)) return rc;
+    DIG_REQUIRE(N < ((int64_t)1 << 62) / C, "N C below 2^62");
+    DIG_REQUIRE(sample_off && (n_pairs == 0 || keys_sorted) && (n_samples == 0 || keep) && (N == 0 || labels), "non-null pointers");
+    DIG_REQUIRE(sample_off[0] == 0 && sample_off[C] == n_samples, "sample_off: 0 first, the sample count last");
+    for (int64_t c = 0; c < C; ++c) DIG_REQUIRE(sample_off[c] <= sample_off[c + 1], "sample_off non-decreasing");
+    for (int64_t i = 1; i < n_pairs; ++i) DIG_REQUIRE(keys_sorted[i - 1] <= keys_sorted[i], "keys ascending (the caller sorts)");
+    const size_t NC = (size_t)N * C;
+    Staging st(device);
+    return st.call(dig_window_objectives, st.in(keys_sorted, n_pairs), n_pairs, st.in(keep, n_samples), st.in(sample_off, C + 1), n_samples,
+                   N, C, n_uid, st.out(labels, NC), static_cast<int32_t*>(st.scratch(NC * sizeof(int32_t))), nullptr);
+}
+
 int dig_scale_suffstats_host(const double* bin_mu, const uint8_t* bin_flag, int64_t N, int64_t C, double* out_sum, int device)
 {
     DIG_REQUIRE(N >= 0 && C >= 0, "N, C >= 0");

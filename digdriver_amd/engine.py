@@ -198,6 +198,83 @@ def gene_counts(gene, sample, annot, cohort, sample_offsets, G, C, tp53, max_mut
     return dict(obs=obs, n_samp=n_samp, n_syn=n_syn, blacklisted=black, n_samp_indel=extra[:, 0], n_pairs=extra[:, 1])
 
 
+def window_objectives(win_chrom, win_start, win_end, row_chrom, row_start, row_end, row_sample, row_uid, row_indel, sample_offsets,
+                      n_uid, keep_from_hits=None, device=0):
+    """The region model's training labels for C cohorts at once (scripts/DataExtractor.py:525-572 add_objectives without --cnv):
+    dig_overlap_join_count/fill of all cohorts' rows with the N windows as one-block elements, dig_window_pair_keys, a key sort,
+    dig_window_sample_hits, `keep_from_hits` on the host, dig_window_objectives.
+    Windows: chromosome id i64, START, END (host arrays, any order; the rows' chromosome ids name the same chromosomes).  Rows: chrom,
+    start, end i64; sample i32 = the GLOBAL sample (sample_offsets [C + 1]: a cohort's first); uid i32 = dense ids, below n_uid, of the
+    cohort's distinct (CHROM, START, END, REF, ALT); indel u8.
+    keep_from_hits(hits): host int32 [S], the distinct windows each sample hits -> the samples that stay, bool / u8 [S] (None: all).
+    Returns dict(labels f64 [N, C]: distinct non-indel mutations of the kept samples per window and cohort; hits, keep: host arrays).
+    CUDA tensors in (the row arrays) -> labels as a CUDA tensor."""
+    be = backend_of(row_chrom, row_start, row_end, row_sample, row_uid, row_indel, device=device)
+    off_host = np.ascontiguousarray(np.asarray(sample_offsets), dtype=np.int64).ravel()
+    C = len(off_host) - 1
+    if C < 1 or off_host[0] != 0 or (np.diff(off_host) < 0).any():
+        raise ValueError("sample_offsets: C + 1 non-decreasing entries, 0 first")
+    S, n_uid = int(off_host[-1]), int(n_uid)
+    # the windows as join blocks: sorted by (chrom, start), composite keys (tabulate_gpu.ElementBlocks)
+    wc, ws, we = (np.asarray(x, np.int64).ravel() for x in (win_chrom, win_start, win_end))
+    N = len(wc)
+    if N and (wc.min() < 0 or wc.max() >= (1 << 22) or ws.min() < 0 or max(ws.max(), we.max()) >= (1 << 40)):
+        raise ValueError("windows: chromosome ids within [0, 2^22), coordinates within [0, 2^40)")
+    order = np.lexsort((ws, wc))
+    wc, ws, we = wc[order], ws[order], np.where(we == ws, ws + 1, we)[order]
+    runmax = np.empty_like(we)
+    for c in np.unique(wc):
+        sel = wc == c
+        runmax[sel] = np.maximum.accumulate(we[sel])
+    start_key, runmax_key, blk_end = be.arr((wc << 40) | ws, "i64"), be.arr((wc << 40) | runmax, "i64"), be.arr(we, "i64")
+    blk_window = be.arr(order, "i32")
+    row_chrom, row_start, row_end = (be.arr(x, "i64", (-1,)) for x in (row_chrom, row_start, row_end))
+    row_sample, row_uid = be.arr(row_sample, "i32", (-1,)), be.arr(row_uid, "i32", (-1,))
+    row_indel = be.arr(row_indel, "u8", (-1,))
+    n = row_chrom.shape[0]
+    assert row_start.shape[0] == row_end.shape[0] == row_sample.shape[0] == row_uid.shape[0] == row_indel.shape[0] == n
+    if be.is_device and n:
+        # (device tensors are checked here; the host twin checks its own arrays inside the library)
+        bad = (row_sample < 0) | (row_sample >= S) | (row_uid < 0) | (row_uid >= n_uid)
+        if bool(bad.any()):
+            raise ValueError("a row outside the tables: global sample within [0, S), mutation id within [0, n_uid)")
+    p = be.ptr
+    total = 0
+    pair_row = pair_blk = be.empty(0, "i32")
+    if n and N:
+        counts = be.arr(np.zeros(n, np.int32), "i32")
+        join = [p(start_key), p(runmax_key), p(blk_end), N, p(row_chrom), p(row_start), p(row_end), n]
+        be.call("dig_overlap_join_count", *join, p(counts))
+        if be.is_device:
+            incl = be.torch.cumsum(counts, 0, dtype=be.torch.int64)
+            total, offsets = int(incl[-1].item()), (incl - counts).contiguous()
+        else:
+            incl = np.cumsum(counts, dtype=np.int64)
+            total, offsets = int(incl[-1]), incl - counts
+        if total >= 2 ** 31:
+            raise ValueError("%d (mutation, window) pairs: the join's pair indices are 32-bit; fewer cohorts per call" % total)
+        if total:
+            pair_row, pair_blk = be.empty(total, "i32"), be.empty(total, "i32")
+            be.call("dig_overlap_join_fill", *join, p(offsets), *([] if be.is_device else [total]), p(pair_row), p(pair_blk))
+    keys = be.empty(total, "i64")
+    be.call("dig_window_pair_keys", p(pair_row), p(pair_blk), total, p(blk_window), N, p(row_sample), p(row_uid), p(row_indel), n,
+            S, N, n_uid, p(keys))
+    keys = keys.sort()[0] if be.is_device else np.sort(keys)               # the caller sorts (plumbing, as for dig_gene_counts)
+    hits = be.empty(S, "i32")
+    be.call("dig_window_sample_hits", p(keys), total, S, N, n_uid, p(hits))
+    hits_host = hits.cpu().numpy() if be.is_device else hits
+    keep_host = np.ones(S, np.uint8) if keep_from_hits is None else np.ascontiguousarray(keep_from_hits(hits_host), dtype=np.uint8)
+    if keep_host.shape != (S,):
+        raise ValueError("keep_from_hits: one entry per global sample")
+    labels = be.empty((N, C), "f64")
+    # (named, so that every buffer of the call is alive at once: a tensor dropped here goes back to the allocator and the next one
+    #  may be given its memory)
+    keep, off = be.arr(keep_host, "u8"), be.arr(off_host, "i64")
+    scratch = [be.empty((N, C), "i32")] if be.is_device else []            # (the host twin stages its own)
+    be.call("dig_window_objectives", p(keys), total, p(keep), p(off), S, N, C, n_uid, p(labels), *[p(s) for s in scratch])
+    return dict(labels=labels, hits=hits_host, keep=keep_host)
+
+
 def gene_pipeline(bin_mu, bin_std, bin_y, bin_flag, bin_ctx, ov_ptr, ov_idx, L, strand_minus, gene_length, d_pr, obs, n_samp, cj,
                   t_indel=None):
     """genic_model (genic_driver_tools.py:31-203) + the gene statistics block as one call on device tensors

@@ -16,7 +16,9 @@ HDF5 library writes it with its default ("earliest") format bounds -- which is w
 
 Not supported (raises H5LiteError): dense groups / dense attributes (fractal heaps), compound and reference types,
 layout v4 chunk indexes, external storage, big-endian data.  Files are rewritten whole (`write_tree`); `update` reads
-a file into a tree first.  Cross-checked against h5py 3.3 in both directions (tests/test_h5_io.py).
+a file into a tree first; `append_dataset` alone extends a file in place (a new root-level dataset behind the end of the file:
+training containers are larger than host memory).  Cross-checked against h5py 3.3 in both directions (tests/test_h5_io.py,
+tests/test_h5_append.py).
 
 Structures follow the public "HDF5 File Format Specification Version 3.0".
 """
@@ -720,12 +722,15 @@ def _msg(mtype, data, flags=0):
 class _Writer:
     LEAF_K, INTERNAL_K = 4, 16
 
-    def __init__(self):
-        self.buf = bytearray(96)              # superblock goes here at the end
+    def __init__(self, origin=None):
+        # origin None: a whole file (the superblock goes to the first 96 bytes at the end); a number: the image is a tail that
+        # will sit at that address of an existing file (append_dataset), and every address handed out counts from there
+        self.origin = 0 if origin is None else int(origin)
+        self.buf = bytearray(96 if origin is None else 0)
         self.gheap = []                       # pending vlen objects of the current collection: bytes
 
     def alloc(self, data):
-        off = len(self.buf)
+        off = self.origin + len(self.buf)
         self.buf += data
         self.buf += b"\x00" * (-len(self.buf) % 8)
         return off
@@ -827,12 +832,19 @@ class _Writer:
                 entries.append((name, haddr, 1, struct.pack("<QQ", bt, hp)))
             else:
                 entries.append((name, self.write_dataset(child), 0, b"\x00" * 16))
+        btree, heap_addr = self.symbol_table([(name.encode("utf-8"), haddr, ctype, scratch) for name, haddr, ctype, scratch in entries])
+        msgs = [_msg(0x11, struct.pack("<QQ", btree, heap_addr))] + [self.attribute(k, v) for k, v in g.attrs.items()]
+        return self.object_header(msgs), btree, heap_addr
+
+    def symbol_table(self, entries):
+        """Local heap + SNODs + B-tree of a group whose members are entries = [(name bytes, object header address, cache type,
+        16 scratch bytes)], sorted by name.  Returns (btree, heap address)."""
         # local heap: "" at offset 0, then the names
         heap_data = bytearray(b"\x00" * 8)
         name_off = {}
         for name, _, _, _ in entries:
             name_off[name] = len(heap_data)
-            heap_data += _pad8(name.encode("utf-8") + b"\x00")
+            heap_data += _pad8(name + b"\x00")
         data_addr = self.alloc(bytes(heap_data))
         heap_addr = self.alloc(b"HEAP" + bytes(4) + struct.pack("<QQQ", len(heap_data), 1, data_addr))
         # leaves
@@ -856,22 +868,21 @@ class _Writer:
                 for addr, last in part:
                     node += struct.pack("<QQ", addr, last)
                 node += b"\x00" * (24 + 8 + 16 * fan - len(node))
-                nodes.append([len(self.buf), part[-1][1] if part else 0, node])
-                self.alloc(bytes(node))
+                nodes.append([self.alloc(bytes(node)), part[-1][1] if part else 0, node])
             # sibling pointers and first keys inside one level
             for j, (addr, _, node) in enumerate(nodes):
                 left = nodes[j - 1][0] if j else UNDEF
                 right = nodes[j + 1][0] if j + 1 < len(nodes) else UNDEF
                 first_key = nodes[j - 1][1] if j else 0
-                self.buf[addr + 8:addr + 24] = struct.pack("<QQ", left, right)
-                self.buf[addr + 24:addr + 32] = struct.pack("<Q", first_key)
+                at = addr - self.origin
+                self.buf[at + 8:at + 24] = struct.pack("<QQ", left, right)
+                self.buf[at + 24:at + 32] = struct.pack("<Q", first_key)
             level = [(addr, last) for addr, last, _ in nodes]
             depth += 1
             if len(level) <= 1:
                 break
         btree = level[0][0]
-        msgs = [_msg(0x11, struct.pack("<QQ", btree, heap_addr))] + [self.attribute(k, v) for k, v in g.attrs.items()]
-        return self.object_header(msgs), btree, heap_addr
+        return btree, heap_addr
 
     def finish(self, root):
         haddr, bt, hp = self.write_group(root)
@@ -890,6 +901,120 @@ def write_tree(path, root):
         f.write(data)
     import os
     os.replace(tmp, path)
+
+
+def _root_symbol_table(r, base):
+    """Where the root group of an old-style file keeps its symbol table: (file offset of the superblock's fields behind the
+    versions, file offset of the 16 bytes (B-tree, heap) of the root object header's symbol-table message).  H5LiteError, naming
+    the feature, for a root group that cannot be extended in place."""
+    b = r.b
+    ver = b[base + 8]
+    if ver not in (0, 1):
+        raise H5LiteError("superblock version %d (a file of the new format: new-style root group, link messages) cannot be "
+                          "extended in place" % ver)
+    p = base + 24 + (4 if ver == 1 else 0)
+    hdr = r.u(p + 32 + 8, 8) + r.base_addr
+    if b[hdr:hdr + 4] == b"OHDR":
+        raise H5LiteError("a new-style root group (version 2 object header, link messages) cannot be extended in place")
+    if b[hdr] != 1:
+        raise H5LiteError("object header version %d at %d is not supported" % (b[hdr], hdr))
+    blocks, found, new_style = [(hdr + 16, hdr + 16 + r.u(hdr + 8, 4))], None, None
+    while blocks:
+        lo, hi = blocks.pop(0)
+        q = lo
+        while q + 8 <= hi:
+            mtype, msize = r.u(q, 2), r.u(q + 2, 2)
+            if mtype == 0x10:
+                blocks.append((r.u(q + 8, 8) + r.base_addr, r.u(q + 8, 8) + r.base_addr + r.u(q + 16, 8)))
+            elif mtype == 0x11 and found is None:
+                found = q + 8
+            elif mtype == 0x02:
+                flags = b[q + 8 + 1]
+                dense = r.u(q + 8 + 2 + (8 if flags & 1 else 0), 8) != UNDEF
+                new_style = "dense link storage (fractal heap)" if dense else "a new-style root group (link messages)"
+            elif mtype == 0x06 and new_style is None:
+                new_style = "a new-style root group (link messages)"
+            q += 8 + msize
+    if found is None:
+        raise H5LiteError("%s cannot be extended in place" % (new_style or "a root group without a symbol table"))
+    return p, found
+
+
+def append_dataset(path, name, array):
+    """Add the contiguous dataset `name` to the root group of the existing file `path` WITHOUT reading or rewriting any dataset
+    that is in it (a training container holds a track tensor far larger than host memory; write_tree / update rewrite whole
+    files).  Written behind the end of the file: the dataset's object header and data, and the root group's symbol table anew --
+    a local heap with the names, symbol-table nodes and B-tree nodes for the old members and the new one (a full node splits as a
+    matter of course; the old heap and nodes, a few hundred bytes per member, stay behind as unused space).  Patched in place, after
+    the tail is on disk: the (B-tree, heap) addresses of the root object header's symbol-table message and of the superblock's root
+    entry, and the superblock's end-of-file address.  Old-style root groups only (what h5py, PyTables and write_tree make with the
+    library's default format); H5LiteError names the feature otherwise, and refuses a name that exists."""
+    import mmap
+    import os
+    name = str(name)
+    if not name or "/" in name:
+        raise H5LiteError("append_dataset adds to the root group: %r is not a plain name" % name)
+    key = name.encode("utf-8")
+    with open(path, "r+b") as f:
+        size = os.fstat(f.fileno()).st_size
+        mm = mmap.mmap(f.fileno(), 0, access=mmap.ACCESS_READ)
+        try:
+            r = _Reader(mm)
+            r.read_superblock()
+            base = 0
+            while mm[base:base + 8] != SIG:
+                base = 512 if base == 0 else base * 2
+            p, st_at = _root_symbol_table(r, base)
+            leaf_k, internal_k = r.u(base + 16, 2), r.u(base + 18, 2)
+            if size < r.u(p + 16, 8) + r.base_addr:
+                raise H5LiteError("the file is shorter than its end-of-file address (truncated)")
+            cached = r.u(p + 32 + 16, 4) == 1          # the root entry caches (B-tree, heap) in its scratch space
+            heap = r.u(st_at + 8, 8) + r.base_addr
+            if mm[heap:heap + 4] != b"HEAP":
+                raise H5LiteError("bad local heap")
+            heap_data = r.u(heap + 24, 8) + r.base_addr
+            entries = []
+
+            def walk(node):
+                if mm[node:node + 4] == b"SNOD":
+                    for i in range(r.u(node + 6, 2)):
+                        e = node + 8 + 40 * i
+                        at = heap_data + r.u(e, 8)
+                        entries.append((bytes(mm[at:mm.find(b"\x00", at)]), r.u(e + 8, 8), r.u(e + 16, 4), bytes(mm[e + 24:e + 40])))
+                    return
+                if mm[node:node + 4] != b"TREE" or mm[node + 4] != 0:
+                    raise H5LiteError("bad group B-tree node")
+                for i in range(r.u(node + 6, 2)):
+                    walk(r.u(node + 24 + 8 + 16 * i, 8) + r.base_addr)
+
+            walk(r.u(st_at, 8) + r.base_addr)
+            base_addr = r.base_addr
+        finally:
+            r = None
+            mm.close()
+        if any(e[0] == key for e in entries):
+            raise H5LiteError("Unable to create dataset (name already exists): %r" % name)
+        start = (size + 7) // 8 * 8
+        w = _Writer(origin=start - base_addr)
+        if leaf_k and internal_k:
+            w.LEAF_K, w.INTERNAL_K = leaf_k, internal_k
+        entries.append((key, w.write_dataset(Dataset(np.asarray(array))), 0, b"\x00" * 16))
+        entries.sort(key=lambda e: e[0])
+        btree, heap_addr = w.symbol_table(entries)
+        f.seek(size)
+        f.write(b"\x00" * (start - size) + bytes(w.buf))
+        f.flush()
+        os.fsync(f.fileno())
+        where = struct.pack("<QQ", btree, heap_addr)
+        f.seek(st_at)
+        f.write(where)
+        if cached:
+            f.seek(p + 32 + 24)
+            f.write(where)
+        f.seek(p + 16)
+        f.write(struct.pack("<Q", w.origin + len(w.buf)))
+        f.flush()
+        os.fsync(f.fileno())
 
 
 def update(path, fn):

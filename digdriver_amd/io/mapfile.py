@@ -273,15 +273,25 @@ def array_dtype(path, key):
     return np.load(os.path.join(path, "A." + _safe(key) + ".npy"), mmap_mode="r", allow_pickle=False).dtype
 
 
-def write_array(path, key, arr, **kw):
+def write_array(path, key, arr, append=False, **kw):
     """(compression keywords of the reference's create_dataset calls are accepted and ignored: datasets are written
-    contiguous, which every HDF5 reader handles)"""
+    contiguous, which every HDF5 reader handles)
+    append=True: a NEW root-level array of an existing HDF5 map is added in place (h5lite.append_dataset) -- nothing that is in the
+    file is read or rewritten, which is the only way to add a label vector to a training container larger than host memory.  A
+    directory map, a map that does not exist yet and a map inside an open batch() are written as without it."""
     if _is_h5(path):
         a = np.asarray(arr)
         if a.dtype.kind == "U":
             a = np.char.encode(a, "utf-8")
         elif a.dtype == object:
             a = np.array([str(x).encode("utf-8") for x in a.reshape(-1)]).reshape(a.shape)
+        if append and os.fspath(path) not in _PENDING and os.path.exists(path):
+            _TREE_CACHE.pop(os.fspath(path), None)
+            try:
+                h5lite.append_dataset(path, key.strip("/"), a)
+            except h5lite.H5LiteError as exc:
+                raise MapFileError("%s: %s" % (path, exc)) from exc
+            return
         _h5_update(path, lambda root: root.set(key, h5lite.Dataset(a)))
         return
     _dir_write_array(path, key, arr)

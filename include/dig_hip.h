@@ -341,6 +341,39 @@ int dig_gene_counts_host(const int64_t *keys_sorted, int64_t n, const int32_t *s
                          double max_muts_per_sample, double max_muts_per_gene_per_sample, int64_t tp53, int64_t G, int64_t C,
                          int32_t *obs, int32_t *n_samp, int32_t *extra, int64_t *n_syn, uint8_t *blacklisted, int device);
 
+/* ---- the region model's training labels for many cohorts (additive: the ABI version stays) -------------------- *
+ * scripts/DataExtractor.py:525-572 add_objectives without --cnv: mutation counts per window of the data container's `idx`.  The
+ * (mutation row, window) pairs come from dig_overlap_join_count/fill with the N windows as one-block elements and the rows of all C
+ * cohorts as mutations.  A row carries its global sample (sample_off i64 [C + 1]: a cohort's first global sample, 0 first, n_samples
+ * last), its mutation id -- dense ids of the distinct (CHROM, START, END, REF, ALT) of its cohort, all below n_uid: with the sample
+ * and the window the identity tabulate_muts_per_sample_per_element(drop_duplicates=True) de-duplicates on, mutation_tools.py:208 --
+ * and its indel byte (ANNOT == 'INDEL').
+ *   dig_window_pair_keys: keys i64 [n_pairs], key = global sample << (wb + 1 + ub) | window << (1 + ub) | indel << ub | mutation id,
+ *     ub / wb the bits of n_uid - 1 / N - 1 (DIG_EINVAL when the fields do not fit 63 bits).  The window of a pair is
+ *     blk_window[pair_blk] (blk_window i32 [n_blk]; NULL: the block row itself).  A pair outside the tables gets key -1 and is counted
+ *     nowhere (the host twin refuses it).
+ *   The caller sorts the keys ascending (as for dig_gene_counts).
+ *   dig_window_sample_hits, from the sorted keys: hits i32 [n_samples] = the distinct windows a sample has a row in, SNV or INDEL --
+ *     what SAMPLE.value_counts() is on the reference's (window, sample) frame (filter_samples_by_stdev, filter_hypermut_samples,
+ *     mutation_tools.py:293-316).  The caller forms keep u8 [n_samples] from it.
+ *   dig_window_objectives, from the same keys: labels f64 [N, C] = per window and cohort the number of DISTINCT keys with a clear indel
+ *     bit among the kept samples (DataExtractor.py:559-562).  scratch: i32 [N, C] of device memory.
+ * Every output is zeroed by its call; integer atomics, one per run of lanes with one destination, so order-independent. */
+int dig_window_pair_keys(const int32_t *pair_row, const int32_t *pair_blk, int64_t n_pairs, const int32_t *blk_window, int64_t n_blk,
+                         const int32_t *row_sample, const int32_t *row_uid, const uint8_t *row_indel, int64_t n_rows,
+                         int64_t n_samples, int64_t N, int64_t n_uid, int64_t *keys, void *stream);
+int dig_window_pair_keys_host(const int32_t *pair_row, const int32_t *pair_blk, int64_t n_pairs, const int32_t *blk_window,
+                              int64_t n_blk, const int32_t *row_sample, const int32_t *row_uid, const uint8_t *row_indel,
+                              int64_t n_rows, int64_t n_samples, int64_t N, int64_t n_uid, int64_t *keys, int device);
+int dig_window_sample_hits(const int64_t *keys_sorted, int64_t n_pairs, int64_t n_samples, int64_t N, int64_t n_uid, int32_t *hits,
+                           void *stream);
+int dig_window_sample_hits_host(const int64_t *keys_sorted, int64_t n_pairs, int64_t n_samples, int64_t N, int64_t n_uid,
+                                int32_t *hits, int device);
+int dig_window_objectives(const int64_t *keys_sorted, int64_t n_pairs, const uint8_t *keep, const int64_t *sample_off,
+                          int64_t n_samples, int64_t N, int64_t C, int64_t n_uid, double *labels, int32_t *scratch, void *stream);
+int dig_window_objectives_host(const int64_t *keys_sorted, int64_t n_pairs, const uint8_t *keep, const int64_t *sample_off,
+                               int64_t n_samples, int64_t N, int64_t C, int64_t n_uid, double *labels, int device);
+
 /* ---- sufficient statistics in canonical chunks (bin-sharded runs) --------------------------- *
  * Same quantity as dig_scale_suffstats / dig_scale_factors, defined so that it does not depend on the sharding: the bins
  * are cut into K canonical chunks of the GLOBAL grid (boundaries floor(N j / K)); a rank computes the chunk sums of the
