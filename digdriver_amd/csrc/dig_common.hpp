@@ -33,18 +33,6 @@ int set_error(int code, const char* fmt, ...);
 // number of CUs of the current device (cached per device)
 int cu_count();
 
-// dig_genecounts.hip: the bits of the global-sample field of a gene-count key; DIG_EINVAL (in the name of entry point `fn`) when
-// (cohort (G + 2) + gene, global sample, class) does not fit 63 bits
-int gene_key_layout(const char* fn, int64_t G, int64_t C, int64_t n_samples, int* sample_bits);
-
-// dig_objectives.hip: the fields of a window-count key,
-//   global sample << (window_bits + 1 + uid_bits) | window << (1 + uid_bits) | indel << uid_bits | mutation id;
-// DIG_EINVAL (in the name of entry point `fn`) when they do not fit 63 bits
-struct WindowKeyLayout {
-    int uid_bits, window_bits;
-};
-int window_key_layout(const char* fn, int64_t n_samples, int64_t N, int64_t n_uid, WindowKeyLayout* lay);
-
 // i / C with a host-computed magic multiplier: e = hi64(i * ceil(2^64 / C)), exact while
 // i * C < 2^64 (the per-pair int64 division the flat [E, C] index would otherwise need costs
 // more than a whole recurrence step).

@@ -25,19 +25,11 @@
 // model and of class 5 count for the sample totals (and class 0 ones for n_syn); the observed-count planes never see them.
 #include <algorithm>
 
-#include "dig_common.hpp"
+#include "dig_keyruns.hpp"
 
 namespace dig {
 
 constexpr int kGeneCountBlock = 256;
-
-// bits that hold the values 0 .. n - 1 (at least one)
-inline int bits_for(int64_t n)
-{
-    int b = 1;
-    while (b < 62 && ((int64_t)1 << b) < n) ++b;
-    return b;
-}
 
 struct GeneKeyArgs {
     const int32_t *gene, *sample, *cohort;
@@ -52,7 +44,6 @@ struct GeneKeyArgs {
 __global__ __launch_bounds__(kGeneCountBlock) void gene_row_keys_kernel(GeneKeyArgs a)
 {
     const int64_t i = (int64_t)blockIdx.x * kGeneCountBlock + threadIdx.x;
-    const int lane = threadIdx.x & 63;
     int gs = -1;                                   // the row's global sample; -1: no row here, or a row outside the tables
     if (i < a.n) {
         const int64_t c = a.cohort[i], g = a.gene[i], s = a.sample[i];
@@ -65,15 +56,8 @@ __global__ __launch_bounds__(kGeneCountBlock) void gene_row_keys_kernel(GeneKeyA
         a.keys[i] = key;
     }
     // one add per run of consecutive lanes with the same sample
-    const int left = __shfl_up(gs, 1, 64);
-    const bool head = gs >= 0 && (lane == 0 || left != gs);
-    const unsigned long long heads = __ballot(head), rows = __ballot(gs >= 0);
-    if (head) {
-        // the run ends at the next head or at the next lane without a valid row, whichever comes first
-        const unsigned long long stop = (heads | ~rows) & (lane == 63 ? 0ull : ~0ull << (lane + 1));
-        const int end = stop ? __ffsll((long long)stop) - 1 : 64;
-        atomicAdd(&a.sample_total[gs], end - lane);
-    }
+    const int rows = segment_count(gs, gs >= 0);
+    if (rows) atomicAdd(&a.sample_total[gs], rows);
 }
 
 struct GeneCountArgs {
@@ -158,8 +142,8 @@ int gene_key_layout(const char* fn, int64_t G, int64_t C, int64_t n_samples, int
     DIG_REQUIRE_IN(fn, G >= 0 && C >= 1 && n_samples >= 0, "G >= 0, C >= 1, n_samples >= 0");
     DIG_REQUIRE_IN(fn, G < ((int64_t)1 << 31) - 2 && C < ((int64_t)1 << 31) && n_samples < ((int64_t)1 << 31),
                    "G + 2, C and the sample count below 2^31");
-    *sample_bits = bits_for(n_samples);
-    DIG_REQUIRE_IN(fn, bits_for(C * (G + 2)) + *sample_bits + 3 <= 63,
+    *sample_bits = key_bits_for(n_samples);
+    DIG_REQUIRE_IN(fn, key_bits_for(C * (G + 2)) + *sample_bits + 3 <= 63,
                    "the key (cohort (G + 2) + gene, global sample, class) does not fit 63 bits: fewer cohorts per call");
     return DIG_OK;
 }
@@ -182,9 +166,9 @@ int dig_gene_row_keys(const int32_t* gene, const int32_t* sample, const uint8_t*
     if (n == 0) return DIG_OK;
     DIG_REQUIRE(gene && sample && annot && cohort && keys, "non-null pointers");
     const GeneKeyArgs a{gene, sample, cohort, annot, sample_off, n, G, C, sb, keys, sample_total};
-    const int64_t blocks = (n + kGeneCountBlock - 1) / kGeneCountBlock;
-    DIG_REQUIRE(blocks < ((int64_t)1 << 31), "n below 2^39 rows");
-    hipLaunchKernelGGL(gene_row_keys_kernel, dim3((unsigned)blocks), dim3(kGeneCountBlock), 0, s, a);
+    unsigned blocks = 0;
+    if (int rc = row_blocks(__func__, n, kGeneCountBlock, &blocks)) return rc;
+    hipLaunchKernelGGL(gene_row_keys_kernel, dim3(blocks), dim3(kGeneCountBlock), 0, s, a);
     DIG_HIP_TRY(hipGetLastError());
     return DIG_OK;
 }
@@ -212,11 +196,11 @@ int dig_gene_counts(const int64_t* keys_sorted, int64_t n, const int32_t* sample
     }
     if (n) {
         DIG_REQUIRE(keys_sorted, "non-null keys");
-        const int64_t blocks = (n + kGeneCountBlock - 1) / kGeneCountBlock;
-        DIG_REQUIRE(blocks < ((int64_t)1 << 31), "n below 2^39 rows");
+        unsigned blocks = 0;
+        if (int rc = row_blocks(__func__, n, kGeneCountBlock, &blocks)) return rc;
         const GeneCountArgs a{keys_sorted, n, sample_total, n_samples, max_muts_per_sample, max_muts_per_gene_per_sample, G, C, tp53, sb,
                               obs, n_samp, extra, scratch, reinterpret_cast<unsigned long long*>(n_syn)};
-        hipLaunchKernelGGL(gene_counts_kernel, dim3((unsigned)blocks), dim3(kGeneCountBlock), 0, s, a);
+        hipLaunchKernelGGL(gene_counts_kernel, dim3(blocks), dim3(kGeneCountBlock), 0, s, a);
         DIG_HIP_TRY(hipGetLastError());
     }
     const int64_t m = std::max<int64_t>((int64_t)GC * 5, n_samples);

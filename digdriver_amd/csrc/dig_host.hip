@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "dig_genome2.hpp"
+#include "dig_keyruns.hpp"
 
 using namespace dig;
 
@@ -110,6 +111,20 @@ int check_regions(const char* fn, const int32_t* reg_chrom, const int64_t* reg_s
         DIG_REQUIRE_IN(fn, reg_chrom[r] >= 0 && reg_chrom[r] < n_chrom, "region chromosome index within [0, n_chrom)");
         DIG_REQUIRE_IN(fn, reg_start[r] >= 0 && reg_end[r] >= 0, "non-negative coordinates");
     }
+    return DIG_OK;
+}
+
+// the cohorts' first global samples of the sorted-key twins
+int check_sample_off(const char* fn, const int64_t* sample_off, int64_t C, int64_t n_samples)
+{
+    DIG_REQUIRE_IN(fn, sample_off[0] == 0 && sample_off[C] == n_samples, "sample_off: 0 first, the sample count last");
+    for (int64_t c = 0; c < C; ++c) DIG_REQUIRE_IN(fn, sample_off[c] <= sample_off[c + 1], "sample_off non-decreasing");
+    return DIG_OK;
+}
+
+int check_ascending(const char* fn, const int64_t* keys, int64_t n)
+{
+    for (int64_t i = 1; i < n; ++i) DIG_REQUIRE_IN(fn, keys[i - 1] <= keys[i], "keys ascending (the caller sorts)");
     return DIG_OK;
 }
 
@@ -290,8 +305,7 @@ int dig_gene_row_keys_host(const int32_t* gene, const int32_t* sample, const uin
                 "non-null pointers");
     int sb = 0;
     if (int rc = gene_key_layout(__func__, G, C, n_samples, &sb)) return rc;
-    DIG_REQUIRE(sample_off[0] == 0 && sample_off[C] == n_samples, "sample_off: 0 first, the sample count last");
-    for (int64_t c = 0; c < C; ++c) DIG_REQUIRE(sample_off[c] <= sample_off[c + 1], "sample_off non-decreasing");
+    if (int rc = check_sample_off(__func__, sample_off, C, n_samples)) return rc;
     for (int64_t i = 0; i < n; ++i) {
         DIG_REQUIRE(cohort[i] >= 0 && cohort[i] < C, "cohort within [0, C)");
         DIG_REQUIRE(gene[i] >= 0 && gene[i] <= G + 1, "gene id within [0, G + 1]");
@@ -312,7 +326,7 @@ int dig_gene_counts_host(const int64_t* keys_sorted, int64_t n, const int32_t* s
                 "non-null pointers");
     int sb = 0;
     if (int rc = gene_key_layout(__func__, G, C, n_samples, &sb)) return rc;
-    for (int64_t i = 1; i < n; ++i) DIG_REQUIRE(keys_sorted[i - 1] <= keys_sorted[i], "keys ascending (the caller sorts)");
+    if (int rc = check_ascending(__func__, keys_sorted, n)) return rc;
     const size_t GC = (size_t)G * C;
     Staging st(device);
     return st.call(dig_gene_counts, st.in(keys_sorted, n), n, st.in(sample_total, n_samples), n_samples, max_muts_per_sample,
@@ -350,7 +364,7 @@ int dig_window_sample_hits_host(const int64_t* keys_sorted, int64_t n_pairs, int
     WindowKeyLayout lay;
     if (int rc = window_key_layout(__func__, n_samples, N, n_uid, &lay)) return rc;
     DIG_REQUIRE((n_pairs == 0 || keys_sorted) && (n_samples == 0 || hits), "non-null pointers");
-    for (int64_t i = 1; i < n_pairs; ++i) DIG_REQUIRE(keys_sorted[i - 1] <= keys_sorted[i], "keys ascending (the caller sorts)");
+    if (int rc = check_ascending(__func__, keys_sorted, n_pairs)) return rc;
     Staging st(device);
     return st.call(dig_window_sample_hits, st.in(keys_sorted, n_pairs), n_pairs, n_samples, N, n_uid, st.out(hits, n_samples), nullptr);
 }
@@ -363,9 +377,8 @@ int dig_window_objectives_host(const int64_t* keys_sorted, int64_t n_pairs, cons
     if (int rc = window_key_layout(__func__, n_samples, N, n_uid, &lay)) return rc;
     DIG_REQUIRE(N < ((int64_t)1 << 62) / C, "N C below 2^62");
     DIG_REQUIRE(sample_off && (n_pairs == 0 || keys_sorted) && (n_samples == 0 || keep) && (N == 0 || labels), "non-null pointers");
-    DIG_REQUIRE(sample_off[0] == 0 && sample_off[C] == n_samples, "sample_off: 0 first, the sample count last");
-    for (int64_t c = 0; c < C; ++c) DIG_REQUIRE(sample_off[c] <= sample_off[c + 1], "sample_off non-decreasing");
-    for (int64_t i = 1; i < n_pairs; ++i) DIG_REQUIRE(keys_sorted[i - 1] <= keys_sorted[i], "keys ascending (the caller sorts)");
+    if (int rc = check_sample_off(__func__, sample_off, C, n_samples)) return rc;
+    if (int rc = check_ascending(__func__, keys_sorted, n_pairs)) return rc;
     const size_t NC = (size_t)N * C;
     Staging st(device);
     return st.call(dig_window_objectives, st.in(keys_sorted, n_pairs), n_pairs, st.in(keep, n_samples), st.in(sample_off, C + 1), n_samples,

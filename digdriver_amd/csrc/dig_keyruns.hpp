@@ -1,0 +1,55 @@
+// dig_keyruns.hpp -- what the two sorted-key counting routes (dig_genecounts.hip, dig_objectives.hip) and their host twins share:
+// rows encoded as 63-bit keys, sorted by the caller, counted as runs with one integer atomic per wave segment.
+#pragma once
+#include "dig_common.hpp"
+
+namespace dig {
+
+// bits that hold the values 0 .. n - 1 (at least one)
+inline int key_bits_for(int64_t n)
+{
+    int b = 1;
+    while (b < 62 && ((int64_t)1 << b) < n) ++b;
+    return b;
+}
+
+// dig_genecounts.hip: the bits of the global-sample field of a gene-count key; DIG_EINVAL (in the name of entry point `fn`) when
+// (cohort (G + 2) + gene, global sample, class) does not fit 63 bits
+int gene_key_layout(const char* fn, int64_t G, int64_t C, int64_t n_samples, int* sample_bits);
+
+// dig_objectives.hip: the fields of a window-count key,
+//   global sample << (window_bits + 1 + uid_bits) | window << (1 + uid_bits) | indel << uid_bits | mutation id;
+// DIG_EINVAL (in the name of entry point `fn`) when they do not fit 63 bits
+struct WindowKeyLayout {
+    int uid_bits, window_bits;
+};
+int window_key_layout(const char* fn, int64_t n_samples, int64_t N, int64_t n_uid, WindowKeyLayout* lay);
+
+// the grid of a kernel with one thread per row: a grid dimension stays below 2^31
+inline int row_blocks(const char* fn, int64_t n, int block, unsigned* blocks)
+{
+    const int64_t b = (n + block - 1) / block;
+    DIG_REQUIRE_IN(fn, b < ((int64_t)1 << 31), "fewer than 2^39 rows or pairs");
+    *blocks = (unsigned)b;
+    return DIG_OK;
+}
+
+// The lanes of a wave form segments: maximal runs of consecutive lanes with the same seg >= 0 (seg < 0: a lane without a
+// destination).  On the first lane of a segment: the number of lanes of the segment with `flag`; on every other lane 0.
+// Every lane of the wave must call it.
+__device__ __forceinline__ int segment_count(int64_t seg, bool flag)
+{
+    const int lane = threadIdx.x & 63;
+    const int64_t left = __shfl_up((long long)seg, 1, 64);
+    const bool first = seg >= 0 && (lane == 0 || left != seg);
+    const unsigned long long firsts = __ballot(first), rows = __ballot(seg >= 0), flags = __ballot(flag && seg >= 0);
+    if (!first) return 0;
+    // the segment ends at the next first lane or at the next lane without a destination, whichever comes first
+    const unsigned long long above = lane == 63 ? 0ull : ~0ull << (lane + 1);
+    const unsigned long long stop = (firsts | ~rows) & above;
+    const int end = stop ? __ffsll((long long)stop) - 1 : 64;
+    const unsigned long long mine = (end == 64 ? ~0ull : ((1ull << end) - 1)) & (above | (1ull << lane));
+    return __popcll(flags & mine);
+}
+
+}  // namespace dig

@@ -16,22 +16,15 @@
 //   window_objectives_kernel     one thread per sorted key; a key counts when its indel bit is clear, its left neighbour is another
 //                                key (the de-duplication) and its sample is kept: labels[window, cohort] += 1
 //   window_labels_f64_kernel     int32 -> float64, the dtype the reference stores
-// Both counting kernels sum their flags over the consecutive lanes of a wave that share the destination (segment_count: three
-// ballots and a population count) and issue one integer atomic per segment.  A (sample, window) run is never walked or searched:
+// Both counting kernels sum their flags over the consecutive lanes of a wave that share the destination (segment_count of
+// dig_keyruns.hpp: three ballots and a population count) and issue one integer atomic per segment.  A run is never walked or searched:
 // a run of 700 keys is eleven wave segments, each lane does O(1) work wherever the run starts or ends, and a run that spans
 // waves or workgroups simply adds once per wave.  Integer atomics only: the result does not depend on the order.
-#include "dig_common.hpp"
+#include "dig_keyruns.hpp"
 
 namespace dig {
 
 constexpr int kObjBlock = 256;
-
-inline int obj_bits_for(int64_t n)
-{
-    int b = 1;
-    while (b < 62 && ((int64_t)1 << b) < n) ++b;
-    return b;
-}
 
 // the key's four fields must fit 63 bits
 int window_key_layout(const char* fn, int64_t n_samples, int64_t N, int64_t n_uid, WindowKeyLayout* lay)
@@ -39,9 +32,9 @@ int window_key_layout(const char* fn, int64_t n_samples, int64_t N, int64_t n_ui
     DIG_REQUIRE_IN(fn, n_samples >= 0 && N >= 0 && n_uid >= 0, "n_samples, N, n_uid >= 0");
     DIG_REQUIRE_IN(fn, n_samples < ((int64_t)1 << 31) && N < ((int64_t)1 << 31) && n_uid < ((int64_t)1 << 31),
                    "the sample, window and mutation-id counts below 2^31");
-    lay->uid_bits = obj_bits_for(n_uid);
-    lay->window_bits = obj_bits_for(N);
-    DIG_REQUIRE_IN(fn, obj_bits_for(n_samples) + lay->window_bits + 1 + lay->uid_bits <= 63,
+    lay->uid_bits = key_bits_for(n_uid);
+    lay->window_bits = key_bits_for(N);
+    DIG_REQUIRE_IN(fn, key_bits_for(n_samples) + lay->window_bits + 1 + lay->uid_bits <= 63,
                    "the key (global sample, window, indel bit, mutation id) does not fit 63 bits: fewer cohorts per call");
     return DIG_OK;
 }
@@ -68,24 +61,6 @@ __global__ __launch_bounds__(kObjBlock) void window_pair_keys_kernel(WindowKeyAr
             key = (((s << a.lay.window_bits) | w) << (1 + a.lay.uid_bits)) | ((int64_t)(a.row_indel[r] != 0) << a.lay.uid_bits) | u;
     }
     a.keys[i] = key;
-}
-
-// The lanes of a wave form segments: maximal runs of consecutive lanes with the same seg >= 0 (seg < 0: a lane without a
-// destination).  On the first lane of a segment: the number of lanes of the segment with `flag`; on every other lane 0.
-// Every lane of the wave must call it.
-__device__ __forceinline__ int segment_count(int64_t seg, bool flag)
-{
-    const int lane = threadIdx.x & 63;
-    const int64_t left = __shfl_up((long long)seg, 1, 64);
-    const bool first = seg >= 0 && (lane == 0 || left != seg);
-    const unsigned long long firsts = __ballot(first), rows = __ballot(seg >= 0), flags = __ballot(flag && seg >= 0);
-    if (!first) return 0;
-    // the segment ends at the next first lane or at the next lane without a destination, whichever comes first
-    const unsigned long long above = lane == 63 ? 0ull : ~0ull << (lane + 1);
-    const unsigned long long stop = (firsts | ~rows) & above;
-    const int end = stop ? __ffsll((long long)stop) - 1 : 64;
-    const unsigned long long mine = (end == 64 ? ~0ull : ((1ull << end) - 1)) & (above | (1ull << lane));
-    return __popcll(flags & mine);
 }
 
 struct WindowCountArgs {
@@ -154,14 +129,6 @@ __global__ __launch_bounds__(kObjBlock) void window_labels_f64_kernel(const int3
     for (int64_t i = (int64_t)blockIdx.x * kObjBlock + threadIdx.x; i < n; i += stride) labels[i] = (double)counts[i];
 }
 
-static int obj_blocks(const char* fn, int64_t n, unsigned* blocks)
-{
-    const int64_t b = (n + kObjBlock - 1) / kObjBlock;
-    DIG_REQUIRE_IN(fn, b < ((int64_t)1 << 31), "fewer than 2^39 pairs");
-    *blocks = (unsigned)b;
-    return DIG_OK;
-}
-
 }  // namespace dig
 
 using namespace dig;
@@ -178,7 +145,7 @@ int dig_window_pair_keys(const int32_t* pair_row, const int32_t* pair_blk, int64
     if (n_pairs == 0) return DIG_OK;
     DIG_REQUIRE(pair_row && pair_blk && row_sample && row_uid && row_indel && keys, "non-null pointers");
     unsigned blocks = 0;
-    if (int rc = obj_blocks(__func__, n_pairs, &blocks)) return rc;
+    if (int rc = row_blocks(__func__, n_pairs, kObjBlock, &blocks)) return rc;
     const WindowKeyArgs a{pair_row, pair_blk, blk_window, row_sample, row_uid, row_indel, n_pairs, n_rows, n_blk, n_samples, N, n_uid,
                           lay, keys};
     hipLaunchKernelGGL(window_pair_keys_kernel, dim3(blocks), dim3(kObjBlock), 0, (hipStream_t)stream, a);
@@ -198,7 +165,7 @@ int dig_window_sample_hits(const int64_t* keys_sorted, int64_t n_pairs, int64_t 
     if (n_pairs == 0 || n_samples == 0) return DIG_OK;
     DIG_REQUIRE(keys_sorted, "non-null keys");
     unsigned blocks = 0;
-    if (int rc = obj_blocks(__func__, n_pairs, &blocks)) return rc;
+    if (int rc = row_blocks(__func__, n_pairs, kObjBlock, &blocks)) return rc;
     const WindowCountArgs a{keys_sorted, n_pairs, n_samples, N, 1, lay, nullptr, nullptr, hits};
     hipLaunchKernelGGL(window_sample_hits_kernel, dim3(blocks), dim3(kObjBlock), 0, s, a);
     DIG_HIP_TRY(hipGetLastError());
@@ -220,7 +187,7 @@ int dig_window_objectives(const int64_t* keys_sorted, int64_t n_pairs, const uin
     if (n_pairs && n_samples) {
         DIG_REQUIRE(keys_sorted, "non-null keys");
         unsigned blocks = 0;
-        if (int rc = obj_blocks(__func__, n_pairs, &blocks)) return rc;
+        if (int rc = row_blocks(__func__, n_pairs, kObjBlock, &blocks)) return rc;
         const WindowCountArgs a{keys_sorted, n_pairs, n_samples, N, C, lay, keep, sample_off, scratch};
         hipLaunchKernelGGL(window_objectives_kernel, dim3(blocks), dim3(kObjBlock), 0, s, a);
         DIG_HIP_TRY(hipGetLastError());

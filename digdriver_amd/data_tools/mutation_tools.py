@@ -429,39 +429,19 @@ def read_raw_mutations(f_mut):
 
 def _gene_range_join(r_chrom, r_start, r_end, m_chrom, m_start, m_end, on_device):
     """(mutation row, range row) pairs of the closed overlap of mutations and gene ranges (both 1-based closed, same chromosome
-    label; ranges sorted by (chrom, start)): dig_overlap_join_count / _fill, the device form or the `_host` twins."""
-    from .. import _lib
+    label; ranges sorted by (chrom, start)): engine.overlap_join on the device or through the `_host` twins, as host int64 arrays."""
+    from .. import engine
+    from .._marshal import backend_on
     labels = {lab: i + 1 for i, lab in enumerate(dict.fromkeys(r_chrom.tolist()))}
     rc = np.array([labels[c] for c in r_chrom.tolist()], np.int64)
     codes, uniq = pd.factorize(m_chrom)
     mc = np.array([labels.get(u, 0) for u in uniq], np.int64)[codes] if len(codes) else np.zeros(0, np.int64)
-    rs, re_ = np.asarray(r_start, np.int64) - 1, np.asarray(r_end, np.int64)                # half-open, 0-based
-    ms, me = _lib.as_host(np.asarray(m_start, np.int64) - 1, np.int64), _lib.as_host(m_end, np.int64)
-    if len(rs) == 0 or len(ms) == 0:
-        return np.zeros(0, np.int64), np.zeros(0, np.int64)
+    # half-open, 0-based (the ranges are sorted already: join_blocks keeps their order, a block row is a range row)
+    _, start_key, runmax_key, blk_end = engine.join_blocks(rc, np.asarray(r_start, np.int64) - 1, r_end)
+    pm, pb = engine.overlap_join(backend_on(0, on_device), start_key, runmax_key, blk_end, mc, np.asarray(m_start, np.int64) - 1, m_end)
     if on_device:
-        import torch
-        from . import tabulate_gpu
-        dev = torch.device("cuda", 0)
-        blocks = tabulate_gpu.ElementBlocks(rc, rs, re_, np.arange(len(rs)), len(rs), dev)   # (the ranges are sorted already: order kept)
-        t = lambda a: torch.as_tensor(a, device=dev)
-        pm, pb = tabulate_gpu.overlap_pairs(blocks, t(mc), t(ms), t(me))
-        return pm.cpu().numpy().astype(np.int64), pb.cpu().numpy().astype(np.int64)
-    runmax = np.empty_like(re_)
-    for c in np.unique(rc):
-        sel = rc == c
-        runmax[sel] = np.maximum.accumulate(re_[sel])
-    keys = [_lib.as_host(a, np.int64) for a in ((rc << 40) | rs, (rc << 40) | runmax, re_)]
-    h = _lib.host_ptr
-    counts = np.zeros(len(ms), np.int32)
-    _lib.call("dig_overlap_join_count_host", h(keys[0]), h(keys[1]), h(keys[2]), len(rs), h(mc), h(ms), h(me), len(ms), h(counts), 0)
-    offsets = np.cumsum(counts, dtype=np.int64) - counts
-    total = int(counts.sum(dtype=np.int64))
-    pm, pb = np.zeros(max(total, 1), np.int32), np.zeros(max(total, 1), np.int32)
-    if total:
-        _lib.call("dig_overlap_join_fill_host", h(keys[0]), h(keys[1]), h(keys[2]), len(rs), h(mc), h(ms), h(me), len(ms), h(offsets),
-                  total, h(pm), h(pb), 0)
-    return pm[:total].astype(np.int64), pb[:total].astype(np.int64)
+        pm, pb = pm.cpu().numpy(), pb.cpu().numpy()
+    return pm.astype(np.int64), pb.astype(np.int64)
 
 
 def _snv_function_from_letters(genome, genes, gene_chrom, g, pos, ref, alt):

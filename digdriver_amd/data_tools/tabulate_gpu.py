@@ -10,7 +10,8 @@ dig_overlap_join_{count,fill}; de-duplication and the segmented counts are sort/
 """
 import numpy as np
 
-from .. import _lib
+from .. import engine
+from .._marshal import device_backend
 from . import mutation_tools
 
 
@@ -19,20 +20,11 @@ class ElementBlocks:
 
     def __init__(self, chrom, start, end, elt_id, n_elements, device):
         import torch
-        chrom = np.asarray(chrom, np.int64)
-        start = np.asarray(start, np.int64)
-        end = np.asarray(end, np.int64)
-        end_eff = np.where(end == start, start + 1, end)
-        order = np.lexsort((start, chrom))
-        chrom, start, end_eff, elt_id = chrom[order], start[order], end_eff[order], np.asarray(elt_id, np.int64)[order]
-        runmax = np.empty_like(end_eff)
-        for c in np.unique(chrom):
-            sel = chrom == c
-            runmax[sel] = np.maximum.accumulate(end_eff[sel])
+        order, start_key, runmax_key, end_eff = engine.join_blocks(chrom, start, end)
         t = lambda a: torch.as_tensor(np.ascontiguousarray(a), device=device)
-        self.start_key, self.runmax_key, self.end = t((chrom << 40) | start), t((chrom << 40) | runmax), t(end_eff)
-        self.elt = t(elt_id)
-        self.n_blocks, self.n_elements, self.device = len(start), int(n_elements), device
+        self.start_key, self.runmax_key, self.end = t(start_key), t(runmax_key), t(end_eff)
+        self.elt = t(np.asarray(elt_id, np.int64)[order])
+        self.n_blocks, self.n_elements, self.device = len(order), int(n_elements), device
 
     @classmethod
     def from_bed12(cls, f_bed, device, names=None):
@@ -56,23 +48,7 @@ class ElementBlocks:
 
 def overlap_pairs(blocks, m_chrom, m_start, m_end):
     """(mutation row, block row) pairs on the device: int32 tensors, mutation-major, blocks ascending."""
-    import torch
-    dev = blocks.device
-    n = m_chrom.numel()
-    counts = torch.zeros(n, dtype=torch.int32, device=dev)
-    args = [_lib.dev_ptr(blocks.start_key), _lib.dev_ptr(blocks.runmax_key), _lib.dev_ptr(blocks.end), blocks.n_blocks,
-            _lib.dev_ptr(m_chrom), _lib.dev_ptr(m_start), _lib.dev_ptr(m_end), n]
-    with torch.cuda.device(dev):
-        _lib.call("dig_overlap_join_count", *args, _lib.dev_ptr(counts), _lib.stream_ptr())
-        incl = torch.cumsum(counts, 0, dtype=torch.int64)
-        total = int(incl[-1].item()) if n else 0
-        offsets = (incl - counts).contiguous()
-        pm = torch.empty(max(total, 1), dtype=torch.int32, device=dev)
-        pb = torch.empty(max(total, 1), dtype=torch.int32, device=dev)
-        if total:
-            _lib.call("dig_overlap_join_fill", *args, _lib.dev_ptr(offsets), _lib.dev_ptr(pm), _lib.dev_ptr(pb),
-                      _lib.stream_ptr())
-    return pm[:total], pb[:total]
+    return engine.overlap_join(device_backend(blocks.device), blocks.start_key, blocks.runmax_key, blocks.end, m_chrom, m_start, m_end)
 
 
 def encode_mutations_host(df_mut, cohort_id=0, chrom_ids=None):

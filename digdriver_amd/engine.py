@@ -157,6 +157,61 @@ def gene_selection(alpha, theta, pi, obs, device=0, out=None):
     return {name: out[i] for i, name in enumerate(SEL_PLANES)}
 
 
+def join_blocks(chrom, start, end):
+    """The block table of the interval join (dig_overlap_join_*) from host arrays, in any order: chromosome id, START, END.
+    Returns (order, start_key, runmax_key, end_eff), host int64: `order` sorts the blocks by (chrom, start) (stably: blocks sorted
+    already keep their rows), and in that order end_eff is the block's end, a zero-length block (end == start) lifted to
+    start + 1, start_key = (chrom << 40) | start and runmax_key = (chrom << 40) | the largest end_eff so far on the chromosome."""
+    chrom, start, end = (np.asarray(x, np.int64).ravel() for x in (chrom, start, end))
+    order = np.lexsort((start, chrom))
+    chrom, start, end_eff = chrom[order], start[order], np.where(end == start, start + 1, end)[order]
+    runmax = np.empty_like(end_eff)
+    for c in np.unique(chrom):
+        sel = chrom == c
+        runmax[sel] = np.maximum.accumulate(end_eff[sel])
+    return order, (chrom << 40) | start, (chrom << 40) | runmax, end_eff
+
+
+def overlap_join(be, start_key, runmax_key, blk_end, m_chrom, m_start, m_end, max_pairs=None,
+                 too_many="%d (row, block) pairs: more than max_pairs"):
+    """The interval join of mutation rows (chromosome id, start, end: half-open, int64) with a block table of join_blocks:
+    dig_overlap_join_count, a cumulative sum, dig_overlap_join_fill.  Returns (pair_row, pair_blk): int32, one entry per
+    overlapping (row, block of the sorted table), mutation-major with the blocks ascending; ValueError, before the fill, for
+    more than max_pairs of them, with the caller's text `too_many` (%d: the pair count).  CUDA tensors on the device backend,
+    arrays on the host one."""
+    tabs = [be.arr(x, "i64", (-1,)) for x in (start_key, runmax_key, blk_end, m_chrom, m_start, m_end)]
+    n_blk, n = tabs[0].shape[0], tabs[3].shape[0]
+    assert tabs[1].shape[0] == tabs[2].shape[0] == n_blk and tabs[4].shape[0] == tabs[5].shape[0] == n
+    if n == 0 or n_blk == 0:
+        return be.empty(0, "i32"), be.empty(0, "i32")
+    p = be.ptr
+    join = [p(x) for x in tabs[:3]] + [n_blk] + [p(x) for x in tabs[3:]] + [n]
+    counts = be.empty(n, "i32")
+    be.call("dig_overlap_join_count", *join, p(counts))
+    incl = be.torch.cumsum(counts, 0, dtype=be.torch.int64) if be.is_device else np.cumsum(counts, dtype=np.int64)
+    total, offsets = int(incl[-1]), incl - counts
+    if max_pairs is not None and total > max_pairs:
+        raise ValueError(too_many % total)
+    pair_row, pair_blk = be.empty(total, "i32"), be.empty(total, "i32")
+    if total:
+        be.call("dig_overlap_join_fill", *join, p(offsets), *([] if be.is_device else [total]), p(pair_row), p(pair_blk))
+    return pair_row, pair_blk
+
+
+def _sample_offsets(x, C=None):
+    """sample_offsets (a host array or a CUDA tensor) -> (host int64 [C + 1], C, the sample count S).  C: the cohort count of a
+    caller that was given one (the library refuses C < 1 for it); without it C comes from the length, at least 1."""
+    off = np.ascontiguousarray(np.asarray(x.cpu() if is_cuda(x) else x), dtype=np.int64).ravel()
+    if (len(off) < 2 if C is None else len(off) != C + 1) or off[0] != 0 or (np.diff(off) < 0).any():
+        raise ValueError("sample_offsets: C + 1 non-decreasing entries, 0 first")
+    return off, len(off) - 1, int(off[-1])
+
+
+def _sorted(be, keys):
+    """The keys ascending: the caller of a sorted-key entry point sorts (plumbing, as for dig_bh_qvalues_sorted)."""
+    return keys.sort()[0] if be.is_device else np.sort(keys)
+
+
 def gene_counts(gene, sample, annot, cohort, sample_offsets, G, C, tp53, max_muts_per_sample=3e9, max_muts_per_gene_per_sample=3e9,
                 device=0):
     """The gene route's integer bookkeeping for the coding rows of C cohorts against one gene index of G rows
@@ -173,11 +228,8 @@ def gene_counts(gene, sample, annot, cohort, sample_offsets, G, C, tp53, max_mut
     annot = be.arr(annot, "u8", (-1,))
     n = gene.shape[0]
     assert sample.shape[0] == annot.shape[0] == cohort.shape[0] == n
-    G, C = int(G), int(C)
-    off_host = np.ascontiguousarray(np.asarray(sample_offsets.cpu() if is_cuda(sample_offsets) else sample_offsets), dtype=np.int64).ravel()
-    if len(off_host) != C + 1 or off_host[0] != 0 or (np.diff(off_host) < 0).any():
-        raise ValueError("sample_offsets: C + 1 non-decreasing entries, 0 first")
-    S = int(off_host[-1])
+    G = int(G)
+    off_host, C, S = _sample_offsets(sample_offsets, int(C))
     off = be.arr(off_host, "i64")
     if be.is_device and n:
         # (device tensors are checked here; the host twin checks its own arrays inside the library)
@@ -189,7 +241,7 @@ def gene_counts(gene, sample, annot, cohort, sample_offsets, G, C, tp53, max_mut
     p = be.ptr
     keys, total = be.empty(n, "i64"), be.empty(S, "i32")
     be.call("dig_gene_row_keys", p(gene), p(sample), p(annot), p(cohort), p(off), n, G, C, S, p(keys), p(total))
-    keys = keys.sort()[0] if be.is_device else np.sort(keys)               # the caller sorts (plumbing, as for dig_bh_qvalues_sorted)
+    keys = _sorted(be, keys)
     obs, n_samp, extra = be.empty((G, 5, C), "i32"), be.empty((G, 6, C), "i32"), be.empty((G, 2, C), "i32")
     n_syn, black = be.empty(C, "i64"), be.empty(S, "u8")
     scratch = [p(be.empty((G, 5, C), "i32"))] if be.is_device else []      # (the host twin stages its own)
@@ -210,23 +262,13 @@ def window_objectives(win_chrom, win_start, win_end, row_chrom, row_start, row_e
     Returns dict(labels f64 [N, C]: distinct non-indel mutations of the kept samples per window and cohort; hits, keep: host arrays).
     CUDA tensors in (the row arrays) -> labels as a CUDA tensor."""
     be = backend_of(row_chrom, row_start, row_end, row_sample, row_uid, row_indel, device=device)
-    off_host = np.ascontiguousarray(np.asarray(sample_offsets), dtype=np.int64).ravel()
-    C = len(off_host) - 1
-    if C < 1 or off_host[0] != 0 or (np.diff(off_host) < 0).any():
-        raise ValueError("sample_offsets: C + 1 non-decreasing entries, 0 first")
-    S, n_uid = int(off_host[-1]), int(n_uid)
-    # the windows as join blocks: sorted by (chrom, start), composite keys (tabulate_gpu.ElementBlocks)
+    off_host, C, S = _sample_offsets(sample_offsets)
+    n_uid = int(n_uid)
     wc, ws, we = (np.asarray(x, np.int64).ravel() for x in (win_chrom, win_start, win_end))
     N = len(wc)
     if N and (wc.min() < 0 or wc.max() >= (1 << 22) or ws.min() < 0 or max(ws.max(), we.max()) >= (1 << 40)):
         raise ValueError("windows: chromosome ids within [0, 2^22), coordinates within [0, 2^40)")
-    order = np.lexsort((ws, wc))
-    wc, ws, we = wc[order], ws[order], np.where(we == ws, ws + 1, we)[order]
-    runmax = np.empty_like(we)
-    for c in np.unique(wc):
-        sel = wc == c
-        runmax[sel] = np.maximum.accumulate(we[sel])
-    start_key, runmax_key, blk_end = be.arr((wc << 40) | ws, "i64"), be.arr((wc << 40) | runmax, "i64"), be.arr(we, "i64")
+    order, start_key, runmax_key, blk_end = join_blocks(wc, ws, we)     # the windows as one-block elements
     blk_window = be.arr(order, "i32")
     row_chrom, row_start, row_end = (be.arr(x, "i64", (-1,)) for x in (row_chrom, row_start, row_end))
     row_sample, row_uid = be.arr(row_sample, "i32", (-1,)), be.arr(row_uid, "i32", (-1,))
@@ -238,28 +280,14 @@ def window_objectives(win_chrom, win_start, win_end, row_chrom, row_start, row_e
         bad = (row_sample < 0) | (row_sample >= S) | (row_uid < 0) | (row_uid >= n_uid)
         if bool(bad.any()):
             raise ValueError("a row outside the tables: global sample within [0, S), mutation id within [0, n_uid)")
+    pair_row, pair_blk = overlap_join(be, start_key, runmax_key, blk_end, row_chrom, row_start, row_end, max_pairs=2 ** 31 - 1,
+                                      too_many="%d (mutation, window) pairs: the join's pair indices are 32-bit; fewer cohorts per call")
+    total = pair_row.shape[0]
     p = be.ptr
-    total = 0
-    pair_row = pair_blk = be.empty(0, "i32")
-    if n and N:
-        counts = be.arr(np.zeros(n, np.int32), "i32")
-        join = [p(start_key), p(runmax_key), p(blk_end), N, p(row_chrom), p(row_start), p(row_end), n]
-        be.call("dig_overlap_join_count", *join, p(counts))
-        if be.is_device:
-            incl = be.torch.cumsum(counts, 0, dtype=be.torch.int64)
-            total, offsets = int(incl[-1].item()), (incl - counts).contiguous()
-        else:
-            incl = np.cumsum(counts, dtype=np.int64)
-            total, offsets = int(incl[-1]), incl - counts
-        if total >= 2 ** 31:
-            raise ValueError("%d (mutation, window) pairs: the join's pair indices are 32-bit; fewer cohorts per call" % total)
-        if total:
-            pair_row, pair_blk = be.empty(total, "i32"), be.empty(total, "i32")
-            be.call("dig_overlap_join_fill", *join, p(offsets), *([] if be.is_device else [total]), p(pair_row), p(pair_blk))
     keys = be.empty(total, "i64")
     be.call("dig_window_pair_keys", p(pair_row), p(pair_blk), total, p(blk_window), N, p(row_sample), p(row_uid), p(row_indel), n,
             S, N, n_uid, p(keys))
-    keys = keys.sort()[0] if be.is_device else np.sort(keys)               # the caller sorts (plumbing, as for dig_gene_counts)
+    keys = _sorted(be, keys)
     hits = be.empty(S, "i32")
     be.call("dig_window_sample_hits", p(keys), total, S, N, n_uid, p(hits))
     hits_host = hits.cpu().numpy() if be.is_device else hits

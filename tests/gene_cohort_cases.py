@@ -61,6 +61,27 @@ def long_run_case(tmp):
     return dict(files=files, C=2, max_muts_per_sample=3e9, max_muts_per_gene_per_sample=500)
 
 
+# (sample, rows) runs of lane_run_case, in file order.  Rows 0 .. 599 in workgroups of 256 rows and waves of 64:
+#   sample 0 starts at lane 0 and comes back in a second run (10 + 46 rows); 1 starts in the middle of a wave; 3 is one row at lane
+#   63 and 4 one row at lane 0; 6 (56 rows) crosses a wave boundary (row 128) and 8 (55 rows) a workgroup boundary (row 256); 9 and
+#   10 are single rows side by side; 12 (56 rows) ends at lane 63 (row 383); 13 fills three whole waves; 14 is row 576, lane 0 of the
+#   last wave.  The totals of the runs on the edges are 55 and 56, so that under the limits 54, 55 and 56 each of them is once the
+#   limit and once the limit + 1: one lane lost or counted twice changes a blacklist byte.
+LANE_RUNS = [(0, 10), (1, 30), (2, 23), (3, 1), (4, 1), (5, 35), (6, 56), (0, 46), (7, 28), (8, 55), (9, 1), (10, 1), (11, 41), (12, 56),
+             (13, 192), (14, 1), (15, 23)]
+LANE_RUN_LIMITS = (54, 55, 56)
+
+
+def lane_run_case(tmp, n, limit):
+    """One cohort whose first n rows (600: all; 577: row 576 is alone in its wave) are those of LANE_RUNS, every row a coding row
+    that every reader keeps; genes of the model and one outside it, all six classes, a per-gene-per-sample cap of 2."""
+    sample = np.repeat([s for s, _ in LANE_RUNS], [k for _, k in LANE_RUNS])[:n]
+    genes = GENES + ["OUT1"]
+    rows = [("1", 1000 + 10 * i, 1001 + 10 * i, "A", "C", "R%02d" % s, genes[i % 13], _ANNOTS[(i // 3) % 6]) for i, s in enumerate(sample)]
+    return dict(files=[write_rows(tmp / ("lanes%d.tsv" % n), rows)], C=1, max_muts_per_sample=limit,
+                max_muts_per_gene_per_sample=2, sample=sample)
+
+
 def coding_tuples(f_mut):
     """(gene, sample, annot) of the coding rows of a file, as the serial route reads them."""
     from digdriver_amd.driver_model import transfer_tools as tt

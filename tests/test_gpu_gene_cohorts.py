@@ -77,6 +77,30 @@ def test_gene_counts_match_the_statement_in_both_forms(which, small, long_run):
         assert sum(len(b) for b in want["blacklist"]) == 1 and want["obs"][:, 4, 2].sum() == 0
 
 
+@pytest.mark.parametrize("n", [600, 577])
+def test_sample_totals_of_runs_placed_on_the_wave_and_workgroup_edges(tmp_path, n):
+    """dig_gene_row_keys adds a sample's rows once per run of consecutive lanes (segment_count): the runs of K.LANE_RUNS start at
+    lane 0 and in mid-wave, end at lane 63, cross a wave and a workgroup boundary, are one row long, and one sample has two of them;
+    the lanes behind row n - 1 hold no row (n = 577: the last row is alone in its wave).  The per-sample totals decide
+    `blacklisted`, and under the three limits every run on an edge is once at the limit and once one above it; long_run above has
+    one 700-row run at the end of random rows and no limit."""
+    for limit in K.LANE_RUN_LIMITS:
+        case = K.lane_run_case(tmp_path, n, limit)
+        want = K.statement_planes(case)
+        dev, offsets, names = _counts(case, True)
+        host, _, _ = _counts(case, False)
+        sample = _encoded(case)[0]["sample"]
+        assert np.array_equal(sample, case["sample"][:n]) and offsets.tolist() == [0, sample.max() + 1]      # ids by first appearance
+        total = np.bincount(sample)
+        assert total[[0, 6, 8, 12]].tolist() == [56, 56, 55, 56] and limit in (total[8] - 1, total[8], total[6])
+        assert np.array_equal(dev["blacklisted"], (total > limit).astype(np.uint8)), limit
+        for k in ("obs", "n_samp", "n_syn", "n_samp_indel", "n_pairs"):
+            assert dev[k].dtype == want[k].dtype and np.array_equal(dev[k], want[k]), (limit, k)
+        for k in dev:
+            assert host[k].dtype == dev[k].dtype and np.array_equal(host[k], dev[k]), (limit, k)
+        assert want["obs"].sum() > 0 and sorted(n_ for n_, b in zip(names[0], dev["blacklisted"]) if b) == want["blacklist"][0]
+
+
 def test_a_fractional_cap_is_clipped_as_a_number_then_cast(small):
     """3, 4 and 1 Missense rows of one gene in three samples under a cap of 2.5: int(2.5 + 2.5 + 1) = 6."""
     from digdriver_amd import engine

@@ -346,3 +346,22 @@ def test_two_bit_genome_against_a_brute_force_walk_and_its_disk_cache(tmp_path):
     os.utime(str(fa), None)
     g3 = PackedGenome.from_fasta(str(fa))
     assert len(g3.two_bit()[1]) == 2 and g3.lengths.tolist() == [10]  # the run of two N and the alignment padding behind the chromosome
+
+
+def test_join_blocks_sorts_lifts_and_restarts_the_running_maximum():
+    """engine.join_blocks against a plain statement on the block table of test_gpu_overlap_join.py: the stable (chrom, start)
+    order, the zero-length block lifted to one base, the running maximum of the ends restarting on every chromosome."""
+    import overlap_join_cases as K
+    from digdriver_amd import engine
+    c, s, e = K.block_table()
+    order, start_key, runmax_key, end_eff = engine.join_blocks(c, s, e)
+    want = np.array(sorted(range(len(c)), key=lambda i: (c[i], s[i], i)))
+    eff = np.where(e == s, s + 1, e)[want]
+    runmax = np.array([eff[:j + 1][c[want][:j + 1] == c[want][j]].max() for j in range(len(c))])
+    assert np.array_equal(order, want) and not np.array_equal(want, np.arange(len(c)))
+    assert np.array_equal(end_eff, eff) and (e == s).sum() == 1 and (end_eff > s[want]).all()
+    assert np.array_equal(start_key, (c[want] << 40) | s[want]) and np.array_equal(runmax_key, (c[want] << 40) | runmax)
+    first = np.flatnonzero(np.diff(c[want], prepend=0))                              # the first block of each chromosome
+    assert len(first) == 3 and np.array_equal(runmax[first], eff[first]) and not np.array_equal(runmax, np.maximum.accumulate(eff))
+    assert (runmax > eff).any()                                                      # nested blocks under a longer one
+    assert all(a.dtype == np.int64 for a in (order, start_key, runmax_key, end_eff))

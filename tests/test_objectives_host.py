@@ -170,3 +170,19 @@ def test_command_line_takes_the_references_arguments_and_refuses_cnv(tmp_path):
         cli.add_objectives(cli.parse_args(["addObjectives", "d.h5", "m.txt", "--cnv"]))
     with pytest.raises(SystemExit):
         cli.parse_args(["addTracks", "d.h5"])
+
+
+def test_too_many_pairs_is_refused_in_window_objectives_own_words(monkeypatch):
+    """engine.window_objectives hands the join its limit (pair indices are 32-bit) and its refusal; no device work in front of it."""
+    from digdriver_amd import engine
+    seen = {}
+
+    def join(be, *tables, max_pairs=None, too_many=None):
+        seen.update(max_pairs=max_pairs, rows=len(tables[3]))
+        raise ValueError(too_many % (max_pairs + 1))
+    monkeypatch.setattr(engine, "overlap_join", join)
+    z = np.zeros(3, np.int64)
+    with pytest.raises(ValueError) as exc:
+        engine.window_objectives([1, 1], [0, 100], [100, 200], z + 1, z, z + 1, z, z, z, [0, 1], 1)
+    assert str(exc.value) == "2147483648 (mutation, window) pairs: the join's pair indices are 32-bit; fewer cohorts per call"
+    assert seen == dict(max_pairs=2 ** 31 - 1, rows=3)
