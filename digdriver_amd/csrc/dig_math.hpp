@@ -1084,7 +1084,9 @@ __device__ __forceinline__ double fisher_combine(double p1, double p2)
     if (isnan(h)) return dnan();
     if (h < 0.0) return 1.0;
     if (isinf(h)) return 0.0;
-    return exp(-h) * (1.0 + h);
+    // one exponential of log1p(h) - h, not exp(-h) (1 + h): below 1e-305 exp(-h) is subnormal and its rounding, times 1 + h ~ 700,
+    // put up to 350 units of 2^-1074 on the result (a factor 2 at fisher(2^-1074, 0.5))
+    return exp(log1p(h) - h);
 }
 
 // scipy.stats.chi2.sf(x, df) for df = 1 and 2 (the likelihood-ratio tests of the gene route's selection block):

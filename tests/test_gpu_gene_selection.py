@@ -1,7 +1,9 @@
 """GPU tests of the gene route's dN/dS correction and selection tests (dig_gene_selection) against the reference's own
 functions: tests/golden/gene_selection_golden.npz holds the 34 columns gene_expected_muts_dnds, gene_pvalue_burden_dnds,
 gene_pvalue_sel_nb, gene_pvalue_sel_gamma and selection_coefficient wrote for 1 000 genes + an edge block x 3 cohorts
-(tests/golden/make_selection_golden.py).  Tolerance: conftest.rel_close, rtol 1e-6, floor 1e-250, matching NaN positions."""
+(tests/golden/make_selection_golden.py).  Tolerance: conftest.rel_close, rtol 1e-6, floor 1e-250, matching NaN positions; the 14
+arithmetic planes (T_SYN, MRFOLD, EXP_c_ML, SEL_c) are the reference's bits.  tests/test_gpu_gene_selection_routes.py holds the
+p-value planes to 80-digit references."""
 import os
 import subprocess
 import sys
@@ -52,6 +54,9 @@ def _check_planes(got, gold):
             rel_close(got[i], gold["planes"][i], 1e-6)
         except AssertionError as exc:
             raise AssertionError("%s: %s" % (name, exc))
+        # pure arithmetic, contraction off: every operation rounds as the reference's numpy operation does
+        if name in ("T_SYN", "MRFOLD") or name.startswith(("EXP_", "SEL_")):
+            assert np.array_equal(got[i], gold["planes"][i], equal_nan=True), "%s: not the reference's bits" % name
 
 
 def test_device_entry_matches_the_reference_planes(gold, device_planes):
