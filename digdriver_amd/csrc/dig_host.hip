@@ -385,6 +385,23 @@ int dig_window_objectives_host(const int64_t* keys_sorted, int64_t n_pairs, cons
                    N, C, n_uid, st.out(labels, NC), static_cast<int32_t*>(st.scratch(NC * sizeof(int32_t))), nullptr);
 }
 
+int dig_sequence_counts_host(const int32_t* pair_row, int64_t n_pairs, const int32_t* row_type, const int32_t* row_cohort, int64_t n,
+                             int64_t K, int64_t C, int64_t* counts, int device)
+{
+    DIG_REQUIRE(n_pairs >= 0 && n >= 0, "n_pairs, n >= 0");
+    DIG_REQUIRE(K >= 1 && K <= kSeqMaxK, "K within [1, 3072] (the workgroup's LDS counters)");
+    DIG_REQUIRE(C >= 1 && C < ((int64_t)1 << 31), "C within [1, 2^31)");
+    DIG_REQUIRE(counts && (n == 0 || (row_type && row_cohort)) && (n_pairs == 0 || pair_row), "non-null pointers");
+    for (int64_t r = 0; r < n; ++r) {
+        DIG_REQUIRE(row_cohort[r] >= 0 && row_cohort[r] < C, "cohort within [0, C)");
+        DIG_REQUIRE(row_type[r] >= 0 && row_type[r] <= K, "type within [0, K] (K: no table entry)");
+    }
+    for (int64_t i = 0; i < n_pairs; ++i) DIG_REQUIRE(pair_row[i] >= 0 && pair_row[i] < n, "a pair within the rows");
+    Staging st(device);
+    return st.call(dig_sequence_counts, st.in(pair_row, n_pairs), n_pairs, st.in(row_type, n), st.in(row_cohort, n), n, K, C,
+                   st.out(counts, (size_t)C * K), nullptr);
+}
+
 int dig_scale_suffstats_host(const double* bin_mu, const uint8_t* bin_flag, int64_t N, int64_t C, double* out_sum, int device)
 {
     DIG_REQUIRE(N >= 0 && C >= 0, "N, C >= 0");

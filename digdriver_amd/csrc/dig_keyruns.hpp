@@ -1,4 +1,4 @@
-// dig_keyruns.hpp -- what the two sorted-key counting routes (dig_genecounts.hip, dig_objectives.hip) and their host twins share:
+// dig_keyruns.hpp -- what the counting routes (dig_genecounts.hip, dig_objectives.hip, dig_seqcounts.hip) and their host twins share:
 // rows encoded as 63-bit keys, sorted by the caller, counted as runs with one integer atomic per wave segment.
 #pragma once
 #include "dig_common.hpp"
@@ -24,6 +24,9 @@ struct WindowKeyLayout {
     int uid_bits, window_bits;
 };
 int window_key_layout(const char* fn, int64_t n_samples, int64_t N, int64_t n_uid, WindowKeyLayout* lay);
+
+// dig_seqcounts.hip: the most table rows K a call takes -- a workgroup's LDS counters, 12 KB: the penta-nucleotide table
+constexpr int kSeqMaxK = 3072;
 
 // the grid of a kernel with one thread per row: a grid dimension stays below 2^31
 inline int row_blocks(const char* fn, int64_t n, int block, unsigned* blocks)

@@ -172,6 +172,14 @@ def join_blocks(chrom, start, end):
     return order, (chrom << 40) | start, (chrom << 40) | runmax, end_eff
 
 
+def _window_blocks(win_chrom, win_start, win_end):
+    """Windows (chromosome id, START, END: host arrays in any order) as the one-block elements of join_blocks."""
+    wc, ws, we = (np.asarray(x, np.int64).ravel() for x in (win_chrom, win_start, win_end))
+    if len(wc) and (wc.min() < 0 or wc.max() >= (1 << 22) or ws.min() < 0 or max(ws.max(), we.max()) >= (1 << 40)):
+        raise ValueError("windows: chromosome ids within [0, 2^22), coordinates within [0, 2^40)")
+    return join_blocks(wc, ws, we)
+
+
 def overlap_join(be, start_key, runmax_key, blk_end, m_chrom, m_start, m_end, max_pairs=None,
                  too_many="%d (row, block) pairs: more than max_pairs"):
     """The interval join of mutation rows (chromosome id, start, end: half-open, int64) with a block table of join_blocks:
@@ -264,11 +272,8 @@ def window_objectives(win_chrom, win_start, win_end, row_chrom, row_start, row_e
     be = backend_of(row_chrom, row_start, row_end, row_sample, row_uid, row_indel, device=device)
     off_host, C, S = _sample_offsets(sample_offsets)
     n_uid = int(n_uid)
-    wc, ws, we = (np.asarray(x, np.int64).ravel() for x in (win_chrom, win_start, win_end))
-    N = len(wc)
-    if N and (wc.min() < 0 or wc.max() >= (1 << 22) or ws.min() < 0 or max(ws.max(), we.max()) >= (1 << 40)):
-        raise ValueError("windows: chromosome ids within [0, 2^22), coordinates within [0, 2^40)")
-    order, start_key, runmax_key, blk_end = join_blocks(wc, ws, we)     # the windows as one-block elements
+    order, start_key, runmax_key, blk_end = _window_blocks(win_chrom, win_start, win_end)
+    N = len(order)
     blk_window = be.arr(order, "i32")
     row_chrom, row_start, row_end = (be.arr(x, "i64", (-1,)) for x in (row_chrom, row_start, row_end))
     row_sample, row_uid = be.arr(row_sample, "i32", (-1,)), be.arr(row_uid, "i32", (-1,))
@@ -301,6 +306,41 @@ def window_objectives(win_chrom, win_start, win_end, row_chrom, row_start, row_e
     scratch = [be.empty((N, C), "i32")] if be.is_device else []            # (the host twin stages its own)
     be.call("dig_window_objectives", p(keys), total, p(keep), p(off), S, N, C, n_uid, p(labels), *[p(s) for s in scratch])
     return dict(labels=labels, hits=hits_host, keep=keep_host)
+
+
+def sequence_counts(win_chrom, win_start, win_end, row_chrom, row_start, row_end, row_type, row_cohort, K, C, device=0):
+    """The sequence model's sufficient statistic for C cohorts at once (scripts/DigPretrain.py:179-208 sequenceModel): per cohort the
+    K counts of (MUT_TYPE, CONTEXT) over the rows that lie in at least one window -- dig_overlap_join_count/fill of all cohorts' rows
+    with the windows as one-block elements, then dig_sequence_counts.
+    Windows: chromosome id i64, START, END (host arrays, any order, doubled or overlapping; the rows' chromosome ids name the same
+    chromosomes).  Rows: chrom, start, end i64; type i32 = the row's row of mk_mutation_context, K for a label pair the table does
+    not hold; cohort i32 within [0, C).  A row counts once however many windows hold it: the reference's rule for one-base rows
+    (restrict_mutations_by_bed(unique=True)); the caller keeps other rows out (sequence_tools.train_sequence_models).
+    Returns counts i64 [C, K]; CUDA tensors in (the row arrays) -> a CUDA tensor."""
+    be = backend_of(row_chrom, row_start, row_end, row_type, row_cohort, device=device)
+    K, C = int(K), int(C)
+    _, start_key, runmax_key, blk_end = _window_blocks(win_chrom, win_start, win_end)
+    row_chrom, row_start, row_end = (be.arr(x, "i64", (-1,)) for x in (row_chrom, row_start, row_end))
+    row_type, row_cohort = be.arr(row_type, "i32", (-1,)), be.arr(row_cohort, "i32", (-1,))
+    n = row_chrom.shape[0]
+    assert row_start.shape[0] == row_end.shape[0] == row_type.shape[0] == row_cohort.shape[0] == n
+    if be.is_device:
+        # (device tensors are checked here; the host twin checks its own arrays inside the library)
+        if K < 1 or C < 1:
+            raise ValueError("K >= 1, C >= 1")
+        if n and bool(((row_cohort < 0) | (row_cohort >= C) | (row_type < 0) | (row_type > K)).any()):
+            raise ValueError("a row outside the tables: cohort within [0, C), type within [0, K]")
+    pair_row, _ = overlap_join(be, start_key, runmax_key, blk_end, row_chrom, row_start, row_end, max_pairs=2 ** 31 - 1,
+                               too_many="%d (row, window) pairs: the join's pair indices are 32-bit; fewer cohorts per call")
+    p = be.ptr
+    counts = be.empty((max(C, 0), max(K, 0)), "i64")
+    try:
+        be.call("dig_sequence_counts", p(pair_row), pair_row.shape[0], p(row_type), p(row_cohort), n, K, C, p(counts))
+    except _lib.DigHipError as exc:
+        if "requirement failed" in str(exc):
+            raise ValueError(str(exc)) from exc
+        raise
+    return counts
 
 
 def gene_pipeline(bin_mu, bin_std, bin_y, bin_flag, bin_ctx, ov_ptr, ov_idx, L, strand_minus, gene_length, d_pr, obs, n_samp, cj,

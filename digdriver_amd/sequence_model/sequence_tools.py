@@ -124,6 +124,104 @@ def train_sequence_model(regions, df_mut, genome_counts, n_up=1, n_down=1, key_p
 
 
 # ---------------------------------------------------------------------------------------------
+# sequence models of many cohorts in one pass (reference: DigPretrain.py sequenceModel, one cohort per process)
+# ---------------------------------------------------------------------------------------------
+_TYPE_TABLES = {}
+
+
+def _type_table(n_up, n_down):
+    """(MUT_TYPE label -> row, CONTEXT label -> column, table i32 [13, n_contexts + 1], K): table[row, column] is the row of
+    mk_mutation_context(n_up, n_down) that holds the label pair, K where it holds none; the last row and column stand for a label
+    the model does not know."""
+    if (n_up, n_down) not in _TYPE_TABLES:
+        df = mk_mutation_context(n_up=n_up, n_down=n_down, collapse=False, return_df=True)
+        muts = {m: i for i, m in enumerate(dict.fromkeys(df.MUT_TYPE))}
+        ctxs = {c: i for i, c in enumerate(dict.fromkeys(df.CONTEXT))}
+        table = np.full((len(muts) + 1, len(ctxs) + 1), len(df), np.int32)
+        table[[muts[m] for m in df.MUT_TYPE], [ctxs[c] for c in df.CONTEXT]] = np.arange(len(df), dtype=np.int32)
+        _TYPE_TABLES[(n_up, n_down)] = (muts, ctxs, table, len(df))
+    return _TYPE_TABLES[(n_up, n_down)]
+
+
+def _label_codes(values, ids):
+    """Per value its id, len(ids) for a value without one (a missing label included)."""
+    codes, uniq = pd.factorize(values)
+    of_uniq = np.array([ids.get(u, len(ids)) for u in uniq] + [len(ids)], np.int64)          # (code -1, a missing label: the last entry)
+    return of_uniq[codes]
+
+
+def encode_sequence_rows(f_mut, chrom_ids, n_up=1, n_down=1):
+    """An annotated mutation file (10 or 11 columns: ... ANNOT MUT_TYPE CONTEXT) as the arrays engine.sequence_counts takes, for one
+    cohort: the rows DigPretrain.py sequenceModel counts from -- read_mutation_file(drop_duplicates=True): autosomes, the first row
+    of every (CHROM, START, END, REF, ALT, SAMPLE), unique indels -- without ANNOT == 'INDEL'.  Chromosomes are compared as the join
+    compares them, as text, with `chrom_ids` (label -> id of the windows' chromosomes); rows on other chromosomes can join nothing
+    and are left out.
+    Returns dict(chrom, start, end i64; type i32: the row of mk_mutation_context(n_up, n_down) with the row's (MUT_TYPE, CONTEXT),
+    K for a pair the table does not hold; one_base: whether every kept row has END - START == 1, the rows a window holds whole or
+    not at all; frame: the kept rows as a frame when one_base is False -- such a cohort is counted by the serial statement)."""
+    df = mutation_tools.read_mutation_file(f_mut, drop_duplicates=True)
+    df = df[df.ANNOT != 'INDEL']
+    one_base = bool((df.END.values - df.START.values == 1).all())
+    muts, ctxs, table, _K = _type_table(n_up, n_down)
+    ch = _label_codes(df.CHROM.values.astype(str), {label: i for i, label in enumerate(chrom_ids)})
+    known = ch < len(chrom_ids)
+    ch = np.array(list(chrom_ids.values()) + [0], np.int64)[ch]
+    t = table[_label_codes(df.MUT_TYPE.values, muts), _label_codes(df.CONTEXT.values, ctxs)]
+    return dict(chrom=ch[known], start=df.START.to_numpy(np.int64)[known], end=df.END.to_numpy(np.int64)[known],
+                type=np.ascontiguousarray(t[known], np.int32), one_base=one_base, frame=None if one_base else df)
+
+
+def train_sequence_models(f_muts, idx, mappability, genome_counts_frame, map_thresh=0.5, n_up=1, n_down=1, on_device=None, device=0):
+    """DigPretrain.py sequenceModel (:179-208) for the cohorts `f_muts` (annotated mutation files) in one pass: idx [N, 3] ints
+    (CHROM, START, END), mappability [N] and genome_counts_frame (all_window_genome_counts: a row per window, a column per context)
+    as the genome-counts container holds them.  The whitelist is the windows with mappability > map_thresh; S_genome, the column sum
+    of the frame over them, is formed once.  The substitution counts of all cohorts come from one engine.sequence_counts call
+    (dig_overlap_join_* + dig_sequence_counts), whose rule -- a row counts once when a whitelisted window holds it -- is the
+    reference's for one-base rows.  A cohort with a kept row of another length (a multi-base substitution carrying an SNV class, an
+    empty interval), of which the reference counts every distinct clipped piece, is counted on the host by the serial statement
+    (restrict_mutations_by_bed + sequence_model_counts) and named in the result.
+    on_device: True = device tensors and the device entry points, False = numpy and the `_host` twins (no torch), None = the device
+    unless the process is torch-free.
+    Returns (models, counts, serial): models[c] = (df_freq_mut, df_freq_context) of train_sequence_model for f_muts[c], counts i64
+    [C, K] in the model's row order, serial = the indices of the cohorts counted on the host."""
+    from .. import _lib, engine
+    f_muts = [f_muts] if isinstance(f_muts, (str, bytes)) or hasattr(f_muts, "__fspath__") else list(f_muts)
+    if not f_muts:
+        raise ValueError("no mutation file")
+    idx = np.asarray(idx)
+    if idx.ndim != 2 or idx.shape[1] != 3 or idx.dtype.kind not in "iu":
+        raise ValueError("idx: an integer array [N, 3] of CHROM, START, END")
+    keep = np.asarray(mappability).reshape(-1) > map_thresh
+    if len(keep) != len(idx) or len(genome_counts_frame) != len(idx):
+        raise ValueError("idx, mappability and the genome counts: one row per window")
+    S_genome = genome_counts_frame[keep].sum(axis=0)
+    white = idx[keep].astype(np.int64)
+    chrom_ids = {str(c): int(c) for c in np.unique(white[:, 0])}
+    C, K = len(f_muts), _type_table(n_up, n_down)[3]
+    cohorts = [encode_sequence_rows(f, chrom_ids, n_up, n_down) for f in f_muts]
+    serial = [c for c in range(C) if not cohorts[c]["one_base"]]
+    batch = [c for c in range(C) if cohorts[c]["one_base"]]
+    cat = lambda k, dt: np.concatenate([np.asarray(cohorts[c][k], dt) for c in batch] + [np.zeros(0, dt)])
+    rows = [cat("chrom", np.int64), cat("start", np.int64), cat("end", np.int64), cat("type", np.int32),
+            np.repeat(np.array(batch, np.int32), [len(cohorts[c]["type"]) for c in batch])]
+    dev = (not _lib.TORCH_FREE) if on_device is None else bool(on_device)
+    if dev:
+        import torch
+        from .._marshal import resolve_device
+        rows = [torch.as_tensor(r, device=resolve_device(device)) for r in rows]
+    counts = engine.sequence_counts(white[:, 0], white[:, 1], white[:, 2], *rows, K, C, device=device)
+    counts = np.array(counts.cpu().numpy() if dev else counts, np.int64)
+    df_bed = pd.DataFrame(white, columns=['CHROM', 'START', 'END'])
+    for c in serial:
+        df_mut = cohorts[c]["frame"]
+        inside = mutation_tools.restrict_mutations_by_bed(df_mut, df_bed, unique=True, remove_X=False)
+        inside.columns = df_mut.columns
+        counts[c] = sequence_model_counts(inside, n_up=n_up, n_down=n_down)[1]
+    models = [train_sequence_model(None, None, S_genome, n_up=n_up, n_down=n_down, counts=counts[c]) for c in range(C)]
+    return models, counts, serial
+
+
+# ---------------------------------------------------------------------------------------------
 # context counting from sequence on the GPU (reference: pysam fetch + Python loop per region)
 # ---------------------------------------------------------------------------------------------
 _GENOMES = {}

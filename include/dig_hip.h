@@ -374,6 +374,23 @@ int dig_window_objectives(const int64_t *keys_sorted, int64_t n_pairs, const uin
 int dig_window_objectives_host(const int64_t *keys_sorted, int64_t n_pairs, const uint8_t *keep, const int64_t *sample_off,
                                int64_t n_samples, int64_t N, int64_t C, int64_t n_uid, double *labels, int device);
 
+/* ---- the sequence model's substitution counts for many cohorts (additive: the ABI version stays) --------------- *
+ * scripts/DigPretrain.py:179-208 sequenceModel: per cohort the K counts of (MUT_TYPE, CONTEXT) -- the rows of mk_mutation_context,
+ * K = 192 or 3 072 -- over the rows that lie in a whitelisted window.  The (row, window) pairs come from dig_overlap_join_count/fill
+ * with the windows as one-block elements and the rows of all C cohorts as mutations: mutation-major, so a row's pairs are
+ * consecutive.  A row carries its table row (row_type i32, 0 .. K - 1; K = no table entry: counted nowhere) and its cohort
+ * (row_cohort i32, 0 .. C - 1).
+ *   dig_sequence_counts: counts i64 [C, K] = per cohort and type the rows with at least one pair -- a pair counts when its left
+ *     neighbour belongs to another row.  Exact for one-base rows (END - START == 1), which restrict_mutations_by_bed(unique=True)
+ *     keeps once however many windows hold them (mutation_tools.py:8-30).  1 <= K <= 3 072, C >= 1 (DIG_EINVAL otherwise).  A row or
+ *     pair outside the tables is counted nowhere (the host twin refuses it).
+ * counts is zeroed by the call; nothing is launched for n_pairs == 0.  A workgroup counts one cohort in 32-bit LDS counters and
+ * adds each non-zero counter with one 64-bit integer atomic, so the result is order-independent. */
+int dig_sequence_counts(const int32_t *pair_row, int64_t n_pairs, const int32_t *row_type, const int32_t *row_cohort, int64_t n,
+                        int64_t K, int64_t C, int64_t *counts, void *stream);
+int dig_sequence_counts_host(const int32_t *pair_row, int64_t n_pairs, const int32_t *row_type, const int32_t *row_cohort, int64_t n,
+                             int64_t K, int64_t C, int64_t *counts, int device);
+
 /* ---- sufficient statistics in canonical chunks (bin-sharded runs) --------------------------- *
  * Same quantity as dig_scale_suffstats / dig_scale_factors, defined so that it does not depend on the sharding: the bins
  * are cut into K canonical chunks of the GLOBAL grid (boundaries floor(N j / K)); a rank computes the chunk sums of the

@@ -6,6 +6,7 @@ Drop-in for the sub-commands of the reference's scripts/DigPretrain.py (:280-477
     regionModel     k-fold CNN+GP results -> idx, mappability, region_params (+ mutation counts)   (:31-100)
     countMutations  cohort-level mutation counts stored as attributes                               (:102-177)
     sequenceModel   sequence_model_192 / sequence_model_64                                          (:179-208)
+    sequenceModels  the same for many cohorts in one pass, one map per mutation file (not in the reference)
     genicModel      genic_model frame                                                               (:226-237)
     elementModel    <save_key> element frame                                                        (:239-268)
     tiledModel      <save_key> tile frame                                                           (:271-278)
@@ -99,6 +100,33 @@ def pretrain_sequence_model(args):
         mapfile.write_frame(args.output_h5, 'sequence_model_64', f64)
 
 
+def pretrain_sequence_models(args):
+    """sequenceModel for many cohorts: one parse per file, one join and one counting launch for all of them (libdig_hip.so through
+    the `_host` entry points: no torch), one pair of frames per map."""
+    if len(args.fmuts) != len(args.maps):
+        raise SystemExit("--mutation-files and --maps: one map per mutation file ({} files, {} maps)".format(len(args.fmuts), len(args.maps)))
+    from digdriver_amd import _lib
+    _lib.TORCH_FREE = True
+    _lib.prewarm_in_background()                # (the HIP runtime starts while the files are parsed)
+    print('Loading genome-wide context counts')
+    df_genome = mapfile.read_frame(args.genome_counts, 'all_window_genome_counts')
+    idx = mapfile.read_array(args.genome_counts, 'idx')
+    mapp = mapfile.read_array(args.genome_counts, 'mappability')
+    print('Training sequence models of {} cohorts'.format(len(args.fmuts)))
+    try:
+        models, _counts, serial = sequence_tools.train_sequence_models(args.fmuts, idx, mapp, df_genome, map_thresh=args.map_thresh,
+                                                                       n_up=args.up, n_down=args.down, on_device=False)
+    except ValueError as exc:
+        raise SystemExit(str(exc))
+    for c in serial:
+        print('{}: rows longer or shorter than one base; counted on the host'.format(args.fmuts[c]))
+    for (f_mut, f_ctx), f_map in zip(models, args.maps):
+        print('Saving sequence models to {}'.format(f_map))
+        with mapfile.batch(f_map):
+            mapfile.write_frame(f_map, 'sequence_model_{}'.format(len(f_mut)), f_mut)
+            mapfile.write_frame(f_map, 'sequence_model_{}'.format(len(f_ctx)), f_ctx)
+
+
 def pretrain_genic_model(args):
     print('Running Genic model')
     frame = genic_driver_tools.genic_model_parallel(args.f_pretrained, args.f_genic, args.N_procs,
@@ -148,6 +176,15 @@ def parse_args(text=None):
     b.add_argument('--map-thresh', default=0.5, type=float, help='minimum bin mappability')
     b.set_defaults(func=pretrain_sequence_model)
 
+    c = sub.add_parser('sequenceModels', help='sequence models of many cohorts in one pass, one map per mutation file')
+    c.add_argument('genome_counts', help='genome-wide context counts container')
+    c.add_argument('--mutation-files', required=True, nargs='+', dest='fmuts', help='annotated mutation files, one per cohort')
+    c.add_argument('--maps', required=True, nargs='+', help='mutation maps to write into, one per mutation file')
+    c.add_argument('--map-thresh', default=0.5, type=float, help='minimum bin mappability')
+    c.add_argument('--up', default=1, type=int, help='context bases in front of the mutated base (1 or 2)')
+    c.add_argument('--down', default=1, type=int, help='context bases behind the mutated base (1 or 2)')
+    c.set_defaults(func=pretrain_sequence_models)
+
     d = sub.add_parser('genicModel', help='per-gene parameters')
     d.add_argument('f_pretrained', help='map with region and sequence models')
     d.add_argument('f_genic', help='preprocessed gene data container')
@@ -180,7 +217,7 @@ def main(text=None):
         _lib.TORCH_FREE = True
         _lib.prewarm_in_background()            # (the HIP runtime starts while pandas is imported and the files are parsed)
     cli.func(cli)
-    if os.environ.get("DIG_CLI_ASSERT_NO_TORCH") == "1" and cli.func is pretrain_nonc_model:
+    if os.environ.get("DIG_CLI_ASSERT_NO_TORCH") == "1" and cli.func in (pretrain_nonc_model, pretrain_sequence_models):
         assert "torch" not in sys.modules, "a torch-free sub-command imported torch"
 
 

@@ -1,0 +1,116 @@
+#!/usr/bin/env python
+"""Wall time of the sequence models of many cohorts: one engine.sequence_counts call on the device (upload, interval join, counting
+kernel, download) plus the C frame pairs, beside C serial sequence_tools.train_sequence_model calls (the host interval join, the
+ten-column drop_duplicates and the tuple value_counts per cohort), on synthetic inputs of the training container's size -- C = 37
+cohorts x 300 000 one-base rows against 288 000 windows of 10 kb on 22 chromosomes.  The type distribution is skewed as in real
+cohorts: a quarter of the rows in four types.  The cohorts are encoded once (encode_sequence_rows' arrays, made here without
+files; the serial side's frames are made from the same arrays outside the timed part): parsing is the same host work on both routes
+and is reported apart, for one file.  The two routes take turns (device, serial, device, ...) behind one untimed pass of each; the
+median and the range of each go to one JSON line.
+
+    python tools/sequence_models_bench.py --rounds 3
+"""
+import argparse
+import json
+import os
+import sys
+import tempfile
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def make_windows(n, width=10_000):
+    per = -(-n // 22)
+    return np.stack([np.repeat(np.arange(1, 23), per)[:n], (np.tile(np.arange(per), 22)[:n]) * width,
+                     (np.tile(np.arange(per), 22)[:n] + 1) * width], 1).astype(np.int64)
+
+
+def make_cohort(rng, n, idx, K, width=10_000):
+    """rows as encode_sequence_rows gives them: a quarter in four types, 1 % without a table entry, 5 % in no whitelisted window"""
+    w = idx[rng.integers(0, len(idx), n)]
+    hot = rng.uniform(size=n) < 0.25
+    typ = np.where(hot, (K // 5) * (1 + rng.integers(0, 4, n)), rng.integers(0, K, n))
+    typ[rng.uniform(size=n) < 0.01] = K
+    start = w[:, 1] + rng.integers(0, width, n)
+    # one row per position, as after read_mutation_file(drop_duplicates=True): a few rows in 300 000 go
+    keep = np.sort(np.unique((w[:, 0] << 40) | start, return_index=True)[1])
+    return dict(chrom=w[keep, 0], start=start[keep], end=start[keep] + 1, type=typ[keep].astype(np.int32),
+                sample=rng.integers(0, 400, len(keep)))
+
+
+def cohort_frame(c, table):
+    """The frame read_mutation_file makes of the cohort's file (REF, ALT from the type's labels; an unknown type: a label pair the
+    table does not hold)."""
+    import pandas as pd
+    mt = np.array(list(table.MUT_TYPE) + ["N>N"], dtype=object)[c["type"]]
+    ctx = np.array(list(table.CONTEXT) + ["NNN"], dtype=object)[c["type"]]
+    return pd.DataFrame(dict(CHROM=c["chrom"], START=c["start"], END=c["end"], REF=[m[0] for m in mt], ALT=[m[2] for m in mt],
+                             SAMPLE=np.char.add("S", c["sample"].astype(str)).astype(object), GENE=".", ANNOT="Noncoding",
+                             MUT_TYPE=mt, CONTEXT=ctx))
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--cohorts", type=int, default=37)
+    ap.add_argument("--mut-rows", type=int, default=300_000)
+    ap.add_argument("--windows", type=int, default=288_000)
+    ap.add_argument("--up", type=int, default=1, help="1: K = 192, 2: K = 3 072")
+    ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--seed", type=int, default=5)
+    args = ap.parse_args()
+    import torch
+    from digdriver_amd import engine
+    from digdriver_amd.sequence_model import sequence_tools as st
+    table = st.mk_mutation_context(args.up, args.up, return_df=True)
+    K, C = len(table), args.cohorts
+    idx = make_windows(args.windows)
+    rng = np.random.default_rng(args.seed)
+    white = idx[rng.uniform(size=len(idx)) >= 0.05]                   # (5 % of the windows below the mappability threshold)
+    S_genome = {c: 1000.0 + i for i, c in enumerate(st.mk_context_sequences(args.up, args.up))}
+    cohorts = [make_cohort(np.random.default_rng([args.seed, c]), args.mut_rows, idx, K) for c in range(C)]
+    rows = [np.concatenate([c[k] for c in cohorts]) for k in ("chrom", "start", "end", "type")] + \
+        [np.repeat(np.arange(C, dtype=np.int32), [len(c["type"]) for c in cohorts])]
+
+    # the host work in front of both routes, for one cohort: a file written and parsed
+    with tempfile.TemporaryDirectory() as tmp:
+        f = os.path.join(tmp, "cohort.annot.txt")
+        cohort_frame(cohorts[0], table).to_csv(f, sep="\t", header=False, index=False)
+        t0 = time.perf_counter()
+        st.encode_sequence_rows(f, {str(i): i for i in range(1, 23)}, args.up, args.up)
+        encode_s = time.perf_counter() - t0
+
+    def device():
+        t0 = time.perf_counter()
+        counts = engine.sequence_counts(white[:, 0], white[:, 1], white[:, 2], *[torch.as_tensor(r, device="cuda") for r in rows], K, C)
+        counts = counts.cpu().numpy()
+        models = [st.train_sequence_model(None, None, S_genome, n_up=args.up, n_down=args.up, counts=counts[c]) for c in range(C)]
+        return time.perf_counter() - t0, counts, models
+
+    def serial():
+        spent, counts = 0.0, np.zeros((C, K), np.int64)
+        for c in range(C):
+            df_mut = cohort_frame(cohorts[c], table)                   # (untimed: the frame the parse gives)
+            t0 = time.perf_counter()
+            f_mut, _ = st.train_sequence_model(white, df_mut, S_genome, n_up=args.up, n_down=args.up)
+            spent += time.perf_counter() - t0
+            counts[c] = f_mut.COUNT.to_numpy(np.int64)
+        return spent, counts, None
+
+    times = {"device": [], "serial": []}
+    (_, a, _), (_, b, _) = device(), serial()                        # untimed: code objects, allocator
+    for _ in range(args.rounds):
+        for name, fn in (("device", device), ("serial", serial)):
+            times[name].append(fn()[0])
+    out = {"cohorts": C, "mut_rows": args.mut_rows, "windows": args.windows, "K": K, "counts_equal": bool(np.array_equal(a, b)),
+           "count_sum": int(a.sum()), "largest_counter": int(a.max()), "encode_one_file_s": round(encode_s, 4)}
+    for name, ts in times.items():
+        out[name + "_s"] = {"median": round(float(np.median(ts)), 4), "min": round(min(ts), 4), "max": round(max(ts), 4), "n": len(ts)}
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
