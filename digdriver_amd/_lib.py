@@ -90,6 +90,12 @@ _SIGNATURES = {
     "dig_window_objectives_host": [_vp, _i64, _vp, _vp] + [_i64] * 4 + [_vp, _int],
     "dig_sequence_counts": [_vp, _i64, _vp, _vp] + [_i64] * 3 + [_vp, _vp],
     "dig_sequence_counts_host": [_vp, _i64, _vp, _vp] + [_i64] * 3 + [_vp, _int],
+    "dig_site_match_count": [_vp] * 4 + [_i64, _i64] + [_vp] * 6 + [_i64] * 3 + [_vp, _vp],
+    "dig_site_match_count_host": [_vp] * 4 + [_i64, _i64] + [_vp] * 6 + [_i64] * 3 + [_vp, _int],
+    "dig_site_match_keys": [_vp] * 4 + [_i64, _i64] + [_vp] * 6 + [_i64] * 3 + [_vp, _i64, _vp, _vp],
+    "dig_site_match_keys_host": [_vp] * 4 + [_i64, _i64] + [_vp] * 6 + [_i64] * 3 + [_vp, _i64, _vp, _int],
+    "dig_site_counts": [_vp] + [_i64] * 4 + [_vp, _vp, _vp],
+    "dig_site_counts_host": [_vp] + [_i64] * 4 + [_vp, _vp, _int],
     "dig_gene_pipeline": [_vp] * 15 + [_int] + [_vp] * 9 + [_i64, _i64, _i64, _vp, _i64, _vp],
     "dig_gene_pipeline_host": [_vp] * 15 + [_int] + [_vp] * 9 + [_i64, _i64, _i64, _int],
     "dig_count_contexts": [_vp, _i64, _vp, _vp, _int, _vp, _vp, _vp, _vp, _i64, _vp, _vp],

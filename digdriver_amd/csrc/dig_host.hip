@@ -171,6 +171,24 @@ size_t dtype_size(int dt)
     }
 }
 
+// the tables of the two site-match twins: sites ascending with elements inside [0, E), rows inside their cohorts
+int check_site_tables(const char* fn, const int64_t* site_pos, const int32_t* site_elt, int64_t S, int64_t E,
+                      const int32_t* row_sample, const int32_t* row_cohort, const int64_t* sample_off, int64_t n, int64_t C,
+                      int64_t n_samples)
+{
+    if (int rc = check_sample_off(fn, sample_off, C, n_samples)) return rc;
+    for (int64_t j = 0; j < S; ++j) {
+        DIG_REQUIRE_IN(fn, site_elt[j] >= 0 && site_elt[j] < E, "site element within [0, E)");
+        DIG_REQUIRE_IN(fn, j == 0 || site_pos[j - 1] <= site_pos[j], "site_pos ascending (the caller sorts)");
+    }
+    for (int64_t i = 0; i < n; ++i) {
+        DIG_REQUIRE_IN(fn, row_cohort[i] >= 0 && row_cohort[i] < C, "cohort within [0, C)");
+        DIG_REQUIRE_IN(fn, row_sample[i] >= sample_off[row_cohort[i]] && row_sample[i] < sample_off[row_cohort[i] + 1],
+                       "global sample within its cohort");
+    }
+    return DIG_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -400,6 +418,59 @@ int dig_sequence_counts_host(const int32_t* pair_row, int64_t n_pairs, const int
     Staging st(device);
     return st.call(dig_sequence_counts, st.in(pair_row, n_pairs), n_pairs, st.in(row_type, n), st.in(row_cohort, n), n, K, C,
                    st.out(counts, (size_t)C * K), nullptr);
+}
+
+int dig_site_match_count_host(const int64_t* site_pos, const int64_t* site_end, const int64_t* site_attr, const int32_t* site_elt,
+                              int64_t S, int64_t E, const int64_t* row_pos, const int64_t* row_end, const int64_t* row_attr,
+                              const int32_t* row_sample, const int32_t* row_cohort, const int64_t* sample_off, int64_t n, int64_t C,
+                              int64_t n_samples, int32_t* counts, int device)
+{
+    DIG_REQUIRE(S >= 0 && S < ((int64_t)1 << 31) && n >= 0, "0 <= S < 2^31, n >= 0");
+    int sb = 0;
+    if (int rc = site_key_layout(__func__, E, C, n_samples, &sb)) return rc;
+    DIG_REQUIRE(sample_off && (S == 0 || (site_pos && site_end && site_attr && site_elt)), "non-null sample_off, site arrays");
+    DIG_REQUIRE(n == 0 || (row_pos && row_end && row_attr && row_sample && row_cohort && counts), "non-null row arrays, counts");
+    if (int rc = check_site_tables(__func__, site_pos, site_elt, S, E, row_sample, row_cohort, sample_off, n, C, n_samples))
+        return rc;
+    Staging st(device);
+    return st.call(dig_site_match_count, st.in(site_pos, S), st.in(site_end, S), st.in(site_attr, S), st.in(site_elt, S), S, E,
+                   st.in(row_pos, n), st.in(row_end, n), st.in(row_attr, n), st.in(row_sample, n), st.in(row_cohort, n),
+                   st.in(sample_off, C + 1), n, C, n_samples, st.out(counts, n), nullptr);
+}
+
+int dig_site_match_keys_host(const int64_t* site_pos, const int64_t* site_end, const int64_t* site_attr, const int32_t* site_elt,
+                             int64_t S, int64_t E, const int64_t* row_pos, const int64_t* row_end, const int64_t* row_attr,
+                             const int32_t* row_sample, const int32_t* row_cohort, const int64_t* sample_off, int64_t n, int64_t C,
+                             int64_t n_samples, const int64_t* offsets, int64_t total, int64_t* keys, int device)
+{
+    DIG_REQUIRE(S >= 0 && S < ((int64_t)1 << 31) && n >= 0 && total >= 0, "0 <= S < 2^31, n, total >= 0");
+    int sb = 0;
+    if (int rc = site_key_layout(__func__, E, C, n_samples, &sb)) return rc;
+    DIG_REQUIRE(sample_off && (S == 0 || (site_pos && site_end && site_attr && site_elt)), "non-null sample_off, site arrays");
+    DIG_REQUIRE(n == 0 || (row_pos && row_end && row_attr && row_sample && row_cohort && offsets), "non-null row arrays, offsets");
+    DIG_REQUIRE(total == 0 || keys, "non-null keys");
+    if (int rc = check_site_tables(__func__, site_pos, site_elt, S, E, row_sample, row_cohort, sample_off, n, C, n_samples))
+        return rc;
+    for (int64_t i = 0; i < n; ++i)
+        DIG_REQUIRE(offsets[i] >= (i ? offsets[i - 1] : 0) && offsets[i] <= total, "offsets: an exclusive prefix sum, 0 first, within total");
+    Staging st(device);
+    return st.call(dig_site_match_keys, st.in(site_pos, S), st.in(site_end, S), st.in(site_attr, S), st.in(site_elt, S), S, E,
+                   st.in(row_pos, n), st.in(row_end, n), st.in(row_attr, n), st.in(row_sample, n), st.in(row_cohort, n),
+                   st.in(sample_off, C + 1), n, C, n_samples, st.in(offsets, n), total, st.out(keys, total), nullptr);
+}
+
+int dig_site_counts_host(const int64_t* keys_sorted, int64_t total, int64_t E, int64_t C, int64_t n_samples, int32_t* obs_snv,
+                         int32_t* obs_samples, int device)
+{
+    DIG_REQUIRE(total >= 0, "total >= 0");
+    int sb = 0;
+    if (int rc = site_key_layout(__func__, E, C, n_samples, &sb)) return rc;
+    DIG_REQUIRE((total == 0 || keys_sorted) && (E == 0 || (obs_snv && obs_samples)), "non-null pointers");
+    if (int rc = check_ascending(__func__, keys_sorted, total)) return rc;
+    const size_t EC = (size_t)E * C;
+    Staging st(device);
+    return st.call(dig_site_counts, st.in(keys_sorted, total), total, E, C, n_samples, st.out(obs_snv, EC), st.out(obs_samples, EC),
+                   nullptr);
 }
 
 int dig_scale_suffstats_host(const double* bin_mu, const uint8_t* bin_flag, int64_t N, int64_t C, double* out_sum, int device)

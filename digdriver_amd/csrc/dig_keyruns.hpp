@@ -1,4 +1,4 @@
-// dig_keyruns.hpp -- what the counting routes (dig_genecounts.hip, dig_objectives.hip, dig_seqcounts.hip) and their host twins share:
+// dig_keyruns.hpp -- what the counting routes (dig_genecounts.hip, dig_objectives.hip, dig_seqcounts.hip, dig_sitematch.hip) and their host twins share:
 // rows encoded as 63-bit keys, sorted by the caller, counted as runs with one integer atomic per wave segment.
 #pragma once
 #include "dig_common.hpp"
@@ -16,6 +16,10 @@ inline int key_bits_for(int64_t n)
 // dig_genecounts.hip: the bits of the global-sample field of a gene-count key; DIG_EINVAL (in the name of entry point `fn`) when
 // (cohort (G + 2) + gene, global sample, class) does not fit 63 bits
 int gene_key_layout(const char* fn, int64_t G, int64_t C, int64_t n_samples, int* sample_bits);
+
+// dig_sitematch.hip: the bits of the global-sample field of a site-match key, (cohort E + element) << bits | global sample; DIG_EINVAL
+// (in the name of entry point `fn`) when the two fields do not fit 63 bits
+int site_key_layout(const char* fn, int64_t E, int64_t C, int64_t n_samples, int* sample_bits);
 
 // dig_objectives.hip: the fields of a window-count key,
 //   global sample << (window_bits + 1 + uid_bits) | window << (1 + uid_bits) | indel << uid_bits | mutation id;

@@ -16,6 +16,10 @@ geneDriver (transfer_tools.run_gene_model, transfer_tools.py:789-874) is batched
 with one gene index, the coding rows of C cohorts counted by engine.gene_counts (dig_gene_row_keys + a key sort +
 dig_gene_counts), then ONE dig_gene_stats launch and, when asked for, ONE dig_gene_selection launch over [G, C]
 (tests/test_gpu_gene_cohorts.py).
+
+elementDriver --f-sites (transfer_tools.run_sites_region_model, transfer_tools.py:1098-1169) likewise -- run_sites_cohorts: the sites
+file encoded once, the rows of C cohorts matched exactly and counted by engine.site_counts (dig_site_match_count / keys + a key sort
++ dig_site_counts), then the statistics element-wise over [E, C] (tests/test_gpu_sites_cohorts.py).
 """
 import numpy as np
 import pandas as pd
@@ -520,6 +524,148 @@ def run_and_write_gene_cohorts(f_muts, f_genemodels, outdir, prefixes, write_thr
         frames = run_gene_cohorts(f_muts, f_genemodels,
                                   on_frame=lambda c, frame: pending.append(pool.submit(mapfile.write_results_tsv, frame, paths[c], threads)),
                                   **kw)
+        for f in pending:
+            f.result()
+    return frames, paths
+
+
+# ---------------------------------------------------------------------------------------------
+# elementDriver --f-sites for many cohorts
+# ---------------------------------------------------------------------------------------------
+_SITE_MODEL_COLS = ['R_OBS'] + transfer_tools._RATE_COLS + ['Pi_SUM']         # transfer_element_model's left side
+
+
+def _read_site_models(f_pretrained, pretrain_key):
+    """The C element models of the sites route as load_pretrained_model leaves them, without its per-map device calls: the frames
+    are read and checked first (one element index: ValueError naming the first map that differs), then the Gamma parameters of all
+    of them are ONE element-wise call over [E, C] (the same bits).  Returns (the frames with transfer_element_model's columns,
+    dict name -> f64 [E, C])."""
+    raw = []
+    for f in f_pretrained:
+        m = mapfile.read_frame(f, pretrain_key)
+        m = m.set_index(m.ELT).rename(columns={'P_SUM': 'Pi_SUM', 'P_INDEL': 'Pi_INDEL'})
+        if raw and not m.index.equals(raw[0].index):
+            raise ValueError("{}: the element index of its '{}' model differs from that of {} (run_sites_cohorts needs one element "
+                             "index for all maps)".format(f, pretrain_key, list(f_pretrained)[0]))
+        raw.append(m)
+    stack = lambda col: np.ascontiguousarray(np.stack([m[col].values for m in raw], axis=1), dtype=np.float64)
+    planes = {col: stack(col) for col in ('MU', 'SIGMA', 'Pi_SUM')}
+    planes['ALPHA'], planes['THETA'] = nb_model.normal_params_to_gamma(planes['MU'], planes['SIGMA'])
+    frames = []
+    for c, m in enumerate(raw):
+        m['ALPHA'], m['THETA'] = planes['ALPHA'][:, c], planes['THETA'][:, c]
+        frames.append(m[_SITE_MODEL_COLS])
+    return frames, planes
+
+
+def _empty_site_table():
+    """mutation_tools.tabulate_sites_in_element for a cohort without a hit: its group-by over an empty merge."""
+    none = pd.DataFrame({'ELT': pd.Series([], dtype=object), 'SAMPLE': pd.Series([], dtype=object), 'CHROM': pd.Series([], dtype=np.int64)})
+    table = none.groupby('ELT').agg(OBS_SAMPLES=('SAMPLE', lambda x: len(set(x))), OBS_SNV=('CHROM', len)).reset_index()
+    return table.set_index('ELT')[['OBS_SAMPLES', 'OBS_SNV']]
+
+
+def run_sites_cohorts(f_muts, f_sites, f_pretrained, pretrain_key, scale_factors=None, scale_by_expectation=True, scale_type=None,
+                      device=0, on_frame=None):
+    """elementDriver --f-sites for C cohorts in one pass: one frame per cohort, with the columns, the column order, the row order
+    (the model's index) and the dtypes of transfer_tools.run_sites_region_model(f_muts[c], f_sites, f_pretrained[c], pretrain_key,
+    ...).  The `pretrain_key` models must share one element index.  Scale factors: the expected synonymous count outside TP53 over
+    a cohort's own gene model (scale_by_expectation, the serial route's own pandas expression per cohort), or given scale_factors
+    [C]; the MSK_230 and genome rules need the maps' bookkeeping and are not batched: NotImplementedError, before any device work.
+    The sites file is read and encoded once (data_tools/sites.py), the rows of all cohorts are matched and counted by
+    engine.site_counts (dig_site_match_count / keys + a key sort + dig_site_counts), the Gamma parameters of all maps are one
+    element-wise call over [E, C] and the two mid-p columns one nb_pvalue_greater_midp call over the stacked [2, E, C] planes.
+    device: the card whose memory holds the rows while they are counted; None: host arrays through the `_host` twins.
+    on_frame(c, frame): called as soon as cohort c's frame exists."""
+    from ..data_tools import sites
+    C = len(f_muts)
+    assert C > 0 and len(f_pretrained) == C
+    given = None if scale_factors is None else np.asarray(scale_factors, float).reshape(C)
+    if not scale_by_expectation and (given is None or not given.all()):
+        raise NotImplementedError("run_sites_cohorts scales by the expected synonymous count (scale_by_expectation) or by given "
+                                  "non-zero scale_factors; the {} rule is run_sites_region_model's".format(
+                                      'MSK_230' if scale_type == 'MSK_230' else 'genome'))
+    table = sites.encode_sites_file(f_sites)
+    rows = [sites.encode_site_rows(f, table["dicts"], c) for c, f in enumerate(f_muts)]
+    models, planes = _read_site_models(f_pretrained, pretrain_key)
+    index = models[0].index
+    offsets = np.concatenate([[0], np.cumsum([len(r["sample_names"]) for r in rows])]).astype(np.int64)
+    if offsets[-1] >= 2 ** 31:
+        raise ValueError("{} samples: the global sample is 32-bit; pass fewer cohorts per call".format(int(offsets[-1])))
+    E_sites = len(table["elt_names"])
+    if device is None:
+        up = np.ascontiguousarray
+    else:
+        import torch
+        dev = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
+        up = lambda a: torch.as_tensor(np.ascontiguousarray(a), device=dev)
+    cat = lambda k: up(np.concatenate([r[k] for r in rows]))
+    sample = up(np.concatenate([r["sample"] + np.int32(offsets[c]) for c, r in enumerate(rows)]))
+    counts = engine.site_counts(up(table["site_pos"]), up(table["site_end"]), up(table["site_attr"]), up(table["site_elt"]),
+                                cat("pos"), cat("end"), cat("attr"), sample, cat("cohort"), offsets, E_sites, C)
+    # site elements -> model rows: an element the model lacks is dropped, a model element no site names counts nothing
+    place = pd.Index(table["elt_names"]).get_indexer(index) if E_sites else np.full(len(index), -1)
+    host = lambda x: x.cpu().numpy() if engine.is_cuda(x) else np.asarray(x)
+    take = lambda x: np.where(place[:, None] >= 0, host(x).astype(np.int64)[np.maximum(place, 0)], 0) if E_sites \
+        else np.zeros((len(index), C), np.int64)
+    obs_snv, obs_samples = take(counts["obs_snv"]), take(counts["obs_samples"])                # [E, C]
+    counts_any = host(counts["obs_snv"]).any(axis=0) if E_sites else np.zeros(C, bool)         # (elements the model lacks included)
+
+    if scale_by_expectation:
+        print('scaling by expected synonymous mutations (excluding TP53)')
+        cj = np.empty(C)
+        for c, f in enumerate(f_pretrained):                               # (transfer_tools.py:1116-1119)
+            genes = mapfile.read_frame(f, 'genic_model')
+            genes = genes.set_index(genes.GENE).rename(columns=transfer_tools._GENE_RENAME)
+            background = genes.loc[genes.index != 'TP53']
+            cj[c] = rows[c]["n_syn"] / (background.MU * background.Pi_SYN).sum()
+    else:
+        cj = given
+    print('Calculating statistics')
+    theta = planes['THETA'] * cj[None, :]
+    exp_snv = planes['ALPHA'] * theta * planes['Pi_SUM']
+    with np.errstate(all="ignore"):
+        prob = 1 / (theta * planes['Pi_SUM'] + 1)
+    k = np.stack([obs_snv, obs_samples]).astype(np.float64)                                    # [2, E, C]
+    pv = np.asarray(nb_model.nb_pvalue_greater_midp(k, np.broadcast_to(planes['ALPHA'], k.shape), np.broadcast_to(prob, k.shape)))
+
+    frames = []
+    for c, m in enumerate(models):
+        d = {col: m[col].values for col in _SITE_MODEL_COLS}
+        d['THETA'] = np.ascontiguousarray(theta[:, c])
+        # a model element without a row in the cohort's count table makes the serial route's left join fill with NaN: float columns
+        kind = np.int64 if len(index) and (obs_snv[:, c] > 0).all() else np.float64
+        kinds = dict(OBS_SAMPLES=kind, OBS_SNV=kind)
+        if not counts_any[c]:
+            # no hit at all: the serial route's EMPTY count table has an object column, and what its join and fillna make of that is
+            # pandas' choice, so its own expressions are asked (an empty table against the model: nothing is counted here)
+            kinds = dict(transfer_tools.transfer_element_model(_empty_site_table(), m, 1.0)[['OBS_SAMPLES', 'OBS_SNV']].dtypes)
+        d['OBS_SAMPLES'], d['OBS_SNV'] = obs_samples[:, c].astype(kinds['OBS_SAMPLES']), obs_snv[:, c].astype(kinds['OBS_SNV'])
+        d['EXP_SNV'] = np.ascontiguousarray(exp_snv[:, c])
+        d['PVAL_SNV_BURDEN'], d['PVAL_SAMPLE_BURDEN'] = np.ascontiguousarray(pv[0, :, c]), np.ascontiguousarray(pv[1, :, c])
+        print("\tScale factor of cohort {} is: {}".format(c, cj[c]))
+        frames.append(pd.DataFrame(d, index=index))
+        if on_frame is not None:
+            on_frame(c, frames[-1])
+    return frames
+
+
+def run_and_write_sites_cohorts(f_muts, f_sites, f_pretrained, pretrain_key, outdir, prefixes, write_threads=None, **kw):
+    """run_sites_cohorts + <outdir>/<prefix>.results.txt per cohort through the native writer, as `DigDriver.py elementDriver
+    --f-sites` writes it (DigDriver.py cmd_element: the OBS_* columns as integers), each file by a worker thread while the frames of
+    the cohorts after it are assembled.  Returns (frames, paths); the files are complete when the call returns."""
+    import os
+    from concurrent.futures import ThreadPoolExecutor
+    os.makedirs(outdir, exist_ok=True)
+    C = len(f_muts)
+    assert len(prefixes) == C
+    paths = [os.path.join(outdir, pfx + '.results.txt') for pfx in prefixes]
+    cores = os.cpu_count() or 1
+    threads = int(write_threads) if write_threads else max(1, min(8, cores // max(C, 1)))
+    pending = []
+    with ThreadPoolExecutor(max_workers=max(1, min(C, cores))) as pool:
+        frames = run_sites_cohorts(f_muts, f_sites, f_pretrained, pretrain_key,
+                                   on_frame=lambda c, frame: pending.append(pool.submit(_write_one, frame, paths[c], threads)), **kw)
         for f in pending:
             f.result()
     return frames, paths

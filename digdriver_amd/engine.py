@@ -343,6 +343,63 @@ def sequence_counts(win_chrom, win_start, win_end, row_chrom, row_start, row_end
     return counts
 
 
+SITE_COUNT_BLOCK = 256          # csrc/dig_sitematch.hip kSiteBlock: the workgroup of dig_site_counts (the tests place runs at its edges)
+
+
+def site_counts(site_pos, site_end, site_attr, site_elt, row_pos, row_end, row_attr, row_sample, row_cohort, sample_offsets, E, C,
+                device=0):
+    """The sites route's observed counts for C cohorts at once (mutation_tools.py:233-281 tabulate_nonc_mutations_at_sites: the inner
+    merge on nine columns and the group-by per element): dig_site_match_count, a cumulative sum, dig_site_match_keys, a key sort,
+    dig_site_counts.
+    Sites (data_tools/sites.encode_sites_file): pos = chrom << 40 | START ascending, end, attr i64 [S]; elt i32 [S] within [0, E).
+    Rows of all cohorts in any order (sites.encode_site_rows): pos, end, attr i64 [n] (attr < 0: matches nothing); sample i32 = the
+    GLOBAL sample, inside its cohort's range of sample_offsets [C + 1]; cohort i32.
+    Returns dict(obs_snv, obs_samples), i32 [E, C]: matched (row, site) pairs and distinct samples among them per (element, cohort).
+    ValueError, before the fill, for more than 2^31 - 1 matches.  CUDA tensors in -> CUDA tensors out."""
+    be = backend_of(site_pos, site_end, site_attr, site_elt, row_pos, row_end, row_attr, row_sample, row_cohort, device=device)
+    E = int(E)
+    off_host, C, n_samples = _sample_offsets(sample_offsets, int(C))
+    site_pos, site_end, site_attr = (be.arr(x, "i64", (-1,)) for x in (site_pos, site_end, site_attr))
+    site_elt = be.arr(site_elt, "i32", (-1,))
+    row_pos, row_end, row_attr = (be.arr(x, "i64", (-1,)) for x in (row_pos, row_end, row_attr))
+    row_sample, row_cohort = be.arr(row_sample, "i32", (-1,)), be.arr(row_cohort, "i32", (-1,))
+    S, n = site_pos.shape[0], row_pos.shape[0]
+    assert site_end.shape[0] == site_attr.shape[0] == site_elt.shape[0] == S
+    assert row_end.shape[0] == row_attr.shape[0] == row_sample.shape[0] == row_cohort.shape[0] == n
+    off = be.arr(off_host, "i64")
+    if be.is_device:
+        # (device tensors are checked here; the host twins check their own arrays inside the library)
+        if S and (bool(((site_elt < 0) | (site_elt >= E)).any()) or bool((site_pos[1:] < site_pos[:-1]).any())):
+            raise ValueError("the site table: site_pos ascending, elements within [0, E)")
+        if n:
+            c = row_cohort.clamp(0, C - 1).long()
+            if bool(((row_cohort < 0) | (row_cohort >= C) | (row_sample < off[c]) | (row_sample >= off[c + 1])).any()):
+                raise ValueError("a row outside the tables: cohort within [0, C), global sample within its cohort")
+    p = be.ptr
+    search = [p(site_pos), p(site_end), p(site_attr), p(site_elt), S, E, p(row_pos), p(row_end), p(row_attr), p(row_sample),
+              p(row_cohort), p(off), n, C, n_samples]
+    try:
+        counts = be.empty(n, "i32")
+        be.call("dig_site_match_count", *search, p(counts))
+        if n:
+            incl = be.torch.cumsum(counts, 0, dtype=be.torch.int64) if be.is_device else np.cumsum(counts, dtype=np.int64)
+            total, offsets = int(incl[-1]), incl - counts
+        else:
+            total, offsets = 0, be.empty(0, "i64")
+        if total > 2 ** 31 - 1:
+            raise ValueError("%d (row, site) matches: the observed counts are 32-bit; pass fewer cohorts per call" % total)
+        keys = be.empty(total, "i64")
+        be.call("dig_site_match_keys", *search, p(offsets), total, p(keys))
+        keys = _sorted(be, keys)
+        obs_snv, obs_samples = be.empty((E, C), "i32"), be.empty((E, C), "i32")
+        be.call("dig_site_counts", p(keys), total, E, C, n_samples, p(obs_snv), p(obs_samples))
+    except _lib.DigHipError as exc:
+        if "requirement failed" in str(exc):
+            raise ValueError(str(exc)) from exc
+        raise
+    return dict(obs_snv=obs_snv, obs_samples=obs_samples)
+
+
 def gene_pipeline(bin_mu, bin_std, bin_y, bin_flag, bin_ctx, ov_ptr, ov_idx, L, strand_minus, gene_length, d_pr, obs, n_samp, cj,
                   t_indel=None):
     """genic_model (genic_driver_tools.py:31-203) + the gene statistics block as one call on device tensors

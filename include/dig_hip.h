@@ -391,6 +391,49 @@ int dig_sequence_counts(const int32_t *pair_row, int64_t n_pairs, const int32_t 
 int dig_sequence_counts_host(const int32_t *pair_row, int64_t n_pairs, const int32_t *row_type, const int32_t *row_cohort, int64_t n,
                              int64_t K, int64_t C, int64_t *counts, int device);
 
+/* ---- the sites route's observed counts for many cohorts (additive: the ABI version stays) ----------------------- *
+ * mutation_tools.py:233-281 tabulate_nonc_mutations_at_sites: a mutation row counts for a site row when CHROM, START, END, REF, ALT,
+ * GENE, ANNOT, MUT_TYPE and CONTEXT all agree -- an exact match, not an overlap -- and per element OBS_SNV = matched (row, site) pairs,
+ * OBS_SAMPLES = distinct samples among them.  The nine columns are three integers: pos = chrom << 40 | START, END, and attr, an
+ * injective code of the six labels (formed by the caller from the sites file's own dictionaries; a negative row_attr matches nothing).
+ * Sites: S rows sorted ascending by site_pos (the only column the search orders by), site_pos, site_end, site_attr i64 [S], site_elt
+ * i32 [S] within [0, E).  Rows of all C cohorts, in any order: row_pos, row_end, row_attr i64 [n], row_sample i32 [n] = the GLOBAL
+ * sample, row_cohort i32 [n]; sample_off i64 [C + 1] = a cohort's first global sample (0 first, n_samples last, as for
+ * dig_gene_row_keys): a row's sample lies in its cohort's range.  S, E, C, n_samples < 2^31.
+ *   dig_site_match_count: counts i32 [n] = the site rows with the row's pos, end and attr (one thread per row: a binary search for
+ *     the first site at the position, then a walk over the equal-position run).
+ *   The caller forms offsets i64 [n], the exclusive prefix sum of counts, and total, their sum (the two-call protocol of
+ *     dig_overlap_join_count / fill).
+ *   dig_site_match_keys: keys i64 [total]; match q of row i is keys[offsets[i] + q] = (cohort E + element) << sb | global sample, sb
+ *     the bits of n_samples - 1 (DIG_EINVAL, from all three entry points, when the fields do not fit 63 bits).  keys is set to -1
+ *     first and nothing is written outside [0, total): offsets that are not the prefix sum leave -1 keys, which count nowhere.
+ *   The caller sorts the keys ascending (as for dig_gene_counts).
+ *   dig_site_counts, from the sorted keys: obs_snv i32 [E, C] = keys per (element, cohort) -- a row that matches k site rows of an
+ *     element counts k times, as the inner merge does -- and obs_samples i32 [E, C] = distinct keys per (element, cohort).
+ * A row outside the tables (cohort outside [0, C), sample outside its cohort) and a site row with an element outside [0, E) match
+ * nothing; the host twins refuse them, and a site table that is not ascending.  Every output is zeroed by its call; nothing is
+ * launched for empty inputs; integer atomics, one per run of lanes with one destination, so order-independent. */
+int dig_site_match_count(const int64_t *site_pos, const int64_t *site_end, const int64_t *site_attr, const int32_t *site_elt, int64_t S,
+                         int64_t E, const int64_t *row_pos, const int64_t *row_end, const int64_t *row_attr, const int32_t *row_sample,
+                         const int32_t *row_cohort, const int64_t *sample_off, int64_t n, int64_t C, int64_t n_samples, int32_t *counts,
+                         void *stream);
+int dig_site_match_count_host(const int64_t *site_pos, const int64_t *site_end, const int64_t *site_attr, const int32_t *site_elt,
+                              int64_t S, int64_t E, const int64_t *row_pos, const int64_t *row_end, const int64_t *row_attr,
+                              const int32_t *row_sample, const int32_t *row_cohort, const int64_t *sample_off, int64_t n, int64_t C,
+                              int64_t n_samples, int32_t *counts, int device);
+int dig_site_match_keys(const int64_t *site_pos, const int64_t *site_end, const int64_t *site_attr, const int32_t *site_elt, int64_t S,
+                        int64_t E, const int64_t *row_pos, const int64_t *row_end, const int64_t *row_attr, const int32_t *row_sample,
+                        const int32_t *row_cohort, const int64_t *sample_off, int64_t n, int64_t C, int64_t n_samples,
+                        const int64_t *offsets, int64_t total, int64_t *keys, void *stream);
+int dig_site_match_keys_host(const int64_t *site_pos, const int64_t *site_end, const int64_t *site_attr, const int32_t *site_elt,
+                             int64_t S, int64_t E, const int64_t *row_pos, const int64_t *row_end, const int64_t *row_attr,
+                             const int32_t *row_sample, const int32_t *row_cohort, const int64_t *sample_off, int64_t n, int64_t C,
+                             int64_t n_samples, const int64_t *offsets, int64_t total, int64_t *keys, int device);
+int dig_site_counts(const int64_t *keys_sorted, int64_t total, int64_t E, int64_t C, int64_t n_samples, int32_t *obs_snv,
+                    int32_t *obs_samples, void *stream);
+int dig_site_counts_host(const int64_t *keys_sorted, int64_t total, int64_t E, int64_t C, int64_t n_samples, int32_t *obs_snv,
+                         int32_t *obs_samples, int device);
+
 /* ---- sufficient statistics in canonical chunks (bin-sharded runs) --------------------------- *
  * Same quantity as dig_scale_suffstats / dig_scale_factors, defined so that it does not depend on the sharding: the bins
  * are cut into K canonical chunks of the GLOBAL grid (boundaries floor(N j / K)); a rank computes the chunk sums of the
