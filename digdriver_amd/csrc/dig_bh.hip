@@ -120,6 +120,7 @@ int dig_bh_qvalues_sorted(const double* p_sorted, int64_t n, int64_t rows, doubl
     if (n == 0 || rows == 0) return DIG_OK;
     DIG_REQUIRE(p_sorted && q_sorted && workspace && workspace_bytes >= dig_bh_workspace(n, rows),
                 "non-null pointers, workspace of dig_bh_workspace(n, rows) bytes");
+    DIG_REQUIRE(((uintptr_t)workspace & 7u) == 0, "workspace 8-byte aligned");
     const int64_t n_chunks = (n + kBhChunk - 1) / kBhChunk;
     DIG_REQUIRE(n_chunks <= 0x7fffffff && rows <= 65535, "n or rows too large for one launch");
     double* chunk_min = (double*)workspace;

@@ -154,6 +154,7 @@ int dig_mutation_contexts(const uint32_t* words2, int64_t n_words2, const int64_
     DIG_REQUIRE(words2 && chrom_off && chrom_len && row_chrom && row_start && row_ref && status && context && workspace,
                 "non-null pointers");
     DIG_REQUIRE(workspace_bytes >= dig_mutation_contexts_workspace(n_rows), "workspace of dig_mutation_contexts_workspace bytes");
+    DIG_REQUIRE(((uintptr_t)workspace & 3u) == 0, "workspace 4-byte aligned");
     const int grid = (int)((n_rows + kMcBlock - 1) / kMcBlock);
     int32_t* wave_last = static_cast<int32_t*>(workspace);
     hipLaunchKernelGGL(mutctx_lookup_kernel, dim3(grid), dim3(kMcBlock), 0, (hipStream_t)stream, G, row_chrom, row_start, row_ref,

@@ -356,6 +356,7 @@ int dig_scale_suffstats_chunked(const double* bin_mu, const uint8_t* bin_flag, i
     ChunkTable tab;
     const int blocks = ss_fill_chunk_table(chunk_rows, n_chunks, C, &tab);
     DIG_REQUIRE(workspace_bytes >= (int64_t)std::max(blocks, 1) * C * (int64_t)sizeof(double), "workspace smaller than dig_scale_suffstats_chunked_workspace");
+    DIG_REQUIRE(((uintptr_t)workspace & 7u) == 0, "workspace 8-byte aligned");
     hipStream_t s = (hipStream_t)stream;
     if (blocks > 0) {
         DIG_REQUIRE(bin_mu, "non-null bin_mu (bin_flag may be NULL: flagged entries of bin_mu are +0.0 then)");

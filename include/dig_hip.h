@@ -107,7 +107,7 @@ int dig_normal_params_to_gamma_host(const double *mu, const double *sigma, doubl
  * out holds DIG_ES_NPLANES planes of E*C doubles: out[plane * E * C + e * C + c].
  * The same entry point serves the gene twins (transfer_tools.py:331-340,425-454,554-583,
  * 709-727): call it once per mutation class with that class's Pi_* / OBS_* / N_SAMP_*.
- * workspace: optional device scratch of at least dig_element_stats_workspace(E, C) bytes.  With it the
+ * workspace: optional device scratch of at least dig_element_stats_workspace(E, C) bytes, 4-byte aligned.  With it the
  * rare expensive tests (k > 64 or p-value < 1e-3: lgamma + continued fraction) are compacted into a
  * queue in LDS and finished by the same kernel at the end of each workgroup (what does not fit there goes through the
  * workspace); with workspace == NULL they are resolved inline (same results, more wave divergence).
@@ -441,7 +441,7 @@ int dig_site_counts_host(const int64_t *keys_sorted, int64_t total, int64_t E, i
  * all ranks are all-gathered in chunk order and added first to last; obs f64 [world, 2, C] hold every rank's observed
  * SNV / indel counts (integers).  Bit-identical scale factors for any number of ranks.
  *   chunk_rows int64 [n_chunks + 1], HOST memory: first row of every chunk in this rank's table (+ end); n_chunks <= 256;
- *   C <= 256.  workspace: dig_scale_suffstats_chunked_workspace(chunk_rows, n_chunks, C) bytes.
+ *   C <= 256.  workspace: dig_scale_suffstats_chunked_workspace(chunk_rows, n_chunks, C) bytes, 8-byte aligned.
  *   bin_flag may be NULL (ABI 5): bin_mu then holds +0.0 in the flagged entries already (a plan-time copy saves the flag
  *   bytes of every step); the same additions, the same bits. */
 int64_t dig_scale_suffstats_chunked_workspace(const int64_t *chunk_rows, int n_chunks, int64_t C);
@@ -588,7 +588,7 @@ int dig_count_contexts5_host(const uint32_t *words2, int64_t n_words2, const int
  *       reported as DIG_MC_HOST with nothing read (the caller rejects it);
  *   context u32 [n_rows] (DIG_MC_KEPT rows): the window at 2 bits per base (A=0 C=1 G=2 T=3), window base k in bits 2 k, 2 k + 1;
  *       collapse != 0: reverse-complemented when the centre is A or G;
- *   workspace: dig_mutation_contexts_workspace(n_rows) bytes.  n_rows < 2^31. */
+ *   workspace: dig_mutation_contexts_workspace(n_rows) bytes, 4-byte aligned.  n_rows < 2^31. */
 #define DIG_MC_KEPT 0
 #define DIG_MC_MISMATCH 1
 #define DIG_MC_DROPPED 2
@@ -740,7 +740,7 @@ int dig_mutctx_file_free_host(void *handle);
 /* ---- Benjamini-Hochberg q-values (nb_model.get_q_vals, nb_model.py:340-342 = statsmodels fdrcorrection, method 'indep') ---- *
  * For `rows` lists of n p-values each, every list ALREADY in ascending order (the caller sorts: torch.sort / rocPRIM; row r at
  * p_sorted + r n): q_sorted[i] = min(1, min_{j >= i} p[j] / ((j + 1) / n)), the same IEEE operations in the same order as the host
- * form (a NaN -- sorted last -- makes every q of its list NaN, as statsmodels does).  workspace: dig_bh_workspace(n, rows) bytes.  One HBM-bound pass (round 5: torch.cummin took 21 ms per 7.2 M values, 99 % of the
+ * form (a NaN -- sorted last -- makes every q of its list NaN, as statsmodels does).  workspace: dig_bh_workspace(n, rows) bytes, 8-byte aligned.  One HBM-bound pass (round 5: torch.cummin took 21 ms per 7.2 M values, 99 % of the
  * per-base route of BASELINE configs[4]). */
 int64_t dig_bh_workspace(int64_t n, int64_t rows);
 int dig_bh_qvalues_sorted(const double *p_sorted, int64_t n, int64_t rows, double *q_sorted, void *workspace, int64_t workspace_bytes,
@@ -764,7 +764,8 @@ int dig_bh_qvalues_sorted(const double *p_sorted, int64_t n, int64_t rows, doubl
  *       so only the keys are sorted, the records go into a table per row and every element finds its q by its own value; a row
  *       with more records than half its length makes the call sort again with a 32-bit payload and write q through it.  The
  *       call synchronises `stream` (row tables go up, one flag word comes back).
- *   workspace: dig_bh_ragged_workspace(row_ptr, rows) bytes (24.2 bytes per element + tables). */
+ *   workspace: dig_bh_ragged_workspace(row_ptr, rows) bytes (24.2 bytes per element + tables) at any alignment: the calls lay
+ *       their tables out from the next 256-byte boundary inside it, and the query includes that slack. */
 int64_t dig_bh_ragged_workspace(const int64_t *row_ptr, int64_t rows);
 int dig_sort_rows(const double *p, const int64_t *row_ptr, int64_t rows, double *p_sorted, uint32_t *order, void *workspace,
                   int64_t workspace_bytes, void *stream);
