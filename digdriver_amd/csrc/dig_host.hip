@@ -473,6 +473,40 @@ int dig_site_counts_host(const int64_t* keys_sorted, int64_t total, int64_t E, i
                    nullptr);
 }
 
+int dig_tile_select_count_host(const double* score, const int32_t* n_valid, const double* cut, int64_t C, int64_t R, int64_t T,
+                               int32_t* counts, int device)
+{
+    if (int rc = tile_select_sizes(__func__, C, R, T)) return rc;
+    const size_t rows = (size_t)C * R;
+    if (rows == 0) return DIG_OK;
+    DIG_REQUIRE(counts && (T == 0 || (score && n_valid && cut)), "non-null score, n_valid, cut, counts");
+    Staging st(device);
+    return st.call(dig_tile_select_count, st.in(score, rows * T), st.in(n_valid, R), st.in(cut, C), C, R, T, st.out(counts, rows),
+                   nullptr);
+}
+
+int dig_tile_select_fill_host(const double* score, const int32_t* n_valid, const double* cut, int64_t C, int64_t R, int64_t T,
+                              const int64_t* offsets, int64_t total, const double* pt, const double* exp_in, const int32_t* k,
+                              int32_t* hit_region, int32_t* hit_tile, double* hit_score, double* hit_pt, double* hit_exp,
+                              int32_t* hit_k, int device)
+{
+    if (int rc = tile_select_sizes(__func__, C, R, T)) return rc;
+    DIG_REQUIRE(total >= 0, "total >= 0");
+    const size_t rows = (size_t)C * R, n = rows * T;
+    if (n == 0 || total == 0) return DIG_OK;
+    DIG_REQUIRE(score && n_valid && cut && offsets, "non-null score, n_valid, cut, offsets");
+    for (size_t i = 0; i < rows; ++i)
+        DIG_REQUIRE(offsets[i] >= (i ? offsets[i - 1] : 0) && offsets[i] <= total, "offsets: an exclusive prefix sum, 0 first, within total");
+    Staging st(device);
+    // (an output the call skips -- NULL, or without its plane -- is not staged: the caller's array stays as it was)
+    const size_t nt = (size_t)total;
+    return st.call(dig_tile_select_fill, st.in(score, n), st.in(n_valid, R), st.in(cut, C), C, R, T, st.in(offsets, rows), total,
+                   st.in(pt, n), st.in(exp_in, n), st.in(k, n), hit_region ? st.out(hit_region, nt) : nullptr,
+                   hit_tile ? st.out(hit_tile, nt) : nullptr, hit_score ? st.out(hit_score, nt) : nullptr,
+                   hit_pt && pt ? st.out(hit_pt, nt) : nullptr, hit_exp && exp_in ? st.out(hit_exp, nt) : nullptr,
+                   hit_k && k ? st.out(hit_k, nt) : nullptr, nullptr);
+}
+
 int dig_scale_suffstats_host(const double* bin_mu, const uint8_t* bin_flag, int64_t N, int64_t C, double* out_sum, int device)
 {
     DIG_REQUIRE(N >= 0 && C >= 0, "N, C >= 0");

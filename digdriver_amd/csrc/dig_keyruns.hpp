@@ -1,4 +1,4 @@
-// dig_keyruns.hpp -- what the counting routes (dig_genecounts.hip, dig_objectives.hip, dig_seqcounts.hip, dig_sitematch.hip) and their host twins share:
+// dig_keyruns.hpp -- what the counting routes (dig_genecounts.hip, dig_objectives.hip, dig_seqcounts.hip, dig_sitematch.hip, dig_tilehits.hip) and their host twins share:
 // rows encoded as 63-bit keys, sorted by the caller, counted as runs with one integer atomic per wave segment.
 #pragma once
 #include "dig_common.hpp"
@@ -28,6 +28,9 @@ struct WindowKeyLayout {
     int uid_bits, window_bits;
 };
 int window_key_layout(const char* fn, int64_t n_samples, int64_t N, int64_t n_uid, WindowKeyLayout* lay);
+
+// dig_tilehits.hip: the sizes of a score plane [C, R, T]; DIG_EINVAL (in the name of entry point `fn`) unless C R < 2^31 and T < 2^31
+int tile_select_sizes(const char* fn, int64_t C, int64_t R, int64_t T);
 
 // dig_seqcounts.hip: the most table rows K a call takes -- a workgroup's LDS counters, 12 KB: the penta-nucleotide table
 constexpr int kSeqMaxK = 3072;

@@ -1132,6 +1132,71 @@ def tiled_nb_model(genome, chroms, starts, ends, s_prob, mu, sigma, mut_chrom, m
     return dict(pval=pval, exp=ex, pt=pt, k=k, first_pos=first, n_valid=nval)
 
 
+def _tile_counts(be, score, n_valid, cut):
+    """dig_tile_select_count on the backend's arrays: (the six leading arguments both entry points take, counts i32 [C R], C, R, T)."""
+    score = be.arr(score, "f64")
+    assert score.ndim == 3, "score must be [C, R, T]"
+    C, R, T = (int(s) for s in score.shape)
+    n_valid, cut = be.arr(n_valid, "i32", (R,)), _per_cohort(be, cut, C)
+    plane = [score, n_valid, cut, C, R, T]
+    counts = be.empty(C * R, "i32")
+    try:
+        be.call("dig_tile_select_count", *[be.ptr(x) for x in plane[:3]], C, R, T, be.ptr(counts))
+    except _lib.DigHipError as exc:
+        if "requirement failed" in str(exc):
+            raise ValueError(str(exc)) from exc
+        raise
+    return plane, counts, C, R, T
+
+
+def tile_select_counts(score, n_valid, cut, device=0):
+    """counts i32 [C, R]: the hits of every (cohort, region) row of a score plane -- the first call of tile_select alone."""
+    be = backend_of(score, n_valid, device=device)
+    _, counts, C, R, _ = _tile_counts(be, score, n_valid, cut)
+    return counts.reshape(C, R)
+
+
+def tile_select(score, n_valid, cut, pt=None, exp=None, k=None, device=0, index=True):
+    """The hits of a score plane of the per-base route, in the row order of the reference's frame: dig_tile_select_count, a
+    cumulative sum, dig_tile_select_fill.  score f64 [C, R, T]; n_valid i32 [R] as base_tile_probs returns it; cut f64 [C] (a
+    single value stands for every cohort).  Tile (c, r, t) is a hit when t < n_valid[r] and score[c, r, t] <= cut[c]; a NaN on
+    either side never hits, cut = +inf takes every existing tile with a non-NaN score.  pt, exp f64 and k i32 [C, R, T]: planes
+    gathered at the hits when given.
+    Returns dict(region i32, tile i32, score f64 [hits], cohort-major, then by region, then by tile; pt / exp / k [hits] for the
+    planes given; cohort_ptr host int64 [C + 1]: where a cohort's hits start); index=False leaves region and tile out (the
+    ragged score lists of a Benjamini-Hochberg pass).  ValueError, before the fill, for more than 2^31 - 1 hits.  CUDA tensors
+    in -> CUDA tensors out."""
+    be = backend_of(score, n_valid, pt, exp, k, device=device)
+    held, counts, C, R, T = _tile_counts(be, score, n_valid, cut)        # (held: the arrays behind the pointers stay alive)
+    planes = dict(pt=be.arr(pt, "f64", (C, R, T)), exp=be.arr(exp, "f64", (C, R, T)), k=be.arr(k, "i32", (C, R, T)))
+    p = be.ptr
+    plane = [p(x) for x in held[:3]] + [C, R, T]
+    try:
+        if C * R:
+            incl = be.torch.cumsum(counts, 0, dtype=be.torch.int64) if be.is_device else np.cumsum(counts, dtype=np.int64)
+            offsets = incl - counts
+            ends = incl[R - 1::R]                                      # the hits up to each cohort's last row
+            cohort_ptr = np.concatenate([[0], ends.cpu().numpy() if be.is_device else ends]).astype(np.int64)
+        else:
+            offsets, cohort_ptr = be.empty(0, "i64"), np.zeros(C + 1, np.int64)
+        total = int(cohort_ptr[-1])
+        if total > 2 ** 31 - 1:
+            raise ValueError("%d hits: a smaller cut or fewer cohorts per call" % total)
+        res = dict(region=be.empty(total, "i32"), tile=be.empty(total, "i32")) if index else {}
+        res["score"] = be.empty(total, "f64")
+        for name, x in planes.items():
+            if x is not None:
+                res[name] = be.empty(total, "i32" if name == "k" else "f64")
+        be.call("dig_tile_select_fill", *plane, p(offsets), total, p(planes["pt"]), p(planes["exp"]), p(planes["k"]),
+                p(res.get("region")), p(res.get("tile")), p(res["score"]), p(res.get("pt")), p(res.get("exp")), p(res.get("k")))
+    except _lib.DigHipError as exc:
+        if "requirement failed" in str(exc):
+            raise ValueError(str(exc)) from exc
+        raise
+    res["cohort_ptr"] = cohort_ptr
+    return res
+
+
 # ---------------------------------------------------------------------------
 # scale factors in canonical chunks: identical bits for any sharding of the bins (dig_scale_suffstats_chunked)
 # ---------------------------------------------------------------------------

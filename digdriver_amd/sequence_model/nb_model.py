@@ -133,21 +133,147 @@ def nb_model(d_pr, idx, mu_lst, sigma_lst, f_tabix, f_fasta, n_up=2, n_down=2, b
                                 muts.END.values, np.zeros(len(muts), np.int32), binsize=binsize, device=device)
     host = {k: v.cpu().numpy() for k, v in res.items()}
     first, nval = host["first_pos"], host["n_valid"].astype(np.int64)
-    n_pos = np.minimum(ends, np.array([g.lengths[i] for i in g.chrom_index(chroms)]) - n_up) - first
-    cols = ["CHROM", "POS", "OBS", "EXP", "PVAL", "Pi", "MU", "SIGMA", "REGION"]
     if len(idx) == 0 or nval.sum() == 0:
-        return pd.DataFrame(columns=cols)
+        return pd.DataFrame(columns=_TILE_COLUMNS)
     # all regions at once (the reference appends one block per region): region of every tile, tile number inside it
     reg = np.repeat(np.arange(len(idx)), nval)
     t = np.arange(nval.sum()) - np.repeat(np.cumsum(nval) - nval, nval)
-    lo = first[reg] + t * binsize
-    hi = np.minimum(lo + binsize, (first + n_pos)[reg]) - 1
     take = lambda a: a[0][reg, t]
-    labels = np.array(["{}:{}-{}".format(c, s_, e) for c, s_, e in idx], dtype=object)
+    return _tile_frame(idx, mu_lst, sigma_lst, first, _region_positions(g, chroms, ends, first, n_up), binsize, reg, t,
+                       take(host["k"]), take(host["exp"]), take(host["pval"]), take(host["pt"]))
+
+
+_TILE_COLUMNS = ["CHROM", "POS", "OBS", "EXP", "PVAL", "Pi", "MU", "SIGMA", "REGION"]
+
+
+def _region_positions(g, chroms, ends, first, n_up):
+    """The positions every region has from its first one on (a window must fit in front of the chromosome's end)."""
+    return np.minimum(ends, np.array([g.lengths[i] for i in g.chrom_index(chroms)], np.int64) - n_up) - first
+
+
+def _tile_frame(idx, mu, sigma, first, n_pos, binsize, reg, t, obs, exp, pval, pi):
+    """Rows of the reference's frame (nb_model.py:141-186) for the tiles (reg[i], t[i]) of one cohort, from host arrays: idx
+    [R, 3], mu, sigma, first, n_pos [R]; obs, exp, pval, pi: the tiles' values.  What nb_model builds for every tile and
+    nb_model_hits for the hits."""
+    import pandas as pd
+    idx, reg, t = np.asarray(idx), np.asarray(reg, np.int64), np.asarray(t, np.int64)
+    lo = np.asarray(first)[reg] + t * binsize
+    hi = np.minimum(lo + binsize, (np.asarray(first) + np.asarray(n_pos))[reg]) - 1
+    used, inv = np.unique(reg, return_inverse=True)          # (a label per region that has a row: a hit list names few regions)
+    labels = np.array(["{}:{}-{}".format(c, s_, e) for c, s_, e in idx[used]], dtype=object)
     return pd.DataFrame({
         "CHROM": idx[reg, 0].astype(float), "POS": (lo + hi) / 2.0 if binsize > 1 else lo.astype(float),
-        "OBS": take(host["k"]).astype(float), "EXP": take(host["exp"]), "PVAL": take(host["pval"]), "Pi": take(host["pt"]),
-        "MU": np.asarray(mu_lst, float)[reg], "SIGMA": np.asarray(sigma_lst, float)[reg], "REGION": labels[reg]})[cols]
+        "OBS": np.asarray(obs).astype(float), "EXP": np.asarray(exp, float), "PVAL": np.asarray(pval, float), "Pi": np.asarray(pi, float),
+        "MU": np.asarray(mu, float)[reg], "SIGMA": np.asarray(sigma, float)[reg],
+        "REGION": labels[inv.reshape(-1)] if len(reg) else np.empty(0, object)})[_TILE_COLUMNS]
+
+
+def bh_cut(p, q, fdr):
+    """p*: the largest p-value of a list whose Benjamini-Hochberg q-value is <= fdr; below 0 when there is none.  q is a
+    non-decreasing step function of p (tied p-values share one q), so {q <= fdr} = {p <= p*}.  p, q: one cohort's testable
+    p-values and their q-values in any common order, numpy arrays or tensors."""
+    sel = q <= fdr
+    return float(p[sel].max()) if bool(sel.any()) else -1.0
+
+
+def hits_q_values(p_hits, n):
+    """The q-values, in a list of n testable p-values, of the hits {p <= p*} of bh_cut, from the hits alone: statsmodels'
+    operations (get_q_vals) with the ranks of the hits and the length of the whole list.  The same bits as the whole list gives:
+    ascending, the hits are the list's head with their own ranks, and the running minimum that arrives from behind the cut is a q
+    above fdr, which every hit's own q lies below."""
+    p = np.asarray(p_hits, dtype=np.float64)
+    if p.size == 0:
+        return p.copy()
+    order = np.argsort(p, kind="stable")
+    q = p[order] / (np.arange(1, p.size + 1) / float(n))
+    q = np.minimum(np.minimum.accumulate(q[::-1])[::-1], 1.0)
+    out = np.empty_like(q)
+    out[order] = q
+    return out
+
+
+def _fdr_cuts(pval, n_valid, fdr):
+    """Per cohort (p*, the number of testable tiles) for BH q <= fdr over the cohort's TESTABLE tiles -- the existing tiles with a
+    non-NaN p-value: the ragged lists come from engine.tile_select at cut = +inf (the plane as it lies when every tile is
+    testable), their q-values from bh_ragged; no q plane is kept."""
+    import torch
+    from .. import engine
+    C, R, T = pval.shape
+    if R and T and int(n_valid.min()) >= T and not bool(torch.isnan(pval).any()):
+        lists, ptr = pval.reshape(-1), np.arange(C + 1, dtype=np.int64) * (R * T)
+    else:
+        got = engine.tile_select(pval, n_valid, float("inf"), index=False)
+        lists, ptr = got["score"], got["cohort_ptr"]
+    cuts = np.full(C, -1.0)
+    if lists.numel():
+        q, _ = bh_ragged(lists, ptr)
+        for c in range(C):
+            cuts[c] = bh_cut(lists[ptr[c]:ptr[c + 1]], q[ptr[c]:ptr[c + 1]], fdr)
+    return cuts, np.diff(ptr)
+
+
+def nb_model_hits(d_prs, idx, mu, sigma, f_muts, f_fasta, n_up=2, n_down=2, binsize=50, collapse=False, pval_max=None, fdr=None,
+                  device=0):
+    """The rows of nb_model's frame that pass a cut, for C cohorts on one bin grid, without building the frame: frame c equals
+    nb_model(d_prs[c], idx, mu[c], sigma[c], f_muts[c], ...) filtered by PVAL <= pval_max, or by q <= fdr -- bit for bit, in
+    order, with the rows' numbers in that full frame as the (int64) index.  Exactly one of pval_max / fdr.
+    fdr: Benjamini-Hochberg over the cohort's TESTABLE tiles, the existing tiles with a non-NaN p-value (a tile whose positions
+    are all non-ACGT has Pi = 0 and a NaN p-value, and one NaN makes every q-value of get_q_vals NaN): q = get_q_vals of
+    frame.PVAL.dropna(); the frame then has a QVAL column as well.
+    d_prs: C S_prob mappings; mu, sigma [C, R]; f_muts: C bed-like mutation files or frames (as nb_model's f_tabix).
+    One engine.tiled_nb_model call over all cohorts, the selection (engine.tile_select) on the device; only the hits come back.
+    The four planes take 28 bytes per (tile, cohort), fdr adds 8 for the lists and the sort's workspace; regions are NOT chunked:
+    the caller passes as many regions as fit.  frame.attrs holds n_testable and n_tiles of the cohort."""
+    if (pval_max is None) == (fdr is None):
+        raise ValueError("exactly one of pval_max and fdr must be given")
+    if n_up != n_down or n_up not in (1, 2):
+        raise NotImplementedError("the tile kernels take n_up = n_down = 1 or 2")
+    import pandas as pd
+    from .. import engine
+    from ..data_tools import genome as genome_mod
+    C = len(d_prs)
+    f_muts = list(f_muts)
+    idx = np.asarray(idx)
+    R = len(idx)
+    mu, sigma = np.asarray(mu, float).reshape(C, R), np.asarray(sigma, float).reshape(C, R)
+    if len(f_muts) != C:
+        raise ValueError("one mutation file per cohort: %d files for %d cohorts" % (len(f_muts), C))
+    g = f_fasta if isinstance(f_fasta, genome_mod.PackedGenome) else genome_mod.PackedGenome.from_fasta(f_fasta)
+    chroms = [str(c) for c in idx[:, 0]] if R else []
+    starts, ends = (idx[:, 1].astype(np.int64), idx[:, 2].astype(np.int64)) if R else (np.zeros(0, np.int64),) * 2
+    known = set(n.replace("chr", "") for n in g.names)
+    rows = []
+    for c, f in enumerate(f_muts):
+        m = f if isinstance(f, pd.DataFrame) else _mutation_rows(f)
+        m = m[m.CHROM.astype(str).str.replace("chr", "", regex=False).isin(known)]
+        rows.append((m.CHROM.astype(str).values, m.START.values.astype(np.int64), m.END.values.astype(np.int64), np.full(len(m), c, np.int32)))
+    mc, ms, me, co = (np.concatenate([r[j] for r in rows]) for j in range(4))
+    s_prob = np.stack([_s_prob_table(d, n_up, collapse) for d in d_prs])
+    res = engine.tiled_nb_model(g, chroms, starts, ends, s_prob, mu, sigma, mc, ms, me, co, binsize=binsize, device=device)
+    nval_dev = res["n_valid"]
+    if fdr is not None:
+        cuts, n_test = _fdr_cuts(res["pval"], nval_dev, fdr)
+    else:
+        cuts = np.full(C, float(pval_max))
+        n_test = engine.tile_select_counts(res["pval"], nval_dev, float("inf")).sum(dim=1).cpu().numpy()
+    hits = engine.tile_select(res["pval"], nval_dev, cuts, pt=res["pt"], exp=res["exp"], k=res["k"])
+    ptr = hits.pop("cohort_ptr")
+    hits = {k: v.cpu().numpy() for k, v in hits.items()}
+    first, nval = res["first_pos"].cpu().numpy(), np.maximum(res["n_valid"].cpu().numpy().astype(np.int64), 0)
+    n_pos = _region_positions(g, chroms, ends, first, n_up) if R else np.zeros(0, np.int64)
+    row0 = np.cumsum(nval) - nval                              # a region's first row in the full frame
+    frames = []
+    for c in range(C):
+        sel = slice(int(ptr[c]), int(ptr[c + 1]))
+        reg, t = hits["region"][sel].astype(np.int64), hits["tile"][sel].astype(np.int64)
+        df = _tile_frame(idx, mu[c], sigma[c], first, n_pos, binsize, reg, t, hits["k"][sel], hits["exp"][sel], hits["score"][sel],
+                         hits["pt"][sel])
+        if fdr is not None:
+            df["QVAL"] = hits_q_values(hits["score"][sel], int(n_test[c]))
+        df.index = pd.Index(row0[reg] + t, dtype=np.int64)
+        df.attrs.update(n_testable=int(n_test[c]), n_tiles=int(nval.sum()))
+        frames.append(df)
+    return frames
 
 
 def bh_ragged(p, row_ptr, n_global=None, rank0=None, carry=None, want_q=True, want_row_min=False, sorted_out=False):

@@ -434,6 +434,36 @@ int dig_site_counts(const int64_t *keys_sorted, int64_t total, int64_t E, int64_
 int dig_site_counts_host(const int64_t *keys_sorted, int64_t total, int64_t E, int64_t C, int64_t n_samples, int32_t *obs_snv,
                          int32_t *obs_samples, int device);
 
+/* ---- the hits of the per-base route for many cohorts (additive: the ABI version stays) -------------------------- *
+ * The entries of a score plane that pass a per-cohort cut, in the row order of the reference's nb_model frame (nb_model.py:188-234:
+ * one block per region, tiles ascending; one frame per cohort), without the frame being built.  score f64 [C, R, T] (the p-values
+ * of dig_tiled_nb_test), n_valid i32 [R] as dig_base_tile_probs* writes it (<= 0, the -1 of an unevaluated region included: the
+ * row has no tiles), cut f64 [C].  Tile (c, r, t) is a HIT when t < n_valid[r] and score[c, r, t] <= cut[c]: a NaN score or a NaN
+ * cut never hits, cut = +inf takes every existing tile with a non-NaN score.  C R < 2^31 and T < 2^31 (DIG_EINVAL otherwise,
+ * before anything is read).  Every typed pointer needs the alignment of its element and no more.
+ *   dig_tile_select_count: counts i32 [C R] = the hits of row (c, r), zeroed and written by the call (one streaming pass over the
+ *     plane; one integer atomic per run of lanes with one row and a hit).
+ *   The caller forms offsets i64 [C R], the exclusive prefix sum of counts, and total, their sum (the two-call protocol of
+ *     dig_overlap_join_count / fill).
+ *   dig_tile_select_fill: hit h of row (c, r), tiles ascending, goes to slot offsets[c R + r] + h -- hits lie cohort-major, then by
+ *     region, then by tile -- as hit_region i32, hit_tile i32, hit_score f64 and, from the planes pt, exp_in f64 and k i32
+ *     [C, R, T], hit_pt, hit_exp, hit_k [total].  Each output and each plane may be NULL: an output that is NULL, or whose plane
+ *     is, is skipped.  A row writes only inside its own slots [offsets[row], offsets[row + 1]) (total behind the last row) and
+ *     inside [0, total): offsets that are not the prefix sum write nowhere else (the host twin refuses them).
+ * Integer atomics only, so order-independent; nothing is launched for empty inputs. */
+int dig_tile_select_count(const double *score, const int32_t *n_valid, const double *cut, int64_t C, int64_t R, int64_t T,
+                          int32_t *counts, void *stream);
+int dig_tile_select_count_host(const double *score, const int32_t *n_valid, const double *cut, int64_t C, int64_t R, int64_t T,
+                               int32_t *counts, int device);
+int dig_tile_select_fill(const double *score, const int32_t *n_valid, const double *cut, int64_t C, int64_t R, int64_t T,
+                         const int64_t *offsets, int64_t total, const double *pt, const double *exp_in, const int32_t *k,
+                         int32_t *hit_region, int32_t *hit_tile, double *hit_score, double *hit_pt, double *hit_exp, int32_t *hit_k,
+                         void *stream);
+int dig_tile_select_fill_host(const double *score, const int32_t *n_valid, const double *cut, int64_t C, int64_t R, int64_t T,
+                              const int64_t *offsets, int64_t total, const double *pt, const double *exp_in, const int32_t *k,
+                              int32_t *hit_region, int32_t *hit_tile, double *hit_score, double *hit_pt, double *hit_exp,
+                              int32_t *hit_k, int device);
+
 /* ---- sufficient statistics in canonical chunks (bin-sharded runs) --------------------------- *
  * Same quantity as dig_scale_suffstats / dig_scale_factors, defined so that it does not depend on the sharding: the bins
  * are cut into K canonical chunks of the GLOBAL grid (boundaries floor(N j / K)); a rank computes the chunk sums of the

@@ -3,7 +3,8 @@
 
 Drop-in for the reference's scripts/DigDriver.py: the same four sub-commands with the same positional
 arguments and option names (DigDriver.py:160-275), and the same output, a tab-separated
-``<outdir>/<outpfx>.results.txt`` with header and index column (DigDriver.py:38-43,115-118).  The statistics
+``<outdir>/<outpfx>.results.txt`` with header and index column (DigDriver.py:38-43,115-118); and `tileDriver`, which the
+reference does not have: the per-base scan of many cohorts, written as ``<outdir>/<outpfx>.hits.txt``.  The statistics
 run through libdig_hip.so; `model` may be the reference's HDF5 map (`*.h5`, read by io/h5lite.py +
 io/pandas_fixed.py: no h5py or PyTables needed) or the directory mirror described in digdriver_amd/io/mapfile.py.
 """
@@ -104,6 +105,51 @@ def cmd_quick(args):
     write_results(res, args)
 
 
+TILE_MODELS = {(1, 1): 'sequence_model_64', (2, 2): 'sequence_model_1024'}
+
+
+def cmd_tile(args):
+    """tileDriver: the per-base scan of many cohorts on one bin grid; per cohort the tiles that pass the cut, as
+    <outdir>/<outpfx>.hits.txt (the rows of nb_model's frame, numbered as in it; with --fdr a QVAL column as well)."""
+    n = len(args.mutation_files)
+    if not len(args.maps) == len(args.outpfx) == n:
+        raise SystemExit("ERROR: --mutation-files, --maps and --outpfx must name the same number of cohorts.")
+    if (args.pval_max is None) == (args.fdr is None):
+        raise SystemExit("ERROR: you must provide exactly one of --pval-max and --fdr.")
+    key = TILE_MODELS.get((args.up, args.down))
+    if key is None:
+        raise NotImplementedError("the tile kernels take n_up = n_down = 1 or 2")
+    import numpy as np
+    from digdriver_amd.sequence_model import nb_model
+    print('Running per-base tile driver detection for {} cohorts'.format(n))
+    cols = ['CHROM', 'START', 'END', 'Y_PRED', 'STD']
+    idx, mu, sigma, d_prs = None, [], [], []
+    for f_map in args.maps:
+        reg = mapfile.read_columns(f_map, 'region_params', cols)
+        grid = np.stack([np.asarray(reg[k]).astype(np.int64) for k in cols[:3]], axis=1)
+        if idx is None:
+            idx = grid
+        elif not np.array_equal(grid, idx):
+            raise ValueError("{}: the rows of region_params (CHROM, START, END) differ from those of {}".format(f_map, args.maps[0]))
+        mu.append(np.asarray(reg['Y_PRED'], float))
+        sigma.append(np.asarray(reg['STD'], float))
+        try:
+            seq = mapfile.read_frame(f_map, key)
+        except KeyError:
+            raise SystemExit("ERROR: {} has no frame {} (--up {} --down {} needs it).".format(f_map, key, args.up, args.down))
+        d_prs.append(seq.set_index('CONTEXT').FREQ if 'CONTEXT' in seq.columns else seq.FREQ)
+    keep = np.ones(len(idx), bool) if not args.chroms else np.isin(idx[:, 0].astype(str), [c.replace('chr', '') for c in args.chroms])
+    if not keep.any():
+        raise SystemExit("ERROR: no region of region_params is left to scan.")
+    frames = nb_model.nb_model_hits(d_prs, idx[keep], np.array(mu)[:, keep], np.array(sigma)[:, keep], args.mutation_files, args.f_fasta,
+                                    n_up=args.up, n_down=args.down, binsize=args.binsize, pval_max=args.pval_max, fdr=args.fdr)
+    os.makedirs(args.outdir, exist_ok=True)
+    for pfx, frame in zip(args.outpfx, frames):
+        target = os.path.join(args.outdir, pfx + '.hits.txt')
+        print('\t{}: {} hits of {} testable tiles; saving to {}'.format(pfx, len(frame), frame.attrs['n_testable'], target))
+        mapfile.write_results_tsv(frame, target)
+
+
 def _common(p, element_caps):
     p.add_argument('fmut', type=str, help='annotated mutation file (DigPreprocess.py annotMutationFile format)')
     p.add_argument('model', type=str, help='pretrained mutation map')
@@ -171,6 +217,21 @@ def parse_args(text=None):
         e.add_argument('--skip_pvals', default=False, action='store_true', help='expected counts only')
         e.add_argument('--scale-factor-indel-manual', default=None, type=float, help='use this indel scale factor')
         e.set_defaults(func=func)
+
+    # not a reference sub-command: the reference's per-base route (nb_model.py:188-234) has no command line
+    d = sub.add_parser('tileDriver', help='per-base scan of many cohorts on one bin grid: the tiles that pass a cut')
+    d.add_argument('f_fasta', type=str, help='reference genome FASTA')
+    d.add_argument('--mutation-files', type=str, nargs='+', required=True, help='one bed-like mutation file per cohort')
+    d.add_argument('--maps', type=str, nargs='+', required=True, help='one pretrained mutation map per cohort, all on one bin grid')
+    d.add_argument('--outdir', type=str, required=True, help='directory for the hit files')
+    d.add_argument('--outpfx', type=str, nargs='+', required=True, help='one prefix per cohort: <outpfx>.hits.txt')
+    d.add_argument('--binsize', type=int, default=50, help='positions per tile')
+    d.add_argument('--up', type=int, default=1, help='context bases in front of a position (1 or 2)')
+    d.add_argument('--down', type=int, default=1, help='context bases behind a position (equal to --up)')
+    d.add_argument('--pval-max', type=float, default=None, help='keep the tiles with PVAL <= this')
+    d.add_argument('--fdr', type=float, default=None, help="keep the tiles with Benjamini-Hochberg q <= this over the cohort's testable tiles")
+    d.add_argument('--chroms', type=str, nargs='+', default=None, help='scan only the regions of these chromosomes')
+    d.set_defaults(func=cmd_tile)
 
     return parser.parse_args(text.split()) if text else parser.parse_args()
 
