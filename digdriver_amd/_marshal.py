@@ -36,6 +36,10 @@ class HostBackend:
     def empty(self, shape, dtype):
         return np.empty(shape, _NP[dtype])
 
+    def cat(self, xs, dtype=None):
+        """The arrays one after the other as `dtype` (None: their own); none at all: an empty array of it (i64 without one)."""
+        return np.concatenate([self.arr(x, dtype) for x in xs]) if len(xs) else self.empty(0, dtype or "i64")
+
     ptr = staticmethod(_lib.host_ptr)
 
     def call(self, name, *args, workspace=None):
@@ -68,6 +72,9 @@ class DeviceBackend:
 
     def empty(self, shape, dtype):
         return self.torch.empty(shape, dtype=self._dt[dtype], device=self.dev)
+
+    def cat(self, xs, dtype=None):
+        return self.torch.cat([self.arr(x, dtype) for x in xs]) if len(xs) else self.empty(0, dtype or "i64")
 
     ptr = staticmethod(_lib.dev_ptr)
 

@@ -14,8 +14,8 @@ Two properties of the reference that are kept on purpose (DESIGN, Training label
 """
 import numpy as np
 
-from .. import _lib
-from . import tabulate_gpu
+from .._marshal import is_cuda
+from . import cohort_rows, tabulate_gpu
 
 
 def objective_name(f_mut, suffix=''):
@@ -112,21 +112,15 @@ def window_objectives(idx, f_muts, max_muts_per_sample=None, sample_filter_stdev
     chrom_ids = {str(c): int(c) for c in np.unique(uniq[:, 0])}
     cohorts = [f if isinstance(f, dict) else encode_objective_rows(f, chrom_ids) for f in f_muts]
     names = [f.get("name", "cohort%d" % i) if isinstance(f, dict) else objective_name(f) for i, f in enumerate(f_muts)]
-    offs = np.concatenate([[0], np.cumsum([len(c["sample_names"]) for c in cohorts])]).astype(np.int64)
-    cat = lambda k, dt: np.concatenate([np.asarray(c[k], dt) for c in cohorts])
-    sample = np.concatenate([np.asarray(c["sample"], np.int32) + np.int32(o) for c, o in zip(cohorts, offs[:-1])])
-    rows = [cat("chrom", np.int64), cat("start", np.int64), cat("end", np.int64), sample, cat("uid", np.int32), cat("indel", np.uint8)]
-    dev = (not _lib.TORCH_FREE) if on_device is None else bool(on_device)
-    if dev:
-        import torch
-        from .._marshal import resolve_device
-        rows = [torch.as_tensor(r, device=resolve_device(device)) for r in rows]
+    offs = cohort_rows.sample_offsets(cohorts)
+    cat = lambda k, dt, shift=None: cohort_rows.column(cohorts, k, dt, shift)
+    rows = cohort_rows.place([cat("chrom", "i64"), cat("start", "i64"), cat("end", "i64"), cat("sample", "i32", offs), cat("uid", "i32"),
+                              cat("indel", "u8")], on_device, device)
     from .. import engine
     out = engine.window_objectives(uniq[:, 0], uniq[:, 1], uniq[:, 2], *rows, offs, max([c["n_uid"] for c in cohorts] + [1]),
                                    keep_from_hits=lambda h: keep_samples(h, offs, max_muts_per_sample, sample_filter_stdev),
                                    device=device)
-    labels = out["labels"]
-    labels = labels.cpu().numpy() if dev else labels
+    labels = out["labels"].cpu().numpy() if is_cuda(out["labels"]) else out["labels"]
     return names, np.ascontiguousarray(labels[inverse])
 
 

@@ -12,7 +12,7 @@ import numpy as np
 
 from .. import engine
 from .._marshal import device_backend
-from . import mutation_tools
+from . import cohort_rows, mutation_tools
 
 
 class ElementBlocks:
@@ -320,13 +320,11 @@ def tabulate_cohorts(blocks, cohorts, drop_duplicates=True, max_muts_per_sample=
     import torch
     dev = blocks.device
     C, E = len(cohorts), blocks.n_elements
-    cat = lambda k: torch.cat([c[k] for c in cohorts])
-    # sample ids are per cohort: make them globally distinct with an offset
-    offs = np.concatenate([[0], np.cumsum([len(c["sample_names"]) for c in cohorts])])
-    sample = torch.cat([c["sample"] + int(o) for c, o in zip(cohorts, offs[:-1])])
-    uid_off = np.concatenate([[0], np.cumsum([int(c["uid"].max().item()) + 1 if c["uid"].numel() else 0 for c in cohorts])])
-    uid = torch.cat([c["uid"] + int(o) for c, o in zip(cohorts, uid_off[:-1])])
-    chrom, start, end, indel, cohort = cat("chrom"), cat("start"), cat("end"), cat("indel"), cat("cohort")
+    # sample and mutation ids are per cohort: make them globally distinct with an offset
+    offs = cohort_rows.sample_offsets(cohorts)
+    sample = cohort_rows.column(cohorts, "sample", shift=offs)
+    uid = cohort_rows.column(cohorts, "uid", shift=cohort_rows.id_offsets(cohorts, "uid"))
+    chrom, start, end, indel, cohort = (cohort_rows.column(cohorts, k) for k in ("chrom", "start", "end", "indel", "cohort"))
     pm, pb = overlap_pairs(blocks, chrom, start, end)
     pm = pm.long()
     elt = blocks.elt[pb.long()]

@@ -25,7 +25,8 @@ import numpy as np
 import pandas as pd
 
 from .. import engine
-from ..data_tools import tabulate_gpu
+from .._marshal import resolve_device
+from ..data_tools import cohort_rows, tabulate_gpu
 from ..io import mapfile
 from ..sequence_model import genic_driver_tools, nb_model
 from . import transfer_tools
@@ -50,12 +51,11 @@ def genome_scale_factors(tables, cohorts, device, dev_tables=None):
     is parsed), and the device only joins, marks the rows that touch an unflagged bin and counts -- no sort (round 4 ran three
     torch.unique row sorts over the 11 M rows of 37 cohorts here: genome_scale_factors_by_sorting, kept as the cross-check)."""
     import torch
-    C = len(cohorts)
     bins = tabulate_gpu.ElementBlocks(tables.chrom, tables.start, tables.start + tables.window, np.arange(len(tables.start)),
                                       len(tables.start), device)
     mu_d, flag = (dev_tables[0], dev_tables[3]) if dev_tables is not None else \
         (torch.as_tensor(tables.mu, device=device), torch.as_tensor(tables.flag, device=device))
-    cat = lambda k: torch.cat([c[k] for c in cohorts])
+    cat = lambda k: cohort_rows.column(cohorts, k)
     chrom, cohort = cat("chrom"), cat("cohort")
     pm, pb = tabulate_gpu.overlap_pairs(bins, chrom, cat("start"), cat("end"))
     pm = pm.long()
@@ -84,20 +84,17 @@ def genome_scale_factors_by_sorting(tables, cohorts, device):
     bins = tabulate_gpu.ElementBlocks(tables.chrom, tables.start, tables.start + tables.window, np.arange(len(tables.start)),
                                       len(tables.start), device)
     flag = torch.as_tensor(tables.flag, device=device)
-    cat = lambda k: torch.cat([c[k] for c in cohorts])
+    cat = lambda k, shift=None: cohort_rows.column(cohorts, k, shift=shift)
     pm, pb = tabulate_gpu.overlap_pairs(bins, cat("chrom"), cat("start"), cat("end"))
     pm = pm.long()
     cohort = cat("cohort")
     ok = flag[bins.elt[pb.long()], cohort[pm]] == 0                    # the overlapped bin is unflagged in that cohort
     # the reference re-reads the intersected rows with read_mutation_file(drop_duplicates=True, unique_indels=True)
     # (mutation_tools.py:22-43,45-104), i.e. two de-duplications one after the other:
-    uid_off = np.concatenate([[0], np.cumsum([int(c["uid"].max().item()) + 1 if c["uid"].numel() else 0 for c in cohorts])])
-    uid = torch.cat([c["uid"] + int(o) for c, o in zip(cohorts, uid_off[:-1])])
-    smp_off = np.concatenate([[0], np.cumsum([len(c["sample_names"]) for c in cohorts])])
-    smp = torch.cat([c["sample"] + int(o) for c, o in zip(cohorts, smp_off[:-1])])
+    uid = cat("uid", cohort_rows.id_offsets(cohorts, "uid"))
+    smp = cat("sample", cohort_rows.sample_offsets(cohorts))
     indel = cat("indel")
-    gene_off = np.concatenate([[0], np.cumsum([int(c["gene"].max().item()) + 1 if c["gene"].numel() else 0 for c in cohorts])])
-    gene = torch.cat([c["gene"] + int(o) for c, o in zip(cohorts, gene_off[:-1])])
+    gene = cat("gene", cohort_rows.id_offsets(cohorts, "gene"))
     pm_ok = pm[ok]
     # step 1, drop_duplicate_mutations (mutation_tools.py:106-108): first row of every (cohort, uid, sample)
     key, inv = torch.unique(torch.stack([cohort[pm_ok], uid[pm_ok], smp[pm_ok]], dim=1), dim=0, return_inverse=True)
@@ -149,7 +146,7 @@ def run_element_cohorts(f_muts, f_pretrained, f_element_data, save_key, scale_fa
     import time
     import torch
     from concurrent.futures import ThreadPoolExecutor
-    dev = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
+    dev = resolve_device(device)
     assert len(f_muts) == len(f_pretrained) and len(f_muts) > 0
     C = len(f_muts)
     if read_workers is None:
@@ -265,46 +262,53 @@ def run_element_cohorts(f_muts, f_pretrained, f_element_data, save_key, scale_fa
     return frames
 
 
-def run_and_write_element_cohorts(f_muts, f_pretrained, f_element_data, save_key, outdir, prefixes, write_threads=None, **kw):
-    """run_element_cohorts + write_results with the two overlapped: cohort c's <outdir>/<prefix>.results.txt is written by a
-    worker thread (the native writer holds no interpreter lock) while the frames of the cohorts after it are assembled.
+def _run_and_write(run, n, outdir, prefixes, write_threads, writer):
+    """frames = run(on_frame) with the result files written as the frames arrive: on_frame(c, *made) takes what the route hands over
+    for cohort c, writer(path, threads, *made) -- called there, by the thread that assembles the frames -- returns the job a worker
+    thread runs (the native writer holds no interpreter lock), and the frames of the cohorts after c are assembled meanwhile.
     Returns (frames, paths); the files are complete when the call returns."""
     import os
     from concurrent.futures import ThreadPoolExecutor
     os.makedirs(outdir, exist_ok=True)
-    C = len(f_muts)
-    assert len(prefixes) == C
+    assert len(prefixes) == n
     paths = [os.path.join(outdir, pfx + '.results.txt') for pfx in prefixes]
     cores = os.cpu_count() or 1
-    threads = int(write_threads) if write_threads else max(1, min(8, cores // max(C, 1)))      # threads the writer uses per file
+    threads = int(write_threads) if write_threads else max(1, min(8, cores // max(n, 1)))      # threads the writer uses per file
     pending = []
-    with ThreadPoolExecutor(max_workers=max(1, min(C, cores))) as pool:
-        labels = []
-
-        def on_frame(c, frame, cols, index):
-            # the writer takes the frame's COLUMN ARRAYS (the dict the frame was built from, the OBS_* columns as integers:
-            # DigDriver.py:108-112) and the row labels encoded once: no pandas object is touched by a writer thread, whose
-            # Python part is then a few microseconds (frame.assign + the column extraction of 37 writer threads held the
-            # interpreter lock for 0.3 s of the 0.4 s the frames took)
-            if not labels:
-                labels.append(mapfile.encode_labels(index))
-            out_cols = [(k, np.asarray(v).astype(np.int64) if k in ('OBS_SAMPLES', 'OBS_SNV', 'OBS_INDEL') else np.asarray(v)) for k, v in cols.items()]
-
-            def write():
-                # (row labels or a column the native writer does not cover -- a quote, a tab or a newline in an element name, an
-                #  object column: encode_labels gives None / write_columns_tsv raises ValueError -- go the route write_results takes
-                #  for them: pandas.  ADVICE r5: the run used to abort here, behind all the device work.)
-                if labels[0] is not None:
-                    try:
-                        return mapfile.write_columns_tsv(paths[c], index.name, labels[0], out_cols, threads)
-                    except ValueError:
-                        pass
-                return _write_one(frame, paths[c], threads)
-            pending.append(pool.submit(write))
-        frames = run_element_cohorts(f_muts, f_pretrained, f_element_data, save_key, on_frame=on_frame, **kw)
+    with ThreadPoolExecutor(max_workers=max(1, min(n, cores))) as pool:
+        frames = run(lambda c, *made: pending.append(pool.submit(writer(paths[c], threads, *made))))
         for f in pending:
             f.result()
     return frames, paths
+
+
+def run_and_write_element_cohorts(f_muts, f_pretrained, f_element_data, save_key, outdir, prefixes, write_threads=None, **kw):
+    """run_element_cohorts + write_results with the two overlapped: cohort c's <outdir>/<prefix>.results.txt is written by a
+    worker thread while the frames of the cohorts after it are assembled (_run_and_write)."""
+    labels = []
+
+    def writer(path, threads, frame, cols, index):
+        # the writer takes the frame's COLUMN ARRAYS (the dict the frame was built from, the OBS_* columns as integers:
+        # DigDriver.py:108-112) and the row labels encoded once: no pandas object is touched by a writer thread, whose
+        # Python part is then a few microseconds (frame.assign + the column extraction of 37 writer threads held the
+        # interpreter lock for 0.3 s of the 0.4 s the frames took)
+        if not labels:
+            labels.append(mapfile.encode_labels(index))
+        out_cols = [(k, np.asarray(v).astype(np.int64) if k in ('OBS_SAMPLES', 'OBS_SNV', 'OBS_INDEL') else np.asarray(v)) for k, v in cols.items()]
+
+        def write():
+            # (row labels or a column the native writer does not cover -- a quote, a tab or a newline in an element name, an
+            #  object column: encode_labels gives None / write_columns_tsv raises ValueError -- go the route write_results takes
+            #  for them: pandas.  ADVICE r5: the run used to abort here, behind all the device work.)
+            if labels[0] is not None:
+                try:
+                    return mapfile.write_columns_tsv(path, index.name, labels[0], out_cols, threads)
+                except ValueError:
+                    pass
+            return _write_one(frame, path, threads)
+        return write
+    return _run_and_write(lambda on_frame: run_element_cohorts(f_muts, f_pretrained, f_element_data, save_key, on_frame=on_frame, **kw),
+                          len(f_muts), outdir, prefixes, write_threads, writer)
 
 
 def _write_one(df, path, threads):
@@ -365,30 +369,45 @@ def write_results(frames, outdir, prefixes, workers=None):
 # ---------------------------------------------------------------------------------------------
 # geneDriver for many cohorts
 # ---------------------------------------------------------------------------------------------
-def _read_gene_models(f_genemodels):
-    """The C gene models as load_pretrained_model leaves them, without its per-map device calls: the frames are read and checked
-    first (one gene index: ValueError naming the first map that differs), then the Gamma parameters of all of them are ONE
-    element-wise call over [G, C] (the same bits).  Returns (the frames with _GENE_COLS_LEFT columns, dict name -> f64 [G, C])."""
-    tt = transfer_tools
+def _read_models(files, key, index_col, rename, differs, stacked, columns):
+    """Frame `key` of the C maps as load_pretrained_model leaves it, without its per-map device calls: the frames are read, indexed
+    by `index_col`, renamed and checked first (one index: ValueError `differs`, formatted with f = the first map that differs, first =
+    the first map and key), then the `stacked` columns become f64 [n, C] planes and the Gamma parameters of every (MU, SIGMA) pair
+    among them are ONE element-wise call over [n, C] (the same bits).  Returns (the frames with `columns`, dict name -> f64 [n, C])."""
     raw = []
-    for f in f_genemodels:
-        m = mapfile.read_frame(f, 'genic_model')
-        m = m.set_index(m.GENE).rename(columns=tt._GENE_RENAME)
-        m['Pi_NONSYN'] = m.Pi_MIS + m.Pi_TRUNC
+    for f in files:
+        m = mapfile.read_frame(f, key)
+        m = m.set_index(m[index_col]).rename(columns=rename)
+        if 'Pi_NONSYN' in columns:                                          # (the gene model's one derived column)
+            m['Pi_NONSYN'] = m.Pi_MIS + m.Pi_TRUNC
         if raw and not m.index.equals(raw[0].index):
-            raise ValueError("{}: its gene model's gene index differs from that of {} (run_gene_cohorts needs one gene index for all "
-                             "maps)".format(f, list(f_genemodels)[0]))
+            raise ValueError(differs.format(f=f, first=list(files)[0], key=key))
         raw.append(m)
-    stack = lambda col: np.ascontiguousarray(np.stack([m[col].values for m in raw], axis=1), dtype=np.float64)
-    planes = {col: stack(col) for col in ['MU', 'SIGMA', 'MU_INDEL', 'SIGMA_INDEL', 'Pi_INDEL'] + ['Pi_' + c for c in tt.GENE_CLASSES]}
-    planes['ALPHA'], planes['THETA'] = nb_model.normal_params_to_gamma(planes['MU'], planes['SIGMA'])
-    planes['ALPHA_INDEL'], planes['THETA_INDEL'] = nb_model.normal_params_to_gamma(planes['MU_INDEL'], planes['SIGMA_INDEL'])
+    planes = {col: np.ascontiguousarray(np.stack([m[col].values for m in raw], axis=1), dtype=np.float64) for col in stacked}
+    pairs = [sfx for sfx in ('', '_INDEL') if 'MU' + sfx in planes]
+    for sfx in pairs:
+        planes['ALPHA' + sfx], planes['THETA' + sfx] = nb_model.normal_params_to_gamma(planes['MU' + sfx], planes['SIGMA' + sfx])
     frames = []
     for c, m in enumerate(raw):
-        for col in ('ALPHA', 'THETA', 'ALPHA_INDEL', 'THETA_INDEL'):
-            m[col] = planes[col][:, c]
-        frames.append(m[tt._GENE_COLS_LEFT])
+        for sfx in pairs:
+            m['ALPHA' + sfx], m['THETA' + sfx] = planes['ALPHA' + sfx][:, c], planes['THETA' + sfx][:, c]
+        frames.append(m[columns])
     return frames, planes
+
+
+def _read_gene_models(f_genemodels):
+    """The C gene models (_read_models): the frames with _GENE_COLS_LEFT columns and the rate, Gamma and Pi_* planes f64 [G, C]."""
+    tt = transfer_tools
+    return _read_models(f_genemodels, 'genic_model', 'GENE', tt._GENE_RENAME,
+                        "{f}: its gene model's gene index differs from that of {first} (run_gene_cohorts needs one gene index for all maps)",
+                        ['MU', 'SIGMA', 'MU_INDEL', 'SIGMA_INDEL', 'Pi_INDEL'] + ['Pi_' + c for c in tt.GENE_CLASSES], tt._GENE_COLS_LEFT)
+
+
+def _expected_syn_scale(genes, n_syn):
+    """The scale factor of a cohort from its gene model (index GENE, renamed) and its synonymous row count: observed over expected
+    synonymous mutations outside TP53 (transfer_tools.py:809-823,1116-1119: the serial routes' own pandas expression, the same bits)."""
+    background = genes.loc[genes.index != 'TP53']
+    return n_syn / (background.MU * background.Pi_SYN).sum()
 
 
 def run_gene_cohorts(f_muts, f_genemodels, scale_by_sample=False, pval_burden_nb=True, pval_burden_dnds=True, pval_sel=True,
@@ -422,13 +441,12 @@ def run_gene_cohorts(f_muts, f_genemodels, scale_by_sample=False, pval_burden_nb
         planes = {k: np.ascontiguousarray(v[inside]) for k, v in planes.items()}
     index = models[0].index
     G = len(index)
-    dev = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
+    dev = resolve_device(device)
 
     rows = [tabulate_gpu.encode_gene_rows(f, index, c, keep=keep) for c, f in enumerate(f_muts)]
-    offsets = np.concatenate([[0], np.cumsum([len(r["sample_names"]) for r in rows])]).astype(np.int64)
     tp53 = int(index.get_loc('TP53')) if 'TP53' in index else G + 1
-    up = lambda k: torch.as_tensor(np.concatenate([r[k] for r in rows]), device=dev)
-    counts = engine.gene_counts(up("gene"), up("sample"), up("annot"), up("cohort"), offsets, G, C, tp53,
+    stack = cohort_rows.place([cohort_rows.column(rows, k) for k in ("gene", "sample", "annot", "cohort")], True, dev)
+    counts = engine.gene_counts(*stack, cohort_rows.sample_offsets(rows), G, C, tp53,
                                 max_muts_per_sample=max_muts_per_sample, max_muts_per_gene_per_sample=max_muts_per_gene_per_sample)
     by_cohort = lambda x: x.transpose(-1, -2).contiguous().cpu().numpy()                     # [..., G, C] -> [..., C, G]
     obs_h = counts["obs"].permute(2, 1, 0).contiguous().cpu().numpy().astype(np.int64)       # [C, 5, G]
@@ -439,10 +457,7 @@ def run_gene_cohorts(f_muts, f_genemodels, scale_by_sample=False, pval_burden_nb
     # scale factors (transfer_tools.py:809-823) and the uniform indel rate (:709-721), a cohort at a time over G values
     if scale_by_expectation:
         print('scaling by expected synonymous mutations (excluding TP53)')
-        cj = np.empty(C)
-        for c, m in enumerate(models):
-            background = m.loc[m.index != 'TP53']
-            cj[c] = int(n_syn[c]) / (background.MU * background.Pi_SYN).sum()
+        cj = np.array([_expected_syn_scale(m, int(n_syn[c])) for c, m in enumerate(models)])
     else:
         cj = scale_factors
     theta = planes['THETA'] * 1.0 * cj[None, :]                          # (_attach_counts scales by 1.0, transfer_gene_model by cj)
@@ -510,23 +525,9 @@ def run_gene_cohorts(f_muts, f_genemodels, scale_by_sample=False, pval_burden_nb
 def run_and_write_gene_cohorts(f_muts, f_genemodels, outdir, prefixes, write_threads=None, **kw):
     """run_gene_cohorts + <outdir>/<prefix>.results.txt per cohort through the native writer, as `DigDriver.py geneDriver` writes
     it (mapfile.write_results_tsv of the frame as it is: the bytes of frame.to_csv), each file by a worker thread while the frames
-    of the cohorts after it are assembled.  Returns (frames, paths); the files are complete when the call returns."""
-    import os
-    from concurrent.futures import ThreadPoolExecutor
-    os.makedirs(outdir, exist_ok=True)
-    C = len(f_muts)
-    assert len(prefixes) == C
-    paths = [os.path.join(outdir, pfx + '.results.txt') for pfx in prefixes]
-    cores = os.cpu_count() or 1
-    threads = int(write_threads) if write_threads else max(1, min(8, cores // max(C, 1)))
-    pending = []
-    with ThreadPoolExecutor(max_workers=max(1, min(C, cores))) as pool:
-        frames = run_gene_cohorts(f_muts, f_genemodels,
-                                  on_frame=lambda c, frame: pending.append(pool.submit(mapfile.write_results_tsv, frame, paths[c], threads)),
-                                  **kw)
-        for f in pending:
-            f.result()
-    return frames, paths
+    of the cohorts after it are assembled (_run_and_write)."""
+    return _run_and_write(lambda on_frame: run_gene_cohorts(f_muts, f_genemodels, on_frame=on_frame, **kw), len(f_muts), outdir, prefixes,
+                          write_threads, lambda path, threads, frame: lambda: mapfile.write_results_tsv(frame, path, threads))
 
 
 # ---------------------------------------------------------------------------------------------
@@ -536,26 +537,11 @@ _SITE_MODEL_COLS = ['R_OBS'] + transfer_tools._RATE_COLS + ['Pi_SUM']         # 
 
 
 def _read_site_models(f_pretrained, pretrain_key):
-    """The C element models of the sites route as load_pretrained_model leaves them, without its per-map device calls: the frames
-    are read and checked first (one element index: ValueError naming the first map that differs), then the Gamma parameters of all
-    of them are ONE element-wise call over [E, C] (the same bits).  Returns (the frames with transfer_element_model's columns,
-    dict name -> f64 [E, C])."""
-    raw = []
-    for f in f_pretrained:
-        m = mapfile.read_frame(f, pretrain_key)
-        m = m.set_index(m.ELT).rename(columns={'P_SUM': 'Pi_SUM', 'P_INDEL': 'Pi_INDEL'})
-        if raw and not m.index.equals(raw[0].index):
-            raise ValueError("{}: the element index of its '{}' model differs from that of {} (run_sites_cohorts needs one element "
-                             "index for all maps)".format(f, pretrain_key, list(f_pretrained)[0]))
-        raw.append(m)
-    stack = lambda col: np.ascontiguousarray(np.stack([m[col].values for m in raw], axis=1), dtype=np.float64)
-    planes = {col: stack(col) for col in ('MU', 'SIGMA', 'Pi_SUM')}
-    planes['ALPHA'], planes['THETA'] = nb_model.normal_params_to_gamma(planes['MU'], planes['SIGMA'])
-    frames = []
-    for c, m in enumerate(raw):
-        m['ALPHA'], m['THETA'] = planes['ALPHA'][:, c], planes['THETA'][:, c]
-        frames.append(m[_SITE_MODEL_COLS])
-    return frames, planes
+    """The C element models of the sites route (_read_models): the frames with transfer_element_model's columns and the MU, SIGMA,
+    Pi_SUM, ALPHA, THETA planes f64 [E, C]."""
+    return _read_models(f_pretrained, pretrain_key, 'ELT', {'P_SUM': 'Pi_SUM', 'P_INDEL': 'Pi_INDEL'},
+                        "{f}: the element index of its '{key}' model differs from that of {first} (run_sites_cohorts needs one element "
+                        "index for all maps)", ('MU', 'SIGMA', 'Pi_SUM'), _SITE_MODEL_COLS)
 
 
 def _empty_site_table():
@@ -589,20 +575,13 @@ def run_sites_cohorts(f_muts, f_sites, f_pretrained, pretrain_key, scale_factors
     rows = [sites.encode_site_rows(f, table["dicts"], c) for c, f in enumerate(f_muts)]
     models, planes = _read_site_models(f_pretrained, pretrain_key)
     index = models[0].index
-    offsets = np.concatenate([[0], np.cumsum([len(r["sample_names"]) for r in rows])]).astype(np.int64)
+    offsets = cohort_rows.sample_offsets(rows)
     if offsets[-1] >= 2 ** 31:
         raise ValueError("{} samples: the global sample is 32-bit; pass fewer cohorts per call".format(int(offsets[-1])))
     E_sites = len(table["elt_names"])
-    if device is None:
-        up = np.ascontiguousarray
-    else:
-        import torch
-        dev = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
-        up = lambda a: torch.as_tensor(np.ascontiguousarray(a), device=dev)
-    cat = lambda k: up(np.concatenate([r[k] for r in rows]))
-    sample = up(np.concatenate([r["sample"] + np.int32(offsets[c]) for c, r in enumerate(rows)]))
-    counts = engine.site_counts(up(table["site_pos"]), up(table["site_end"]), up(table["site_attr"]), up(table["site_elt"]),
-                                cat("pos"), cat("end"), cat("attr"), sample, cat("cohort"), offsets, E_sites, C)
+    stack = [table[k] for k in ("site_pos", "site_end", "site_attr", "site_elt")] + [cohort_rows.column(rows, k) for k in ("pos", "end", "attr")] + \
+        [cohort_rows.column(rows, "sample", shift=offsets), cohort_rows.column(rows, "cohort")]
+    counts = engine.site_counts(*cohort_rows.place(stack, device is not None, device), offsets, E_sites, C)
     # site elements -> model rows: an element the model lacks is dropped, a model element no site names counts nothing
     place = pd.Index(table["elt_names"]).get_indexer(index) if E_sites else np.full(len(index), -1)
     host = lambda x: x.cpu().numpy() if engine.is_cuda(x) else np.asarray(x)
@@ -616,9 +595,7 @@ def run_sites_cohorts(f_muts, f_sites, f_pretrained, pretrain_key, scale_factors
         cj = np.empty(C)
         for c, f in enumerate(f_pretrained):                               # (transfer_tools.py:1116-1119)
             genes = mapfile.read_frame(f, 'genic_model')
-            genes = genes.set_index(genes.GENE).rename(columns=transfer_tools._GENE_RENAME)
-            background = genes.loc[genes.index != 'TP53']
-            cj[c] = rows[c]["n_syn"] / (background.MU * background.Pi_SYN).sum()
+            cj[c] = _expected_syn_scale(genes.set_index(genes.GENE).rename(columns=transfer_tools._GENE_RENAME), rows[c]["n_syn"])
     else:
         cj = given
     print('Calculating statistics')
@@ -653,19 +630,6 @@ def run_sites_cohorts(f_muts, f_sites, f_pretrained, pretrain_key, scale_factors
 def run_and_write_sites_cohorts(f_muts, f_sites, f_pretrained, pretrain_key, outdir, prefixes, write_threads=None, **kw):
     """run_sites_cohorts + <outdir>/<prefix>.results.txt per cohort through the native writer, as `DigDriver.py elementDriver
     --f-sites` writes it (DigDriver.py cmd_element: the OBS_* columns as integers), each file by a worker thread while the frames of
-    the cohorts after it are assembled.  Returns (frames, paths); the files are complete when the call returns."""
-    import os
-    from concurrent.futures import ThreadPoolExecutor
-    os.makedirs(outdir, exist_ok=True)
-    C = len(f_muts)
-    assert len(prefixes) == C
-    paths = [os.path.join(outdir, pfx + '.results.txt') for pfx in prefixes]
-    cores = os.cpu_count() or 1
-    threads = int(write_threads) if write_threads else max(1, min(8, cores // max(C, 1)))
-    pending = []
-    with ThreadPoolExecutor(max_workers=max(1, min(C, cores))) as pool:
-        frames = run_sites_cohorts(f_muts, f_sites, f_pretrained, pretrain_key,
-                                   on_frame=lambda c, frame: pending.append(pool.submit(_write_one, frame, paths[c], threads)), **kw)
-        for f in pending:
-            f.result()
-    return frames, paths
+    the cohorts after it are assembled (_run_and_write)."""
+    return _run_and_write(lambda on_frame: run_sites_cohorts(f_muts, f_sites, f_pretrained, pretrain_key, on_frame=on_frame, **kw),
+                          len(f_muts), outdir, prefixes, write_threads, lambda path, threads, frame: lambda: _write_one(frame, path, threads))

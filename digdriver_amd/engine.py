@@ -13,12 +13,17 @@ element at a time:
 
 Every function takes either torch CUDA tensors (device entry points, enqueued on
 torch's current stream, zero copies) or numpy arrays (``*_host`` twins); each is written
-once on the backend pair of _marshal.py.  PyTorch is used only for device memory and streams.
+once on the backend pair of _marshal.py (the plans keep their cached-argument run() paths).  The two-call entry points
+(counts, fill) share `_scan`, the routes that turn a refused requirement into ValueError share `_requirements_as_value_errors`, and
+the callers stack their cohorts with data_tools/cohort_rows.py; nothing here imports data_tools.  PyTorch is used only for device
+memory and streams.
 """
+import contextlib
+
 import numpy as np
 
 from . import _lib
-from ._marshal import backend_of, backend_on, device_backend, is_cuda, resolve_device
+from ._marshal import backend_of, backend_on, device_backend, is_cuda
 
 ES_PLANES = _lib.ES_PLANES
 GS_PLANES = _lib.GS_PLANES
@@ -57,6 +62,31 @@ def _workspace(kind, E, C, dev, private=False):
 def _shared_workspace(be, kind, E, C, use=True):
     """The `workspace=` of be.call for a one-shot launch: the cached buffer on the device (NULL with use=False), nothing on the host."""
     return _workspace(kind, E, C, be.dev) if be.is_device and use else (None, 0)
+
+
+def _scan(be, counts, groups=None):
+    """The i32 counts of a two-call entry point -> (their exclusive prefix sum, i64 on the backend; the total as a host int).
+    groups: the counts are that many runs of one length (tile_select's cohorts); then also, from the same transfer as the total,
+    where every run starts and the last one ends: host int64 [groups + 1]."""
+    n, g = counts.shape[0], 1 if groups is None else groups
+    offsets, ends = be.empty(0, "i64"), np.zeros(g, np.int64)
+    if n:
+        incl = be.torch.cumsum(counts, 0, dtype=be.torch.int64) if be.is_device else np.cumsum(counts, dtype=np.int64)
+        ends = incl[n // g - 1::n // g]                                   # the running total behind every run; the last is the total
+        offsets, ends = incl - counts, ends.cpu().numpy() if be.is_device else ends
+    ptr = np.concatenate([[0], ends]).astype(np.int64)
+    return (offsets, int(ptr[-1])) if groups is None else (offsets, int(ptr[-1]), ptr)
+
+
+@contextlib.contextmanager
+def _requirements_as_value_errors():
+    """A requirement the library refuses ("requirement failed" in the DigHipError) leaves as ValueError with the same text."""
+    try:
+        yield
+    except _lib.DigHipError as exc:
+        if "requirement failed" in str(exc):
+            raise ValueError(str(exc)) from exc
+        raise
 
 
 def _cols(a):
@@ -196,8 +226,7 @@ def overlap_join(be, start_key, runmax_key, blk_end, m_chrom, m_start, m_end, ma
     join = [p(x) for x in tabs[:3]] + [n_blk] + [p(x) for x in tabs[3:]] + [n]
     counts = be.empty(n, "i32")
     be.call("dig_overlap_join_count", *join, p(counts))
-    incl = be.torch.cumsum(counts, 0, dtype=be.torch.int64) if be.is_device else np.cumsum(counts, dtype=np.int64)
-    total, offsets = int(incl[-1]), incl - counts
+    offsets, total = _scan(be, counts)
     if max_pairs is not None and total > max_pairs:
         raise ValueError(too_many % total)
     pair_row, pair_blk = be.empty(total, "i32"), be.empty(total, "i32")
@@ -334,12 +363,8 @@ def sequence_counts(win_chrom, win_start, win_end, row_chrom, row_start, row_end
                                too_many="%d (row, window) pairs: the join's pair indices are 32-bit; fewer cohorts per call")
     p = be.ptr
     counts = be.empty((max(C, 0), max(K, 0)), "i64")
-    try:
+    with _requirements_as_value_errors():
         be.call("dig_sequence_counts", p(pair_row), pair_row.shape[0], p(row_type), p(row_cohort), n, K, C, p(counts))
-    except _lib.DigHipError as exc:
-        if "requirement failed" in str(exc):
-            raise ValueError(str(exc)) from exc
-        raise
     return counts
 
 
@@ -378,14 +403,10 @@ def site_counts(site_pos, site_end, site_attr, site_elt, row_pos, row_end, row_a
     p = be.ptr
     search = [p(site_pos), p(site_end), p(site_attr), p(site_elt), S, E, p(row_pos), p(row_end), p(row_attr), p(row_sample),
               p(row_cohort), p(off), n, C, n_samples]
-    try:
+    with _requirements_as_value_errors():
         counts = be.empty(n, "i32")
         be.call("dig_site_match_count", *search, p(counts))
-        if n:
-            incl = be.torch.cumsum(counts, 0, dtype=be.torch.int64) if be.is_device else np.cumsum(counts, dtype=np.int64)
-            total, offsets = int(incl[-1]), incl - counts
-        else:
-            total, offsets = 0, be.empty(0, "i64")
+        offsets, total = _scan(be, counts)
         if total > 2 ** 31 - 1:
             raise ValueError("%d (row, site) matches: the observed counts are 32-bit; pass fewer cohorts per call" % total)
         keys = be.empty(total, "i64")
@@ -393,10 +414,6 @@ def site_counts(site_pos, site_end, site_attr, site_elt, row_pos, row_end, row_a
         keys = _sorted(be, keys)
         obs_snv, obs_samples = be.empty((E, C), "i32"), be.empty((E, C), "i32")
         be.call("dig_site_counts", p(keys), total, E, C, n_samples, p(obs_snv), p(obs_samples))
-    except _lib.DigHipError as exc:
-        if "requirement failed" in str(exc):
-            raise ValueError(str(exc)) from exc
-        raise
     return dict(obs_snv=obs_snv, obs_samples=obs_samples)
 
 
@@ -434,34 +451,28 @@ def scale_suffstats(bin_mu, bin_flag, device=0, out=None):
 def scale_factors_local(bin_mu, bin_flag, n_snv_obs, n_ind_obs, out=None):
     """Single-shard scale factors (transfer_tools.py:148-156): masked column sums and the two divisions in one pair of
     kernels (dig_scale_factors_local).  Returns (cj, cj_indel, exp_sum) device tensors."""
-    import torch
-    dev = bin_mu.device
-    bin_mu, bin_flag = _t(bin_mu, "f64", dev), _t(bin_flag, "u8", dev)
+    be = device_backend(bin_mu.device)
+    bin_mu, bin_flag = be.arr(bin_mu, "f64"), be.arr(bin_flag, "u8")
     N, C = bin_mu.shape
-    n_snv_obs, n_ind_obs = _t(n_snv_obs, "f64", dev), _t(n_ind_obs, "f64", dev)
+    n_snv_obs, n_ind_obs = be.arr(n_snv_obs, "f64"), be.arr(n_ind_obs, "f64")
     if out is None:
-        out = tuple(torch.empty(C, dtype=torch.float64, device=dev) for _ in range(3))
-    ws, wsb = _workspace("suffstats", N, C, dev)
-    with torch.cuda.device(dev):
-        _lib.call("dig_scale_factors_local", _lib.dev_ptr(bin_mu), _lib.dev_ptr(bin_flag), N, C, _lib.dev_ptr(n_snv_obs),
-                  _lib.dev_ptr(n_ind_obs), _lib.dev_ptr(out[2]), _lib.dev_ptr(out[0]), _lib.dev_ptr(out[1]), _lib.dev_ptr(ws),
-                  wsb, _lib.stream_ptr())
+        out = tuple(be.empty(C, "f64") for _ in range(3))
+    p = be.ptr
+    be.call("dig_scale_factors_local", p(bin_mu), p(bin_flag), N, C, p(n_snv_obs), p(n_ind_obs), p(out[2]), p(out[0]), p(out[1]),
+            workspace=_shared_workspace(be, "suffstats", N, C))
     return out
 
 
 def scale_factors_from_parts(parts, out=None):
     """cj, cj_indel from the all-gathered per-shard statistics `parts` f64 [world, 3, C] on the device
     (rank-ordered sums + division in one kernel; transfer_tools.py:153-154)."""
-    import torch
-    dev = parts.device
-    parts = _t(parts, "f64", dev)
+    be = device_backend(parts.device)
+    parts = be.arr(parts, "f64")
     world, three, C = parts.shape
     assert three == 3
     if out is None:
-        out = (torch.empty(C, dtype=torch.float64, device=dev), torch.empty(C, dtype=torch.float64, device=dev))
-    with torch.cuda.device(dev):
-        _lib.call("dig_scale_factors", _lib.dev_ptr(parts), world, C, _lib.dev_ptr(out[0]), _lib.dev_ptr(out[1]),
-                  _lib.stream_ptr())
+        out = (be.empty(C, "f64"), be.empty(C, "f64"))
+    be.call("dig_scale_factors", be.ptr(parts), world, C, be.ptr(out[0]), be.ptr(out[1]))
     return out
 
 
@@ -1060,14 +1071,14 @@ def check_tile_regions(starts, ends, n_up):
         raise ValueError("a region that starts at 1 would fetch from a negative position (the reference's pysam fetch fails too)")
 
 
-def base_tile_probs(genome, chroms, starts, ends, s_prob, binsize, n_tiles=None, device=0):
+def base_tile_probs(genome, chroms, starts, ends, s_prob, binsize, n_tiles=None, device=0, on_device=True):
     """Tile probabilities of regions of a PackedGenome for C cohorts at once (sequence_tools.py:292-317 + the tiling of
     nb_model.py:126-186).  s_prob: f64 [C, 64] (trinucleotide contexts, index 16 b0 + 4 b1 + b2) or [C, 1024]
     (penta-nucleotide: the reference's default n_up = n_down = 2; index in itertools.product('ACGT', repeat=5) order).
-    Returns device tensors (pt [C, R, n_tiles], first_pos [R], n_valid [R]); n_tiles defaults to what the longest region
-    needs."""
-    import torch
-    dev = resolve_device(device)
+    Returns (pt [C, R, n_tiles], first_pos [R], n_valid [R]); n_tiles defaults to what the longest region needs.
+    on_device=True keeps the genome resident in HBM and returns device tensors; False goes through the host twin and returns
+    arrays."""
+    be = backend_on(device, on_device)
     ci = genome.chrom_index(chroms)
     R = len(ci)
     st, en = _lib.as_host(starts, np.int64).ravel(), _lib.as_host(ends, np.int64).ravel()
@@ -1076,21 +1087,17 @@ def base_tile_probs(genome, chroms, starts, ends, s_prob, binsize, n_tiles=None,
     binsize = int(binsize)
     if n_tiles is None:
         n_tiles = int(max(1, -(-int((en - st).max() if R else 1) // binsize)))
-    s_prob = _t(s_prob, "f64", dev)
-    assert s_prob.dim() == 2 and s_prob.shape[1] in (64, 1024), "s_prob must be [C, 64] (trinucleotide) or [C, 1024] (penta-nucleotide)"
+    s_prob = be.arr(s_prob, "f64")
+    assert s_prob.ndim == 2 and s_prob.shape[1] in (64, 1024), "s_prob must be [C, 64] (trinucleotide) or [C, 1024] (penta-nucleotide)"
     C = s_prob.shape[0]
     n_up = 1 if s_prob.shape[1] == 64 else 2
     check_tile_regions(st, en, n_up)
-    words, off, ln = genome.on_device(dev)
-    t = lambda a: torch.as_tensor(a, device=dev)
-    rc, rs, re_ = t(ci), t(st), t(en)
-    pt = torch.empty((C, R, n_tiles), dtype=torch.float64, device=dev)
-    first = torch.empty(R, dtype=torch.int64, device=dev)
-    nval = torch.empty(R, dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        _lib.call("dig_base_tile_probs_ctx", _lib.dev_ptr(words), words.numel(), _lib.dev_ptr(off), _lib.dev_ptr(ln),
-                  len(genome.names), _lib.dev_ptr(rc), _lib.dev_ptr(rs), _lib.dev_ptr(re_), R, _lib.dev_ptr(s_prob), C, n_up,
-                  binsize, n_tiles, _lib.dev_ptr(pt), _lib.dev_ptr(first), _lib.dev_ptr(nval), _lib.stream_ptr())
+    words, off, ln = genome.on_device(be.dev) if be.is_device else (genome.words, genome.offsets, genome.lengths)
+    regions = [be.arr(a) for a in (ci, st, en)]
+    pt, first, nval = be.empty((C, R, n_tiles), "f64"), be.empty(R, "i64"), be.empty(R, "i32")
+    p = be.ptr
+    be.call("dig_base_tile_probs_ctx", p(words), words.shape[0], p(off), p(ln), len(genome.names), *[p(a) for a in regions], R,
+            p(s_prob), C, n_up, binsize, n_tiles, p(pt), p(first), p(nval))
     return pt, first, nval
 
 
@@ -1098,37 +1105,33 @@ def tile_mut_counts(genome, chroms, starts, ends, first_pos, n_valid, mut_chrom,
                     n_tiles):
     """k i32 [C, R, n_tiles]: mutation rows per tile and cohort (nb_model.py:133-136,160-163).  Regions and mutations
     are joined with the interval-join kernels (a tabix fetch returns the rows overlapping the region); a row counts in
-    the tile that holds its START.  mut_* are device tensors or host arrays (chromosome labels as in `chroms`)."""
-    import torch
-    from .data_tools import tabulate_gpu
-    dev = first_pos.device
-    R = first_pos.numel()
-    ci = genome.chrom_index(chroms)
-    blocks = tabulate_gpu.ElementBlocks(ci, _lib.as_host(starts, np.int64).ravel(), _lib.as_host(ends, np.int64).ravel(),
-                                        np.arange(R), R, dev)
-    mc = torch.as_tensor(genome.chrom_index(list(np.asarray(mut_chrom).astype(str))) if not is_cuda(mut_chrom) else mut_chrom,
-                         device=dev).to(torch.int64)
-    ms, me = _t(mut_start, "i64", dev), _t(mut_end, "i64", dev)
-    co = _t(mut_cohort, "i32", dev)
-    pm, pb = tabulate_gpu.overlap_pairs(blocks, mc, ms, me)
-    pr = blocks.elt[pb.long()].to(torch.int32).contiguous()          # block row -> region index
-    k = torch.empty((int(C), R, int(n_tiles)), dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        _lib.call("dig_tile_mut_counts", _lib.dev_ptr(pm), _lib.dev_ptr(pr), pm.numel(), _lib.dev_ptr(ms), _lib.dev_ptr(co),
-                  _lib.dev_ptr(first_pos), _lib.dev_ptr(n_valid), int(binsize), int(n_tiles), R, int(C), _lib.dev_ptr(k),
-                  _lib.stream_ptr())
+    the tile that holds its START.  first_pos, n_valid as base_tile_probs returns them: device tensors -> a device tensor, arrays
+    -> the host twins.  mut_*: device tensors or host arrays (chromosome labels as in `chroms`)."""
+    be = backend_of(first_pos, n_valid)
+    first_pos, n_valid = be.arr(first_pos, "i64", (-1,)), be.arr(n_valid, "i32", (-1,))
+    R = first_pos.shape[0]
+    order, start_key, runmax_key, blk_end = join_blocks(genome.chrom_index(chroms), _lib.as_host(starts, np.int64),
+                                                        _lib.as_host(ends, np.int64))
+    mc = be.arr(mut_chrom if is_cuda(mut_chrom) else genome.chrom_index(list(np.asarray(mut_chrom).astype(str))), "i64")
+    ms, me, co = be.arr(mut_start, "i64"), be.arr(mut_end, "i64"), be.arr(mut_cohort, "i32")
+    pm, pb = overlap_join(be, start_key, runmax_key, blk_end, mc, ms, me)
+    pr = be.arr(order, "i32")[pb.long() if be.is_device else pb]      # block of the sorted table -> region
+    k = be.empty((int(C), R, int(n_tiles)), "i32")
+    p = be.ptr
+    be.call("dig_tile_mut_counts", p(pm), p(pr), pm.shape[0], p(ms), *([] if be.is_device else [ms.shape[0]]), p(co), p(first_pos),
+            p(n_valid), int(binsize), int(n_tiles), R, int(C), p(k))
     return k
 
 
 def tiled_nb_model(genome, chroms, starts, ends, s_prob, mu, sigma, mut_chrom, mut_start, mut_end, mut_cohort, binsize=50,
-                   device=0):
+                   device=0, on_device=True):
     """nb_model (nb_model.py:188-234) for C cohorts x R regions in three launches + the interval join:
-    base_tile_probs -> tile_mut_counts -> tiled_nb_test.  mu, sigma: [C, R].  Returns a dict of device tensors
-    pval, exp, pt [C, R, n_tiles], k i32 [C, R, n_tiles], first_pos [R], n_valid [R]."""
-    pt, first, nval = base_tile_probs(genome, chroms, starts, ends, s_prob, binsize, device=device)
+    base_tile_probs -> tile_mut_counts -> tiled_nb_test.  mu, sigma: [C, R].  Returns a dict of device tensors (arrays with
+    on_device=False) pval, exp, pt [C, R, n_tiles], k i32 [C, R, n_tiles], first_pos [R], n_valid [R]."""
+    pt, first, nval = base_tile_probs(genome, chroms, starts, ends, s_prob, binsize, device=device, on_device=on_device)
     C, R, n_tiles = pt.shape
     k = tile_mut_counts(genome, chroms, starts, ends, first, nval, mut_chrom, mut_start, mut_end, mut_cohort, C, binsize, n_tiles)
-    pval, ex = tiled_nb_test(pt, k, mu, sigma)
+    pval, ex = tiled_nb_test(pt, k, mu, sigma, device=device)
     return dict(pval=pval, exp=ex, pt=pt, k=k, first_pos=first, n_valid=nval)
 
 
@@ -1140,12 +1143,8 @@ def _tile_counts(be, score, n_valid, cut):
     n_valid, cut = be.arr(n_valid, "i32", (R,)), _per_cohort(be, cut, C)
     plane = [score, n_valid, cut, C, R, T]
     counts = be.empty(C * R, "i32")
-    try:
+    with _requirements_as_value_errors():
         be.call("dig_tile_select_count", *[be.ptr(x) for x in plane[:3]], C, R, T, be.ptr(counts))
-    except _lib.DigHipError as exc:
-        if "requirement failed" in str(exc):
-            raise ValueError(str(exc)) from exc
-        raise
     return plane, counts, C, R, T
 
 
@@ -1171,15 +1170,8 @@ def tile_select(score, n_valid, cut, pt=None, exp=None, k=None, device=0, index=
     planes = dict(pt=be.arr(pt, "f64", (C, R, T)), exp=be.arr(exp, "f64", (C, R, T)), k=be.arr(k, "i32", (C, R, T)))
     p = be.ptr
     plane = [p(x) for x in held[:3]] + [C, R, T]
-    try:
-        if C * R:
-            incl = be.torch.cumsum(counts, 0, dtype=be.torch.int64) if be.is_device else np.cumsum(counts, dtype=np.int64)
-            offsets = incl - counts
-            ends = incl[R - 1::R]                                      # the hits up to each cohort's last row
-            cohort_ptr = np.concatenate([[0], ends.cpu().numpy() if be.is_device else ends]).astype(np.int64)
-        else:
-            offsets, cohort_ptr = be.empty(0, "i64"), np.zeros(C + 1, np.int64)
-        total = int(cohort_ptr[-1])
+    with _requirements_as_value_errors():
+        offsets, total, cohort_ptr = _scan(be, counts, groups=C)
         if total > 2 ** 31 - 1:
             raise ValueError("%d hits: a smaller cut or fewer cohorts per call" % total)
         res = dict(region=be.empty(total, "i32"), tile=be.empty(total, "i32")) if index else {}
@@ -1189,10 +1181,6 @@ def tile_select(score, n_valid, cut, pt=None, exp=None, k=None, device=0, index=
                 res[name] = be.empty(total, "i32" if name == "k" else "f64")
         be.call("dig_tile_select_fill", *plane, p(offsets), total, p(planes["pt"]), p(planes["exp"]), p(planes["k"]),
                 p(res.get("region")), p(res.get("tile")), p(res["score"]), p(res.get("pt")), p(res.get("exp")), p(res.get("k")))
-    except _lib.DigHipError as exc:
-        if "requirement failed" in str(exc):
-            raise ValueError(str(exc)) from exc
-        raise
     res["cohort_ptr"] = cohort_ptr
     return res
 

@@ -230,7 +230,7 @@ def nb_model_hits(d_prs, idx, mu, sigma, f_muts, f_fasta, n_up=2, n_down=2, bins
         raise NotImplementedError("the tile kernels take n_up = n_down = 1 or 2")
     import pandas as pd
     from .. import engine
-    from ..data_tools import genome as genome_mod
+    from ..data_tools import cohort_rows, genome as genome_mod
     C = len(d_prs)
     f_muts = list(f_muts)
     idx = np.asarray(idx)
@@ -243,11 +243,12 @@ def nb_model_hits(d_prs, idx, mu, sigma, f_muts, f_fasta, n_up=2, n_down=2, bins
     starts, ends = (idx[:, 1].astype(np.int64), idx[:, 2].astype(np.int64)) if R else (np.zeros(0, np.int64),) * 2
     known = set(n.replace("chr", "") for n in g.names)
     rows = []
-    for c, f in enumerate(f_muts):
+    for f in f_muts:
         m = f if isinstance(f, pd.DataFrame) else _mutation_rows(f)
         m = m[m.CHROM.astype(str).str.replace("chr", "", regex=False).isin(known)]
-        rows.append((m.CHROM.astype(str).values, m.START.values.astype(np.int64), m.END.values.astype(np.int64), np.full(len(m), c, np.int32)))
-    mc, ms, me, co = (np.concatenate([r[j] for r in rows]) for j in range(4))
+        rows.append(dict(chrom=m.CHROM.astype(str).values, start=m.START.values, end=m.END.values))
+    mc, ms, me = cohort_rows.column(rows, "chrom"), cohort_rows.column(rows, "start", "i64"), cohort_rows.column(rows, "end", "i64")
+    co = cohort_rows.cohort_column(rows, "start")
     s_prob = np.stack([_s_prob_table(d, n_up, collapse) for d in d_prs])
     res = engine.tiled_nb_model(g, chroms, starts, ends, s_prob, mu, sigma, mc, ms, me, co, binsize=binsize, device=device)
     nval_dev = res["n_valid"]

@@ -184,7 +184,8 @@ def train_sequence_models(f_muts, idx, mappability, genome_counts_frame, map_thr
     unless the process is torch-free.
     Returns (models, counts, serial): models[c] = (df_freq_mut, df_freq_context) of train_sequence_model for f_muts[c], counts i64
     [C, K] in the model's row order, serial = the indices of the cohorts counted on the host."""
-    from .. import _lib, engine
+    from .. import engine
+    from ..data_tools import cohort_rows
     f_muts = [f_muts] if isinstance(f_muts, (str, bytes)) or hasattr(f_muts, "__fspath__") else list(f_muts)
     if not f_muts:
         raise ValueError("no mutation file")
@@ -201,16 +202,11 @@ def train_sequence_models(f_muts, idx, mappability, genome_counts_frame, map_thr
     cohorts = [encode_sequence_rows(f, chrom_ids, n_up, n_down) for f in f_muts]
     serial = [c for c in range(C) if not cohorts[c]["one_base"]]
     batch = [c for c in range(C) if cohorts[c]["one_base"]]
-    cat = lambda k, dt: np.concatenate([np.asarray(cohorts[c][k], dt) for c in batch] + [np.zeros(0, dt)])
-    rows = [cat("chrom", np.int64), cat("start", np.int64), cat("end", np.int64), cat("type", np.int32),
-            np.repeat(np.array(batch, np.int32), [len(cohorts[c]["type"]) for c in batch])]
-    dev = (not _lib.TORCH_FREE) if on_device is None else bool(on_device)
-    if dev:
-        import torch
-        from .._marshal import resolve_device
-        rows = [torch.as_tensor(r, device=resolve_device(device)) for r in rows]
+    cat = lambda k, dt: cohort_rows.column(cohorts, k, dt, subset=batch)
+    rows = cohort_rows.place([cat("chrom", "i64"), cat("start", "i64"), cat("end", "i64"), cat("type", "i32"),
+                              cohort_rows.cohort_column(cohorts, "type", batch)], on_device, device)
     counts = engine.sequence_counts(white[:, 0], white[:, 1], white[:, 2], *rows, K, C, device=device)
-    counts = np.array(counts.cpu().numpy() if dev else counts, np.int64)
+    counts = np.array(counts.cpu().numpy() if engine.is_cuda(counts) else counts, np.int64)
     df_bed = pd.DataFrame(white, columns=['CHROM', 'START', 'END'])
     for c in serial:
         df_mut = cohorts[c]["frame"]

@@ -114,8 +114,12 @@ class GuardedArena:
         assert variant in ("A", "B")
         self.torch, self.bufs, self.variant = torch, dict(bufs), variant
         total = BAND + sum(2 * BAND + b.nbytes + 2 * 2 * b.align + 16 for b in self.bufs.values()) + BAND
-        self.slab = torch.empty(total, dtype=torch.uint8, device=device)
+        # the slab starts at a multiple of 8192 (2 a of the largest alignment a buffer may ask for): where a buffer lands in its slab
+        # then follows from the buffers alone, not from the address the allocator gave, so two arenas over the same buffers agree
+        raw = torch.empty(total + 8192, dtype=torch.uint8, device=device)
+        self.slab = raw[-raw.data_ptr() % 8192:][:total]
         self.base = self.slab.data_ptr()
+        assert self.base % 8192 == 0
         # placement: front band, buffer at a (mod 2a), rear band from the buffer's last byte + 1
         self.off, self.bands = {}, []               # name -> byte offset; bands: (start, end, name, side)
         cur = 0

@@ -64,6 +64,7 @@ def main():
     args = ap.parse_args()
     import torch
     from digdriver_amd import engine
+    from digdriver_amd.data_tools import cohort_rows
     from digdriver_amd.sequence_model import sequence_tools as st
     table = st.mk_mutation_context(args.up, args.up, return_df=True)
     K, C = len(table), args.cohorts
@@ -72,8 +73,7 @@ def main():
     white = idx[rng.uniform(size=len(idx)) >= 0.05]                   # (5 % of the windows below the mappability threshold)
     S_genome = {c: 1000.0 + i for i, c in enumerate(st.mk_context_sequences(args.up, args.up))}
     cohorts = [make_cohort(np.random.default_rng([args.seed, c]), args.mut_rows, idx, K) for c in range(C)]
-    rows = [np.concatenate([c[k] for c in cohorts]) for k in ("chrom", "start", "end", "type")] + \
-        [np.repeat(np.arange(C, dtype=np.int32), [len(c["type"]) for c in cohorts])]
+    rows = [cohort_rows.column(cohorts, k) for k in ("chrom", "start", "end", "type")] + [cohort_rows.cohort_column(cohorts, "type")]
 
     # the host work in front of both routes, for one cohort: a file written and parsed
     with tempfile.TemporaryDirectory() as tmp:

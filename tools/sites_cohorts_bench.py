@@ -83,22 +83,20 @@ def stage_times(f_sites, f_muts):
     """The batched route's counting, stage by stage, on the same files: seconds on the host, milliseconds on the device."""
     import torch
     from digdriver_amd import _lib
-    from digdriver_amd.data_tools import sites
+    from digdriver_amd.data_tools import cohort_rows, sites
     out = {}
     t0 = time.perf_counter()
     table = sites.encode_sites_file(f_sites)
     rows = [sites.encode_site_rows(f, table["dicts"], c) for c, f in enumerate(f_muts)]
     out["parse_encode_s"] = round(time.perf_counter() - t0, 3)
     C, E, S = len(f_muts), len(table["elt_names"]), len(table["site_pos"])
-    off = np.concatenate([[0], np.cumsum([len(r["sample_names"]) for r in rows])]).astype(np.int64)
-    host = [table[k] for k in ("site_pos", "site_end", "site_attr", "site_elt")] + \
-        [np.concatenate([r[k] for r in rows]) for k in ("pos", "end", "attr")] + \
-        [np.concatenate([r["sample"] + np.int32(off[c]) for c, r in enumerate(rows)]).astype(np.int32),
-         np.concatenate([r["cohort"] for r in rows]), off]
+    off = cohort_rows.sample_offsets(rows)
+    host = [table[k] for k in ("site_pos", "site_end", "site_attr", "site_elt")] + [cohort_rows.column(rows, k) for k in ("pos", "end", "attr")] + \
+        [cohort_rows.column(rows, "sample", "i32", off), cohort_rows.column(rows, "cohort"), off]
     n = len(host[4])
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    dev = [torch.as_tensor(np.ascontiguousarray(a), device="cuda") for a in host]
+    dev = cohort_rows.place(host, True, "cuda")
     torch.cuda.synchronize()
     out["upload_s"] = round(time.perf_counter() - t0, 4)
     d, stream = _lib.dev_ptr, _lib.stream_ptr()
