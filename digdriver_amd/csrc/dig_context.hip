@@ -458,7 +458,7 @@ int dig_count_contexts(const uint32_t* genome_words, int64_t n_words, const int6
     DIG_REQUIRE(genome_words && chrom_off && chrom_len && reg_chrom && reg_start && reg_end && reg_minus && out,
                 "non-null pointers");
     DIG_REQUIRE(((uintptr_t)genome_words & 15) == 0, "genome_words 16-byte aligned");
-    const int grid = grid_for(R * 64, kCtxBlock, DIG_CTX_PER_CU);
+    const int grid = grid_for(R * 64, kCtxBlock, DIG_CTX_PER_CU);        // (past the cap: test_context_counts_past_one_pass_of_the_grid, tests/test_gpu_grid_wrap.py)
     hipLaunchKernelGGL(context_count_kernel, dim3(grid), dim3(kCtxBlock), 0, (hipStream_t)stream, genome_words, n_words,
                        chrom_off, chrom_len, reg_chrom, reg_start, reg_end, reg_minus, R, out);
     DIG_HIP_TRY(hipGetLastError());
@@ -476,6 +476,7 @@ int dig_count_contexts2(const uint32_t* words2, int64_t n_words2, const int64_t*
     DIG_REQUIRE(words2 && chrom_off && chrom_len && reg_chrom && reg_start && reg_end && reg_minus && out, "non-null pointers");
     DIG_REQUIRE(((uintptr_t)words2 & 15) == 0, "words2 16-byte aligned");
     const int grid = grid_for(R, kC2Block, 1);          // one lane per region, one workgroup (128 KB of LDS) per CU
+                                                        // (past the cap: test_context_counts_past_one_pass_of_the_grid, tests/test_gpu_grid_wrap.py)
     hipLaunchKernelGGL(context_count2_kernel, dim3(grid), dim3(kC2Block), 0, (hipStream_t)stream, G, reg_chrom, reg_start,
                        reg_end, reg_minus, R, out);
     DIG_HIP_TRY(hipGetLastError());

@@ -350,29 +350,29 @@ static int launch_gather(const void* x, int64_t n_total, int64_t L, int64_t T, c
     if (!transpose_out && !tracks && ((L * T) & 3) == 0 && ((uintptr_t)x & 31) == 0 && ((uintptr_t)out & 15) == 0) {
         const int64_t nv = (L * T) >> 2;
         const int chunks = (int)std::min<int64_t>((nv + kGatherBlock * kBlockUnroll - 1) / (kGatherBlock * kBlockUnroll), 64);
-        const int gy = (int)std::min<int64_t>(B, 65535);
+        const int gy = (int)std::min<int64_t>(B, 65535);                // (past 64 chunks and 65 535 bins: test_gather_block_kernel_past_its_grid_in_y_and_in_x, tests/test_gpu_grid_wrap.py)
         hipLaunchKernelGGL((gather_block_kernel<S, D>), dim3(chunks, gy), dim3(kGatherBlock), 0, stream, (const S*)x, L * T,
                            rows, B, (D*)out);
     } else if (!transpose_out && tracks && T <= kWideMaxT && (T_sel & 3) == 0 && T_sel > 0 && T_sel <= 256 * kSubsetMaxVec &&
                ((uintptr_t)out & 15) == 0 && ((uintptr_t)tracks & 15) == 0 && ((uintptr_t)x & 7) == 0 &&
                (L * T * (int64_t)sizeof(S)) % 8 == 0 && L % (8 / (int64_t)sizeof(S)) == 0 && (T_sel * (int64_t)sizeof(D)) % 16 == 0) {
         const int64_t n_groups = B * (L / (8 / (int64_t)sizeof(S)));
-        int grid = (int)std::max<int64_t>(1, std::min<int64_t>((n_groups + 3) / 4, (int64_t)cu_count() * 4));
+        int grid = (int)std::max<int64_t>(1, std::min<int64_t>((n_groups + 3) / 4, (int64_t)cu_count() * 4));      // (past the cap: test_gather_bins_past_one_pass_of_every_capped_grid, tests/test_gpu_grid_wrap.py)
         hipLaunchKernelGGL((gather_rows_subset_wide_kernel<S, D>), dim3(grid), dim3(kGatherBlock), 0, stream, (const S*)x, L, T, rows,
                            B, tracks, T_sel, (D*)out);
     } else if (!transpose_out && tracks && T <= kSubsetMaxT && (T_sel & 3) == 0 && T_sel > 0 && T_sel <= 256 * kSubsetMaxVec &&
                ((uintptr_t)out & 15) == 0 && ((uintptr_t)tracks & 15) == 0) {
-        int grid = (int)std::min<int64_t>(B, (int64_t)cu_count() * 8);
+        int grid = (int)std::min<int64_t>(B, (int64_t)cu_count() * 8);  // (past the cap: test_gather_bins_past_one_pass_of_every_capped_grid, tests/test_gpu_grid_wrap.py)
         hipLaunchKernelGGL((gather_rows_subset_kernel<S, D>), dim3(grid), dim3(kGatherBlock), 0, stream, (const S*)x, L, T, rows,
                            B, tracks, T_sel, (D*)out);
     } else if (!transpose_out) {
-        int grid = (int)std::min<int64_t>(B, (int64_t)cu_count() * 8);
+        int grid = (int)std::min<int64_t>(B, (int64_t)cu_count() * 8);  // (past the cap: test_gather_bins_past_one_pass_of_every_capped_grid, tests/test_gpu_grid_wrap.py)
         hipLaunchKernelGGL((gather_rows_kernel<S, D>), dim3(grid), dim3(kGatherBlock), 0, stream, (const S*)x, L, T, rows,
                            B, tracks, T_sel, (D*)out);
     } else if (!tracks && (L & 3) == 0 && L <= 252 && ((uintptr_t)out & 15) == 0 && ((uintptr_t)x & (4 * sizeof(S) - 1)) == 0) {
         const size_t lds = (size_t)64 * (L + 1) * sizeof(float);
         const int tiles = (int)((T + 63) / 64);
-        const int gy = (int)std::min<int64_t>(B, std::max<int64_t>(1, (int64_t)cu_count() * 16 / tiles));
+        const int gy = (int)std::min<int64_t>(B, std::max<int64_t>(1, (int64_t)cu_count() * 16 / tiles));        // (past the cap: test_gather_bins_past_one_pass_of_every_capped_grid, tests/test_gpu_grid_wrap.py)
         DIG_HIP_TRY(hipFuncSetAttribute((const void*)gather_transpose_all_kernel<S, D>,
                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         hipLaunchKernelGGL((gather_transpose_all_kernel<S, D>), dim3(tiles, gy), dim3(kGatherBlock), lds, stream,
@@ -381,7 +381,7 @@ static int launch_gather(const void* x, int64_t n_total, int64_t L, int64_t T, c
         const size_t lds = (size_t)L * 65 * sizeof(float);
         if (lds > 150 * 1024) return set_error(DIG_EINVAL, "gather: L=%lld too long for the LDS transpose tile", (long long)L);
         const int tiles = (int)((T_sel + 63) / 64);
-        int gy = (int)std::min<int64_t>(B, std::max<int64_t>(1, (int64_t)cu_count() * 8 / tiles));
+        int gy = (int)std::min<int64_t>(B, std::max<int64_t>(1, (int64_t)cu_count() * 8 / tiles));               // (past the cap: test_gather_bins_past_one_pass_of_every_capped_grid, tests/test_gpu_grid_wrap.py)
         DIG_HIP_TRY(hipFuncSetAttribute((const void*)gather_transpose_kernel<S, D>,
                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         hipLaunchKernelGGL((gather_transpose_kernel<S, D>), dim3(tiles, gy), dim3(kGatherBlock), lds, stream,

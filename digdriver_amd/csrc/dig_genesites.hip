@@ -142,7 +142,8 @@ int dig_gene_site_counts(const uint32_t* words2, int64_t n_words2, const int64_t
     DIG_REQUIRE(words2 && chrom_off && chrom_len, "non-null genome arrays");
     DIG_REQUIRE(gene_chrom && gene_minus && blk_ptr && spl_ptr, "non-null gene_chrom, gene_minus, blk_ptr, spl_ptr");
     DIG_REQUIRE(L && n_stop_loss && status, "non-null outputs");
-    const int64_t cap = (int64_t)cu_count() * 64;                    // (a workgroup takes the genes blockIdx, blockIdx + grid, ...)
+    const int64_t cap = (int64_t)cu_count() * 64;                    // (a workgroup takes the genes blockIdx, blockIdx + grid, ...;
+                                                                     //  past the cap: test_gene_site_counts_past_one_pass_of_the_grid, tests/test_gpu_grid_wrap.py)
     hipLaunchKernelGGL(gene_site_counts_kernel, dim3((unsigned)(n_genes < cap ? n_genes : cap)), dim3(kGsBlock), 0, (hipStream_t)stream,
                        G, gene_chrom, gene_minus, blk_ptr, blk_start, blk_end, cds_off, spl_ptr, spl_pos, n_genes, L, n_stop_loss,
                        status);

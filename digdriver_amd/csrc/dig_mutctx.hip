@@ -109,6 +109,7 @@ __global__ __launch_bounds__(kMcBlock) void mutctx_resolve_kernel(const int32_t*
     if (!(heads & 1ull)) {                                           // the wave's first row continues a run of earlier waves
         int32_t cH = -1, cB = -1;
         for (int64_t w0 = w - 1; w0 >= 0; w0 -= 64) {                // row 0 heads a run: the walk ends at wave 0 at the latest
+                                                                     // (more than one step: test_mutation_context_runs_that_span_many_waves, tests/test_gpu_grid_wrap.py)
             const int64_t ww = w0 - lane;
             const int32_t ah = ww >= 0 ? wave_last[2 * ww] : -1, ab = ww >= 0 ? wave_last[2 * ww + 1] : -1;
             const uint64_t m = __ballot(ah >= 0);

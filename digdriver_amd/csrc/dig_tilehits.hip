@@ -184,7 +184,7 @@ int dig_tile_select_count(const double* score, const int32_t* n_valid, const dou
     if (n == 0) return DIG_OK;
     DIG_REQUIRE(score && n_valid && cut, "non-null score, n_valid, cut");
     const int lead = (int)(((uintptr_t)score >> 3) & 1);                        // a plane at 8 (mod 16): its first element stands alone
-    const int grid = grid_for((n - lead) >> 1, kTileHitBlock);
+    const int grid = grid_for((n - lead) >> 1, kTileHitBlock);                  // (past the cap: test_tile_select_past_one_trip_of_the_grid, tests/test_gpu_grid_wrap.py)
     const int64_t block = 2 * (int64_t)grid * kTileHitBlock;                    // elements of one block of pairs; a trip is two
     TileSelectArgs a{};
     a.score = score, a.n_valid = n_valid, a.cut = cut, a.C = C, a.R = R, a.T = T, a.counts = counts;

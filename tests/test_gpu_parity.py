@@ -455,7 +455,8 @@ def test_gather_bins(torch_dev, src):
     xo = np.ascontiguousarray(x[:, :99, :])
     assert np.array_equal(engine.gather_bins(torch.as_tensor(xo, device=torch_dev), rows, None).cpu().numpy(),
                           xo[rows].astype(np.float32))
-    big = rng.integers(0, N, 700)                      # more bins than one grid pass of the block kernel needs
+    big = rng.integers(0, N, 700)                      # many bins; still inside one pass of the block kernel's grid (65 535 bins
+                                                       # in y): test_gpu_grid_wrap.py goes past it
     assert np.array_equal(engine.gather_bins(xd, big, None).cpu().numpy(), x[big].astype(np.float32))
 
 
@@ -681,8 +682,9 @@ def test_context_counting_2bit_form_on_letter_runs_and_every_alignment():
     """dig_count_contexts2 (2 bits per base + the list of non-ACGT runs; 4-mers at even bases, counters that are never
     cleared, take-backs at the group ends, single centres, interval corrections) against the oracle: genomes from N-free to
     90 % N, runs that start / end at every offset of a region and of a 64-base group, adjacent runs one base apart, regions
-    of 0 ... 3 000 centres at every alignment, chromosome starts and ends, both strands; many more regions than waves, so
-    that every wave's running totals carry over many regions."""
+    of 0 ... 3 000 centres at every alignment, chromosome starts and ends, both strands.  A lane takes one region and the
+    grid holds a lane per region here: every lane's running totals start from zero.  Their carry from region to region, over
+    more than two passes of the grid, is in test_gpu_grid_wrap.py."""
     import torch
     from digdriver_amd import engine
     from digdriver_amd.data_tools.genome import PackedGenome
