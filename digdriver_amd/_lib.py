@@ -117,6 +117,8 @@ _SIGNATURES = {
                                   [_vp] * 5 + [_int],
     "dig_gene_site_counts": [_vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _int] + [_vp] * 8 + [_i64] + [_vp] * 4,
     "dig_gene_site_counts_host": [_vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _int] + [_vp] * 8 + [_i64] + [_vp] * 3 + [_int],
+    "dig_element_context_counts": [_vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _int] + [_vp] * 5 + [_i64, _i64, _vp, _vp, _i64, _vp],
+    "dig_element_context_counts_host": [_vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _int] + [_vp] * 5 + [_i64, _i64, _vp, _int],
     "dig_mutctx_file_parse_host": [ctypes.c_char_p, _vp, _vp, _vp],
     "dig_mutctx_file_fetch_host": [_vp, _vp, _vp, _vp],
     "dig_mutctx_file_write_host": [_vp, ctypes.c_char_p, _vp, _vp, _vp, _vp, _int, _int],
@@ -166,6 +168,7 @@ _SIZE_QUERIES = {
     "dig_bh_workspace": [_i64, _i64],
     "dig_bh_ragged_workspace": [_vp, _i64],
     "dig_mutation_contexts_workspace": [_i64],
+    "dig_element_context_counts_workspace": [_i64],
 }
 
 ABI_VERSION = 12         # include/dig_hip.h: DIG_ABI_VERSION

@@ -669,6 +669,36 @@ int dig_gene_site_counts_host(const uint32_t* words2, int64_t n_words2, const in
                         st.in(spl_pos, n_spl), n_genes, st.out(L, ng * 4 * 192), st.out(n_stop_loss, ng), st.out(status, ng), nullptr);
 }
 
+int dig_element_context_counts_host(const uint32_t* words2, int64_t n_words2, const int64_t* nint_start, const int64_t* nint_end,
+                                    int64_t n_int, const int32_t* nint_bucket, int64_t n_buckets, const int64_t* chrom_off,
+                                    const int64_t* chrom_len, int n_chrom, const int32_t* elt_chrom, const uint8_t* elt_minus,
+                                    const int64_t* blk_ptr, const int64_t* blk_start, const int64_t* blk_end, int64_t E, int64_t n_blocks,
+                                    int32_t* out, int device)
+{
+    DIG_REQUIRE(E >= 0 && n_blocks >= 0, "E, n_blocks >= 0");
+    DIG_REQUIRE(E < ((int64_t)1 << 31) && n_blocks < ((int64_t)1 << 31), "E, n_blocks < 2^31");
+    const Genome2 H = {words2, n_words2, nint_start, nint_end, n_int, nint_bucket, n_buckets, chrom_off, chrom_len, n_chrom};
+    if (int rc = genome2_check(__func__, H, E)) return rc;
+    if (E == 0) return DIG_OK;
+    DIG_REQUIRE(words2 && chrom_off && chrom_len, "non-null genome arrays");
+    DIG_REQUIRE(elt_chrom && elt_minus && blk_ptr && out, "non-null elt_chrom, elt_minus, blk_ptr, out");
+    DIG_REQUIRE(((uintptr_t)out & 3) == 0, "out 4-byte aligned");
+    DIG_REQUIRE(n_blocks == 0 || (blk_start && blk_end), "non-null blk_start, blk_end");
+    DIG_REQUIRE(blk_ptr[0] == 0 && blk_ptr[E] == n_blocks, "blk_ptr from 0 to n_blocks");
+    for (int64_t e = 0; e < E; ++e) {
+        DIG_REQUIRE(blk_ptr[e] <= blk_ptr[e + 1], "blk_ptr non-decreasing");
+        DIG_REQUIRE(elt_chrom[e] >= 0 && elt_chrom[e] < n_chrom, "element chromosome index within [0, n_chrom)");
+    }
+    for (int64_t b = 0; b < n_blocks; ++b) DIG_REQUIRE(blk_start[b] >= 0 && blk_end[b] >= 0, "non-negative coordinates");
+    if (int rc = genome2_check_host(__func__, H)) return rc;
+    const int64_t ws = dig_element_context_counts_workspace(n_blocks);
+    const size_t ne = (size_t)E;
+    Staging st(device);
+    return call_genome2(st, dig_element_context_counts, H, st.in(elt_chrom, ne), st.in(elt_minus, ne), st.in(blk_ptr, ne + 1),
+                        st.in(blk_start, n_blocks), st.in(blk_end, n_blocks), E, n_blocks, st.out(out, ne * 64), st.scratch(ws), ws,
+                        nullptr);
+}
+
 int dig_element_pipeline_host(const double* bin_mu, const double* bin_std, const int32_t* bin_y, const uint8_t* bin_flag,
                               const int32_t* bin_ctx, const int64_t* ov_ptr, const int32_t* ov_idx, const int32_t* L,
                               const uint8_t* strand_minus, const int32_t* gene_length, const double* d_pr,

@@ -20,13 +20,17 @@ dig_gene_counts), then ONE dig_gene_stats launch and, when asked for, ONE dig_ge
 elementDriver --f-sites (transfer_tools.run_sites_region_model, transfer_tools.py:1098-1169) likewise -- run_sites_cohorts: the sites
 file encoded once, the rows of C cohorts matched exactly and counted by engine.site_counts (dig_site_match_count / keys + a key sort
 + dig_site_counts), then the statistics element-wise over [E, C] (tests/test_gpu_sites_cohorts.py).
+
+quickDriver (onthefly_tools.DIG_onthefly: ad-hoc elements, no pretrained element model) likewise -- run_quick_cohorts: the elements'
+context counts are one engine.element_context_counts launch over the bed12 (dig_element_context_counts), the grid's window contexts
+one engine.count_contexts launch, and the rest is run_element_cohorts without its element container (tests/test_gpu_quick_cohorts.py).
 """
 import numpy as np
 import pandas as pd
 
 from .. import engine
 from .._marshal import resolve_device
-from ..data_tools import cohort_rows, tabulate_gpu
+from ..data_tools import cohort_rows, mutation_tools, tabulate_gpu
 from ..io import mapfile
 from ..sequence_model import genic_driver_tools, nb_model
 from . import transfer_tools
@@ -633,3 +637,208 @@ def run_and_write_sites_cohorts(f_muts, f_sites, f_pretrained, pretrain_key, out
     the cohorts after it are assembled (_run_and_write)."""
     return _run_and_write(lambda on_frame: run_sites_cohorts(f_muts, f_sites, f_pretrained, pretrain_key, on_frame=on_frame, **kw),
                           len(f_muts), outdir, prefixes, write_threads, lambda path, threads, frame: lambda: _write_one(frame, path, threads))
+
+
+# ---------------------------------------------------------------------------------------------
+# quickDriver for many cohorts
+# ---------------------------------------------------------------------------------------------
+_QUICK_SCALE_TYPES = (None, 'genome')
+
+
+def _quick_elements(f_elts_bed):
+    """The elements of a bed12 as the single route reads them (mutation_tools.bed12_boundaries: autosomes only, bed order):
+    (names, chrom i32, minus u8, blk_ptr, blk_start, blk_end i64) and the number of rows the bed file lists."""
+    df = mutation_tools.bed12_boundaries(f_elts_bed)
+    names = df.ELT.values
+    if len(set(names.tolist())) != len(names):
+        raise ValueError("{}: an element name occurs more than once (run_quick_cohorts needs one row per element)".format(f_elts_bed))
+    blk_ptr = np.concatenate([[0], np.cumsum([len(b) for b in df.BLOCK_STARTS])]).astype(np.int64)
+    blk_start = np.array([s for b in df.BLOCK_STARTS for s in b], np.int64)
+    blk_end = np.array([e for b in df.BLOCK_ENDS for e in b], np.int64)
+    minus = np.array([(s == '-1' or s == '-') for s in df.STRAND.astype(str)], np.uint8)     # onthefly_tools.py:126
+    n_listed = len(pd.read_csv(f_elts_bed, sep="\t", header=None, usecols=[3]))
+    return names, df.CHROM.values.astype(np.int32), minus, blk_ptr, blk_start, blk_end, n_listed
+
+
+def opposite_strand_pair(names, chrom, minus, blk_ptr, blk_start, blk_end):
+    """The first block (chrom, start, end) that elements of OPPOSITE strands share, as (element, other element, chrom, start, end),
+    or None.  The single route counts such a block once, on the strand of its first occurrence, for both elements (the reference
+    de-duplicates its frame of block counts by 'chr{}:{}-{}': sequence_tools.py:481-525); the element kernel counts every block on
+    its own element's strand."""
+    owner = np.repeat(np.arange(len(names)), np.diff(blk_ptr))
+    if not len(owner):
+        return None
+    rows = np.stack([chrom[owner].astype(np.int64), blk_start, blk_end, minus[owner].astype(np.int64)], axis=1)
+    uniq, first = np.unique(rows, axis=0, return_index=True)               # (sorted: the two strands of a block are neighbours)
+    same = (uniq[1:, :3] == uniq[:-1, :3]).all(axis=1)
+    if not same.any():
+        return None
+    hits = np.flatnonzero(same)
+    k = hits[np.argmin(np.minimum(first[hits], first[hits + 1]))]          # the pair that appears first in the bed file
+    a, b = sorted((int(first[k]), int(first[k + 1])))
+    return names[owner[a]], names[owner[b]], int(uniq[k, 0]), int(uniq[k, 1]), int(uniq[k, 2])
+
+
+def _quick_obs_sample_kinds(index, o_smp, n_listed):
+    """The dtype of OBS_SAMPLES in tabulate_mutations_in_element(all_elements=True) (mutation_tools.py:155-189): the integer
+    counts are left-joined onto the bed's rows, so they stay integers only when every listed row has a count."""
+    return np.int64 if len(index) and n_listed == len(index) and (o_smp > 0).all() else np.float64
+
+
+def run_quick_cohorts(f_muts, f_pretrained, f_fasta, f_elts_bed=None, region_str=None, scale_factors=None, scale_type=None,
+                      scale_by_expectation=True, max_muts_per_sample=3e9, max_muts_per_elt_per_sample=3e9, skip_pvals=False,
+                      all_cosmic=None, strict_reference=True, device=0, on_frame=None):
+    """quickDriver for C cohorts in one pass: one frame per cohort with the columns, the column order, the dtypes, the row order
+    and the index of onthefly_tools.DIG_onthefly(f_pretrained[c], f_muts[c], f_fasta, ...) with the same options -- burden tests
+    for ad-hoc elements (a bed12 file, or a region string: the one-block '+' element UserELT) without a pretrained element model.
+    The maps must share one bin grid.  What the single route takes from the FASTA one block row at a time -- L, through a frame
+    keyed by strings and np.add.at -- is ONE engine.element_context_counts launch over the bed12 ([E, 64], expanded to the 192
+    sorted substitution columns by a gather on the device); the window contexts of the grid are one engine.count_contexts launch
+    over all N windows; then the bin overlaps, the join and tabulation and one engine.PipelinePlan run (the general form of the
+    accumulation, as the single route runs it) as in run_element_cohorts.
+    Scale factors, by the single route's own rules: scale_by_expectation (default; CohortRun.synonymous_scale and
+    uniform_indel_scale over a cohort's coding rows without the samples the tabulation blacklisted: host work per cohort), else
+    scale_factors = (cj [C], cj_indel [C]) as given, else scale_type 'genome' (genome_scale_factors); the other scale types need a
+    map's bookkeeping and are not batched: NotImplementedError before any device work.
+    strict_reference=True keeps the reference's double application of cj_indel to THETA_INDEL (DIG_onthefly) -- and refuses a bed
+    file in which a block occurs in elements of opposite strands (ValueError naming the first pair: opposite_strand_pair);
+    False counts such blocks per strand and applies cj_indel once.
+    Only the bed's autosome rows are elements (bed12_boundaries); with other rows in the file OBS_SAMPLES is a float column.
+    on_frame(c, frame): called as soon as cohort c's frame exists."""
+    f_muts, f_pretrained = list(f_muts), list(f_pretrained)
+    C = len(f_muts)
+    if C == 0 or len(f_pretrained) != C:
+        raise ValueError("run_quick_cohorts: {} mutation files for {} maps (one map per cohort, at least one cohort)".format(C, len(f_pretrained)))
+    if not (f_elts_bed or region_str):
+        raise ValueError("run_quick_cohorts: you must provide f_elts_bed or region_str")
+    given = None
+    if not scale_by_expectation:
+        if scale_factors is not None:
+            if len(scale_factors) != 2:
+                raise ValueError("run_quick_cohorts: scale_factors is the pair (cj [C], cj_indel [C])")
+            given = [np.asarray(x, float).reshape(-1) for x in scale_factors]
+            if not all(len(x) == C for x in given):
+                raise ValueError("run_quick_cohorts: scale_factors must hold one value per cohort ({})".format(C))
+        elif scale_type not in _QUICK_SCALE_TYPES:
+            raise NotImplementedError("run_quick_cohorts scales by the expected number of mutations (scale_by_expectation), by given "
+                                      "scale_factors or by the genome rule; the {} rule is DIG_onthefly's".format(scale_type))
+    temp_name = None
+    if region_str and not f_elts_bed:                      # onthefly_tools.py:33-38
+        import os
+        import tempfile
+        from .onthefly_tools import region_str_to_params
+        ch, lo, hi = region_str_to_params(region_str)
+        handle, temp_name = tempfile.mkstemp()
+        with os.fdopen(handle, "w") as bed:
+            bed.write("\t".join(str(x) for x in (ch, lo, hi, "UserELT", 0, "+", 0, 0, ".", 1, "%d," % (hi - lo), "0,")))
+        f_elts_bed = temp_name
+    try:
+        names, chrom, minus, blk_ptr, blk_start, blk_end, n_listed = _quick_elements(f_elts_bed)
+    finally:
+        if temp_name:
+            import os
+            os.remove(temp_name)
+    if strict_reference:
+        pair = opposite_strand_pair(names, chrom, minus, blk_ptr, blk_start, blk_end)
+        if pair is not None:
+            raise ValueError("elements {} and {} lie on opposite strands and share the block chr{}:{}-{}: the reference counts such a "
+                             "block once, on the strand of its first occurrence, for both elements; pass strict_reference=False to "
+                             "count it on each element's own strand".format(*pair))
+    return _quick_cohorts(f_muts, f_pretrained, f_fasta, (names, chrom, minus, blk_ptr, blk_start, blk_end, n_listed), given,
+                          scale_by_expectation, max_muts_per_sample, max_muts_per_elt_per_sample, skip_pvals, all_cosmic,
+                          strict_reference, device, on_frame)
+
+
+def _quick_cohorts(f_muts, f_pretrained, f_fasta, elements, given, scale_by_expectation, max_muts_per_sample,
+                   max_muts_per_elt_per_sample, skip_pvals, all_cosmic, strict_reference, device, on_frame):
+    """The device work of run_quick_cohorts and the frames (its arguments checked)."""
+    import torch
+    from ..sequence_model import sequence_tools
+    names, chrom, minus, blk_ptr, blk_start, blk_end, n_listed = elements
+    dev = resolve_device(device)
+    C, E = len(f_muts), len(names)
+    files, tables, d_pr = genic_driver_tools._load_cohorts(f_pretrained, workers=None if C >= 8 else 1)
+    w = tables.window
+    cohorts = _encode_all_mutations(f_muts, None if C >= 8 else 1, device=dev)
+    genome = sequence_tools.load_genome(f_fasta)
+    t = lambda a: torch.as_tensor(np.ascontiguousarray(a), device=dev)
+    # L: the elements' strand-aware context counts from the 2-bit genome, every sorted substitution column its context's count
+    # (sequence_tools._context_columns: the rule of nonc_elt_context_count)
+    print('Counting element contexts')
+    L64 = engine.element_context_counts(genome, ['chr' + str(c) for c in chrom], minus, blk_ptr, blk_start, blk_end, device=dev,
+                                        on_device=True)
+    _, cols = sequence_tools._context_columns(sequence_tools.mk_trans_idx(n_up=1, n_down=1, collapse=False))
+    L = L64[:, t(cols)].contiguous()
+    # the window contexts of the whole grid (onthefly_tools.py:118-120 counts the touched windows; DESIGN.md section 8.3: all of them
+    # cost under a millisecond)
+    ctx = engine.count_contexts(genome, ['chr' + str(c) for c in tables.chrom], tables.start, tables.start + w, device=dev)
+    ov_ptr, ov_idx = engine.ideal_overlaps(chrom, blk_ptr, blk_start, blk_end, w, tables.chrom, tables.start)
+    print('Tabulating mutations')
+    owner = np.repeat(np.arange(E), np.diff(blk_ptr))
+    blocks = tabulate_gpu.ElementBlocks(chrom[owner], blk_start, blk_end, owner, E, dev)
+    obs_snv, obs_smp, obs_ind, blacklists = tabulate_gpu.tabulate_cohorts(blocks, cohorts, drop_duplicates=True,
+                                                                          max_muts_per_sample=max_muts_per_sample,
+                                                                          max_muts_per_elt_per_sample=max_muts_per_elt_per_sample)
+    dev_tables = tables.on_device(dev)
+    if scale_by_expectation:                               # onthefly_tools.py:44-63, a cohort at a time on the host
+        print('scaling by expected number of mutations')
+        cj_h, cji_h = np.empty(C), np.empty(C)
+        null = transfer_tools.cosmic_null_set(all_cosmic)
+        for c in range(C):
+            run = transfer_tools.CohortRun(f_muts[c], files[c])
+            coding = run.coding_rows()
+            coding = coding.loc[~coding.SAMPLE.astype(str).isin(set(str(s) for s in blacklists[c]))]
+            cj_h[c] = run.synonymous_scale(run.gene_model(), coding, dedup=True)
+            cji_h[c] = run.uniform_indel_scale(run.gene_model(), coding, null)
+    elif given is not None:
+        cj_h, cji_h = given
+    else:
+        print('Calculating scale factor')
+        cj_d, cji_d = genome_scale_factors(tables, cohorts, dev, dev_tables)
+        cj_h, cji_h = cj_d.cpu().numpy(), cji_d.cpu().numpy()
+    # THETA_INDEL: the reference scales it by cj_indel where the frame is made and again in element_pvalue_indel
+    # (onthefly_tools.py:151,181); once without strict_reference
+    cji_eff = cji_h * cji_h if strict_reference else cji_h
+    print('Calculating statistics')
+    plan = engine.PipelinePlan(*dev_tables, ctx, t(ov_ptr), t(ov_idx), L, t(minus), t(d_pr), obs_snv, obs_smp, obs_ind, compact=False,
+                               pack_bins=True, records_out=True)
+    acc, _ = plan.run(t(np.asarray(cj_h, float)), t(np.asarray(cji_eff, float)))
+    st_cm = torch.empty((len(engine.ES_PLANES), plan.C, plan.E), dtype=torch.float64, device=dev)
+    rates = {"MU": torch.empty((plan.C, plan.E), dtype=torch.float64, device=dev),
+             "SIGMA": torch.empty((plan.C, plan.E), dtype=torch.float64, device=dev),
+             "R_OBS": torch.empty((plan.C, plan.E), dtype=torch.int32, device=dev),
+             "FLAG": torch.empty((plan.C, plan.E), dtype=torch.int32, device=dev)}
+    plan.unpack(cohort_major=True, stats=st_cm, rates=rates)
+    alpha, theta = nb_model.normal_params_to_gamma(rates["MU"], rates["SIGMA"])
+    host = lambda x: x.cpu().numpy()
+    by_cohort = lambda x: host(x.transpose(-1, -2).contiguous())
+    A = {k: host(v) for k, v in acc.items() if k not in ('P', 'MU', 'SIGMA', 'R_OBS', 'FLAG')}
+    A.update({k: host(v) for k, v in rates.items()})
+    S, al, th = host(st_cm), host(alpha), host(theta)
+    P0 = host(acc['P'][:, 0, :].transpose(0, 1).contiguous())
+    o_snv, o_smp, o_ind = by_cohort(obs_snv), by_cohort(obs_smp), by_cohort(obs_ind)
+    frames = []
+    index = pd.Index(np.asarray(names, dtype=object), name='ELT')
+    for c in range(C):
+        # the columns of df_mut_tab.merge(pretrain_df) (onthefly_tools.py:104-112), then the statistics in the order they are added
+        d = {'OBS_SAMPLES': o_smp[c].astype(_quick_obs_sample_kinds(index, o_smp[c], n_listed)), 'OBS_SNV': o_snv[c].astype(float),
+             'OBS_INDEL': o_ind[c].astype(float), 'ELT_SIZE': A['ELT_SIZE'], 'FLAG': A['FLAG'][c], 'R_SIZE': A['R_SIZE'],
+             'R_OBS': A['R_OBS'][c], 'R_INDEL': A['R_OBS'][c], 'MU': A['MU'][c], 'SIGMA': A['SIGMA'][c], 'ALPHA': al[c],
+             'THETA': th[c] * cj_h[c], 'MU_INDEL': A['MU'][c], 'SIGMA_INDEL': A['SIGMA'][c], 'ALPHA_INDEL': al[c],
+             'THETA_INDEL': (th[c] * cji_h[c] if strict_reference else th[c]) if skip_pvals else S[3][c],
+             'Pi_SUM': P0[c], 'Pi_INDEL': A['P_INDEL'], 'EXP_SNV': S[0][c]}
+        if not skip_pvals:
+            d.update({'PVAL_SNV_BURDEN': S[1][c], 'PVAL_SAMPLE_BURDEN': S[2][c], 'EXP_INDEL': S[4][c], 'PVAL_INDEL_BURDEN': S[5][c],
+                      'PVAL_MUT_BURDEN': S[6][c]})
+        frames.append(pd.DataFrame(d, index=index))
+        if on_frame is not None:
+            on_frame(c, frames[-1])
+    return frames
+
+
+def run_and_write_quick_cohorts(f_muts, f_pretrained, f_fasta, outdir, prefixes, write_threads=None, **kw):
+    """run_quick_cohorts + <outdir>/<prefix>.results.txt per cohort through the native writer, as `DigDriver.py quickDriver` writes
+    it (the OBS_* columns as integers), each file by a worker thread while the frames of the cohorts after it are assembled
+    (_run_and_write)."""
+    return _run_and_write(lambda on_frame: run_quick_cohorts(f_muts, f_pretrained, f_fasta, on_frame=on_frame, **kw), len(f_muts), outdir,
+                          prefixes, write_threads, lambda path, threads, frame: lambda: _write_one(frame, path, threads))

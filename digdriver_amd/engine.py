@@ -868,6 +868,53 @@ def count_contexts(genome, chroms, starts, ends, minus=None, device=0, on_device
     return out
 
 
+def element_context_counts(genome, elt_chrom, elt_minus, blk_ptr, blk_start, blk_end, device=0, on_device=None):
+    """Strand-aware trinucleotide counts of bed12 elements straight from a PackedGenome (dig_element_context_counts): i32 [E, 64],
+    row e = the sum over the blocks blk_ptr[e] .. blk_ptr[e + 1] - 1 of the count_contexts row of (elt_chrom[e], blk_start, blk_end,
+    elt_minus[e]) -- the L of quickDriver's elements (onthefly_tools.py: one count_contexts row per block, summed on the host).
+    elt_chrom: chromosome labels, resolved against the genome as count_contexts resolves them (a CUDA tensor: the genome's i32
+    chromosome indices); elt_minus: non-zero for a '-' element.  Host arrays go through the `_host` twin (no torch) and give a
+    numpy array, CUDA tensors go to the device entry point on torch's current stream and give a tensor; on_device=True / False
+    places host arrays on `device` (the genome stays resident in HBM) / copies tensors back first.  What the library would refuse
+    -- a blk_ptr that does not run from 0 to the block count without decreasing, a chromosome outside the genome, negative
+    coordinates, 2^31 elements or blocks -- is a ValueError here, before any device work."""
+    tensors = [x for x in (elt_chrom, elt_minus, blk_ptr, blk_start, blk_end) if is_cuda(x)]
+    if on_device is None:
+        on_device = bool(tensors)
+    be = device_backend(tensors[0].device) if on_device and tensors else backend_on(device, on_device)
+    if is_cuda(elt_chrom):
+        ci = be.arr(elt_chrom, "i32", (-1,)) if be.is_device else _lib.as_host(elt_chrom.cpu().numpy(), np.int32).ravel()
+    else:
+        try:
+            ci = be.arr(genome.chrom_index(list(np.asarray(elt_chrom).ravel())), "i32")
+        except KeyError as exc:
+            raise ValueError("element_context_counts: %s" % exc.args[0]) from exc
+    host = lambda x: x.cpu().numpy() if is_cuda(x) else np.asarray(x)
+    place = lambda x, dt: be.arr(x if be.is_device else host(x), dt, (-1,))
+    mi = place(elt_minus if is_cuda(elt_minus) else np.asarray(elt_minus).astype(np.uint8), "u8")
+    ptr, bs, en = place(blk_ptr, "i64"), place(blk_start, "i64"), place(blk_end, "i64")
+    E, n_blocks = int(ci.shape[0]), int(bs.shape[0])
+    if not (mi.shape[0] == E and ptr.shape[0] == E + 1 and en.shape[0] == n_blocks):
+        raise ValueError("element_context_counts: elt_chrom, elt_minus [E], blk_ptr [E + 1] and blk_start, blk_end [blk_ptr[E]] disagree")
+    if E >= 2 ** 31 or n_blocks >= 2 ** 31:
+        raise ValueError("element_context_counts: %d elements, %d blocks: both must stay below 2^31" % (E, n_blocks))
+    true = lambda x: bool(x.all())                                    # (numpy and torch alike)
+    if not (int(ptr[0]) == 0 and int(ptr[E]) == n_blocks and true(ptr[1:] >= ptr[:-1])):
+        raise ValueError("element_context_counts: blk_ptr must run from 0 to the block count without decreasing")
+    if E and not true((ci >= 0) & (ci < len(genome.names))):
+        raise ValueError("element_context_counts: element chromosome index outside [0, %d)" % len(genome.names))
+    if n_blocks and not true((bs >= 0) & (en >= 0)):
+        raise ValueError("element_context_counts: negative block coordinates")
+    out = be.empty((E, 64), "i32")
+    if E == 0:
+        return out
+    n_ws = int(_lib.load().dig_element_context_counts_workspace(n_blocks)) if be.is_device else 0
+    p = be.ptr
+    be.call("dig_element_context_counts", *genome.genome2_args(be.dev), p(ci), p(mi), p(ptr), p(bs), p(en), E, n_blocks, p(out),
+            workspace=(be.empty(n_ws, "u8") if be.is_device else None, n_ws))
+    return out
+
+
 MC_KEPT, MC_MISMATCH, MC_DROPPED, MC_HOST = 0, 1, 2, 3          # include/dig_hip.h DIG_MC_*
 _REF_CODE = {"A": 0, "C": 1, "G": 2, "T": 3}
 

@@ -718,6 +718,34 @@ int dig_gene_site_counts_host(const uint32_t *words2, int64_t n_words2, const in
                               const int64_t *spl_ptr, const int64_t *spl_pos, int64_t n_genes, int32_t *L, int32_t *n_stop_loss,
                               uint8_t *status, int device);
 
+/* ---- context counts of bed12 elements (cohort_batch.run_quick_cohorts: the L of ad-hoc elements) ---------- *
+ * The strand-aware trinucleotide counts of E elements straight from the 2-bit genome of dig_count_contexts2 (the same ten
+ * genome arguments):
+ *   elt_chrom i32 [E]; elt_minus u8 [E] (non-zero: the element lies on the - strand);
+ *   blk_ptr i64 [E + 1], non-decreasing from 0 to n_blocks; blk_start / blk_end i64 [n_blocks]: the blocks of element e are
+ *       blk_ptr[e] .. blk_ptr[e + 1] - 1, in any order, overlapping or repeated as the bed file has them;
+ *   out i32 [E, 64], 4-byte aligned, context index 16 b0 + 4 b1 + b2: out[e] = the sum over the blocks b of element e of the row
+ *       dig_count_contexts2 gives for (elt_chrom[e], blk_start[b], blk_end[b], elt_minus[e]): centres max(start, 1) ..
+ *       min(end, chrom_len - 1) - 1, a triplet holding a letter other than ACGT skipped, the reverse complement for a - element;
+ *       a block listed twice counts twice; an element without blocks and an empty or inverted block give zeros.  Every row is
+ *       written (zeroed, then added to).  Integer counts: bit-exact whatever the mapping.
+ *   workspace: dig_element_context_counts_workspace(n_blocks) bytes, 8-byte aligned (the list of the blocks that are cut
+ *       across waves).  E, n_blocks < 2^31.
+ * The device entry point cannot see its device arrays: a chromosome id outside [0, n_chrom) counts nothing there and a blk_ptr
+ * that is not as stated gives unspecified counts (nothing outside the arrays is read or written); the _host twin refuses both
+ * with DIG_EINVAL, as it refuses negative coordinates and blk_ptr[E] != n_blocks. */
+int64_t dig_element_context_counts_workspace(int64_t n_blocks);
+int dig_element_context_counts(const uint32_t *words2, int64_t n_words2, const int64_t *nint_start, const int64_t *nint_end,
+                               int64_t n_int, const int32_t *nint_bucket, int64_t n_buckets, const int64_t *chrom_off,
+                               const int64_t *chrom_len, int n_chrom, const int32_t *elt_chrom, const uint8_t *elt_minus,
+                               const int64_t *blk_ptr, const int64_t *blk_start, const int64_t *blk_end, int64_t E,
+                               int64_t n_blocks, int32_t *out, void *workspace, int64_t workspace_bytes, void *stream);
+int dig_element_context_counts_host(const uint32_t *words2, int64_t n_words2, const int64_t *nint_start, const int64_t *nint_end,
+                                    int64_t n_int, const int32_t *nint_bucket, int64_t n_buckets, const int64_t *chrom_off,
+                                    const int64_t *chrom_len, int n_chrom, const int32_t *elt_chrom, const uint8_t *elt_minus,
+                                    const int64_t *blk_ptr, const int64_t *blk_start, const int64_t *blk_end, int64_t E,
+                                    int64_t n_blocks, int32_t *out, int device);
+
 /* ---- result files (ABI 6; host code only) ------------------------------------------------- *
  * The text DataFrame.to_csv(path, header=True, index=True, sep="\t") writes for a frame (DigDriver.py:115-118): `header`
  * (a complete first line, no newline), then n_rows rows  label TAB col_0 TAB ... col_{n_cols-1}.

@@ -4,7 +4,8 @@
 Drop-in for the reference's scripts/DigDriver.py: the same four sub-commands with the same positional
 arguments and option names (DigDriver.py:160-275), and the same output, a tab-separated
 ``<outdir>/<outpfx>.results.txt`` with header and index column (DigDriver.py:38-43,115-118); and `tileDriver`, which the
-reference does not have: the per-base scan of many cohorts, written as ``<outdir>/<outpfx>.hits.txt``.  The statistics
+reference does not have: the per-base scan of many cohorts, written as ``<outdir>/<outpfx>.hits.txt``; and `quickCohorts`,
+`quickDriver` for many cohorts in one pass, one ``<outdir>/<outpfx>.results.txt`` per cohort.  The statistics
 run through libdig_hip.so; `model` may be the reference's HDF5 map (`*.h5`, read by io/h5lite.py +
 io/pandas_fixed.py: no h5py or PyTables needed) or the directory mirror described in digdriver_amd/io/mapfile.py.
 """
@@ -103,6 +104,31 @@ def cmd_quick(args):
         if col in res.columns:
             res[col] = res[col].astype(int)
     write_results(res, args)
+
+
+def cmd_quick_cohorts(args):
+    """quickCohorts: quickDriver for many cohorts on one bin grid in one pass; per cohort <outdir>/<outpfx>.results.txt."""
+    _use_panel_dir(args)
+    n = len(args.mutation_files)
+    if not len(args.maps) == len(args.outpfx) == n:
+        raise SystemExit("ERROR: --mutation-files, --maps and --outpfx must name the same number of cohorts.")
+    if not (args.f_elts_bed or args.region_str):
+        raise SystemExit("ERROR: you must provide --f_elts_bed or --region_str.")
+    _scale_mode(args)
+    factors = None
+    if args.scale_factor_manual:
+        if not len(args.scale_factor_manual) == len(args.scale_factor_indel_manual) == n:
+            raise SystemExit("ERROR: --scale-factor-manual and --scale-factor-indel-manual take one value per cohort.")
+        factors = (args.scale_factor_manual, args.scale_factor_indel_manual)
+    from digdriver_amd.driver_model import cohort_batch
+    print('Running user-defined element driver detection for {} cohorts'.format(n))
+    _, paths = cohort_batch.run_and_write_quick_cohorts(
+        args.mutation_files, args.maps, args.f_fasta, args.outdir, args.outpfx, f_elts_bed=args.f_elts_bed,
+        region_str=args.region_str, scale_factors=factors, scale_type=args.scale_type, scale_by_expectation=args.scale_by_expectation,
+        max_muts_per_sample=args.max_muts_per_sample, max_muts_per_elt_per_sample=args.max_muts_per_elt_per_sample,
+        skip_pvals=args.skip_pvals)
+    for path in paths:
+        print('\tSaved results to {}'.format(path))
 
 
 TILE_MODELS = {(1, 1): 'sequence_model_64', (2, 2): 'sequence_model_1024'}
@@ -232,6 +258,24 @@ def parse_args(text=None):
     d.add_argument('--fdr', type=float, default=None, help="keep the tiles with Benjamini-Hochberg q <= this over the cohort's testable tiles")
     d.add_argument('--chroms', type=str, nargs='+', default=None, help='scan only the regions of these chromosomes')
     d.set_defaults(func=cmd_tile)
+
+    # not a reference sub-command: quickDriver for many cohorts at once (driver_model/cohort_batch.py run_quick_cohorts)
+    q = sub.add_parser('quickCohorts', help='quickDriver for many cohorts on one bin grid: ad-hoc elements or a region string')
+    q.add_argument('f_fasta', type=str, help='reference genome FASTA (hg19)')
+    q.add_argument('--mutation-files', type=str, nargs='+', required=True, help='one annotated mutation file per cohort')
+    q.add_argument('--maps', type=str, nargs='+', required=True, help='one pretrained mutation map per cohort, all on one bin grid')
+    q.add_argument('--outdir', type=str, required=True, help='directory for the results files')
+    q.add_argument('--outpfx', type=str, nargs='+', required=True, help='one prefix per cohort: <outpfx>.results.txt')
+    q.add_argument('--f_elts_bed', type=str, default="", help='bed12 file of elements')
+    q.add_argument('--region_str', type=str, default="", help='region as chr{}:start-end')
+    q.add_argument('--max-muts-per-sample', type=int, default=3e9, help='drop samples with more mutations in elements than this')
+    q.add_argument('--max-muts-per-elt-per-sample', type=int, default=3e9, help='cap of mutations one sample adds to an element')
+    q.add_argument('--scale-type', default=None, choices=SCALE_TYPES, help='how to derive the cohort scale factors')
+    q.add_argument('--scale-factor-manual', default=None, type=float, nargs='+', help='use these SNV scale factors, one per cohort')
+    q.add_argument('--scale-factor-indel-manual', default=None, type=float, nargs='+', help='use these indel scale factors, one per cohort')
+    q.add_argument('--skip_pvals', default=False, action='store_true', help='expected counts only')
+    q.add_argument('--panel-dir', type=str, default=None, help='directory holding the gene panel files genes_<NAME>.txt')
+    q.set_defaults(func=cmd_quick_cohorts)
 
     return parser.parse_args(text.split()) if text else parser.parse_args()
 
