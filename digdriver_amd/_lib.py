@@ -82,6 +82,10 @@ _SIGNATURES = {
     "dig_gene_row_keys_host": [_vp] * 5 + [_i64] * 4 + [_vp, _vp, _int],
     "dig_gene_counts": [_vp, _i64, _vp, _i64, ctypes.c_double, ctypes.c_double, _i64, _i64, _i64] + [_vp] * 7,
     "dig_gene_counts_host": [_vp, _i64, _vp, _i64, ctypes.c_double, ctypes.c_double, _i64, _i64, _i64] + [_vp] * 5 + [_int],
+    "dig_panel_row_keys": [_vp] * 7 + [_i64] * 5 + [_vp, _vp, _vp],
+    "dig_panel_row_keys_host": [_vp] * 7 + [_i64] * 5 + [_vp, _vp, _int],
+    "dig_panel_counts": [_vp, _i64, _vp, _vp] + [_i64] * 4 + [_vp] * 4,
+    "dig_panel_counts_host": [_vp, _i64, _vp, _vp] + [_i64] * 4 + [_vp] * 3 + [_int],
     "dig_window_pair_keys": [_vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp] + [_i64] * 4 + [_vp, _vp],
     "dig_window_pair_keys_host": [_vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp] + [_i64] * 4 + [_vp, _int],
     "dig_window_sample_hits": [_vp] + [_i64] * 4 + [_vp, _vp],

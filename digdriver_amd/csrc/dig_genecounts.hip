@@ -72,20 +72,6 @@ struct GeneCountArgs {
     unsigned long long* n_syn;     // [C]
 };
 
-// first index in [lo, n) whose key is above v (keys ascending, keys[lo - 1] == v)
-__device__ __forceinline__ int64_t keys_upper_bound(const int64_t* keys, int64_t lo, int64_t n, int64_t v)
-{
-    int64_t hi = n;
-    while (lo < hi) {
-        const int64_t mid = lo + ((hi - lo) >> 1);
-        if (keys[mid] > v)
-            hi = mid;
-        else
-            lo = mid + 1;
-    }
-    return lo;
-}
-
 __global__ __launch_bounds__(kGeneCountBlock) void gene_counts_kernel(GeneCountArgs a)
 {
     const int64_t i = (int64_t)blockIdx.x * kGeneCountBlock + threadIdx.x;

@@ -352,6 +352,41 @@ int dig_gene_counts_host(const int64_t* keys_sorted, int64_t n, const int32_t* s
                    st.out(n_syn, C), st.out(blacklisted, n_samples), static_cast<int32_t*>(st.scratch(GC * 5 * sizeof(int32_t))), nullptr);
 }
 
+int dig_panel_row_keys_host(const int32_t* label, const int32_t* sample, const uint8_t* annot, const int32_t* cohort,
+                            const int64_t* sample_off, const uint8_t* skip, const uint32_t* label_mask, int64_t n, int64_t L, int64_t P,
+                            int64_t C, int64_t n_samples, int64_t* keys, int64_t* n_cds, int device)
+{
+    DIG_REQUIRE(n >= 0, "n >= 0");
+    int lb = 0;
+    if (int rc = panel_key_layout(__func__, L, P, C, n_samples, &lb)) return rc;
+    DIG_REQUIRE(sample_off && label_mask && n_cds && (n == 0 || (label && sample && annot && cohort && keys)), "non-null pointers");
+    if (int rc = check_sample_off(__func__, sample_off, C, n_samples)) return rc;
+    for (int64_t i = 0; i < n; ++i) {
+        DIG_REQUIRE(cohort[i] >= 0 && cohort[i] < C, "cohort within [0, C)");
+        DIG_REQUIRE(label[i] >= 0 && label[i] <= L, "label within [0, L]");
+        DIG_REQUIRE(annot[i] <= 6, "annotation class within [0, 6]");
+        DIG_REQUIRE(sample[i] >= 0 && sample_off[cohort[i]] + sample[i] < sample_off[cohort[i] + 1], "sample id within its cohort");
+    }
+    Staging st(device);
+    return st.call(dig_panel_row_keys, st.in(label, n), st.in(sample, n), st.in(annot, n), st.in(cohort, n), st.in(sample_off, C + 1),
+                   st.in(skip, n_samples), st.in(label_mask, L), n, L, P, C, n_samples, st.out(keys, n), st.out(n_cds, C), nullptr);
+}
+
+int dig_panel_counts_host(const int64_t* keys_sorted, int64_t n, const uint32_t* label_mask, const int64_t* sample_off, int64_t L,
+                          int64_t P, int64_t C, int64_t n_samples, int64_t* n_mut, int64_t* n_pairs, int64_t* n_sample, int device)
+{
+    DIG_REQUIRE(n >= 0, "n >= 0");
+    int lb = 0;
+    if (int rc = panel_key_layout(__func__, L, P, C, n_samples, &lb)) return rc;
+    DIG_REQUIRE(sample_off && label_mask && n_mut && n_pairs && n_sample && (n == 0 || keys_sorted), "non-null pointers");
+    if (int rc = check_sample_off(__func__, sample_off, C, n_samples)) return rc;
+    if (int rc = check_ascending(__func__, keys_sorted, n)) return rc;
+    const size_t CP = (size_t)C * P;
+    Staging st(device);
+    return st.call(dig_panel_counts, st.in(keys_sorted, n), n, st.in(label_mask, L), st.in(sample_off, C + 1), L, P, C, n_samples,
+                   st.out(n_mut, CP), st.out(n_pairs, CP), st.out(n_sample, CP), nullptr);
+}
+
 int dig_window_pair_keys_host(const int32_t* pair_row, const int32_t* pair_blk, int64_t n_pairs, const int32_t* blk_window, int64_t n_blk,
                               const int32_t* row_sample, const int32_t* row_uid, const uint8_t* row_indel, int64_t n_rows,
                               int64_t n_samples, int64_t N, int64_t n_uid, int64_t* keys, int device)

@@ -1,4 +1,4 @@
-// dig_keyruns.hpp -- what the counting routes (dig_genecounts.hip, dig_objectives.hip, dig_seqcounts.hip, dig_sitematch.hip, dig_tilehits.hip) and their host twins share:
+// dig_keyruns.hpp -- what the counting routes (dig_genecounts.hip, dig_objectives.hip, dig_panelcounts.hip, dig_seqcounts.hip, dig_sitematch.hip, dig_tilehits.hip) and their host twins share:
 // rows encoded as 63-bit keys, sorted by the caller, counted as runs with one integer atomic per wave segment.
 #pragma once
 #include "dig_common.hpp"
@@ -28,6 +28,10 @@ struct WindowKeyLayout {
     int uid_bits, window_bits;
 };
 int window_key_layout(const char* fn, int64_t n_samples, int64_t N, int64_t n_uid, WindowKeyLayout* lay);
+
+// dig_panelcounts.hip: the bits of the label field of a panel-count key, global sample << bits | label; DIG_EINVAL (in the name of
+// entry point `fn`) when the two fields do not fit 63 bits
+int panel_key_layout(const char* fn, int64_t L, int64_t P, int64_t C, int64_t n_samples, int* label_bits);
 
 // dig_tilehits.hip: the sizes of a score plane [C, R, T]; DIG_EINVAL (in the name of entry point `fn`) unless C R < 2^31 and T < 2^31
 int tile_select_sizes(const char* fn, int64_t C, int64_t R, int64_t T);
@@ -60,6 +64,20 @@ __device__ __forceinline__ int segment_count(int64_t seg, bool flag)
     const int end = stop ? __ffsll((long long)stop) - 1 : 64;
     const unsigned long long mine = (end == 64 ? ~0ull : ((1ull << end) - 1)) & (above | (1ull << lane));
     return __popcll(flags & mine);
+}
+
+// first index in [lo, n) whose key is above v (keys ascending, keys[lo - 1] == v)
+__device__ __forceinline__ int64_t keys_upper_bound(const int64_t* keys, int64_t lo, int64_t n, int64_t v)
+{
+    int64_t hi = n;
+    while (lo < hi) {
+        const int64_t mid = lo + ((hi - lo) >> 1);
+        if (keys[mid] > v)
+            hi = mid;
+        else
+            lo = mid + 1;
+    }
+    return lo;
 }
 
 }  // namespace dig

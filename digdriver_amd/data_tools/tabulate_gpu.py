@@ -177,6 +177,35 @@ def encode_gene_rows(f_mut, gene_index, cohort_id=0, keep=None):
                 sample_names=list(sample_names))
 
 
+PANEL_ROW_CLASSES = dict(GENE_ROW_CLASSES, Noncoding=6)                                                  # anything else: 5
+
+
+def encode_panel_rows(f_mut, labels, cohort_id=0):
+    """The rows of a cohort file as engine.panel_counts takes them: every row of read_mutation_file(f_mut, drop_duplicates=True) --
+    autosomes only, one row per (mutation, sample), then get_unique_indels -- i.e. the rows CohortRun.panel_scale and
+    DigPretrain.py countMutations start from, before the blacklist and the class filter (the pandas route: the native parser carries
+    no annotation class).
+    labels: the gene table (L labels, the union of the panels asked for).  Returns dict(label i32: the GENE's place in `labels`, L for
+    a gene in none of them; sample i32: dense ids in order of first appearance; annot u8: PANEL_ROW_CLASSES, 5 for any other label;
+    cohort i32; sample_names).  ValueError naming the file when it has no GENE / ANNOT columns, and for a row without a SAMPLE label."""
+    import pandas as pd
+    rows = mutation_tools.read_mutation_file(f_mut, drop_duplicates=False, unique_indels=False)
+    if 'GENE' not in rows.columns or 'ANNOT' not in rows.columns:
+        raise ValueError("{}: no GENE / ANNOT columns (an annotated mutation file has 8 or more)".format(f_mut))
+    rows = mutation_tools.get_unique_indels(mutation_tools.drop_duplicate_mutations(rows))      # (what drop_duplicates=True does)
+    if rows.SAMPLE.isna().any():
+        raise ValueError("{}: a row without a SAMPLE label".format(f_mut))
+    labels = list(labels)
+    L = len(labels)
+    place = {name: i for i, name in enumerate(labels)}
+    codes, uniq = pd.factorize(rows.GENE.values)
+    lookup = np.array([place.get(u, L) for u in uniq] + [L], np.int32)                                  # (a missing label: code -1)
+    sample, sample_names = pd.factorize(rows.SAMPLE.values)
+    annot = rows.ANNOT.map(PANEL_ROW_CLASSES).fillna(5).to_numpy(np.uint8)
+    return dict(label=lookup[codes], sample=sample.astype(np.int32), annot=annot, cohort=np.full(len(rows), int(cohort_id), np.int32),
+                sample_names=list(sample_names))
+
+
 def _encode_mutation_file_native(path, cohort_id):
     """encode_mutation_file through the library's parser (dig_mutation_file_*_host, include/dig_hip.h): the same arrays, no
     interpreter lock held while a file is parsed -- 37 files side by side: 0.83 s -> 0.1 s on the 256 cores of the GPU box.

@@ -24,6 +24,12 @@ file encoded once, the rows of C cohorts matched exactly and counted by engine.s
 quickDriver (onthefly_tools.DIG_onthefly: ad-hoc elements, no pretrained element model) likewise -- run_quick_cohorts: the elements'
 context counts are one engine.element_context_counts launch over the bed12 (dig_element_context_counts), the grid's window contexts
 one engine.count_contexts launch, and the rest is run_element_cohorts without its element container (tests/test_gpu_quick_cohorts.py).
+
+targetDriver (transfer_tools.run_target_model, transfer_tools.py:876-967) likewise -- run_target_cohorts: the tested rows go the
+gene route's way (engine.gene_counts), the scale factor's rows inside the panel are counted by engine.panel_counts
+(dig_panel_row_keys + a key sort + dig_panel_counts), then ONE dig_gene_stats launch over [G, C]; count_cohort_mutations writes the
+attributes of `DigPretrain.py countMutations` for C maps from one such call over all installed panels
+(tests/test_gpu_target_cohorts.py).
 """
 import numpy as np
 import pandas as pd
@@ -414,6 +420,62 @@ def _expected_syn_scale(genes, n_syn):
     return n_syn / (background.MU * background.Pi_SYN).sum()
 
 
+_OBS_NAMES = ('OBS_SYN', 'OBS_MIS', 'OBS_NONS', 'OBS_SPL', 'OBS_INDEL')
+
+
+def _restrict_gene_models(models, planes, keep):
+    """The rows of the C gene models (and of their planes) whose gene is in the set `keep` (cgc_genes, a panel)."""
+    inside = models[0].index.isin(keep)
+    return [m.loc[inside] for m in models], {k: np.ascontiguousarray(v[inside]) for k, v in planes.items()}
+
+
+def _gene_counts_on_host(counts):
+    """engine.gene_counts' planes cohort-major on the host: obs i64 [C, 5, G], n_samp i64 [C, 6, G], n_samp_indel i64 [C, G],
+    n_pairs [C, G]."""
+    by_cohort = lambda x: x.transpose(-1, -2).contiguous().cpu().numpy()                     # [..., G, C] -> [..., C, G]
+    obs_h = counts["obs"].permute(2, 1, 0).contiguous().cpu().numpy().astype(np.int64)       # [C, 5, G]
+    n_samp_h = counts["n_samp"].permute(2, 1, 0).contiguous().cpu().numpy().astype(np.int64)
+    return obs_h, n_samp_h, by_cohort(counts["n_samp_indel"]).astype(np.int64), by_cohort(counts["n_pairs"])
+
+
+def _gene_burden_planes(planes, counts, cj, t_indel, dev):
+    """ONE engine.gene_stats launch over [G, C] for the models' planes, the counts of engine.gene_counts, cj [C] and t_indel [C] (None:
+    no indel block).  Returns (pi as a tensor [G, 6, C], dict plane name -> host array [C, G])."""
+    import torch
+    tt = transfer_tools
+    t = lambda a: torch.as_tensor(np.ascontiguousarray(a), device=dev)
+    pi = t(np.stack([planes['Pi_' + c] for c in tt.GENE_CLASSES], axis=1))                    # [G, 6, C]
+    st = engine.gene_stats(t(planes['MU']), t(planes['SIGMA']), pi, t(planes['Pi_INDEL']), counts["obs"], counts["n_samp"], t(cj),
+                           None if t_indel is None else t(t_indel), mu_indel=t(planes['MU_INDEL']), sigma_indel=t(planes['SIGMA_INDEL']))
+    return pi, {k: v.transpose(-1, -2).contiguous().cpu().numpy() for k, v in st.items()}
+
+
+def _gene_count_columns(m, theta, obs, n_samp, n_samp_indel, n_pairs):
+    """The columns of transfer_gene_model for one cohort: the model's (m), THETA as scaled, OBS_* (obs i64 [5, G]) and N_SAMP_* (n_samp
+    i64 [6, G], n_samp_indel [G]); n_pairs [G]: the (gene, sample) pairs with a row of any class."""
+    tt = transfer_tools
+    d = {col: m[col].values for col in tt._GENE_COLS_LEFT}
+    d['THETA'] = np.ascontiguousarray(theta)
+    # a model gene without a row in the cohort's count table makes the serial route's left join fill with NaN: float columns
+    kind = np.int64 if (n_pairs > 0).all() else np.float64
+    for q, name in enumerate(_OBS_NAMES):
+        d[name] = obs[q].astype(kind)
+    d['OBS_TRUNC'] = d['OBS_NONS'] + d['OBS_SPL']
+    d['OBS_NONSYN'] = d['OBS_MIS'] + d['OBS_TRUNC']
+    for q, cls in enumerate(tt.GENE_CLASSES):
+        d['N_SAMP_' + cls] = n_samp[q]
+    d['N_SAMP_INDEL'] = n_samp_indel
+    return d
+
+
+def _burden_columns(d, S, c):
+    """The twelve burden p-value columns of cohort c from the planes of _gene_burden_planes."""
+    for pattern in ('PVAL_%s_BURDEN', 'PVAL_%s_BURDEN_SAMPLE'):
+        for cls in transfer_tools.GENE_CLASSES:
+            d[pattern % cls] = S[pattern % cls][c]
+    return d
+
+
 def run_gene_cohorts(f_muts, f_genemodels, scale_by_sample=False, pval_burden_nb=True, pval_burden_dnds=True, pval_sel=True,
                      max_muts_per_sample=3e9, max_muts_per_gene_per_sample=3e9, scale_factors=None, scale_by_expectation=True,
                      cgc_genes=False, all_cosmic=None, selection=False, device=0, on_frame=None):
@@ -440,9 +502,7 @@ def run_gene_cohorts(f_muts, f_genemodels, scale_by_sample=False, pval_burden_nb
     keep = None
     if cgc_genes:
         keep = set(tt.gene_panel(cgc_genes))
-        inside = models[0].index.isin(keep)
-        models = [m.loc[inside] for m in models]
-        planes = {k: np.ascontiguousarray(v[inside]) for k, v in planes.items()}
+        models, planes = _restrict_gene_models(models, planes, keep)
     index = models[0].index
     G = len(index)
     dev = resolve_device(device)
@@ -453,9 +513,7 @@ def run_gene_cohorts(f_muts, f_genemodels, scale_by_sample=False, pval_burden_nb
     counts = engine.gene_counts(*stack, cohort_rows.sample_offsets(rows), G, C, tp53,
                                 max_muts_per_sample=max_muts_per_sample, max_muts_per_gene_per_sample=max_muts_per_gene_per_sample)
     by_cohort = lambda x: x.transpose(-1, -2).contiguous().cpu().numpy()                     # [..., G, C] -> [..., C, G]
-    obs_h = counts["obs"].permute(2, 1, 0).contiguous().cpu().numpy().astype(np.int64)       # [C, 5, G]
-    n_samp_h = counts["n_samp"].permute(2, 1, 0).contiguous().cpu().numpy().astype(np.int64)
-    n_samp_indel, n_pairs = by_cohort(counts["n_samp_indel"]).astype(np.int64), by_cohort(counts["n_pairs"])
+    obs_h, n_samp_h, n_samp_indel, n_pairs = _gene_counts_on_host(counts)
     n_syn = counts["n_syn"].cpu().numpy()
 
     # scale factors (transfer_tools.py:809-823) and the uniform indel rate (:709-721), a cohort at a time over G values
@@ -477,37 +535,23 @@ def run_gene_cohorts(f_muts, f_genemodels, scale_by_sample=False, pval_burden_nb
 
     print('Calculating statistics')
     t = lambda a: torch.as_tensor(np.ascontiguousarray(a), device=dev)
-    pi = np.stack([planes['Pi_' + c] for c in tt.GENE_CLASSES], axis=1)                       # [G, 6, C]
     S = {}
     if pval_burden_nb:
-        st = engine.gene_stats(t(planes['MU']), t(planes['SIGMA']), t(pi), t(planes['Pi_INDEL']), counts["obs"], counts["n_samp"], t(cj),
-                               t(t_indel), mu_indel=t(planes['MU_INDEL']), sigma_indel=t(planes['SIGMA_INDEL']))
-        S.update({k: by_cohort(v) for k, v in st.items()})
+        pi, S = _gene_burden_planes(planes, counts, cj, t_indel, dev)
+    else:
+        pi = t(np.stack([planes['Pi_' + c] for c in tt.GENE_CLASSES], axis=1))                # [G, 6, C]
     if selection:
-        sel = engine.gene_selection(t(planes['ALPHA']), t(theta), t(pi), counts["obs"])
+        sel = engine.gene_selection(t(planes['ALPHA']), t(theta), pi, counts["obs"])
         S.update({k: by_cohort(v) for k, v in sel.items()})
 
     frames = []
-    obs_names = ('OBS_SYN', 'OBS_MIS', 'OBS_NONS', 'OBS_SPL', 'OBS_INDEL')
     for c, m in enumerate(models):
-        d = {col: m[col].values for col in tt._GENE_COLS_LEFT}
-        d['THETA'] = np.ascontiguousarray(theta[:, c])
-        # a model gene without a row in the cohort's count table makes the serial route's left join fill with NaN: float columns
-        kind = np.int64 if (n_pairs[c] > 0).all() else np.float64
-        for q, name in enumerate(obs_names):
-            d[name] = obs_h[c, q].astype(kind)
-        d['OBS_TRUNC'] = d['OBS_NONS'] + d['OBS_SPL']
-        d['OBS_NONSYN'] = d['OBS_MIS'] + d['OBS_TRUNC']
-        for q, cls in enumerate(tt.GENE_CLASSES):
-            d['N_SAMP_' + cls] = n_samp_h[c, q]
-        d['N_SAMP_INDEL'] = n_samp_indel[c]
+        d = _gene_count_columns(m, theta[:, c], obs_h[c], n_samp_h[c], n_samp_indel[c], n_pairs[c])
         rate = m.ALPHA.values * d['THETA']
         for q, cls in enumerate(tt.GENE_CLASSES):                          # gene_expected_muts_nb: the serial route's own products
             d['EXP_' + cls] = S['EXP_' + cls][c] if pval_burden_nb and not selection else rate * m['Pi_' + cls].values
         if pval_burden_nb:
-            for pattern in ('PVAL_%s_BURDEN', 'PVAL_%s_BURDEN_SAMPLE'):
-                for cls in tt.GENE_CLASSES:
-                    d[pattern % cls] = S[pattern % cls][c]
+            _burden_columns(d, S, c)
         if selection:
             names = ['T_SYN', 'MRFOLD'] + ['EXP_%s_ML' % cls for cls in tt.GENE_CLASSES]
             if pval_burden_dnds:
@@ -532,6 +576,169 @@ def run_and_write_gene_cohorts(f_muts, f_genemodels, outdir, prefixes, write_thr
     of the cohorts after it are assembled (_run_and_write)."""
     return _run_and_write(lambda on_frame: run_gene_cohorts(f_muts, f_genemodels, on_frame=on_frame, **kw), len(f_muts), outdir, prefixes,
                           write_threads, lambda path, threads, frame: lambda: mapfile.write_results_tsv(frame, path, threads))
+
+
+# ---------------------------------------------------------------------------------------------
+# targetDriver and countMutations for many cohorts
+# ---------------------------------------------------------------------------------------------
+def _panel_table(panels):
+    """The label table of engine.panel_counts for the panels {name: genes} (at most 32): (labels: the union of their genes in order of
+    first appearance, label_mask u32 [L]: bit p set for a gene of the p-th panel)."""
+    if len(panels) > 32:
+        raise ValueError("{} panels: a panel is a bit of a 32-bit mask".format(len(panels)))
+    place, bits = {}, []
+    for p, genes in enumerate(panels.values()):
+        for gene in genes:
+            if gene not in place:
+                place[gene] = len(bits)
+                bits.append(0)
+            bits[place[gene]] |= 1 << p
+    return list(place), np.array(bits, np.uint64).astype(np.uint32)
+
+
+def _panel_counts_on_host(rows, label_mask, P, skip, device):
+    """engine.panel_counts over the stacked rows of encode_panel_rows (device None: host arrays through the `_host` twins), its
+    counts as host arrays."""
+    if len(label_mask) == 0:                      # no panel at all: one label without a panel (every row carries it; n_cds still counts)
+        label_mask = np.zeros(1, np.uint32)
+    stack =cohort_rows.place([cohort_rows.column(rows, k) for k in ("label", "sample", "annot", "cohort")], device is not None, device)
+    counts = engine.panel_counts(*stack, cohort_rows.sample_offsets(rows), label_mask, P, skip=skip, device=device or 0)
+    return {k: (v.cpu().numpy() if engine.is_cuda(v) else np.asarray(v)) for k, v in counts.items()}
+
+
+def run_target_cohorts(f_muts, f_genemodels, panel="MSK_341", scale_by_sample=False, max_muts_per_sample=3e9,
+                       max_muts_per_gene_per_sample=3e9, drop_synonymous=True, cgc_genes=False, scale_factors=None, device=0,
+                       on_frame=None):
+    """targetDriver for C cohorts in one pass: one frame per cohort, with the columns, the column order, the dtypes and the values of
+    transfer_tools.run_target_model(f_muts[c], f_genemodels[c], ...) and the same keywords (scale_factors: an array [C] in place of
+    scale_factor; as there, a zero stands for "not given").  The gene models must share one gene index (ValueError); a map without the
+    N_MUT_<panel> (scale_by_sample: N_SAMPLE_<panel>) attribute its scale factor needs: KeyError naming the map, before any device
+    work.
+    The tested rows (the panel's genes, or those of cgc_genes; without Synonymous rows when drop_synonymous) are counted by
+    engine.gene_counts, which also gives the blacklist of max_muts_per_sample; the blacklist is carried by sample name onto the rows
+    of tabulate_gpu.encode_panel_rows -- read_mutation_file(drop_duplicates=True) -- which engine.panel_counts counts inside the
+    PANEL's genes: rows (or, scale_by_sample, distinct samples) whose ANNOT is none of Noncoding, Synonymous, Essential_Splice.  The
+    scale factor is the serial route's own division by the map's attribute (the same bits); the statistics are one engine.gene_stats
+    launch over [G, C], without the indel block (run_target_model has none).
+    on_frame(c, frame): called as soon as cohort c's frame exists."""
+    tt = transfer_tools
+    f_muts, f_genemodels = list(f_muts), list(f_genemodels)
+    C = len(f_muts)
+    if C == 0 or len(f_genemodels) != C:
+        raise ValueError("run_target_cohorts: {} mutation files for {} maps (one map per cohort, at least one cohort)".format(C, len(f_genemodels)))
+    given = np.zeros(C) if scale_factors is None else np.asarray(scale_factors, float).reshape(-1)
+    if len(given) != C:
+        raise ValueError("run_target_cohorts: scale_factors must hold one value per cohort ({})".format(C))
+    print(panel)
+    panel_genes = tt.gene_panel(panel)
+    tested = set(tt.gene_panel(cgc_genes)) if cgc_genes else set(panel_genes)
+    attr = 'N_SAMPLE_{}'.format(panel) if scale_by_sample else 'N_MUT_{}'.format(panel)
+    denom = {}
+    for c in np.flatnonzero(given == 0):
+        attrs = mapfile.read_attrs(f_genemodels[c])
+        if attr not in attrs:
+            raise KeyError("{}: no attribute {} (DigPretrain.py countMutations writes it; or pass scale_factors)".format(f_genemodels[c], attr))
+        denom[c] = attrs[attr]
+    models, planes = _read_gene_models(f_genemodels)
+    models, planes = _restrict_gene_models(models, planes, tested)
+    index = models[0].index
+    G = len(index)
+    dev = resolve_device(device)
+
+    # row set A: the tested rows -> observed counts, N_SAMP_*, the blacklist
+    rows = [tabulate_gpu.encode_gene_rows(f, index, c, keep=tested) for c, f in enumerate(f_muts)]
+    if drop_synonymous:
+        for r in rows:
+            kept = r["annot"] != 0
+            for k in ("gene", "sample", "annot", "cohort"):
+                r[k] = r[k][kept]
+    tp53 = int(index.get_loc('TP53')) if 'TP53' in index else G + 1
+    offsets = cohort_rows.sample_offsets(rows)
+    stack = cohort_rows.place([cohort_rows.column(rows, k) for k in ("gene", "sample", "annot", "cohort")], True, dev)
+    counts = engine.gene_counts(*stack, offsets, G, C, tp53, max_muts_per_sample=max_muts_per_sample,
+                                max_muts_per_gene_per_sample=max_muts_per_gene_per_sample)
+    obs_h, n_samp_h, n_samp_indel, n_pairs = _gene_counts_on_host(counts)
+
+    # row set B: the scale factor's rows inside the panel, without the samples row set A blacklisted (carried over by name)
+    cj = given.copy()
+    if denom:
+        black = counts["blacklisted"].cpu().numpy()
+        labels, label_mask = _panel_table({panel: panel_genes})
+        rows_b = [tabulate_gpu.encode_panel_rows(f, labels, c) for c, f in enumerate(f_muts)]
+        off_b = cohort_rows.sample_offsets(rows_b)
+        skip = np.zeros(int(off_b[-1]), np.uint8)
+        for c in range(C):
+            listed = set(name for j, name in enumerate(rows[c]["sample_names"]) if black[offsets[c] + j])
+            if listed:
+                skip[off_b[c]:off_b[c + 1]] = [name in listed for name in rows_b[c]["sample_names"]]
+        inside = _panel_counts_on_host(rows_b, label_mask, 1, skip, dev)
+        counted = inside["n_sample"] if scale_by_sample else inside["n_mut"]
+        for c, d in denom.items():
+            cj[c] = int(counted[c, 0]) / d                                # (CohortRun.panel_scale's own division)
+
+    print('Calculating statistics')
+    theta = planes['THETA'] * 1.0 * cj[None, :]                           # (_attach_counts scales by 1.0, transfer_gene_model by cj)
+    _, S = _gene_burden_planes(planes, counts, cj, None, dev)
+    frames = []
+    for c, m in enumerate(models):
+        d = _gene_count_columns(m, theta[:, c], obs_h[c], n_samp_h[c], n_samp_indel[c], n_pairs[c])
+        rate = m.ALPHA.values * d['THETA']
+        for cls in tt.GENE_CLASSES:                                        # gene_expected_muts_nb: the serial route's own products
+            d['EXP_' + cls] = rate * m['Pi_' + cls].values
+        _burden_columns(d, S, c)
+        print("\tScaling factor of cohort {} is: {}".format(c, cj[c]))
+        frames.append(pd.DataFrame(d, index=index))
+        if on_frame is not None:
+            on_frame(c, frames[-1])
+    return frames
+
+
+def run_and_write_target_cohorts(f_muts, f_genemodels, outdir, prefixes, write_threads=None, **kw):
+    """run_target_cohorts + <outdir>/<prefix>.results.txt per cohort through the native writer, as `DigDriver.py targetDriver` writes
+    it (mapfile.write_results_tsv of the frame as it is), each file by a worker thread while the frames of the cohorts after it are
+    assembled (_run_and_write)."""
+    return _run_and_write(lambda on_frame: run_target_cohorts(f_muts, f_genemodels, on_frame=on_frame, **kw), len(f_muts), outdir,
+                          prefixes, write_threads, lambda path, threads, frame: lambda: mapfile.write_results_tsv(frame, path, threads))
+
+
+COUNT_PANELS = ('MSK_230', 'MSK_341', 'MSK_410', 'MSK_468', 'metabric_173', 'ucla_1202')     # DigPretrain.py:163-176
+
+
+def count_cohort_mutations(f_muts, f_maps, write=True, device=0):
+    """DigPretrain.py countMutations for C maps in one pass: the attribute dicts of count_training_mutations(f_muts[c] -> f_maps[c]),
+    keys and values, from ONE engine.panel_counts call over the rows of all cohorts and all installed panels (a panel whose
+    genes_<name>.txt is not found is skipped, as the serial function skips it).  N_SAMPLES is the length of the encoder's sample
+    table, N_MUT_CDS (stored as N_MUT_SAMPLE_CDS too: the reference's slip, kept) the rows that are not Noncoding, N_MUT_TOTAL /
+    N_MUT_TRAIN come from each map's region_params.  write=True stores every dict with mapfile.write_attrs.
+    device: the card whose memory holds the rows while they are counted; None: host arrays through the `_host` twins."""
+    f_muts, f_maps = list(f_muts), list(f_maps)
+    C = len(f_muts)
+    if C == 0 or len(f_maps) != C:
+        raise ValueError("count_cohort_mutations: {} mutation files for {} maps (one map per cohort, at least one cohort)".format(C, len(f_maps)))
+    panels = {}
+    for name in COUNT_PANELS:
+        try:
+            panels[name] = transfer_tools.gene_panel(name)
+        except FileNotFoundError:
+            continue                               # panel list not installed (see INTEGRATION.md)
+    labels, label_mask = _panel_table(panels)
+    rows = [tabulate_gpu.encode_panel_rows(f, labels, c) for c, f in enumerate(f_muts)]
+    counts = _panel_counts_on_host(rows, label_mask, max(len(panels), 1), None, device)
+    out = []
+    for c, f_map in enumerate(f_maps):
+        df = mapfile.read_frame(f_map, 'region_params')
+        flag = df.FLAG.values.astype(bool)
+        attrs = {'N_MUT_TOTAL': int(df.Y_TRUE.sum()), 'N_MUT_TRAIN': int(df.Y_TRUE.values[~flag].sum()),
+                 'N_SAMPLES': len(rows[c]["sample_names"]), 'N_MUT_CDS': int(counts["n_cds"][c]), 'N_MUT_SAMPLE_CDS': int(counts["n_cds"][c])}
+        for p, name in enumerate(panels):
+            attrs['N_MUT_' + name] = int(counts["n_mut"][c, p])
+            attrs['N_MUT_SAMPLE_' + name] = int(counts["n_pairs"][c, p])
+            if name == 'MSK_230':
+                attrs['N_SAMPLE_MSK_230'] = int(counts["n_sample"][c, p])
+        if write:
+            mapfile.write_attrs(f_map, **attrs)
+        out.append(attrs)
+    return out
 
 
 # ---------------------------------------------------------------------------------------------

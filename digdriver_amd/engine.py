@@ -287,6 +287,49 @@ def gene_counts(gene, sample, annot, cohort, sample_offsets, G, C, tp53, max_mut
     return dict(obs=obs, n_samp=n_samp, n_syn=n_syn, blacklisted=black, n_samp_indel=extra[:, 0], n_pairs=extra[:, 1])
 
 
+def panel_counts(label, sample, annot, cohort, sample_offsets, label_mask, P, skip=None, device=0):
+    """The target route's panel bookkeeping for the rows of C cohorts and P <= 32 panels (CohortRun.panel_scale,
+    transfer_tools.py:905-935; DigPretrain.py countMutations, :103-177): dig_panel_row_keys, a key sort, dig_panel_counts.  Rows as
+    tabulate_gpu.encode_panel_rows gives them: label i32 (0 .. L - 1 = the place in the label table, L = in no panel), sample i32
+    (dense per cohort), annot u8 (0 SYN, 1 MIS, 2 NONS, 3 SPL, 4 INDEL, 5 other, 6 Noncoding), cohort i32; sample_offsets [C + 1];
+    label_mask u32 [L] (a host array): bit p set when the label is in panel p; skip u8 per global sample or None: the blacklist.
+    Returns dict(n_mut, n_pairs, n_sample i64 [C, P]: counted rows, distinct (label, sample) pairs and distinct samples per cohort
+    and panel; n_cds i64 [C]: rows that are not Noncoding).  CUDA tensors in -> CUDA tensors out."""
+    be = backend_of(label, sample, annot, cohort, device=device)
+    label, sample, cohort = (be.arr(x, "i32", (-1,)) for x in (label, sample, cohort))
+    annot = be.arr(annot, "u8", (-1,))
+    n = label.shape[0]
+    assert sample.shape[0] == annot.shape[0] == cohort.shape[0] == n
+    P = int(P)
+    off_host, C, S = _sample_offsets(sample_offsets)
+    mask_host = np.ascontiguousarray(np.asarray(label_mask.cpu() if is_cuda(label_mask) else label_mask)).ravel()
+    if mask_host.dtype != np.uint32:
+        if len(mask_host) and (mask_host.min() < 0 or mask_host.max() >= 2 ** 32):
+            raise ValueError("label_mask: 32-bit masks")
+        mask_host = mask_host.astype(np.uint32)
+    L = len(mask_host)
+    mask = be.arr(mask_host.view(np.int32), "i32")          # (the bits; the library reads them as u32)
+    off = be.arr(off_host, "i64")
+    skip = be.arr(skip, "u8", (-1,))
+    if skip is not None and skip.shape[0] != S:
+        raise ValueError("skip: one byte per global sample ({})".format(S))
+    if be.is_device and n:
+        # (device tensors are checked here; the host twin checks its own arrays inside the library)
+        per_row = (off[1:] - off[:-1])[cohort.clamp(0, C - 1).long()]
+        bad = (cohort < 0) | (cohort >= C) | (label < 0) | (label > L) | (annot > 6) | (sample < 0) | (sample >= per_row)
+        if bool(bad.any()):
+            raise ValueError("a row outside the tables: cohort within [0, C), label within [0, L], annot within [0, 6], sample "
+                             "within its cohort")
+    p = be.ptr
+    keys, n_cds = be.empty(n, "i64"), be.empty(C, "i64")
+    with _requirements_as_value_errors():
+        be.call("dig_panel_row_keys", p(label), p(sample), p(annot), p(cohort), p(off), p(skip), p(mask), n, L, P, C, S, p(keys), p(n_cds))
+        keys = _sorted(be, keys)
+        n_mut, n_pairs, n_sample = (be.empty((C, P), "i64") for _ in range(3))
+        be.call("dig_panel_counts", p(keys), n, p(mask), p(off), L, P, C, S, p(n_mut), p(n_pairs), p(n_sample))
+    return dict(n_mut=n_mut, n_pairs=n_pairs, n_sample=n_sample, n_cds=n_cds)
+
+
 def window_objectives(win_chrom, win_start, win_end, row_chrom, row_start, row_end, row_sample, row_uid, row_indel, sample_offsets,
                       n_uid, keep_from_hits=None, device=0):
     """The region model's training labels for C cohorts at once (scripts/DataExtractor.py:525-572 add_objectives without --cnv):

@@ -39,7 +39,8 @@ extern "C" {
                              * 5: + dig_bin_records_pack, `bin_records` argument of dig_element_pipeline; 6: + dig_count_contexts2 (2-bit genome), dig_write_tsv_host;
                              * 7: + dig_mutation_file_*_host; 8: + dig_stage_timer_*; 9: + DIG_PIPE_RECORDS, dig_element_records_*;
                              * 12 (round 6): + dig_sort_rows, dig_bh_qvalues_ragged; - dig_element_pipeline_scaled*, dig_element_pipeline_pack_counts /
-                             * DIG_PIPE_PACKED_COUNTS (round 5's measured losers: tools/rejected/r05_*.patch) */
+                             * DIG_PIPE_PACKED_COUNTS (round 5's measured losers: tools/rejected/r05_*.patch); still 12: + dig_panel_row_keys,
+                             * dig_panel_counts and their _host twins (additions) */
 
 /* dtype codes for dig_gather_bins */
 #define DIG_F32 0
@@ -340,6 +341,33 @@ int dig_gene_counts(const int64_t *keys_sorted, int64_t n, const int32_t *sample
 int dig_gene_counts_host(const int64_t *keys_sorted, int64_t n, const int32_t *sample_total, int64_t n_samples,
                          double max_muts_per_sample, double max_muts_per_gene_per_sample, int64_t tp53, int64_t G, int64_t C,
                          int32_t *obs, int32_t *n_samp, int32_t *extra, int64_t *n_syn, uint8_t *blacklisted, int device);
+
+/* ---- the target route's panel counts for many cohorts (additive: the ABI version stays) ------------------------ *
+ * What CohortRun.panel_scale (transfer_tools.py:905-935) and DigPretrain.py countMutations (:103-177) count per sequencing panel, for
+ * the rows of C cohorts and P <= 32 panels at once.  A row is (label, sample id dense per cohort, class, cohort): label 0 .. L - 1 =
+ * the place of the row's GENE in a table of L genes (the union of the panels), L = in no panel; label_mask u32 [L]: bit p set when the
+ * gene is in panel p (bits from P on are ignored); class 0 Synonymous, 1 Missense, 2 Nonsense, 3 Essential_Splice, 4 INDEL, 5 any
+ * other label, 6 Noncoding.  sample_off i64 [C + 1] as for dig_gene_row_keys; skip u8 [n_samples] or NULL: non-zero = a blacklisted
+ * sample, whose rows count nowhere.  L within [1, 2^31), C < 2^31.
+ *   dig_panel_row_keys: n_cds i64 [C] = rows of class != 6, and keys i64 [n]: a row of class 1, 2, 4 or 5 whose label has a panel
+ *     gets key = global sample << lb | label with lb the bits of L - 1 (DIG_EINVAL, before any launch, when the two fields do not
+ *     fit 63 bits); every other row, and a row outside the tables (the host twin refuses that one), gets key -1.
+ *   The caller sorts the keys ascending (as for dig_gene_counts).
+ *   dig_panel_counts, from the sorted keys, i64 [C, P] each: n_mut = counted rows per (cohort, panel), n_pairs = distinct (label,
+ *     sample) pairs, n_sample = distinct samples with a counted row in the panel.  Distinct samples: the head of a sample's first
+ *     (sample, label) run walks that sample's label runs and ORs their masks -- no scratch buffer, no size query, no second kernel.
+ *   Every output is zeroed by the call; integer atomics, so order-independent.  Alignment: that of the element types (8 bytes for
+ *   keys, sample_off and the outputs, 4 for label, sample, cohort and label_mask, 1 for annot and skip). */
+int dig_panel_row_keys(const int32_t *label, const int32_t *sample, const uint8_t *annot, const int32_t *cohort, const int64_t *sample_off,
+                       const uint8_t *skip, const uint32_t *label_mask, int64_t n, int64_t L, int64_t P, int64_t C, int64_t n_samples,
+                       int64_t *keys, int64_t *n_cds, void *stream);
+int dig_panel_row_keys_host(const int32_t *label, const int32_t *sample, const uint8_t *annot, const int32_t *cohort,
+                            const int64_t *sample_off, const uint8_t *skip, const uint32_t *label_mask, int64_t n, int64_t L, int64_t P,
+                            int64_t C, int64_t n_samples, int64_t *keys, int64_t *n_cds, int device);
+int dig_panel_counts(const int64_t *keys_sorted, int64_t n, const uint32_t *label_mask, const int64_t *sample_off, int64_t L, int64_t P,
+                     int64_t C, int64_t n_samples, int64_t *n_mut, int64_t *n_pairs, int64_t *n_sample, void *stream);
+int dig_panel_counts_host(const int64_t *keys_sorted, int64_t n, const uint32_t *label_mask, const int64_t *sample_off, int64_t L,
+                          int64_t P, int64_t C, int64_t n_samples, int64_t *n_mut, int64_t *n_pairs, int64_t *n_sample, int device);
 
 /* ---- the region model's training labels for many cohorts (additive: the ABI version stays) -------------------- *
  * scripts/DataExtractor.py:525-572 add_objectives without --cnv: mutation counts per window of the data container's `idx`.  The

@@ -5,7 +5,8 @@ Drop-in for the reference's scripts/DigDriver.py: the same four sub-commands wit
 arguments and option names (DigDriver.py:160-275), and the same output, a tab-separated
 ``<outdir>/<outpfx>.results.txt`` with header and index column (DigDriver.py:38-43,115-118); and `tileDriver`, which the
 reference does not have: the per-base scan of many cohorts, written as ``<outdir>/<outpfx>.hits.txt``; and `quickCohorts`,
-`quickDriver` for many cohorts in one pass, one ``<outdir>/<outpfx>.results.txt`` per cohort.  The statistics
+`quickDriver` for many cohorts in one pass, one ``<outdir>/<outpfx>.results.txt`` per cohort; and `targetCohorts` and
+`geneCohorts`, the same for `targetDriver` and `geneDriver`.  The statistics
 run through libdig_hip.so; `model` may be the reference's HDF5 map (`*.h5`, read by io/h5lite.py +
 io/pandas_fixed.py: no h5py or PyTables needed) or the directory mirror described in digdriver_amd/io/mapfile.py.
 """
@@ -127,6 +128,48 @@ def cmd_quick_cohorts(args):
         region_str=args.region_str, scale_factors=factors, scale_type=args.scale_type, scale_by_expectation=args.scale_by_expectation,
         max_muts_per_sample=args.max_muts_per_sample, max_muts_per_elt_per_sample=args.max_muts_per_elt_per_sample,
         skip_pvals=args.skip_pvals)
+    for path in paths:
+        print('\tSaved results to {}'.format(path))
+
+
+def _cohort_lists(args):
+    n = len(args.mutation_files)
+    if not len(args.maps) == len(args.outpfx) == n:
+        raise SystemExit("ERROR: --mutation-files, --maps and --outpfx must name the same number of cohorts.")
+    if args.scale_factor_manual and len(args.scale_factor_manual) != n:
+        raise SystemExit("ERROR: --scale-factor-manual takes one value per cohort.")
+    return n
+
+
+def cmd_target_cohorts(args):
+    """targetCohorts: targetDriver for many cohorts in one pass; per cohort <outdir>/<outpfx>.results.txt."""
+    _use_panel_dir(args)
+    n = _cohort_lists(args)
+    from digdriver_amd.driver_model import cohort_batch
+    print('Running MSK-IMPACT driver detection for {} cohorts'.format(n))
+    _, paths = cohort_batch.run_and_write_target_cohorts(
+        args.mutation_files, args.maps, args.outdir, args.outpfx, scale_by_sample=args.scale_by_samples, panel=args.panel,
+        max_muts_per_sample=args.max_muts_per_sample, max_muts_per_gene_per_sample=args.max_muts_per_gene_per_sample,
+        cgc_genes=args.cgc_genes, scale_factors=args.scale_factor_manual, drop_synonymous=False)
+    for path in paths:
+        print('\tSaved results to {}'.format(path))
+
+
+def cmd_gene_cohorts(args):
+    """geneCohorts: geneDriver for many cohorts in one pass; per cohort <outdir>/<outpfx>.results.txt.  Scale rules: the expected
+    synonymous count (the default) or manual factors, as cohort_batch.run_gene_cohorts takes them."""
+    _use_panel_dir(args)
+    n = _cohort_lists(args)
+    if args.scale_by_samples or not (args.scale_by_expectation or args.scale_factor_manual):
+        raise SystemExit("ERROR: geneCohorts scales by expected synonymous mutations or by --scale-factor-manual; the sample and "
+                         "mutation-count ratios are geneDriver's.")
+    from digdriver_amd.driver_model import cohort_batch
+    print('Running gene driver detection for {} cohorts'.format(n))
+    _, paths = cohort_batch.run_and_write_gene_cohorts(
+        args.mutation_files, args.maps, args.outdir, args.outpfx, pval_burden_nb=args.pval_burden,
+        max_muts_per_sample=args.max_muts_per_sample, max_muts_per_gene_per_sample=args.max_muts_per_gene_per_sample,
+        scale_factors=args.scale_factor_manual, scale_by_expectation=args.scale_by_expectation, cgc_genes=args.cgc_genes,
+        selection=args.selection, pval_burden_dnds=args.pval_burden_dnds, pval_sel=args.pval_sel)
     for path in paths:
         print('\tSaved results to {}'.format(path))
 
@@ -276,6 +319,38 @@ def parse_args(text=None):
     q.add_argument('--skip_pvals', default=False, action='store_true', help='expected counts only')
     q.add_argument('--panel-dir', type=str, default=None, help='directory holding the gene panel files genes_<NAME>.txt')
     q.set_defaults(func=cmd_quick_cohorts)
+
+    def cohort_lists(p):
+        p.add_argument('--mutation-files', type=str, nargs='+', required=True, help='one annotated mutation file per cohort')
+        p.add_argument('--maps', type=str, nargs='+', required=True, help='one pretrained mutation map per cohort, all with one gene index')
+        p.add_argument('--outdir', type=str, required=True, help='directory for the results files')
+        p.add_argument('--outpfx', type=str, nargs='+', required=True, help='one prefix per cohort: <outpfx>.results.txt')
+        p.add_argument('--max-muts-per-sample', type=int, default=3e9, help='drop samples with more mutations than this')
+        p.add_argument('--max-muts-per-gene-per-sample', type=int, default=3e9, help='cap of mutations one sample adds to a gene')
+        p.add_argument('--scale-by-samples', action='store_true', default=False, help='scale by the number of samples')
+        p.add_argument('--scale-factor-manual', default=None, type=float, nargs='+', help='use these scale factors, one per cohort')
+        p.add_argument('--cgc-genes', choices=CGC_SETS, default=False, help='restrict to a Cancer Gene Census set')
+        p.add_argument('--panel-dir', type=str, default=None, help='directory holding the gene panel files genes_<NAME>.txt')
+
+    # not a reference sub-command: targetDriver for many cohorts at once (driver_model/cohort_batch.py run_target_cohorts)
+    tc = sub.add_parser('targetCohorts', help='targetDriver for many cohorts: the genes of a targeted sequencing panel')
+    cohort_lists(tc)
+    tc.add_argument('--panel', type=str, choices=PANELS, help='gene panel')
+    tc.set_defaults(func=cmd_target_cohorts)
+
+    # not a reference sub-command: geneDriver for many cohorts at once (driver_model/cohort_batch.py run_gene_cohorts)
+    gc = sub.add_parser('geneCohorts', help='geneDriver for many cohorts: every gene of every cohort')
+    cohort_lists(gc)
+    gc.add_argument('--scale-by-mutations', action='store_false', default=True, dest="scale_by_expectation",
+                    help='with --scale-factor-manual: use the manual factors instead of expected synonymous mutations')
+    gc.add_argument('--no-pval-burden', dest='pval_burden', action='store_false', default=True, help='skip the burden p-values')
+    gc.add_argument('--selection', action='store_true', default=False,
+                    help='add the dN/dS-corrected expectations, their burden p-values and the selection p-values')
+    gc.add_argument('--no-pval-burden-dnds', dest='pval_burden_dnds', action='store_false', default=True,
+                    help='with --selection: skip the dN/dS-corrected burden p-values')
+    gc.add_argument('--no-pval-sel', dest='pval_sel', action='store_false', default=True,
+                    help='with --selection: skip the selection p-values')
+    gc.set_defaults(func=cmd_gene_cohorts)
 
     return parser.parse_args(text.split()) if text else parser.parse_args()
 

@@ -5,6 +5,7 @@ Drop-in for the sub-commands of the reference's scripts/DigPretrain.py (:280-477
 
     regionModel     k-fold CNN+GP results -> idx, mappability, region_params (+ mutation counts)   (:31-100)
     countMutations  cohort-level mutation counts stored as attributes                               (:102-177)
+    countMutationsCohorts  the same for many cohorts in one pass, one map per mutation file (not in the reference)
     sequenceModel   sequence_model_192 / sequence_model_64                                          (:179-208)
     sequenceModels  the same for many cohorts in one pass, one map per mutation file (not in the reference)
     genicModel      genic_model frame                                                               (:226-237)
@@ -80,6 +81,22 @@ def count_training_mutations(args):
         if panel == 'MSK_230':
             attrs['N_SAMPLE_MSK_230'] = int(len(sub.SAMPLE.unique()))
     mapfile.write_attrs(args.outputFile, **attrs)
+
+
+def count_training_mutations_cohorts(args):
+    """countMutations for many cohorts: one parse per file and one counting call for all cohorts and panels (libdig_hip.so through
+    the `_host` entry points: no torch), the attributes written into one map per mutation file."""
+    if len(args.fmuts) != len(args.maps):
+        raise SystemExit("--mutation-files and --maps: one map per mutation file ({} files, {} maps)".format(len(args.fmuts), len(args.maps)))
+    from digdriver_amd import _lib
+    _lib.TORCH_FREE = True
+    _lib.prewarm_in_background()                # (the HIP runtime starts while the files are parsed)
+    from digdriver_amd.driver_model import cohort_batch
+    print('Adding mutation counts of {} cohorts...'.format(len(args.fmuts)))
+    try:
+        cohort_batch.count_cohort_mutations(args.fmuts, args.maps, write=True, device=None)
+    except ValueError as exc:
+        raise SystemExit(str(exc))
 
 
 def pretrain_sequence_model(args):
@@ -169,6 +186,12 @@ def parse_args(text=None):
     a1.add_argument('--mutation-file', required=True, type=str, dest='fmut', help='mutation file')
     a1.set_defaults(func=count_training_mutations)
 
+    # not a reference sub-command: countMutations for many cohorts at once (driver_model/cohort_batch.py count_cohort_mutations)
+    a2 = sub.add_parser('countMutationsCohorts', help='store the mutation counts of many cohorts, one map per mutation file')
+    a2.add_argument('--mutation-files', required=True, nargs='+', dest='fmuts', help='annotated mutation files, one per cohort')
+    a2.add_argument('--maps', required=True, nargs='+', help='mutation maps to write into, one per mutation file')
+    a2.set_defaults(func=count_training_mutations_cohorts)
+
     b = sub.add_parser('sequenceModel', help='trinucleotide sequence model from genome counts + mutations')
     b.add_argument('fmut', help='annotated mutation file')
     b.add_argument('genome_counts', help='genome-wide context counts container')
@@ -217,7 +240,8 @@ def main(text=None):
         _lib.TORCH_FREE = True
         _lib.prewarm_in_background()            # (the HIP runtime starts while pandas is imported and the files are parsed)
     cli.func(cli)
-    if os.environ.get("DIG_CLI_ASSERT_NO_TORCH") == "1" and cli.func in (pretrain_nonc_model, pretrain_sequence_models):
+    if os.environ.get("DIG_CLI_ASSERT_NO_TORCH") == "1" and cli.func in (pretrain_nonc_model, pretrain_sequence_models,
+                                                                      count_training_mutations_cohorts):
         assert "torch" not in sys.modules, "a torch-free sub-command imported torch"
 
 
