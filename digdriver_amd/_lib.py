@@ -104,6 +104,10 @@ _SIGNATURES = {
     "dig_tile_select_count_host": [_vp] * 3 + [_i64] * 3 + [_vp, _int],
     "dig_tile_select_fill": [_vp] * 3 + [_i64] * 3 + [_vp, _i64] + [_vp] * 9 + [_vp],
     "dig_tile_select_fill_host": [_vp] * 3 + [_i64] * 3 + [_vp, _i64] + [_vp] * 9 + [_int],
+    "dig_tile_sample_keys": [_vp, _vp, _i64, _vp, _i64] + [_vp] * 5 + [_int] + [_i64] * 4 + [_vp, _vp],
+    "dig_tile_sample_keys_host": [_vp, _vp, _i64, _vp, _i64] + [_vp] * 5 + [_int] + [_i64] * 4 + [_vp, _int],
+    "dig_tile_sample_counts": [_vp] + [_i64] * 6 + [_vp, _vp, _vp],
+    "dig_tile_sample_counts_host": [_vp] + [_i64] * 6 + [_vp, _vp, _int],
     "dig_gene_pipeline": [_vp] * 15 + [_int] + [_vp] * 9 + [_i64, _i64, _i64, _vp, _i64, _vp],
     "dig_gene_pipeline_host": [_vp] * 15 + [_int] + [_vp] * 9 + [_i64, _i64, _i64, _int],
     "dig_count_contexts": [_vp, _i64, _vp, _vp, _int, _vp, _vp, _vp, _vp, _i64, _vp, _vp],

@@ -852,6 +852,45 @@ int dig_tile_mut_counts_host(const int32_t* pair_mut, const int32_t* pair_reg, i
                    st.in(mut_cohort, n_mut), st.in(first_pos, R), st.in(n_valid, R), binsize, n_tiles, R, C, st.out(k, n), nullptr);
 }
 
+int dig_tile_sample_keys_host(const int32_t* pair_mut, const int32_t* pair_reg, int64_t n_pairs, const int64_t* mut_start, int64_t n_mut,
+                              const int32_t* mut_cohort, const int32_t* mut_sample, const uint8_t* keep, const int64_t* first_pos,
+                              const int32_t* n_valid, int binsize, int64_t n_tiles, int64_t R, int64_t C, int64_t n_samples,
+                              int64_t* keys, int device)
+{
+    DIG_REQUIRE(n_pairs >= 0 && n_mut >= 0 && binsize >= 1, "n_pairs, n_mut >= 0, binsize >= 1");
+    int sb = 0;
+    if (int rc = tile_sample_key_layout(__func__, C, R, n_tiles, n_samples, &sb)) return rc;
+    if (n_pairs == 0) return DIG_OK;
+    DIG_REQUIRE(pair_mut && pair_reg && keys, "non-null pair arrays, keys");
+    DIG_REQUIRE(n_mut == 0 || (mut_start && mut_cohort && mut_sample), "non-null mutation arrays");
+    DIG_REQUIRE(R == 0 || (first_pos && n_valid), "non-null region tables");
+    for (int64_t i = 0; i < n_pairs; ++i)
+        DIG_REQUIRE(pair_mut[i] >= 0 && pair_mut[i] < n_mut && pair_reg[i] >= 0 && pair_reg[i] < R, "pairs inside the mutation / region tables");
+    for (int64_t m = 0; m < n_mut; ++m)
+        DIG_REQUIRE(mut_cohort[m] < 0 || mut_cohort[m] >= C || (mut_sample[m] >= 0 && mut_sample[m] < n_samples),
+                    "global sample within [0, n_samples) for every row of a cohort within [0, C)");
+    Staging st(device);
+    return st.call(dig_tile_sample_keys, st.in(pair_mut, n_pairs), st.in(pair_reg, n_pairs), n_pairs, st.in(mut_start, n_mut), n_mut,
+                   st.in(mut_cohort, n_mut), st.in(mut_sample, n_mut), st.in(keep, n_samples), st.in(first_pos, R), st.in(n_valid, R),
+                   binsize, n_tiles, R, C, n_samples, st.out(keys, n_pairs), nullptr);
+}
+
+int dig_tile_sample_counts_host(const int64_t* keys_sorted, int64_t n, int64_t C, int64_t R, int64_t n_tiles, int64_t n_samples,
+                                int64_t cap, int32_t* k_cap, int32_t* k_samples, int device)
+{
+    DIG_REQUIRE(n >= 0 && n <= INT32_MAX, "0 <= n < 2^31 (the counts are 32-bit)");
+    int sb = 0;
+    if (int rc = tile_sample_key_layout(__func__, C, R, n_tiles, n_samples, &sb)) return rc;
+    const size_t slots = (size_t)C * R * n_tiles;
+    if (slots == 0 || (!k_cap && !k_samples)) return DIG_OK;
+    DIG_REQUIRE(n == 0 || keys_sorted, "non-null keys");
+    if (int rc = check_ascending(__func__, keys_sorted, n)) return rc;
+    Staging st(device);
+    // (a plane that is NULL is not staged: the call skips it)
+    return st.call(dig_tile_sample_counts, st.in(keys_sorted, n), n, C, R, n_tiles, n_samples, cap, k_cap ? st.out(k_cap, slots) : nullptr,
+                   k_samples ? st.out(k_samples, slots) : nullptr, nullptr);
+}
+
 int dig_overlap_join_count_host(const int64_t* blk_start_key, const int64_t* blk_runmax_key, const int64_t* blk_end, int64_t n_blk,
                                 const int64_t* mut_chrom, const int64_t* mut_start, const int64_t* mut_end, int64_t n_mut,
                                 int32_t* counts, int device)

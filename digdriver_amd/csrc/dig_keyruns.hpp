@@ -1,4 +1,4 @@
-// dig_keyruns.hpp -- what the counting routes (dig_genecounts.hip, dig_objectives.hip, dig_panelcounts.hip, dig_seqcounts.hip, dig_sitematch.hip, dig_tilehits.hip) and their host twins share:
+// dig_keyruns.hpp -- what the counting routes (dig_genecounts.hip, dig_objectives.hip, dig_panelcounts.hip, dig_seqcounts.hip, dig_sitematch.hip, dig_tilehits.hip, dig_tilesamples.hip) and their host twins share:
 // rows encoded as 63-bit keys, sorted by the caller, counted as runs with one integer atomic per wave segment.
 #pragma once
 #include "dig_common.hpp"
@@ -36,6 +36,11 @@ int panel_key_layout(const char* fn, int64_t L, int64_t P, int64_t C, int64_t n_
 // dig_tilehits.hip: the sizes of a score plane [C, R, T]; DIG_EINVAL (in the name of entry point `fn`) unless C R < 2^31 and T < 2^31
 int tile_select_sizes(const char* fn, int64_t C, int64_t R, int64_t T);
 
+// dig_tilesamples.hip: the bits of the global-sample field of a tile-sample key, ((cohort R + region) T + tile) << bits | global sample
+// (bits for n_samples + 1 values: the all-ones key is no real one); DIG_EINVAL (in the name of entry point `fn`) when the two fields
+// do not fit 63 bits
+int tile_sample_key_layout(const char* fn, int64_t C, int64_t R, int64_t T, int64_t n_samples, int* sample_bits);
+
 // dig_seqcounts.hip: the most table rows K a call takes -- a workgroup's LDS counters, 12 KB: the penta-nucleotide table
 constexpr int kSeqMaxK = 3072;
 
@@ -64,6 +69,26 @@ __device__ __forceinline__ int segment_count(int64_t seg, bool flag)
     const int end = stop ? __ffsll((long long)stop) - 1 : 64;
     const unsigned long long mine = (end == 64 ? ~0ull : ((1ull << end) - 1)) & (above | (1ull << lane));
     return __popcll(flags & mine);
+}
+
+// segment_count with a value per lane: on the first lane of a segment the sum of `value` over the segment's lanes; on every other
+// lane 0.  A suffix sum in six shuffle steps that never crosses a segment's end.  Every lane of the wave must call it.
+__device__ __forceinline__ int segment_sum(int64_t seg, int value)
+{
+    const int lane = threadIdx.x & 63;
+    const int64_t left = __shfl_up((long long)seg, 1, 64);
+    const bool first = seg >= 0 && (lane == 0 || left != seg);
+    const unsigned long long firsts = __ballot(first), rows = __ballot(seg >= 0);
+    const unsigned long long above = lane == 63 ? 0ull : ~0ull << (lane + 1);
+    const unsigned long long stop = (firsts | ~rows) & above;
+    const int end = stop ? __ffsll((long long)stop) - 1 : 64;
+    int v = seg >= 0 ? value : 0;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const int other = __shfl_down(v, d, 64);      // after the step v covers the lanes [lane, min(lane + 2 d, end))
+        if (lane + d < end) v += other;
+    }
+    return first ? v : 0;
 }
 
 // first index in [lo, n) whose key is above v (keys ascending, keys[lo - 1] == v)

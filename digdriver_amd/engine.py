@@ -1200,12 +1200,8 @@ def tile_mut_counts(genome, chroms, starts, ends, first_pos, n_valid, mut_chrom,
     be = backend_of(first_pos, n_valid)
     first_pos, n_valid = be.arr(first_pos, "i64", (-1,)), be.arr(n_valid, "i32", (-1,))
     R = first_pos.shape[0]
-    order, start_key, runmax_key, blk_end = join_blocks(genome.chrom_index(chroms), _lib.as_host(starts, np.int64),
-                                                        _lib.as_host(ends, np.int64))
-    mc = be.arr(mut_chrom if is_cuda(mut_chrom) else genome.chrom_index(list(np.asarray(mut_chrom).astype(str))), "i64")
-    ms, me, co = be.arr(mut_start, "i64"), be.arr(mut_end, "i64"), be.arr(mut_cohort, "i32")
-    pm, pb = overlap_join(be, start_key, runmax_key, blk_end, mc, ms, me)
-    pr = be.arr(order, "i32")[pb.long() if be.is_device else pb]      # block of the sorted table -> region
+    pm, pr, ms = _tile_pairs(be, genome, chroms, starts, ends, mut_chrom, mut_start, mut_end)
+    co = be.arr(mut_cohort, "i32")
     k = be.empty((int(C), R, int(n_tiles)), "i32")
     p = be.ptr
     be.call("dig_tile_mut_counts", p(pm), p(pr), pm.shape[0], p(ms), *([] if be.is_device else [ms.shape[0]]), p(co), p(first_pos),
@@ -1213,16 +1209,81 @@ def tile_mut_counts(genome, chroms, starts, ends, first_pos, n_valid, mut_chrom,
     return k
 
 
+def _tile_pairs(be, genome, chroms, starts, ends, mut_chrom, mut_start, mut_end):
+    """The interval join of the per-base route: (pair_mut, pair_reg) i32, one entry per (mutation row, region) that overlap, and the
+    rows' START as the counting entry points read it."""
+    order, start_key, runmax_key, blk_end = join_blocks(genome.chrom_index(chroms), _lib.as_host(starts, np.int64),
+                                                        _lib.as_host(ends, np.int64))
+    mc = be.arr(mut_chrom if is_cuda(mut_chrom) else genome.chrom_index(list(np.asarray(mut_chrom).astype(str))), "i64")
+    ms, me = be.arr(mut_start, "i64"), be.arr(mut_end, "i64")
+    pm, pb = overlap_join(be, start_key, runmax_key, blk_end, mc, ms, me)
+    pr = be.arr(order, "i32")[pb.long() if be.is_device else pb]      # block of the sorted table -> region
+    return pm, pr, ms
+
+
+def tile_sample_counts(genome, chroms, starts, ends, first_pos, n_valid, mut_chrom, mut_start, mut_end, mut_cohort, mut_sample,
+                       sample_offsets, keep, cap, C, binsize, n_tiles):
+    """(k_cap, k_samples) i32 [C, R, n_tiles]: tile_mut_counts by sample -- with n the rows of one sample that tile_mut_counts counts
+    in a tile, k_cap = the sum over the kept samples of min(n, cap) and k_samples = the kept samples with n > 0: the same join,
+    dig_tile_sample_keys, a key sort, dig_tile_sample_counts.  mut_sample i32: the row's GLOBAL sample, inside its cohort's range of
+    sample_offsets [C + 1] (a cohort's first global sample; equal labels in two cohorts are two samples); keep u8 per global sample
+    or None: a sample with keep == 0 counts nowhere; cap: an integer >= 1, or None for no cap.  Everything else, and the choice of
+    the backend, as tile_mut_counts.  ValueError for a row whose sample is outside its cohort and for a key (cohort, region, tile,
+    sample) that does not fit 63 bits."""
+    be = backend_of(first_pos, n_valid)
+    first_pos, n_valid = be.arr(first_pos, "i64", (-1,)), be.arr(n_valid, "i32", (-1,))
+    R, C, T = first_pos.shape[0], int(C), int(n_tiles)
+    off_host, _, S = _sample_offsets(sample_offsets, C)
+    if cap is not None and (int(cap) != cap or cap < 1):
+        raise ValueError("cap: an integer >= 1 (None: no cap)")
+    co, sa = be.arr(mut_cohort, "i32", (-1,)), be.arr(mut_sample, "i32", (-1,))
+    keep = be.arr(keep, "u8", (-1,))
+    if keep is not None and keep.shape[0] != S:
+        raise ValueError("keep: one byte per global sample ({})".format(S))
+    if sa.shape[0] != co.shape[0]:
+        raise ValueError("mut_sample: one entry per mutation row")
+    if co.shape[0]:
+        # (a row of a cohort outside [0, C) counts nowhere, as in tile_mut_counts; every other row must name a sample of its cohort)
+        off, c = be.arr(off_host, "i64"), be.arr(co.clip(0, C - 1), "i64")
+        if bool(((co >= 0) & (co < C) & ((sa < off[c]) | (sa >= off[c + 1]))).any()):
+            raise ValueError("a row outside the tables: global sample within its cohort's range of sample_offsets")
+    pm, pr, ms = _tile_pairs(be, genome, chroms, starts, ends, mut_chrom, mut_start, mut_end)
+    if ms.shape[0] != co.shape[0]:
+        raise ValueError("mut_cohort, mut_sample: one entry per mutation row")
+    p = be.ptr
+    n = pm.shape[0]
+    keys = be.empty(n, "i64")
+    k_cap, k_samples = be.empty((C, R, T), "i32"), be.empty((C, R, T), "i32")
+    with _requirements_as_value_errors():
+        be.call("dig_tile_sample_keys", p(pm), p(pr), n, p(ms), ms.shape[0], p(co), p(sa), p(keep), p(first_pos), p(n_valid),
+                int(binsize), T, R, C, S, p(keys))
+        keys = _sorted(be, keys)
+        be.call("dig_tile_sample_counts", p(keys), n, C, R, T, S, 0 if cap is None else int(cap), p(k_cap), p(k_samples))
+    return k_cap, k_samples
+
+
 def tiled_nb_model(genome, chroms, starts, ends, s_prob, mu, sigma, mut_chrom, mut_start, mut_end, mut_cohort, binsize=50,
-                   device=0, on_device=True):
+                   device=0, on_device=True, mut_sample=None, sample_offsets=None, keep=None, cap=None, by_sample=False):
     """nb_model (nb_model.py:188-234) for C cohorts x R regions in three launches + the interval join:
     base_tile_probs -> tile_mut_counts -> tiled_nb_test.  mu, sigma: [C, R].  Returns a dict of device tensors (arrays with
-    on_device=False) pval, exp, pt [C, R, n_tiles], k i32 [C, R, n_tiles], first_pos [R], n_valid [R]."""
+    on_device=False) pval, exp, pt [C, R, n_tiles], k i32 [C, R, n_tiles], first_pos [R], n_valid [R].
+    mut_sample (with sample_offsets; keep, cap as tile_sample_counts takes them): the counts by sample -- k is then k_cap, and with
+    by_sample the dict also holds k_samples and pval_sample, the same test on k_samples."""
     pt, first, nval = base_tile_probs(genome, chroms, starts, ends, s_prob, binsize, device=device, on_device=on_device)
     C, R, n_tiles = pt.shape
-    k = tile_mut_counts(genome, chroms, starts, ends, first, nval, mut_chrom, mut_start, mut_end, mut_cohort, C, binsize, n_tiles)
+    if mut_sample is None:
+        if sample_offsets is not None or keep is not None or cap is not None or by_sample:
+            raise ValueError("sample_offsets, keep, cap and by_sample need mut_sample")
+        k = tile_mut_counts(genome, chroms, starts, ends, first, nval, mut_chrom, mut_start, mut_end, mut_cohort, C, binsize, n_tiles)
+        pval, ex = tiled_nb_test(pt, k, mu, sigma, device=device)
+        return dict(pval=pval, exp=ex, pt=pt, k=k, first_pos=first, n_valid=nval)
+    k, k_samples = tile_sample_counts(genome, chroms, starts, ends, first, nval, mut_chrom, mut_start, mut_end, mut_cohort, mut_sample,
+                                      sample_offsets, keep, cap, C, binsize, n_tiles)
     pval, ex = tiled_nb_test(pt, k, mu, sigma, device=device)
-    return dict(pval=pval, exp=ex, pt=pt, k=k, first_pos=first, n_valid=nval)
+    res = dict(pval=pval, exp=ex, pt=pt, k=k, first_pos=first, n_valid=nval)
+    if by_sample:
+        res["k_samples"], res["pval_sample"] = k_samples, tiled_nb_test(pt, k_samples, mu, sigma, device=device)[0]
+    return res
 
 
 def _tile_counts(be, score, n_valid, cut):

@@ -360,7 +360,10 @@ class ShardedTiles:
     single-process frame order) and every rank keeps the q-values of its own tiles."""
 
     def __init__(self, genome, chroms, starts, ends, s_prob, mu, sigma, mut_chrom, mut_start, mut_end, mut_cohort, binsize,
-                 device, rank, world, group=None):
+                 device, rank, world, group=None, mut_sample=None, sample_offsets=None, keep=None, cap=None, by_sample=False):
+        if mut_sample is not None or sample_offsets is not None or keep is not None or cap is not None or by_sample:
+            raise NotImplementedError("ShardedTiles counts rows (dig_tile_mut_counts): the counts by sample of engine.tiled_nb_model "
+                                      "(mut_sample, sample_offsets, keep, cap, by_sample) run on one device")
         self.rank, self.world, self.group, self.device, self.binsize = int(rank), int(world), group, device, int(binsize)
         chroms = np.asarray([str(c) for c in chroms])
         starts, ends = np.asarray(starts, np.int64), np.asarray(ends, np.int64)

@@ -98,52 +98,134 @@ def _s_prob_table(d_pr, n_up=1, collapse=False):
             exc, n_up, ", collapse=True" if collapse else "", "C- and T-centred " if collapse else "", 2 * n_up + 1)) from exc
 
 
-def _mutation_rows(f_mut):
+def _mutation_rows(f_mut, samples=False):
     """The rows a tabix fetch hands to tabix_to_dataframe (nb_model.py:13-33): CHROM, START, END of a bed-like mutation
-    file (plain or gzip; 6-9 columns)."""
+    file (plain or gzip; 6-9 columns).  samples=True: column 6 as well, the row's sample label ID (as a string, nothing read as a
+    missing value); ValueError for a file with fewer than 6 columns."""
     import pandas as pd
-    df = pd.read_csv(f_mut, sep="\t", header=None, usecols=[0, 1, 2], names=["CHROM", "START", "END"], dtype={0: str},
-                     comment="#", low_memory=False)
+    if not samples:
+        df = pd.read_csv(f_mut, sep="\t", header=None, usecols=[0, 1, 2], names=["CHROM", "START", "END"], dtype={0: str},
+                         comment="#", low_memory=False)
+    else:
+        try:
+            df = pd.read_csv(f_mut, sep="\t", header=None, usecols=[0, 1, 2, 5], dtype={0: str, 5: str}, comment="#", low_memory=False,
+                             keep_default_na=False)
+        except (ValueError, pd.errors.ParserError) as exc:
+            raise ValueError("{}: the sample options read the sample label from column 6, and the file has fewer than 6 "
+                             "columns ({})".format(f_mut, exc)) from exc
+        df.columns = ["CHROM", "START", "END", "ID"]
     df["CHROM"] = df.CHROM.str.replace("chr", "", regex=False)
     return df
 
 
-def nb_model(d_pr, idx, mu_lst, sigma_lst, f_tabix, f_fasta, n_up=2, n_down=2, binsize=50, collapse=False, device=0):
+def _sample_ids(muts, what):
+    """The sample labels of a cohort's counted rows -> (dense ids int32 per row, the labels in id order).  ValueError for a frame
+    without the column ID or a row with an empty label."""
+    if "ID" not in muts.columns:
+        raise ValueError("{}: the sample options need the sample label of every row (column ID, column 6 of a file)".format(what))
+    lab = muts.ID
+    empty = lab.isna() | (lab.astype(str).str.strip() == "")
+    if bool(empty.any()):
+        raise ValueError("{}: {} rows without a sample label in column 6".format(what, int(empty.sum())))
+    names, ids = np.unique(lab.astype(str).values, return_inverse=True)
+    return ids.astype(np.int32).reshape(-1), list(names)
+
+
+def sample_keep(n_rows, max_muts_per_sample):
+    """keep u8 [S] of --max-muts-per-sample: a sample stays unless its rows (n_rows [S], counted over the cohort's file after the
+    "chromosome known to the genome" filter) number MORE than max_muts_per_sample.  None: every sample stays."""
+    n_rows = np.asarray(n_rows)
+    if max_muts_per_sample is None:
+        return np.ones(len(n_rows), np.uint8)
+    return (n_rows <= max_muts_per_sample).astype(np.uint8)
+
+
+def _cohort_rows(f_muts, known, samples, max_muts_per_sample=None):
+    """The rows of C mutation files or frames on the chromosomes `known`, as the records cohort_rows stacks: chrom, start, end and,
+    with samples, sample (dense per cohort), sample_names and keep (sample_keep of the cohort's own row counts)."""
+    import pandas as pd
+    rows = []
+    for c, f in enumerate(f_muts):
+        m = f if isinstance(f, pd.DataFrame) else _mutation_rows(f, samples)
+        m = m[m.CHROM.astype(str).str.replace("chr", "", regex=False).isin(known)]
+        rec = dict(chrom=m.CHROM.astype(str).values, start=m.START.values, end=m.END.values)
+        if samples:
+            rec["sample"], rec["sample_names"] = _sample_ids(m, f if isinstance(f, str) else "cohort %d" % c)
+            rec["keep"] = sample_keep(np.bincount(rec["sample"], minlength=len(rec["sample_names"])), max_muts_per_sample)
+        rows.append(rec)
+    return rows
+
+
+def _sample_arguments(rows, max_muts_per_tile_per_sample, by_sample):
+    """The keywords engine.tiled_nb_model takes for the counts by sample, from the records of _cohort_rows(samples=True)."""
+    from ..data_tools import cohort_rows
+    off = cohort_rows.sample_offsets(rows)
+    return dict(mut_sample=cohort_rows.column(rows, "sample", "i32", shift=off), sample_offsets=off,
+                keep=cohort_rows.column(rows, "keep", "u8"), cap=max_muts_per_tile_per_sample, by_sample=by_sample)
+
+
+def _check_sample_options(max_muts_per_sample, max_muts_per_tile_per_sample, by_sample, cut_on="PVAL"):
+    """True when any sample option is set (the reader then takes column 6); ValueError for values outside their domains."""
+    if max_muts_per_sample is not None and max_muts_per_sample < 0:
+        raise ValueError("max_muts_per_sample: a number >= 0")
+    cap = max_muts_per_tile_per_sample
+    if cap is not None and (int(cap) != cap or cap < 1):
+        raise ValueError("max_muts_per_tile_per_sample: an integer >= 1")
+    if cut_on not in ("PVAL", "PVAL_SAMPLE"):
+        raise ValueError("cut_on: PVAL or PVAL_SAMPLE")
+    if cut_on == "PVAL_SAMPLE" and not by_sample:
+        raise ValueError("cut_on PVAL_SAMPLE requires by_sample")
+    return max_muts_per_sample is not None or cap is not None or bool(by_sample)
+
+
+def nb_model(d_pr, idx, mu_lst, sigma_lst, f_tabix, f_fasta, n_up=2, n_down=2, binsize=50, collapse=False, device=0,
+             max_muts_per_sample=None, max_muts_per_tile_per_sample=None, by_sample=False):
     """nb_model.py:188-234: the tiled NB test over the bins `idx` [(chrom, start, end)] of one cohort; returns the
     reference's frame (CHROM, POS, OBS, EXP, PVAL, Pi, MU, SIGMA, REGION; numeric columns as float, as its np.hstack makes
     them).  `f_tabix`: the cohort's bed-like mutation file (the reference reads it through tabix; here it is joined on the
     GPU in one pass); `f_fasta`: the genome (data_tools.genome.PackedGenome or a FASTA path).  All bins in three launches
     (engine.tiled_nb_model).  n_up = n_down = 2 (penta-nucleotide contexts, the reference's default) or 1 (the trinucleotide
     models every live part of the pipeline trains); collapse=True: S_prob keyed by the pyrimidine-centred contexts (the
-    96-substitution model), windows centred on a purine looked up as their reverse complement."""
+    96-substitution model), windows centred on a purine looked up as their reverse complement.
+    The sample options (not in the reference; DESIGN.md "Samples in the per-base route") read the sample label from column 6 (ID):
+    max_muts_per_sample drops the samples with more rows in the file than that; max_muts_per_tile_per_sample caps what one sample
+    adds to a tile's OBS; by_sample adds two columns behind REGION: OBS_SAMPLES (the kept samples with a row in the tile) and
+    PVAL_SAMPLE (the same test on OBS_SAMPLES).  Without them the frame, the launches and the columns read are those of today."""
     import pandas as pd
     from .. import engine
     from ..data_tools import genome as genome_mod
     if n_up != n_down or n_up not in (1, 2):
         raise NotImplementedError("the tile kernels take n_up = n_down = 1 or 2")
+    samples = _check_sample_options(max_muts_per_sample, max_muts_per_tile_per_sample, by_sample)
     g = f_fasta if isinstance(f_fasta, genome_mod.PackedGenome) else genome_mod.PackedGenome.from_fasta(f_fasta)
     idx = np.asarray(idx)
     chroms = [str(c) for c in idx[:, 0]]
     starts, ends = idx[:, 1].astype(np.int64), idx[:, 2].astype(np.int64)
-    muts = f_tabix if isinstance(f_tabix, pd.DataFrame) else _mutation_rows(f_tabix)
     known = set(n.replace("chr", "") for n in g.names)
-    muts = muts[muts.CHROM.astype(str).str.replace("chr", "", regex=False).isin(known)]
+    rows = _cohort_rows([f_tabix], known, samples, max_muts_per_sample)
+    extra = _sample_arguments(rows, max_muts_per_tile_per_sample, by_sample) if samples else {}
+    m = rows[0]
     res = engine.tiled_nb_model(g, chroms, starts, ends, _s_prob_table(d_pr, n_up, collapse)[None, :], np.asarray(mu_lst, float)[None, :],
-                                np.asarray(sigma_lst, float)[None, :], muts.CHROM.astype(str).values, muts.START.values,
-                                muts.END.values, np.zeros(len(muts), np.int32), binsize=binsize, device=device)
+                                np.asarray(sigma_lst, float)[None, :], m["chrom"], m["start"], m["end"],
+                                np.zeros(len(m["start"]), np.int32), binsize=binsize, device=device, **extra)
     host = {k: v.cpu().numpy() for k, v in res.items()}
     first, nval = host["first_pos"], host["n_valid"].astype(np.int64)
+    columns = _TILE_COLUMNS + (_SAMPLE_COLUMNS if by_sample else [])
     if len(idx) == 0 or nval.sum() == 0:
-        return pd.DataFrame(columns=_TILE_COLUMNS)
+        return pd.DataFrame(columns=columns)
     # all regions at once (the reference appends one block per region): region of every tile, tile number inside it
     reg = np.repeat(np.arange(len(idx)), nval)
     t = np.arange(nval.sum()) - np.repeat(np.cumsum(nval) - nval, nval)
     take = lambda a: a[0][reg, t]
-    return _tile_frame(idx, mu_lst, sigma_lst, first, _region_positions(g, chroms, ends, first, n_up), binsize, reg, t,
-                       take(host["k"]), take(host["exp"]), take(host["pval"]), take(host["pt"]))
+    df = _tile_frame(idx, mu_lst, sigma_lst, first, _region_positions(g, chroms, ends, first, n_up), binsize, reg, t,
+                     take(host["k"]), take(host["exp"]), take(host["pval"]), take(host["pt"]))
+    if by_sample:
+        df["OBS_SAMPLES"], df["PVAL_SAMPLE"] = take(host["k_samples"]).astype(float), take(host["pval_sample"])
+    return df
 
 
 _TILE_COLUMNS = ["CHROM", "POS", "OBS", "EXP", "PVAL", "Pi", "MU", "SIGMA", "REGION"]
+_SAMPLE_COLUMNS = ["OBS_SAMPLES", "PVAL_SAMPLE"]      # behind the reference's columns, in front of QVAL; only with by_sample
 
 
 def _region_positions(g, chroms, ends, first, n_up):
@@ -213,7 +295,7 @@ def _fdr_cuts(pval, n_valid, fdr):
 
 
 def nb_model_hits(d_prs, idx, mu, sigma, f_muts, f_fasta, n_up=2, n_down=2, binsize=50, collapse=False, pval_max=None, fdr=None,
-                  device=0):
+                  device=0, max_muts_per_sample=None, max_muts_per_tile_per_sample=None, by_sample=False, cut_on="PVAL"):
     """The rows of nb_model's frame that pass a cut, for C cohorts on one bin grid, without building the frame: frame c equals
     nb_model(d_prs[c], idx, mu[c], sigma[c], f_muts[c], ...) filtered by PVAL <= pval_max, or by q <= fdr -- bit for bit, in
     order, with the rows' numbers in that full frame as the (int64) index.  Exactly one of pval_max / fdr.
@@ -223,11 +305,15 @@ def nb_model_hits(d_prs, idx, mu, sigma, f_muts, f_fasta, n_up=2, n_down=2, bins
     d_prs: C S_prob mappings; mu, sigma [C, R]; f_muts: C bed-like mutation files or frames (as nb_model's f_tabix).
     One engine.tiled_nb_model call over all cohorts, the selection (engine.tile_select) on the device; only the hits come back.
     The four planes take 28 bytes per (tile, cohort), fdr adds 8 for the lists and the sort's workspace; regions are NOT chunked:
-    the caller passes as many regions as fit.  frame.attrs holds n_testable and n_tiles of the cohort."""
+    the caller passes as many regions as fit.  frame.attrs holds n_testable and n_tiles of the cohort.
+    The sample options as nb_model takes them; cut_on: the score that pval_max / fdr select on, PVAL or (with by_sample) PVAL_SAMPLE
+    -- the testable tiles, the Benjamini-Hochberg pass, QVAL and n_testable then belong to that score.  OBS_SAMPLES and PVAL_SAMPLE
+    stand behind REGION, in front of QVAL."""
     if (pval_max is None) == (fdr is None):
         raise ValueError("exactly one of pval_max and fdr must be given")
     if n_up != n_down or n_up not in (1, 2):
         raise NotImplementedError("the tile kernels take n_up = n_down = 1 or 2")
+    samples = _check_sample_options(max_muts_per_sample, max_muts_per_tile_per_sample, by_sample, cut_on)
     import pandas as pd
     from .. import engine
     from ..data_tools import cohort_rows, genome as genome_mod
@@ -242,24 +328,28 @@ def nb_model_hits(d_prs, idx, mu, sigma, f_muts, f_fasta, n_up=2, n_down=2, bins
     chroms = [str(c) for c in idx[:, 0]] if R else []
     starts, ends = (idx[:, 1].astype(np.int64), idx[:, 2].astype(np.int64)) if R else (np.zeros(0, np.int64),) * 2
     known = set(n.replace("chr", "") for n in g.names)
-    rows = []
-    for f in f_muts:
-        m = f if isinstance(f, pd.DataFrame) else _mutation_rows(f)
-        m = m[m.CHROM.astype(str).str.replace("chr", "", regex=False).isin(known)]
-        rows.append(dict(chrom=m.CHROM.astype(str).values, start=m.START.values, end=m.END.values))
+    rows = _cohort_rows(f_muts, known, samples, max_muts_per_sample)
+    extra = _sample_arguments(rows, max_muts_per_tile_per_sample, by_sample) if samples else {}
     mc, ms, me = cohort_rows.column(rows, "chrom"), cohort_rows.column(rows, "start", "i64"), cohort_rows.column(rows, "end", "i64")
     co = cohort_rows.cohort_column(rows, "start")
     s_prob = np.stack([_s_prob_table(d, n_up, collapse) for d in d_prs])
-    res = engine.tiled_nb_model(g, chroms, starts, ends, s_prob, mu, sigma, mc, ms, me, co, binsize=binsize, device=device)
+    res = engine.tiled_nb_model(g, chroms, starts, ends, s_prob, mu, sigma, mc, ms, me, co, binsize=binsize, device=device, **extra)
     nval_dev = res["n_valid"]
+    score = res["pval_sample" if cut_on == "PVAL_SAMPLE" else "pval"]
     if fdr is not None:
-        cuts, n_test = _fdr_cuts(res["pval"], nval_dev, fdr)
+        cuts, n_test = _fdr_cuts(score, nval_dev, fdr)
     else:
         cuts = np.full(C, float(pval_max))
-        n_test = engine.tile_select_counts(res["pval"], nval_dev, float("inf")).sum(dim=1).cpu().numpy()
-    hits = engine.tile_select(res["pval"], nval_dev, cuts, pt=res["pt"], exp=res["exp"], k=res["k"])
+        n_test = engine.tile_select_counts(score, nval_dev, float("inf")).sum(dim=1).cpu().numpy()
+    hits = engine.tile_select(score, nval_dev, cuts, pt=res["pt"], exp=res["exp"], k=res["k"])
     ptr = hits.pop("cohort_ptr")
+    if by_sample:
+        # the planes tile_select does not gather, taken at the hits' (cohort, region, tile) (not a hot path: the hits are few)
+        import torch
+        at = (torch.as_tensor(np.repeat(np.arange(C), np.diff(ptr)), device=score.device), hits["region"].long(), hits["tile"].long())
+        hits.update(pval=res["pval"][at], k_samples=res["k_samples"][at], pval_sample=res["pval_sample"][at])
     hits = {k: v.cpu().numpy() for k, v in hits.items()}
+    hits.setdefault("pval", hits["score"])                     # (without by_sample the score is PVAL)
     first, nval = res["first_pos"].cpu().numpy(), np.maximum(res["n_valid"].cpu().numpy().astype(np.int64), 0)
     n_pos = _region_positions(g, chroms, ends, first, n_up) if R else np.zeros(0, np.int64)
     row0 = np.cumsum(nval) - nval                              # a region's first row in the full frame
@@ -267,8 +357,10 @@ def nb_model_hits(d_prs, idx, mu, sigma, f_muts, f_fasta, n_up=2, n_down=2, bins
     for c in range(C):
         sel = slice(int(ptr[c]), int(ptr[c + 1]))
         reg, t = hits["region"][sel].astype(np.int64), hits["tile"][sel].astype(np.int64)
-        df = _tile_frame(idx, mu[c], sigma[c], first, n_pos, binsize, reg, t, hits["k"][sel], hits["exp"][sel], hits["score"][sel],
+        df = _tile_frame(idx, mu[c], sigma[c], first, n_pos, binsize, reg, t, hits["k"][sel], hits["exp"][sel], hits["pval"][sel],
                          hits["pt"][sel])
+        if by_sample:
+            df["OBS_SAMPLES"], df["PVAL_SAMPLE"] = hits["k_samples"][sel].astype(float), hits["pval_sample"][sel]
         if fdr is not None:
             df["QVAL"] = hits_q_values(hits["score"][sel], int(n_test[c]))
         df.index = pd.Index(row0[reg] + t, dtype=np.int64)

@@ -40,7 +40,8 @@ extern "C" {
                              * 7: + dig_mutation_file_*_host; 8: + dig_stage_timer_*; 9: + DIG_PIPE_RECORDS, dig_element_records_*;
                              * 12 (round 6): + dig_sort_rows, dig_bh_qvalues_ragged; - dig_element_pipeline_scaled*, dig_element_pipeline_pack_counts /
                              * DIG_PIPE_PACKED_COUNTS (round 5's measured losers: tools/rejected/r05_*.patch); still 12: + dig_panel_row_keys,
-                             * dig_panel_counts and their _host twins (additions) */
+                             * dig_panel_counts and their _host twins (additions); + dig_tile_sample_keys, dig_tile_sample_counts and
+                             * their _host twins (additions) */
 
 /* dtype codes for dig_gather_bins */
 #define DIG_F32 0
@@ -491,6 +492,38 @@ int dig_tile_select_fill_host(const double *score, const int32_t *n_valid, const
                               const int64_t *offsets, int64_t total, const double *pt, const double *exp_in, const int32_t *k,
                               int32_t *hit_region, int32_t *hit_tile, double *hit_score, double *hit_pt, double *hit_exp,
                               int32_t *hit_k, int device);
+
+/* ---- the per-base route's counts by sample for many cohorts (additive: the ABI version stays) ------------------- *
+ * dig_tile_mut_counts counts rows, whoever they belong to.  These two entry points count them per sample: with n(c, r, t, s) the
+ * rows of GLOBAL sample s that dig_tile_mut_counts would count in tile (c, r, t) -- the same pairs, the same skip rules --
+ *   k_cap[c, r, t]     = sum over the kept samples of min(n, cap)     (cap <= 0: no cap)
+ *   k_samples[c, r, t] = the kept samples with n > 0
+ * i32 [C, R, n_tiles] each.  mut_sample i32 [n_mut]: the row's global sample (the samples of all cohorts numbered as one list of
+ * n_samples; equal labels in two cohorts are two samples); keep u8 [n_samples] or NULL: a sample with keep == 0 counts nowhere.
+ *   dig_tile_sample_keys: keys i64 [n_pairs], one per (mutation, region) pair of dig_overlap_join_count/fill:
+ *     (((cohort R + region) n_tiles + tile) << sb) | global sample, sb = the bits that hold the values 0 .. n_samples; a pair that
+ *     counts nowhere (START in front of the region, tile at or past n_valid[region] or n_tiles, cohort outside [0, C), sample outside
+ *     [0, n_samples) or not kept, pair outside the tables) gets the all-ones 63-bit key INT64_MAX, which sorts behind every real one.
+ *   The caller sorts the keys ascending.
+ *   dig_tile_sample_counts: a run of equal keys is one (tile, sample) with n = its length; both planes are zeroed by the call, either
+ *     may be NULL and is then skipped.  Negative keys, the all-ones key and keys of a tile outside the planes are passed over.
+ *     n < 2^31.  One integer atomic per plane, wave segment and tile: the cost does not depend on how many rows a sample has in a
+ *     tile.  Integer atomics only, so order-independent.
+ * DIG_EINVAL, before anything is read or launched, when C, R, n_tiles or n_samples reach 2^31 or the key's fields do not fit 63
+ * bits.  Every typed pointer needs the alignment of its element and no more.  The host twins refuse pairs outside the tables, a row
+ * of a cohort within [0, C) whose sample is outside [0, n_samples), and keys that are not ascending. */
+int dig_tile_sample_keys(const int32_t *pair_mut, const int32_t *pair_reg, int64_t n_pairs, const int64_t *mut_start, int64_t n_mut,
+                         const int32_t *mut_cohort, const int32_t *mut_sample, const uint8_t *keep, const int64_t *first_pos,
+                         const int32_t *n_valid, int binsize, int64_t n_tiles, int64_t R, int64_t C, int64_t n_samples,
+                         int64_t *keys, void *stream);
+int dig_tile_sample_keys_host(const int32_t *pair_mut, const int32_t *pair_reg, int64_t n_pairs, const int64_t *mut_start,
+                              int64_t n_mut, const int32_t *mut_cohort, const int32_t *mut_sample, const uint8_t *keep,
+                              const int64_t *first_pos, const int32_t *n_valid, int binsize, int64_t n_tiles, int64_t R, int64_t C,
+                              int64_t n_samples, int64_t *keys, int device);
+int dig_tile_sample_counts(const int64_t *keys_sorted, int64_t n, int64_t C, int64_t R, int64_t n_tiles, int64_t n_samples,
+                           int64_t cap, int32_t *k_cap, int32_t *k_samples, void *stream);
+int dig_tile_sample_counts_host(const int64_t *keys_sorted, int64_t n, int64_t C, int64_t R, int64_t n_tiles, int64_t n_samples,
+                                int64_t cap, int32_t *k_cap, int32_t *k_samples, int device);
 
 /* ---- sufficient statistics in canonical chunks (bin-sharded runs) --------------------------- *
  * Same quantity as dig_scale_suffstats / dig_scale_factors, defined so that it does not depend on the sharding: the bins

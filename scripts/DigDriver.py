@@ -179,12 +179,20 @@ TILE_MODELS = {(1, 1): 'sequence_model_64', (2, 2): 'sequence_model_1024'}
 
 def cmd_tile(args):
     """tileDriver: the per-base scan of many cohorts on one bin grid; per cohort the tiles that pass the cut, as
-    <outdir>/<outpfx>.hits.txt (the rows of nb_model's frame, numbered as in it; with --fdr a QVAL column as well)."""
+    <outdir>/<outpfx>.hits.txt (the rows of nb_model's frame, numbered as in it; with --fdr a QVAL column as well).  The sample
+    options (--max-muts-per-sample, --max-muts-per-tile-per-sample, --by-sample, --cut-on) read the sample label from column 6 of
+    the mutation files; --by-sample adds OBS_SAMPLES and PVAL_SAMPLE behind REGION."""
     n = len(args.mutation_files)
     if not len(args.maps) == len(args.outpfx) == n:
         raise SystemExit("ERROR: --mutation-files, --maps and --outpfx must name the same number of cohorts.")
     if (args.pval_max is None) == (args.fdr is None):
         raise SystemExit("ERROR: you must provide exactly one of --pval-max and --fdr.")
+    if args.cut_on == 'PVAL_SAMPLE' and not args.by_sample:
+        raise SystemExit("ERROR: --cut-on PVAL_SAMPLE requires --by-sample.")
+    if args.max_muts_per_tile_per_sample is not None and args.max_muts_per_tile_per_sample < 1:
+        raise SystemExit("ERROR: --max-muts-per-tile-per-sample takes an integer >= 1.")
+    if args.max_muts_per_sample is not None and args.max_muts_per_sample < 0:
+        raise SystemExit("ERROR: --max-muts-per-sample takes an integer >= 0.")
     key = TILE_MODELS.get((args.up, args.down))
     if key is None:
         raise NotImplementedError("the tile kernels take n_up = n_down = 1 or 2")
@@ -210,8 +218,18 @@ def cmd_tile(args):
     keep = np.ones(len(idx), bool) if not args.chroms else np.isin(idx[:, 0].astype(str), [c.replace('chr', '') for c in args.chroms])
     if not keep.any():
         raise SystemExit("ERROR: no region of region_params is left to scan.")
-    frames = nb_model.nb_model_hits(d_prs, idx[keep], np.array(mu)[:, keep], np.array(sigma)[:, keep], args.mutation_files, args.f_fasta,
-                                    n_up=args.up, n_down=args.down, binsize=args.binsize, pval_max=args.pval_max, fdr=args.fdr)
+    # (the sample options are passed only when one is set: without them the call is the one of before)
+    sample_opts = {} if (args.max_muts_per_sample is None and args.max_muts_per_tile_per_sample is None and not args.by_sample) else dict(
+        max_muts_per_sample=args.max_muts_per_sample, max_muts_per_tile_per_sample=args.max_muts_per_tile_per_sample,
+        by_sample=args.by_sample, cut_on=args.cut_on)
+    try:
+        frames = nb_model.nb_model_hits(d_prs, idx[keep], np.array(mu)[:, keep], np.array(sigma)[:, keep], args.mutation_files,
+                                        args.f_fasta, n_up=args.up, n_down=args.down, binsize=args.binsize, pval_max=args.pval_max,
+                                        fdr=args.fdr, **sample_opts)
+    except ValueError as exc:
+        if not sample_opts or 'column 6' not in str(exc):
+            raise
+        raise SystemExit("ERROR: {}".format(exc))           # (a mutation file without sample labels)
     os.makedirs(args.outdir, exist_ok=True)
     for pfx, frame in zip(args.outpfx, frames):
         target = os.path.join(args.outdir, pfx + '.hits.txt')
@@ -300,6 +318,13 @@ def parse_args(text=None):
     d.add_argument('--pval-max', type=float, default=None, help='keep the tiles with PVAL <= this')
     d.add_argument('--fdr', type=float, default=None, help="keep the tiles with Benjamini-Hochberg q <= this over the cohort's testable tiles")
     d.add_argument('--chroms', type=str, nargs='+', default=None, help='scan only the regions of these chromosomes')
+    # the sample guards of the other routes, for tiles; any of them makes column 6 of the mutation files the sample label
+    d.add_argument('--max-muts-per-sample', type=int, default=None, help='drop samples with more rows in their file than this')
+    d.add_argument('--max-muts-per-tile-per-sample', type=int, default=None, help='cap of rows one sample adds to a tile (>= 1)')
+    d.add_argument('--by-sample', action='store_true', default=False,
+                   help='add OBS_SAMPLES (samples with a row in the tile) and PVAL_SAMPLE (the test on it)')
+    d.add_argument('--cut-on', choices=['PVAL', 'PVAL_SAMPLE'], default='PVAL',
+                   help='the score --pval-max / --fdr select on (PVAL_SAMPLE requires --by-sample)')
     d.set_defaults(func=cmd_tile)
 
     # not a reference sub-command: quickDriver for many cohorts at once (driver_model/cohort_batch.py run_quick_cohorts)
