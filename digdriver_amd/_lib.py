@@ -108,6 +108,12 @@ _SIGNATURES = {
     "dig_tile_sample_keys_host": [_vp, _vp, _i64, _vp, _i64] + [_vp] * 5 + [_int] + [_i64] * 4 + [_vp, _int],
     "dig_tile_sample_counts": [_vp] + [_i64] * 6 + [_vp, _vp, _vp],
     "dig_tile_sample_counts_host": [_vp] + [_i64] * 6 + [_vp, _vp, _int],
+    "dig_tile_census": [_vp, _i64, _vp, _vp, _int, _vp, _vp, _vp, _i64, _vp, _i64, _int, _int, _i64] + [_vp] * 4 + [_vp, _i64, _vp],
+    "dig_tile_census_host": [_vp, _i64, _vp, _vp, _int, _vp, _vp, _vp, _i64, _vp, _i64, _int, _int, _i64] + [_vp] * 4 + [_int],
+    "dig_sparse_tile_keys": [_vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _int] + [_i64] * 3 + [_vp, _vp],
+    "dig_sparse_tile_keys_host": [_vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _int] + [_i64] * 3 + [_vp, _int],
+    "dig_sparse_tile_test": [_vp, _i64, _vp, _vp, _int, _vp, _vp, _vp, _i64, _vp, _i64, _int, _int, _i64] + [_vp] * 4 + [_i64] + [_vp] * 7 + [_vp],
+    "dig_sparse_tile_test_host": [_vp, _i64, _vp, _vp, _int, _vp, _vp, _vp, _i64, _vp, _i64, _int, _int, _i64] + [_vp] * 4 + [_i64] + [_vp] * 7 + [_int],
     "dig_gene_pipeline": [_vp] * 15 + [_int] + [_vp] * 9 + [_i64, _i64, _i64, _vp, _i64, _vp],
     "dig_gene_pipeline_host": [_vp] * 15 + [_int] + [_vp] * 9 + [_i64, _i64, _i64, _int],
     "dig_count_contexts": [_vp, _i64, _vp, _vp, _int, _vp, _vp, _vp, _vp, _i64, _vp, _vp],
@@ -177,6 +183,7 @@ _SIZE_QUERIES = {
     "dig_bh_ragged_workspace": [_vp, _i64],
     "dig_mutation_contexts_workspace": [_i64],
     "dig_element_context_counts_workspace": [_i64],
+    "dig_tile_census_workspace": [_i64, _int],
 }
 
 ABI_VERSION = 12         # include/dig_hip.h: DIG_ABI_VERSION

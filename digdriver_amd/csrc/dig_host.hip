@@ -891,6 +891,93 @@ int dig_tile_sample_counts_host(const int64_t* keys_sorted, int64_t n, int64_t C
                    k_samples ? st.out(k_samples, slots) : nullptr, nullptr);
 }
 
+// what the two genome-walking twins of the sparse per-base scan check of their host arrays (`fn`: the twin's name)
+static int check_sparse_regions(const char* fn, const uint32_t* genome_words, int64_t n_words, const int64_t* chrom_off,
+                                const int64_t* chrom_len, int n_chrom, const int32_t* reg_chrom, const int64_t* reg_start,
+                                const int64_t* reg_end, int64_t R, int64_t C, int n_up, int binsize, int64_t n_tiles)
+{
+    DIG_REQUIRE_IN(fn, n_up == 1 || n_up == 2, "n_up = n_down = 1 or 2");
+    DIG_REQUIRE_IN(fn, R >= 0 && C >= 0 && n_words >= 2 && n_chrom >= 0 && n_tiles >= 0 && binsize >= 1,
+                   "non-negative sizes, n_words >= 2 (pad words), binsize >= 1");
+    if (R == 0) return DIG_OK;
+    DIG_REQUIRE_IN(fn, genome_words && chrom_off && chrom_len && reg_chrom && reg_start && reg_end, "non-null genome and region tables");
+    for (int c = 0; c < n_chrom; ++c)
+        DIG_REQUIRE_IN(fn, chrom_off[c] >= 0 && chrom_len[c] >= 0 && (chrom_off[c] + chrom_len[c] + 7) / 8 + 1 <= n_words,
+                       "chromosomes inside the genome array");
+    for (int64_t r = 0; r < R; ++r) {
+        DIG_REQUIRE_IN(fn, reg_chrom[r] >= 0 && reg_chrom[r] < n_chrom && reg_start[r] >= 0 && reg_end[r] >= 0, "regions inside the genome table");
+        DIG_REQUIRE_IN(fn, n_up == 1 || reg_end[r] - reg_start[r] <= 16384, "a region of the general-context form holds at most 16 384 positions");
+        DIG_REQUIRE_IN(fn, n_up == 1 || reg_start[r] == 0 || reg_start[r] >= n_up, "a region that starts inside (0, n_up) would fetch from a negative position");
+    }
+    return DIG_OK;
+}
+
+int dig_tile_census_host(const uint32_t* genome_words, int64_t n_words, const int64_t* chrom_off, const int64_t* chrom_len, int n_chrom,
+                         const int32_t* reg_chrom, const int64_t* reg_start, const int64_t* reg_end, int64_t R, const double* s_prob,
+                         int64_t C, int n_up, int binsize, int64_t n_tiles, int64_t* first_pos, int32_t* n_valid, double* denom,
+                         int32_t* n_positive, int device)
+{
+    if (int rc = check_sparse_regions(__func__, genome_words, n_words, chrom_off, chrom_len, n_chrom, reg_chrom, reg_start, reg_end, R, C,
+                                      n_up, binsize, n_tiles))
+        return rc;
+    int64_t slots = 0;
+    if (int rc = sparse_tile_slots(__func__, C, R, n_tiles, &slots)) return rc;
+    if (R == 0) return DIG_OK;
+    DIG_REQUIRE(first_pos && n_valid, "non-null first_pos, n_valid");
+    DIG_REQUIRE(C == 0 || (s_prob && denom && n_positive), "non-null s_prob, denom, n_positive");
+    const size_t nsp = (size_t)C * (n_up == 1 ? 64 : 1024), rows = (size_t)C * R;
+    const int64_t wsb = tile_census_workspace_bytes(C, n_up);
+    Staging st(device);
+    return st.call(dig_tile_census, st.in(genome_words, n_words), n_words, st.in(chrom_off, n_chrom), st.in(chrom_len, n_chrom), n_chrom,
+                   st.in(reg_chrom, R), st.in(reg_start, R), st.in(reg_end, R), R, st.in(s_prob, nsp), C, n_up, binsize, n_tiles,
+                   st.out(first_pos, R), st.out(n_valid, R), C ? st.out(denom, rows) : nullptr, C ? st.out(n_positive, rows) : nullptr,
+                   st.scratch(wsb), wsb, nullptr);
+}
+
+int dig_sparse_tile_keys_host(const int32_t* pair_mut, const int32_t* pair_reg, int64_t n_pairs, const int64_t* mut_start, int64_t n_mut,
+                              const int32_t* mut_cohort, const int64_t* first_pos, const int32_t* n_valid, int binsize, int64_t n_tiles,
+                              int64_t R, int64_t C, int64_t* keys, int device)
+{
+    DIG_REQUIRE(n_pairs >= 0 && n_mut >= 0 && binsize >= 1, "n_pairs, n_mut >= 0, binsize >= 1");
+    int64_t slots = 0;
+    if (int rc = sparse_tile_slots(__func__, C, R, n_tiles, &slots)) return rc;
+    if (n_pairs == 0) return DIG_OK;
+    DIG_REQUIRE(pair_mut && pair_reg && keys, "non-null pair arrays, keys");
+    DIG_REQUIRE(n_mut == 0 || (mut_start && mut_cohort), "non-null mutation arrays");
+    DIG_REQUIRE(R == 0 || (first_pos && n_valid), "non-null region tables");
+    for (int64_t i = 0; i < n_pairs; ++i)
+        DIG_REQUIRE(pair_mut[i] >= 0 && pair_mut[i] < n_mut && pair_reg[i] >= 0 && pair_reg[i] < R, "pairs inside the mutation / region tables");
+    Staging st(device);
+    return st.call(dig_sparse_tile_keys, st.in(pair_mut, n_pairs), st.in(pair_reg, n_pairs), n_pairs, st.in(mut_start, n_mut), n_mut,
+                   st.in(mut_cohort, n_mut), st.in(first_pos, R), st.in(n_valid, R), binsize, n_tiles, R, C, st.out(keys, n_pairs), nullptr);
+}
+
+int dig_sparse_tile_test_host(const uint32_t* genome_words, int64_t n_words, const int64_t* chrom_off, const int64_t* chrom_len,
+                              int n_chrom, const int32_t* reg_chrom, const int64_t* reg_start, const int64_t* reg_end, int64_t R,
+                              const double* s_prob, int64_t C, int n_up, int binsize, int64_t n_tiles, const double* denom,
+                              const double* mu, const double* sigma, const int64_t* keys_sorted, int64_t n, int32_t* out_cohort,
+                              int32_t* out_region, int32_t* out_tile, int32_t* out_k, double* out_pt, double* out_exp, double* out_pval,
+                              int device)
+{
+    if (int rc = check_sparse_regions(__func__, genome_words, n_words, chrom_off, chrom_len, n_chrom, reg_chrom, reg_start, reg_end, R, C,
+                                      n_up, binsize, n_tiles))
+        return rc;
+    DIG_REQUIRE(n >= 0 && n <= INT32_MAX, "0 <= n < 2^31 (the counts are 32-bit)");
+    int64_t slots = 0;
+    if (int rc = sparse_tile_slots(__func__, C, R, n_tiles, &slots)) return rc;
+    if (n == 0) return DIG_OK;
+    DIG_REQUIRE(keys_sorted && out_cohort && out_region && out_tile && out_k && out_pt && out_exp && out_pval, "non-null keys and outputs");
+    DIG_REQUIRE(slots == 0 || (s_prob && denom && mu && sigma), "non-null s_prob, denom, mu, sigma");
+    if (int rc = check_ascending(__func__, keys_sorted, n)) return rc;
+    const size_t nsp = (size_t)C * (n_up == 1 ? 64 : 1024), rows = (size_t)C * R;
+    Staging st(device);
+    return st.call(dig_sparse_tile_test, st.in(genome_words, n_words), n_words, st.in(chrom_off, n_chrom), st.in(chrom_len, n_chrom),
+                   n_chrom, st.in(reg_chrom, R), st.in(reg_start, R), st.in(reg_end, R), R, st.in(s_prob, nsp), C, n_up, binsize, n_tiles,
+                   st.in(denom, rows), st.in(mu, rows), st.in(sigma, rows), st.in(keys_sorted, n), n, st.out(out_cohort, n),
+                   st.out(out_region, n), st.out(out_tile, n), st.out(out_k, n), st.out(out_pt, n), st.out(out_exp, n),
+                   st.out(out_pval, n), nullptr);
+}
+
 int dig_overlap_join_count_host(const int64_t* blk_start_key, const int64_t* blk_runmax_key, const int64_t* blk_end, int64_t n_blk,
                                 const int64_t* mut_chrom, const int64_t* mut_start, const int64_t* mut_end, int64_t n_mut,
                                 int32_t* counts, int device)

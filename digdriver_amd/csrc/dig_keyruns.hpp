@@ -1,4 +1,4 @@
-// dig_keyruns.hpp -- what the counting routes (dig_genecounts.hip, dig_objectives.hip, dig_panelcounts.hip, dig_seqcounts.hip, dig_sitematch.hip, dig_tilehits.hip, dig_tilesamples.hip) and their host twins share:
+// dig_keyruns.hpp -- what the counting routes (dig_genecounts.hip, dig_objectives.hip, dig_panelcounts.hip, dig_seqcounts.hip, dig_sitematch.hip, dig_tilehits.hip, dig_tilesamples.hip, dig_tilesparse.hip) and their host twins share:
 // rows encoded as 63-bit keys, sorted by the caller, counted as runs with one integer atomic per wave segment.
 #pragma once
 #include "dig_common.hpp"
@@ -40,6 +40,11 @@ int tile_select_sizes(const char* fn, int64_t C, int64_t R, int64_t T);
 // (bits for n_samples + 1 values: the all-ones key is no real one); DIG_EINVAL (in the name of entry point `fn`) when the two fields
 // do not fit 63 bits
 int tile_sample_key_layout(const char* fn, int64_t C, int64_t R, int64_t T, int64_t n_samples, int* sample_bits);
+
+// dig_tilesparse.hip: the slots C R T of a sparse-scan key, (cohort R + region) T + tile; DIG_EINVAL (in the name of entry point `fn`)
+// unless C, R, T < 2^31 and the product fits 62 bits.  tile_census_workspace_bytes: what dig_tile_census_workspace returns
+int sparse_tile_slots(const char* fn, int64_t C, int64_t R, int64_t T, int64_t* slots);
+int64_t tile_census_workspace_bytes(int64_t C, int n_up);
 
 // dig_seqcounts.hip: the most table rows K a call takes -- a workgroup's LDS counters, 12 KB: the penta-nucleotide table
 constexpr int kSeqMaxK = 3072;

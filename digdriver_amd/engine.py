@@ -1286,6 +1286,80 @@ def tiled_nb_model(genome, chroms, starts, ends, s_prob, mu, sigma, mut_chrom, m
     return res
 
 
+# ---------------------------------------------------------------------------
+# per-base route for the mutated tiles only (dig_tilesparse.hip): nothing here is [C, R, T]
+# ---------------------------------------------------------------------------
+def _tile_genome(be, genome, chroms, starts, ends, s_prob, binsize, n_tiles):
+    """The arguments dig_tile_census and dig_sparse_tile_test share, checked as base_tile_probs checks them: (the pointers and sizes
+    up to n_tiles in the entry points' order, the arrays behind them, C, R, n_tiles, n_up, binsize)."""
+    ci = genome.chrom_index(chroms)
+    R = len(ci)
+    st, en = _lib.as_host(starts, np.int64).ravel(), _lib.as_host(ends, np.int64).ravel()
+    if (st < 0).any() or (en < 0).any():
+        raise ValueError("negative region coordinates")
+    binsize = int(binsize)
+    if binsize < 1:
+        raise ValueError("binsize >= 1")
+    if n_tiles is None:
+        n_tiles = int(max(1, -(-int((en - st).max() if R else 1) // binsize)))
+    s_prob = be.arr(s_prob, "f64")
+    if s_prob.ndim != 2 or s_prob.shape[1] not in (64, 1024):
+        raise ValueError("s_prob must be [C, 64] (trinucleotide) or [C, 1024] (penta-nucleotide)")
+    C = s_prob.shape[0]
+    n_up = 1 if s_prob.shape[1] == 64 else 2
+    check_tile_regions(st, en, n_up)
+    words, off, ln = genome.on_device(be.dev) if be.is_device else (genome.words, genome.offsets, genome.lengths)
+    held = [words, off, ln] + [be.arr(a) for a in (ci, st, en)] + [s_prob]
+    p = be.ptr
+    args = [p(words), words.shape[0], p(off), p(ln), len(genome.names), p(held[3]), p(held[4]), p(held[5]), R, p(s_prob), C, n_up, binsize,
+            int(n_tiles)]
+    return args, held, C, R, int(n_tiles), n_up, binsize
+
+
+def tile_census(genome, chroms, starts, ends, s_prob, binsize, n_tiles=None, device=0, on_device=True):
+    """What the sparse per-base scan knows of the regions without a [C, R, T] plane (dig_tile_census): first_pos i64 [R], n_valid i32
+    [R] -- the bits base_tile_probs returns --, denom f64 [C, R], the region's sum of s_prob over its positions (what the dense route
+    divides by), and n_positive i32 [C, R], the tiles below n_valid whose dense pt is > 0.  Arguments as base_tile_probs; returns
+    (first_pos, n_valid, denom, n_positive), device tensors or (on_device=False, the host twin) arrays."""
+    be = backend_on(device, on_device)
+    args, held, C, R, _, n_up, _ = _tile_genome(be, genome, chroms, starts, ends, s_prob, binsize, n_tiles)
+    first, nval = be.empty(R, "i64"), be.empty(R, "i32")
+    denom, npos = be.empty((C, R), "f64"), be.empty((C, R), "i32")
+    wsb = int(_lib.load().dig_tile_census_workspace(C, n_up))
+    p = be.ptr
+    with _requirements_as_value_errors():
+        be.call("dig_tile_census", *args, p(first), p(nval), p(denom), p(npos), workspace=(be.empty(wsb, "u8"), wsb) if be.is_device else None)
+    return first, nval, denom, npos
+
+
+def sparse_tile_test(genome, chroms, starts, ends, s_prob, binsize, n_tiles, first_pos, n_valid, denom, mu, sigma, mut_chrom, mut_start,
+                     mut_end, mut_cohort):
+    """The NB test of the tiles that hold a row, and of no other: the join of tile_mut_counts, dig_sparse_tile_keys, a key sort,
+    dig_sparse_tile_test, and the runs' heads kept.  first_pos, n_valid, denom as tile_census returns them (device tensors -> device
+    tensors, arrays -> the host twins); mu, sigma [C, R]; mut_*: as tile_mut_counts takes them.  Returns dict(cohort, region, tile, k
+    i32, pt, exp, pval f64): one entry per mutated tile, cohort-major, then by region, then by tile -- the order of the dense frame.
+    k is dig_tile_mut_counts' count, pt / exp / pval what the dense route has there (pt to rounding: another order of additions)."""
+    be = backend_of(first_pos, n_valid, denom)
+    args, held, C, R, T, _, binsize = _tile_genome(be, genome, chroms, starts, ends, s_prob, binsize, n_tiles)
+    first_pos, n_valid = be.arr(first_pos, "i64", (R,)), be.arr(n_valid, "i32", (R,))
+    denom, mu, sigma = (be.arr(x, "f64", (C, R)) for x in (denom, mu, sigma))
+    pm, pr, ms = _tile_pairs(be, genome, chroms, starts, ends, mut_chrom, mut_start, mut_end)
+    co = be.arr(mut_cohort, "i32", (-1,))
+    if ms.shape[0] != co.shape[0]:
+        raise ValueError("mut_cohort: one entry per mutation row")
+    p = be.ptr
+    n = pm.shape[0]
+    keys = be.empty(n, "i64")
+    names = ("cohort", "region", "tile", "k", "pt", "exp", "pval")
+    with _requirements_as_value_errors():
+        be.call("dig_sparse_tile_keys", p(pm), p(pr), n, p(ms), ms.shape[0], p(co), p(first_pos), p(n_valid), binsize, T, R, C, p(keys))
+        keys = _sorted(be, keys)
+        out = {k: be.empty(n, "i32" if i < 4 else "f64") for i, k in enumerate(names)}
+        be.call("dig_sparse_tile_test", *args, p(denom), p(mu), p(sigma), p(keys), n, *[p(out[k]) for k in names])
+    head = out["k"] > 0
+    return {k: v[head] for k, v in out.items()}
+
+
 def _tile_counts(be, score, n_valid, cut):
     """dig_tile_select_count on the backend's arrays: (the six leading arguments both entry points take, counts i32 [C R], C, R, T)."""
     score = be.arr(score, "f64")

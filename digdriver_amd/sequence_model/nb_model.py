@@ -369,6 +369,158 @@ def nb_model_hits(d_prs, idx, mu, sigma, f_muts, f_fasta, n_up=2, n_down=2, bins
     return frames
 
 
+# ---------------------------------------------------------------------------------------------
+# the per-base scan over the mutated tiles only (DESIGN.md "Sparse per-base scan")
+# ---------------------------------------------------------------------------------------------
+ZERO_FLOOR_MARGIN = 4e-6       # p-values are pinned to 1e-6 relative, pt to 1e-12: both sides' error twice over
+
+
+def _one_cut(pval_max, fdr, bonferroni):
+    if sum(x is not None for x in (pval_max, fdr, bonferroni)) != 1:
+        raise ValueError("exactly one of pval_max, fdr and bonferroni must be given")
+    if bonferroni is not None and not 0.0 < bonferroni <= 1.0:
+        raise ValueError("bonferroni: a level within (0, 1]")
+
+
+def testable_regions(mu, sigma):
+    """[C, R] bool: the (cohort, region) rows whose empty tiles with pt > 0 have a p-value -- the NaN rule of nb_exact
+    (csrc/dig_math.hpp) at k = 0: alpha = mu^2 / sigma^2 must be a finite number > 0 and theta = sigma^2 / mu a number > 0.  (mu NaN,
+    0 or negative, sigma NaN, 0 or infinite: k = 0 is then not below the NB mean, the upper tail is betainc(0, alpha, .) = NaN.)"""
+    mu, sigma = np.asarray(mu, float), np.asarray(sigma, float)
+    with np.errstate(all="ignore"):
+        alpha, theta = (mu * mu) / (sigma * sigma), (sigma * sigma) / mu
+    return np.isfinite(alpha) & (alpha > 0) & (theta > 0)
+
+
+def zero_tile_floor(denom, smax, smin_pos, mu, sigma, binsize, n_positive=None):
+    """floor [C]: a lower bound of the p-value of every EMPTY testable tile of a cohort, from the region denominators alone.  An
+    empty tile below the NB mean has PVAL = P(X = 0) = (1 + theta pt)^(-alpha), which falls as pt grows, and no tile's pt exceeds
+    u = min(1, binsize smax[c] / denom[c, r]): floor[c] = min over the testable regions with denom > 0 of (1 + theta u)^(-alpha);
+    +inf for a cohort without such a region (it has no empty testable tile).
+    denom, n_positive: host arrays or device tensors as engine.tile_census returns them (the arithmetic then runs where they lie:
+    at 200 000 regions x 37 cohorts numpy took 0.2 s of a 0.27 s scan); floor comes back as a host array.
+    Also returns testable [C, R] (testable_regions, on the same side as denom) and checks the other end: the smallest positive pt a region can hold,
+    smin_pos[c] / denom[c, r], must still give p = 1 / (theta pt + 1) < 1 and an NB mean > 0 -- else a tile with pt > 0 would have
+    a NaN p-value in the dense route (p rounds to 1) and the census could not count the testable tiles: ValueError."""
+    be = backend_of(denom, n_positive)
+    x = be.torch if be.is_device else np                     # (the few operations below have one spelling in both)
+    denom = be.arr(denom, "f64")
+    C, R = denom.shape
+    mu, sigma = be.arr(mu, "f64", (C, R)), be.arr(sigma, "f64", (C, R))
+    smax, smin_pos = be.arr(smax, "f64", (C, 1)), be.arr(smin_pos, "f64", (C, 1))
+    with np.errstate(all="ignore"):
+        alpha, theta = (mu * mu) / (sigma * sigma), (sigma * sigma) / mu
+        testable = x.isfinite(alpha) & (alpha > 0) & (theta > 0)              # (testable_regions)
+        ok = testable & (denom > 0)
+        ratio = binsize * smax / denom
+        u = x.where(ratio < 1.0, ratio, x.ones_like(ratio))
+        f = x.exp(-alpha * x.log1p(theta * u))
+        p_low = 1.0 / (theta * (smin_pos / denom) + 1.0)
+        lost = ok & ~((p_low < 1.0) & (alpha * (1.0 - p_low) / p_low > 0))
+    if n_positive is not None:
+        lost = lost & (be.arr(n_positive, None, (C, R)) > 0)
+    if bool(lost.any()):
+        c, r = np.argwhere(lost.cpu().numpy() if be.is_device else lost)[0]
+        raise ValueError("cohort %d, region %d: theta pt of the smallest tile probability is below the rounding of 1 / (theta pt + 1): "
+                         "the testable tiles cannot be counted without evaluating every tile (use nb_model_hits)" % (c, r))
+    if R == 0:
+        return np.full(C, np.inf), testable
+    floor = x.amin(x.where(ok, f, x.full_like(f, float("inf"))), 1)
+    return (floor.cpu().numpy() if be.is_device else floor), testable
+
+
+def nb_model_hits_sparse(d_prs, idx, mu, sigma, f_muts, f_fasta, n_up=2, n_down=2, binsize=1, collapse=False, pval_max=None, fdr=None,
+                         bonferroni=None, device=0):
+    """nb_model_hits over the tiles that hold a mutation row, and no other: memory and work follow the rows and C R, no [C, R, T]
+    array is allocated.  Exactly one of pval_max / fdr / bonferroni (cut = bonferroni / n_testable of the cohort).  Frames as
+    nb_model_hits makes them (columns, dtypes, row order, int64 index = the row number in the full dense frame; QVAL with fdr;
+    attrs n_testable and n_tiles), with two more attrs:
+      zero_floor  a lower bound of the p-value of every empty testable tile of the cohort (zero_tile_floor);
+      complete    zero_floor (1 - 4e-6) > cut: no empty tile can be a hit, the frame is ALL of the dense hits.  When it is false the
+                  frame is the dense hits with OBS >= 1 (pval_max, bonferroni).
+    fdr: every cohort must be complete at cut = fdr, else ValueError (naming the cohorts, their floors and fdr) before any tile is
+    tested; the frames are then exactly the dense ones: every p <= fdr belongs to a mutated tile and holds its rank, and the
+    Benjamini-Hochberg pivot p_(j) <= fdr j / m <= fdr < floor is no empty tile.
+    n_testable is the dense route's: the tiles with pt > 0 of the testable regions (engine.tile_census counts them), plus the
+    mutated tiles outside that set whose p-value is a number (a row on a tile of windows with an N: Pi = 0, PVAL = 0)."""
+    _one_cut(pval_max, fdr, bonferroni)
+    if n_up != n_down or n_up not in (1, 2):
+        raise NotImplementedError("the tile kernels take n_up = n_down = 1 or 2")
+    import pandas as pd
+    from .. import engine
+    from ..data_tools import cohort_rows, genome as genome_mod
+    C = len(d_prs)
+    f_muts = list(f_muts)
+    idx = np.asarray(idx)
+    R = len(idx)
+    mu, sigma = np.asarray(mu, float).reshape(C, R), np.asarray(sigma, float).reshape(C, R)
+    if len(f_muts) != C:
+        raise ValueError("one mutation file per cohort: %d files for %d cohorts" % (len(f_muts), C))
+    s_prob = np.stack([_s_prob_table(d, n_up, collapse) for d in d_prs]) if C else np.zeros((0, 4 ** (2 * n_up + 1)))
+    if (s_prob < 0).any():
+        raise ValueError("S_prob: a negative entry (cohort %d)" % int(np.argwhere(s_prob < 0)[0][0]))
+    starts, ends = (idx[:, 1].astype(np.int64), idx[:, 2].astype(np.int64)) if R else (np.zeros(0, np.int64),) * 2
+    engine.check_tile_regions(starts, ends, n_up)
+    g = f_fasta if isinstance(f_fasta, genome_mod.PackedGenome) else genome_mod.PackedGenome.from_fasta(f_fasta)
+    chroms = [str(c) for c in idx[:, 0]] if R else []
+    known = set(n.replace("chr", "") for n in g.names)
+    rows = _cohort_rows(f_muts, known, False)
+    mc, ms, me = cohort_rows.column(rows, "chrom"), cohort_rows.column(rows, "start", "i64"), cohort_rows.column(rows, "end", "i64")
+    co = cohort_rows.cohort_column(rows, "start")
+    first_d, nval_d, denom_d, npos_d = engine.tile_census(g, chroms, starts, ends, s_prob, binsize, device=device)
+    first, nval = first_d.cpu().numpy(), np.maximum(nval_d.cpu().numpy().astype(np.int64), 0)
+    smax = s_prob.max(axis=1) if C else np.zeros(0)
+    smin = np.where(s_prob > 0, s_prob, np.inf).min(axis=1) if C else np.zeros(0)
+    floor, testable_d = zero_tile_floor(denom_d, smax, smin, mu, sigma, binsize, npos_d)
+    n_census = (npos_d.long() * testable_d).sum(dim=1).cpu().numpy() if R else np.zeros(C, np.int64)
+    testable = testable_d.cpu().numpy()
+    if fdr is not None:
+        bad = [c for c in range(C) if not floor[c] * (1.0 - ZERO_FLOOR_MARGIN) > fdr]
+        if bad:
+            raise ValueError("fdr = %g: no certificate that an empty tile is no hit for cohorts %s (zero-tile floors %s): a smaller fdr, "
+                             "a smaller binsize, or nb_model_hits" % (fdr, bad, ["%.3g" % floor[c] for c in bad]))
+    n_tiles = int(max(1, -(-int((ends - starts).max() if R else 1) // int(binsize))))
+    res = engine.sparse_tile_test(g, chroms, starts, ends, s_prob, binsize, n_tiles, first_d, nval_d, denom_d, mu, sigma, mc, ms, me, co)
+    p_dev = res["pval"]
+    tiles = {k: v.cpu().numpy() for k, v in res.items()}
+    tc, tr = tiles["cohort"].astype(np.int64), tiles["region"].astype(np.int64)
+    number = ~np.isnan(tiles["pval"])
+    counted = testable[tc, tr] & (tiles["pt"] > 0) if len(tc) else np.zeros(0, bool)       # (the census has these tiles already)
+    n_test = n_census + np.bincount(tc[number & ~counted], minlength=C)[:C]
+    ptr = np.searchsorted(tc, np.arange(C + 1))                       # (the tiles lie cohort-major)
+    if fdr is not None:
+        cuts = np.full(C, -1.0)
+        if number.any():
+            # the mutated tiles' testable p-values, ranked in a list of n_testable: every rank up to the pivot is theirs
+            import torch
+            keep = torch.as_tensor(number, device=p_dev.device)
+            lists, lptr = p_dev[keep].contiguous(), np.searchsorted(tc[number], np.arange(C + 1)).astype(np.int64)
+            q, _ = bh_ragged(lists, lptr, n_global=np.maximum(n_test, 1).astype(np.float64))
+            for c in range(C):
+                cuts[c] = bh_cut(lists[lptr[c]:lptr[c + 1]], q[lptr[c]:lptr[c + 1]], fdr)
+        level = np.full(C, float(fdr))
+    elif bonferroni is not None:
+        cuts = level = float(bonferroni) / np.maximum(n_test, 1)
+    else:
+        cuts = level = np.full(C, float(pval_max))
+    n_pos = _region_positions(g, chroms, ends, first, n_up) if R else np.zeros(0, np.int64)
+    row0 = np.cumsum(nval) - nval
+    frames = []
+    for c in range(C):
+        sel = np.arange(ptr[c], ptr[c + 1])
+        sel = sel[tiles["pval"][sel] <= cuts[c]]                       # (a NaN never passes)
+        reg, t = tr[sel], tiles["tile"][sel].astype(np.int64)
+        df = _tile_frame(idx, mu[c], sigma[c], first, n_pos, binsize, reg, t, tiles["k"][sel], tiles["exp"][sel], tiles["pval"][sel],
+                         tiles["pt"][sel])
+        if fdr is not None:
+            df["QVAL"] = hits_q_values(tiles["pval"][sel], int(n_test[c]))
+        df.index = pd.Index(row0[reg] + t, dtype=np.int64)
+        df.attrs.update(n_testable=int(n_test[c]), n_tiles=int(nval.sum()), zero_floor=float(floor[c]),
+                        complete=bool(floor[c] * (1.0 - ZERO_FLOOR_MARGIN) > level[c]))
+        frames.append(df)
+    return frames
+
+
 def bh_ragged(p, row_ptr, n_global=None, rank0=None, carry=None, want_q=True, want_row_min=False, sorted_out=False):
     """dig_bh_qvalues_ragged (csrc/dig_sort.hip): Benjamini-Hochberg q-values of ragged rows of one float64 device tensor -- the
     library's own batched radix sort (63-bit keys, 32-bit payload, one kernel per pass), the Benjamini-Hochberg pass and the

@@ -41,7 +41,8 @@ extern "C" {
                              * 12 (round 6): + dig_sort_rows, dig_bh_qvalues_ragged; - dig_element_pipeline_scaled*, dig_element_pipeline_pack_counts /
                              * DIG_PIPE_PACKED_COUNTS (round 5's measured losers: tools/rejected/r05_*.patch); still 12: + dig_panel_row_keys,
                              * dig_panel_counts and their _host twins (additions); + dig_tile_sample_keys, dig_tile_sample_counts and
-                             * their _host twins (additions) */
+                             * their _host twins (additions); + dig_tile_census(_workspace), dig_sparse_tile_keys, dig_sparse_tile_test
+                             * and their _host twins (additions) */
 
 /* dtype codes for dig_gather_bins */
 #define DIG_F32 0
@@ -524,6 +525,62 @@ int dig_tile_sample_counts(const int64_t *keys_sorted, int64_t n, int64_t C, int
                            int64_t cap, int32_t *k_cap, int32_t *k_samples, void *stream);
 int dig_tile_sample_counts_host(const int64_t *keys_sorted, int64_t n, int64_t C, int64_t R, int64_t n_tiles, int64_t n_samples,
                                 int64_t cap, int32_t *k_cap, int32_t *k_samples, int device);
+
+/* ---- the per-base route for the mutated tiles only (additive: the ABI version stays) ------------------------------ *
+ * The dense route keeps four [C, R, n_tiles] planes.  These entry points keep nothing of that size: a census of the regions
+ * ([R] and [C, R] arrays), one key per (mutation, region) pair, and one test per run of equal keys -- a tile that holds a row.
+ * Genome, chromosome and region arguments, s_prob [C, 4^(2 n_up + 1)], n_up, binsize and n_tiles as dig_base_tile_probs_ctx
+ * takes them; both genome walkers clamp every word index into [0, n_words).
+ *   dig_tile_census_workspace(C, n_up): the bytes of dig_tile_census's workspace, ceil(C / 64) (at least 1) words of 8 bytes per
+ *     context; 0 for arguments outside their domains.  The workspace is aligned to 8 bytes.
+ *   dig_tile_census: first_pos i64 [R], n_valid i32 [R]: bit-equal to what dig_base_tile_probs_ctx writes.
+ *     denom f64 [C, R]: the region's sum of s_prob over its positions (a window that holds a letter other than ACGT adds nothing),
+ *     what the dense route divides by, regrouped by context: exact integer context counts times the table, added in one order -- lane l
+ *     of a 64-lane wave takes the contexts l, l + 64, ... ascending (fma), then the lanes fold by halves (32, 16, ..., 1).  No
+ *     floating-point atomics: the bits depend on the region and the table alone.
+ *     n_positive i32 [C, R]: the tiles t < n_valid[r] that hold at least one all-ACGT window with s_prob[c][context] > 0 -- the
+ *     tiles whose dense pt is > 0.  Cohorts go in passes of 64 (one mask word per context).
+ *     A region whose chromosome id is outside [0, n_chrom) is read as one without positions.  R < 2^31 (a workgroup per region).
+ *   dig_sparse_tile_keys: keys i64 [n_pairs], one per (mutation, region) pair of dig_overlap_join_count/fill, under the skip rules of
+ *     dig_tile_mut_counts: (cohort R + region) n_tiles + tile for the tile that holds the row's START; INT64_MAX for a pair that counts
+ *     nowhere (START in front of the region, tile at or past n_valid[region] or n_tiles, cohort outside [0, C), pair outside the tables).
+ *   The caller sorts the keys ascending.
+ *   dig_sparse_tile_test: a run of equal keys is one mutated tile with k = its length.  At the index of the run's FIRST key:
+ *     out_cohort, out_region, out_tile, out_k i32 and out_pt (the sum of s_prob[c] over the tile's positions in position order,
+ *     divided by denom[c, r]), out_exp (pt mu), out_pval f64 -- the arithmetic of dig_tiled_nb_test through the same device functions.
+ *     Every other index gets cohort = region = tile = -1, k = 0 and NaN: all n entries of all seven outputs are written.  A key
+ *     outside [0, C R n_tiles) (negative, INT64_MAX) is passed over and never dereferenced.  denom, mu, sigma f64 [C, R].  n < 2^31.
+ *     One search per run: the cost does not depend on how many rows a tile holds.
+ * DIG_EINVAL, before anything is read or launched, when C, R or n_tiles reach 2^31 or C R n_tiles does not fit 62 bits.  Every typed
+ * pointer needs the alignment of its element and no more.  The host twins refuse regions outside the genome table (and what
+ * dig_base_tile_probs_ctx_host refuses of a region), pairs outside the tables and keys that are not ascending. */
+int64_t dig_tile_census_workspace(int64_t C, int n_up);
+int dig_tile_census(const uint32_t *genome_words, int64_t n_words, const int64_t *chrom_off, const int64_t *chrom_len, int n_chrom,
+                    const int32_t *reg_chrom, const int64_t *reg_start, const int64_t *reg_end, int64_t R, const double *s_prob,
+                    int64_t C, int n_up, int binsize, int64_t n_tiles, int64_t *first_pos, int32_t *n_valid, double *denom,
+                    int32_t *n_positive, void *workspace, int64_t workspace_bytes, void *stream);
+int dig_tile_census_host(const uint32_t *genome_words, int64_t n_words, const int64_t *chrom_off, const int64_t *chrom_len,
+                         int n_chrom, const int32_t *reg_chrom, const int64_t *reg_start, const int64_t *reg_end, int64_t R,
+                         const double *s_prob, int64_t C, int n_up, int binsize, int64_t n_tiles, int64_t *first_pos,
+                         int32_t *n_valid, double *denom, int32_t *n_positive, int device);
+int dig_sparse_tile_keys(const int32_t *pair_mut, const int32_t *pair_reg, int64_t n_pairs, const int64_t *mut_start, int64_t n_mut,
+                         const int32_t *mut_cohort, const int64_t *first_pos, const int32_t *n_valid, int binsize, int64_t n_tiles,
+                         int64_t R, int64_t C, int64_t *keys, void *stream);
+int dig_sparse_tile_keys_host(const int32_t *pair_mut, const int32_t *pair_reg, int64_t n_pairs, const int64_t *mut_start,
+                              int64_t n_mut, const int32_t *mut_cohort, const int64_t *first_pos, const int32_t *n_valid,
+                              int binsize, int64_t n_tiles, int64_t R, int64_t C, int64_t *keys, int device);
+int dig_sparse_tile_test(const uint32_t *genome_words, int64_t n_words, const int64_t *chrom_off, const int64_t *chrom_len,
+                         int n_chrom, const int32_t *reg_chrom, const int64_t *reg_start, const int64_t *reg_end, int64_t R,
+                         const double *s_prob, int64_t C, int n_up, int binsize, int64_t n_tiles, const double *denom,
+                         const double *mu, const double *sigma, const int64_t *keys_sorted, int64_t n, int32_t *out_cohort,
+                         int32_t *out_region, int32_t *out_tile, int32_t *out_k, double *out_pt, double *out_exp, double *out_pval,
+                         void *stream);
+int dig_sparse_tile_test_host(const uint32_t *genome_words, int64_t n_words, const int64_t *chrom_off, const int64_t *chrom_len,
+                              int n_chrom, const int32_t *reg_chrom, const int64_t *reg_start, const int64_t *reg_end, int64_t R,
+                              const double *s_prob, int64_t C, int n_up, int binsize, int64_t n_tiles, const double *denom,
+                              const double *mu, const double *sigma, const int64_t *keys_sorted, int64_t n, int32_t *out_cohort,
+                              int32_t *out_region, int32_t *out_tile, int32_t *out_k, double *out_pt, double *out_exp,
+                              double *out_pval, int device);
 
 /* ---- sufficient statistics in canonical chunks (bin-sharded runs) --------------------------- *
  * Same quantity as dig_scale_suffstats / dig_scale_factors, defined so that it does not depend on the sharding: the bins

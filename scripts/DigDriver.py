@@ -179,13 +179,24 @@ TILE_MODELS = {(1, 1): 'sequence_model_64', (2, 2): 'sequence_model_1024'}
 
 def cmd_tile(args):
     """tileDriver: the per-base scan of many cohorts on one bin grid; per cohort the tiles that pass the cut, as
-    <outdir>/<outpfx>.hits.txt (the rows of nb_model's frame, numbered as in it; with --fdr a QVAL column as well).  The sample
+    <outdir>/<outpfx>.hits.txt (the rows of nb_model's frame, numbered as in it; with --fdr a QVAL column as well).  --sparse tests
+    the mutated tiles only (nb_model_hits_sparse; --bonferroni is its third cut, the sample options are not part of it).  The sample
     options (--max-muts-per-sample, --max-muts-per-tile-per-sample, --by-sample, --cut-on) read the sample label from column 6 of
     the mutation files; --by-sample adds OBS_SAMPLES and PVAL_SAMPLE behind REGION."""
     n = len(args.mutation_files)
     if not len(args.maps) == len(args.outpfx) == n:
         raise SystemExit("ERROR: --mutation-files, --maps and --outpfx must name the same number of cohorts.")
-    if (args.pval_max is None) == (args.fdr is None):
+    if args.bonferroni is not None and not args.sparse:
+        raise SystemExit("ERROR: --bonferroni is valid only with --sparse.")
+    if args.sparse:
+        if sum(x is not None for x in (args.pval_max, args.fdr, args.bonferroni)) != 1:
+            raise SystemExit("ERROR: you must provide exactly one of --pval-max, --fdr and --bonferroni.")
+        if args.bonferroni is not None and not 0.0 < args.bonferroni <= 1.0:
+            raise SystemExit("ERROR: --bonferroni takes a level within (0, 1].")
+        if args.max_muts_per_sample is not None or args.max_muts_per_tile_per_sample is not None or args.by_sample or args.cut_on != 'PVAL':
+            raise SystemExit("ERROR: --sparse does not take the sample options (--max-muts-per-sample, --max-muts-per-tile-per-sample, "
+                             "--by-sample, --cut-on).")
+    elif (args.pval_max is None) == (args.fdr is None):
         raise SystemExit("ERROR: you must provide exactly one of --pval-max and --fdr.")
     if args.cut_on == 'PVAL_SAMPLE' and not args.by_sample:
         raise SystemExit("ERROR: --cut-on PVAL_SAMPLE requires --by-sample.")
@@ -222,6 +233,23 @@ def cmd_tile(args):
     sample_opts = {} if (args.max_muts_per_sample is None and args.max_muts_per_tile_per_sample is None and not args.by_sample) else dict(
         max_muts_per_sample=args.max_muts_per_sample, max_muts_per_tile_per_sample=args.max_muts_per_tile_per_sample,
         by_sample=args.by_sample, cut_on=args.cut_on)
+    if args.sparse:
+        try:
+            frames = nb_model.nb_model_hits_sparse(d_prs, idx[keep], np.array(mu)[:, keep], np.array(sigma)[:, keep], args.mutation_files,
+                                                   args.f_fasta, n_up=args.up, n_down=args.down, binsize=args.binsize,
+                                                   pval_max=args.pval_max, fdr=args.fdr, bonferroni=args.bonferroni)
+        except ValueError as exc:
+            if 'no certificate' not in str(exc):
+                raise
+            raise SystemExit("ERROR: {}".format(exc))
+        os.makedirs(args.outdir, exist_ok=True)
+        for pfx, frame in zip(args.outpfx, frames):
+            target = os.path.join(args.outdir, pfx + '.hits.txt')
+            print('\t{}: {} hits of {} testable tiles, zero-tile floor {:.3g}{}; saving to {}'.format(
+                pfx, len(frame), frame.attrs['n_testable'], frame.attrs['zero_floor'],
+                '' if frame.attrs['complete'] else ' (mutated tiles only)', target))
+            mapfile.write_results_tsv(frame, target)
+        return
     try:
         frames = nb_model.nb_model_hits(d_prs, idx[keep], np.array(mu)[:, keep], np.array(sigma)[:, keep], args.mutation_files,
                                         args.f_fasta, n_up=args.up, n_down=args.down, binsize=args.binsize, pval_max=args.pval_max,
@@ -318,6 +346,11 @@ def parse_args(text=None):
     d.add_argument('--pval-max', type=float, default=None, help='keep the tiles with PVAL <= this')
     d.add_argument('--fdr', type=float, default=None, help="keep the tiles with Benjamini-Hochberg q <= this over the cohort's testable tiles")
     d.add_argument('--chroms', type=str, nargs='+', default=None, help='scan only the regions of these chromosomes')
+    # the scan over the mutated tiles only: memory follows the rows, not the genome (DESIGN.md "Sparse per-base scan")
+    d.add_argument('--sparse', action='store_true', default=False,
+                   help='test only the tiles that hold a mutation row; an empty tile is ruled out by a bound on its p-value')
+    d.add_argument('--bonferroni', type=float, default=None,
+                   help="with --sparse: keep the tiles with PVAL <= this / the cohort's testable tiles")
     # the sample guards of the other routes, for tiles; any of them makes column 6 of the mutation files the sample label
     d.add_argument('--max-muts-per-sample', type=int, default=None, help='drop samples with more rows in their file than this')
     d.add_argument('--max-muts-per-tile-per-sample', type=int, default=None, help='cap of rows one sample adds to a tile (>= 1)')
