@@ -328,7 +328,7 @@ def test_row_walk_on_ten_kb_bins_against_the_general_kernel_and_the_oracle():
     """base_tile_probs_rows_kernel (dig_tiles_rows.hip: what dig_base_tile_probs_ctx runs at n_up = 2) on 10-kb bins, the
     shape of BASELINE configs[4]: more regions than workgroups, 37 cohorts (passes of 16 + 16 + 5), N runs and single N,
     a bin at a chromosome's start and one over its end, a 12-kb region (more positions than the walk stages: left to the general
-    kernel by the n_valid = -2 mark), binsize 50 / 64 / 60 (trips of 10 / 8 / 12 positions; fewer tiles asked for than a region has) and 1 (every region deferred);
+    kernel by the n_valid = -2 mark), binsize 50 / 64 / 60 (trips of 25 / 8 / 12 positions; fewer tiles asked for than a region has) and 1 (every region deferred);
     against the general kernel (DIG_TILES_FORM=general, own process) and, for a sample, the oracle."""
     import subprocess
     import sys
