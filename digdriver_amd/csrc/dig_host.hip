@@ -891,6 +891,21 @@ int dig_tile_sample_counts_host(const int64_t* keys_sorted, int64_t n, int64_t C
                    k_samples ? st.out(k_samples, slots) : nullptr, nullptr);
 }
 
+int dig_tile_window_test_host(const double* pt, const int32_t* k, const double* mu, const double* sigma, const int32_t* n_valid,
+                              int64_t C, int64_t R, int64_t T, int32_t width, double* pt_w, int32_t* k_w, double* exp_w,
+                              double* pval_w, int32_t* n_windows, int device)
+{
+    if (int rc = tile_window_sizes(__func__, C, R, T, width)) return rc;
+    const size_t rows = (size_t)C * R, n = rows * T;
+    if (n == 0 || (!pt_w && !k_w && !exp_w && !pval_w && !n_windows)) return DIG_OK;
+    DIG_REQUIRE(pt && k && mu && sigma && n_valid, "non-null pt, k, mu, sigma, n_valid");
+    Staging st(device);
+    // (an output that is NULL is not staged: the call skips it)
+    return st.call(dig_tile_window_test, st.in(pt, n), st.in(k, n), st.in(mu, rows), st.in(sigma, rows), st.in(n_valid, R), C, R, T, width,
+                   pt_w ? st.out(pt_w, n) : nullptr, k_w ? st.out(k_w, n) : nullptr, exp_w ? st.out(exp_w, n) : nullptr,
+                   pval_w ? st.out(pval_w, n) : nullptr, n_windows ? st.out(n_windows, R) : nullptr, nullptr);
+}
+
 // what the two genome-walking twins of the sparse per-base scan check of their host arrays (`fn`: the twin's name)
 static int check_sparse_regions(const char* fn, const uint32_t* genome_words, int64_t n_words, const int64_t* chrom_off,
                                 const int64_t* chrom_len, int n_chrom, const int32_t* reg_chrom, const int64_t* reg_start,

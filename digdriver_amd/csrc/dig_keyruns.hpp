@@ -1,4 +1,4 @@
-// dig_keyruns.hpp -- what the counting routes (dig_genecounts.hip, dig_objectives.hip, dig_panelcounts.hip, dig_seqcounts.hip, dig_sitematch.hip, dig_tilehits.hip, dig_tilesamples.hip, dig_tilesparse.hip) and their host twins share:
+// dig_keyruns.hpp -- what the counting routes (dig_genecounts.hip, dig_objectives.hip, dig_panelcounts.hip, dig_seqcounts.hip, dig_sitematch.hip, dig_tilehits.hip, dig_tilesamples.hip, dig_tilesparse.hip, dig_tilewindows.hip) and their host twins share:
 // rows encoded as 63-bit keys, sorted by the caller, counted as runs with one integer atomic per wave segment.
 #pragma once
 #include "dig_common.hpp"
@@ -35,6 +35,9 @@ int panel_key_layout(const char* fn, int64_t L, int64_t P, int64_t C, int64_t n_
 
 // dig_tilehits.hip: the sizes of a score plane [C, R, T]; DIG_EINVAL (in the name of entry point `fn`) unless C R < 2^31 and T < 2^31
 int tile_select_sizes(const char* fn, int64_t C, int64_t R, int64_t T);
+
+// dig_tilewindows.hip: tile_select_sizes and 1 <= width <= DIG_TILE_WINDOW_MAX_WIDTH, for dig_tile_window_test and its host twin
+int tile_window_sizes(const char* fn, int64_t C, int64_t R, int64_t T, int32_t width);
 
 // dig_tilesamples.hip: the bits of the global-sample field of a tile-sample key, ((cohort R + region) T + tile) << bits | global sample
 // (bits for n_samples + 1 values: the all-ones key is no real one); DIG_EINVAL (in the name of entry point `fn`) when the two fields

@@ -1286,6 +1286,41 @@ def tiled_nb_model(genome, chroms, starts, ends, s_prob, mu, sigma, mut_chrom, m
     return res
 
 
+TILE_WINDOW_MAX_WIDTH = 2048        # DIG_TILE_WINDOW_MAX_WIDTH (include/dig_hip.h)
+
+
+def tile_window_test(pt, k, mu, sigma, n_valid, width, device=0, out=None):
+    """The NB test of every window of `width` consecutive tiles (dig_tile_window_test): pt f64, k i32 [C, R, T] and n_valid i32 [R] as
+    base_tile_probs and tile_mut_counts / tile_sample_counts leave them, mu, sigma f64 [C, R].  Returns dict(pt, exp, pval f64, k i32
+    [C, R, T]; n_windows i32 [R]): window t of region r covers the tiles t .. min(t + width, n_valid[r]) - 1; n_windows[r] is
+    max(n_valid[r] - width + 1, 1), or 0 for a region without tiles; pt is the window's sum added left to right, k the integer sum,
+    pval and exp the test of tiled_nb_test on them (the same bits); behind the last window pt, exp, pval are NaN and k is 0.
+    Device tensors in -> device tensors out; arrays go through the host twin.  out: a dict a former call returned, for the same
+    shapes: its planes are written again (nb_model_window_hits keeps one set for all its widths).  ValueError for what the library
+    refuses: a width outside [1, TILE_WINDOW_MAX_WIDTH], C R or T at or above 2^31."""
+    if isinstance(width, bool) or int(width) != width:
+        raise ValueError("width: an integer >= 1")
+    width = int(width)
+    be = backend_of(pt, k, n_valid, device=device)
+    pt, k = be.arr(pt, "f64"), be.arr(k, "i32")
+    if pt.ndim != 3 or tuple(k.shape) != tuple(pt.shape):
+        raise ValueError("pt and k must be [C, R, T]")
+    C, R, T = (int(s) for s in pt.shape)
+    mu, sigma, n_valid = be.arr(mu, "f64", (C, R)), be.arr(sigma, "f64", (C, R)), be.arr(n_valid, "i32", (R,))
+    if out is None:
+        out = dict(pt=be.empty((C, R, T), "f64"), k=be.empty((C, R, T), "i32"), exp=be.empty((C, R, T), "f64"),
+                   pval=be.empty((C, R, T), "f64"), n_windows=be.empty(R, "i32"))
+    p = be.ptr
+    with _requirements_as_value_errors():
+        be.call("dig_tile_window_test", p(pt), p(k), p(mu), p(sigma), p(n_valid), C, R, T, width, p(out["pt"]), p(out["k"]), p(out["exp"]),
+                p(out["pval"]), p(out["n_windows"]))
+    if C * R * T == 0 and R:
+        # (nothing was launched: the region table from n_valid alone)
+        nv = n_valid.clip(0, T)
+        out["n_windows"][:] = (nv > 0) * (nv - width + 1).clip(1)
+    return out
+
+
 # ---------------------------------------------------------------------------
 # per-base route for the mutated tiles only (dig_tilesparse.hip): nothing here is [C, R, T]
 # ---------------------------------------------------------------------------

@@ -370,6 +370,139 @@ def nb_model_hits(d_prs, idx, mu, sigma, f_muts, f_fasta, n_up=2, n_down=2, bins
 
 
 # ---------------------------------------------------------------------------------------------
+# sliding windows of consecutive tiles (DESIGN.md "Sliding windows in the per-base route")
+# ---------------------------------------------------------------------------------------------
+_WINDOW_COLUMNS = ["WIDTH", "PEAK"]                    # behind the reference's columns, in front of QVAL
+
+
+def _check_widths(widths):
+    """The window widths of nb_model_window_hits as a list of ints, in the order given; ValueError for none, for one that is not an
+    integer >= 1 and for one given twice."""
+    try:
+        given = list(widths)
+    except TypeError:
+        given = [widths]
+    if not given:
+        raise ValueError("widths: at least one window width")
+    out = []
+    for w in given:
+        if isinstance(w, (bool, np.bool_)) or not isinstance(w, (int, np.integer, float, np.floating)) or w != w or int(w) != w or w < 1:
+            raise ValueError("widths: every width an integer >= 1 (got %r)" % (w,))
+        if int(w) in out:
+            raise ValueError("widths: width %d is given twice" % int(w))
+        out.append(int(w))
+    return out
+
+
+def window_peaks(region, tile, score, width):
+    """PEAK of the hits of one cohort at one width (host arrays, one entry per hit): inside every region the hits are walked in the
+    order of (score, tile); a hit is a peak unless a hit already marked as a peak overlaps it, |t1 - t2| < width.  Returns bool [hits]."""
+    region, tile, score = np.asarray(region, np.int64), np.asarray(tile, np.int64), np.asarray(score, float)
+    peak = np.zeros(len(tile), bool)
+    taken = {}                                          # region -> the tiles of its peaks
+    for i in np.lexsort((tile, score)):                 # (score first, then tile; regions do not interact)
+        mine = taken.setdefault(int(region[i]), [])
+        if all(abs(int(tile[i]) - t) >= width for t in mine):
+            peak[i] = True
+            mine.append(int(tile[i]))
+    return peak
+
+
+def nb_model_window_hits(d_prs, idx, mu, sigma, f_muts, f_fasta, n_up=2, n_down=2, binsize=50, widths=(2,), collapse=False, pval_max=None,
+                         fdr=None, device=0, max_muts_per_sample=None, max_muts_per_tile_per_sample=None, by_sample=False, cut_on="PVAL"):
+    """nb_model_hits over every window of m consecutive tiles, for each m of `widths`: "any m binsize consecutive positions of a
+    region" instead of the tiles of one grid.  One base_tile_probs and one counting pass (tile_mut_counts, or tile_sample_counts with
+    max_muts_per_sample / max_muts_per_tile_per_sample: OBS is then the capped count) over all cohorts; the base test is not run.  Per
+    width, in the order given: one engine.tile_window_test into planes that are reused from width to width, then the selection of
+    nb_model_hits (engine.tile_select, _fdr_cuts) with n_windows in the place of n_valid.
+    Window t of a region covers its tiles t .. t + m - 1; a region with fewer than m tiles has one window over all of them.
+    Returns C frames; rows by width as given, then as nb_model_hits orders them.  Columns: the reference's nine (POS: the middle of
+    the window's positions, (lo + hi) / 2 with hi cut at the region's last position; Pi, OBS, EXP, PVAL: the window's), WIDTH (hi -
+    lo + 1), PEAK (window_peaks per cohort, width and region), and QVAL with fdr: Benjamini-Hochberg per cohort and PER WIDTH over that
+    width's testable windows.  The index is the row number in the full frame of that width (the exclusive cumulative sum of n_windows,
+    plus t); attrs n_testable and n_windows hold one entry per width.
+    ValueError before any device work: by_sample or cut_on other than PVAL (the distinct samples of a window are not the sum of
+    its tiles'), an empty widths, a width that is not an integer >= 1 or above engine.TILE_WINDOW_MAX_WIDTH, a width given twice."""
+    if (pval_max is None) == (fdr is None):
+        raise ValueError("exactly one of pval_max and fdr must be given")
+    if by_sample or cut_on != "PVAL":
+        raise ValueError("windows take no by_sample and no cut_on other than PVAL: the distinct samples of a window are not the sum "
+                         "of its tiles' samples")
+    widths = _check_widths(widths)
+    from .. import engine
+    if max(widths) > engine.TILE_WINDOW_MAX_WIDTH:
+        raise ValueError("widths: at most %d tiles" % engine.TILE_WINDOW_MAX_WIDTH)
+    if n_up != n_down or n_up not in (1, 2):
+        raise NotImplementedError("the tile kernels take n_up = n_down = 1 or 2")
+    samples = _check_sample_options(max_muts_per_sample, max_muts_per_tile_per_sample, False)
+    import pandas as pd
+    from ..data_tools import cohort_rows, genome as genome_mod
+    C = len(d_prs)
+    f_muts = list(f_muts)
+    idx = np.asarray(idx)
+    R = len(idx)
+    mu, sigma = np.asarray(mu, float).reshape(C, R), np.asarray(sigma, float).reshape(C, R)
+    if len(f_muts) != C:
+        raise ValueError("one mutation file per cohort: %d files for %d cohorts" % (len(f_muts), C))
+    g = f_fasta if isinstance(f_fasta, genome_mod.PackedGenome) else genome_mod.PackedGenome.from_fasta(f_fasta)
+    chroms = [str(c) for c in idx[:, 0]] if R else []
+    starts, ends = (idx[:, 1].astype(np.int64), idx[:, 2].astype(np.int64)) if R else (np.zeros(0, np.int64),) * 2
+    known = set(n.replace("chr", "") for n in g.names)
+    rows = _cohort_rows(f_muts, known, samples, max_muts_per_sample)
+    mc, ms, me = cohort_rows.column(rows, "chrom"), cohort_rows.column(rows, "start", "i64"), cohort_rows.column(rows, "end", "i64")
+    co = cohort_rows.cohort_column(rows, "start")
+    s_prob = np.stack([_s_prob_table(d, n_up, collapse) for d in d_prs])
+    # the front half, once for every width
+    pt, first_d, nval_d = engine.base_tile_probs(g, chroms, starts, ends, s_prob, binsize, device=device)
+    T = int(pt.shape[2])
+    if samples:
+        sa = _sample_arguments(rows, max_muts_per_tile_per_sample, False)
+        k, _ = engine.tile_sample_counts(g, chroms, starts, ends, first_d, nval_d, mc, ms, me, co, sa["mut_sample"], sa["sample_offsets"],
+                                         sa["keep"], sa["cap"], C, binsize, T)
+    else:
+        k = engine.tile_mut_counts(g, chroms, starts, ends, first_d, nval_d, mc, ms, me, co, C, binsize, T)
+    first, nval = first_d.cpu().numpy(), np.clip(nval_d.cpu().numpy().astype(np.int64), 0, T)
+    n_pos = _region_positions(g, chroms, ends, first, n_up) if R else np.zeros(0, np.int64)
+    last = first + n_pos                                       # one past a region's last position
+    planes = None
+    per_width = []                                             # (m, hits as host arrays, cohort_ptr, n_testable [C], n_windows [R])
+    for m in widths:
+        planes = engine.tile_window_test(pt, k, mu, sigma, nval_d, m, device=device, out=planes)
+        nwin_d = planes["n_windows"]
+        if fdr is not None:
+            cuts, n_test = _fdr_cuts(planes["pval"], nwin_d, fdr)
+        else:
+            cuts = np.full(C, float(pval_max))
+            n_test = engine.tile_select_counts(planes["pval"], nwin_d, float("inf")).sum(dim=1).cpu().numpy()
+        hits = engine.tile_select(planes["pval"], nwin_d, cuts, pt=planes["pt"], exp=planes["exp"], k=planes["k"])
+        ptr = hits.pop("cohort_ptr")
+        per_width.append((m, {name: v.cpu().numpy() for name, v in hits.items()}, ptr, np.asarray(n_test), nwin_d.cpu().numpy().astype(np.int64)))
+    frames = []
+    for c in range(C):
+        cols = {name: [] for name in ("reg", "t", "k", "exp", "pval", "pt", "lo", "hi", "peak", "q", "row")}
+        for m, hits, ptr, n_test, nwin in per_width:
+            sel = slice(int(ptr[c]), int(ptr[c + 1]))
+            reg, t, score = hits["region"][sel].astype(np.int64), hits["tile"][sel].astype(np.int64), hits["score"][sel]
+            lo = first[reg] + t * binsize
+            hi = np.minimum(lo + np.minimum(m, nval[reg] - t) * binsize, last[reg]) - 1
+            cols["reg"].append(reg), cols["t"].append(t), cols["lo"].append(lo), cols["hi"].append(hi)
+            cols["k"].append(hits["k"][sel]), cols["exp"].append(hits["exp"][sel]), cols["pval"].append(score), cols["pt"].append(hits["pt"][sel])
+            cols["peak"].append(window_peaks(reg, t, score, m))
+            cols["q"].append(hits_q_values(score, int(n_test[c])) if fdr is not None else score)
+            cols["row"].append((np.cumsum(nwin) - nwin)[reg] + t)
+        cat = {name: np.concatenate(v) for name, v in cols.items()}
+        df = _tile_frame(idx, mu[c], sigma[c], first, n_pos, binsize, cat["reg"], cat["t"], cat["k"], cat["exp"], cat["pval"], cat["pt"])
+        df["POS"] = (cat["lo"] + cat["hi"]) / 2.0
+        df["WIDTH"], df["PEAK"] = (cat["hi"] - cat["lo"] + 1).astype(float), cat["peak"].astype(bool)
+        if fdr is not None:
+            df["QVAL"] = cat["q"]
+        df.index = pd.Index(cat["row"], dtype=np.int64)
+        df.attrs.update(n_testable=[int(w[3][c]) for w in per_width], n_windows=[int(w[4].sum()) for w in per_width])
+        frames.append(df)
+    return frames
+
+
+# ---------------------------------------------------------------------------------------------
 # the per-base scan over the mutated tiles only (DESIGN.md "Sparse per-base scan")
 # ---------------------------------------------------------------------------------------------
 ZERO_FLOOR_MARGIN = 4e-6       # p-values are pinned to 1e-6 relative, pt to 1e-12: both sides' error twice over

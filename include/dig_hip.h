@@ -42,7 +42,7 @@ extern "C" {
                              * DIG_PIPE_PACKED_COUNTS (round 5's measured losers: tools/rejected/r05_*.patch); still 12: + dig_panel_row_keys,
                              * dig_panel_counts and their _host twins (additions); + dig_tile_sample_keys, dig_tile_sample_counts and
                              * their _host twins (additions); + dig_tile_census(_workspace), dig_sparse_tile_keys, dig_sparse_tile_test
-                             * and their _host twins (additions) */
+                             * and their _host twins (additions); + dig_tile_window_test and its _host twin (additions) */
 
 /* dtype codes for dig_gather_bins */
 #define DIG_F32 0
@@ -581,6 +581,29 @@ int dig_sparse_tile_test_host(const uint32_t *genome_words, int64_t n_words, con
                               const double *mu, const double *sigma, const int64_t *keys_sorted, int64_t n, int32_t *out_cohort,
                               int32_t *out_region, int32_t *out_tile, int32_t *out_k, double *out_pt, double *out_exp,
                               double *out_pval, int device);
+
+/* ---- sliding windows in the per-base route (additive: the ABI version stays) --------------------------------------- *
+ * The NB test of every run of `width` = m consecutive tiles of a region, from the base planes pt f64, k i32 [C, R, T] and n_valid
+ * i32 [R] as dig_base_tile_probs* and dig_tile_mut_counts (or dig_tile_sample_counts) leave them; mu, sigma f64 [C, R].  With
+ * nv = min(n_valid[r], T) (n_valid[r] <= 0: the region has no tiles):
+ *   n_windows i32 [R]: 0 when nv <= 0, else max(nv - m + 1, 1).  Window t of region r covers the tiles t .. min(t + m, nv) - 1: a
+ *     region has full windows only, or a single window over all its tiles when it has fewer than m.
+ *   pt_w f64 [C, R, T]: the window's pt values added LEFT TO RIGHT in float64, ((pt[t] + pt[t + 1]) + pt[t + 2]) + ..., the first
+ *     term taken as it is.  The order is part of the contract.   k_w i32 [C, R, T]: the integer sum.
+ *   pval_w, exp_w f64 [C, R, T]: alpha, theta from (mu, sigma), p = 1 / (pt_w theta + 1), pval_w = nb_exact(k_w, alpha, p),
+ *     exp_w = pt_w mu -- the device functions of dig_tiled_nb_test: equal inputs give equal bits, and width 1 gives its planes.
+ *   For t >= n_windows[r]: pt_w is the NaN of the base planes, k_w 0, and exp_w, pval_w what dig_tiled_nb_test makes of those (NaN).
+ * pt_w, k_w, exp_w, pval_w and n_windows may each be NULL and are then skipped.  DIG_TILE_WINDOW_MAX_WIDTH is the largest width (a
+ * workgroup stages 1024 tiles and the width - 1 behind them in LDS).  DIG_EINVAL, before anything is read or launched, for a width
+ * outside [1, DIG_TILE_WINDOW_MAX_WIDTH], C R >= 2^31, T >= 2^31 or more than 2^31 - 1 workgroups (C R ceil(T / 1024)).  Nothing is
+ * launched or written -- n_windows neither -- when C R T = 0.  Every typed pointer needs the alignment of its element and no more. */
+#define DIG_TILE_WINDOW_MAX_WIDTH 2048
+int dig_tile_window_test(const double *pt, const int32_t *k, const double *mu, const double *sigma, const int32_t *n_valid, int64_t C,
+                         int64_t R, int64_t T, int32_t width, double *pt_w, int32_t *k_w, double *exp_w, double *pval_w,
+                         int32_t *n_windows, void *stream);
+int dig_tile_window_test_host(const double *pt, const int32_t *k, const double *mu, const double *sigma, const int32_t *n_valid,
+                              int64_t C, int64_t R, int64_t T, int32_t width, double *pt_w, int32_t *k_w, double *exp_w,
+                              double *pval_w, int32_t *n_windows, int device);
 
 /* ---- sufficient statistics in canonical chunks (bin-sharded runs) --------------------------- *
  * Same quantity as dig_scale_suffstats / dig_scale_factors, defined so that it does not depend on the sharding: the bins

@@ -11,6 +11,7 @@ run through libdig_hip.so; `model` may be the reference's HDF5 map (`*.h5`, read
 io/pandas_fixed.py: no h5py or PyTables needed) or the directory mirror described in digdriver_amd/io/mapfile.py.
 """
 import argparse
+import functools
 import os
 import sys
 
@@ -182,10 +183,20 @@ def cmd_tile(args):
     <outdir>/<outpfx>.hits.txt (the rows of nb_model's frame, numbered as in it; with --fdr a QVAL column as well).  --sparse tests
     the mutated tiles only (nb_model_hits_sparse; --bonferroni is its third cut, the sample options are not part of it).  The sample
     options (--max-muts-per-sample, --max-muts-per-tile-per-sample, --by-sample, --cut-on) read the sample label from column 6 of
-    the mutation files; --by-sample adds OBS_SAMPLES and PVAL_SAMPLE behind REGION."""
+    the mutation files; --by-sample adds OBS_SAMPLES and PVAL_SAMPLE behind REGION.  --window-tiles M [M ...] tests every window of M
+    consecutive tiles instead (nb_model_window_hits: WIDTH and PEAK behind REGION; not with --sparse, --by-sample, --cut-on PVAL_SAMPLE)."""
     n = len(args.mutation_files)
     if not len(args.maps) == len(args.outpfx) == n:
         raise SystemExit("ERROR: --mutation-files, --maps and --outpfx must name the same number of cohorts.")
+    if args.window_tiles is not None:
+        if args.sparse:
+            raise SystemExit("ERROR: --window-tiles is not part of --sparse (the sparse scan tests single tiles).")
+        if args.by_sample:
+            raise SystemExit("ERROR: --window-tiles does not take --by-sample (the samples of a window are not the sum of its tiles' samples).")
+        if args.cut_on != 'PVAL':
+            raise SystemExit("ERROR: --window-tiles selects on PVAL only (--cut-on PVAL_SAMPLE needs --by-sample, which it does not take).")
+        if min(args.window_tiles) < 1 or len(set(args.window_tiles)) != len(args.window_tiles):
+            raise SystemExit("ERROR: --window-tiles takes distinct integers >= 1.")
     if args.bonferroni is not None and not args.sparse:
         raise SystemExit("ERROR: --bonferroni is valid only with --sparse.")
     if args.sparse:
@@ -250,10 +261,12 @@ def cmd_tile(args):
                 '' if frame.attrs['complete'] else ' (mutated tiles only)', target))
             mapfile.write_results_tsv(frame, target)
         return
+    # (--window-tiles alone picks the other function: without it the call is the one of before)
+    scan = nb_model.nb_model_hits if args.window_tiles is None else functools.partial(nb_model.nb_model_window_hits, widths=args.window_tiles)
     try:
-        frames = nb_model.nb_model_hits(d_prs, idx[keep], np.array(mu)[:, keep], np.array(sigma)[:, keep], args.mutation_files,
-                                        args.f_fasta, n_up=args.up, n_down=args.down, binsize=args.binsize, pval_max=args.pval_max,
-                                        fdr=args.fdr, **sample_opts)
+        frames = scan(d_prs, idx[keep], np.array(mu)[:, keep], np.array(sigma)[:, keep], args.mutation_files,
+                      args.f_fasta, n_up=args.up, n_down=args.down, binsize=args.binsize, pval_max=args.pval_max,
+                      fdr=args.fdr, **sample_opts)
     except ValueError as exc:
         if not sample_opts or 'column 6' not in str(exc):
             raise
@@ -261,7 +274,11 @@ def cmd_tile(args):
     os.makedirs(args.outdir, exist_ok=True)
     for pfx, frame in zip(args.outpfx, frames):
         target = os.path.join(args.outdir, pfx + '.hits.txt')
-        print('\t{}: {} hits of {} testable tiles; saving to {}'.format(pfx, len(frame), frame.attrs['n_testable'], target))
+        if args.window_tiles is None:
+            print('\t{}: {} hits of {} testable tiles; saving to {}'.format(pfx, len(frame), frame.attrs['n_testable'], target))
+        else:
+            print('\t{}: {} hits of {} testable windows (widths {}); saving to {}'.format(
+                pfx, len(frame), frame.attrs['n_testable'], args.window_tiles, target))
         mapfile.write_results_tsv(frame, target)
 
 
@@ -358,6 +375,9 @@ def parse_args(text=None):
                    help='add OBS_SAMPLES (samples with a row in the tile) and PVAL_SAMPLE (the test on it)')
     d.add_argument('--cut-on', choices=['PVAL', 'PVAL_SAMPLE'], default='PVAL',
                    help='the score --pval-max / --fdr select on (PVAL_SAMPLE requires --by-sample)')
+    # every run of M consecutive tiles instead of the tiles of one grid (DESIGN.md "Sliding windows in the per-base route")
+    d.add_argument('--window-tiles', type=int, nargs='+', default=None, metavar='M',
+                   help='test every window of M consecutive tiles, for each M given (adds WIDTH and PEAK; not with --sparse, --by-sample)')
     d.set_defaults(func=cmd_tile)
 
     # not a reference sub-command: quickDriver for many cohorts at once (driver_model/cohort_batch.py run_quick_cohorts)
