@@ -25,6 +25,10 @@ the argument, the side and the first byte offset; `guarded_runs` runs both varia
 Limit: an over-READ whose value never reaches an output is not detectable this way (and, inside the slab, harmless); an
 over-read that does reach one is seen as an A / B difference, not located.  Stores are located exactly, up to a band's width
 (a store further than 64 KiB from its buffer lands in a neighbour's band or buffer, or outside the slab).
+
+On a GPU `guarded_runs` adds a fourth run that pins on which QUEUE the call works: the same call inside a side stream while the
+default stream is held busy (`side_stream_run`; `side_stream_call` is the same protocol for a route of the package, used by
+tests/test_gpu_side_streams.py).  `judge_side_run` is its verdict, a pure function tested on the CPU.  DESIGN.md section 5.6.
 """
 import bisect
 
@@ -250,10 +254,259 @@ def same_bits(x, y):
     return x.shape == y.shape and x.dtype == y.dtype and np.array_equal(x.reshape(-1).view(np.uint8), y.reshape(-1).view(np.uint8))
 
 
-def guarded_runs(bufs, invoke, device="cpu", what="", plain=False):
+# ---- the side-stream run ----------------------------------------------------------------------------------------------------------
+# On the null stream a kernel, memset, copy or host wait issued on the wrong queue still gives the right answer.  Here the call
+# runs on a side stream while the default stream is held busy by a delay enqueued in front of everything else on it:
+#   reading R1 (after side.synchronize() alone, copied on the side stream) still holds poison where a PRODUCER went to the default stream;
+#   reading R2 (after the device is idle) differs where a memset or copy went there and CLOBBERED the result after the fact;
+#   the default stream must still be busy when R1 has been read: otherwise the call waited for it (or for the device), or the delay
+#   was too short, and the case is INCONCLUSIVE -- a failure, never a pass or a skip.
+MIN_DELAY_MS, DELAY_FACTOR, MAX_DELAY_MS = 20.0, 10.0, 2000.0
+SIDE = {"streams": [], "tried": 0, "cycles_per_ms": None, "muls_per_ms": None, "busy": None, "runs": 0}       # one per process
+
+
+class SideStreamViolation(GuardViolation):
+    pass
+
+
+def _first_difference(x, y):
+    """The first element at which two arrays of one type and shape differ in their bits (None: none)."""
+    x, y = np.ascontiguousarray(x), np.ascontiguousarray(y)
+    if x.shape != y.shape or x.dtype != y.dtype:
+        return 0
+    w = max(x.dtype.itemsize, 1)
+    d = np.flatnonzero(x.reshape(-1).view(np.uint8) != y.reshape(-1).view(np.uint8))
+    return int(d[0]) // w if d.size else None
+
+
+def judge_side_run(r1, r2, plain, still_busy, what=""):
+    """The verdict of one side-stream run, a pure function of its four observations: r1, r2, plain are dicts output name -> numpy
+    array (R1 read on the side stream after its synchronisation alone, R2 after the device went idle, the same call on the default
+    stream), still_busy whether the default stream was still busy once R1 had been read.  Raises SideStreamViolation under one of
+    three names -- "inconclusive", "late producer", "late clobber" -- with the output, the reading and the first element."""
+    what = what or "the call"
+    if not still_busy:
+        raise SideStreamViolation("%s: inconclusive: the default stream was idle once the side stream's results had been read -- the call "
+                                  "waited for the default stream or for the whole device, or the delay in front of it was too short" % what)
+    for name in plain:
+        e = _first_difference(r1[name], plain[name])
+        if e is not None:
+            raise SideStreamViolation("%s: late producer: output `%s` was not ready when the side stream was (something that produces it "
+                                      "was issued on another stream): reading R1 differs from the default-stream run, first at element %d"
+                                      % (what, name, e))
+    for name in plain:
+        e = _first_difference(r2[name], plain[name])
+        if e is not None:
+            raise SideStreamViolation("%s: late clobber: output `%s` changed after the side stream had finished (a memset or copy was "
+                                      "issued on another stream): reading R2 differs from the default-stream run, first at element %d"
+                                      % (what, name, e))
+
+
+def _timed_ms(torch, fn):
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    fn()
+    b.record()
+    b.synchronize()
+    return a.elapsed_time(b)
+
+
+def _calibrate(torch, dev):
+    """Once per process, two events around a delay on an idle device: spin cycles of torch.cuda._sleep per millisecond (it touches
+    no memory, so it does not compete for HBM with the call under test); without that attribute the multiplications of a 256 MiB
+    tensor per millisecond, the loop of tests/test_gpu_backend_forms.py test_scale_factors_land_on_the_current_stream."""
+    if SIDE["cycles_per_ms"] or SIDE["muls_per_ms"]:
+        return
+    torch.cuda.synchronize(dev)
+    if hasattr(torch.cuda, "_sleep"):
+        torch.cuda._sleep(1000)                                                        # (loads the kernel)
+        torch.cuda.synchronize(dev)
+        cycles = 1_000_000
+        while True:
+            ms = _timed_ms(torch, lambda: torch.cuda._sleep(cycles))
+            if ms >= 5.0 or cycles >= 1 << 36:
+                break
+            cycles *= 8
+        SIDE["cycles_per_ms"] = cycles / ms
+    else:
+        SIDE["busy"] = busy = torch.ones(1 << 26, dtype=torch.float32, device=dev)
+        busy.mul_(1.0001)
+        torch.cuda.synchronize(dev)
+        SIDE["muls_per_ms"] = 50 / _timed_ms(torch, lambda: [busy.mul_(1.0001) for _ in range(50)])
+
+
+def enqueue_delay(torch, dev, ms):
+    """About `ms` milliseconds of work on the CURRENT stream that nothing else waits for."""
+    _calibrate(torch, dev)
+    if SIDE["cycles_per_ms"]:
+        torch.cuda._sleep(int(ms * SIDE["cycles_per_ms"]))
+    else:
+        for _ in range(int(ms * SIDE["muls_per_ms"]) + 1):
+            SIDE["busy"].mul_(1.0001)
+
+
+def side_streams(torch, dev, n=1):
+    """The process's n (1 or 2) side streams, made once.  A stream may share a hardware queue with the null stream and then runs
+    behind it, so each is probed when it is made: a delay on the default stream, a one-element kernel on the candidate, its
+    synchronisation, and the default stream must still be busy.  A candidate that fails is dropped for the next stream of torch's
+    pool (32 streams handed out in turn), at most 8 draws in all: a draw that returns a stream already kept counts as one."""
+    assert n in (1, 2)
+    _calibrate(torch, dev)
+    default = torch.cuda.default_stream(dev)
+    while len(SIDE["streams"]) < n:
+        if SIDE["tried"] >= 8:
+            raise SideStreamViolation("no stream independent of the default stream among the first 8 of torch's pool: each ran behind "
+                                      "a delay enqueued on the default stream (do they all share its hardware queue?)")
+        SIDE["tried"] += 1
+        cand = torch.cuda.Stream(device=dev)
+        if any(cand.cuda_stream == s.cuda_stream for s in SIDE["streams"]):
+            continue
+        one = torch.zeros(1, device=dev)
+        torch.cuda.synchronize(dev)
+        with torch.cuda.stream(default):
+            enqueue_delay(torch, dev, MIN_DELAY_MS)
+        with torch.cuda.stream(cand):
+            one.add_(1.0)
+        cand.synchronize()
+        independent = default.query() is False
+        torch.cuda.synchronize(dev)
+        if independent and float(one) == 1.0:
+            SIDE["streams"].append(cand)
+    return SIDE["streams"][:n]
+
+
+def delay_for(plain_ms, what=""):
+    """The delay in front of a case: 10 times the host wall time of its default-stream run (enqueue to synchronize; the factor covers
+    host jitter and a stream's first use), at least 20 ms.  More than 2 s: the case is too large for a side-stream run."""
+    ms = max(MIN_DELAY_MS, DELAY_FACTOR * plain_ms)
+    if ms > MAX_DELAY_MS:
+        raise SideStreamViolation("%s: its default-stream run took %.0f ms on the host, so its side-stream run would need a delay of "
+                                  "%.0f ms: shrink the case (limit %.0f ms)" % (what or "the call", plain_ms, ms, MAX_DELAY_MS))
+    SIDE["runs"] += 1
+    return ms
+
+
+def side_stream_run(bufs, invoke, device, what, plain_out, plain_ms):
+    """The fourth run of guarded_runs: `invoke` on a variant-B arena inside torch.cuda.stream(side), the default stream busy."""
+    import torch
+    dev = torch.device(device)
+    side, = side_streams(torch, dev, 1)
+    default = torch.cuda.default_stream(dev)
+    names = [n for n, b in bufs.items() if b.role == "out"]
+    ms = delay_for(plain_ms, what)
+    arena = GuardedArena(bufs, "B", dev)
+    torch.cuda.synchronize(dev)
+    with torch.cuda.stream(default):
+        enqueue_delay(torch, dev, ms)
+    with torch.cuda.stream(side):
+        invoke(arena)
+        side.synchronize()
+        r1 = {n: arena.read(n) for n in names}                                         # (copied on `side` as well)
+    still_busy = default.query() is False
+    torch.cuda.synchronize(dev)
+    r2 = {n: arena.read(n) for n in names}
+    arena.assert_intact("%s (side stream)" % (what or "the call"))
+    judge_side_run(r1, r2, plain_out, still_busy, "%s (side stream)" % (what or "the call"))
+
+
+def _host_copy(torch, x):
+    """A tensor, or a dict / list / tuple of tensors, host values and None -> the same with every tensor as a numpy array (its
+    bits: bf16 and bool through integers), copied on the current stream."""
+    if isinstance(x, dict):
+        return {k: _host_copy(torch, v) for k, v in x.items()}
+    if isinstance(x, (list, tuple)):
+        return [_host_copy(torch, v) for v in x]
+    if isinstance(x, torch.Tensor):
+        if x.dtype == torch.bfloat16:
+            x = x.view(torch.int16)
+        return x.cpu().numpy().copy()
+    return x
+
+
+def _flatten(x, prefix, into):
+    if isinstance(x, dict):
+        for k, v in x.items():
+            _flatten(v, "%s.%s" % (prefix, k) if prefix else str(k), into)
+    elif isinstance(x, (list, tuple)):
+        for i, v in enumerate(x):
+            _flatten(v, "%s[%d]" % (prefix, i), into)
+    elif x is not None:
+        into[prefix or "result"] = np.asarray(x)
+    return into
+
+
+def _spoil(torch, x):
+    """Overwrite every tensor of a result (or of a plan's scratch) so that neither it nor the allocator's next block holds a right answer."""
+    if isinstance(x, dict):
+        x = list(x.values())
+    if isinstance(x, (list, tuple)):
+        for v in x:
+            _spoil(torch, v)
+    elif isinstance(x, torch.Tensor) and x.numel():
+        # (bytes -- a workspace -- get the arena's poison B, which every guarded entry point has run on; other integers are outputs only)
+        x.fill_(float("nan") if x.dtype.is_floating_point else (False if x.dtype == torch.bool else 1 if x.dtype == torch.uint8 else 85))
+
+
+def side_stream_call(fn, device, what, explicit=False, scratch=(), restore=None):
+    """The same protocol one level up, for a route of the package: fn(stream) returns its results (tensors, or a dict / list of
+    tensors and host values).  The reference is fn(None) on the default stream, compared bit for bit.
+
+    scratch: tensors that outlive a call and that the call writes before it reads them -- a plan's intermediates, its workspace.  They
+    are overwritten between the reference run and the side run together with the reference's outputs: otherwise they would still
+    hold the reference run's (equal) values, and a kernel or copy that fills them on the wrong queue could not be seen.  restore: called
+    behind that on the default stream, for what a plan wrote into its scratch when it was built and never writes again.
+
+    explicit=False, the current-stream form: fn(None) runs inside torch.cuda.stream(side).
+    explicit=True: fn(side) runs with the busy default stream current; only the reads are issued inside torch.cuda.stream(side).
+    Returns the reference's host arrays (flattened: name -> numpy array)."""
+    import time
+    import torch
+    dev = torch.device(device)
+    side, = side_streams(torch, dev, 1)
+    default = torch.cuda.default_stream(dev)
+    _spoil(torch, fn(None))                     # (untimed: the first call of a route loads kernels and uploads what it keeps resident)
+    torch.cuda.synchronize(dev)
+    t0 = time.perf_counter()
+    ref_dev = fn(None)
+    torch.cuda.synchronize(dev)
+    ms = delay_for((time.perf_counter() - t0) * 1e3, what)
+    plain = _flatten(_host_copy(torch, ref_dev), "", {})
+    _spoil(torch, ref_dev)                      # outputs that persist (a plan's) must be produced again; freed ones hold no right answer
+    _spoil(torch, list(scratch))
+    if restore is not None:
+        restore()
+    del ref_dev
+    torch.cuda.synchronize(dev)
+    with torch.cuda.stream(default):
+        enqueue_delay(torch, dev, ms)
+    if explicit:
+        got = fn(side)
+        side.synchronize()
+        with torch.cuda.stream(side):
+            r1 = _flatten(_host_copy(torch, got), "", {})
+    else:
+        with torch.cuda.stream(side):
+            got = fn(None)
+            side.synchronize()
+            r1 = _flatten(_host_copy(torch, got), "", {})
+    still_busy = default.query() is False
+    torch.cuda.synchronize(dev)
+    r2 = _flatten(_host_copy(torch, got), "", {})
+    _spoil(torch, got)
+    torch.cuda.synchronize(dev)
+    assert set(r1) == set(plain) == set(r2), (what, sorted(plain), sorted(r1))
+    judge_side_run(r1, r2, plain, still_busy, "%s (%s)" % (what, "stream=side" if explicit else "side stream current"))
+    return plain
+
+
+def guarded_runs(bufs, invoke, device="cpu", what="", plain=False, side_stream=True):
     """Run `invoke(arena)` on a variant-A and a variant-B arena.  Checks (a) every band intact after each run and (b) every
-    output bit-identical between the two; with plain=True also on PlainBuffers, whose outputs must carry the same bits.  Returns
-    dict name -> numpy array of the outputs (role "out") for the caller's comparison with the reference, check (c)."""
+    output bit-identical between the two; with plain=True also on PlainBuffers, whose outputs must carry the same bits.  On a GPU
+    and with side_stream=True a fourth run follows (side_stream_run): the call on a side stream while the default stream is busy,
+    against the PlainBuffers run (made for it where plain=False).  Returns dict name -> numpy array of the outputs (role "out") for
+    the caller's comparison with the reference, check (c)."""
+    import time
+    on_gpu = str(device).startswith("cuda")
     res = {}
     for variant in ("A", "B"):
         arena = GuardedArena(bufs, variant, device)
@@ -266,14 +519,21 @@ def guarded_runs(bufs, invoke, device="cpu", what="", plain=False):
             raise GuardViolation("%s: output `%s` depends on what lies around its arguments or in its scratch: poison A and B give "
                                  "different bits, first at byte offset %d (element %d)" %
                                  (what or "the call", n, int(d[0]), int(d[0]) // bufs[n].np.itemsize))
-    if plain:
+    side_stream = side_stream and on_gpu
+    if plain or side_stream:
         pb = PlainBuffers(bufs, device)
+        pb.assert_intact()                                       # (the copies in are done: the time below is the call's own)
+        t0 = time.perf_counter()
         invoke(pb)
         pb.assert_intact()
-        for n in res["A"]:
-            got = pb.read(n)
+        plain_ms = (time.perf_counter() - t0) * 1e3
+        plain_out = {n: pb.read(n) for n in res["A"]}
+        for n in res["A"] if plain else ():
+            got = plain_out[n]
             if not same_bits(res["A"][n], got):
                 d = np.flatnonzero(res["A"][n].reshape(-1).view(np.uint8) != got.reshape(-1).view(np.uint8))
                 raise GuardViolation("%s: output `%s` at the documented minimum alignment differs from the call on ordinary tensors, "
                                      "first at element %d" % (what or "the call", n, int(d[0]) // bufs[n].np.itemsize))
+    if side_stream:
+        side_stream_run(bufs, invoke, device, what, plain_out, plain_ms)
     return res["A"]

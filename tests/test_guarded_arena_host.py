@@ -4,7 +4,7 @@ per argument (`arena.window(name, lo, hi)` is pointer arithmetic on it) and the 
 import numpy as np
 import pytest
 
-from guarded_arena import BAND, GuardViolation, GuardedArena, guarded_runs, inp, out, ws
+from guarded_arena import BAND, GuardViolation, GuardedArena, SideStreamViolation, guarded_runs, inp, judge_side_run, out, ws
 
 N = 1000
 
@@ -158,3 +158,52 @@ def test_plain_buffers_run_the_same_call_and_a_difference_from_them_is_reported(
 
     with pytest.raises(GuardViolation, match="differs from the call on ordinary tensors"):
         guarded_runs(_bufs(), depends_on_alignment, plain=True)
+
+
+# ---- the side-stream verdict: a pure function of (R1, R2, plain, still_busy), here on what four stand-ins would leave behind ---------
+def _readings(kind):
+    """What the side-stream run of guarded_runs observes of a call that fills `y` (pre-filled with poison B, 1e300) and zeroes `n`."""
+    plain = {"y": np.arange(1.0, 9.0), "n": np.zeros(3, np.int32)}
+    r1, r2, busy = {k: v.copy() for k, v in plain.items()}, {k: v.copy() for k, v in plain.items()}, True
+    if kind == "late producer":              # the kernel that writes y went to the default stream: R1 still holds the poison
+        r1["y"][:] = 1e300
+    elif kind == "late clobber":             # the memset of n went to the default stream and ran after the side stream's kernel
+        plain["n"][:] = r1["n"][:] = [4, 0, 7]
+    elif kind == "inconclusive":             # the call waited for the default stream: right values, nothing shown
+        busy = False
+    return r1, r2, plain, busy
+
+
+def test_side_stream_verdict_passes_a_correct_call():
+    assert judge_side_run(*_readings("correct"), what="stand-in") is None
+
+
+@pytest.mark.parametrize("kind, detail", [("late producer", r"output `y` .* reading R1 differs .* first at element 0$"),
+                                          ("late clobber", r"output `n` .* reading R2 differs .* first at element 0$"),
+                                          ("inconclusive", r"the default stream was idle")])
+def test_side_stream_verdict_names_what_went_wrong(kind, detail):
+    with pytest.raises(SideStreamViolation, match=r"stand-in: %s: %s" % (kind, detail)):
+        judge_side_run(*_readings(kind), what="stand-in")
+
+
+def test_side_stream_verdict_reports_the_first_element_and_puts_inconclusive_first():
+    r1, r2, plain, busy = _readings("correct")
+    r2["y"][5] = np.nan                                          # one element, late
+    with pytest.raises(SideStreamViolation, match=r"late clobber: output `y` .* first at element 5$"):
+        judge_side_run(r1, r2, plain, busy)
+    r1["y"][6] = -plain["y"][6]
+    with pytest.raises(SideStreamViolation, match=r"late producer: output `y` .* first at element 6$"):
+        judge_side_run(r1, r2, plain, busy)
+    with pytest.raises(SideStreamViolation, match=r"inconclusive"):       # wrong values prove nothing about an idle default stream
+        judge_side_run(r1, r2, plain, False)
+    assert issubclass(SideStreamViolation, GuardViolation)
+    zero, minus = {"y": np.array([0.0])}, {"y": np.array([-0.0])}         # bits, not values
+    with pytest.raises(SideStreamViolation, match=r"late producer"):
+        judge_side_run(minus, zero, zero, True)
+
+
+def test_cpu_callers_get_no_side_stream_run():
+    """device="cpu" (the helper's own tests, the `_host` twins): three runs as before, whatever side_stream says."""
+    calls = []
+    guarded_runs(_bufs(), lambda a: (calls.append(type(a).__name__), _correct(a)), plain=True, side_stream=True)
+    assert calls == ["GuardedArena", "GuardedArena", "PlainBuffers"]
