@@ -17,6 +17,7 @@ LIB_PATH = os.environ.get("DIG_HIP_LIB") or os.path.join(_HERE, "lib", "libdig_h
 DIG_F32, DIG_F64, DIG_I16, DIG_BF16 = 0, 1, 2, 3
 DIG_PIPE_CONTEXTS, DIG_PIPE_DOT, DIG_PIPE_STATISTICS, DIG_PIPE_WORKLIST_CLEAN, DIG_PIPE_COMPACT_L, DIG_PIPE_RECORDS = 1, 2, 4, 8, 16, 32
 DIG_REC_DOUBLES, DIG_REC_MU, DIG_REC_SIGMA, DIG_REC_ROBS_FLAG = 10, 7, 8, 9
+DIG_CNV_SCAN_CHUNK = 2048          # windows per chunk of dig_cnv_window_means' scan
 GENE_CLASSES = ("SYN", "MIS", "NONS", "SPL", "TRUNC", "NONSYN")
 GS_PLANES = tuple("EXP_" + c for c in GENE_CLASSES) + tuple("PVAL_%s_BURDEN" % c for c in GENE_CLASSES) + \
     tuple("PVAL_%s_BURDEN_SAMPLE" % c for c in GENE_CLASSES) + ("THETA_INDEL", "EXP_INDEL", "PVAL_INDEL_BURDEN", "PVAL_MUT_BURDEN")
@@ -92,6 +93,10 @@ _SIGNATURES = {
     "dig_window_sample_hits_host": [_vp] + [_i64] * 4 + [_vp, _int],
     "dig_window_objectives": [_vp, _i64, _vp, _vp] + [_i64] * 4 + [_vp, _vp, _vp],
     "dig_window_objectives_host": [_vp, _i64, _vp, _vp] + [_i64] * 4 + [_vp, _int],
+    "dig_cnv_segment_deltas": [_vp, _vp, _vp, _i64, _i64, _i64] + [_vp] * 6 + [_i64, _i64, _vp, _vp],
+    "dig_cnv_segment_deltas_host": [_vp, _vp, _vp, _i64, _i64, _i64] + [_vp] * 6 + [_i64, _i64, _vp, _int],
+    "dig_cnv_window_means": [_vp, _i64, _i64, _i64, _vp, _vp, _vp],
+    "dig_cnv_window_means_host": [_vp, _i64, _i64, _i64, _vp, _int],
     "dig_sequence_counts": [_vp, _i64, _vp, _vp] + [_i64] * 3 + [_vp, _vp],
     "dig_sequence_counts_host": [_vp, _i64, _vp, _vp] + [_i64] * 3 + [_vp, _int],
     "dig_site_match_count": [_vp] * 4 + [_i64, _i64] + [_vp] * 6 + [_i64] * 3 + [_vp, _vp],
@@ -186,6 +191,8 @@ _SIZE_QUERIES = {
     "dig_mutation_contexts_workspace": [_i64],
     "dig_element_context_counts_workspace": [_i64],
     "dig_tile_census_workspace": [_i64, _int],
+    "dig_cnv_segment_deltas_size": [_i64, _i64],
+    "dig_cnv_window_means_size": [_i64, _i64],
 }
 
 ABI_VERSION = 12         # include/dig_hip.h: DIG_ABI_VERSION

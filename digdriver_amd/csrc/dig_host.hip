@@ -438,6 +438,47 @@ int dig_window_objectives_host(const int64_t* keys_sorted, int64_t n_pairs, cons
                    N, C, n_uid, st.out(labels, NC), static_cast<int32_t*>(st.scratch(NC * sizeof(int32_t))), nullptr);
 }
 
+int dig_cnv_segment_deltas_host(const int64_t* win_start, const int64_t* chrom_id, const int64_t* chrom_off, int64_t n_chrom, int64_t N,
+                                int64_t W, const int64_t* seg_chrom, const int64_t* seg_start, const int64_t* seg_end,
+                                const uint8_t* seg_class, const int32_t* seg_weight, const int32_t* seg_cohort, int64_t n_seg, int64_t C,
+                                int64_t* deltas, int device)
+{
+    DIG_REQUIRE(n_chrom >= 0 && n_chrom <= N && n_seg >= 0, "0 <= n_chrom <= N, n_seg >= 0");
+    CnvSizes sz;
+    if (int rc = cnv_sizes(__func__, C, N, W, &sz)) return rc;
+    DIG_REQUIRE(deltas && chrom_off && (N == 0 || (win_start && chrom_id)), "non-null window tables and deltas");
+    DIG_REQUIRE(n_seg == 0 || (seg_chrom && seg_start && seg_end && seg_class && seg_weight && seg_cohort), "non-null segment arrays");
+    DIG_REQUIRE(chrom_off[0] == 0 && chrom_off[n_chrom] == N, "chrom_off: 0 first, N last");
+    for (int64_t r = 0; r < n_chrom; ++r) {
+        DIG_REQUIRE(chrom_off[r] < chrom_off[r + 1], "chrom_off ascending: every chromosome of chrom_id has a window");
+        DIG_REQUIRE(r == 0 || chrom_id[r - 1] < chrom_id[r], "chrom_id ascending");
+        for (int64_t n = chrom_off[r]; n < chrom_off[r + 1]; ++n) {
+            DIG_REQUIRE(win_start[n] >= 0 && win_start[n] < ((int64_t)1 << 40), "window starts within [0, 2^40)");
+            DIG_REQUIRE(n == chrom_off[r] || win_start[n - 1] < win_start[n], "window starts distinct and ascending within a chromosome");
+        }
+    }
+    for (int64_t i = 0; i < n_seg; ++i) {
+        DIG_REQUIRE(seg_start[i] >= 0 && seg_start[i] < seg_end[i] && seg_end[i] <= ((int64_t)1 << 40), "segments with 0 <= start < end <= 2^40");
+        DIG_REQUIRE(seg_class[i] <= 2 && seg_weight[i] >= 1, "class within [0, 2], weight >= 1");
+        DIG_REQUIRE(seg_cohort[i] >= 0 && seg_cohort[i] < C, "cohort within [0, C)");
+    }
+    Staging st(device);
+    return st.call(dig_cnv_segment_deltas, st.in(win_start, N), st.in(chrom_id, n_chrom), st.in(chrom_off, n_chrom + 1), n_chrom, N, W,
+                   st.in(seg_chrom, n_seg), st.in(seg_start, n_seg), st.in(seg_end, n_seg), st.in(seg_class, n_seg), st.in(seg_weight, n_seg),
+                   st.in(seg_cohort, n_seg), n_seg, C, st.out(deltas, (size_t)sz.delta_bytes / sizeof(int64_t)), nullptr);
+}
+
+int dig_cnv_window_means_host(const int64_t* deltas, int64_t N, int64_t C, int64_t W, double* labels, int device)
+{
+    CnvSizes sz;
+    if (int rc = cnv_sizes(__func__, C, N, W, &sz)) return rc;
+    if (N == 0) return DIG_OK;
+    DIG_REQUIRE(deltas && labels, "non-null pointers");
+    Staging st(device);
+    return st.call(dig_cnv_window_means, st.in(deltas, (size_t)sz.delta_bytes / sizeof(int64_t)), N, C, W, st.out(labels, (size_t)C * N * 3),
+                   static_cast<int64_t*>(st.scratch((size_t)sz.carry_bytes)), nullptr);
+}
+
 int dig_sequence_counts_host(const int32_t* pair_row, int64_t n_pairs, const int32_t* row_type, const int32_t* row_cohort, int64_t n,
                              int64_t K, int64_t C, int64_t* counts, int device)
 {

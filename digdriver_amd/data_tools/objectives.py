@@ -11,6 +11,12 @@ Two properties of the reference that are kept on purpose (DESIGN, Training label
     changes a label.  The argument is accepted and does nothing.
   * a sample's load in both sample filters is SAMPLE.value_counts() of the (window, sample) frame: the number of distinct windows
     the sample hits, not its number of mutations.
+
+The copy-number branch (add_objectives --cnv, DataExtractor.py:100-154,535-539) is window_cnv_objectives / add_cnv_objectives: per
+window [START, START + W), W = idx[0, 2] - idx[0, 1] for every window, the mean over its W positions of the duplication, copy-neutral
+/ LOH and deletion tracks of a cohort's segments, float64 [N, 3] per file (engine.window_cnv_means: dig_cnv_segment_deltas,
+dig_cnv_window_means).  The reference reads the segments through a tabix index; here the file is read whole (a bgzip file is a
+multi-member gzip file) and no index is needed.  DESIGN, Copy-number labels, has the decisions.
 """
 import numpy as np
 
@@ -145,4 +151,102 @@ def add_objectives(data_file, f_muts, suffix='', max_muts_per_sample=None, sampl
     _, labels = window_objectives(idx, f_muts, max_muts_per_sample, sample_filter_stdev, max_muts_per_elt_per_sample, on_device, device)
     for c, name in enumerate(names):
         mapfile.write_array(data_file, name, np.ascontiguousarray(labels[:, c]), append=True)
+    return names
+
+
+def _open_text(path):
+    """A text file that may be gzip or bgzip (a multi-member gzip file), told by its first two bytes."""
+    import gzip
+    with open(path, "rb") as f:
+        magic = f.read(2)
+    return gzip.open(path, "rt") if magic == b"\x1f\x8b" else open(path, "r")
+
+
+def encode_cnv_rows(f_cnv, chrom_ids):
+    """A copy-number segment file (tab-separated, no header, plain or gzip / bgzip: chr start end cp_num cp_Maj cp_min donor) as the
+    arrays engine.window_cnv_means takes, for one cohort.  Only chr, start, end and cp_num are read.  Chromosome labels are compared as
+    TEXT with `chrom_ids` (label -> id of the windows' chromosomes), as the reference queries its index with the decimal form of idx's
+    CHROM: '1' matches, 'chr1' does not, and rows on other chromosomes are left out.  Every row counts: no de-duplication, no sample
+    filter.  Class and weight come from cp_num alone: 2 -> LOH (1), weight 1, whatever cp_min says; below 2 -> deletion (2), weight
+    2 - cp_num; above 2 -> duplication (0), weight cp_num - 2.
+    ValueError, naming the file and the line, for a cp_num that is missing, negative or not integer-valued ("3" and "3.0" are), for
+    coordinates that are not non-negative integers, and for end <= start -- on every row, whatever its chromosome.
+    Returns dict(chrom, start, end i64; klass u8; weight i32)."""
+    import pandas as pd
+    with _open_text(f_cnv) as f:
+        try:
+            seg = pd.read_csv(f, sep="\t", header=None, dtype=str, usecols=[0, 1, 2, 3], skip_blank_lines=False, na_filter=False,
+                              quoting=3)
+        except pd.errors.EmptyDataError:
+            seg = pd.DataFrame({c: [] for c in range(4)}, dtype=str)
+        except ValueError as exc:
+            raise ValueError("%s: a segment file has at least the four columns chr start end cp_num (%s)" % (f_cnv, exc)) from exc
+    seg = seg[(seg != "").any(axis=1)]                                   # (blank lines; the index keeps the line numbers)
+    line = seg.index.to_numpy() + 1
+
+    def refuse(bad, what):
+        if bad.any():
+            i = int(np.flatnonzero(bad)[0])
+            raise ValueError("%s, line %d: %s (%s)" % (f_cnv, line[i], what, "\t".join(seg.iloc[i].tolist())))
+
+    num = [pd.to_numeric(seg[c], errors="coerce").to_numpy(np.float64) for c in (1, 2, 3)]
+    whole = lambda x: np.isfinite(x) & (x == np.floor(x)) & (x >= 0) & (x < 2.0 ** 40)
+    refuse(~whole(num[2]) | (num[2] > 2.0 ** 31), "cp_num must be a non-negative integer")
+    refuse(~whole(num[0]) | ~whole(num[1]), "start and end must be non-negative integers")
+    refuse(num[1] <= num[0], "end <= start")
+    ch = seg[0].map(chrom_ids)
+    keep = ch.notna().to_numpy()
+    start, end, cp = (x[keep].astype(np.int64) for x in num)
+    klass = np.where(cp == 2, 1, np.where(cp < 2, 2, 0)).astype(np.uint8)
+    weight = np.where(cp == 2, 1, np.abs(cp - 2)).astype(np.int32)
+    return dict(chrom=ch[keep].to_numpy(np.int64), start=start, end=end, klass=klass, weight=weight)
+
+
+def window_cnv_objectives(idx, f_cnvs, on_device=None, device=0):
+    """Copy-number labels of the N windows `idx` ([N, 3] ints: CHROM, START, END) for the cohorts `f_cnvs` (a segment file, or a list of
+    them; an entry may also be the dict encode_cnv_rows made of a file): (names, labels float64 [N, 3, C]) with names[c] =
+    objective_name(f_cnvs[c]) and labels[:, :, c] what add_objectives --cnv stores for that file (DataExtractor.py:535-539): columns
+    duplications, copy-neutral / LOH, deletions.  Every window is [START, START + W) with W = idx[0, 2] - idx[0, 1], as in the
+    reference, which never reads another row's END.  Windows may be unsorted, repeated or overlapping.  A chromosome of idx without a
+    row in a file gives zeros (the reference's tabix fetch raises there).
+    on_device: as in window_objectives."""
+    idx = _windows(idx)
+    f_cnvs = [f_cnvs] if isinstance(f_cnvs, (str, bytes, dict)) or hasattr(f_cnvs, "__fspath__") else list(f_cnvs)
+    if not f_cnvs:
+        raise ValueError("no segment file")
+    if len(idx) == 0:
+        raise ValueError("idx: no window (the window width is idx[0, 2] - idx[0, 1])")
+    W = int(idx[0, 2] - idx[0, 1])
+    if W < 1:
+        raise ValueError("idx: the first window is empty (the window width is idx[0, 2] - idx[0, 1] = %d)" % W)
+    chrom_ids = {str(c): int(c) for c in np.unique(idx[:, 0])}
+    cohorts = [f if isinstance(f, dict) else encode_cnv_rows(f, chrom_ids) for f in f_cnvs]
+    names = [f.get("name", "cohort%d" % i) if isinstance(f, dict) else objective_name(f) for i, f in enumerate(f_cnvs)]
+    cat = lambda k, dt: cohort_rows.column(cohorts, k, dt)
+    rows = cohort_rows.place([cat("chrom", "i64"), cat("start", "i64"), cat("end", "i64"), cat("klass", "u8"), cat("weight", "i32"),
+                              cohort_rows.cohort_column(cohorts, "chrom")], on_device, device)
+    from .. import engine
+    labels = engine.window_cnv_means(idx[:, 0], idx[:, 1], W, *rows, len(cohorts), device=device)
+    return names, np.ascontiguousarray(labels.cpu().numpy() if is_cuda(labels) else labels)
+
+
+def add_cnv_objectives(data_file, f_cnvs, suffix='', on_device=None, device=0):
+    """DataExtractor.py addObjectives --cnv for one or more cohorts: reads `idx` from the data container (an HDF5 file or a directory
+    mirror, io/mapfile.py), computes the labels of every file in one pass and stores each cohort's float64 [N, 3] under
+    objective_name(file, suffix).  An HDF5 container is extended in place (h5lite.append_dataset): no existing dataset is read or
+    rewritten.  The same refusals as add_objectives, before any device work.  Returns the names."""
+    from ..io import mapfile
+    f_cnvs = [f_cnvs] if isinstance(f_cnvs, (str, bytes)) or hasattr(f_cnvs, "__fspath__") else list(f_cnvs)
+    names = [objective_name(f, suffix) for f in f_cnvs]
+    for name in names:
+        if not name:
+            raise ValueError("a segment file whose name gives an empty dataset name")
+        if names.count(name) > 1:
+            raise ValueError("two segment files give the dataset name %r" % name)
+        if mapfile.has_key(data_file, name):
+            raise ValueError("Unable to create dataset (name already exists): %r in %s" % (name, data_file))
+    idx = mapfile.read_array(data_file, 'idx')
+    _, labels = window_cnv_objectives(idx, f_cnvs, on_device, device)
+    for c, name in enumerate(names):
+        mapfile.write_array(data_file, name, np.ascontiguousarray(labels[:, :, c]), append=True)
     return names

@@ -380,6 +380,56 @@ def window_objectives(win_chrom, win_start, win_end, row_chrom, row_start, row_e
     return dict(labels=labels, hits=hits_host, keep=keep_host)
 
 
+def window_cnv_means(win_chrom, win_start, W, seg_chrom, seg_start, seg_end, seg_class, seg_weight, seg_cohort, C, device=0):
+    """The region model's copy-number training labels for C cohorts at once (scripts/DataExtractor.py:100-154,535-539 add_objectives
+    --cnv): per window [START, START + W) the mean over its W positions of the duplication, copy-neutral / LOH and deletion tracks of
+    a cohort's segments -- dig_cnv_segment_deltas (one thread per segment into a difference array), dig_cnv_window_means (its prefix
+    sums / W).  No (segment, window) pair is formed.
+    Windows: chromosome id, START (host arrays, any order, repeated or overlapping each other); the distinct (chrom, START) are
+    sorted here and the result scattered back.  Segments: chrom (the windows' chromosome ids; another one adds nothing), start, end
+    i64, half-open; class u8 (0 duplication, 1 LOH, 2 deletion); weight i32 >= 1; cohort i32 within [0, C).
+    Returns labels f64 [N, 3, C], N = the windows as given; CUDA tensors in (the segment arrays) -> a CUDA tensor."""
+    be = backend_of(seg_chrom, seg_start, seg_end, seg_class, seg_weight, seg_cohort, device=device)
+    C, W = int(C), int(W)
+    wc, ws = (np.asarray(x, np.int64).ravel() for x in (win_chrom, win_start))
+    if wc.shape != ws.shape:
+        raise ValueError("windows: one START per chromosome id")
+    if len(wc) and (wc.min() < 0 or wc.max() >= (1 << 22) or ws.min() < 0 or ws.max() >= (1 << 40)):
+        raise ValueError("windows: chromosome ids within [0, 2^22), starts within [0, 2^40)")
+    key, inverse = np.unique((wc << 40) | ws, return_inverse=True)                           # the distinct windows by (chrom, START)
+    inverse = np.asarray(inverse).reshape(-1)
+    N = len(key)
+    uniq_start = key & ((1 << 40) - 1)
+    chrom_id, first = np.unique(key >> 40, return_index=True)
+    chrom_off = np.concatenate([first, [N]]).astype(np.int64)
+    seg_chrom, seg_start, seg_end = (be.arr(x, "i64", (-1,)) for x in (seg_chrom, seg_start, seg_end))
+    seg_class, seg_weight, seg_cohort = be.arr(seg_class, "u8", (-1,)), be.arr(seg_weight, "i32", (-1,)), be.arr(seg_cohort, "i32", (-1,))
+    n = seg_chrom.shape[0]
+    assert seg_start.shape[0] == seg_end.shape[0] == seg_class.shape[0] == seg_weight.shape[0] == seg_cohort.shape[0] == n
+    if be.is_device and n:
+        # (device tensors are checked here; the host twin checks its own arrays inside the library)
+        bad = (seg_start < 0) | (seg_end <= seg_start) | (seg_end > (1 << 40)) | (seg_class > 2) | (seg_weight < 1) | (seg_cohort < 0) | \
+            (seg_cohort >= C)
+        if bool(bad.any()):
+            raise ValueError("a segment outside the tables: 0 <= start < end <= 2^40, class within [0, 2], weight >= 1, cohort within [0, C)")
+    p = be.ptr
+    with _requirements_as_value_errors():
+        lib = _lib.load()
+        delta_bytes, carry_bytes = int(lib.dig_cnv_segment_deltas_size(C, N)), int(lib.dig_cnv_window_means_size(C, N))
+        if delta_bytes < 0 or carry_bytes < 0:
+            raise ValueError(_lib.last_error())
+        # (named, so that every buffer of the two calls is alive at once)
+        starts, ids, off = be.arr(uniq_start, "i64"), be.arr(chrom_id, "i64"), be.arr(chrom_off, "i64")
+        deltas, labels = be.empty(delta_bytes // 8, "i64"), be.empty((C, N, 3), "f64")
+        be.call("dig_cnv_segment_deltas", p(starts), p(ids), p(off), len(chrom_id), N, W, p(seg_chrom), p(seg_start), p(seg_end), p(seg_class),
+                p(seg_weight), p(seg_cohort), n, C, p(deltas))
+        scratch = [be.empty(carry_bytes // 8, "i64")] if be.is_device else []              # (the host twin stages its own)
+        be.call("dig_cnv_window_means", p(deltas), N, C, W, p(labels), *[p(s) for s in scratch])
+    if be.is_device:
+        return labels.permute(1, 2, 0)[be.arr(inverse, "i64")].contiguous()
+    return np.ascontiguousarray(labels.transpose(1, 2, 0)[inverse])
+
+
 def sequence_counts(win_chrom, win_start, win_end, row_chrom, row_start, row_end, row_type, row_cohort, K, C, device=0):
     """The sequence model's sufficient statistic for C cohorts at once (scripts/DigPretrain.py:179-208 sequenceModel): per cohort the
     K counts of (MUT_TYPE, CONTEXT) over the rows that lie in at least one window -- dig_overlap_join_count/fill of all cohorts' rows

@@ -42,7 +42,8 @@ extern "C" {
                              * DIG_PIPE_PACKED_COUNTS (round 5's measured losers: tools/rejected/r05_*.patch); still 12: + dig_panel_row_keys,
                              * dig_panel_counts and their _host twins (additions); + dig_tile_sample_keys, dig_tile_sample_counts and
                              * their _host twins (additions); + dig_tile_census(_workspace), dig_sparse_tile_keys, dig_sparse_tile_test
-                             * and their _host twins (additions); + dig_tile_window_test and its _host twin (additions) */
+                             * and their _host twins (additions); + dig_tile_window_test and its _host twin (additions);
+                             * + dig_cnv_segment_deltas, dig_cnv_window_means, their size queries and _host twins (additions) */
 
 /* dtype codes for dig_gather_bins */
 #define DIG_F32 0
@@ -372,7 +373,7 @@ int dig_panel_counts_host(const int64_t *keys_sorted, int64_t n, const uint32_t 
                           int64_t P, int64_t C, int64_t n_samples, int64_t *n_mut, int64_t *n_pairs, int64_t *n_sample, int device);
 
 /* ---- the region model's training labels for many cohorts (additive: the ABI version stays) -------------------- *
- * scripts/DataExtractor.py:525-572 add_objectives without --cnv: mutation counts per window of the data container's `idx`.  The
+ * scripts/DataExtractor.py:525-572 add_objectives, the SNV branch (--cnv: dig_cnv_* below): mutation counts per window of the data container's `idx`.  The
  * (mutation row, window) pairs come from dig_overlap_join_count/fill with the N windows as one-block elements and the rows of all C
  * cohorts as mutations.  A row carries its global sample (sample_off i64 [C + 1]: a cohort's first global sample, 0 first, n_samples
  * last), its mutation id -- dense ids of the distinct (CHROM, START, END, REF, ALT) of its cohort, all below n_uid: with the sample
@@ -403,6 +404,40 @@ int dig_window_objectives(const int64_t *keys_sorted, int64_t n_pairs, const uin
                           int64_t n_samples, int64_t N, int64_t C, int64_t n_uid, double *labels, int32_t *scratch, void *stream);
 int dig_window_objectives_host(const int64_t *keys_sorted, int64_t n_pairs, const uint8_t *keep, const int64_t *sample_off,
                                int64_t n_samples, int64_t N, int64_t C, int64_t n_uid, double *labels, int device);
+
+/* ---- the region model's copy-number training labels for many cohorts (additive: the ABI version stays) -------- *
+ * scripts/DataExtractor.py:100-154,535-539 add_objectives --cnv: per window [s, s + W) of the data container's `idx` the mean over its
+ * W positions of three per-base tracks built from a cohort's copy-number segments,
+ *   label[window, class] = (double)S / (double)W,  S = sum over the segments with start < s + W and end > s (0-based, half-open) of
+ *   weight * (min(end, s + W) - max(start, s));  class 0 duplications (weight cp_num - 2), 1 copy-neutral / LOH (cp_num == 2, weight 1),
+ *   2 deletions (weight 2 - cp_num).
+ * Windows: win_start i64 [N], the DISTINCT starts, ascending within each chromosome's run; chrom_id i64 [n_chrom] ascending, the
+ * chromosomes that have a window; chrom_off i64 [n_chrom + 1], a chromosome's first window, 0 first and N last.  Segments of all C
+ * cohorts: seg_chrom (a chromosome id: one that chrom_id does not hold adds nothing), seg_start, seg_end i64 with 0 <= start < end <=
+ * 2^40; seg_class u8 within [0, 2]; seg_weight i32 >= 1; seg_cohort i32 within [0, C).  The device entry point passes over a segment
+ * outside these domains; the host twin refuses it, and a window table that is not as described.  Duplicate segments count twice.
+ *   dig_cnv_segment_deltas: deltas i64 [C, 3, N + 1], zeroed by the call, of dig_cnv_segment_deltas_size(C, N) bytes: a difference
+ *     array whose inclusive prefix sum along N is S.  One thread per segment, four binary searches into win_start: the windows a segment
+ *     covers whole get + weight W at the first and - weight W one past the last, every window it covers in part its exact overlap v as
+ *     + v at n and - v at n + 1.  64-bit integer atomics: the result does not depend on their order.
+ *   dig_cnv_window_means: labels f64 [C, N, 3] from deltas, which it leaves as they are: the prefix sums in chunks of
+ *     DIG_CNV_SCAN_CHUNK windows with a carry pass between.  carries: i64 scratch of dig_cnv_window_means_size(C, N) bytes.  S below
+ *     2^53 is exact, and the division is IEEE: the bits of np.mean over the W positions.
+ * 1 <= C < 2^20, 0 <= N < 2^31, 1 <= W < 2^31, 3 C (N + 1) < 2^40 (DIG_EINVAL otherwise; the size queries then return -1).  Buffers
+ * at the alignment of their elements.  N = 0: nothing is written. */
+#define DIG_CNV_SCAN_CHUNK 2048
+int64_t dig_cnv_segment_deltas_size(int64_t C, int64_t N);
+int64_t dig_cnv_window_means_size(int64_t C, int64_t N);
+int dig_cnv_segment_deltas(const int64_t *win_start, const int64_t *chrom_id, const int64_t *chrom_off, int64_t n_chrom, int64_t N,
+                           int64_t W, const int64_t *seg_chrom, const int64_t *seg_start, const int64_t *seg_end,
+                           const uint8_t *seg_class, const int32_t *seg_weight, const int32_t *seg_cohort, int64_t n_seg, int64_t C,
+                           int64_t *deltas, void *stream);
+int dig_cnv_segment_deltas_host(const int64_t *win_start, const int64_t *chrom_id, const int64_t *chrom_off, int64_t n_chrom, int64_t N,
+                                int64_t W, const int64_t *seg_chrom, const int64_t *seg_start, const int64_t *seg_end,
+                                const uint8_t *seg_class, const int32_t *seg_weight, const int32_t *seg_cohort, int64_t n_seg,
+                                int64_t C, int64_t *deltas, int device);
+int dig_cnv_window_means(const int64_t *deltas, int64_t N, int64_t C, int64_t W, double *labels, int64_t *carries, void *stream);
+int dig_cnv_window_means_host(const int64_t *deltas, int64_t N, int64_t C, int64_t W, double *labels, int device);
 
 /* ---- the sequence model's substitution counts for many cohorts (additive: the ABI version stays) --------------- *
  * scripts/DigPretrain.py:179-208 sequenceModel: per cohort the K counts of (MUT_TYPE, CONTEXT) -- the rows of mk_mutation_context,
