@@ -8,6 +8,7 @@
 
 #include "dig_genome2.hpp"
 #include "dig_keyruns.hpp"
+#include "dig_tiles.hpp"
 
 using namespace dig;
 
@@ -136,6 +137,49 @@ int call_genome2(Staging& st, Fn fn, const Genome2& H, Args... args)
     return st.call(fn, st.in(H.words, H.n_words), H.n_words, st.in(H.nint_start, H.n_int), st.in(H.nint_end, H.n_int), H.n_int,
                    st.in(H.nint_bucket, H.n_int ? H.n_buckets : 0), H.n_buckets, st.in(H.chrom_off, nc), st.in(H.chrom_len, nc),
                    H.n_chrom, args...);
+}
+
+// What a twin that walks the 4-bit genome requires of the 14 arguments (check_tile_args) and, on its host arrays, of the genome
+// and region tables: the checks no device entry point can make
+int check_tile_tables_host(const char* fn, const TileArgs& a, bool dense)
+{
+    DIG_REQUIRE_IN(fn, a.n_up == 1 || a.n_up == 2, "n_up = n_down = 1 or 2");
+    if (int rc = check_tile_args(fn, a, dense)) return rc;
+    const TileGenome& g = a.g;
+    static_assert(kCtxMaxPos == 16384, "the message below");
+    for (int c = 0; c < (g.R ? g.n_chrom : 0); ++c)
+        DIG_REQUIRE_IN(fn, g.chrom_off[c] >= 0 && g.chrom_len[c] >= 0 && (g.chrom_off[c] + g.chrom_len[c] + 7) / 8 + 1 <= g.n_words,
+                       "chromosomes inside the genome array");
+    for (int64_t r = 0; r < g.R; ++r) {
+        DIG_REQUIRE_IN(fn, g.reg_chrom[r] >= 0 && g.reg_chrom[r] < g.n_chrom && g.reg_start[r] >= 0 && g.reg_end[r] >= 0,
+                       "regions inside the genome table");
+        DIG_REQUIRE_IN(fn, a.n_up == 1 || g.reg_end[r] - g.reg_start[r] <= kCtxMaxPos,
+                       "a region of the general-context form holds at most 16 384 positions");
+        DIG_REQUIRE_IN(fn, a.n_up == 1 || g.reg_start[r] == 0 || g.reg_start[r] >= a.n_up,
+                       "a region that starts inside (0, n_up) would fetch from a negative position");
+    }
+    return DIG_OK;
+}
+
+// st.call(fn, the leading arguments of `a` up to C staged on the device, args...): the twins of the entry points that walk the 4-bit
+// genome.  (The kernels load every cohort's table, whatever there is to write: a table that may be NULL then is staged as scratch.)
+template <typename Fn, typename... Args>
+int call_tile_genome(Staging& st, Fn fn, const TileArgs& a, Args... args)
+{
+    const TileGenome& g = a.g;
+    const size_t nsp = (size_t)a.C * tile_contexts(a.n_up);
+    const double* d_sp = a.s_prob ? st.in(a.s_prob, nsp) : static_cast<const double*>(st.scratch(nsp * sizeof(double)));
+    return st.call(fn, st.in(g.words, g.n_words), g.n_words, st.in(g.chrom_off, g.n_chrom), st.in(g.chrom_len, g.n_chrom), g.n_chrom,
+                   st.in(g.reg_chrom, g.R), st.in(g.reg_start, g.R), st.in(g.reg_end, g.R), g.R, d_sp, a.C, args...);
+}
+
+// the (mutation, region) pairs of the row-counting twins
+int check_pairs_host(const char* fn, const int32_t* pair_mut, const int32_t* pair_reg, int64_t n_pairs, int64_t n_mut, int64_t R)
+{
+    for (int64_t i = 0; i < n_pairs; ++i)
+        DIG_REQUIRE_IN(fn, pair_mut[i] >= 0 && pair_mut[i] < n_mut && pair_reg[i] >= 0 && pair_reg[i] < R,
+                       "pairs inside the mutation / region tables");
+    return DIG_OK;
 }
 
 // the gene table of the genic twins, once its pointers are known to be non-null
@@ -843,14 +887,13 @@ int dig_base_tile_probs_host(const uint32_t* genome_words, int64_t n_words, cons
                              const double* s_prob, int64_t C, int binsize, int64_t n_tiles, double* pt, int64_t* first_pos,
                              int32_t* n_valid, int device)
 {
-    DIG_REQUIRE(R >= 0 && C >= 0 && n_words >= 2 && n_chrom >= 0 && n_tiles >= 0, "non-negative sizes, n_words >= 2 (pad words)");
+    const TileArgs a{{genome_words, n_words, chrom_off, chrom_len, n_chrom, reg_chrom, reg_start, reg_end, R}, s_prob, C, 1, binsize,
+                     n_tiles, pt, first_pos, n_valid, nullptr};
+    if (int rc = check_tile_tables_host(__func__, a, true)) return rc;
     if (R == 0) return DIG_OK;
-    DIG_REQUIRE(genome_words && chrom_off && chrom_len && reg_chrom && reg_start && reg_end && first_pos && n_valid, "non-null pointers");
-    DIG_REQUIRE(C == 0 || n_tiles == 0 || (s_prob && pt), "s_prob and pt");
     Staging st(device);
-    return st.call(dig_base_tile_probs, st.in(genome_words, n_words), n_words, st.in(chrom_off, n_chrom), st.in(chrom_len, n_chrom),
-                   n_chrom, st.in(reg_chrom, R), st.in(reg_start, R), st.in(reg_end, R), R, st.in(s_prob, (size_t)C * 64), C, binsize,
-                   n_tiles, st.out(pt, (size_t)C * R * n_tiles), st.out(first_pos, R), st.out(n_valid, R), nullptr);
+    return call_tile_genome(st, dig_base_tile_probs, a, binsize, n_tiles, st.out(pt, (size_t)C * R * n_tiles), st.out(first_pos, R),
+                            st.out(n_valid, R), nullptr);
 }
 
 int dig_base_tile_probs_ctx_host(const uint32_t* genome_words, int64_t n_words, const int64_t* chrom_off, const int64_t* chrom_len,
@@ -858,23 +901,13 @@ int dig_base_tile_probs_ctx_host(const uint32_t* genome_words, int64_t n_words, 
                                  const double* s_prob, int64_t C, int n_up, int binsize, int64_t n_tiles, double* pt,
                                  int64_t* first_pos, int32_t* n_valid, int device)
 {
-    DIG_REQUIRE(n_up == 1 || n_up == 2, "n_up = n_down = 1 or 2");
-    DIG_REQUIRE(R >= 0 && C >= 0 && n_words >= 2 && n_chrom >= 0 && n_tiles >= 0, "non-negative sizes, n_words >= 2 (pad words)");
+    const TileArgs a{{genome_words, n_words, chrom_off, chrom_len, n_chrom, reg_chrom, reg_start, reg_end, R}, s_prob, C, n_up, binsize,
+                     n_tiles, pt, first_pos, n_valid, nullptr};
+    if (int rc = check_tile_tables_host(__func__, a, true)) return rc;
     if (R == 0) return DIG_OK;
-    DIG_REQUIRE(genome_words && chrom_off && chrom_len && reg_chrom && reg_start && reg_end && first_pos && n_valid, "non-null pointers");
-    DIG_REQUIRE(C == 0 || n_tiles == 0 || (s_prob && pt), "s_prob and pt");
-    for (int64_t r = 0; r < R; ++r) {
-        DIG_REQUIRE(reg_chrom[r] >= 0 && reg_chrom[r] < n_chrom && reg_start[r] >= 0 && reg_end[r] >= 0, "regions inside the genome table");
-        DIG_REQUIRE(n_up == 1 || reg_end[r] - reg_start[r] <= 16384, "a region of the general-context form holds at most 16 384 positions");
-        DIG_REQUIRE(n_up == 1 || reg_start[r] == 0 || reg_start[r] >= n_up, "a region that starts inside (0, n_up) would fetch from a negative position");
-    }
-    const size_t nsp = (size_t)C * (n_up == 1 ? 64 : 1024);
     Staging st(device);
-    // the context kernels load the table of every cohort even when n_tiles == 0 (s_prob may be NULL then)
-    const double* d_sp = s_prob ? st.in(s_prob, nsp) : static_cast<const double*>(st.scratch(nsp * sizeof(double)));
-    return st.call(dig_base_tile_probs_ctx, st.in(genome_words, n_words), n_words, st.in(chrom_off, n_chrom),
-                   st.in(chrom_len, n_chrom), n_chrom, st.in(reg_chrom, R), st.in(reg_start, R), st.in(reg_end, R), R, d_sp, C, n_up,
-                   binsize, n_tiles, st.out(pt, (size_t)C * R * n_tiles), st.out(first_pos, R), st.out(n_valid, R), nullptr);
+    return call_tile_genome(st, dig_base_tile_probs_ctx, a, n_up, binsize, n_tiles, st.out(pt, (size_t)C * R * n_tiles), st.out(first_pos, R),
+                            st.out(n_valid, R), nullptr);
 }
 
 int dig_tile_mut_counts_host(const int32_t* pair_mut, const int32_t* pair_reg, int64_t n_pairs, const int64_t* mut_start,
@@ -886,8 +919,7 @@ int dig_tile_mut_counts_host(const int32_t* pair_mut, const int32_t* pair_reg, i
     if (n == 0) return DIG_OK;
     DIG_REQUIRE(k && first_pos && n_valid, "non-null outputs / region tables");
     DIG_REQUIRE(n_pairs == 0 || (pair_mut && pair_reg && mut_start && mut_cohort), "non-null pair / mutation arrays");
-    for (int64_t i = 0; i < n_pairs; ++i)
-        DIG_REQUIRE(pair_mut[i] >= 0 && pair_mut[i] < n_mut && pair_reg[i] >= 0 && pair_reg[i] < R, "pairs inside the mutation / region tables");
+    if (int rc = check_pairs_host(__func__, pair_mut, pair_reg, n_pairs, n_mut, R)) return rc;
     Staging st(device);
     return st.call(dig_tile_mut_counts, st.in(pair_mut, n_pairs), st.in(pair_reg, n_pairs), n_pairs, st.in(mut_start, n_mut),
                    st.in(mut_cohort, n_mut), st.in(first_pos, R), st.in(n_valid, R), binsize, n_tiles, R, C, st.out(k, n), nullptr);
@@ -905,8 +937,7 @@ int dig_tile_sample_keys_host(const int32_t* pair_mut, const int32_t* pair_reg, 
     DIG_REQUIRE(pair_mut && pair_reg && keys, "non-null pair arrays, keys");
     DIG_REQUIRE(n_mut == 0 || (mut_start && mut_cohort && mut_sample), "non-null mutation arrays");
     DIG_REQUIRE(R == 0 || (first_pos && n_valid), "non-null region tables");
-    for (int64_t i = 0; i < n_pairs; ++i)
-        DIG_REQUIRE(pair_mut[i] >= 0 && pair_mut[i] < n_mut && pair_reg[i] >= 0 && pair_reg[i] < R, "pairs inside the mutation / region tables");
+    if (int rc = check_pairs_host(__func__, pair_mut, pair_reg, n_pairs, n_mut, R)) return rc;
     for (int64_t m = 0; m < n_mut; ++m)
         DIG_REQUIRE(mut_cohort[m] < 0 || mut_cohort[m] >= C || (mut_sample[m] >= 0 && mut_sample[m] < n_samples),
                     "global sample within [0, n_samples) for every row of a cohort within [0, C)");
@@ -947,47 +978,24 @@ int dig_tile_window_test_host(const double* pt, const int32_t* k, const double* 
                    pval_w ? st.out(pval_w, n) : nullptr, n_windows ? st.out(n_windows, R) : nullptr, nullptr);
 }
 
-// what the two genome-walking twins of the sparse per-base scan check of their host arrays (`fn`: the twin's name)
-static int check_sparse_regions(const char* fn, const uint32_t* genome_words, int64_t n_words, const int64_t* chrom_off,
-                                const int64_t* chrom_len, int n_chrom, const int32_t* reg_chrom, const int64_t* reg_start,
-                                const int64_t* reg_end, int64_t R, int64_t C, int n_up, int binsize, int64_t n_tiles)
-{
-    DIG_REQUIRE_IN(fn, n_up == 1 || n_up == 2, "n_up = n_down = 1 or 2");
-    DIG_REQUIRE_IN(fn, R >= 0 && C >= 0 && n_words >= 2 && n_chrom >= 0 && n_tiles >= 0 && binsize >= 1,
-                   "non-negative sizes, n_words >= 2 (pad words), binsize >= 1");
-    if (R == 0) return DIG_OK;
-    DIG_REQUIRE_IN(fn, genome_words && chrom_off && chrom_len && reg_chrom && reg_start && reg_end, "non-null genome and region tables");
-    for (int c = 0; c < n_chrom; ++c)
-        DIG_REQUIRE_IN(fn, chrom_off[c] >= 0 && chrom_len[c] >= 0 && (chrom_off[c] + chrom_len[c] + 7) / 8 + 1 <= n_words,
-                       "chromosomes inside the genome array");
-    for (int64_t r = 0; r < R; ++r) {
-        DIG_REQUIRE_IN(fn, reg_chrom[r] >= 0 && reg_chrom[r] < n_chrom && reg_start[r] >= 0 && reg_end[r] >= 0, "regions inside the genome table");
-        DIG_REQUIRE_IN(fn, n_up == 1 || reg_end[r] - reg_start[r] <= 16384, "a region of the general-context form holds at most 16 384 positions");
-        DIG_REQUIRE_IN(fn, n_up == 1 || reg_start[r] == 0 || reg_start[r] >= n_up, "a region that starts inside (0, n_up) would fetch from a negative position");
-    }
-    return DIG_OK;
-}
-
 int dig_tile_census_host(const uint32_t* genome_words, int64_t n_words, const int64_t* chrom_off, const int64_t* chrom_len, int n_chrom,
                          const int32_t* reg_chrom, const int64_t* reg_start, const int64_t* reg_end, int64_t R, const double* s_prob,
                          int64_t C, int n_up, int binsize, int64_t n_tiles, int64_t* first_pos, int32_t* n_valid, double* denom,
                          int32_t* n_positive, int device)
 {
-    if (int rc = check_sparse_regions(__func__, genome_words, n_words, chrom_off, chrom_len, n_chrom, reg_chrom, reg_start, reg_end, R, C,
-                                      n_up, binsize, n_tiles))
-        return rc;
+    const TileArgs a{{genome_words, n_words, chrom_off, chrom_len, n_chrom, reg_chrom, reg_start, reg_end, R}, s_prob, C, n_up, binsize,
+                     n_tiles, nullptr, first_pos, n_valid, nullptr};
+    if (int rc = check_tile_tables_host(__func__, a, false)) return rc;
     int64_t slots = 0;
     if (int rc = sparse_tile_slots(__func__, C, R, n_tiles, &slots)) return rc;
     if (R == 0) return DIG_OK;
     DIG_REQUIRE(first_pos && n_valid, "non-null first_pos, n_valid");
     DIG_REQUIRE(C == 0 || (s_prob && denom && n_positive), "non-null s_prob, denom, n_positive");
-    const size_t nsp = (size_t)C * (n_up == 1 ? 64 : 1024), rows = (size_t)C * R;
+    const size_t rows = (size_t)C * R;
     const int64_t wsb = tile_census_workspace_bytes(C, n_up);
     Staging st(device);
-    return st.call(dig_tile_census, st.in(genome_words, n_words), n_words, st.in(chrom_off, n_chrom), st.in(chrom_len, n_chrom), n_chrom,
-                   st.in(reg_chrom, R), st.in(reg_start, R), st.in(reg_end, R), R, st.in(s_prob, nsp), C, n_up, binsize, n_tiles,
-                   st.out(first_pos, R), st.out(n_valid, R), C ? st.out(denom, rows) : nullptr, C ? st.out(n_positive, rows) : nullptr,
-                   st.scratch(wsb), wsb, nullptr);
+    return call_tile_genome(st, dig_tile_census, a, n_up, binsize, n_tiles, st.out(first_pos, R), st.out(n_valid, R),
+                            C ? st.out(denom, rows) : nullptr, C ? st.out(n_positive, rows) : nullptr, st.scratch(wsb), wsb, nullptr);
 }
 
 int dig_sparse_tile_keys_host(const int32_t* pair_mut, const int32_t* pair_reg, int64_t n_pairs, const int64_t* mut_start, int64_t n_mut,
@@ -1001,8 +1009,7 @@ int dig_sparse_tile_keys_host(const int32_t* pair_mut, const int32_t* pair_reg, 
     DIG_REQUIRE(pair_mut && pair_reg && keys, "non-null pair arrays, keys");
     DIG_REQUIRE(n_mut == 0 || (mut_start && mut_cohort), "non-null mutation arrays");
     DIG_REQUIRE(R == 0 || (first_pos && n_valid), "non-null region tables");
-    for (int64_t i = 0; i < n_pairs; ++i)
-        DIG_REQUIRE(pair_mut[i] >= 0 && pair_mut[i] < n_mut && pair_reg[i] >= 0 && pair_reg[i] < R, "pairs inside the mutation / region tables");
+    if (int rc = check_pairs_host(__func__, pair_mut, pair_reg, n_pairs, n_mut, R)) return rc;
     Staging st(device);
     return st.call(dig_sparse_tile_keys, st.in(pair_mut, n_pairs), st.in(pair_reg, n_pairs), n_pairs, st.in(mut_start, n_mut), n_mut,
                    st.in(mut_cohort, n_mut), st.in(first_pos, R), st.in(n_valid, R), binsize, n_tiles, R, C, st.out(keys, n_pairs), nullptr);
@@ -1015,9 +1022,9 @@ int dig_sparse_tile_test_host(const uint32_t* genome_words, int64_t n_words, con
                               int32_t* out_region, int32_t* out_tile, int32_t* out_k, double* out_pt, double* out_exp, double* out_pval,
                               int device)
 {
-    if (int rc = check_sparse_regions(__func__, genome_words, n_words, chrom_off, chrom_len, n_chrom, reg_chrom, reg_start, reg_end, R, C,
-                                      n_up, binsize, n_tiles))
-        return rc;
+    const TileArgs a{{genome_words, n_words, chrom_off, chrom_len, n_chrom, reg_chrom, reg_start, reg_end, R}, s_prob, C, n_up, binsize,
+                     n_tiles, nullptr, nullptr, nullptr, nullptr};
+    if (int rc = check_tile_tables_host(__func__, a, false)) return rc;
     DIG_REQUIRE(n >= 0 && n <= INT32_MAX, "0 <= n < 2^31 (the counts are 32-bit)");
     int64_t slots = 0;
     if (int rc = sparse_tile_slots(__func__, C, R, n_tiles, &slots)) return rc;
@@ -1025,13 +1032,11 @@ int dig_sparse_tile_test_host(const uint32_t* genome_words, int64_t n_words, con
     DIG_REQUIRE(keys_sorted && out_cohort && out_region && out_tile && out_k && out_pt && out_exp && out_pval, "non-null keys and outputs");
     DIG_REQUIRE(slots == 0 || (s_prob && denom && mu && sigma), "non-null s_prob, denom, mu, sigma");
     if (int rc = check_ascending(__func__, keys_sorted, n)) return rc;
-    const size_t nsp = (size_t)C * (n_up == 1 ? 64 : 1024), rows = (size_t)C * R;
+    const size_t rows = (size_t)C * R;
     Staging st(device);
-    return st.call(dig_sparse_tile_test, st.in(genome_words, n_words), n_words, st.in(chrom_off, n_chrom), st.in(chrom_len, n_chrom),
-                   n_chrom, st.in(reg_chrom, R), st.in(reg_start, R), st.in(reg_end, R), R, st.in(s_prob, nsp), C, n_up, binsize, n_tiles,
-                   st.in(denom, rows), st.in(mu, rows), st.in(sigma, rows), st.in(keys_sorted, n), n, st.out(out_cohort, n),
-                   st.out(out_region, n), st.out(out_tile, n), st.out(out_k, n), st.out(out_pt, n), st.out(out_exp, n),
-                   st.out(out_pval, n), nullptr);
+    return call_tile_genome(st, dig_sparse_tile_test, a, n_up, binsize, n_tiles, st.in(denom, rows), st.in(mu, rows), st.in(sigma, rows),
+                            st.in(keys_sorted, n), n, st.out(out_cohort, n), st.out(out_region, n), st.out(out_tile, n), st.out(out_k, n),
+                            st.out(out_pt, n), st.out(out_exp, n), st.out(out_pval, n), nullptr);
 }
 
 int dig_overlap_join_count_host(const int64_t* blk_start_key, const int64_t* blk_runmax_key, const int64_t* blk_end, int64_t n_blk,

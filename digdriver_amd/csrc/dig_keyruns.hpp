@@ -40,8 +40,8 @@ int tile_select_sizes(const char* fn, int64_t C, int64_t R, int64_t T);
 int tile_window_sizes(const char* fn, int64_t C, int64_t R, int64_t T, int32_t width);
 
 // dig_tilesamples.hip: the bits of the global-sample field of a tile-sample key, ((cohort R + region) T + tile) << bits | global sample
-// (bits for n_samples + 1 values: the all-ones key is no real one); DIG_EINVAL (in the name of entry point `fn`) when the two fields
-// do not fit 63 bits
+// (bits for n_samples + 1 values: the all-ones key is no real one); DIG_EINVAL (in the name of entry point `fn`) when the tile field
+// is refused by sparse_tile_slots or the two fields do not fit 63 bits
 int tile_sample_key_layout(const char* fn, int64_t C, int64_t R, int64_t T, int64_t n_samples, int* sample_bits);
 
 // dig_tilesparse.hip: the slots C R T of a sparse-scan key, (cohort R + region) T + tile; DIG_EINVAL (in the name of entry point `fn`)
@@ -69,6 +69,16 @@ inline int row_blocks(const char* fn, int64_t n, int block, unsigned* blocks)
     return DIG_OK;
 }
 
+// One past the last lane (64 at most) of the segment that lane `lane` begins, from two ballots of the wave: `firsts`, the lanes
+// that begin a segment, and `rows`, the lanes that belong to one.  It ends at the next first lane or at the next lane outside `rows`,
+// whichever comes first.  No ballot of its own: the caller's ballots are what every lane of the wave must reach.
+__device__ __forceinline__ int segment_end(unsigned long long firsts, unsigned long long rows, int lane)
+{
+    const unsigned long long above = lane == 63 ? 0ull : ~0ull << (lane + 1);
+    const unsigned long long stop = (firsts | ~rows) & above;
+    return stop ? __ffsll((long long)stop) - 1 : 64;
+}
+
 // The lanes of a wave form segments: maximal runs of consecutive lanes with the same seg >= 0 (seg < 0: a lane without a
 // destination).  On the first lane of a segment: the number of lanes of the segment with `flag`; on every other lane 0.
 // Every lane of the wave must call it.
@@ -79,11 +89,8 @@ __device__ __forceinline__ int segment_count(int64_t seg, bool flag)
     const bool first = seg >= 0 && (lane == 0 || left != seg);
     const unsigned long long firsts = __ballot(first), rows = __ballot(seg >= 0), flags = __ballot(flag && seg >= 0);
     if (!first) return 0;
-    // the segment ends at the next first lane or at the next lane without a destination, whichever comes first
-    const unsigned long long above = lane == 63 ? 0ull : ~0ull << (lane + 1);
-    const unsigned long long stop = (firsts | ~rows) & above;
-    const int end = stop ? __ffsll((long long)stop) - 1 : 64;
-    const unsigned long long mine = (end == 64 ? ~0ull : ((1ull << end) - 1)) & (above | (1ull << lane));
+    const int end = segment_end(firsts, rows, lane);
+    const unsigned long long mine = (end == 64 ? ~0ull : ((1ull << end) - 1)) & ~((1ull << lane) - 1);      // the lanes [lane, end)
     return __popcll(flags & mine);
 }
 
@@ -94,10 +101,7 @@ __device__ __forceinline__ int segment_sum(int64_t seg, int value)
     const int lane = threadIdx.x & 63;
     const int64_t left = __shfl_up((long long)seg, 1, 64);
     const bool first = seg >= 0 && (lane == 0 || left != seg);
-    const unsigned long long firsts = __ballot(first), rows = __ballot(seg >= 0);
-    const unsigned long long above = lane == 63 ? 0ull : ~0ull << (lane + 1);
-    const unsigned long long stop = (firsts | ~rows) & above;
-    const int end = stop ? __ffsll((long long)stop) - 1 : 64;
+    const int end = segment_end(__ballot(first), __ballot(seg >= 0), lane);
     int v = seg >= 0 ? value : 0;
 #pragma unroll
     for (int d = 1; d < 64; d <<= 1) {
@@ -119,6 +123,21 @@ __device__ __forceinline__ int64_t keys_upper_bound(const int64_t* keys, int64_t
             lo = mid + 1;
     }
     return lo;
+}
+
+// One thread per sorted key (key = keys[i]; row: the key counts; head: it counts and keys[i - 1] -- read from global memory: it may lie
+// in the previous wave or workgroup -- is another key).  On a head: the length of its run of equal keys; on every other lane 0.  The
+// run ends inside the wave at the next head or the next lane without a row; only one that reaches the wave's last lane looks further:
+// one load tells whether it goes on at all, then keys_upper_bound.  Every lane of the wave must call it.
+__device__ __forceinline__ int64_t run_length(const int64_t* keys, int64_t n, int64_t i, int64_t key, bool head, bool row)
+{
+    const int lane = threadIdx.x & 63;
+    const unsigned long long heads = __ballot(head), rows = __ballot(row);
+    if (!head) return 0;
+    const int end = segment_end(heads, rows, lane);
+    int64_t len = end - lane;
+    if (end == 64 && i + len < n && keys[i + len] == key) len = keys_upper_bound(keys, i + len + 1, n, key) - i;
+    return len;
 }
 
 }  // namespace dig

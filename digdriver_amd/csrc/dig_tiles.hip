@@ -22,13 +22,14 @@
 // ulp (1e-15 relative, tests/test_gpu_tiles.py); counts are exact.
 //
 // dig_tile_mut_counts: k[c][region][tile] from the (mutation, region) pairs of dig_overlap_join_*: one atomic add per
-// pair whose START lies inside the region's positions.
+// pair that tile_slot (dig_tiles.hpp) gives a tile.
 //
 // Four kernels here (base_tile_probs_kernel: the plain fallback; base_tile_probs_mfma_kernel and base_tile_probs_roles_kernel:
 // the matrix forms; base_tile_probs_ctx_kernel: general contexts), the row walk in dig_tiles_rows.hip.  What they share lives in
-// dig_tiles.hpp: a region's positions (region_positions), the packed-word window of a base range (word_window, load_word) and
-// its staging (stage_load / stage_store), the nibble squeezes, the matrix kernels' cohort operands, and on the host the argument
-// block (TileArgs: launch, check_tile_args) and the DIG_TILES_FORM switch.  The cut of a cohort chunk into tiles and quads
+// dig_tiles.hpp: the genome view (TileGenome), a region's positions (region_positions), the packed-word window of a base range
+// (word_window, load_word) and its staging (stage_load / stage_store), the nibble squeezes, the matrix kernels' cohort operands, the
+// tile of a mutation row (tile_slot), and on the host the argument block (TileArgs: launch, check_tile_args) and the DIG_TILES_FORM
+// switch.  The cut of a cohort chunk into tiles and quads
 // (chunk_cut, dispatch_cut) is the dot kernels' (dig_accumulate.hip) as well: dig_common.hpp.
 #include "dig_tiles.hpp"
 
@@ -713,7 +714,6 @@ __global__ __launch_bounds__(kTsBlock, 1) void base_tile_probs_roles_kernel(
 constexpr int kCtxBlock = 1024;           // threads per workgroup: kCtxWalkers walkers of 8 lanes (512: 5.5 ms where 1024 take 4.6)
 constexpr int kCtxWalkers = kCtxBlock / 8;
 constexpr int kCtxCoh = 8;                // cohorts per pass = lanes per walker
-constexpr int kCtxMaxPos = 16384;         // positions of a region whose codes are staged
 constexpr int kCtxSumTiles = 512;         // tile sums kept per walk
 constexpr int kCtxSumStride = kCtxSumTiles + 1;
 
@@ -1008,13 +1008,8 @@ __global__ __launch_bounds__(256) void tile_mut_counts_kernel(const int32_t* __r
     const int64_t stride = (int64_t)gridDim.x * 256;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n_pairs; i += stride) {
         const int64_t m = pair_mut[i], r = pair_reg[i];
-        const int64_t off = mut_start[m] - first_pos[r];           // START must be one of the region's positions (:160-163)
-        if (off < 0) continue;
-        const int64_t t = off / binsize;
-        if (t >= n_valid[r]) continue;
-        const int64_t c = mut_cohort[m];
-        if ((uint64_t)c >= (uint64_t)C) continue;                  // a cohort id outside [0, C) has no plane to count in
-        atomicAdd(&k[(c * R + r) * n_tiles + t], 1);
+        const int64_t slot = tile_slot(mut_start[m], mut_cohort[m], first_pos[r], n_valid[r], binsize, n_tiles, R, C, r);
+        if (slot >= 0) atomicAdd(&k[slot], 1);
     }
 }
 
@@ -1029,9 +1024,9 @@ int dig_base_tile_probs(const uint32_t* genome_words, int64_t n_words, const int
                         const double* s_prob, int64_t C, int binsize, int64_t n_tiles, double* pt, int64_t* first_pos,
                         int32_t* n_valid, void* stream)
 {
-    const TileArgs a{genome_words, n_words, chrom_off, chrom_len, reg_chrom, reg_start, reg_end, R, s_prob, C, binsize, n_tiles,
-                     pt, first_pos, n_valid, (hipStream_t)stream};
-    if (const int rc = check_tile_args(__func__, a, n_chrom)) return rc;
+    const TileArgs a{{genome_words, n_words, chrom_off, chrom_len, n_chrom, reg_chrom, reg_start, reg_end, R}, s_prob, C, 1, binsize,
+                     n_tiles, pt, first_pos, n_valid, (hipStream_t)stream};
+    if (const int rc = check_tile_args(__func__, a, true)) return rc;
     if (R == 0) return DIG_OK;
     DIG_REQUIRE(binsize <= kTilePassPos, "binsize at most 12 280 positions");
     const bool mfma = binsize >= 2 && n_tiles >= 1 && n_tiles <= kTileBlock && C >= 1 && n_tiles * binsize <= kTilePassPos;
@@ -1068,21 +1063,20 @@ int dig_base_tile_probs_ctx(const uint32_t* genome_words, int64_t n_words, const
                             const double* s_prob, int64_t C, int n_up, int binsize, int64_t n_tiles, double* pt, int64_t* first_pos,
                             int32_t* n_valid, void* stream)
 {
-    DIG_REQUIRE(n_up == 1 || n_up == 2, "n_up = n_down = 1 (trinucleotide) or 2 (penta-nucleotide)");
+    const TileArgs a{{genome_words, n_words, chrom_off, chrom_len, n_chrom, reg_chrom, reg_start, reg_end, R}, s_prob, C, n_up, binsize,
+                     n_tiles, pt, first_pos, n_valid, (hipStream_t)stream};
+    if (const int rc = check_tile_args(__func__, a, true)) return rc;
     const TilesForm form = tiles_form();
     if (n_up == 1 && form != TilesForm::kGeneral && form != TilesForm::kRows)
         return dig_base_tile_probs(genome_words, n_words, chrom_off, chrom_len, n_chrom, reg_chrom, reg_start, reg_end, R, s_prob, C,
                                    binsize, n_tiles, pt, first_pos, n_valid, stream);
-    const TileArgs a{genome_words, n_words, chrom_off, chrom_len, reg_chrom, reg_start, reg_end, R, s_prob, C, binsize, n_tiles,
-                     pt, first_pos, n_valid, (hipStream_t)stream};
-    if (const int rc = check_tile_args(__func__, a, n_chrom)) return rc;
     if (R == 0) return DIG_OK;
     // The row walk (dig_tiles_rows.hip) takes every region its LDS budget covers and marks the others n_valid = -2; the general
     // kernel behind it takes those (a region of more than kCtxMaxPos positions is not evaluated -- n_valid -1, pt NaN; the host
     // wrappers, which know the coordinates, refuse such regions before the launch).
     const int only_deferred = form == TilesForm::kGeneral ? 0 : 1;
     if (only_deferred)
-        if (const int rc = launch_tile_probs_rows(a, n_up)) return rc;
+        if (const int rc = launch_tile_probs_rows(a)) return rc;
     const int grid = grid_for(R * kCtxBlock, kCtxBlock, 1);
     if (n_up == 1) a.launch(base_tile_probs_ctx_kernel<1>, grid, kCtxBlock, C, binsize, n_tiles)(only_deferred);
     else a.launch(base_tile_probs_ctx_kernel<2>, grid, kCtxBlock, C, binsize, n_tiles)(only_deferred);

@@ -1,6 +1,8 @@
-// dig_tiles.hpp -- what the tile-probability kernels of dig_tiles.hip and dig_tiles_rows.hip share: a region's positions, the
-// packed-word window of a base range and its staging, the two nibble squeezes, the cohort operands of the matrix kernels, and
-// the host-side argument block, argument check, launch helper and DIG_TILES_FORM switch of the two entry points.
+// dig_tiles.hpp -- what the kernels of the per-base route (dig_tiles.hip, dig_tiles_rows.hip, dig_tilesamples.hip, dig_tilesparse.hip)
+// and their host twins (dig_host.hip) share: the view of the 4-bit genome and the region table (TileGenome) with a region's positions,
+// the packed-word window of a base range and its staging, the two nibble squeezes, the cohort operands of the matrix kernels, the
+// tile a mutation row counts in (tile_slot), and on the host the argument block of the entry points that take the genome (TileArgs:
+// launch, check_tile_args) and the DIG_TILES_FORM switch.
 #pragma once
 #include <stdlib.h>
 
@@ -10,7 +12,21 @@
 
 namespace dig {
 
-// ---- a region's positions ----
+// ---- the 4-bit genome and the region table ----
+constexpr int kCtxMaxPos = 16384;       // positions of the longest penta-nucleotide region that is evaluated (engine.TILE_CTX_MAX_POSITIONS)
+constexpr int tile_contexts(int n_up) { return 1 << (2 * (2 * n_up + 1)); }      // rows of a cohort's table: 64 (n_up 1) or 1024 (2)
+
+// The nine genome and region arguments of an entry point, in their order; the sparse kernels take it by value.
+struct TileGenome {
+    const uint32_t* words;
+    int64_t n_words;
+    const int64_t *chrom_off, *chrom_len;
+    int n_chrom;
+    const int32_t* reg_chrom;
+    const int64_t *reg_start, *reg_end;
+    int64_t R;
+};
+
 struct TileRegion {
     int64_t first;      // first position (chromosome coordinates)
     int64_t n_pos;      // number of positions
@@ -28,6 +44,34 @@ __device__ __forceinline__ TileRegion region_positions(int U, int64_t len, int64
     t.n_pos = stop > t.first ? stop - t.first : 0;
     t.g0 = off + t.first;
     return t;
+}
+
+// region r of the view, with a chromosome id outside the table read as a region without positions; too_long: a penta-nucleotide
+// region of more than kCtxMaxPos positions, which no kernel evaluates
+template <int U>
+__device__ __forceinline__ TileRegion sparse_region(const TileGenome& g, int64_t r, bool* too_long)
+{
+    const int chrom = g.reg_chrom[r];
+    const int64_t start = g.reg_start[r], end = g.reg_end[r];
+    TileRegion q{start == 0 ? U : start, 0, 0};
+    if ((unsigned)chrom < (unsigned)g.n_chrom) q = region_positions(U, g.chrom_len[chrom], g.chrom_off[chrom], start, end);
+    *too_long = U == 2 && q.n_pos > kCtxMaxPos;
+    return q;
+}
+
+// ---- the tile a mutation row counts in ----
+// A row (START `start`, cohort c) paired with region r (first_pos, n_valid: the region's entries of the tables the probability kernels
+// and the census write): the slot (c R + r) n_tiles + t of its tile, or -1 for a row that counts nowhere -- START in front of the region
+// (nb_model.py:160-163), a tile at or past n_valid (<= 0: a region without tiles) or n_tiles, a cohort outside [0, C), in this order.
+__device__ __forceinline__ int64_t tile_slot(int64_t start, int64_t c, int64_t first_pos, int64_t n_valid, int binsize, int64_t n_tiles,
+                                             int64_t R, int64_t C, int64_t r)
+{
+    const int64_t off = start - first_pos;
+    if (off < 0) return -1;
+    const int64_t t = off / binsize;
+    if (t >= n_valid || t >= n_tiles) return -1;
+    if ((uint64_t)c >= (uint64_t)C) return -1;
+    return (c * R + r) * n_tiles + t;
 }
 
 // ---- the packed words of a base range (eight 4-bit codes per word; word 0 of the array is the leading pad word) ----
@@ -144,19 +188,14 @@ __device__ __forceinline__ void load_cohort_operands(double (&A)[MT > 0 ? MT : 1
 }
 
 // ---- host side ----
-// The arguments the five kernels share.  The kernels keep their own parameter lists (and their __restrict__): `launch` puts
-// the genome, the regions and the table in front of a kernel's own arguments and the three outputs behind them, and returns
-// the call that takes whatever the kernel declares behind the outputs.
+// The 14 arguments the entry points that walk the genome begin with (n_up = 1 for dig_base_tile_probs, which has none) and the three
+// outputs of the probability kernels.  Those kernels keep their own parameter lists (and their __restrict__): `launch` puts the genome,
+// the regions and the table in front of a kernel's own arguments, the outputs behind them, and returns the call that takes the rest.
 struct TileArgs {
-    const uint32_t* words;
-    int64_t n_words;
-    const int64_t *chrom_off, *chrom_len;
-    const int32_t* reg_chrom;
-    const int64_t *reg_start, *reg_end;
-    int64_t R;
+    TileGenome g;
     const double* s_prob;
     int64_t C;
-    int binsize;
+    int n_up, binsize;
     int64_t n_tiles;
     double* pt;
     int64_t* first_pos;
@@ -167,22 +206,27 @@ struct TileArgs {
     auto launch(Kernel kernel, int grid, int block, Own... own) const
     {
         return [=, a = *this](auto... last) {
-            hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), 0, a.stream, a.words, a.n_words, a.chrom_off, a.chrom_len, a.reg_chrom,
-                               a.reg_start, a.reg_end, a.R, a.s_prob, own..., a.pt, a.first_pos, a.n_valid, last...);
+            hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), 0, a.stream, a.g.words, a.g.n_words, a.g.chrom_off, a.g.chrom_len,
+                               a.g.reg_chrom, a.g.reg_start, a.g.reg_end, a.g.R, a.s_prob, own..., a.pt, a.first_pos, a.n_valid, last...);
         };
     }
 };
 
-// what dig_base_tile_probs and dig_base_tile_probs_ctx (fn: the one that asks) require of their arguments; R == 0 passes with
-// the sizes checked alone
-inline int check_tile_args(const char* fn, const TileArgs& a, int n_chrom)
+// What entry point `fn` requires of the 14 arguments; R == 0 passes with the sizes checked alone.  dense: the probability entries,
+// whose three outputs belong to the block; the sparse entries check their own outputs, and their keys need the sizes below 2^31.
+inline int check_tile_args(const char* fn, const TileArgs& a, bool dense)
 {
-    DIG_REQUIRE_IN(fn, a.R >= 0 && a.C >= 0 && a.n_words >= 2 && n_chrom >= 0 && a.n_tiles >= 0,
+    DIG_REQUIRE_IN(fn, a.n_up == 1 || a.n_up == 2, "n_up = n_down = 1 (trinucleotide) or 2 (penta-nucleotide)");
+    DIG_REQUIRE_IN(fn, a.g.R >= 0 && a.C >= 0 && a.g.n_words >= 2 && a.g.n_chrom >= 0 && a.n_tiles >= 0,
                    "non-negative sizes, n_words >= 2 (pad words)");
     DIG_REQUIRE_IN(fn, a.binsize >= 1, "binsize >= 1");
-    if (a.R == 0) return DIG_OK;
-    DIG_REQUIRE_IN(fn, a.words && a.chrom_off && a.chrom_len && a.reg_chrom && a.reg_start && a.reg_end && a.first_pos && a.n_valid,
-                   "non-null pointers");
+    const int64_t lim = (int64_t)1 << 31;
+    DIG_REQUIRE_IN(fn, dense || (a.g.R < lim && a.C < lim && a.n_tiles < lim), "C, R and n_tiles below 2^31");
+    if (a.g.R == 0) return DIG_OK;
+    const bool tables = a.g.words && a.g.chrom_off && a.g.chrom_len && a.g.reg_chrom && a.g.reg_start && a.g.reg_end;
+    DIG_REQUIRE_IN(fn, dense || tables, "non-null genome and region tables");
+    if (!dense) return DIG_OK;
+    DIG_REQUIRE_IN(fn, tables && a.first_pos && a.n_valid, "non-null pointers");
     DIG_REQUIRE_IN(fn, a.C == 0 || a.n_tiles == 0 || (a.s_prob && a.pt), "s_prob and pt");
     return DIG_OK;
 }
@@ -215,6 +259,6 @@ inline bool dispatch_const(int v, F&& f)
 
 // dig_tiles_rows.hip: the row walk of the tile probabilities, one launch per cohort pass; regions it does not take are left with
 // n_valid = -2 for the general kernel (dig_tiles.hip)
-int launch_tile_probs_rows(const TileArgs& a, int n_up);
+int launch_tile_probs_rows(const TileArgs& a);
 
 }  // namespace dig

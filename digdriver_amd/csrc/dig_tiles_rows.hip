@@ -396,7 +396,7 @@ __global__ __launch_bounds__(1024) void base_tile_probs_rows_kernel(
 
 // The passes of one call: sixteen cohorts while more than eight are left, then one pass of eight (4-lane walkers) or four
 // (2-lane walkers).  Every pass is a launch of its own (its table is staged once per workgroup).
-int launch_tile_probs_rows(const TileArgs& a, int n_up)
+int launch_tile_probs_rows(const TileArgs& a)
 {
     const int binsize = a.binsize;
     // positions per trip: the one that wastes the fewest slots of a tile's last trip (ties: the longer trip)
@@ -410,7 +410,7 @@ int launch_tile_probs_rows(const TileArgs& a, int n_up)
         }
     }
     const unsigned bin_magic = binsize >= 2 ? (unsigned)(((1ull << 32) + (unsigned)binsize - 1) / (unsigned)binsize) : 0u;
-    const int grid = grid_for(a.R * 1024, 1024, 1);
+    const int grid = grid_for(a.g.R * 1024, 1024, 1);
     // waves per workgroup (tiles are dealt by tickets: more waves hide more latency, and a wave = a cohort in the output phase)
     const int n_waves = 16;
     int c0 = 0;
@@ -419,7 +419,7 @@ int launch_tile_probs_rows(const TileArgs& a, int n_up)
         const int left = (int)(a.C - c0);
         const int lw = left > 8 ? 8 : (left > 4 ? 4 : 2);
         const int cc = left < 2 * lw ? left : 2 * lw;
-        dispatch_const<1, 2>(n_up, [&](auto u) {
+        dispatch_const<1, 2>(a.n_up, [&](auto u) {
             dispatch_const<8, 4, 2>(lw, [&](auto l) {
                 dispatch_const<25, 12, 10, 8>(tp, [&](auto t) {
                     a.launch(base_tile_probs_rows_kernel<u.value, l.value, t.value, true>, grid, 64 * n_waves, c0, cc, binsize, bin_magic,

@@ -9,21 +9,20 @@
 //   k_cap[c, r, t]     = sum over the kept samples of min(n, cap)            (cap <= 0: no cap, the sum of n)
 //   k_samples[c, r, t] = the kept samples with n > 0
 // Two kernels around one key sort:
-//   tile_sample_keys_kernel    one thread per (mutation, region) pair of the interval join.  The skip rules of
-//                              tile_mut_counts_kernel in its order (START in front of the region, tile at or past n_valid, cohort
-//                              outside [0, C)), then the sample (outside [0, n_samples), or keep[sample] == 0).  A pair that counts
-//                              gets key = (((cohort R + region) T + tile) << sb) | global sample; every other pair the all-ones
-//                              63-bit key, which sorts behind every real one.
+//   tile_sample_keys_kernel    one thread per (mutation, region) pair of the interval join.  The tile is tile_mut_counts_kernel's
+//                              (tile_slot, dig_tiles.hpp), then the sample (outside [0, n_samples), or keep[sample] == 0).  A pair
+//                              that counts gets key = (((cohort R + region) T + tile) << sb) | global sample; every other pair the
+//                              all-ones 63-bit key, which sorts behind every real one.
 //   -- the caller sorts the keys --
 //   tile_sample_counts_kernel  one thread per sorted key.  A run of equal keys is one (tile, sample) with n = its length.  The thread
 //                              whose left neighbour -- read from global memory: it may lie in the previous wave or workgroup -- has
-//                              another key is the run's head; it alone carries min(n, cap) and the 1 of its sample.  n is the distance
-//                              to the next head inside the wave; only a run that reaches the wave's last lane looks further
-//                              (keys_upper_bound, after one load that tells whether the run goes on at all).  The heads' values are
+//                              another key is the run's head; it alone carries min(n, cap) and the 1 of its sample (n: run_length,
+//                              dig_keyruns.hpp).  The heads' values are
 //                              added up per tile inside the wave (segment_sum, segment_count) and leave as one integer atomic per
 //                              plane, wave segment and tile: a tile that one sample hits with thousands of rows costs one atomic.
 // Integer atomics only: the result does not depend on the order.
 #include "dig_keyruns.hpp"
+#include "dig_tiles.hpp"
 
 namespace dig {
 
@@ -36,9 +35,10 @@ int tile_sample_key_layout(const char* fn, int64_t C, int64_t R, int64_t T, int6
     DIG_REQUIRE_IN(fn, C >= 0 && R >= 0 && T >= 0 && n_samples >= 0, "C, R, n_tiles, n_samples >= 0");
     const int64_t lim = (int64_t)1 << 31;
     DIG_REQUIRE_IN(fn, C < lim && R < lim && T < lim && n_samples < lim, "C, R, n_tiles and the sample count below 2^31");
+    int64_t slots = 0;
+    if (int rc = sparse_tile_slots(fn, C, R, T, &slots)) return rc;
     *sample_bits = key_bits_for(n_samples + 1);
-    const int64_t rows = C * R;                      // < 2^62
-    DIG_REQUIRE_IN(fn, (T == 0 || rows <= (((int64_t)1 << 62) - 1) / T) && key_bits_for(rows * T) + *sample_bits <= 63,
+    DIG_REQUIRE_IN(fn, key_bits_for(slots) + *sample_bits <= 63,
                    "the key (cohort, region, tile, global sample) does not fit 63 bits: fewer cohorts or regions per call");
     return DIG_OK;
 }
@@ -65,17 +65,10 @@ __global__ __launch_bounds__(kTileSampleBlock) void tile_sample_keys_kernel(Tile
     const int64_t m = a.pair_mut[i], r = a.pair_reg[i];
     int64_t key = kTileSampleNoKey;
     if ((uint64_t)m < (uint64_t)a.n_mut && (uint64_t)r < (uint64_t)a.R) {        // (a pair outside the tables reads nothing)
-        const int64_t off = a.mut_start[m] - a.first_pos[r];                     // START must be one of the region's positions
-        if (off >= 0) {
-            const int64_t t = off / a.binsize;
-            if (t < a.n_valid[r] && t < a.n_tiles) {
-                const int64_t c = a.mut_cohort[m];
-                if ((uint64_t)c < (uint64_t)a.C) {                               // a cohort id outside [0, C) has no plane to count in
-                    const int64_t s = a.mut_sample[m];
-                    if ((uint64_t)s < (uint64_t)a.n_samples && !(a.keep && a.keep[s] == 0))
-                        key = ((((c * a.R + r) * a.n_tiles) + t) << a.sample_bits) | s;
-                }
-            }
+        const int64_t slot = tile_slot(a.mut_start[m], a.mut_cohort[m], a.first_pos[r], a.n_valid[r], a.binsize, a.n_tiles, a.R, a.C, r);
+        if (slot >= 0) {
+            const int64_t s = a.mut_sample[m];
+            if ((uint64_t)s < (uint64_t)a.n_samples && !(a.keep && a.keep[s] == 0)) key = (slot << a.sample_bits) | s;
         }
     }
     a.keys[i] = key;
@@ -92,7 +85,6 @@ struct TileSampleCountArgs {
 __global__ __launch_bounds__(kTileSampleBlock) void tile_sample_counts_kernel(TileSampleCountArgs a)
 {
     const int64_t i = (int64_t)blockIdx.x * kTileSampleBlock + threadIdx.x;
-    const int lane = threadIdx.x & 63;
     int64_t slot = -1, key = -1;                     // slot: the tile, (cohort R + region) T + tile; -1: no key here, or one that counts nowhere
     bool head = false;
     if (i < a.n) {
@@ -102,17 +94,8 @@ __global__ __launch_bounds__(kTileSampleBlock) void tile_sample_counts_kernel(Ti
             head = i == 0 || a.keys[i - 1] != key;
         }
     }
-    // the run of a head inside the wave ends at the next head or at the next lane without a tile, whichever comes first
-    const unsigned long long heads = __ballot(head), rows = __ballot(slot >= 0);
-    int value = 0;
-    if (head) {
-        const unsigned long long above = lane == 63 ? 0ull : ~0ull << (lane + 1);
-        const unsigned long long stop = (heads | ~rows) & above;
-        int64_t len = (stop ? __ffsll((long long)stop) - 1 : 64) - lane;
-        // a run that reaches the wave's last lane may go on behind it: any number of waves and workgroups further
-        if (!stop && i + len < a.n && a.keys[i + len] == key) len = keys_upper_bound(a.keys, i + len + 1, a.n, key) - i;
-        value = (int)(a.cap > 0 && len > a.cap ? a.cap : len);
-    }
+    const int64_t len = run_length(a.keys, a.n, i, key, head, slot >= 0);
+    const int value = (int)(a.cap > 0 && len > a.cap ? a.cap : len);
     const int samples = segment_count(slot, head), capped = segment_sum(slot, value);
     if (!samples) return;                            // (a segment without a head: the tail of a run that another wave counts)
     if (a.k_cap) atomicAdd(&a.k_cap[slot], capped);

@@ -13,16 +13,17 @@
 //                             denom[c, r] = sum over the contexts of count * S[c][context] in ONE order: lane l of a wave adds the
 //                             contexts l, l + 64, ... ascending with fma, then the 64 partial sums fold by halves (32, 16, ..., 1).
 //                             No floating-point atomics: the bits depend on the region and the table alone.
-//   sparse_tile_keys_kernel   one thread per (mutation, region) pair of the interval join: the skip rules of tile_mut_counts_kernel
-//                             in its order; key = (cohort R + region) T + tile, INT64_MAX for a pair that counts nowhere.
+//   sparse_tile_keys_kernel   one thread per (mutation, region) pair of the interval join: key = tile_mut_counts_kernel's slot
+//                             (tile_slot, dig_tiles.hpp), (cohort R + region) T + tile; INT64_MAX for a pair that counts nowhere.
 //   -- the caller sorts the keys --
 //   sparse_tile_test_kernel   one thread per sorted key.  A run of equal keys is one mutated tile with k = its length; the run's
-//                             head (left neighbour in global memory differs) finds the length inside the wave by ballot and past
-//                             the wave with one keys_upper_bound, walks the tile's positions in order, pt = sum / denom, and runs
+//                             head (left neighbour in global memory differs) finds the length (run_length, dig_keyruns.hpp),
+//                             walks the tile's positions in order, pt = sum / denom, and runs
 //                             the arithmetic of tiled_nb_generic_kernel through the same device functions.  Every other entry is
 //                             written as "no tile" (k = 0).  Neighbouring lanes hold neighbouring tiles of one cohort: neighbouring
 //                             genome words and one table.
-// Both genome walkers read the tile kernels' 4-bit layout (dig_tiles.hpp), every word index clamped into the array.
+// Both genome walkers read the tile kernels' 4-bit layout through its view (TileGenome, sparse_region: dig_tiles.hpp), every word
+// index clamped into the array.
 #include "dig_keyruns.hpp"
 #include "dig_math.hpp"
 #include "dig_tiles.hpp"
@@ -31,7 +32,6 @@ namespace dig {
 
 constexpr int kSparseBlock = 256;
 constexpr int64_t kSparseNoKey = INT64_MAX;          // a pair that counts nowhere: sorts behind every real key
-constexpr int kSparseMaxPosPenta = 16384;            // kCtxMaxPos of dig_tiles.hip: a longer penta-nucleotide region is not evaluated
 
 // the sizes of the key (cohort R + region) T + tile: each below 2^31, the product within 62 bits
 int sparse_tile_slots(const char* fn, int64_t C, int64_t R, int64_t T, int64_t* slots)
@@ -49,30 +49,8 @@ int sparse_tile_slots(const char* fn, int64_t C, int64_t R, int64_t T, int64_t* 
 int64_t tile_census_workspace_bytes(int64_t C, int n_up)
 {
     if (C < 0 || (n_up != 1 && n_up != 2)) return 0;
-    const int64_t K = n_up == 1 ? 64 : 1024, passes = (C + 63) / 64;
+    const int64_t K = tile_contexts(n_up), passes = (C + 63) / 64;
     return (passes > 0 ? passes : 1) * K * (int64_t)sizeof(uint64_t);
-}
-
-// ---- a region, with a chromosome id outside the table read as a region without positions ----
-struct SparseGenome {
-    const uint32_t* words;
-    int64_t n_words;
-    const int64_t *chrom_off, *chrom_len;
-    int n_chrom;
-    const int32_t* reg_chrom;
-    const int64_t *reg_start, *reg_end;
-    int64_t R;
-};
-
-template <int U>
-__device__ __forceinline__ TileRegion sparse_region(const SparseGenome& g, int64_t r, bool* too_long)
-{
-    const int chrom = g.reg_chrom[r];
-    const int64_t start = g.reg_start[r], end = g.reg_end[r];
-    TileRegion q{start == 0 ? U : start, 0, 0};
-    if ((unsigned)chrom < (unsigned)g.n_chrom) q = region_positions(U, g.chrom_len[chrom], g.chrom_off[chrom], start, end);
-    *too_long = U == 2 && q.n_pos > kSparseMaxPosPenta;
-    return q;
 }
 
 // The windows of consecutive positions, one base at a time: ref is the table index of the last W bases (the leftmost base counts
@@ -128,7 +106,7 @@ __global__ __launch_bounds__(kSparseBlock) void tile_census_mask_kernel(const do
 }
 
 struct CensusArgs {
-    SparseGenome g;
+    TileGenome g;
     const double* s_prob;
     int64_t C;
     int binsize;
@@ -227,21 +205,15 @@ __global__ __launch_bounds__(kSparseBlock) void sparse_tile_keys_kernel(SparseKe
     const int64_t m = a.pair_mut[i], r = a.pair_reg[i];
     int64_t key = kSparseNoKey;
     if ((uint64_t)m < (uint64_t)a.n_mut && (uint64_t)r < (uint64_t)a.R) {        // (a pair outside the tables reads nothing)
-        const int64_t off = a.mut_start[m] - a.first_pos[r];                     // START must be one of the region's positions
-        if (off >= 0) {
-            const int64_t t = off / a.binsize;
-            if (t < a.n_valid[r] && t < a.n_tiles) {
-                const int64_t c = a.mut_cohort[m];
-                if ((uint64_t)c < (uint64_t)a.C) key = (c * a.R + r) * a.n_tiles + t;
-            }
-        }
+        const int64_t slot = tile_slot(a.mut_start[m], a.mut_cohort[m], a.first_pos[r], a.n_valid[r], a.binsize, a.n_tiles, a.R, a.C, r);
+        if (slot >= 0) key = slot;
     }
     a.keys[i] = key;
 }
 
 // ---- test ----
 struct SparseTestArgs {
-    SparseGenome g;
+    TileGenome g;
     const double* s_prob;
     int64_t C;
     int binsize;
@@ -259,7 +231,6 @@ __global__ __launch_bounds__(kSparseBlock) void sparse_tile_test_kernel(SparseTe
     constexpr int K = WindowWalk<U>::K;
     nb_tables_init();
     const int64_t i = (int64_t)blockIdx.x * kSparseBlock + threadIdx.x;
-    const int lane = threadIdx.x & 63;
     int64_t key = -1;
     bool row = false, head = false;                  // row: a key of a tile
     if (i < a.n) {
@@ -267,15 +238,10 @@ __global__ __launch_bounds__(kSparseBlock) void sparse_tile_test_kernel(SparseTe
         row = key >= 0 && key < a.slots;             // (negative, INT64_MAX or past the last tile: passed over, never dereferenced)
         head = row && (i == 0 || a.keys[i - 1] != key);
     }
-    const unsigned long long heads = __ballot(head), rows = __ballot(row);
+    const int64_t len = run_length(a.keys, a.n, i, key, head, row);
     int32_t c = -1, r = -1, t = -1, k = 0;
     double pt = dnan(), ex = dnan(), pv = dnan();
     if (head) {
-        // the run ends inside the wave at the next head or the next lane without a tile; one that reaches the last lane may go on
-        const unsigned long long above = lane == 63 ? 0ull : ~0ull << (lane + 1);
-        const unsigned long long stop = (heads | ~rows) & above;
-        int64_t len = (stop ? __ffsll((long long)stop) - 1 : 64) - lane;
-        if (!stop && i + len < a.n && a.keys[i + len] == key) len = keys_upper_bound(a.keys, i + len + 1, a.n, key) - i;
         const int64_t cr = key / a.n_tiles, tt = key - cr * a.n_tiles;
         const int64_t cc = cr / a.g.R, rr = cr - cc * a.g.R;
         bool too_long;
@@ -309,18 +275,6 @@ __global__ __launch_bounds__(kSparseBlock) void sparse_tile_test_kernel(SparseTe
     }
 }
 
-static int check_sparse_genome(const char* fn, const SparseGenome& g, int n_up, int binsize, int64_t C, int64_t n_tiles)
-{
-    DIG_REQUIRE_IN(fn, n_up == 1 || n_up == 2, "n_up = n_down = 1 (trinucleotide) or 2 (penta-nucleotide)");
-    DIG_REQUIRE_IN(fn, g.R >= 0 && C >= 0 && g.n_words >= 2 && g.n_chrom >= 0 && n_tiles >= 0, "non-negative sizes, n_words >= 2 (pad words)");
-    DIG_REQUIRE_IN(fn, binsize >= 1, "binsize >= 1");
-    const int64_t lim = (int64_t)1 << 31;
-    DIG_REQUIRE_IN(fn, g.R < lim && C < lim && n_tiles < lim, "C, R and n_tiles below 2^31");
-    if (g.R == 0) return DIG_OK;
-    DIG_REQUIRE_IN(fn, g.words && g.chrom_off && g.chrom_len && g.reg_chrom && g.reg_start && g.reg_end, "non-null genome and region tables");
-    return DIG_OK;
-}
-
 }  // namespace dig
 
 using namespace dig;
@@ -334,21 +288,22 @@ int dig_tile_census(const uint32_t* genome_words, int64_t n_words, const int64_t
                     int64_t C, int n_up, int binsize, int64_t n_tiles, int64_t* first_pos, int32_t* n_valid, double* denom,
                     int32_t* n_positive, void* workspace, int64_t workspace_bytes, void* stream)
 {
-    const SparseGenome g{genome_words, n_words, chrom_off, chrom_len, n_chrom, reg_chrom, reg_start, reg_end, R};
-    if (int rc = check_sparse_genome(__func__, g, n_up, binsize, C, n_tiles)) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    const TileArgs t{{genome_words, n_words, chrom_off, chrom_len, n_chrom, reg_chrom, reg_start, reg_end, R}, s_prob, C, n_up, binsize,
+                     n_tiles, nullptr, first_pos, n_valid, s};
+    if (int rc = check_tile_args(__func__, t, false)) return rc;
     if (R == 0) return DIG_OK;
     DIG_REQUIRE(first_pos && n_valid, "non-null first_pos, n_valid");
     DIG_REQUIRE(C == 0 || (s_prob && denom && n_positive), "non-null s_prob, denom, n_positive");
     const int64_t need = tile_census_workspace_bytes(C, n_up);
     DIG_REQUIRE(workspace && workspace_bytes >= need, "workspace of dig_tile_census_workspace(C, n_up) bytes");
     DIG_REQUIRE(((uintptr_t)workspace & 7) == 0, "workspace aligned to 8 bytes");
-    hipStream_t s = (hipStream_t)stream;
-    const int K = n_up == 1 ? 64 : 1024;
+    const int K = tile_contexts(n_up);
     uint64_t* mask = static_cast<uint64_t*>(workspace);
     const int64_t n_mask = need / (int64_t)sizeof(uint64_t);
     hipLaunchKernelGGL(tile_census_mask_kernel, dim3((unsigned)((n_mask + kSparseBlock - 1) / kSparseBlock)), dim3(kSparseBlock), 0, s,
                        s_prob, C, K, mask, n_mask);
-    const CensusArgs a{g, s_prob, C, binsize, n_tiles, mask, first_pos, n_valid, denom, n_positive};
+    const CensusArgs a{t.g, s_prob, C, binsize, n_tiles, mask, first_pos, n_valid, denom, n_positive};
     if (n_up == 1) hipLaunchKernelGGL(tile_census_kernel<1>, dim3((unsigned)R), dim3(kSparseBlock), 0, s, a);
     else hipLaunchKernelGGL(tile_census_kernel<2>, dim3((unsigned)R), dim3(kSparseBlock), 0, s, a);
     DIG_HIP_TRY(hipGetLastError());
@@ -380,15 +335,16 @@ int dig_sparse_tile_test(const uint32_t* genome_words, int64_t n_words, const in
                          const int64_t* keys_sorted, int64_t n, int32_t* out_cohort, int32_t* out_region, int32_t* out_tile,
                          int32_t* out_k, double* out_pt, double* out_exp, double* out_pval, void* stream)
 {
-    const SparseGenome g{genome_words, n_words, chrom_off, chrom_len, n_chrom, reg_chrom, reg_start, reg_end, R};
-    if (int rc = check_sparse_genome(__func__, g, n_up, binsize, C, n_tiles)) return rc;
+    const TileArgs t{{genome_words, n_words, chrom_off, chrom_len, n_chrom, reg_chrom, reg_start, reg_end, R}, s_prob, C, n_up, binsize,
+                     n_tiles, nullptr, nullptr, nullptr, (hipStream_t)stream};
+    if (int rc = check_tile_args(__func__, t, false)) return rc;
     DIG_REQUIRE(n >= 0 && n <= INT32_MAX, "0 <= n < 2^31 (the counts are 32-bit)");
     int64_t slots = 0;
     if (int rc = sparse_tile_slots(__func__, C, R, n_tiles, &slots)) return rc;
     if (n == 0) return DIG_OK;
     DIG_REQUIRE(keys_sorted && out_cohort && out_region && out_tile && out_k && out_pt && out_exp && out_pval, "non-null keys and outputs");
     DIG_REQUIRE(slots == 0 || (s_prob && denom && mu && sigma), "non-null s_prob, denom, mu, sigma");
-    const SparseTestArgs a{g, s_prob, C, binsize, n_tiles, denom, mu, sigma, keys_sorted, n, slots,
+    const SparseTestArgs a{t.g, s_prob, C, binsize, n_tiles, denom, mu, sigma, keys_sorted, n, slots,
                            out_cohort, out_region, out_tile, out_k, out_pt, out_exp, out_pval};
     unsigned blocks = 0;
     if (int rc = row_blocks(__func__, n, kSparseBlock, &blocks)) return rc;

@@ -1197,7 +1197,7 @@ def tiled_nb_test(pt, k, mu, sigma, device=0):
 # ---------------------------------------------------------------------------
 # per-base / tiled route: front half (dig_base_tile_probs + dig_tile_mut_counts) and the whole chain
 # ---------------------------------------------------------------------------
-TILE_CTX_MAX_POSITIONS = 16384      # positions of a region base_tile_probs_ctx_kernel evaluates (kCtxMaxPos, dig_tiles.hip)
+TILE_CTX_MAX_POSITIONS = 16384      # positions of the longest penta-nucleotide region the tile kernels evaluate (kCtxMaxPos, dig_tiles.hpp)
 
 
 def check_tile_regions(starts, ends, n_up):
@@ -1211,6 +1211,34 @@ def check_tile_regions(starts, ends, n_up):
         raise ValueError("a region that starts at 1 would fetch from a negative position (the reference's pysam fetch fails too)")
 
 
+def _tile_genome(be, genome, chroms, starts, ends, s_prob, binsize, n_tiles, dense=False):
+    """The 14 arguments dig_base_tile_probs_ctx, dig_tile_census and dig_sparse_tile_test begin with, checked: (the pointers and sizes
+    up to n_tiles in the entry points' order, the arrays behind them, C, R, n_tiles, n_up, binsize).  dense: base_tile_probs, which
+    leaves binsize to the library and asserts the table's shape."""
+    ci = genome.chrom_index(chroms)
+    R = len(ci)
+    st, en = _lib.as_host(starts, np.int64).ravel(), _lib.as_host(ends, np.int64).ravel()
+    if (st < 0).any() or (en < 0).any():
+        raise ValueError("negative region coordinates")
+    binsize = int(binsize)
+    if binsize < 1 and not dense:
+        raise ValueError("binsize >= 1")
+    if n_tiles is None:
+        n_tiles = int(max(1, -(-int((en - st).max() if R else 1) // binsize)))
+    s_prob = be.arr(s_prob, "f64")
+    if s_prob.ndim != 2 or s_prob.shape[1] not in (64, 1024):
+        raise (AssertionError if dense else ValueError)("s_prob must be [C, 64] (trinucleotide) or [C, 1024] (penta-nucleotide)")
+    C = s_prob.shape[0]
+    n_up = 1 if s_prob.shape[1] == 64 else 2
+    check_tile_regions(st, en, n_up)
+    words, off, ln = genome.on_device(be.dev) if be.is_device else (genome.words, genome.offsets, genome.lengths)
+    held = [words, off, ln] + [be.arr(a) for a in (ci, st, en)] + [s_prob]
+    p = be.ptr
+    args = [p(words), words.shape[0], p(off), p(ln), len(genome.names), p(held[3]), p(held[4]), p(held[5]), R, p(s_prob), C, n_up, binsize,
+            int(n_tiles)]
+    return args, held, C, R, int(n_tiles), n_up, binsize
+
+
 def base_tile_probs(genome, chroms, starts, ends, s_prob, binsize, n_tiles=None, device=0, on_device=True):
     """Tile probabilities of regions of a PackedGenome for C cohorts at once (sequence_tools.py:292-317 + the tiling of
     nb_model.py:126-186).  s_prob: f64 [C, 64] (trinucleotide contexts, index 16 b0 + 4 b1 + b2) or [C, 1024]
@@ -1219,25 +1247,10 @@ def base_tile_probs(genome, chroms, starts, ends, s_prob, binsize, n_tiles=None,
     on_device=True keeps the genome resident in HBM and returns device tensors; False goes through the host twin and returns
     arrays."""
     be = backend_on(device, on_device)
-    ci = genome.chrom_index(chroms)
-    R = len(ci)
-    st, en = _lib.as_host(starts, np.int64).ravel(), _lib.as_host(ends, np.int64).ravel()
-    if (st < 0).any() or (en < 0).any():
-        raise ValueError("negative region coordinates")
-    binsize = int(binsize)
-    if n_tiles is None:
-        n_tiles = int(max(1, -(-int((en - st).max() if R else 1) // binsize)))
-    s_prob = be.arr(s_prob, "f64")
-    assert s_prob.ndim == 2 and s_prob.shape[1] in (64, 1024), "s_prob must be [C, 64] (trinucleotide) or [C, 1024] (penta-nucleotide)"
-    C = s_prob.shape[0]
-    n_up = 1 if s_prob.shape[1] == 64 else 2
-    check_tile_regions(st, en, n_up)
-    words, off, ln = genome.on_device(be.dev) if be.is_device else (genome.words, genome.offsets, genome.lengths)
-    regions = [be.arr(a) for a in (ci, st, en)]
+    args, held, C, R, n_tiles, _, _ = _tile_genome(be, genome, chroms, starts, ends, s_prob, binsize, n_tiles, dense=True)
     pt, first, nval = be.empty((C, R, n_tiles), "f64"), be.empty(R, "i64"), be.empty(R, "i32")
     p = be.ptr
-    be.call("dig_base_tile_probs_ctx", p(words), words.shape[0], p(off), p(ln), len(genome.names), *[p(a) for a in regions], R,
-            p(s_prob), C, n_up, binsize, n_tiles, p(pt), p(first), p(nval))
+    be.call("dig_base_tile_probs_ctx", *args, p(pt), p(first), p(nval))
     return pt, first, nval
 
 
@@ -1248,15 +1261,26 @@ def tile_mut_counts(genome, chroms, starts, ends, first_pos, n_valid, mut_chrom,
     the tile that holds its START.  first_pos, n_valid as base_tile_probs returns them: device tensors -> a device tensor, arrays
     -> the host twins.  mut_*: device tensors or host arrays (chromosome labels as in `chroms`)."""
     be = backend_of(first_pos, n_valid)
-    first_pos, n_valid = be.arr(first_pos, "i64", (-1,)), be.arr(n_valid, "i32", (-1,))
+    first_pos, n_valid, pm, pr, ms, co = _tile_rows(be, genome, chroms, starts, ends, first_pos, n_valid, mut_chrom, mut_start, mut_end,
+                                                    mut_cohort)
     R = first_pos.shape[0]
-    pm, pr, ms = _tile_pairs(be, genome, chroms, starts, ends, mut_chrom, mut_start, mut_end)
-    co = be.arr(mut_cohort, "i32")
     k = be.empty((int(C), R, int(n_tiles)), "i32")
     p = be.ptr
     be.call("dig_tile_mut_counts", p(pm), p(pr), pm.shape[0], p(ms), *([] if be.is_device else [ms.shape[0]]), p(co), p(first_pos),
             p(n_valid), int(binsize), int(n_tiles), R, int(C), p(k))
     return k
+
+
+def _tile_rows(be, genome, chroms, starts, ends, first_pos, n_valid, mut_chrom, mut_start, mut_end, mut_cohort, R=-1,
+               what="mut_cohort"):
+    """What the three row-counting routes hand their entry points, checked: (first_pos i64 [R], n_valid i32 [R], pair_mut, pair_reg,
+    mut_start, mut_cohort i32 -- one entry per mutation row, or ValueError in the name of `what`)."""
+    first_pos, n_valid = be.arr(first_pos, "i64", (R,)), be.arr(n_valid, "i32", (R,))
+    pm, pr, ms = _tile_pairs(be, genome, chroms, starts, ends, mut_chrom, mut_start, mut_end)
+    co = be.arr(mut_cohort, "i32", (-1,))
+    if ms.shape[0] != co.shape[0]:
+        raise ValueError(what + ": one entry per mutation row")
+    return first_pos, n_valid, pm, pr, ms, co
 
 
 def _tile_pairs(be, genome, chroms, starts, ends, mut_chrom, mut_start, mut_end):
@@ -1281,8 +1305,7 @@ def tile_sample_counts(genome, chroms, starts, ends, first_pos, n_valid, mut_chr
     the backend, as tile_mut_counts.  ValueError for a row whose sample is outside its cohort and for a key (cohort, region, tile,
     sample) that does not fit 63 bits."""
     be = backend_of(first_pos, n_valid)
-    first_pos, n_valid = be.arr(first_pos, "i64", (-1,)), be.arr(n_valid, "i32", (-1,))
-    R, C, T = first_pos.shape[0], int(C), int(n_tiles)
+    C, T = int(C), int(n_tiles)
     off_host, _, S = _sample_offsets(sample_offsets, C)
     if cap is not None and (int(cap) != cap or cap < 1):
         raise ValueError("cap: an integer >= 1 (None: no cap)")
@@ -1297,11 +1320,10 @@ def tile_sample_counts(genome, chroms, starts, ends, first_pos, n_valid, mut_chr
         off, c = be.arr(off_host, "i64"), be.arr(co.clip(0, C - 1), "i64")
         if bool(((co >= 0) & (co < C) & ((sa < off[c]) | (sa >= off[c + 1]))).any()):
             raise ValueError("a row outside the tables: global sample within its cohort's range of sample_offsets")
-    pm, pr, ms = _tile_pairs(be, genome, chroms, starts, ends, mut_chrom, mut_start, mut_end)
-    if ms.shape[0] != co.shape[0]:
-        raise ValueError("mut_cohort, mut_sample: one entry per mutation row")
+    first_pos, n_valid, pm, pr, ms, co = _tile_rows(be, genome, chroms, starts, ends, first_pos, n_valid, mut_chrom, mut_start, mut_end, co,
+                                                    what="mut_cohort, mut_sample")
     p = be.ptr
-    n = pm.shape[0]
+    n, R = pm.shape[0], first_pos.shape[0]
     keys = be.empty(n, "i64")
     k_cap, k_samples = be.empty((C, R, T), "i32"), be.empty((C, R, T), "i32")
     with _requirements_as_value_errors():
@@ -1321,14 +1343,13 @@ def tiled_nb_model(genome, chroms, starts, ends, s_prob, mu, sigma, mut_chrom, m
     by_sample the dict also holds k_samples and pval_sample, the same test on k_samples."""
     pt, first, nval = base_tile_probs(genome, chroms, starts, ends, s_prob, binsize, device=device, on_device=on_device)
     C, R, n_tiles = pt.shape
+    rows = (genome, chroms, starts, ends, first, nval, mut_chrom, mut_start, mut_end, mut_cohort)
     if mut_sample is None:
         if sample_offsets is not None or keep is not None or cap is not None or by_sample:
             raise ValueError("sample_offsets, keep, cap and by_sample need mut_sample")
-        k = tile_mut_counts(genome, chroms, starts, ends, first, nval, mut_chrom, mut_start, mut_end, mut_cohort, C, binsize, n_tiles)
-        pval, ex = tiled_nb_test(pt, k, mu, sigma, device=device)
-        return dict(pval=pval, exp=ex, pt=pt, k=k, first_pos=first, n_valid=nval)
-    k, k_samples = tile_sample_counts(genome, chroms, starts, ends, first, nval, mut_chrom, mut_start, mut_end, mut_cohort, mut_sample,
-                                      sample_offsets, keep, cap, C, binsize, n_tiles)
+        k = tile_mut_counts(*rows, C, binsize, n_tiles)
+    else:
+        k, k_samples = tile_sample_counts(*rows, mut_sample, sample_offsets, keep, cap, C, binsize, n_tiles)
     pval, ex = tiled_nb_test(pt, k, mu, sigma, device=device)
     res = dict(pval=pval, exp=ex, pt=pt, k=k, first_pos=first, n_valid=nval)
     if by_sample:
@@ -1374,33 +1395,6 @@ def tile_window_test(pt, k, mu, sigma, n_valid, width, device=0, out=None):
 # ---------------------------------------------------------------------------
 # per-base route for the mutated tiles only (dig_tilesparse.hip): nothing here is [C, R, T]
 # ---------------------------------------------------------------------------
-def _tile_genome(be, genome, chroms, starts, ends, s_prob, binsize, n_tiles):
-    """The arguments dig_tile_census and dig_sparse_tile_test share, checked as base_tile_probs checks them: (the pointers and sizes
-    up to n_tiles in the entry points' order, the arrays behind them, C, R, n_tiles, n_up, binsize)."""
-    ci = genome.chrom_index(chroms)
-    R = len(ci)
-    st, en = _lib.as_host(starts, np.int64).ravel(), _lib.as_host(ends, np.int64).ravel()
-    if (st < 0).any() or (en < 0).any():
-        raise ValueError("negative region coordinates")
-    binsize = int(binsize)
-    if binsize < 1:
-        raise ValueError("binsize >= 1")
-    if n_tiles is None:
-        n_tiles = int(max(1, -(-int((en - st).max() if R else 1) // binsize)))
-    s_prob = be.arr(s_prob, "f64")
-    if s_prob.ndim != 2 or s_prob.shape[1] not in (64, 1024):
-        raise ValueError("s_prob must be [C, 64] (trinucleotide) or [C, 1024] (penta-nucleotide)")
-    C = s_prob.shape[0]
-    n_up = 1 if s_prob.shape[1] == 64 else 2
-    check_tile_regions(st, en, n_up)
-    words, off, ln = genome.on_device(be.dev) if be.is_device else (genome.words, genome.offsets, genome.lengths)
-    held = [words, off, ln] + [be.arr(a) for a in (ci, st, en)] + [s_prob]
-    p = be.ptr
-    args = [p(words), words.shape[0], p(off), p(ln), len(genome.names), p(held[3]), p(held[4]), p(held[5]), R, p(s_prob), C, n_up, binsize,
-            int(n_tiles)]
-    return args, held, C, R, int(n_tiles), n_up, binsize
-
-
 def tile_census(genome, chroms, starts, ends, s_prob, binsize, n_tiles=None, device=0, on_device=True):
     """What the sparse per-base scan knows of the regions without a [C, R, T] plane (dig_tile_census): first_pos i64 [R], n_valid i32
     [R] -- the bits base_tile_probs returns --, denom f64 [C, R], the region's sum of s_prob over its positions (what the dense route
@@ -1426,12 +1420,9 @@ def sparse_tile_test(genome, chroms, starts, ends, s_prob, binsize, n_tiles, fir
     k is dig_tile_mut_counts' count, pt / exp / pval what the dense route has there (pt to rounding: another order of additions)."""
     be = backend_of(first_pos, n_valid, denom)
     args, held, C, R, T, _, binsize = _tile_genome(be, genome, chroms, starts, ends, s_prob, binsize, n_tiles)
-    first_pos, n_valid = be.arr(first_pos, "i64", (R,)), be.arr(n_valid, "i32", (R,))
     denom, mu, sigma = (be.arr(x, "f64", (C, R)) for x in (denom, mu, sigma))
-    pm, pr, ms = _tile_pairs(be, genome, chroms, starts, ends, mut_chrom, mut_start, mut_end)
-    co = be.arr(mut_cohort, "i32", (-1,))
-    if ms.shape[0] != co.shape[0]:
-        raise ValueError("mut_cohort: one entry per mutation row")
+    first_pos, n_valid, pm, pr, ms, co = _tile_rows(be, genome, chroms, starts, ends, first_pos, n_valid, mut_chrom, mut_start, mut_end,
+                                                    mut_cohort, R)
     p = be.ptr
     n = pm.shape[0]
     keys = be.empty(n, "i64")
