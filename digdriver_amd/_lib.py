@@ -109,6 +109,12 @@ _SIGNATURES = {
     "dig_tile_select_count_host": [_vp] * 3 + [_i64] * 3 + [_vp, _int],
     "dig_tile_select_fill": [_vp] * 3 + [_i64] * 3 + [_vp, _i64] + [_vp] * 9 + [_vp],
     "dig_tile_select_fill_host": [_vp] * 3 + [_i64] * 3 + [_vp, _i64] + [_vp] * 9 + [_int],
+    "dig_row_select_count": [_vp, _vp, _i64, _i64, _vp, _vp],
+    "dig_row_select_count_host": [_vp, _vp, _i64, _i64, _vp, _int],
+    "dig_row_select_fill": [_vp, _vp, _i64, _i64, _vp, _i64, _vp, _vp, _vp],
+    "dig_row_select_fill_host": [_vp, _vp, _i64, _i64, _vp, _i64, _vp, _vp, _int],
+    "dig_row_scatter": [_vp, _vp, _i64, _i64, _vp, _i64, _vp, ctypes.c_double, _vp, _vp],
+    "dig_row_scatter_host": [_vp, _vp, _i64, _i64, _vp, _i64, _vp, ctypes.c_double, _vp, _int],
     "dig_tile_sample_keys": [_vp, _vp, _i64, _vp, _i64] + [_vp] * 5 + [_int] + [_i64] * 4 + [_vp, _vp],
     "dig_tile_sample_keys_host": [_vp, _vp, _i64, _vp, _i64] + [_vp] * 5 + [_int] + [_i64] * 4 + [_vp, _int],
     "dig_tile_sample_counts": [_vp] + [_i64] * 6 + [_vp, _vp, _vp],
@@ -193,6 +199,8 @@ _SIZE_QUERIES = {
     "dig_tile_census_workspace": [_i64, _int],
     "dig_cnv_segment_deltas_size": [_i64, _i64],
     "dig_cnv_window_means_size": [_i64, _i64],
+    "dig_row_select_chunk": [],
+    "dig_row_select_counts_size": [_i64, _i64],
 }
 
 ABI_VERSION = 12         # include/dig_hip.h: DIG_ABI_VERSION

@@ -627,6 +627,58 @@ int dig_tile_select_fill_host(const double* score, const int32_t* n_valid, const
                    hit_k && k ? st.out(hit_k, nt) : nullptr, nullptr);
 }
 
+// the offsets of a row-select twin: an exclusive prefix sum within total
+static int check_row_offsets(const char* fn, const int64_t* offsets, size_t n, int64_t total)
+{
+    for (size_t i = 0; i < n; ++i)
+        DIG_REQUIRE_IN(fn, offsets[i] >= (i ? offsets[i - 1] : 0) && offsets[i] <= total,
+                       "offsets: an exclusive prefix sum, 0 first, within total");
+    return DIG_OK;
+}
+
+int dig_row_select_count_host(const double* score, const double* cut, int64_t rows, int64_t n, int32_t* counts, int device)
+{
+    int64_t chunks = 0;
+    if (int rc = row_select_sizes(__func__, rows, n, &chunks)) return rc;
+    const size_t slots = (size_t)rows * chunks;
+    if (slots == 0) return DIG_OK;
+    DIG_REQUIRE(score && cut && counts, "non-null score, cut, counts");
+    Staging st(device);
+    return st.call(dig_row_select_count, st.in(score, (size_t)rows * n), st.in(cut, rows), rows, n, st.out(counts, slots), nullptr);
+}
+
+int dig_row_select_fill_host(const double* score, const double* cut, int64_t rows, int64_t n, const int64_t* offsets, int64_t total,
+                             int32_t* hit_index, double* hit_score, int device)
+{
+    int64_t chunks = 0;
+    if (int rc = row_select_sizes(__func__, rows, n, &chunks)) return rc;
+    DIG_REQUIRE(total >= 0, "total >= 0");
+    const size_t slots = (size_t)rows * chunks;
+    if (slots == 0 || total == 0) return DIG_OK;
+    DIG_REQUIRE(score && cut && offsets, "non-null score, cut, offsets");
+    if (int rc = check_row_offsets(__func__, offsets, slots, total)) return rc;
+    Staging st(device);
+    // (an output the call skips is not staged: the caller's array stays as it was)
+    return st.call(dig_row_select_fill, st.in(score, (size_t)rows * n), st.in(cut, rows), rows, n, st.in(offsets, slots), total,
+                   hit_index ? st.out(hit_index, (size_t)total) : nullptr, hit_score ? st.out(hit_score, (size_t)total) : nullptr,
+                   nullptr);
+}
+
+int dig_row_scatter_host(const double* score, const double* cut, int64_t rows, int64_t n, const int64_t* offsets, int64_t total,
+                         const double* values, double fill, double* out, int device)
+{
+    int64_t chunks = 0;
+    if (int rc = row_select_sizes(__func__, rows, n, &chunks)) return rc;
+    DIG_REQUIRE(total >= 0, "total >= 0");
+    const size_t slots = (size_t)rows * chunks;
+    if (slots == 0) return DIG_OK;
+    DIG_REQUIRE(score && cut && offsets && out && (values || total == 0), "non-null score, cut, offsets, out, values");
+    if (int rc = check_row_offsets(__func__, offsets, slots, total)) return rc;
+    Staging st(device);
+    return st.call(dig_row_scatter, st.in(score, (size_t)rows * n), st.in(cut, rows), rows, n, st.in(offsets, slots), total,
+                   st.in(values, (size_t)total), fill, st.out(out, (size_t)rows * n), nullptr);
+}
+
 int dig_scale_suffstats_host(const double* bin_mu, const uint8_t* bin_flag, int64_t N, int64_t C, double* out_sum, int device)
 {
     DIG_REQUIRE(N >= 0 && C >= 0, "N, C >= 0");

@@ -1,4 +1,4 @@
-// dig_keyruns.hpp -- what the counting routes (dig_genecounts.hip, dig_objectives.hip, dig_panelcounts.hip, dig_seqcounts.hip, dig_sitematch.hip, dig_tilehits.hip, dig_tilesamples.hip, dig_tilesparse.hip, dig_tilewindows.hip, dig_cnvwindows.hip) and their host twins share:
+// dig_keyruns.hpp -- what the counting routes (dig_genecounts.hip, dig_objectives.hip, dig_panelcounts.hip, dig_seqcounts.hip, dig_sitematch.hip, dig_tilehits.hip, dig_rowhits.hip, dig_tilesamples.hip, dig_tilesparse.hip, dig_tilewindows.hip, dig_cnvwindows.hip) and their host twins share:
 // rows encoded as 63-bit keys, sorted by the caller, counted as runs with one integer atomic per wave segment.
 #pragma once
 #include "dig_common.hpp"
@@ -35,6 +35,12 @@ int panel_key_layout(const char* fn, int64_t L, int64_t P, int64_t C, int64_t n_
 
 // dig_tilehits.hip: the sizes of a score plane [C, R, T]; DIG_EINVAL (in the name of entry point `fn`) unless C R < 2^31 and T < 2^31
 int tile_select_sizes(const char* fn, int64_t C, int64_t R, int64_t T);
+
+// dig_rowhits.hip: the elements of a chunk of a score plane [rows, n] (dig_row_select_chunk), the size checks of its entry points
+// and the chunks per row, ceil(n / kRowSelectChunk); DIG_EINVAL (in the name of entry point `fn`) unless rows, n >= 0, n < 2^31 and
+// rows * chunks < 2^31
+constexpr int kRowSelectChunk = 2048;
+int row_select_sizes(const char* fn, int64_t rows, int64_t n, int64_t* chunks);
 
 // dig_tilewindows.hip: tile_select_sizes and 1 <= width <= DIG_TILE_WINDOW_MAX_WIDTH, for dig_tile_window_test and its host twin
 int tile_window_sizes(const char* fn, int64_t C, int64_t R, int64_t T, int32_t width);

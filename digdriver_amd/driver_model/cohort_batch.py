@@ -137,18 +137,17 @@ class _Stages:
         self.t = now
 
 
-def run_element_cohorts(f_muts, f_pretrained, f_element_data, save_key, scale_factors=None, max_muts_per_sample=3e9,
-                        max_muts_per_elt_per_sample=3e9, device=0, timings=None, read_workers=None, on_frame=None,
-                        output_form="records"):
-    """One result frame per cohort (index ELT, the columns of run_element_region_model) for the mutation files
-    `f_muts[c]` against the pretrained maps `f_pretrained[c]` (one bin grid) and the element set `save_key` of
-    `f_element_data`.  scale_factors: (cj [C], cj_indel [C]) or None for the genome mode.
-    timings: dict that receives seconds per stage; read_workers: threads that parse the C mutation files and read the C
-    maps side by side (default: min(C, cores) from 8 cohorts on, else 1 = in this process).
-    on_frame(c, frame, columns, index): called as soon as cohort c's frame exists -- the frame, the dict of column arrays it was
-    built from and its row index (run_and_write_element_cohorts hands them to a writer thread there, so that the result files
-    are written while the next frames are assembled).
-    output_form: "records" (default) or "planes" -- the layout the statistics stage writes on the device (see below; same frames).
+_PVAL_PLANES = {'PVAL_SNV_BURDEN': 1, 'PVAL_SAMPLE_BURDEN': 2, 'PVAL_INDEL_BURDEN': 5, 'PVAL_MUT_BURDEN': 6}     # in engine.ES_PLANES
+_QVAL_COLUMNS = ['QVAL_' + k[5:] for k in _PVAL_PLANES]                 # in the order they stand behind the frame's columns
+
+
+def _element_pass(f_muts, f_pretrained, f_element_data, save_key, scale_factors=None, max_muts_per_sample=3e9,
+                  max_muts_per_elt_per_sample=3e9, device=0, timings=None, read_workers=None, output_form="records"):
+    """The front half run_element_cohorts and run_element_calls share: the three inputs read side by side, the tabulation, the scale
+    factors, the plan's pass and its unpacking.  Returns (planes, names, stages): `planes()` gives every plane a frame is built from
+    as a device tensor, a cohort's column one contiguous row -- ELT_SIZE, R_SIZE, P_INDEL [E]; FLAG, R_OBS, MU, SIGMA, ALPHA, THETA
+    (unscaled), P0, OBS_SNV, OBS_SAMPLES, OBS_INDEL [C, E]; S [7, C, E] (engine.ES_PLANES); CJ [C] -- `names` the element names and
+    `stages` the _Stages of `timings`, marked up to "kernels".
     The three inputs are independent until the kernels need them, so they are read SIDE BY SIDE (round 5; one after the other
     they were 0.8 of the 1.5 s of a 37-cohort run): the maps (a thread per map), the element container, and the mutation
     files -- each parsed by the library's own parser and uploaded by its own thread as soon as it is parsed."""
@@ -227,8 +226,7 @@ def run_element_cohorts(f_muts, f_pretrained, f_element_data, save_key, scale_fa
     # cache misses on the host) -- in ONE kernel; the plane form (`output_form="planes"`: eleven [E, C] arrays) needs a transpose per
     # plane behind the pass.  Same bits.  The general (192-substitution) form of the accumulation, as the per-cohort route runs it:
     # the same P to the last bit.
-    host = lambda x: x.cpu().numpy()
-    by_cohort = lambda x: host(x.transpose(-1, -2).contiguous())
+    by_cohort = lambda x: x.transpose(-1, -2).contiguous()
     plan = engine.PipelinePlan(*args, obs_snv, obs_smp, obs_ind, compact=False, pack_bins=True, records_out=(output_form == "records"))
     if plan.records_out:
         acc, _ = plan.run(cj, cji)
@@ -240,36 +238,169 @@ def run_element_cohorts(f_muts, f_pretrained, f_element_data, save_key, scale_fa
         plan.unpack(cohort_major=True, stats=st_cm, rates=rates)
         alpha, theta = nb_model.normal_params_to_gamma(rates["MU"], rates["SIGMA"])
         st_.mark("kernels")
-        A = {k: host(v) for k, v in acc.items() if k not in ('P', 'MU', 'SIGMA', 'R_OBS', 'FLAG')}
-        A.update({k: host(v) for k, v in rates.items()})
-        S, al, th = host(st_cm), host(alpha), host(theta)
+
+        def planes():
+            D = {k: v for k, v in acc.items() if k not in ('P', 'MU', 'SIGMA', 'R_OBS', 'FLAG')}
+            D.update(rates, S=st_cm, ALPHA=alpha, THETA=theta)
+            return D
     else:
         acc, st = plan.run(cj, cji)
         alpha, theta = nb_model.normal_params_to_gamma(acc["MU"], acc["SIGMA"])
         st_.mark("kernels")
-        A = {k: (by_cohort(v) if v.dim() == 2 else host(v)) for k, v in acc.items() if k != 'P'}            # (P [E, 1, C]: its one class below)
-        S, al, th = by_cohort(st), by_cohort(alpha), by_cohort(theta)
-    P0 = host(acc['P'][:, 0, :].transpose(0, 1).contiguous())
-    cj_h, cji_h = host(cj), host(cji)
-    o_snv, o_smp, o_ind = by_cohort(obs_snv), by_cohort(obs_smp), by_cohort(obs_ind)
+
+        def planes():
+            D = {k: (by_cohort(v) if v.dim() == 2 else v) for k, v in acc.items() if k != 'P'}              # (P [E, 1, C]: its one class below)
+            D.update(S=by_cohort(st), ALPHA=by_cohort(alpha), THETA=by_cohort(theta))
+            return D
+
+    def all_planes():
+        D = planes()
+        D.update(P0=acc['P'][:, 0, :].transpose(0, 1).contiguous(), CJ=cj, OBS_SNV=by_cohort(obs_snv), OBS_SAMPLES=by_cohort(obs_smp),
+                 OBS_INDEL=by_cohort(obs_ind))
+        return D
+    return all_planes, elts['names'], st_
+
+
+def _element_columns(x, cj, have_indel, q=None):
+    """The columns of one cohort's frame, in the frame's order, from host arrays: x maps a plane of _element_pass to the cohort's row of
+    it (S: [7, rows]) -- every element for run_element_cohorts, the hits for run_element_calls --, cj is the cohort's scale factor,
+    q [4, rows] or None the q-values of the four PVAL columns."""
+    S = x['S']
+    d = {'ELT_SIZE': x['ELT_SIZE'], 'FLAG': x['FLAG'].astype(bool), 'R_SIZE': x['R_SIZE'], 'R_OBS': x['R_OBS'],
+         'R_INDEL': x['R_OBS'], 'MU': x['MU'], 'SIGMA': x['SIGMA'], 'ALPHA': x['ALPHA'],
+         'THETA': x['THETA'] * cj, 'MU_INDEL': x['MU'], 'SIGMA_INDEL': x['SIGMA'], 'ALPHA_INDEL': x['ALPHA'],
+         'THETA_INDEL': S[3] if have_indel else x['THETA'], 'Pi_SUM': x['P0'], 'Pi_INDEL': x['P_INDEL'],
+         'OBS_SAMPLES': x['OBS_SAMPLES'].astype(float), 'OBS_SNV': x['OBS_SNV'].astype(float), 'OBS_INDEL': x['OBS_INDEL'].astype(float),
+         'EXP_SNV': S[0], 'PVAL_SNV_BURDEN': S[1], 'PVAL_SAMPLE_BURDEN': S[2]}
+    if have_indel:                                           # transfer_tools.py:1079-1087
+        d.update({'EXP_INDEL': S[4], 'PVAL_INDEL_BURDEN': S[5], 'PVAL_MUT_BURDEN': S[6]})
+    if q is not None:
+        d.update({k: q[i] for i, k in enumerate(_QVAL_COLUMNS[:4 if have_indel else 2])})
+    return d
+
+
+def _cohort_rows_of(X, c):
+    """Cohort c's row of every host plane of _element_pass (a per-element plane as it is, CJ left out)."""
+    return {k: (v if v.ndim == 1 else v[:, c] if v.ndim == 3 else v[c]) for k, v in X.items() if k != 'CJ'}
+
+
+def _ragged_qvalues(p):
+    """p f64 [rows, n] on the device -> (the non-NaN values of every row as ragged lists: engine.row_select at cut = +inf, index
+    left out; their Benjamini-Hochberg q-values within the row, in the lists' order: nb_model.bh_ragged)."""
+    lists = engine.row_select(p, float("inf"), index=False)
+    q = nb_model.bh_ragged(lists["score"], lists["row_ptr"])[0] if lists["score"].numel() else lists["score"].clone()
+    return lists, q
+
+
+def plane_qvalues(p):
+    """Benjamini-Hochberg q-values along the last axis of an f64 device tensor [..., n], over the TESTABLE (non-NaN) values of every
+    row: row r of the result holds the bits of nb_model.get_q_vals(p[r][~isnan(p[r])]) where p is a number and NaN where it is NaN.
+    engine.row_select at cut = +inf takes the testable values out, nb_model.bh_ragged ranks them (dig_bh_qvalues_ragged),
+    engine.row_scatter puts the q-values back; no argsort on the host."""
+    import torch
+    assert p.is_cuda and p.dtype == torch.float64
+    flat = p.contiguous().reshape(-1, p.shape[-1])
+    _, q = _ragged_qvalues(flat)
+    return engine.row_scatter(flat, float("inf"), q, float("nan")).reshape(p.shape)
+
+
+def run_element_cohorts(f_muts, f_pretrained, f_element_data, save_key, scale_factors=None, max_muts_per_sample=3e9,
+                        max_muts_per_elt_per_sample=3e9, device=0, timings=None, read_workers=None, on_frame=None,
+                        output_form="records", qvalues=False):
+    """One result frame per cohort (index ELT, the columns of run_element_region_model) for the mutation files
+    `f_muts[c]` against the pretrained maps `f_pretrained[c]` (one bin grid) and the element set `save_key` of
+    `f_element_data`.  scale_factors: (cj [C], cj_indel [C]) or None for the genome mode.
+    timings: dict that receives seconds per stage; read_workers: threads that parse the C mutation files and read the C
+    maps side by side (default: min(C, cores) from 8 cohorts on, else 1 = in this process).
+    on_frame(c, frame, columns, index): called as soon as cohort c's frame exists -- the frame, the dict of column arrays it was
+    built from and its row index (run_and_write_element_cohorts hands them to a writer thread there, so that the result files
+    are written while the next frames are assembled).
+    output_form: "records" (default) or "planes" -- the layout the statistics stage writes on the device (same frames).
+    qvalues: behind the columns of the frame, QVAL_SNV_BURDEN, QVAL_SAMPLE_BURDEN and, where the cohort has indel columns,
+    QVAL_INDEL_BURDEN, QVAL_MUT_BURDEN: Benjamini-Hochberg over the column's non-NaN p-values (plane_qvalues; NaN where PVAL is)."""
+    planes, names, st_ = _element_pass(f_muts, f_pretrained, f_element_data, save_key, scale_factors, max_muts_per_sample,
+                                       max_muts_per_elt_per_sample, device, timings, read_workers, output_form)
+    D = planes()
+    if qvalues:
+        Q = plane_qvalues(D['S'][list(_PVAL_PLANES.values())]).cpu().numpy()             # [4, C, E]
+        st_.mark("qvalues")
+    X = {k: v.cpu().numpy() for k, v in D.items()}
     st_.mark("d2h")
     frames = []
-    index = pd.Index(elts['names'], name='ELT')              # one object for all cohorts
-    for c in range(C):
-        have_indel = o_ind[c].sum() != 0
-        d = {'ELT_SIZE': A['ELT_SIZE'], 'FLAG': A['FLAG'][c].astype(bool), 'R_SIZE': A['R_SIZE'], 'R_OBS': A['R_OBS'][c],
-             'R_INDEL': A['R_OBS'][c], 'MU': A['MU'][c], 'SIGMA': A['SIGMA'][c], 'ALPHA': al[c],
-             'THETA': th[c] * cj_h[c], 'MU_INDEL': A['MU'][c], 'SIGMA_INDEL': A['SIGMA'][c], 'ALPHA_INDEL': al[c],
-             'THETA_INDEL': S[3][c] if have_indel else th[c], 'Pi_SUM': P0[c], 'Pi_INDEL': A['P_INDEL'],
-             'OBS_SAMPLES': o_smp[c].astype(float), 'OBS_SNV': o_snv[c].astype(float), 'OBS_INDEL': o_ind[c].astype(float),
-             'EXP_SNV': S[0][c], 'PVAL_SNV_BURDEN': S[1][c], 'PVAL_SAMPLE_BURDEN': S[2][c]}
-        if have_indel:                                       # transfer_tools.py:1079-1087
-            d.update({'EXP_INDEL': S[4][c], 'PVAL_INDEL_BURDEN': S[5][c], 'PVAL_MUT_BURDEN': S[6][c]})
+    index = pd.Index(names, name='ELT')                      # one object for all cohorts
+    for c in range(len(f_muts)):
+        d = _element_columns(_cohort_rows_of(X, c), X['CJ'][c], X['OBS_INDEL'][c].sum() != 0, Q[:, c] if qvalues else None)
         frames.append(pd.DataFrame(d, index=index))
         if on_frame is not None:
             on_frame(c, frames[-1], d, index)
     st_.mark("frames")
     return frames
+
+
+def run_element_calls(f_muts, f_pretrained, f_element_data, save_key, pval_max=None, fdr=None, cut_on='PVAL_SNV_BURDEN',
+                      scale_factors=None, max_muts_per_sample=3e9, max_muts_per_elt_per_sample=3e9, device=0, timings=None,
+                      read_workers=None, output_form="records"):
+    """The rows of run_element_cohorts(..., qvalues=True)'s frames that pass a cut, without the frames being built: frame c equals
+    that frame restricted to the rows with `cut_on` <= pval_max, or with the q-value of `cut_on` <= fdr -- the same columns, dtypes,
+    row order and bits.  Exactly one of pval_max / fdr; cut_on: one of the four PVAL_*_BURDEN columns (an indel column that a cohort
+    lacks is a ValueError).  frame.attrs['n_testable']: the non-NaN values of cut_on in the cohort.
+    fdr: p* per cohort from nb_model.bh_cut over the cohort's testable p-values ({q <= fdr} = {p <= p*}); the hits are
+    engine.row_select at p* (pval_max: at pval_max), every column is gathered at (cohort, element) on the device, and only the hits
+    cross to the host.  The other options as run_element_cohorts takes them."""
+    if (pval_max is None) == (fdr is None):
+        raise ValueError("exactly one of pval_max and fdr must be given")
+    if cut_on not in _PVAL_PLANES:
+        raise ValueError("cut_on: one of %s" % ", ".join(_PVAL_PLANES))
+    import torch
+    planes, names, st_ = _element_pass(f_muts, f_pretrained, f_element_data, save_key, scale_factors, max_muts_per_sample,
+                                       max_muts_per_elt_per_sample, device, timings, read_workers, output_form)
+    D = planes()
+    C, E = D['MU'].shape
+    have_indel = (D['OBS_INDEL'].sum(dim=1) != 0).cpu().numpy()
+    j = list(_PVAL_PLANES).index(cut_on)
+    if j >= 2 and not have_indel.all():
+        raise ValueError("cut_on = %s: cohorts %s have no indel columns" % (cut_on, [c for c in range(C) if not have_indel[c]]))
+    pvals = D['S'][list(_PVAL_PLANES.values())].reshape(4 * C, E)                     # row k C + c: PVAL column k of cohort c
+    lists, q_lists = _ragged_qvalues(pvals)
+    Q = engine.row_scatter(pvals, float("inf"), q_lists, float("nan")).reshape(4, C, E)
+    ptr = lists["row_ptr"][j * C:(j + 1) * C + 1]                                     # the lists of cut_on
+    if fdr is not None:
+        cuts = np.array([nb_model.bh_cut(lists["score"][ptr[c]:ptr[c + 1]], q_lists[ptr[c]:ptr[c + 1]], fdr) for c in range(C)])
+    else:
+        cuts = np.full(C, float(pval_max))
+    hits = engine.row_select(pvals[j * C:(j + 1) * C], cuts)
+    hit_ptr, elt = hits["row_ptr"], hits["index"].long()
+    st_.mark("qvalues_select")
+    cohort = torch.as_tensor(np.repeat(np.arange(C), np.diff(hit_ptr)), device=elt.device)
+    at = lambda v: v[elt] if v.dim() == 1 else v[:, cohort, elt] if v.dim() == 3 else v[cohort, elt]
+    X = {k: (v if k == 'CJ' else at(v)).cpu().numpy() for k, v in D.items()}
+    q_hits, elt = at(Q).cpu().numpy(), elt.cpu().numpy()
+    st_.mark("d2h")
+    frames = []
+    index = pd.Index(names, name='ELT')
+    for c in range(C):
+        lo, hi = int(hit_ptr[c]), int(hit_ptr[c + 1])
+        d = _element_columns({k: v[..., lo:hi] for k, v in X.items() if k != 'CJ'}, X['CJ'][c], have_indel[c], q_hits[:, lo:hi])
+        frames.append(pd.DataFrame(d, index=index[elt[lo:hi]]))
+        frames[-1].attrs['n_testable'] = int(ptr[c + 1] - ptr[c])
+    st_.mark("frames")
+    return frames
+
+
+def run_and_write_element_calls(f_muts, f_pretrained, f_element_data, save_key, outdir, prefixes, write_threads=None, **kw):
+    """run_element_calls with cohort c's hits written to <outdir>/<prefix>.hits.txt (mapfile.write_results_tsv, the OBS_* columns as
+    integers like those of the results files), several files at a time as write_results writes them.  Returns (frames, paths)."""
+    import os
+    from concurrent.futures import ThreadPoolExecutor
+    frames = run_element_calls(f_muts, f_pretrained, f_element_data, save_key, **kw)
+    assert len(prefixes) == len(frames)
+    os.makedirs(outdir, exist_ok=True)
+    paths = [os.path.join(outdir, pfx + '.hits.txt') for pfx in prefixes]
+    cores = os.cpu_count() or 1
+    threads = int(write_threads) if write_threads else max(1, min(8, cores // max(len(frames), 1)))
+    with ThreadPoolExecutor(max_workers=max(1, min(len(frames), cores))) as pool:
+        list(pool.map(lambda job: _write_one(job[0], job[1], threads), zip(frames, paths)))
+    return frames, paths
 
 
 def _run_and_write(run, n, outdir, prefixes, write_threads, writer):

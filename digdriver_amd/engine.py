@@ -1486,6 +1486,73 @@ def tile_select(score, n_valid, cut, pt=None, exp=None, k=None, device=0, index=
     return res
 
 
+def row_select_chunk():
+    """The elements of a chunk of dig_row_select_* (a wave's share of a row): dig_row_select_chunk."""
+    return int(_lib.load().dig_row_select_chunk())
+
+
+def _row_counts(be, score, cut):
+    """dig_row_select_count on the backend's arrays: ((score [rows, n], cut [rows]), counts i32 [rows * chunks], rows, n)."""
+    score = be.arr(score, "f64")
+    assert score.ndim == 2, "score must be [rows, n]"
+    rows, n = (int(s) for s in score.shape)
+    # (a Python number is made a float64 array first: as a tensor it would be rounded to float32, and the rule is inclusive)
+    cut = _per_cohort(be, cut if is_cuda(cut) else np.asarray(cut, np.float64), rows)
+    with _requirements_as_value_errors():
+        size = int(_lib.load().dig_row_select_counts_size(rows, n))
+        if size < 0:
+            raise ValueError(_lib.last_error())
+        counts = be.empty(size, "i32")
+        be.call("dig_row_select_count", be.ptr(score), be.ptr(cut), rows, n, be.ptr(counts))
+    return (score, cut), counts, rows, n
+
+
+def row_select_counts(score, cut, device=0):
+    """counts i32 [rows, chunks]: the selected elements of every chunk (row_select_chunk() elements) of every row of a score plane
+    -- the first call of row_select alone."""
+    be = backend_of(score, device=device)
+    _, counts, rows, _ = _row_counts(be, score, cut)
+    return counts.reshape(rows, int(counts.shape[0]) // rows if rows else 0)
+
+
+def row_select(score, cut, device=0, index=True):
+    """The elements of a score plane f64 [rows, n] that pass their row's cut, as ragged lists: dig_row_select_count, a cumulative
+    sum, dig_row_select_fill.  cut f64 [rows] (a single value stands for every row).  Element (r, e) is selected when
+    score[r, e] <= cut[r]; a NaN on either side never is, cut = +inf takes every score that is a number.
+    Returns dict(index i32, score f64 [selected], row-major and ascending in e within a row; row_ptr host int64 [rows + 1]: where
+    a row's list starts); index=False leaves the index out (the lists of a Benjamini-Hochberg pass).  ValueError, before the fill,
+    for more than 2^31 - 1 selected elements.  CUDA tensors in -> CUDA tensors out."""
+    be = backend_of(score, device=device)
+    held, counts, rows, n = _row_counts(be, score, cut)                  # (held: the arrays behind the pointers stay alive)
+    p = be.ptr
+    with _requirements_as_value_errors():
+        offsets, total, row_ptr = _scan(be, counts, groups=rows)
+        if total > 2 ** 31 - 1:
+            raise ValueError("%d selected elements: a smaller cut or fewer rows per call" % total)
+        res = dict(index=be.empty(total, "i32")) if index else {}
+        res["score"] = be.empty(total, "f64")
+        be.call("dig_row_select_fill", p(held[0]), p(held[1]), rows, n, p(offsets), total, p(res.get("index")), p(res["score"]))
+    res["row_ptr"] = row_ptr
+    return res
+
+
+def row_scatter(score, cut, values, fill=float("nan"), device=0):
+    """The inverse of row_select: out f64 [rows, n] with values[slot] where (r, e) is selected -- values f64 [selected], in the order
+    of row_select's lists -- and `fill` elsewhere (dig_row_select_count, a cumulative sum, dig_row_scatter).  Every element of out
+    is written.  CUDA tensors in -> CUDA tensors out."""
+    be = backend_of(score, values, device=device)
+    held, counts, rows, n = _row_counts(be, score, cut)
+    values = be.arr(values, "f64", (-1,))
+    p = be.ptr
+    with _requirements_as_value_errors():
+        offsets, total = _scan(be, counts)
+        if int(values.shape[0]) != total:
+            raise ValueError("%d values for %d selected elements" % (int(values.shape[0]), total))
+        out = be.empty((rows, n), "f64")
+        be.call("dig_row_scatter", p(held[0]), p(held[1]), rows, n, p(offsets), total, p(values), float(fill), p(out))
+    return out
+
+
 # ---------------------------------------------------------------------------
 # scale factors in canonical chunks: identical bits for any sharding of the bins (dig_scale_suffstats_chunked)
 # ---------------------------------------------------------------------------

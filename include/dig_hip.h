@@ -529,6 +529,35 @@ int dig_tile_select_fill_host(const double *score, const int32_t *n_valid, const
                               int32_t *hit_region, int32_t *hit_tile, double *hit_score, double *hit_pt, double *hit_exp,
                               int32_t *hit_k, int device);
 
+/* ---- the calls of the element route: ragged lists out of a score plane and back (additive: the ABI version stays) -- *
+ * score f64 [rows, n] (a row: one p-value column of one cohort over n elements), cut f64 [rows].  Element (r, e) is SELECTED when
+ * score[r, e] <= cut[r]: the rule of dig_tile_select_* without n_valid.  A NaN score or a NaN cut selects nothing, cut = +inf takes
+ * every score that is a number.  A row is cut into chunks of K = dig_row_select_chunk() consecutive elements, chunks =
+ * ceil(n / K) per row, chunk w = r * chunks + c; one wave owns a chunk.  rows, n >= 0, n < 2^31, rows * chunks < 2^31 and
+ * total >= 0 (DIG_EINVAL otherwise, before anything is read).  Every typed pointer needs the alignment of its element and no more.
+ *   dig_row_select_counts_size(rows, n) = rows * chunks, the elements of counts and of offsets (-1 for sizes that are refused).
+ *   dig_row_select_count: counts i32 [rows * chunks] = the selected elements of every chunk; each slot is written once, by the
+ *     chunk's wave: no atomics, and counts need not be zeroed.
+ *   The caller forms offsets i64 [rows * chunks], the exclusive prefix sum of counts, and total, their sum.
+ *   dig_row_select_fill: the selected elements in row-major order, ascending in e within a row, as hit_index i32 [total] (e) and
+ *     hit_score f64 [total]; each may be NULL.  A chunk writes only inside its own slots [offsets[w], offsets[w + 1]) (total behind
+ *     the last chunk) and inside [0, total): offsets that are not the prefix sum write nowhere else (the host twin refuses them).
+ *   dig_row_scatter: the inverse of the fill.  out f64 [rows, n]: out[r, e] = values[slot of (r, e)] where (r, e) is selected and
+ *     its slot lies in the chunk's range, `fill` elsewhere; values f64 [total].  Every element of out is written.
+ * No atomics; nothing is launched for empty inputs. */
+int64_t dig_row_select_chunk(void);
+int64_t dig_row_select_counts_size(int64_t rows, int64_t n);
+int dig_row_select_count(const double *score, const double *cut, int64_t rows, int64_t n, int32_t *counts, void *stream);
+int dig_row_select_count_host(const double *score, const double *cut, int64_t rows, int64_t n, int32_t *counts, int device);
+int dig_row_select_fill(const double *score, const double *cut, int64_t rows, int64_t n, const int64_t *offsets, int64_t total,
+                        int32_t *hit_index, double *hit_score, void *stream);
+int dig_row_select_fill_host(const double *score, const double *cut, int64_t rows, int64_t n, const int64_t *offsets, int64_t total,
+                             int32_t *hit_index, double *hit_score, int device);
+int dig_row_scatter(const double *score, const double *cut, int64_t rows, int64_t n, const int64_t *offsets, int64_t total,
+                    const double *values, double fill, double *out, void *stream);
+int dig_row_scatter_host(const double *score, const double *cut, int64_t rows, int64_t n, const int64_t *offsets, int64_t total,
+                         const double *values, double fill, double *out, int device);
+
 /* ---- the per-base route's counts by sample for many cohorts (additive: the ABI version stays) ------------------- *
  * dig_tile_mut_counts counts rows, whoever they belong to.  These two entry points count them per sample: with n(c, r, t, s) the
  * rows of GLOBAL sample s that dig_tile_mut_counts would count in tile (c, r, t) -- the same pairs, the same skip rules --

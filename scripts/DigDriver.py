@@ -6,7 +6,8 @@ arguments and option names (DigDriver.py:160-275), and the same output, a tab-se
 ``<outdir>/<outpfx>.results.txt`` with header and index column (DigDriver.py:38-43,115-118); and `tileDriver`, which the
 reference does not have: the per-base scan of many cohorts, written as ``<outdir>/<outpfx>.hits.txt``; and `quickCohorts`,
 `quickDriver` for many cohorts in one pass, one ``<outdir>/<outpfx>.results.txt`` per cohort; and `targetCohorts` and
-`geneCohorts`, the same for `targetDriver` and `geneDriver`.  The statistics
+`geneCohorts`, the same for `targetDriver` and `geneDriver`; and `elementCohorts`, the same for `elementDriver`, with q-values and,
+at a cut, only the hits (``<outdir>/<outpfx>.hits.txt``).  The statistics
 run through libdig_hip.so; `model` may be the reference's HDF5 map (`*.h5`, read by io/h5lite.py +
 io/pandas_fixed.py: no h5py or PyTables needed) or the directory mirror described in digdriver_amd/io/mapfile.py.
 """
@@ -131,6 +132,49 @@ def cmd_quick_cohorts(args):
         skip_pvals=args.skip_pvals)
     for path in paths:
         print('\tSaved results to {}'.format(path))
+
+
+def cmd_element_cohorts(args):
+    """elementCohorts: elementDriver for many cohorts on one bin grid in one pass.  Without a cut, per cohort
+    <outdir>/<outpfx>.results.txt (--qvalues: with the QVAL_* columns behind the others); with --fdr or --pval-max (on --cut-on,
+    default PVAL_SNV_BURDEN) only the elements that pass, as <outdir>/<outpfx>.hits.txt, QVAL_* columns included."""
+    n = len(args.mutation_files)
+    if not len(args.maps) == len(args.outpfx) == n:
+        raise SystemExit("ERROR: --mutation-files, --maps and --outpfx must name the same number of cohorts.")
+    factors = None
+    if args.scale_factor_manual or args.scale_factor_indel_manual:
+        if not (args.scale_factor_manual and args.scale_factor_indel_manual):
+            raise SystemExit("ERROR: must specify both --scale-factor-manual and --scale-factor-indel-manual.")
+        if not len(args.scale_factor_manual) == len(args.scale_factor_indel_manual) == n:
+            raise SystemExit("ERROR: --scale-factor-manual and --scale-factor-indel-manual take one value per cohort.")
+        factors = (args.scale_factor_manual, args.scale_factor_indel_manual)
+    if args.fdr is not None and args.pval_max is not None:
+        raise SystemExit("ERROR: you must provide at most one of --pval-max and --fdr.")
+    cut = args.fdr if args.fdr is not None else args.pval_max
+    if cut is None and args.cut_on is not None:
+        raise SystemExit("ERROR: --cut-on needs --fdr or --pval-max.")
+    if cut is not None and not 0.0 < cut <= 1.0:
+        raise SystemExit("ERROR: --fdr and --pval-max take a level within (0, 1].")
+    from digdriver_amd.driver_model import cohort_batch
+    print('Running user-defined element driver detection for {} cohorts'.format(n))
+    common = dict(scale_factors=factors, max_muts_per_sample=args.max_muts_per_sample,
+                  max_muts_per_elt_per_sample=args.max_muts_per_elt_per_sample)
+    if cut is None:
+        _, paths = cohort_batch.run_and_write_element_cohorts(args.mutation_files, args.maps, args.f_element_data, args.save_key,
+                                                              args.outdir, args.outpfx, qvalues=args.qvalues, **common)
+        for path in paths:
+            print('\tSaved results to {}'.format(path))
+        return
+    try:
+        frames, paths = cohort_batch.run_and_write_element_calls(
+            args.mutation_files, args.maps, args.f_element_data, args.save_key, args.outdir, args.outpfx, pval_max=args.pval_max,
+            fdr=args.fdr, cut_on=args.cut_on or 'PVAL_SNV_BURDEN', **common)
+    except ValueError as exc:
+        if 'no indel columns' not in str(exc):
+            raise
+        raise SystemExit("ERROR: {}".format(exc))
+    for pfx, frame, path in zip(args.outpfx, frames, paths):
+        print('\t{}: {} hits of {} testable elements; saved to {}'.format(pfx, len(frame), frame.attrs['n_testable'], path))
 
 
 def _cohort_lists(args):
@@ -397,6 +441,27 @@ def parse_args(text=None):
     q.add_argument('--skip_pvals', default=False, action='store_true', help='expected counts only')
     q.add_argument('--panel-dir', type=str, default=None, help='directory holding the gene panel files genes_<NAME>.txt')
     q.set_defaults(func=cmd_quick_cohorts)
+
+    # not a reference sub-command: elementDriver for many cohorts at once, with q-values and calls (driver_model/cohort_batch.py
+    # run_element_cohorts / run_element_calls)
+    ec = sub.add_parser('elementCohorts', help='elementDriver for many cohorts on one bin grid: results, or only the elements that pass a cut')
+    ec.add_argument('f_element_data', type=str, help='element data container (DigPreprocess.py)')
+    ec.add_argument('save_key', type=str, help='key of the element set inside the container')
+    ec.add_argument('--mutation-files', type=str, nargs='+', required=True, help='one annotated mutation file per cohort')
+    ec.add_argument('--maps', type=str, nargs='+', required=True, help='one pretrained mutation map per cohort, all on one bin grid')
+    ec.add_argument('--outdir', type=str, required=True, help='directory for the results or hit files')
+    ec.add_argument('--outpfx', type=str, nargs='+', required=True, help='one prefix per cohort: <outpfx>.results.txt or <outpfx>.hits.txt')
+    ec.add_argument('--max-muts-per-sample', type=int, default=3e9, help='drop samples with more mutations in elements than this')
+    ec.add_argument('--max-muts-per-elt-per-sample', type=int, default=3e9, help='cap of mutations one sample adds to an element')
+    ec.add_argument('--scale-factor-manual', default=None, type=float, nargs='+', help='use these SNV scale factors, one per cohort')
+    ec.add_argument('--scale-factor-indel-manual', default=None, type=float, nargs='+', help='use these indel scale factors, one per cohort')
+    ec.add_argument('--qvalues', action='store_true', default=False,
+                    help="add a Benjamini-Hochberg QVAL_* column per PVAL_* column, over the cohort's testable elements")
+    ec.add_argument('--fdr', type=float, default=None, help='write only the elements with q <= this, as <outpfx>.hits.txt')
+    ec.add_argument('--pval-max', type=float, default=None, help='write only the elements with p <= this, as <outpfx>.hits.txt')
+    ec.add_argument('--cut-on', default=None, choices=['PVAL_SNV_BURDEN', 'PVAL_SAMPLE_BURDEN', 'PVAL_INDEL_BURDEN', 'PVAL_MUT_BURDEN'],
+                    help='the column --fdr / --pval-max select on (default PVAL_SNV_BURDEN)')
+    ec.set_defaults(func=cmd_element_cohorts)
 
     def cohort_lists(p):
         p.add_argument('--mutation-files', type=str, nargs='+', required=True, help='one annotated mutation file per cohort')

@@ -2,6 +2,7 @@
 """End-to-end wall-clock of the drop-in on BASELINE configs[2] WRITTEN AS FILES.
 
     python tools/e2e_bench.py [--bins 288000 --elements 120091 --cohorts 37 --mut-rows 300000] [--workdir DIR] [--json OUT]
+                              [--calls FDR] [--reps N]
 
 Inputs (synthetic, seeded; written once, untimed): C pretrained maps as real HDF5 files (region_params and
 sequence_model_192 as pandas 'fixed' frames, idx, attributes -- io/h5lite.py), one element-data container (window context
@@ -11,7 +12,9 @@ one result frame per cohort) and cohort_batch.write_results (C x <prefix>.result
 seconds of every stage.  Then, for ONE cohort, the two command lines a user of the reference runs:
 `scripts/DigPretrain.py elementModel` + `scripts/DigDriver.py elementDriver` (two fresh processes, wall-clock).
 Beside it: the reference's own per-element loop rate measured in the build container (profiles/r04_reference_loop_rate.json;
-/root/reference does not exist on the GPU box)."""
+/root/reference does not exist on the GPU box).
+--calls FDR times the hits-only route instead: cohort_batch.run_and_write_element_calls at that FDR on PVAL_SNV_BURDEN (files ->
+C x <prefix>.hits.txt; no full frame is built), and nothing else."""
 import argparse
 import json
 import os
@@ -107,7 +110,7 @@ def write_inputs(args, work):
 
 
 def run_e2e(bins=288_000, elements=120_091, cohorts=37, mut_rows=300_000, seed=3, workdir="/tmp/dig_e2e", read_workers=None,
-            skip_cli=False, reps=5, keep=False):
+            skip_cli=False, reps=5, keep=False, calls=None):
     """Write the inputs (untimed), run the many-cohort pipeline `reps` times with stage timings, then the two per-cohort command
     lines once; returns the record tools/e2e_bench.py prints and bench.py embeds as `e2e`."""
     import shutil
@@ -136,20 +139,33 @@ def run_e2e(bins=288_000, elements=120_091, cohorts=37, mut_rows=300_000, seed=3
     for rep in range(reps):                               # the second run has the files in the page cache and the kernels loaded
         stages = {}
         t0 = time.perf_counter()
-        frames, out = cohort_batch.run_and_write_element_cohorts(paths["mut"], paths["pre"], paths["ed"], "elts", outdir,
-                                                                 ["cohort%02d" % c for c in range(cohorts)], timings=stages,
-                                                                 read_workers=read_workers)
+        if calls is not None:
+            frames, out = cohort_batch.run_and_write_element_calls(paths["mut"], paths["pre"], paths["ed"], "elts", outdir,
+                                                                   ["cohort%02d" % c for c in range(cohorts)], fdr=calls, timings=stages,
+                                                                   read_workers=read_workers)
+        else:
+            frames, out = cohort_batch.run_and_write_element_cohorts(paths["mut"], paths["pre"], paths["ed"], "elts", outdir,
+                                                                     ["cohort%02d" % c for c in range(cohorts)], timings=stages,
+                                                                     read_workers=read_workers)
         t2 = time.perf_counter()
         total = t2 - t0
         inside = stages.pop("inside_read_parse_upload", None)
-        stages["results_txt_behind_the_last_frame"] = total - sum(stages.values())
+        stages["hits_txt" if calls is not None else "results_txt_behind_the_last_frame"] = total - sum(stages.values())
         res["runs"].append({"total_s": total, "stages_s": {k: round(v, 4) for k, v in stages.items()},
                             "inside_read_parse_upload_s": inside,
                             "element_cohort_tests_per_s": elements * cohorts / total, "seconds_per_cohort": total / cohorts})
+        if calls is not None:
+            res["runs"][-1].update(hits=[len(f) for f in frames], n_testable=[f.attrs["n_testable"] for f in frames])
         del frames
     res["results_files"] = len(out)
     tot = sorted(r["total_s"] for r in res["runs"])
     res["total_s_median"] = tot[len(tot) // 2]
+    if calls is not None:
+        res["what"] = ("BASELINE configs[2] as FILES -> %d hits.txt at FDR %g on PVAL_SNV_BURDEN: driver_model.cohort_batch."
+                       "run_and_write_element_calls, wall-clock by stage; inputs written beforehand, untimed" % (cohorts, calls))
+        if not keep:
+            shutil.rmtree(workdir, ignore_errors=True)
+        return res
     # the overlapped route writes the bytes the plain route writes (run_element_cohorts, then write_results; untimed)
     serial_dir = os.path.join(workdir, "results_serial")
     frames = cohort_batch.run_element_cohorts(paths["mut"], paths["pre"], paths["ed"], "elts", read_workers=1)
@@ -201,9 +217,11 @@ def main():
     ap.add_argument("--read-workers", type=int, default=None)
     ap.add_argument("--skip-cli", action="store_true")
     ap.add_argument("--keep", action="store_true")
+    ap.add_argument("--calls", type=float, default=None, metavar="FDR", help="time files -> hits.txt at this FDR instead")
+    ap.add_argument("--reps", type=int, default=5, help="timed runs in this process")
     args = ap.parse_args()
     res = run_e2e(args.bins, args.elements, args.cohorts, args.mut_rows, args.seed, args.workdir, args.read_workers, args.skip_cli,
-                  keep=args.keep)
+                  reps=args.reps, keep=args.keep, calls=args.calls)
     txt = json.dumps(res, indent=1)
     print(txt)
     if args.json:
