@@ -115,6 +115,10 @@ _SIGNATURES = {
     "dig_row_select_fill_host": [_vp, _vp, _i64, _i64, _vp, _i64, _vp, _vp, _int],
     "dig_row_scatter": [_vp, _vp, _i64, _i64, _vp, _i64, _vp, ctypes.c_double, _vp, _vp],
     "dig_row_scatter_host": [_vp, _vp, _i64, _i64, _vp, _i64, _vp, ctypes.c_double, _vp, _int],
+    "dig_group_fisher": [_vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp],
+    "dig_group_fisher_host": [_vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _int],
+    "dig_group_sums": [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp],
+    "dig_group_sums_host": [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp, _int],
     "dig_tile_sample_keys": [_vp, _vp, _i64, _vp, _i64] + [_vp] * 5 + [_int] + [_i64] * 4 + [_vp, _vp],
     "dig_tile_sample_keys_host": [_vp, _vp, _i64, _vp, _i64] + [_vp] * 5 + [_int] + [_i64] * 4 + [_vp, _int],
     "dig_tile_sample_counts": [_vp] + [_i64] * 6 + [_vp, _vp, _vp],

@@ -679,6 +679,32 @@ int dig_row_scatter_host(const double* score, const double* cut, int64_t rows, i
                    st.in(values, (size_t)total), fill, st.out(out, (size_t)rows * n), nullptr);
 }
 
+int dig_group_fisher_host(const double* p, const uint8_t* member, int64_t R, int64_t C, int64_t E, int64_t M, double* out_p, int32_t* out_n,
+                          int device)
+{
+    int64_t chunks = 0;
+    if (int rc = group_sizes(__func__, R, C, E, M, &chunks)) return rc;
+    const size_t n_out = (size_t)R * M * E, n_in = (size_t)R * C * E;
+    if (n_out == 0) return DIG_OK;
+    DIG_REQUIRE(out_p && (C == 0 || (p && member)), "non-null p, member, out_p");
+    Staging st(device);
+    return st.call(dig_group_fisher, st.in(p, n_in), st.in(member, (size_t)M * C), R, C, E, M, st.out(out_p, n_out),
+                   out_n ? st.out(out_n, n_out) : nullptr, nullptr);
+}
+
+int dig_group_sums_host(const double* x, const double* gate, const uint8_t* member, int64_t R, int64_t C, int64_t E, int64_t M, double* out,
+                        int device)
+{
+    int64_t chunks = 0;
+    if (int rc = group_sizes(__func__, R, C, E, M, &chunks)) return rc;
+    const size_t n_out = (size_t)R * M * E, n_in = (size_t)R * C * E;
+    if (n_out == 0) return DIG_OK;
+    DIG_REQUIRE(out && (C == 0 || (x && member)), "non-null x, member, out");
+    Staging st(device);
+    return st.call(dig_group_sums, st.in(x, n_in), st.in(gate, n_in), st.in(member, (size_t)M * C), R, C, E, M, st.out(out, n_out),
+                   nullptr);
+}
+
 int dig_scale_suffstats_host(const double* bin_mu, const uint8_t* bin_flag, int64_t N, int64_t C, double* out_sum, int device)
 {
     DIG_REQUIRE(N >= 0 && C >= 0, "N, C >= 0");

@@ -42,6 +42,11 @@ int tile_select_sizes(const char* fn, int64_t C, int64_t R, int64_t T);
 constexpr int kRowSelectChunk = 2048;
 int row_select_sizes(const char* fn, int64_t rows, int64_t n, int64_t* chunks);
 
+// dig_groupfisher.hip: the size checks of dig_group_fisher / dig_group_sums over planes [R, C, E] and M groups, and the chunks (one
+// per workgroup) of a row; DIG_EINVAL (in the name of entry point `fn`) unless R, C, E, M >= 0, C <= 64, M <= 32, E < 2^31 and
+// R * chunks < 2^31
+int group_sizes(const char* fn, int64_t R, int64_t C, int64_t E, int64_t M, int64_t* chunks);
+
 // dig_tilewindows.hip: tile_select_sizes and 1 <= width <= DIG_TILE_WINDOW_MAX_WIDTH, for dig_tile_window_test and its host twin
 int tile_window_sizes(const char* fn, int64_t C, int64_t R, int64_t T, int32_t width);
 

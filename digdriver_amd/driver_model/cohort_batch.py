@@ -306,7 +306,7 @@ def plane_qvalues(p):
 
 def run_element_cohorts(f_muts, f_pretrained, f_element_data, save_key, scale_factors=None, max_muts_per_sample=3e9,
                         max_muts_per_elt_per_sample=3e9, device=0, timings=None, read_workers=None, on_frame=None,
-                        output_form="records", qvalues=False):
+                        output_form="records", qvalues=False, element_pass=None):
     """One result frame per cohort (index ELT, the columns of run_element_region_model) for the mutation files
     `f_muts[c]` against the pretrained maps `f_pretrained[c]` (one bin grid) and the element set `save_key` of
     `f_element_data`.  scale_factors: (cj [C], cj_indel [C]) or None for the genome mode.
@@ -317,9 +317,11 @@ def run_element_cohorts(f_muts, f_pretrained, f_element_data, save_key, scale_fa
     are written while the next frames are assembled).
     output_form: "records" (default) or "planes" -- the layout the statistics stage writes on the device (same frames).
     qvalues: behind the columns of the frame, QVAL_SNV_BURDEN, QVAL_SAMPLE_BURDEN and, where the cohort has indel columns,
-    QVAL_INDEL_BURDEN, QVAL_MUT_BURDEN: Benjamini-Hochberg over the column's non-NaN p-values (plane_qvalues; NaN where PVAL is)."""
-    planes, names, st_ = _element_pass(f_muts, f_pretrained, f_element_data, save_key, scale_factors, max_muts_per_sample,
-                                       max_muts_per_elt_per_sample, device, timings, read_workers, output_form)
+    QVAL_INDEL_BURDEN, QVAL_MUT_BURDEN: Benjamini-Hochberg over the column's non-NaN p-values (plane_qvalues; NaN where PVAL is).
+    element_pass: what _element_pass returned for the same inputs, for a caller that runs several routes behind ONE pass (the
+    command line with --groups); the inputs are then not read again."""
+    planes, names, st_ = element_pass or _element_pass(f_muts, f_pretrained, f_element_data, save_key, scale_factors, max_muts_per_sample,
+                                                       max_muts_per_elt_per_sample, device, timings, read_workers, output_form)
     D = planes()
     if qvalues:
         Q = plane_qvalues(D['S'][list(_PVAL_PLANES.values())]).cpu().numpy()             # [4, C, E]
@@ -339,7 +341,7 @@ def run_element_cohorts(f_muts, f_pretrained, f_element_data, save_key, scale_fa
 
 def run_element_calls(f_muts, f_pretrained, f_element_data, save_key, pval_max=None, fdr=None, cut_on='PVAL_SNV_BURDEN',
                       scale_factors=None, max_muts_per_sample=3e9, max_muts_per_elt_per_sample=3e9, device=0, timings=None,
-                      read_workers=None, output_form="records"):
+                      read_workers=None, output_form="records", element_pass=None):
     """The rows of run_element_cohorts(..., qvalues=True)'s frames that pass a cut, without the frames being built: frame c equals
     that frame restricted to the rows with `cut_on` <= pval_max, or with the q-value of `cut_on` <= fdr -- the same columns, dtypes,
     row order and bits.  Exactly one of pval_max / fdr; cut_on: one of the four PVAL_*_BURDEN columns (an indel column that a cohort
@@ -352,8 +354,8 @@ def run_element_calls(f_muts, f_pretrained, f_element_data, save_key, pval_max=N
     if cut_on not in _PVAL_PLANES:
         raise ValueError("cut_on: one of %s" % ", ".join(_PVAL_PLANES))
     import torch
-    planes, names, st_ = _element_pass(f_muts, f_pretrained, f_element_data, save_key, scale_factors, max_muts_per_sample,
-                                       max_muts_per_elt_per_sample, device, timings, read_workers, output_form)
+    planes, names, st_ = element_pass or _element_pass(f_muts, f_pretrained, f_element_data, save_key, scale_factors, max_muts_per_sample,
+                                                       max_muts_per_elt_per_sample, device, timings, read_workers, output_form)
     D = planes()
     C, E = D['MU'].shape
     have_indel = (D['OBS_INDEL'].sum(dim=1) != 0).cpu().numpy()
@@ -396,6 +398,203 @@ def run_and_write_element_calls(f_muts, f_pretrained, f_element_data, save_key, 
     assert len(prefixes) == len(frames)
     os.makedirs(outdir, exist_ok=True)
     paths = [os.path.join(outdir, pfx + '.hits.txt') for pfx in prefixes]
+    cores = os.cpu_count() or 1
+    threads = int(write_threads) if write_threads else max(1, min(8, cores // max(len(frames), 1)))
+    with ThreadPoolExecutor(max_workers=max(1, min(len(frames), cores))) as pool:
+        list(pool.map(lambda job: _write_one(job[0], job[1], threads), zip(frames, paths)))
+    return frames, paths
+
+
+# ---------------------------------------------------------------------------------------------
+# meta-cohorts of the element route: groups of cohorts combined per element
+# ---------------------------------------------------------------------------------------------
+def _meta_groups(groups, labels, C):
+    """The groups of run_element_meta checked before any file is read: (names, the members of every group as ascending cohort
+    indices, labels as a list of str or None).  groups: an ordered dict group name -> list of cohort indices, or of labels from
+    `labels` (one per cohort).  ValueError for no group, an empty group, an index outside [0, C), an unknown label or a repeated
+    member."""
+    if labels is not None:
+        labels = [str(v) for v in labels]
+        if len(labels) != C or len(set(labels)) != C:
+            raise ValueError("labels: one label per cohort (%d), each once" % C)
+    if not groups:
+        raise ValueError("groups: at least one group")
+    names, members = [], []
+    for name, listed in groups.items():
+        listed = list(listed)
+        if not listed:
+            raise ValueError("group %r is empty" % (name,))
+        idx = []
+        for v in listed:
+            if isinstance(v, (int, np.integer)) and not isinstance(v, bool):
+                if not 0 <= v < C:
+                    raise ValueError("group %r: cohort index %d outside [0, %d)" % (name, v, C))
+                idx.append(int(v))
+            elif labels is None or str(v) not in labels:
+                raise ValueError("group %r: unknown cohort label %r" % (name, v))
+            else:
+                idx.append(labels.index(str(v)))
+        if len(set(idx)) != len(idx):
+            raise ValueError("group %r names a cohort more than once" % (name,))
+        names.append(str(name))
+        members.append(sorted(idx))
+    return names, members, labels
+
+
+_N_TESTED_COLUMNS = ['N_TESTED_' + k[5:] for k in _PVAL_PLANES]
+
+
+def _meta_planes(D, members, best_on):
+    """The device half of the meta routes from the planes of _element_pass: dict(P f64 [4, M, E] the combined _PVAL_PLANES, N i32
+    [4, M, E] the members that tested, OBS f64 [3, M, E] the sums of OBS_SAMPLES, OBS_SNV, OBS_INDEL, EXP f64 [2, M, E] those of EXP_SNV
+    and EXP_INDEL over the members that tested the SNV / the indel burden, BEST i64 [M, E] the member with the smallest p-value of
+    plane `best_on` (ties: the lowest cohort; -1 where none tested), have_indel bool [C] on the host).  The indel and mut planes of a
+    cohort without indel columns (the test of run_element_calls) count as not tested."""
+    import torch
+    S = D['S']
+    C, E = D['MU'].shape
+    have_indel = D['OBS_INDEL'].sum(dim=1) != 0
+    P = S[list(_PVAL_PLANES.values())].clone()                                        # [4, C, E]
+    P[2:, ~have_indel] = float("nan")
+    member = torch.zeros((len(members), C), dtype=torch.uint8, device=S.device)
+    for g, idx in enumerate(members):
+        member[g, idx] = 1
+    gf = engine.group_fisher(P, member)
+    obs = engine.group_sums(torch.stack([D['OBS_SAMPLES'], D['OBS_SNV'], D['OBS_INDEL']]).double(), member)
+    exp = engine.group_sums(torch.stack([S[0], S[4]]), member, gate=torch.stack([P[0], P[2]]))
+    # one masked argmin per group, over its member rows only (the first of equal minima: the lowest cohort)
+    best = []
+    for g, idx in enumerate(members):
+        at = torch.as_tensor(idx, device=S.device)
+        rows = P[best_on][at]                                                         # [members, E]
+        first = torch.where(rows.isnan(), float("inf"), rows).argmin(dim=0)
+        best.append(torch.where(gf["n_used"][best_on, g] > 0, at[first], -1))
+    return dict(P=gf["pval"], N=gf["n_used"], OBS=obs, EXP=exp, BEST=torch.stack(best), have_indel=have_indel.cpu().numpy())
+
+
+def _meta_columns(x, n_members, have_indel, q, labels):
+    """The columns of one group's frame, in the frame's order, from host arrays: x maps ELT_SIZE [rows], OBS [3, rows], EXP [2, rows],
+    P [4, rows], N [4, rows], BEST [rows] of _meta_planes to the group's rows -- every element for run_element_meta, the hits for
+    run_element_meta_calls --, have_indel whether a member of the group has indel columns, q [4, rows] or None the q-values."""
+    n_p = 4 if have_indel else 2
+    d = {'ELT_SIZE': x['ELT_SIZE'], 'N_COHORTS': np.full(len(x['ELT_SIZE']), n_members, np.int64),
+         'OBS_SAMPLES': x['OBS'][0], 'OBS_SNV': x['OBS'][1], 'OBS_INDEL': x['OBS'][2], 'EXP_SNV': x['EXP'][0]}
+    if have_indel:
+        d['EXP_INDEL'] = x['EXP'][1]
+    d.update({k: x['P'][i] for i, k in enumerate(list(_PVAL_PLANES)[:n_p])})
+    d.update({k: x['N'][i].astype(np.int64) for i, k in enumerate(_N_TESTED_COLUMNS[:n_p])})
+    if q is not None:
+        d.update({k: q[i] for i, k in enumerate(_QVAL_COLUMNS[:n_p])})
+    best = x['BEST'].astype(np.int64)
+    d['BEST_COHORT'] = best if labels is None else np.array(labels + [''], dtype=object)[best]
+    return d
+
+
+def _best_on(name, what):
+    if name not in _PVAL_PLANES:
+        raise ValueError("%s: one of %s" % (what, ", ".join(_PVAL_PLANES)))
+    return list(_PVAL_PLANES).index(name)
+
+
+def run_element_meta(f_muts, f_pretrained, f_element_data, save_key, groups, labels=None, qvalues=True, best_on='PVAL_SNV_BURDEN',
+                     scale_factors=None, max_muts_per_sample=3e9, max_muts_per_elt_per_sample=3e9, device=0, timings=None,
+                     read_workers=None, output_form="records", element_pass=None):
+    """One frame per GROUP of cohorts (index ELT) from one pass of the element route over all cohorts: the cohorts' p-values combined
+    per element by Fisher's method over the members that tested it (engine.group_fisher: chi2.sf(-2 sum ln p_c, 2 m); a NaN p did not
+    test), and the counts summed (engine.group_sums).  groups: an ordered dict group name -> list of cohort indices, or of labels from
+    `labels` (one per cohort); a cohort may be in many groups.  An unknown label, an empty list or a repeated member is a ValueError
+    raised before any file is read.  Columns: ELT_SIZE, N_COHORTS (the members), OBS_SAMPLES, OBS_SNV, OBS_INDEL (sums over the
+    members), EXP_SNV, EXP_INDEL (sums over the members that tested the SNV / the indel burden), the four PVAL_*_BURDEN combined, the
+    four N_TESTED_*_BURDEN (the members behind each), with qvalues the four QVAL_*_BURDEN (Benjamini-Hochberg over the group's testable
+    elements, plane_qvalues), and BEST_COHORT: the label (without labels: the index) of the member with the smallest p-value of
+    `best_on`, ties to the lowest cohort index, '' (-1) where none tested.  The indel and mut planes of a cohort without indel columns
+    count as not tested; a group in which no member has indel columns leaves out EXP_INDEL and its indel and mut columns, as a cohort's
+    frame does.  The other options as run_element_cohorts takes them."""
+    names_g, members, labels = _meta_groups(groups, labels, len(f_muts))
+    j = _best_on(best_on, "best_on")
+    planes, names, st_ = element_pass or _element_pass(f_muts, f_pretrained, f_element_data, save_key, scale_factors, max_muts_per_sample,
+                                                       max_muts_per_elt_per_sample, device, timings, read_workers, output_form)
+    D = planes()
+    T = _meta_planes(D, members, j)
+    have_indel = T.pop('have_indel')
+    Q = plane_qvalues(T['P']).cpu().numpy() if qvalues else None
+    st_.mark("meta")
+    X = {k: v.cpu().numpy() for k, v in T.items()}
+    elt_size = D['ELT_SIZE'].cpu().numpy()
+    st_.mark("d2h")
+    frames = []
+    index = pd.Index(names, name='ELT')
+    for g, idx in enumerate(members):
+        x = dict({k: v[:, g] for k, v in X.items() if k != 'BEST'}, BEST=X['BEST'][g], ELT_SIZE=elt_size)
+        d = _meta_columns(x, len(idx), bool(have_indel[idx].any()), Q[:, g] if qvalues else None, labels)
+        frames.append(pd.DataFrame(d, index=index))
+        frames[-1].attrs['group'] = names_g[g]
+    st_.mark("frames")
+    return frames
+
+
+def run_element_meta_calls(f_muts, f_pretrained, f_element_data, save_key, groups, labels=None, pval_max=None, fdr=None,
+                           cut_on='PVAL_SNV_BURDEN', scale_factors=None, max_muts_per_sample=3e9, max_muts_per_elt_per_sample=3e9,
+                           device=0, timings=None, read_workers=None, output_form="records", element_pass=None):
+    """The rows of run_element_meta(..., qvalues=True, best_on=cut_on)'s frames that pass a cut, without the frames being built: frame
+    g equals that frame restricted to the rows with the group's combined `cut_on` <= pval_max, or with its q-value <= fdr -- the same
+    columns, dtypes, row order and bits.  Exactly one of pval_max / fdr; an indel column that a group lacks is a ValueError.  The
+    selection is run_element_calls' over the groups' combined planes (nb_model.bh_cut, engine.row_select at p*, a gather at (group,
+    element)); only the hits cross to the host.  frame.attrs['n_testable']: the non-NaN values of cut_on in the group."""
+    if (pval_max is None) == (fdr is None):
+        raise ValueError("exactly one of pval_max and fdr must be given")
+    j = _best_on(cut_on, "cut_on")
+    names_g, members, labels = _meta_groups(groups, labels, len(f_muts))
+    import torch
+    planes, names, st_ = element_pass or _element_pass(f_muts, f_pretrained, f_element_data, save_key, scale_factors, max_muts_per_sample,
+                                                       max_muts_per_elt_per_sample, device, timings, read_workers, output_form)
+    D = planes()
+    T = _meta_planes(D, members, j)
+    have_indel = np.array([bool(T['have_indel'][idx].any()) for idx in members])
+    del T['have_indel']
+    if j >= 2 and not have_indel.all():
+        raise ValueError("cut_on = %s: groups %s have no indel columns" % (cut_on, [n for n, h in zip(names_g, have_indel) if not h]))
+    M, E = T['BEST'].shape
+    pvals = T['P'].reshape(4 * M, E)                                                  # row k M + g: PVAL column k of group g
+    lists, q_lists = _ragged_qvalues(pvals)
+    Q = engine.row_scatter(pvals, float("inf"), q_lists, float("nan")).reshape(4, M, E)
+    ptr = lists["row_ptr"][j * M:(j + 1) * M + 1]
+    if fdr is not None:
+        cuts = np.array([nb_model.bh_cut(lists["score"][ptr[g]:ptr[g + 1]], q_lists[ptr[g]:ptr[g + 1]], fdr) for g in range(M)])
+    else:
+        cuts = np.full(M, float(pval_max))
+    hits = engine.row_select(pvals[j * M:(j + 1) * M], cuts)
+    hit_ptr, elt = hits["row_ptr"], hits["index"].long()
+    st_.mark("meta_select")
+    group = torch.as_tensor(np.repeat(np.arange(M), np.diff(hit_ptr)), device=elt.device)
+    X = {k: (v[group, elt] if v.dim() == 2 else v[:, group, elt]).cpu().numpy() for k, v in T.items()}
+    X['ELT_SIZE'] = D['ELT_SIZE'][elt].cpu().numpy()
+    q_hits, elt = Q[:, group, elt].cpu().numpy(), elt.cpu().numpy()
+    st_.mark("d2h")
+    frames = []
+    index = pd.Index(names, name='ELT')
+    for g, idx in enumerate(members):
+        lo, hi = int(hit_ptr[g]), int(hit_ptr[g + 1])
+        d = _meta_columns({k: v[..., lo:hi] for k, v in X.items()}, len(idx), have_indel[g], q_hits[:, lo:hi], labels)
+        frames.append(pd.DataFrame(d, index=index[elt[lo:hi]]))
+        frames[-1].attrs.update(group=names_g[g], n_testable=int(ptr[g + 1] - ptr[g]))
+    st_.mark("frames")
+    return frames
+
+
+def run_and_write_element_meta(f_muts, f_pretrained, f_element_data, save_key, groups, outdir, labels=None, write_threads=None, **kw):
+    """run_element_meta -- with pval_max or fdr among the keywords run_element_meta_calls -- with group g's frame written to
+    <outdir>/<group>.meta.results.txt (<group>.meta.hits.txt under a cut) as the cohorts' files are written (_write_one).  Returns
+    (frames, paths)."""
+    import os
+    from concurrent.futures import ThreadPoolExecutor
+    cut = kw.get('pval_max') is not None or kw.get('fdr') is not None
+    run = run_element_meta_calls if cut else run_element_meta
+    if not cut:
+        kw = {k: v for k, v in kw.items() if k not in ('pval_max', 'fdr', 'cut_on')}
+    frames = run(f_muts, f_pretrained, f_element_data, save_key, groups, labels=labels, **kw)
+    os.makedirs(outdir, exist_ok=True)
+    paths = [os.path.join(outdir, f.attrs['group'] + ('.meta.hits.txt' if cut else '.meta.results.txt')) for f in frames]
     cores = os.cpu_count() or 1
     threads = int(write_threads) if write_threads else max(1, min(8, cores // max(len(frames), 1)))
     with ThreadPoolExecutor(max_workers=max(1, min(len(frames), cores))) as pool:

@@ -1553,6 +1553,71 @@ def row_scatter(score, cut, values, fill=float("nan"), device=0):
     return out
 
 
+GROUPS_PER_LAUNCH = 32                                   # include/dig_hip.h: M <= 32 per call of dig_group_fisher / dig_group_sums
+
+
+def _group_planes(be, x, member, what):
+    """(x f64 [R, C, E] -- a [C, E] plane is R = 1 --, member u8 [M, C] as 0 / 1, whether x came as 2-D, R, C, E, M)."""
+    x = be.arr(x, "f64")
+    if x.ndim not in (2, 3):
+        raise ValueError("%s must be [C, E] or [R, C, E]" % what)
+    flat = x.ndim == 2
+    if flat:
+        x = x.reshape((1,) + tuple(x.shape))
+    R, C, E = (int(s) for s in x.shape)
+    member = be.arr(member)
+    if member.ndim != 2 or int(member.shape[1]) != C:
+        raise ValueError("member must be [M, C] with C = %d cohorts, not %s" % (C, tuple(member.shape)))
+    member = be.arr(member != 0, "u8")
+    return x, member, flat, R, C, E, int(member.shape[0])
+
+
+def _group_launches(be, M, R, E, flat, dtypes, call):
+    """The outputs [R, M, E] of `dtypes`, filled by call(first group, groups, the outputs' slices) per slice of GROUPS_PER_LAUNCH groups
+    (a slice of the groups is written into an array of its own and copied in: the entry point's output is [R, groups, E])."""
+    outs = [be.empty((R, M, E), d) for d in dtypes]
+    with _requirements_as_value_errors():
+        for g0 in range(0, max(M, 1), GROUPS_PER_LAUNCH):
+            n = min(GROUPS_PER_LAUNCH, M - g0)
+            part = outs if n == M else [be.empty((R, n, E), d) for d in dtypes]
+            call(g0, n, part)
+            if part is not outs:
+                for o, q in zip(outs, part):
+                    o[:, g0:g0 + n] = q
+    return [o.reshape(M, E) if flat else o for o in outs]
+
+
+def group_fisher(p, member, device=0, counts=True):
+    """Fisher's method over groups of cohorts, per element (dig_group_fisher): p f64 [R, C, E] or [C, E] (R stacked p-value columns, C
+    <= 64 cohorts, E elements), member [M, C] (non-zero: cohort c belongs to group g).  A NaN p is not testable: it adds nothing and is
+    not counted.  Returns dict(pval f64 [R, M, E], n_used i32 [R, M, E] (None with counts=False)) -- [M, E] for a 2-D p: with m = n_used
+    the testable members, pval is NaN for m = 0, the member's p for m = 1, fisher_combine of the pair for m = 2 and
+    chi2.sf(-2 sum ln p, 2 m) for m >= 3.  More than 32 groups run as several launches.  CUDA tensors in -> CUDA tensors out."""
+    be = backend_of(p, member, device=device)
+    p, member, flat, R, C, E, M = _group_planes(be, p, member, "p")
+
+    def call(g0, n, part):
+        be.call("dig_group_fisher", be.ptr(p), be.ptr(member[g0:g0 + n]), R, C, E, n, be.ptr(part[0]), be.ptr(part[1]) if counts else None)
+    pval, n_used = _group_launches(be, M, R, E, flat, ("f64", "i32") if counts else ("f64",), call) + ([] if counts else [None])
+    return dict(pval=pval, n_used=n_used)
+
+
+def group_sums(x, member, gate=None, device=0):
+    """The sums of x f64 [R, C, E] (or [C, E]) over the members of every group, in ascending cohort order, one addition per member
+    (dig_group_sums): f64 [R, M, E] ([M, E]).  gate f64 of x's shape: only the members whose gate is not NaN are added.  A group with
+    nothing to add gives 0.0.  More than 32 groups run as several launches.  CUDA tensors in -> CUDA tensors out."""
+    be = backend_of(x, member, gate, device=device)
+    x, member, flat, R, C, E, M = _group_planes(be, x, member, "x")
+    if gate is not None:
+        gate = be.arr(gate, "f64")
+        if tuple(gate.shape) != ((C, E) if flat else (R, C, E)):
+            raise ValueError("gate must have the shape of x")
+
+    def call(g0, n, part):
+        be.call("dig_group_sums", be.ptr(x), be.ptr(gate), be.ptr(member[g0:g0 + n]), R, C, E, n, be.ptr(part[0]))
+    return _group_launches(be, M, R, E, flat, ("f64",), call)[0]
+
+
 # ---------------------------------------------------------------------------
 # scale factors in canonical chunks: identical bits for any sharding of the bins (dig_scale_suffstats_chunked)
 # ---------------------------------------------------------------------------

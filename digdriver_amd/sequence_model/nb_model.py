@@ -77,6 +77,21 @@ def fisher_combine(p1, p2, device=0):
     return _elementwise("dig_fisher", (p1, p2), 1, device)[0]
 
 
+def fisher_combine_groups(p, member, device=0):
+    """Fisher's method over groups of the rows of p: p [C, E] (or [R, C, E]; a DataFrame's rows are the cohorts), member [M, C] with
+    non-zero where row c belongs to group g.  chi2.sf(-2 sum ln p_c, 2 m) over the m members whose p is a number: NaN for m = 0, the
+    member's own p for m = 1, fisher_combine of the pair for m = 2 (engine.group_fisher).  f64 [M, E] ([R, M, E]); device tensors in ->
+    device tensors out, a DataFrame in -> a DataFrame with its columns."""
+    from .. import engine
+    is_frame = lambda v: type(v).__name__ == "DataFrame"
+    got = engine.group_fisher(p.values if is_frame(p) else p, member.values if is_frame(member) else member, device=device,
+                              counts=False)["pval"]
+    if is_frame(p):
+        import pandas as pd
+        return pd.DataFrame(got, columns=p.columns, index=member.index if is_frame(member) else None)
+    return got
+
+
 # ---------------------------------------------------------------------------------------------
 # per-base / tiled route (nb_model.py:126-234, 340-342)
 # ---------------------------------------------------------------------------------------------

@@ -558,6 +558,32 @@ int dig_row_scatter(const double *score, const double *cut, int64_t rows, int64_
 int dig_row_scatter_host(const double *score, const double *cut, int64_t rows, int64_t n, const int64_t *offsets, int64_t total,
                          const double *values, double fill, double *out, int device);
 
+/* ---- the meta-cohorts of the element route: groups of cohorts combined per element (additive: the ABI version stays) -- *
+ * Planes are f64 [R, C, E] (R stacked columns, C cohorts, E elements, E contiguous); member u8 [M, C]: non-zero where cohort c
+ * belongs to group g (a cohort may be in many groups, or in none); outputs are [R, M, E].  R, C, E, M >= 0, C <= 64, M <= 32 per
+ * call, E < 2^31 and R * ceil(E / 128) < 2^31 (DIG_EINVAL otherwise, before anything is read).  Every typed pointer needs the
+ * alignment of its element and no more (16-byte loads and stores are used where an address allows them).
+ *   dig_group_fisher: Fisher's method over the TESTABLE members of a group, chi2.sf(-2 sum ln p_c, 2 m).  A member whose p is NaN
+ *     is not testable: it adds nothing and is not counted.  With s = the sum of -ln p over the testable members in ascending c and
+ *     m their number, out_n i32 [R, M, E] = m (out_n may be NULL) and out_p =
+ *       m = 0 (an empty group included)   NaN
+ *       m = 1                             that member's p, bit for bit
+ *       m = 2                             what dig_fisher gives for the pair (p_a, p_b), a < b, bit for bit
+ *       m >= 3                            Q(m, s) = e^-s sum_{j<m} s^j / j! as exp(log(r) - s), r = 1 + s/1 (1 + s/2 (... (1 + s/(m-1))))
+ *                                         by Horner; s < 0 (a p above 1) -> 1.0, s = +inf (a p of 0) -> 0.0, a NaN s -> NaN
+ *   dig_group_sums: out[r, g, e] = the sum of x[r, c, e] over the members c of g in ascending c, one IEEE addition each, from +0.0;
+ *     with a gate f64 [R, C, E] (NULL: none) only over the members whose gate[r, c, e] is not NaN.  Nothing to add: 0.0.
+ * Every p (x, gate) is read once per call and every output written once, by its owner: no atomics, outputs need not be zeroed.
+ * Nothing is launched when R M E = 0. */
+int dig_group_fisher(const double *p, const uint8_t *member, int64_t R, int64_t C, int64_t E, int64_t M, double *out_p, int32_t *out_n,
+                     void *stream);
+int dig_group_fisher_host(const double *p, const uint8_t *member, int64_t R, int64_t C, int64_t E, int64_t M, double *out_p,
+                          int32_t *out_n, int device);
+int dig_group_sums(const double *x, const double *gate, const uint8_t *member, int64_t R, int64_t C, int64_t E, int64_t M, double *out,
+                   void *stream);
+int dig_group_sums_host(const double *x, const double *gate, const uint8_t *member, int64_t R, int64_t C, int64_t E, int64_t M,
+                        double *out, int device);
+
 /* ---- the per-base route's counts by sample for many cohorts (additive: the ABI version stays) ------------------- *
  * dig_tile_mut_counts counts rows, whoever they belong to.  These two entry points count them per sample: with n(c, r, t, s) the
  * rows of GLOBAL sample s that dig_tile_mut_counts would count in tile (c, r, t) -- the same pairs, the same skip rules --

@@ -137,7 +137,9 @@ def cmd_quick_cohorts(args):
 def cmd_element_cohorts(args):
     """elementCohorts: elementDriver for many cohorts on one bin grid in one pass.  Without a cut, per cohort
     <outdir>/<outpfx>.results.txt (--qvalues: with the QVAL_* columns behind the others); with --fdr or --pval-max (on --cut-on,
-    default PVAL_SNV_BURDEN) only the elements that pass, as <outdir>/<outpfx>.hits.txt, QVAL_* columns included."""
+    default PVAL_SNV_BURDEN) only the elements that pass, as <outdir>/<outpfx>.hits.txt, QVAL_* columns included.  With --groups FILE
+    also per group of cohorts <outdir>/<group>.meta.results.txt, or under the cut <outdir>/<group>.meta.hits.txt: the members'
+    p-values combined per element by Fisher's method (cohort_batch.run_element_meta / run_element_meta_calls)."""
     n = len(args.mutation_files)
     if not len(args.maps) == len(args.outpfx) == n:
         raise SystemExit("ERROR: --mutation-files, --maps and --outpfx must name the same number of cohorts.")
@@ -155,15 +157,34 @@ def cmd_element_cohorts(args):
         raise SystemExit("ERROR: --cut-on needs --fdr or --pval-max.")
     if cut is not None and not 0.0 < cut <= 1.0:
         raise SystemExit("ERROR: --fdr and --pval-max take a level within (0, 1].")
+    groups = _read_groups(args.groups, args.outpfx) if args.groups else None
     from digdriver_amd.driver_model import cohort_batch
     print('Running user-defined element driver detection for {} cohorts'.format(n))
     common = dict(scale_factors=factors, max_muts_per_sample=args.max_muts_per_sample,
                   max_muts_per_elt_per_sample=args.max_muts_per_elt_per_sample)
+    if groups is not None:                        # the cohorts' files and the groups' behind ONE pass over the inputs
+        common['element_pass'] = cohort_batch._element_pass(args.mutation_files, args.maps, args.f_element_data, args.save_key, factors,
+                                                            args.max_muts_per_sample, args.max_muts_per_elt_per_sample)
+
+    def meta(**cut_kw):
+        # (the groups' files beside the cohorts': <group>.meta.results.txt, or <group>.meta.hits.txt under the same cut)
+        if groups is None:
+            return
+        frames, paths = cohort_batch.run_and_write_element_meta(args.mutation_files, args.maps, args.f_element_data, args.save_key,
+                                                                groups, args.outdir, labels=args.outpfx, **cut_kw, **common)
+        for frame, path in zip(frames, paths):
+            if cut_kw:
+                print('\t{}: {} hits of {} testable elements; saved to {}'.format(frame.attrs['group'], len(frame),
+                                                                                 frame.attrs['n_testable'], path))
+            else:
+                print('\tSaved results to {}'.format(path))
+
     if cut is None:
         _, paths = cohort_batch.run_and_write_element_cohorts(args.mutation_files, args.maps, args.f_element_data, args.save_key,
                                                               args.outdir, args.outpfx, qvalues=args.qvalues, **common)
         for path in paths:
             print('\tSaved results to {}'.format(path))
+        meta()
         return
     try:
         frames, paths = cohort_batch.run_and_write_element_calls(
@@ -175,6 +196,40 @@ def cmd_element_cohorts(args):
         raise SystemExit("ERROR: {}".format(exc))
     for pfx, frame, path in zip(args.outpfx, frames, paths):
         print('\t{}: {} hits of {} testable elements; saved to {}'.format(pfx, len(frame), frame.attrs['n_testable'], path))
+    try:
+        meta(pval_max=args.pval_max, fdr=args.fdr, cut_on=args.cut_on or 'PVAL_SNV_BURDEN')
+    except ValueError as exc:
+        if 'no indel columns' not in str(exc):
+            raise
+        raise SystemExit("ERROR: {}".format(exc))
+
+
+def _read_groups(path, prefixes):
+    """--groups FILE of elementCohorts: two tab-separated columns, group name and cohort prefix (one of --outpfx; a cohort may be in
+    many groups) -> an ordered dict group name -> prefixes.  An empty file, an unknown prefix, a repeated pair and a group name that
+    repeats a cohort prefix (its files would be confused with the cohort's) end the command before a cohort's file is read."""
+    if len(set(prefixes)) != len(prefixes):
+        raise SystemExit("ERROR: --groups names cohorts by their --outpfx, which must then differ from each other.")
+    groups = {}
+    with open(path) as fh:
+        for n, line in enumerate(fh, 1):
+            line = line.rstrip('\r\n')
+            if not line.strip() or line.startswith('#'):
+                continue
+            cols = line.split('\t')
+            if len(cols) != 2 or not cols[0].strip() or not cols[1].strip():
+                raise SystemExit("ERROR: --groups {}, line {}: two tab-separated columns, group name and cohort prefix.".format(path, n))
+            name, pfx = cols[0].strip(), cols[1].strip()
+            if pfx not in prefixes:
+                raise SystemExit("ERROR: --groups {}, line {}: {} is not one of --outpfx.".format(path, n, pfx))
+            if name in prefixes:
+                raise SystemExit("ERROR: --groups {}, line {}: the group name {} repeats a cohort prefix.".format(path, n, name))
+            if pfx in groups.setdefault(name, []):
+                raise SystemExit("ERROR: --groups {}, line {}: {} is in group {} already.".format(path, n, pfx, name))
+            groups[name].append(pfx)
+    if not groups:
+        raise SystemExit("ERROR: --groups {} names no group.".format(path))
+    return groups
 
 
 def _cohort_lists(args):
@@ -461,6 +516,9 @@ def parse_args(text=None):
     ec.add_argument('--pval-max', type=float, default=None, help='write only the elements with p <= this, as <outpfx>.hits.txt')
     ec.add_argument('--cut-on', default=None, choices=['PVAL_SNV_BURDEN', 'PVAL_SAMPLE_BURDEN', 'PVAL_INDEL_BURDEN', 'PVAL_MUT_BURDEN'],
                     help='the column --fdr / --pval-max select on (default PVAL_SNV_BURDEN)')
+    ec.add_argument('--groups', type=str, default=None,
+                    help='file of two tab-separated columns, group name and cohort prefix (one of --outpfx): per group the cohorts\' '
+                         'p-values combined by Fisher\'s method, as <group>.meta.results.txt (under a cut: <group>.meta.hits.txt)')
     ec.set_defaults(func=cmd_element_cohorts)
 
     def cohort_lists(p):
