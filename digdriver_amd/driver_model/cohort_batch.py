@@ -30,6 +30,14 @@ gene route's way (engine.gene_counts), the scale factor's rows inside the panel 
 (dig_panel_row_keys + a key sort + dig_panel_counts), then ONE dig_gene_stats launch over [G, C]; count_cohort_mutations writes the
 attributes of `DigPretrain.py countMutations` for C maps from one such call over all installed panels
 (tests/test_gpu_target_cohorts.py).
+
+What the routes share, each written once:
+    _element_planes   overlaps, tabulation, scale callback, plan, unpack, gamma -> planes()     element_pass (element, calls, meta), quick
+    _select_hits, _hit_frames, _check_cut   q-values, cut, row_select, gather, hit frames       run_element_calls, run_element_meta_calls
+    _gene_row_counts, _gene_frame_columns, _gene_frame_done   rows -> gene_counts -> columns    gene, target
+    _run_and_write    files written while the frames behind them are assembled                  the five run_and_write_*_cohorts
+    _write_frames     finished frames to files, several at a time                               write_results, the calls' and the groups' files
+    _writer_threads, _usable_cores   every pool's size, from the cores the process may use      all of the above, _encode_all_mutations
 """
 import numpy as np
 import pandas as pd
@@ -39,16 +47,8 @@ from .._marshal import resolve_device
 from ..data_tools import cohort_rows, mutation_tools, tabulate_gpu
 from ..io import mapfile
 from ..sequence_model import genic_driver_tools, nb_model
+from ..sequence_model.genic_driver_tools import _usable_cores
 from . import transfer_tools
-
-_MUT_COLS10 = ['CHROM', 'START', 'END', 'REF', 'ALT', 'SAMPLE', 'GENE', 'ANNOT', 'MUT_TYPE', 'CONTEXT']
-
-
-def _read_raw_mutations(f_mut):
-    df = pd.read_csv(f_mut, sep="\t", header=None, low_memory=False, dtype={0: str})
-    df = df.iloc[:, :8].copy()
-    df.columns = _MUT_COLS10[:8]
-    return df
 
 
 def genome_scale_factors(tables, cohorts, device, dev_tables=None):
@@ -141,25 +141,23 @@ _PVAL_PLANES = {'PVAL_SNV_BURDEN': 1, 'PVAL_SAMPLE_BURDEN': 2, 'PVAL_INDEL_BURDE
 _QVAL_COLUMNS = ['QVAL_' + k[5:] for k in _PVAL_PLANES]                 # in the order they stand behind the frame's columns
 
 
-def _element_pass(f_muts, f_pretrained, f_element_data, save_key, scale_factors=None, max_muts_per_sample=3e9,
-                  max_muts_per_elt_per_sample=3e9, device=0, timings=None, read_workers=None, output_form="records"):
-    """The front half run_element_cohorts and run_element_calls share: the three inputs read side by side, the tabulation, the scale
-    factors, the plan's pass and its unpacking.  Returns (planes, names, stages): `planes()` gives every plane a frame is built from
-    as a device tensor, a cohort's column one contiguous row -- ELT_SIZE, R_SIZE, P_INDEL [E]; FLAG, R_OBS, MU, SIGMA, ALPHA, THETA
-    (unscaled), P0, OBS_SNV, OBS_SAMPLES, OBS_INDEL [C, E]; S [7, C, E] (engine.ES_PLANES); CJ [C] -- `names` the element names and
-    `stages` the _Stages of `timings`, marked up to "kernels".
+def element_pass(f_muts, f_pretrained, f_element_data, save_key, scale_factors=None, max_muts_per_sample=3e9,
+                 max_muts_per_elt_per_sample=3e9, device=0, timings=None, read_workers=None, output_form="records"):
+    """The front half the four element routes share, and what their `element_pass=` argument takes: the three inputs read side by
+    side, then _element_planes (the tabulation, the scale factors, the plan's pass and its unpacking).  Returns (planes, names,
+    stages): `planes()` gives every plane a frame is built from as a device tensor, a cohort's column one contiguous row -- ELT_SIZE,
+    R_SIZE, P_INDEL [E]; FLAG, R_OBS, MU, SIGMA, ALPHA, THETA (unscaled), P0, OBS_SNV, OBS_SAMPLES, OBS_INDEL [C, E]; S [7, C, E]
+    (engine.ES_PLANES); CJ [C] -- `names` the element names and `stages` the _Stages of `timings`, marked up to "kernels".
     The three inputs are independent until the kernels need them, so they are read SIDE BY SIDE (round 5; one after the other
     they were 0.8 of the 1.5 s of a 37-cohort run): the maps (a thread per map), the element container, and the mutation
     files -- each parsed by the library's own parser and uploaded by its own thread as soon as it is parsed."""
-    import os
     import time
-    import torch
     from concurrent.futures import ThreadPoolExecutor
     dev = resolve_device(device)
     assert len(f_muts) == len(f_pretrained) and len(f_muts) > 0
     C = len(f_muts)
     if read_workers is None:
-        read_workers = min(C, os.cpu_count() or 1) if C >= 8 else 1
+        read_workers = min(C, _usable_cores()) if C >= 8 else 1
     st_ = _Stages(timings, dev)
     first = list(f_pretrained)[0]
     idx0 = mapfile.read_array(first, 'idx')
@@ -193,31 +191,46 @@ def _element_pass(f_muts, f_pretrained, f_element_data, save_key, scale_factors=
         elts, si_index, si_values = timed("read_element_data", read_elements)()
         cohorts = timed("parse_and_upload_mutation_files", lambda: _encode_all_mutations(f_muts, 1, device=dev))()
     assert tables.window == w, "the maps' bin grid and the first map's idx disagree"
-    E = len(elts['names'])
     ctx = tables.aligned_context(si_index, si_values)
     st_.mark("read_parse_upload")
     if timings is not None:
         timings["inside_read_parse_upload"] = {k: round(v, 4) for k, v in spans.items()}
-    ov_ptr, ov_idx = engine.ideal_overlaps(elts['chrom'], elts['blk_ptr'], elts['blk_start'], elts['blk_end'], w,
+
+    def scale(blacklists, dev_tables):
+        if scale_factors is not None:
+            return scale_factors
+        print('Calculating scale factor')
+        return genome_scale_factors(tables, cohorts, dev, dev_tables)
+    return _element_planes(elts, tables, d_pr, ctx, cohorts, scale, max_muts_per_sample, max_muts_per_elt_per_sample, dev, st_,
+                           output_form), elts['names'], st_
+
+
+def _element_planes(elts, tables, d_pr, ctx, cohorts, scale, max_muts_per_sample, max_muts_per_elt_per_sample, dev, st_,
+                    output_form="records"):
+    """What the element and the quick route do alike once both hold the elements (elts: chrom, blk_ptr, blk_start, blk_end,
+    strand_minus, L -- host arrays or device tensors), the maps' tables and d_pr, the grid's window contexts ctx and the encoded
+    cohorts: the bin overlaps, the join and tabulation, the scale factors, the plan's pass, its unpacking and the Gamma parameters.
+    scale(blacklists, dev_tables) -> (cj [C], cj_indel [C]) is the route's own rule, called once behind the tabulation (the quick
+    route's expectation rule needs the samples the tabulation blacklisted).  Returns `planes`: planes() is the dict of device planes
+    element_pass describes.  st_: the _Stages marked from "bin_overlaps" to "kernels"."""
+    import torch
+    C, E = len(cohorts), len(elts['blk_ptr']) - 1
+    ov_ptr, ov_idx = engine.ideal_overlaps(elts['chrom'], elts['blk_ptr'], elts['blk_start'], elts['blk_end'], tables.window,
                                            tables.chrom, tables.start)
     st_.mark("bin_overlaps")
     print('Tabulating mutations')
     owner = np.repeat(np.arange(E), np.diff(elts['blk_ptr']))
     blocks = tabulate_gpu.ElementBlocks(elts['chrom'][owner], elts['blk_start'], elts['blk_end'], owner, E, dev)
-    obs_snv, obs_smp, obs_ind, _ = tabulate_gpu.tabulate_cohorts(blocks, cohorts, drop_duplicates=True,
-                                                                 max_muts_per_sample=max_muts_per_sample,
-                                                                 max_muts_per_elt_per_sample=max_muts_per_elt_per_sample)
+    obs_snv, obs_smp, obs_ind, blacklists = tabulate_gpu.tabulate_cohorts(blocks, cohorts, drop_duplicates=True,
+                                                                          max_muts_per_sample=max_muts_per_sample,
+                                                                          max_muts_per_elt_per_sample=max_muts_per_elt_per_sample)
     st_.mark("join_tabulate")
     dev_tables = tables.on_device(dev)                      # [N, C] on the device (uploaded cohort-major, transposed there)
-    if scale_factors is None:
-        print('Calculating scale factor')
-        cj, cji = genome_scale_factors(tables, cohorts, dev, dev_tables)
-    else:
-        cj = torch.as_tensor(np.asarray(scale_factors[0], float), device=dev).reshape(C)
-        cji = torch.as_tensor(np.asarray(scale_factors[1], float), device=dev).reshape(C)
+    cj, cji = (x if torch.is_tensor(x) else torch.as_tensor(np.asarray(x, float), device=dev).reshape(C)
+               for x in scale(blacklists, dev_tables))
     st_.mark("scale_factors")
     print('Calculating statistics')
-    t = lambda a: torch.as_tensor(np.ascontiguousarray(a), device=dev)
+    t = lambda a: a if torch.is_tensor(a) else torch.as_tensor(np.ascontiguousarray(a), device=dev)
     args = (*dev_tables, t(ctx), t(ov_ptr), t(ov_idx), t(elts['L']), t(elts['strand_minus']), t(d_pr))
     st_.mark("h2d")
     # The pass.  The statistics stage writes tile-blocked RECORDS (DIG_PIPE_RECORDS: one aligned run per 64-pair tile instead of
@@ -231,10 +244,8 @@ def _element_pass(f_muts, f_pretrained, f_element_data, save_key, scale_factors=
     if plan.records_out:
         acc, _ = plan.run(cj, cji)
         st_cm = torch.empty((len(engine.ES_PLANES), plan.C, plan.E), dtype=torch.float64, device=dev)
-        rates = {"MU": torch.empty((plan.C, plan.E), dtype=torch.float64, device=dev),
-                 "SIGMA": torch.empty((plan.C, plan.E), dtype=torch.float64, device=dev),
-                 "R_OBS": torch.empty((plan.C, plan.E), dtype=torch.int32, device=dev),
-                 "FLAG": torch.empty((plan.C, plan.E), dtype=torch.int32, device=dev)}
+        rates = {k: torch.empty((plan.C, plan.E), dtype=kind, device=dev)
+                 for k, kind in (("MU", torch.float64), ("SIGMA", torch.float64), ("R_OBS", torch.int32), ("FLAG", torch.int32))}
         plan.unpack(cohort_major=True, stats=st_cm, rates=rates)
         alpha, theta = nb_model.normal_params_to_gamma(rates["MU"], rates["SIGMA"])
         st_.mark("kernels")
@@ -258,11 +269,11 @@ def _element_pass(f_muts, f_pretrained, f_element_data, save_key, scale_factors=
         D.update(P0=acc['P'][:, 0, :].transpose(0, 1).contiguous(), CJ=cj, OBS_SNV=by_cohort(obs_snv), OBS_SAMPLES=by_cohort(obs_smp),
                  OBS_INDEL=by_cohort(obs_ind))
         return D
-    return all_planes, elts['names'], st_
+    return all_planes
 
 
 def _element_columns(x, cj, have_indel, q=None):
-    """The columns of one cohort's frame, in the frame's order, from host arrays: x maps a plane of _element_pass to the cohort's row of
+    """The columns of one cohort's frame, in the frame's order, from host arrays: x maps a plane of element_pass to the cohort's row of
     it (S: [7, rows]) -- every element for run_element_cohorts, the hits for run_element_calls --, cj is the cohort's scale factor,
     q [4, rows] or None the q-values of the four PVAL columns."""
     S = x['S']
@@ -280,7 +291,7 @@ def _element_columns(x, cj, have_indel, q=None):
 
 
 def _cohort_rows_of(X, c):
-    """Cohort c's row of every host plane of _element_pass (a per-element plane as it is, CJ left out)."""
+    """Cohort c's row of every host plane of element_pass (a per-element plane as it is, CJ left out)."""
     return {k: (v if v.ndim == 1 else v[:, c] if v.ndim == 3 else v[c]) for k, v in X.items() if k != 'CJ'}
 
 
@@ -304,6 +315,62 @@ def plane_qvalues(p):
     return engine.row_scatter(flat, float("inf"), q, float("nan")).reshape(p.shape)
 
 
+def _planes_of(given, *inputs):
+    """(the device planes, the element names, the stages) of a route's element_pass= argument, or of element_pass(*inputs) without it."""
+    planes, names, st_ = given or element_pass(*inputs)
+    return planes(), names, st_
+
+
+def _check_cut(pval_max, fdr, cut_on, what="cut_on"):
+    """A cut's arguments, checked before a file is read: exactly one of pval_max / fdr, `cut_on` one of the four PVAL_*_BURDEN columns;
+    returns its place among them (0..3).  what="best_on": the column run_element_meta ranks the members by, which no cut goes with."""
+    if what == "cut_on" and (pval_max is None) == (fdr is None):
+        raise ValueError("exactly one of pval_max and fdr must be given")
+    if cut_on not in _PVAL_PLANES:
+        raise ValueError("%s: one of %s" % (what, ", ".join(_PVAL_PLANES)))
+    return list(_PVAL_PLANES).index(cut_on)
+
+
+def _select_hits(P, j, pval_max, fdr):
+    """The selection over the p-value planes P f64 [4, R, E] on the device (R rows: cohorts or groups), cut on plane j: the q-values of
+    all four planes (_ragged_qvalues, scattered back: NaN where P is), the cut per row -- nb_model.bh_cut over the row's testable
+    values of plane j at `fdr`, or `pval_max` for every row -- and engine.row_select at it.  Returns (Q f64 [4, R, E], hit_ptr host
+    [R + 1], the hits' row and element as device index tensors, n_testable [R]: the non-NaN values of plane j)."""
+    import torch
+    _, R, E = P.shape
+    pvals = P.reshape(4 * R, E)
+    lists, q_lists = _ragged_qvalues(pvals)
+    Q = engine.row_scatter(pvals, float("inf"), q_lists, float("nan")).reshape(4, R, E)
+    ptr = lists["row_ptr"][j * R:(j + 1) * R + 1]                                     # the lists of plane j
+    if fdr is not None:
+        cuts = np.array([nb_model.bh_cut(lists["score"][ptr[r]:ptr[r + 1]], q_lists[ptr[r]:ptr[r + 1]], fdr) for r in range(R)])
+    else:
+        cuts = np.full(R, float(pval_max))
+    hits = engine.row_select(pvals[j * R:(j + 1) * R], cuts)
+    hit_ptr, elt = hits["row_ptr"], hits["index"].long()
+    row = torch.as_tensor(np.repeat(np.arange(R), np.diff(hit_ptr)), device=elt.device)
+    return Q, hit_ptr, row, elt, np.diff(ptr)
+
+
+def _hit_frames(planes, hits, names, st_, columns):
+    """One frame per row of _select_hits' `hits` from the device planes ([E], [R, E] or [k, R, E]) gathered at (row, element) -- only
+    the hits cross to the host --: columns(r, x, q) gives row r's columns from its slice x of every plane and q [4, hits] of the
+    q-values.  Index: the hits' element names; attrs['n_testable']."""
+    Q, hit_ptr, row, elt, n_testable = hits
+    at = lambda v: v[elt] if v.dim() == 1 else v[:, row, elt] if v.dim() == 3 else v[row, elt]
+    X = {k: at(v).cpu().numpy() for k, v in planes.items()}
+    q_hits, elt = at(Q).cpu().numpy(), elt.cpu().numpy()
+    st_.mark("d2h")
+    frames = []
+    index = pd.Index(names, name='ELT')
+    for r in range(len(hit_ptr) - 1):
+        lo, hi = int(hit_ptr[r]), int(hit_ptr[r + 1])
+        frames.append(pd.DataFrame(columns(r, {k: v[..., lo:hi] for k, v in X.items()}, q_hits[:, lo:hi]), index=index[elt[lo:hi]]))
+        frames[-1].attrs['n_testable'] = int(n_testable[r])
+    st_.mark("frames")
+    return frames
+
+
 def run_element_cohorts(f_muts, f_pretrained, f_element_data, save_key, scale_factors=None, max_muts_per_sample=3e9,
                         max_muts_per_elt_per_sample=3e9, device=0, timings=None, read_workers=None, on_frame=None,
                         output_form="records", qvalues=False, element_pass=None):
@@ -318,11 +385,10 @@ def run_element_cohorts(f_muts, f_pretrained, f_element_data, save_key, scale_fa
     output_form: "records" (default) or "planes" -- the layout the statistics stage writes on the device (same frames).
     qvalues: behind the columns of the frame, QVAL_SNV_BURDEN, QVAL_SAMPLE_BURDEN and, where the cohort has indel columns,
     QVAL_INDEL_BURDEN, QVAL_MUT_BURDEN: Benjamini-Hochberg over the column's non-NaN p-values (plane_qvalues; NaN where PVAL is).
-    element_pass: what _element_pass returned for the same inputs, for a caller that runs several routes behind ONE pass (the
+    element_pass: what element_pass returned for the same inputs, for a caller that runs several routes behind ONE pass (the
     command line with --groups); the inputs are then not read again."""
-    planes, names, st_ = element_pass or _element_pass(f_muts, f_pretrained, f_element_data, save_key, scale_factors, max_muts_per_sample,
-                                                       max_muts_per_elt_per_sample, device, timings, read_workers, output_form)
-    D = planes()
+    D, names, st_ = _planes_of(element_pass, f_muts, f_pretrained, f_element_data, save_key, scale_factors, max_muts_per_sample,
+                               max_muts_per_elt_per_sample, device, timings, read_workers, output_form)
     if qvalues:
         Q = plane_qvalues(D['S'][list(_PVAL_PLANES.values())]).cpu().numpy()             # [4, C, E]
         st_.mark("qvalues")
@@ -349,60 +415,25 @@ def run_element_calls(f_muts, f_pretrained, f_element_data, save_key, pval_max=N
     fdr: p* per cohort from nb_model.bh_cut over the cohort's testable p-values ({q <= fdr} = {p <= p*}); the hits are
     engine.row_select at p* (pval_max: at pval_max), every column is gathered at (cohort, element) on the device, and only the hits
     cross to the host.  The other options as run_element_cohorts takes them."""
-    if (pval_max is None) == (fdr is None):
-        raise ValueError("exactly one of pval_max and fdr must be given")
-    if cut_on not in _PVAL_PLANES:
-        raise ValueError("cut_on: one of %s" % ", ".join(_PVAL_PLANES))
-    import torch
-    planes, names, st_ = element_pass or _element_pass(f_muts, f_pretrained, f_element_data, save_key, scale_factors, max_muts_per_sample,
-                                                       max_muts_per_elt_per_sample, device, timings, read_workers, output_form)
-    D = planes()
-    C, E = D['MU'].shape
+    j = _check_cut(pval_max, fdr, cut_on)
+    D, names, st_ = _planes_of(element_pass, f_muts, f_pretrained, f_element_data, save_key, scale_factors, max_muts_per_sample,
+                               max_muts_per_elt_per_sample, device, timings, read_workers, output_form)
     have_indel = (D['OBS_INDEL'].sum(dim=1) != 0).cpu().numpy()
-    j = list(_PVAL_PLANES).index(cut_on)
     if j >= 2 and not have_indel.all():
-        raise ValueError("cut_on = %s: cohorts %s have no indel columns" % (cut_on, [c for c in range(C) if not have_indel[c]]))
-    pvals = D['S'][list(_PVAL_PLANES.values())].reshape(4 * C, E)                     # row k C + c: PVAL column k of cohort c
-    lists, q_lists = _ragged_qvalues(pvals)
-    Q = engine.row_scatter(pvals, float("inf"), q_lists, float("nan")).reshape(4, C, E)
-    ptr = lists["row_ptr"][j * C:(j + 1) * C + 1]                                     # the lists of cut_on
-    if fdr is not None:
-        cuts = np.array([nb_model.bh_cut(lists["score"][ptr[c]:ptr[c + 1]], q_lists[ptr[c]:ptr[c + 1]], fdr) for c in range(C)])
-    else:
-        cuts = np.full(C, float(pval_max))
-    hits = engine.row_select(pvals[j * C:(j + 1) * C], cuts)
-    hit_ptr, elt = hits["row_ptr"], hits["index"].long()
+        raise ValueError("cut_on = %s: cohorts %s have no indel columns" % (cut_on, [c for c in range(len(have_indel)) if not have_indel[c]]))
+    hits = _select_hits(D['S'][list(_PVAL_PLANES.values())], j, pval_max, fdr)        # row k C + c: PVAL column k of cohort c
     st_.mark("qvalues_select")
-    cohort = torch.as_tensor(np.repeat(np.arange(C), np.diff(hit_ptr)), device=elt.device)
-    at = lambda v: v[elt] if v.dim() == 1 else v[:, cohort, elt] if v.dim() == 3 else v[cohort, elt]
-    X = {k: (v if k == 'CJ' else at(v)).cpu().numpy() for k, v in D.items()}
-    q_hits, elt = at(Q).cpu().numpy(), elt.cpu().numpy()
-    st_.mark("d2h")
-    frames = []
-    index = pd.Index(names, name='ELT')
-    for c in range(C):
-        lo, hi = int(hit_ptr[c]), int(hit_ptr[c + 1])
-        d = _element_columns({k: v[..., lo:hi] for k, v in X.items() if k != 'CJ'}, X['CJ'][c], have_indel[c], q_hits[:, lo:hi])
-        frames.append(pd.DataFrame(d, index=index[elt[lo:hi]]))
-        frames[-1].attrs['n_testable'] = int(ptr[c + 1] - ptr[c])
-    st_.mark("frames")
-    return frames
+    cj = D.pop('CJ').cpu().numpy()
+    return _hit_frames(D, hits, names, st_, lambda c, x, q: _element_columns(x, cj[c], have_indel[c], q))
 
 
 def run_and_write_element_calls(f_muts, f_pretrained, f_element_data, save_key, outdir, prefixes, write_threads=None, **kw):
     """run_element_calls with cohort c's hits written to <outdir>/<prefix>.hits.txt (mapfile.write_results_tsv, the OBS_* columns as
     integers like those of the results files), several files at a time as write_results writes them.  Returns (frames, paths)."""
     import os
-    from concurrent.futures import ThreadPoolExecutor
     frames = run_element_calls(f_muts, f_pretrained, f_element_data, save_key, **kw)
     assert len(prefixes) == len(frames)
-    os.makedirs(outdir, exist_ok=True)
-    paths = [os.path.join(outdir, pfx + '.hits.txt') for pfx in prefixes]
-    cores = os.cpu_count() or 1
-    threads = int(write_threads) if write_threads else max(1, min(8, cores // max(len(frames), 1)))
-    with ThreadPoolExecutor(max_workers=max(1, min(len(frames), cores))) as pool:
-        list(pool.map(lambda job: _write_one(job[0], job[1], threads), zip(frames, paths)))
-    return frames, paths
+    return frames, _write_frames(frames, [os.path.join(outdir, pfx + '.hits.txt') for pfx in prefixes], write_threads)
 
 
 # ---------------------------------------------------------------------------------------------
@@ -445,7 +476,7 @@ _N_TESTED_COLUMNS = ['N_TESTED_' + k[5:] for k in _PVAL_PLANES]
 
 
 def _meta_planes(D, members, best_on):
-    """The device half of the meta routes from the planes of _element_pass: dict(P f64 [4, M, E] the combined _PVAL_PLANES, N i32
+    """The device half of the meta routes from the planes of element_pass: dict(P f64 [4, M, E] the combined _PVAL_PLANES, N i32
     [4, M, E] the members that tested, OBS f64 [3, M, E] the sums of OBS_SAMPLES, OBS_SNV, OBS_INDEL, EXP f64 [2, M, E] those of EXP_SNV
     and EXP_INDEL over the members that tested the SNV / the indel burden, BEST i64 [M, E] the member with the smallest p-value of
     plane `best_on` (ties: the lowest cohort; -1 where none tested), have_indel bool [C] on the host).  The indel and mut planes of a
@@ -490,12 +521,6 @@ def _meta_columns(x, n_members, have_indel, q, labels):
     return d
 
 
-def _best_on(name, what):
-    if name not in _PVAL_PLANES:
-        raise ValueError("%s: one of %s" % (what, ", ".join(_PVAL_PLANES)))
-    return list(_PVAL_PLANES).index(name)
-
-
 def run_element_meta(f_muts, f_pretrained, f_element_data, save_key, groups, labels=None, qvalues=True, best_on='PVAL_SNV_BURDEN',
                      scale_factors=None, max_muts_per_sample=3e9, max_muts_per_elt_per_sample=3e9, device=0, timings=None,
                      read_workers=None, output_form="records", element_pass=None):
@@ -511,10 +536,9 @@ def run_element_meta(f_muts, f_pretrained, f_element_data, save_key, groups, lab
     count as not tested; a group in which no member has indel columns leaves out EXP_INDEL and its indel and mut columns, as a cohort's
     frame does.  The other options as run_element_cohorts takes them."""
     names_g, members, labels = _meta_groups(groups, labels, len(f_muts))
-    j = _best_on(best_on, "best_on")
-    planes, names, st_ = element_pass or _element_pass(f_muts, f_pretrained, f_element_data, save_key, scale_factors, max_muts_per_sample,
-                                                       max_muts_per_elt_per_sample, device, timings, read_workers, output_form)
-    D = planes()
+    j = _check_cut(None, None, best_on, "best_on")
+    D, names, st_ = _planes_of(element_pass, f_muts, f_pretrained, f_element_data, save_key, scale_factors, max_muts_per_sample,
+                               max_muts_per_elt_per_sample, device, timings, read_workers, output_form)
     T = _meta_planes(D, members, j)
     have_indel = T.pop('have_indel')
     Q = plane_qvalues(T['P']).cpu().numpy() if qvalues else None
@@ -541,44 +565,21 @@ def run_element_meta_calls(f_muts, f_pretrained, f_element_data, save_key, group
     columns, dtypes, row order and bits.  Exactly one of pval_max / fdr; an indel column that a group lacks is a ValueError.  The
     selection is run_element_calls' over the groups' combined planes (nb_model.bh_cut, engine.row_select at p*, a gather at (group,
     element)); only the hits cross to the host.  frame.attrs['n_testable']: the non-NaN values of cut_on in the group."""
-    if (pval_max is None) == (fdr is None):
-        raise ValueError("exactly one of pval_max and fdr must be given")
-    j = _best_on(cut_on, "cut_on")
+    j = _check_cut(pval_max, fdr, cut_on)
     names_g, members, labels = _meta_groups(groups, labels, len(f_muts))
-    import torch
-    planes, names, st_ = element_pass or _element_pass(f_muts, f_pretrained, f_element_data, save_key, scale_factors, max_muts_per_sample,
-                                                       max_muts_per_elt_per_sample, device, timings, read_workers, output_form)
-    D = planes()
+    D, names, st_ = _planes_of(element_pass, f_muts, f_pretrained, f_element_data, save_key, scale_factors, max_muts_per_sample,
+                               max_muts_per_elt_per_sample, device, timings, read_workers, output_form)
     T = _meta_planes(D, members, j)
     have_indel = np.array([bool(T['have_indel'][idx].any()) for idx in members])
     del T['have_indel']
     if j >= 2 and not have_indel.all():
         raise ValueError("cut_on = %s: groups %s have no indel columns" % (cut_on, [n for n, h in zip(names_g, have_indel) if not h]))
-    M, E = T['BEST'].shape
-    pvals = T['P'].reshape(4 * M, E)                                                  # row k M + g: PVAL column k of group g
-    lists, q_lists = _ragged_qvalues(pvals)
-    Q = engine.row_scatter(pvals, float("inf"), q_lists, float("nan")).reshape(4, M, E)
-    ptr = lists["row_ptr"][j * M:(j + 1) * M + 1]
-    if fdr is not None:
-        cuts = np.array([nb_model.bh_cut(lists["score"][ptr[g]:ptr[g + 1]], q_lists[ptr[g]:ptr[g + 1]], fdr) for g in range(M)])
-    else:
-        cuts = np.full(M, float(pval_max))
-    hits = engine.row_select(pvals[j * M:(j + 1) * M], cuts)
-    hit_ptr, elt = hits["row_ptr"], hits["index"].long()
+    hits = _select_hits(T['P'], j, pval_max, fdr)                                     # row k M + g: PVAL column k of group g
     st_.mark("meta_select")
-    group = torch.as_tensor(np.repeat(np.arange(M), np.diff(hit_ptr)), device=elt.device)
-    X = {k: (v[group, elt] if v.dim() == 2 else v[:, group, elt]).cpu().numpy() for k, v in T.items()}
-    X['ELT_SIZE'] = D['ELT_SIZE'][elt].cpu().numpy()
-    q_hits, elt = Q[:, group, elt].cpu().numpy(), elt.cpu().numpy()
-    st_.mark("d2h")
-    frames = []
-    index = pd.Index(names, name='ELT')
-    for g, idx in enumerate(members):
-        lo, hi = int(hit_ptr[g]), int(hit_ptr[g + 1])
-        d = _meta_columns({k: v[..., lo:hi] for k, v in X.items()}, len(idx), have_indel[g], q_hits[:, lo:hi], labels)
-        frames.append(pd.DataFrame(d, index=index[elt[lo:hi]]))
-        frames[-1].attrs.update(group=names_g[g], n_testable=int(ptr[g + 1] - ptr[g]))
-    st_.mark("frames")
+    frames = _hit_frames(dict(T, ELT_SIZE=D['ELT_SIZE']), hits, names, st_,
+                         lambda g, x, q: _meta_columns(x, len(members[g]), have_indel[g], q, labels))
+    for g, frame in enumerate(frames):
+        frame.attrs['group'] = names_g[g]
     return frames
 
 
@@ -587,19 +588,41 @@ def run_and_write_element_meta(f_muts, f_pretrained, f_element_data, save_key, g
     <outdir>/<group>.meta.results.txt (<group>.meta.hits.txt under a cut) as the cohorts' files are written (_write_one).  Returns
     (frames, paths)."""
     import os
-    from concurrent.futures import ThreadPoolExecutor
     cut = kw.get('pval_max') is not None or kw.get('fdr') is not None
     run = run_element_meta_calls if cut else run_element_meta
     if not cut:
         kw = {k: v for k, v in kw.items() if k not in ('pval_max', 'fdr', 'cut_on')}
     frames = run(f_muts, f_pretrained, f_element_data, save_key, groups, labels=labels, **kw)
-    os.makedirs(outdir, exist_ok=True)
-    paths = [os.path.join(outdir, f.attrs['group'] + ('.meta.hits.txt' if cut else '.meta.results.txt')) for f in frames]
-    cores = os.cpu_count() or 1
-    threads = int(write_threads) if write_threads else max(1, min(8, cores // max(len(frames), 1)))
-    with ThreadPoolExecutor(max_workers=max(1, min(len(frames), cores))) as pool:
-        list(pool.map(lambda job: _write_one(job[0], job[1], threads), zip(frames, paths)))
-    return frames, paths
+    sfx = '.meta.hits.txt' if cut else '.meta.results.txt'
+    return frames, _write_frames(frames, [os.path.join(outdir, f.attrs['group'] + sfx) for f in frames], write_threads)
+
+
+def _writer_threads(n, write_threads=None):
+    """For n files written side by side: (the worker threads, one per file up to the usable cores; the threads the native writer
+    uses per file -- write_threads, or the cores shared out among the files, at most 8: the writer keeps one buffer per thread, so
+    files side by side do not contend)."""
+    cores = _usable_cores()
+    return max(1, min(n, cores)), int(write_threads) if write_threads else max(1, min(8, cores // max(n, 1)))
+
+
+def _write_frames(frames, paths, write_threads=None, workers=None):
+    """Frame k written to paths[k] as _write_one writes it (the directories are made), several files at a time -- the native call
+    does not hold the interpreter lock.  workers: the files in flight (default: _writer_threads; 1: one after the other, in this
+    thread).  Returns paths."""
+    import os
+    from concurrent.futures import ThreadPoolExecutor
+    jobs = list(zip(frames, paths))
+    pool_size, threads = _writer_threads(len(jobs), write_threads)
+    workers = pool_size if workers is None else int(workers)
+    for d in set(os.path.dirname(p) for _, p in jobs):
+        os.makedirs(d or '.', exist_ok=True)
+    if workers <= 1 or len(jobs) <= 1:
+        for frame, path in jobs:
+            _write_one(frame, path, threads)
+    else:
+        with ThreadPoolExecutor(max_workers=workers) as pool:
+            list(pool.map(lambda job: _write_one(job[0], job[1], threads), jobs))
+    return list(paths)
 
 
 def _run_and_write(run, n, outdir, prefixes, write_threads, writer):
@@ -612,10 +635,9 @@ def _run_and_write(run, n, outdir, prefixes, write_threads, writer):
     os.makedirs(outdir, exist_ok=True)
     assert len(prefixes) == n
     paths = [os.path.join(outdir, pfx + '.results.txt') for pfx in prefixes]
-    cores = os.cpu_count() or 1
-    threads = int(write_threads) if write_threads else max(1, min(8, cores // max(n, 1)))      # threads the writer uses per file
+    pool_size, threads = _writer_threads(n, write_threads)                # (threads: what the writer uses per file)
     pending = []
-    with ThreadPoolExecutor(max_workers=max(1, min(n, cores))) as pool:
+    with ThreadPoolExecutor(max_workers=pool_size) as pool:
         frames = run(lambda c, *made: pending.append(pool.submit(writer(paths[c], threads, *made))))
         for f in pending:
             f.result()
@@ -663,9 +685,8 @@ def _encode_all_mutations(f_muts, workers=None, device=None):
     cohort's file is 10^5 - 10^6 rows (pandas: 0.45 s per 300 000; C of them one after the other were the largest stage of a
     many-cohort run).  Threads, not processes: pyarrow's reader and numpy's sorts release the interpreter lock, and worker
     processes would have to be spawned -- this process may hold the GPU -- which re-imports the caller's main module."""
-    import os
     n = len(f_muts)
-    workers = min(n, os.cpu_count() or 1) if workers is None else int(workers)
+    workers = min(n, _usable_cores()) if workers is None else int(workers)
     # device: every file's arrays are uploaded by the thread that parsed it, as soon as it is parsed (round 4 uploaded the 37 x 8
     # arrays one after the other behind the last parse: 0.13 s of small pageable copies)
     def job(cf):
@@ -684,25 +705,12 @@ def write_results(frames, outdir, prefixes, workers=None):
     of DataFrame.to_csv), several files at a time (the native call does not hold the interpreter lock)."""
     import os
     os.makedirs(outdir, exist_ok=True)
+    frames = list(frames)
     paths = [os.path.join(outdir, pfx + '.results.txt') for pfx in prefixes]
-
-    jobs = list(zip(frames, paths))
-    cores = os.cpu_count() or 1
-    workers = min(len(jobs), cores) if workers is None else int(workers)
-    threads = max(1, min(8, cores // max(workers, 1)))      # (the writer keeps one buffer per thread: files side by side do not contend)
-
-    def one(job):
-        return _write_one(job[0], job[1], threads)
-
-    if jobs:
-        one(jobs[0])                                         # (fills the label cache)
-    if workers <= 1:
-        for job in jobs[1:]:
-            one(job)
-    elif len(jobs) > 1:
-        from concurrent.futures import ThreadPoolExecutor
-        with ThreadPoolExecutor(max_workers=workers) as pool:
-            list(pool.map(one, jobs[1:]))
+    workers = _writer_threads(min(len(frames), len(paths)))[0] if workers is None else int(workers)
+    threads = _writer_threads(workers)[1]
+    _write_frames(frames[:1], paths[:1], threads)            # (fills the label cache)
+    _write_frames(frames[1:], paths[1:], threads, workers)
     return paths
 
 
@@ -806,6 +814,44 @@ def _burden_columns(d, S, c):
     return d
 
 
+def _gene_row_counts(f_muts, index, keep, drop_synonymous, dev, max_muts_per_sample, max_muts_per_gene_per_sample):
+    """The front half of the gene and the target route: the coding rows of every cohort encoded against the gene `index` (keep: the
+    set of genes whose rows count, or None; drop_synonymous: without the Synonymous rows), stacked and counted by engine.gene_counts
+    (TP53 apart, the hypermutator filter, the per-gene cap).  Returns (rows, their sample offsets, the device counts, the planes of
+    _gene_counts_on_host)."""
+    rows = [tabulate_gpu.encode_gene_rows(f, index, c, keep=keep) for c, f in enumerate(f_muts)]
+    if drop_synonymous:
+        for r in rows:
+            kept = r["annot"] != 0
+            for k in ("gene", "sample", "annot", "cohort"):
+                r[k] = r[k][kept]
+    G = len(index)
+    tp53 = int(index.get_loc('TP53')) if 'TP53' in index else G + 1
+    offsets = cohort_rows.sample_offsets(rows)
+    stack = cohort_rows.place([cohort_rows.column(rows, k) for k in ("gene", "sample", "annot", "cohort")], True, dev)
+    counts = engine.gene_counts(*stack, offsets, G, len(rows), tp53, max_muts_per_sample=max_muts_per_sample,
+                                max_muts_per_gene_per_sample=max_muts_per_gene_per_sample)
+    return rows, offsets, counts, _gene_counts_on_host(counts)
+
+
+def _gene_frame_columns(m, theta, host, c):
+    """The columns both gene-shaped frames start with: _gene_count_columns of cohort c from the planes of _gene_counts_on_host, then
+    EXP_<class> = ALPHA THETA Pi_<class> (gene_expected_muts_nb: the serial route's own products)."""
+    d = _gene_count_columns(m, theta, *(plane[c] for plane in host))
+    rate = m.ALPHA.values * d['THETA']
+    for cls in transfer_tools.GENE_CLASSES:
+        d['EXP_' + cls] = rate * m['Pi_' + cls].values
+    return d
+
+
+def _gene_frame_done(frames, d, index, cj, on_frame):
+    """The tail of both gene-shaped routes for the next cohort: its scale factor printed, its frame made, appended and handed on."""
+    print("\tScaling factor of cohort {} is: {}".format(len(frames), cj))
+    frames.append(pd.DataFrame(d, index=index))
+    if on_frame is not None:
+        on_frame(len(frames) - 1, frames[-1])
+
+
 def run_gene_cohorts(f_muts, f_genemodels, scale_by_sample=False, pval_burden_nb=True, pval_burden_dnds=True, pval_sel=True,
                      max_muts_per_sample=3e9, max_muts_per_gene_per_sample=3e9, scale_factors=None, scale_by_expectation=True,
                      cgc_genes=False, all_cosmic=None, selection=False, device=0, on_frame=None):
@@ -834,16 +880,10 @@ def run_gene_cohorts(f_muts, f_genemodels, scale_by_sample=False, pval_burden_nb
         keep = set(tt.gene_panel(cgc_genes))
         models, planes = _restrict_gene_models(models, planes, keep)
     index = models[0].index
-    G = len(index)
     dev = resolve_device(device)
-
-    rows = [tabulate_gpu.encode_gene_rows(f, index, c, keep=keep) for c, f in enumerate(f_muts)]
-    tp53 = int(index.get_loc('TP53')) if 'TP53' in index else G + 1
-    stack = cohort_rows.place([cohort_rows.column(rows, k) for k in ("gene", "sample", "annot", "cohort")], True, dev)
-    counts = engine.gene_counts(*stack, cohort_rows.sample_offsets(rows), G, C, tp53,
-                                max_muts_per_sample=max_muts_per_sample, max_muts_per_gene_per_sample=max_muts_per_gene_per_sample)
+    _, _, counts, host = _gene_row_counts(f_muts, index, keep, False, dev, max_muts_per_sample, max_muts_per_gene_per_sample)
     by_cohort = lambda x: x.transpose(-1, -2).contiguous().cpu().numpy()                     # [..., G, C] -> [..., C, G]
-    obs_h, n_samp_h, n_samp_indel, n_pairs = _gene_counts_on_host(counts)
+    obs_h = host[0]
     n_syn = counts["n_syn"].cpu().numpy()
 
     # scale factors (transfer_tools.py:809-823) and the uniform indel rate (:709-721), a cohort at a time over G values
@@ -876,11 +916,10 @@ def run_gene_cohorts(f_muts, f_genemodels, scale_by_sample=False, pval_burden_nb
 
     frames = []
     for c, m in enumerate(models):
-        d = _gene_count_columns(m, theta[:, c], obs_h[c], n_samp_h[c], n_samp_indel[c], n_pairs[c])
-        rate = m.ALPHA.values * d['THETA']
-        for q, cls in enumerate(tt.GENE_CLASSES):                          # gene_expected_muts_nb: the serial route's own products
-            d['EXP_' + cls] = S['EXP_' + cls][c] if pval_burden_nb and not selection else rate * m['Pi_' + cls].values
+        d = _gene_frame_columns(m, theta[:, c], host, c)
         if pval_burden_nb:
+            if not selection:                                              # (EXP_<class> as the statistics kernel formed them)
+                d.update({'EXP_' + cls: S['EXP_' + cls][c] for cls in tt.GENE_CLASSES})
             _burden_columns(d, S, c)
         if selection:
             names = ['T_SYN', 'MRFOLD'] + ['EXP_%s_ML' % cls for cls in tt.GENE_CLASSES]
@@ -893,10 +932,7 @@ def run_gene_cohorts(f_muts, f_genemodels, scale_by_sample=False, pval_burden_nb
         if has_indel[c]:                                                   # (pval_burden_nb holds here)
             for name in ('THETA_INDEL', 'EXP_INDEL', 'PVAL_INDEL_BURDEN', 'PVAL_MUT_BURDEN'):
                 d[name] = S[name][c]
-        print("\tScaling factor of cohort {} is: {}".format(c, cj[c]))
-        frames.append(pd.DataFrame(d, index=index))
-        if on_frame is not None:
-            on_frame(c, frames[-1])
+        _gene_frame_done(frames, d, index, cj[c], on_frame)
     return frames
 
 
@@ -972,22 +1008,10 @@ def run_target_cohorts(f_muts, f_genemodels, panel="MSK_341", scale_by_sample=Fa
     models, planes = _read_gene_models(f_genemodels)
     models, planes = _restrict_gene_models(models, planes, tested)
     index = models[0].index
-    G = len(index)
     dev = resolve_device(device)
-
     # row set A: the tested rows -> observed counts, N_SAMP_*, the blacklist
-    rows = [tabulate_gpu.encode_gene_rows(f, index, c, keep=tested) for c, f in enumerate(f_muts)]
-    if drop_synonymous:
-        for r in rows:
-            kept = r["annot"] != 0
-            for k in ("gene", "sample", "annot", "cohort"):
-                r[k] = r[k][kept]
-    tp53 = int(index.get_loc('TP53')) if 'TP53' in index else G + 1
-    offsets = cohort_rows.sample_offsets(rows)
-    stack = cohort_rows.place([cohort_rows.column(rows, k) for k in ("gene", "sample", "annot", "cohort")], True, dev)
-    counts = engine.gene_counts(*stack, offsets, G, C, tp53, max_muts_per_sample=max_muts_per_sample,
-                                max_muts_per_gene_per_sample=max_muts_per_gene_per_sample)
-    obs_h, n_samp_h, n_samp_indel, n_pairs = _gene_counts_on_host(counts)
+    rows, offsets, counts, host = _gene_row_counts(f_muts, index, tested, drop_synonymous, dev, max_muts_per_sample,
+                                                   max_muts_per_gene_per_sample)
 
     # row set B: the scale factor's rows inside the panel, without the samples row set A blacklisted (carried over by name)
     cj = given.copy()
@@ -1011,15 +1035,8 @@ def run_target_cohorts(f_muts, f_genemodels, panel="MSK_341", scale_by_sample=Fa
     _, S = _gene_burden_planes(planes, counts, cj, None, dev)
     frames = []
     for c, m in enumerate(models):
-        d = _gene_count_columns(m, theta[:, c], obs_h[c], n_samp_h[c], n_samp_indel[c], n_pairs[c])
-        rate = m.ALPHA.values * d['THETA']
-        for cls in tt.GENE_CLASSES:                                        # gene_expected_muts_nb: the serial route's own products
-            d['EXP_' + cls] = rate * m['Pi_' + cls].values
-        _burden_columns(d, S, c)
-        print("\tScaling factor of cohort {} is: {}".format(c, cj[c]))
-        frames.append(pd.DataFrame(d, index=index))
-        if on_frame is not None:
-            on_frame(c, frames[-1])
+        d = _burden_columns(_gene_frame_columns(m, theta[:, c], host, c), S, c)
+        _gene_frame_done(frames, d, index, cj[c], on_frame)
     return frames
 
 
@@ -1281,19 +1298,10 @@ def run_quick_cohorts(f_muts, f_pretrained, f_fasta, f_elts_bed=None, region_str
             raise ValueError("elements {} and {} lie on opposite strands and share the block chr{}:{}-{}: the reference counts such a "
                              "block once, on the strand of its first occurrence, for both elements; pass strict_reference=False to "
                              "count it on each element's own strand".format(*pair))
-    return _quick_cohorts(f_muts, f_pretrained, f_fasta, (names, chrom, minus, blk_ptr, blk_start, blk_end, n_listed), given,
-                          scale_by_expectation, max_muts_per_sample, max_muts_per_elt_per_sample, skip_pvals, all_cosmic,
-                          strict_reference, device, on_frame)
-
-
-def _quick_cohorts(f_muts, f_pretrained, f_fasta, elements, given, scale_by_expectation, max_muts_per_sample,
-                   max_muts_per_elt_per_sample, skip_pvals, all_cosmic, strict_reference, device, on_frame):
-    """The device work of run_quick_cohorts and the frames (its arguments checked)."""
+    # the arguments are checked: the device work
     import torch
     from ..sequence_model import sequence_tools
-    names, chrom, minus, blk_ptr, blk_start, blk_end, n_listed = elements
     dev = resolve_device(device)
-    C, E = len(f_muts), len(names)
     files, tables, d_pr = genic_driver_tools._load_cohorts(f_pretrained, workers=None if C >= 8 else 1)
     w = tables.window
     cohorts = _encode_all_mutations(f_muts, None if C >= 8 else 1, device=dev)
@@ -1309,68 +1317,59 @@ def _quick_cohorts(f_muts, f_pretrained, f_fasta, elements, given, scale_by_expe
     # the window contexts of the whole grid (onthefly_tools.py:118-120 counts the touched windows; DESIGN.md section 8.3: all of them
     # cost under a millisecond)
     ctx = engine.count_contexts(genome, ['chr' + str(c) for c in tables.chrom], tables.start, tables.start + w, device=dev)
-    ov_ptr, ov_idx = engine.ideal_overlaps(chrom, blk_ptr, blk_start, blk_end, w, tables.chrom, tables.start)
-    print('Tabulating mutations')
-    owner = np.repeat(np.arange(E), np.diff(blk_ptr))
-    blocks = tabulate_gpu.ElementBlocks(chrom[owner], blk_start, blk_end, owner, E, dev)
-    obs_snv, obs_smp, obs_ind, blacklists = tabulate_gpu.tabulate_cohorts(blocks, cohorts, drop_duplicates=True,
-                                                                          max_muts_per_sample=max_muts_per_sample,
-                                                                          max_muts_per_elt_per_sample=max_muts_per_elt_per_sample)
-    dev_tables = tables.on_device(dev)
-    if scale_by_expectation:                               # onthefly_tools.py:44-63, a cohort at a time on the host
-        print('scaling by expected number of mutations')
-        cj_h, cji_h = np.empty(C), np.empty(C)
-        null = transfer_tools.cosmic_null_set(all_cosmic)
-        for c in range(C):
-            run = transfer_tools.CohortRun(f_muts[c], files[c])
-            coding = run.coding_rows()
-            coding = coding.loc[~coding.SAMPLE.astype(str).isin(set(str(s) for s in blacklists[c]))]
-            cj_h[c] = run.synonymous_scale(run.gene_model(), coding, dedup=True)
-            cji_h[c] = run.uniform_indel_scale(run.gene_model(), coding, null)
-    elif given is not None:
-        cj_h, cji_h = given
-    else:
-        print('Calculating scale factor')
-        cj_d, cji_d = genome_scale_factors(tables, cohorts, dev, dev_tables)
-        cj_h, cji_h = cj_d.cpu().numpy(), cji_d.cpu().numpy()
-    # THETA_INDEL: the reference scales it by cj_indel where the frame is made and again in element_pvalue_indel
-    # (onthefly_tools.py:151,181); once without strict_reference
-    cji_eff = cji_h * cji_h if strict_reference else cji_h
-    print('Calculating statistics')
-    plan = engine.PipelinePlan(*dev_tables, ctx, t(ov_ptr), t(ov_idx), L, t(minus), t(d_pr), obs_snv, obs_smp, obs_ind, compact=False,
-                               pack_bins=True, records_out=True)
-    acc, _ = plan.run(t(np.asarray(cj_h, float)), t(np.asarray(cji_eff, float)))
-    st_cm = torch.empty((len(engine.ES_PLANES), plan.C, plan.E), dtype=torch.float64, device=dev)
-    rates = {"MU": torch.empty((plan.C, plan.E), dtype=torch.float64, device=dev),
-             "SIGMA": torch.empty((plan.C, plan.E), dtype=torch.float64, device=dev),
-             "R_OBS": torch.empty((plan.C, plan.E), dtype=torch.int32, device=dev),
-             "FLAG": torch.empty((plan.C, plan.E), dtype=torch.int32, device=dev)}
-    plan.unpack(cohort_major=True, stats=st_cm, rates=rates)
-    alpha, theta = nb_model.normal_params_to_gamma(rates["MU"], rates["SIGMA"])
-    host = lambda x: x.cpu().numpy()
-    by_cohort = lambda x: host(x.transpose(-1, -2).contiguous())
-    A = {k: host(v) for k, v in acc.items() if k not in ('P', 'MU', 'SIGMA', 'R_OBS', 'FLAG')}
-    A.update({k: host(v) for k, v in rates.items()})
-    S, al, th = host(st_cm), host(alpha), host(theta)
-    P0 = host(acc['P'][:, 0, :].transpose(0, 1).contiguous())
-    o_snv, o_smp, o_ind = by_cohort(obs_snv), by_cohort(obs_smp), by_cohort(obs_ind)
+    cji_h = []
+
+    def scale(blacklists, dev_tables):
+        if scale_by_expectation:                           # onthefly_tools.py:44-63, a cohort at a time on the host
+            print('scaling by expected number of mutations')
+            cj, cji = np.empty(C), np.empty(C)
+            null = transfer_tools.cosmic_null_set(all_cosmic)
+            for c in range(C):
+                run = transfer_tools.CohortRun(f_muts[c], files[c])
+                coding = run.coding_rows()
+                coding = coding.loc[~coding.SAMPLE.astype(str).isin(set(str(s) for s in blacklists[c]))]
+                cj[c] = run.synonymous_scale(run.gene_model(), coding, dedup=True)
+                cji[c] = run.uniform_indel_scale(run.gene_model(), coding, null)
+        elif given is not None:
+            cj, cji = given
+        else:
+            print('Calculating scale factor')
+            cj, cji = (x.cpu().numpy() for x in genome_scale_factors(tables, cohorts, dev, dev_tables))
+        cji_h.append(cji)
+        # THETA_INDEL: the reference scales it by cj_indel where the frame is made and again in element_pvalue_indel
+        # (onthefly_tools.py:151,181); once without strict_reference
+        return cj, cji * cji if strict_reference else cji
+    elts = dict(chrom=chrom, blk_ptr=blk_ptr, blk_start=blk_start, blk_end=blk_end, strand_minus=minus, L=L)
+    planes = _element_planes(elts, tables, d_pr, ctx, cohorts, scale, max_muts_per_sample, max_muts_per_elt_per_sample, dev,
+                             _Stages(None, dev))
+    X = {k: v.cpu().numpy() for k, v in planes().items()}
     frames = []
     index = pd.Index(np.asarray(names, dtype=object), name='ELT')
     for c in range(C):
-        # the columns of df_mut_tab.merge(pretrain_df) (onthefly_tools.py:104-112), then the statistics in the order they are added
-        d = {'OBS_SAMPLES': o_smp[c].astype(_quick_obs_sample_kinds(index, o_smp[c], n_listed)), 'OBS_SNV': o_snv[c].astype(float),
-             'OBS_INDEL': o_ind[c].astype(float), 'ELT_SIZE': A['ELT_SIZE'], 'FLAG': A['FLAG'][c], 'R_SIZE': A['R_SIZE'],
-             'R_OBS': A['R_OBS'][c], 'R_INDEL': A['R_OBS'][c], 'MU': A['MU'][c], 'SIGMA': A['SIGMA'][c], 'ALPHA': al[c],
-             'THETA': th[c] * cj_h[c], 'MU_INDEL': A['MU'][c], 'SIGMA_INDEL': A['SIGMA'][c], 'ALPHA_INDEL': al[c],
-             'THETA_INDEL': (th[c] * cji_h[c] if strict_reference else th[c]) if skip_pvals else S[3][c],
-             'Pi_SUM': P0[c], 'Pi_INDEL': A['P_INDEL'], 'EXP_SNV': S[0][c]}
-        if not skip_pvals:
-            d.update({'PVAL_SNV_BURDEN': S[1][c], 'PVAL_SAMPLE_BURDEN': S[2][c], 'EXP_INDEL': S[4][c], 'PVAL_INDEL_BURDEN': S[5][c],
-                      'PVAL_MUT_BURDEN': S[6][c]})
+        d = _quick_columns(_cohort_rows_of(X, c), X['CJ'][c], cji_h[0][c], index, n_listed, skip_pvals, strict_reference)
         frames.append(pd.DataFrame(d, index=index))
         if on_frame is not None:
             on_frame(c, frames[-1])
     return frames
+
+
+def _quick_columns(x, cj, cji, index, n_listed, skip_pvals, strict_reference):
+    """The columns of one cohort's quick frame from the rows _cohort_rows_of gives _element_columns -- a builder of its own because the
+    frame is DIG_onthefly's, not run_element_region_model's: the columns of df_mut_tab.merge(pretrain_df) (onthefly_tools.py:104-112:
+    the OBS_* first), then the statistics in the order they are added; FLAG stays the int32 of the merge; OBS_SAMPLES has the dtype
+    rule of the left join (_quick_obs_sample_kinds); skip_pvals leaves THETA_INDEL the frame's own product with cji (once more
+    under strict_reference) and drops the tests; and the indel columns are there whether or not the cohort has an indel."""
+    S, th = x['S'], x['THETA']
+    d = {'OBS_SAMPLES': x['OBS_SAMPLES'].astype(_quick_obs_sample_kinds(index, x['OBS_SAMPLES'], n_listed)),
+         'OBS_SNV': x['OBS_SNV'].astype(float), 'OBS_INDEL': x['OBS_INDEL'].astype(float), 'ELT_SIZE': x['ELT_SIZE'], 'FLAG': x['FLAG'],
+         'R_SIZE': x['R_SIZE'], 'R_OBS': x['R_OBS'], 'R_INDEL': x['R_OBS'], 'MU': x['MU'], 'SIGMA': x['SIGMA'], 'ALPHA': x['ALPHA'],
+         'THETA': th * cj, 'MU_INDEL': x['MU'], 'SIGMA_INDEL': x['SIGMA'], 'ALPHA_INDEL': x['ALPHA'],
+         'THETA_INDEL': (th * cji if strict_reference else th) if skip_pvals else S[3],
+         'Pi_SUM': x['P0'], 'Pi_INDEL': x['P_INDEL'], 'EXP_SNV': S[0]}
+    if not skip_pvals:
+        d.update({'PVAL_SNV_BURDEN': S[1], 'PVAL_SAMPLE_BURDEN': S[2], 'EXP_INDEL': S[4], 'PVAL_INDEL_BURDEN': S[5],
+                  'PVAL_MUT_BURDEN': S[6]})
+    return d
 
 
 def run_and_write_quick_cohorts(f_muts, f_pretrained, f_fasta, outdir, prefixes, write_threads=None, **kw):

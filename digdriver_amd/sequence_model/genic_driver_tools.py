@@ -153,12 +153,18 @@ def _read_cohort_frames(args):
     return mapfile.read_columns(f, key, ['CHROM', 'START', 'END', 'Y_PRED', 'STD', 'Y_TRUE', 'FLAG']), mapfile.read_frame(f, 'sequence_model_192')
 
 
+def _usable_cores():
+    """The cores this process may run on: the length of its affinity mask where the platform has one (a process confined to a few
+    cores of a large machine sizes its pools by those), else the machine's count."""
+    import os
+    return len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
+
+
 def _load_cohorts(f_pretrained, key='region_params', workers=1):
     """The maps' region_params as RegionTables + the [C, 192] sequence models.  workers > 1: the C maps are read side by
     side by spawned processes (37 whole-genome maps: 37 x 288 000 rows of HDF5)."""
     files = [f_pretrained] if isinstance(f_pretrained, (str, bytes)) or hasattr(f_pretrained, "__fspath__") else list(f_pretrained)
-    import os
-    workers = min(len(files), os.cpu_count() or 1) if workers is None else int(workers)
+    workers = min(len(files), _usable_cores()) if workers is None else int(workers)
     if workers > 1 and len(files) > 1:
         from concurrent.futures import ThreadPoolExecutor          # (zlib and numpy release the interpreter lock)
         with ThreadPoolExecutor(max_workers=workers) as pool:

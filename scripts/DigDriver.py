@@ -112,9 +112,7 @@ def cmd_quick(args):
 def cmd_quick_cohorts(args):
     """quickCohorts: quickDriver for many cohorts on one bin grid in one pass; per cohort <outdir>/<outpfx>.results.txt."""
     _use_panel_dir(args)
-    n = len(args.mutation_files)
-    if not len(args.maps) == len(args.outpfx) == n:
-        raise SystemExit("ERROR: --mutation-files, --maps and --outpfx must name the same number of cohorts.")
+    n = _cohort_lists(args, manual=False)
     if not (args.f_elts_bed or args.region_str):
         raise SystemExit("ERROR: you must provide --f_elts_bed or --region_str.")
     _scale_mode(args)
@@ -140,9 +138,7 @@ def cmd_element_cohorts(args):
     default PVAL_SNV_BURDEN) only the elements that pass, as <outdir>/<outpfx>.hits.txt, QVAL_* columns included.  With --groups FILE
     also per group of cohorts <outdir>/<group>.meta.results.txt, or under the cut <outdir>/<group>.meta.hits.txt: the members'
     p-values combined per element by Fisher's method (cohort_batch.run_element_meta / run_element_meta_calls)."""
-    n = len(args.mutation_files)
-    if not len(args.maps) == len(args.outpfx) == n:
-        raise SystemExit("ERROR: --mutation-files, --maps and --outpfx must name the same number of cohorts.")
+    n = _cohort_lists(args, manual=False)
     factors = None
     if args.scale_factor_manual or args.scale_factor_indel_manual:
         if not (args.scale_factor_manual and args.scale_factor_indel_manual):
@@ -163,8 +159,7 @@ def cmd_element_cohorts(args):
     common = dict(scale_factors=factors, max_muts_per_sample=args.max_muts_per_sample,
                   max_muts_per_elt_per_sample=args.max_muts_per_elt_per_sample)
     if groups is not None:                        # the cohorts' files and the groups' behind ONE pass over the inputs
-        common['element_pass'] = cohort_batch._element_pass(args.mutation_files, args.maps, args.f_element_data, args.save_key, factors,
-                                                            args.max_muts_per_sample, args.max_muts_per_elt_per_sample)
+        common['element_pass'] = cohort_batch.element_pass(args.mutation_files, args.maps, args.f_element_data, args.save_key, **common)
 
     def meta(**cut_kw):
         # (the groups' files beside the cohorts': <group>.meta.results.txt, or <group>.meta.hits.txt under the same cut)
@@ -186,18 +181,18 @@ def cmd_element_cohorts(args):
             print('\tSaved results to {}'.format(path))
         meta()
         return
-    try:
-        frames, paths = cohort_batch.run_and_write_element_calls(
-            args.mutation_files, args.maps, args.f_element_data, args.save_key, args.outdir, args.outpfx, pval_max=args.pval_max,
-            fdr=args.fdr, cut_on=args.cut_on or 'PVAL_SNV_BURDEN', **common)
-    except ValueError as exc:
-        if 'no indel columns' not in str(exc):
-            raise
-        raise SystemExit("ERROR: {}".format(exc))
+    cut_kw = dict(pval_max=args.pval_max, fdr=args.fdr, cut_on=args.cut_on or 'PVAL_SNV_BURDEN')
+    frames, paths = _without_indel_columns_exit(cohort_batch.run_and_write_element_calls, args.mutation_files, args.maps,
+                                                args.f_element_data, args.save_key, args.outdir, args.outpfx, **cut_kw, **common)
     for pfx, frame, path in zip(args.outpfx, frames, paths):
         print('\t{}: {} hits of {} testable elements; saved to {}'.format(pfx, len(frame), frame.attrs['n_testable'], path))
+    _without_indel_columns_exit(meta, **cut_kw)
+
+
+def _without_indel_columns_exit(run, *args, **kw):
+    """run(*args, **kw); a cut on an indel column that a cohort or a group lacks ends the command with the route's own words."""
     try:
-        meta(pval_max=args.pval_max, fdr=args.fdr, cut_on=args.cut_on or 'PVAL_SNV_BURDEN')
+        return run(*args, **kw)
     except ValueError as exc:
         if 'no indel columns' not in str(exc):
             raise
@@ -232,11 +227,12 @@ def _read_groups(path, prefixes):
     return groups
 
 
-def _cohort_lists(args):
+def _cohort_lists(args, manual=True):
+    """The number of cohorts, the lists checked: one map and one prefix per mutation file and (manual) one --scale-factor-manual."""
     n = len(args.mutation_files)
     if not len(args.maps) == len(args.outpfx) == n:
         raise SystemExit("ERROR: --mutation-files, --maps and --outpfx must name the same number of cohorts.")
-    if args.scale_factor_manual and len(args.scale_factor_manual) != n:
+    if manual and args.scale_factor_manual and len(args.scale_factor_manual) != n:
         raise SystemExit("ERROR: --scale-factor-manual takes one value per cohort.")
     return n
 
@@ -284,9 +280,7 @@ def cmd_tile(args):
     options (--max-muts-per-sample, --max-muts-per-tile-per-sample, --by-sample, --cut-on) read the sample label from column 6 of
     the mutation files; --by-sample adds OBS_SAMPLES and PVAL_SAMPLE behind REGION.  --window-tiles M [M ...] tests every window of M
     consecutive tiles instead (nb_model_window_hits: WIDTH and PEAK behind REGION; not with --sparse, --by-sample, --cut-on PVAL_SAMPLE)."""
-    n = len(args.mutation_files)
-    if not len(args.maps) == len(args.outpfx) == n:
-        raise SystemExit("ERROR: --mutation-files, --maps and --outpfx must name the same number of cohorts.")
+    n = _cohort_lists(args, manual=False)
     if args.window_tiles is not None:
         if args.sparse:
             raise SystemExit("ERROR: --window-tiles is not part of --sparse (the sparse scan tests single tiles).")

@@ -1,5 +1,7 @@
 """The plumbing the many-cohort routes share, without a device and without the library: engine._scan and
-engine._requirements_as_value_errors, data_tools/cohort_rows.py, and cohort_batch._read_models behind the two model readers."""
+engine._requirements_as_value_errors, data_tools/cohort_rows.py, and cohort_batch._read_models behind the two model readers; and, with
+the library's host writer, cohort_batch._check_cut, _write_frames (against the bytes of before: tests/golden/write_frames_golden.json)
+and _usable_cores."""
 import subprocess
 import sys
 
@@ -243,3 +245,69 @@ def test_a_differing_index_gets_the_routes_own_message(in_memory):
     assert str(info.value) == ("c: the element index of its 'mysites' model differs from that of a (run_sites_cohorts needs one element "
                                "index for all maps)")
     assert calls == []                                                                 # refused in front of the element-wise call
+
+
+# ---- the cut's arguments, the writer of finished frames, the cores ------------------------------------------------------------
+def test_the_cut_is_checked_and_its_column_numbered():
+    from digdriver_amd.driver_model import cohort_batch
+    columns = ["PVAL_SNV_BURDEN", "PVAL_SAMPLE_BURDEN", "PVAL_INDEL_BURDEN", "PVAL_MUT_BURDEN"]
+    assert [cohort_batch._check_cut(0.5, None, k) for k in columns] == [0, 1, 2, 3]
+    assert [cohort_batch._check_cut(None, 0.1, k) for k in columns] == [0, 1, 2, 3]
+    for pval_max, fdr in ((None, None), (0.5, 0.1)):
+        with pytest.raises(ValueError) as info:
+            cohort_batch._check_cut(pval_max, fdr, "PVAL_SNV_BURDEN")
+        assert str(info.value) == "exactly one of pval_max and fdr must be given"
+    with pytest.raises(ValueError) as info:
+        cohort_batch._check_cut(0.5, None, "QVAL_SNV_BURDEN")
+    assert str(info.value) == "cut_on: one of " + ", ".join(columns)
+    # the column run_element_meta ranks the members by goes with no cut, and is named in its own words
+    assert cohort_batch._check_cut(None, None, "PVAL_MUT_BURDEN", "best_on") == 3
+    with pytest.raises(ValueError) as info:
+        cohort_batch._check_cut(None, None, "MU", "best_on")
+    assert str(info.value) == "best_on: one of " + ", ".join(columns)
+
+
+def _hand_frames():
+    """Three small result frames: bools, NaN, the extremes of float printing, an int32 column, OBS_* columns (written as integers),
+    another index in the second (the label cache must not serve it), and a quoted element name in the third (pandas writes it)."""
+    a = pd.DataFrame({"FLAG": np.array([True, False, False]), "MU": np.array([0.1, np.nan, 1e-300]), "R_OBS": np.array([3, 0, 12], np.int32),
+                      "OBS_SAMPLES": np.array([2.0, 0.0, 5.0]), "OBS_SNV": np.array([2.0, 0.0, 7.0]),
+                      "PVAL_SNV_BURDEN": np.array([0.25, np.nan, 1.5e-17])}, index=pd.Index(["e1", "e2", "e3"], name="ELT"))
+    b = pd.DataFrame({"MU": np.array([1.0 / 3.0, 2.5]), "OBS_INDEL": np.array([1.0, 0.0]), "N_COHORTS": np.array([3, 3], np.int64)},
+                     index=pd.Index(["e2", "e9"], name="ELT"))
+    c = pd.DataFrame({"MU": np.array([0.5, 1e22]), "OBS_SNV": np.array([4.0, 1.0])}, index=pd.Index(['e"quoted"', "e4"], name="ELT"))
+    return [a, b, c]
+
+
+def test_finished_frames_are_written_with_the_bytes_of_before_at_any_thread_count(tmp_path):
+    import json
+    import os
+    from digdriver_amd.driver_model import cohort_batch
+    golden = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "write_frames_golden.json")
+    want = {k: v.encode("ascii") for k, v in json.load(open(golden)).items()}          # what write_results wrote before _write_frames
+    assert sorted(want) == ["a.results.txt", "b.results.txt", "c.results.txt"] and b'"e""quoted"""' in want["c.results.txt"]
+    names = ["a", "b", "c"]
+    for threads in (1, 4):
+        out = tmp_path / ("threads%d" % threads) / "nested"
+        paths = cohort_batch._write_frames(_hand_frames(), [str(out / (n + ".results.txt")) for n in names], threads)
+        assert [os.path.basename(p) for p in paths] == sorted(want)
+        for p in paths:
+            assert open(p, "rb").read() == want[os.path.basename(p)], (threads, p)
+    for workers in (None, 1, 2):
+        paths = cohort_batch.write_results(_hand_frames(), str(tmp_path / ("workers%s" % workers)), names, workers=workers)
+        assert [open(p, "rb").read() for p in paths] == [want[n + ".results.txt"] for n in names]
+    assert cohort_batch._write_frames([], []) == [] and cohort_batch.write_results([], str(tmp_path / "none"), []) == []
+
+
+def test_usable_cores_follow_the_affinity_mask():
+    import os
+    from digdriver_amd.driver_model import cohort_batch
+    from digdriver_amd.sequence_model import genic_driver_tools
+    n = cohort_batch._usable_cores()
+    assert type(n) is int and 1 <= n <= os.cpu_count()
+    if hasattr(os, "sched_getaffinity"):
+        assert n == len(os.sched_getaffinity(0))
+    assert genic_driver_tools._usable_cores is cohort_batch._usable_cores           # (the maps' reader sizes its pool by the same)
+    files, per_file = cohort_batch._writer_threads(3)
+    assert files == min(3, n) and per_file == max(1, min(8, n // 3)) and cohort_batch._writer_threads(3, 2) == (files, 2)
+    assert cohort_batch._writer_threads(0) == (1, min(8, n)) and cohort_batch._writer_threads(10 ** 6) == (n, 1)
