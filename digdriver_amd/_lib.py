@@ -125,6 +125,10 @@ _SIGNATURES = {
     "dig_tile_sample_counts_host": [_vp] + [_i64] * 6 + [_vp, _vp, _int],
     "dig_tile_window_test": [_vp] * 5 + [_i64] * 3 + [_int] + [_vp] * 5 + [_vp],
     "dig_tile_window_test_host": [_vp] * 5 + [_i64] * 3 + [_int] + [_vp] * 5 + [_int],
+    "dig_tile_window_sample_keys": [_vp] + [_i64] * 5 + [_vp, _vp],
+    "dig_tile_window_sample_keys_host": [_vp] + [_i64] * 5 + [_vp, _int],
+    "dig_tile_window_samples": [_vp, _i64, _vp] + [_i64] * 4 + [_int, _vp, _vp],
+    "dig_tile_window_samples_host": [_vp, _i64, _vp] + [_i64] * 4 + [_int, _vp, _int],
     "dig_tile_census": [_vp, _i64, _vp, _vp, _int, _vp, _vp, _vp, _i64, _vp, _i64, _int, _int, _i64] + [_vp] * 4 + [_vp, _i64, _vp],
     "dig_tile_census_host": [_vp, _i64, _vp, _vp, _int, _vp, _vp, _vp, _i64, _vp, _i64, _int, _int, _i64] + [_vp] * 4 + [_int],
     "dig_sparse_tile_keys": [_vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _int] + [_i64] * 3 + [_vp, _vp],

@@ -1056,6 +1056,34 @@ int dig_tile_window_test_host(const double* pt, const int32_t* k, const double* 
                    pval_w ? st.out(pval_w, n) : nullptr, n_windows ? st.out(n_windows, R) : nullptr, nullptr);
 }
 
+int dig_tile_window_sample_keys_host(const int64_t* keys, int64_t n, int64_t C, int64_t R, int64_t T, int64_t n_samples,
+                                     int64_t* keys_out, int device)
+{
+    DIG_REQUIRE(n >= 0, "n >= 0");
+    int sb = 0;
+    if (int rc = tile_sample_key_layout(__func__, C, R, T, n_samples, &sb)) return rc;
+    if (n == 0) return DIG_OK;
+    DIG_REQUIRE(keys && keys_out, "non-null keys, keys_out");
+    Staging st(device);
+    return st.call(dig_tile_window_sample_keys, st.in(keys, n), n, C, R, T, n_samples, st.out(keys_out, n), nullptr);
+}
+
+int dig_tile_window_samples_host(const int64_t* keys_sorted, int64_t n, const int32_t* n_valid, int64_t C, int64_t R, int64_t T,
+                                 int64_t n_samples, int32_t width, int32_t* s_w, int device)
+{
+    if (int rc = tile_window_sizes(__func__, C, R, T, width)) return rc;
+    DIG_REQUIRE(n >= 0 && n <= INT32_MAX, "0 <= n < 2^31 (the counts are 32-bit)");
+    int sb = 0;
+    if (int rc = tile_sample_key_layout(__func__, C, R, T, n_samples, &sb)) return rc;
+    const size_t slots = (size_t)C * R * T;
+    if (slots == 0) return DIG_OK;
+    DIG_REQUIRE(s_w && n_valid && (n == 0 || keys_sorted), "non-null s_w, n_valid, keys");
+    if (int rc = check_ascending(__func__, keys_sorted, n)) return rc;
+    Staging st(device);
+    return st.call(dig_tile_window_samples, st.in(keys_sorted, n), n, st.in(n_valid, R), C, R, T, n_samples, width, st.out(s_w, slots),
+                   nullptr);
+}
+
 int dig_tile_census_host(const uint32_t* genome_words, int64_t n_words, const int64_t* chrom_off, const int64_t* chrom_len, int n_chrom,
                          const int32_t* reg_chrom, const int64_t* reg_start, const int64_t* reg_end, int64_t R, const double* s_prob,
                          int64_t C, int n_up, int binsize, int64_t n_tiles, int64_t* first_pos, int32_t* n_valid, double* denom,

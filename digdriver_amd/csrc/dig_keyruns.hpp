@@ -1,4 +1,4 @@
-// dig_keyruns.hpp -- what the counting routes (dig_genecounts.hip, dig_objectives.hip, dig_panelcounts.hip, dig_seqcounts.hip, dig_sitematch.hip, dig_tilehits.hip, dig_rowhits.hip, dig_tilesamples.hip, dig_tilesparse.hip, dig_tilewindows.hip, dig_cnvwindows.hip) and their host twins share:
+// dig_keyruns.hpp -- what the counting routes (dig_genecounts.hip, dig_objectives.hip, dig_panelcounts.hip, dig_seqcounts.hip, dig_sitematch.hip, dig_tilehits.hip, dig_rowhits.hip, dig_tilesamples.hip, dig_tilesparse.hip, dig_tilewindows.hip, dig_tilewindowsamples.hip, dig_cnvwindows.hip) and their host twins share:
 // rows encoded as 63-bit keys, sorted by the caller, counted as runs with one integer atomic per wave segment.
 #pragma once
 #include "dig_common.hpp"

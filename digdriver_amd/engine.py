@@ -1296,14 +1296,15 @@ def _tile_pairs(be, genome, chroms, starts, ends, mut_chrom, mut_start, mut_end)
 
 
 def tile_sample_counts(genome, chroms, starts, ends, first_pos, n_valid, mut_chrom, mut_start, mut_end, mut_cohort, mut_sample,
-                       sample_offsets, keep, cap, C, binsize, n_tiles):
+                       sample_offsets, keep, cap, C, binsize, n_tiles, return_keys=False):
     """(k_cap, k_samples) i32 [C, R, n_tiles]: tile_mut_counts by sample -- with n the rows of one sample that tile_mut_counts counts
     in a tile, k_cap = the sum over the kept samples of min(n, cap) and k_samples = the kept samples with n > 0: the same join,
     dig_tile_sample_keys, a key sort, dig_tile_sample_counts.  mut_sample i32: the row's GLOBAL sample, inside its cohort's range of
     sample_offsets [C + 1] (a cohort's first global sample; equal labels in two cohorts are two samples); keep u8 per global sample
     or None: a sample with keep == 0 counts nowhere; cap: an integer >= 1, or None for no cap.  Everything else, and the choice of
     the backend, as tile_mut_counts.  ValueError for a row whose sample is outside its cohort and for a key (cohort, region, tile,
-    sample) that does not fit 63 bits."""
+    sample) that does not fit 63 bits.  return_keys: (k_cap, k_samples, keys) -- the sorted keys of dig_tile_sample_keys, i64, one
+    per pair of the join, for tile_window_sample_keys: the join and the key kernel then run once."""
     be = backend_of(first_pos, n_valid)
     C, T = int(C), int(n_tiles)
     off_host, _, S = _sample_offsets(sample_offsets, C)
@@ -1331,7 +1332,7 @@ def tile_sample_counts(genome, chroms, starts, ends, first_pos, n_valid, mut_chr
                 int(binsize), T, R, C, S, p(keys))
         keys = _sorted(be, keys)
         be.call("dig_tile_sample_counts", p(keys), n, C, R, T, S, 0 if cap is None else int(cap), p(k_cap), p(k_samples))
-    return k_cap, k_samples
+    return (k_cap, k_samples, keys) if return_keys else (k_cap, k_samples)
 
 
 def tiled_nb_model(genome, chroms, starts, ends, s_prob, mu, sigma, mut_chrom, mut_start, mut_end, mut_cohort, binsize=50,
@@ -1389,6 +1390,40 @@ def tile_window_test(pt, k, mu, sigma, n_valid, width, device=0, out=None):
         # (nothing was launched: the region table from n_valid alone)
         nv = n_valid.clip(0, T)
         out["n_windows"][:] = (nv > 0) * (nv - width + 1).clip(1)
+    return out
+
+
+def tile_window_sample_keys(keys, C, R, T, n_samples, device=0):
+    """The keys of tile_sample_counts(return_keys=True), ((row T + tile) << sb) | sample, re-keyed sample-major (((row << sb) | sample)
+    T + tile: dig_tile_window_sample_keys) and sorted ascending: what tile_window_samples takes, once for every width.  i64 [n]; a
+    device tensor in -> a device tensor out, an array goes through the host twin.  ValueError for what the library refuses."""
+    be = backend_of(keys, device=device)
+    keys = be.arr(keys, "i64", (-1,))
+    out = be.empty(keys.shape[0], "i64")
+    p = be.ptr
+    with _requirements_as_value_errors():
+        be.call("dig_tile_window_sample_keys", p(keys), keys.shape[0], int(C), int(R), int(T), int(n_samples), p(out))
+    return _sorted(be, out)
+
+
+def tile_window_samples(keys_sm, n_valid, C, R, T, n_samples, width, device=0, out=None):
+    """s_w i32 [C, R, T]: the distinct kept samples with a counted row in window t of `width` consecutive tiles
+    (dig_tile_window_samples), 0 behind the last window; the windows are those of tile_window_test.  keys_sm: what
+    tile_window_sample_keys returns; n_valid i32 [R] as base_tile_probs leaves it.  Device tensors in -> a device tensor out; arrays go
+    through the host twin.  out: a plane a former call returned, for the same shape: it is written again.  ValueError for what the
+    library refuses: a width outside [1, TILE_WINDOW_MAX_WIDTH], C R, T or the key count at or above 2^31, a key that does not fit."""
+    if isinstance(width, bool) or int(width) != width:
+        raise ValueError("width: an integer >= 1")
+    C, R, T = int(C), int(R), int(T)
+    be = backend_of(keys_sm, n_valid, device=device)
+    keys_sm, n_valid = be.arr(keys_sm, "i64", (-1,)), be.arr(n_valid, "i32", (R,))
+    if out is None:
+        out = be.empty((C, R, T), "i32")
+    elif tuple(out.shape) != (C, R, T):
+        raise ValueError("out must be [C, R, T]")
+    p = be.ptr
+    with _requirements_as_value_errors():
+        be.call("dig_tile_window_samples", p(keys_sm), keys_sm.shape[0], p(n_valid), C, R, T, int(n_samples), int(width), p(out))
     return out
 
 

@@ -388,6 +388,7 @@ def nb_model_hits(d_prs, idx, mu, sigma, f_muts, f_fasta, n_up=2, n_down=2, bins
 # sliding windows of consecutive tiles (DESIGN.md "Sliding windows in the per-base route")
 # ---------------------------------------------------------------------------------------------
 _WINDOW_COLUMNS = ["WIDTH", "PEAK"]                    # behind the reference's columns, in front of QVAL
+_SAMPLE_WINDOW_PLANES = ("k_samples", "pval_sample")   # what window_samples gathers at the hits: OBS_SAMPLES, PVAL_SAMPLE, in front of WIDTH
 
 
 def _check_widths(widths):
@@ -424,7 +425,8 @@ def window_peaks(region, tile, score, width):
 
 
 def nb_model_window_hits(d_prs, idx, mu, sigma, f_muts, f_fasta, n_up=2, n_down=2, binsize=50, widths=(2,), collapse=False, pval_max=None,
-                         fdr=None, device=0, max_muts_per_sample=None, max_muts_per_tile_per_sample=None, by_sample=False, cut_on="PVAL"):
+                         fdr=None, device=0, max_muts_per_sample=None, max_muts_per_tile_per_sample=None, by_sample=False, cut_on="PVAL",
+                         window_samples=False):
     """nb_model_hits over every window of m consecutive tiles, for each m of `widths`: "any m binsize consecutive positions of a
     region" instead of the tiles of one grid.  One base_tile_probs and one counting pass (tile_mut_counts, or tile_sample_counts with
     max_muts_per_sample / max_muts_per_tile_per_sample: OBS is then the capped count) over all cohorts; the base test is not run.  Per
@@ -436,20 +438,29 @@ def nb_model_window_hits(d_prs, idx, mu, sigma, f_muts, f_fasta, n_up=2, n_down=
     lo + 1), PEAK (window_peaks per cohort, width and region), and QVAL with fdr: Benjamini-Hochberg per cohort and PER WIDTH over that
     width's testable windows.  The index is the row number in the full frame of that width (the exclusive cumulative sum of n_windows,
     plus t); attrs n_testable and n_windows hold one entry per width.
-    ValueError before any device work: by_sample or cut_on other than PVAL (the distinct samples of a window are not the sum of
-    its tiles'), an empty widths, a width that is not an integer >= 1 or above engine.TILE_WINDOW_MAX_WIDTH, a width given twice."""
+    window_samples (DESIGN.md "Samples in sliding windows"; the sample label is read from column 6, as by the other sample options):
+    the keys of the counting pass are kept, re-keyed sample-major and sorted once; per width engine.tile_window_samples counts the
+    DISTINCT kept samples with a counted row in the window (one sample with rows in ten tiles of a window is one sample) into one
+    reused plane, and engine.tiled_nb_test runs on (the window's Pi, that count).  The frames gain OBS_SAMPLES and PVAL_SAMPLE
+    behind REGION, in front of WIDTH.  cut_on="PVAL_SAMPLE" (only with window_samples) selects on that score: the testable windows,
+    Benjamini-Hochberg, QVAL, n_testable and PEAK then belong to it.  OBS stays the (capped) row count.
+    ValueError before any device work: by_sample, or cut_on other than PVAL without window_samples (the distinct samples of a window
+    are not the sum of its tiles'; window_samples counts them), an empty widths, a width that is not an integer >= 1 or above
+    engine.TILE_WINDOW_MAX_WIDTH, a width given twice."""
     if (pval_max is None) == (fdr is None):
         raise ValueError("exactly one of pval_max and fdr must be given")
-    if by_sample or cut_on != "PVAL":
+    if by_sample or (cut_on != "PVAL" and not window_samples):
         raise ValueError("windows take no by_sample and no cut_on other than PVAL: the distinct samples of a window are not the sum "
-                         "of its tiles' samples")
+                         "of its tiles' samples (window_samples=True counts them and takes cut_on PVAL_SAMPLE)")
+    if cut_on not in ("PVAL", "PVAL_SAMPLE"):
+        raise ValueError("cut_on: PVAL or PVAL_SAMPLE")
     widths = _check_widths(widths)
     from .. import engine
     if max(widths) > engine.TILE_WINDOW_MAX_WIDTH:
         raise ValueError("widths: at most %d tiles" % engine.TILE_WINDOW_MAX_WIDTH)
     if n_up != n_down or n_up not in (1, 2):
         raise NotImplementedError("the tile kernels take n_up = n_down = 1 or 2")
-    samples = _check_sample_options(max_muts_per_sample, max_muts_per_tile_per_sample, False)
+    samples = _check_sample_options(max_muts_per_sample, max_muts_per_tile_per_sample, False) or bool(window_samples)
     import pandas as pd
     from ..data_tools import cohort_rows, genome as genome_mod
     C = len(d_prs)
@@ -472,42 +483,60 @@ def nb_model_window_hits(d_prs, idx, mu, sigma, f_muts, f_fasta, n_up=2, n_down=
     T = int(pt.shape[2])
     if samples:
         sa = _sample_arguments(rows, max_muts_per_tile_per_sample, False)
-        k, _ = engine.tile_sample_counts(g, chroms, starts, ends, first_d, nval_d, mc, ms, me, co, sa["mut_sample"], sa["sample_offsets"],
-                                         sa["keep"], sa["cap"], C, binsize, T)
+        k, _, keys = engine.tile_sample_counts(g, chroms, starts, ends, first_d, nval_d, mc, ms, me, co, sa["mut_sample"],
+                                               sa["sample_offsets"], sa["keep"], sa["cap"], C, binsize, T, return_keys=True)
+        if window_samples:
+            n_samples = int(sa["sample_offsets"][-1])
+            keys = engine.tile_window_sample_keys(keys, C, R, T, n_samples)        # sample-major, sorted: once for every width
     else:
         k = engine.tile_mut_counts(g, chroms, starts, ends, first_d, nval_d, mc, ms, me, co, C, binsize, T)
     first, nval = first_d.cpu().numpy(), np.clip(nval_d.cpu().numpy().astype(np.int64), 0, T)
     n_pos = _region_positions(g, chroms, ends, first, n_up) if R else np.zeros(0, np.int64)
     last = first + n_pos                                       # one past a region's last position
-    planes = None
+    planes = s_w = None
     per_width = []                                             # (m, hits as host arrays, cohort_ptr, n_testable [C], n_windows [R])
     for m in widths:
         planes = engine.tile_window_test(pt, k, mu, sigma, nval_d, m, device=device, out=planes)
         nwin_d = planes["n_windows"]
+        score = planes["pval"]
+        if window_samples:
+            s_w = engine.tile_window_samples(keys, nval_d, C, R, T, n_samples, m, device=device, out=s_w)
+            pval_s = engine.tiled_nb_test(planes["pt"], s_w, mu, sigma, device=device)[0]
+            score = pval_s if cut_on == "PVAL_SAMPLE" else score
         if fdr is not None:
-            cuts, n_test = _fdr_cuts(planes["pval"], nwin_d, fdr)
+            cuts, n_test = _fdr_cuts(score, nwin_d, fdr)
         else:
             cuts = np.full(C, float(pval_max))
-            n_test = engine.tile_select_counts(planes["pval"], nwin_d, float("inf")).sum(dim=1).cpu().numpy()
-        hits = engine.tile_select(planes["pval"], nwin_d, cuts, pt=planes["pt"], exp=planes["exp"], k=planes["k"])
+            n_test = engine.tile_select_counts(score, nwin_d, float("inf")).sum(dim=1).cpu().numpy()
+        hits = engine.tile_select(score, nwin_d, cuts, pt=planes["pt"], exp=planes["exp"], k=planes["k"])
         ptr = hits.pop("cohort_ptr")
+        if window_samples:
+            # the planes tile_select does not gather, taken at the hits' (cohort, region, tile), as nb_model_hits does
+            import torch
+            at = (torch.as_tensor(np.repeat(np.arange(C), np.diff(ptr)), device=score.device), hits["region"].long(), hits["tile"].long())
+            hits.update(pval=planes["pval"][at], k_samples=s_w[at], pval_sample=pval_s[at])
         per_width.append((m, {name: v.cpu().numpy() for name, v in hits.items()}, ptr, np.asarray(n_test), nwin_d.cpu().numpy().astype(np.int64)))
     frames = []
     for c in range(C):
-        cols = {name: [] for name in ("reg", "t", "k", "exp", "pval", "pt", "lo", "hi", "peak", "q", "row")}
+        cols = {name: [] for name in ("reg", "t", "k", "exp", "pval", "pt", "lo", "hi", "peak", "q", "row", "k_samples", "pval_sample")}
         for m, hits, ptr, n_test, nwin in per_width:
             sel = slice(int(ptr[c]), int(ptr[c + 1]))
             reg, t, score = hits["region"][sel].astype(np.int64), hits["tile"][sel].astype(np.int64), hits["score"][sel]
             lo = first[reg] + t * binsize
             hi = np.minimum(lo + np.minimum(m, nval[reg] - t) * binsize, last[reg]) - 1
             cols["reg"].append(reg), cols["t"].append(t), cols["lo"].append(lo), cols["hi"].append(hi)
-            cols["k"].append(hits["k"][sel]), cols["exp"].append(hits["exp"][sel]), cols["pval"].append(score), cols["pt"].append(hits["pt"][sel])
+            cols["k"].append(hits["k"][sel]), cols["exp"].append(hits["exp"][sel]), cols["pt"].append(hits["pt"][sel])
+            cols["pval"].append(hits["pval"][sel] if window_samples else score)      # (without window_samples the score is PVAL)
+            for name in _SAMPLE_WINDOW_PLANES if window_samples else ():
+                cols[name].append(hits[name][sel])
             cols["peak"].append(window_peaks(reg, t, score, m))
             cols["q"].append(hits_q_values(score, int(n_test[c])) if fdr is not None else score)
             cols["row"].append((np.cumsum(nwin) - nwin)[reg] + t)
-        cat = {name: np.concatenate(v) for name, v in cols.items()}
+        cat = {name: np.concatenate(v) for name, v in cols.items() if v}
         df = _tile_frame(idx, mu[c], sigma[c], first, n_pos, binsize, cat["reg"], cat["t"], cat["k"], cat["exp"], cat["pval"], cat["pt"])
         df["POS"] = (cat["lo"] + cat["hi"]) / 2.0
+        if window_samples:
+            df["OBS_SAMPLES"], df["PVAL_SAMPLE"] = cat["k_samples"].astype(float), cat["pval_sample"]
         df["WIDTH"], df["PEAK"] = (cat["hi"] - cat["lo"] + 1).astype(float), cat["peak"].astype(bool)
         if fdr is not None:
             df["QVAL"] = cat["q"]

@@ -43,6 +43,7 @@ extern "C" {
                              * dig_panel_counts and their _host twins (additions); + dig_tile_sample_keys, dig_tile_sample_counts and
                              * their _host twins (additions); + dig_tile_census(_workspace), dig_sparse_tile_keys, dig_sparse_tile_test
                              * and their _host twins (additions); + dig_tile_window_test and its _host twin (additions);
+                             * + dig_tile_window_sample_keys, dig_tile_window_samples and their _host twins (additions);
                              * + dig_cnv_segment_deltas, dig_cnv_window_means, their size queries and _host twins (additions) */
 
 /* dtype codes for dig_gather_bins */
@@ -694,6 +695,38 @@ int dig_tile_window_test(const double *pt, const int32_t *k, const double *mu, c
 int dig_tile_window_test_host(const double *pt, const int32_t *k, const double *mu, const double *sigma, const int32_t *n_valid,
                               int64_t C, int64_t R, int64_t T, int32_t width, double *pt_w, int32_t *k_w, double *exp_w,
                               double *pval_w, int32_t *n_windows, int device);
+
+/* ---- the distinct samples of sliding windows (additive: the ABI version stays) -------------------------------------- *
+ * The samples of a window are not the sum of its tiles' samples: one sample with rows in several tiles of a window is one sample.
+ * With n(c, r, t, s) the rows of global sample s that dig_tile_sample_keys counts in tile (c, r, t) -- the same skip rules, the same
+ * keep -- and n_windows, "window t covers the tiles t .. min(t + width, nv) - 1", nv = min(n_valid[r], T) as dig_tile_window_test
+ * defines them:
+ *   s_w[c, r, t] = the samples s with n(c, r, u, s) > 0 for a tile u of window t      for t < n_windows[r], else 0.
+ * The NB test of dig_tiled_nb_test on (pt_w, s_w, mu, sigma) is the window's PVAL_SAMPLE; width 1 gives k_samples of
+ * dig_tile_sample_counts.
+ *   dig_tile_window_sample_keys: the keys of dig_tile_sample_keys, ((row T + tile) << sb) | sample with row = cohort R + region and sb
+ *     the bits that hold 0 .. n_samples, re-keyed sample-major: keys_out[i] = ((row << sb) | sample) T + tile, which fits 63 bits
+ *     whenever the old key does.  A negative key, INT64_MAX and a key of a tile outside [0, C R T) become INT64_MAX.  keys i64 [n],
+ *     sorted or not; keys_out i64 [n] may be keys.  One lane per key.
+ *   The caller sorts keys_out ascending: the tiles of one sample in one row then lie next to each other, ascending.
+ *   dig_tile_window_samples: s_w i32 [C, R, T] is zeroed; the head of every run of equal keys adds +1 at the first window in which its
+ *     tile is the sample's first one, max(t_prev + 1, t - width + 1, 0) with t_prev the sample's previous tile in the row (the left
+ *     neighbour of the head in keys_sorted, when it is of the same row and sample; else -1), and -1 one past the last such window,
+ *     min(t + 1, n_windows[r]) (when that is below T); an in-place prefix sum along every row then gives the counts.  Two integer
+ *     atomics per (tile, sample), however many rows it has; order-independent.  Keys that are negative, INT64_MAX, of a row >= C R or
+ *     of a tile >= nv are passed over and never dereference anything.  n_valid i32 [R].
+ * DIG_EINVAL, before anything is read or launched, for a width outside [1, DIG_TILE_WINDOW_MAX_WIDTH], C R >= 2^31, T >= 2^31,
+ * n >= 2^31, C, R, T or n_samples at or above 2^31 and key fields that do not fit 63 bits.  Nothing is launched or written when
+ * C R T = 0.  Every typed pointer needs the alignment of its element and no more.  The host twin of dig_tile_window_samples refuses
+ * keys that are not ascending. */
+int dig_tile_window_sample_keys(const int64_t *keys, int64_t n, int64_t C, int64_t R, int64_t T, int64_t n_samples, int64_t *keys_out,
+                                void *stream);
+int dig_tile_window_sample_keys_host(const int64_t *keys, int64_t n, int64_t C, int64_t R, int64_t T, int64_t n_samples,
+                                     int64_t *keys_out, int device);
+int dig_tile_window_samples(const int64_t *keys_sorted, int64_t n, const int32_t *n_valid, int64_t C, int64_t R, int64_t T,
+                            int64_t n_samples, int32_t width, int32_t *s_w, void *stream);
+int dig_tile_window_samples_host(const int64_t *keys_sorted, int64_t n, const int32_t *n_valid, int64_t C, int64_t R, int64_t T,
+                                 int64_t n_samples, int32_t width, int32_t *s_w, int device);
 
 /* ---- sufficient statistics in canonical chunks (bin-sharded runs) --------------------------- *
  * Same quantity as dig_scale_suffstats / dig_scale_factors, defined so that it does not depend on the sharding: the bins

@@ -279,15 +279,21 @@ def cmd_tile(args):
     the mutated tiles only (nb_model_hits_sparse; --bonferroni is its third cut, the sample options are not part of it).  The sample
     options (--max-muts-per-sample, --max-muts-per-tile-per-sample, --by-sample, --cut-on) read the sample label from column 6 of
     the mutation files; --by-sample adds OBS_SAMPLES and PVAL_SAMPLE behind REGION.  --window-tiles M [M ...] tests every window of M
-    consecutive tiles instead (nb_model_window_hits: WIDTH and PEAK behind REGION; not with --sparse, --by-sample, --cut-on PVAL_SAMPLE)."""
+    consecutive tiles instead (nb_model_window_hits: WIDTH and PEAK behind REGION; not with --sparse, --by-sample, --cut-on PVAL_SAMPLE).
+    --window-samples (with --window-tiles) counts the distinct samples of every window: OBS_SAMPLES and PVAL_SAMPLE behind REGION, and
+    --cut-on PVAL_SAMPLE selects on them."""
     n = _cohort_lists(args, manual=False)
+    if args.window_samples and args.window_tiles is None:
+        raise SystemExit("ERROR: --window-samples needs --window-tiles (the tiles' own samples: --by-sample).")
     if args.window_tiles is not None:
         if args.sparse:
             raise SystemExit("ERROR: --window-tiles is not part of --sparse (the sparse scan tests single tiles).")
         if args.by_sample:
-            raise SystemExit("ERROR: --window-tiles does not take --by-sample (the samples of a window are not the sum of its tiles' samples).")
-        if args.cut_on != 'PVAL':
-            raise SystemExit("ERROR: --window-tiles selects on PVAL only (--cut-on PVAL_SAMPLE needs --by-sample, which it does not take).")
+            raise SystemExit("ERROR: --window-tiles does not take --by-sample (the samples of a window are not the sum of its tiles' samples); "
+                             "--window-samples counts a window's distinct samples.")
+        if args.cut_on != 'PVAL' and not args.window_samples:
+            raise SystemExit("ERROR: --window-tiles selects on PVAL only (--cut-on PVAL_SAMPLE needs --by-sample, which it does not take); "
+                             "with --window-samples it selects on the windows' PVAL_SAMPLE.")
         if min(args.window_tiles) < 1 or len(set(args.window_tiles)) != len(args.window_tiles):
             raise SystemExit("ERROR: --window-tiles takes distinct integers >= 1.")
     if args.bonferroni is not None and not args.sparse:
@@ -302,7 +308,7 @@ def cmd_tile(args):
                              "--by-sample, --cut-on).")
     elif (args.pval_max is None) == (args.fdr is None):
         raise SystemExit("ERROR: you must provide exactly one of --pval-max and --fdr.")
-    if args.cut_on == 'PVAL_SAMPLE' and not args.by_sample:
+    if args.cut_on == 'PVAL_SAMPLE' and not (args.by_sample or args.window_samples):
         raise SystemExit("ERROR: --cut-on PVAL_SAMPLE requires --by-sample.")
     if args.max_muts_per_tile_per_sample is not None and args.max_muts_per_tile_per_sample < 1:
         raise SystemExit("ERROR: --max-muts-per-tile-per-sample takes an integer >= 1.")
@@ -334,9 +340,12 @@ def cmd_tile(args):
     if not keep.any():
         raise SystemExit("ERROR: no region of region_params is left to scan.")
     # (the sample options are passed only when one is set: without them the call is the one of before)
-    sample_opts = {} if (args.max_muts_per_sample is None and args.max_muts_per_tile_per_sample is None and not args.by_sample) else dict(
+    sample_opts = {} if (args.max_muts_per_sample is None and args.max_muts_per_tile_per_sample is None and not args.by_sample
+                         and not args.window_samples) else dict(
         max_muts_per_sample=args.max_muts_per_sample, max_muts_per_tile_per_sample=args.max_muts_per_tile_per_sample,
         by_sample=args.by_sample, cut_on=args.cut_on)
+    if args.window_samples:
+        sample_opts['window_samples'] = True
     if args.sparse:
         try:
             frames = nb_model.nb_model_hits_sparse(d_prs, idx[keep], np.array(mu)[:, keep], np.array(sigma)[:, keep], args.mutation_files,
@@ -471,6 +480,9 @@ def parse_args(text=None):
     # every run of M consecutive tiles instead of the tiles of one grid (DESIGN.md "Sliding windows in the per-base route")
     d.add_argument('--window-tiles', type=int, nargs='+', default=None, metavar='M',
                    help='test every window of M consecutive tiles, for each M given (adds WIDTH and PEAK; not with --sparse, --by-sample)')
+    d.add_argument('--window-samples', action='store_true', default=False,
+                   help="with --window-tiles: count every window's distinct samples (adds OBS_SAMPLES and PVAL_SAMPLE; --cut-on PVAL_SAMPLE "
+                        "then selects on them)")
     d.set_defaults(func=cmd_tile)
 
     # not a reference sub-command: quickDriver for many cohorts at once (driver_model/cohort_batch.py run_quick_cohorts)
