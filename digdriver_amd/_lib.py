@@ -135,6 +135,12 @@ _SIGNATURES = {
     "dig_sparse_tile_keys_host": [_vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _int] + [_i64] * 3 + [_vp, _int],
     "dig_sparse_tile_test": [_vp, _i64, _vp, _vp, _int, _vp, _vp, _vp, _i64, _vp, _i64, _int, _int, _i64] + [_vp] * 4 + [_i64] + [_vp] * 7 + [_vp],
     "dig_sparse_tile_test_host": [_vp, _i64, _vp, _vp, _int, _vp, _vp, _vp, _i64, _vp, _i64, _int, _int, _i64] + [_vp] * 4 + [_i64] + [_vp] * 7 + [_int],
+    "dig_tile_window_census": [_vp, _i64, _vp, _vp, _int, _vp, _vp, _vp, _i64, _vp, _i64, _int, _int, _i64] + [_int] + [_vp] * 3 + [_vp, _i64, _vp],
+    "dig_tile_window_census_host": [_vp, _i64, _vp, _vp, _int, _vp, _vp, _vp, _i64, _vp, _i64, _int, _int, _i64] + [_int] + [_vp] * 3 + [_int],
+    "dig_sparse_window_count": [_vp, _i64, _vp] + [_i64] * 3 + [_int, _vp, _vp],
+    "dig_sparse_window_count_host": [_vp, _i64, _vp] + [_i64] * 3 + [_int, _vp, _int],
+    "dig_sparse_window_test": [_vp, _i64, _vp, _vp, _int, _vp, _vp, _vp, _i64, _vp, _i64, _int, _int, _i64] + [_vp] * 4 + [_i64, _vp, _int, _i64, _i64] + [_vp] * 7 + [_vp],
+    "dig_sparse_window_test_host": [_vp, _i64, _vp, _vp, _int, _vp, _vp, _vp, _i64, _vp, _i64, _int, _int, _i64] + [_vp] * 4 + [_i64, _vp, _int, _i64, _i64] + [_vp] * 7 + [_int],
     "dig_gene_pipeline": [_vp] * 15 + [_int] + [_vp] * 9 + [_i64, _i64, _i64, _vp, _i64, _vp],
     "dig_gene_pipeline_host": [_vp] * 15 + [_int] + [_vp] * 9 + [_i64, _i64, _i64, _int],
     "dig_count_contexts": [_vp, _i64, _vp, _vp, _int, _vp, _vp, _vp, _vp, _i64, _vp, _vp],

@@ -1145,6 +1145,68 @@ int dig_sparse_tile_test_host(const uint32_t* genome_words, int64_t n_words, con
                             st.out(out_pt, n), st.out(out_exp, n), st.out(out_pval, n), nullptr);
 }
 
+int dig_tile_window_census_host(const uint32_t* genome_words, int64_t n_words, const int64_t* chrom_off, const int64_t* chrom_len,
+                                int n_chrom, const int32_t* reg_chrom, const int64_t* reg_start, const int64_t* reg_end, int64_t R,
+                                const double* s_prob, int64_t C, int n_up, int binsize, int64_t n_tiles, int32_t width,
+                                const int32_t* n_positive, int32_t* n_windows, int32_t* n_positive_w, int device)
+{
+    const TileArgs a{{genome_words, n_words, chrom_off, chrom_len, n_chrom, reg_chrom, reg_start, reg_end, R}, s_prob, C, n_up, binsize,
+                     n_tiles, nullptr, nullptr, nullptr, nullptr};
+    if (int rc = check_tile_tables_host(__func__, a, false)) return rc;
+    int64_t slots = 0;
+    if (int rc = sparse_window_sizes(__func__, C, R, n_tiles, width, &slots)) return rc;
+    if (R == 0) return DIG_OK;
+    DIG_REQUIRE(n_windows, "non-null n_windows");
+    DIG_REQUIRE(C == 0 || (s_prob && n_positive_w), "non-null s_prob, n_positive_w");
+    const size_t rows = (size_t)C * R;
+    const int64_t wsb = tile_census_workspace_bytes(C, n_up);
+    Staging st(device);
+    return call_tile_genome(st, dig_tile_window_census, a, n_up, binsize, n_tiles, width, st.in(n_positive, rows), st.out(n_windows, R),
+                            C ? st.out(n_positive_w, rows) : nullptr, st.scratch(wsb), wsb, nullptr);
+}
+
+int dig_sparse_window_count_host(const int64_t* keys_sorted, int64_t n, const int32_t* n_valid, int64_t C, int64_t R, int64_t T,
+                                 int32_t width, int64_t* counts, int device)
+{
+    DIG_REQUIRE(n >= 0, "n >= 0");
+    int64_t slots = 0;
+    if (int rc = sparse_window_sizes(__func__, C, R, T, width, &slots)) return rc;
+    if (n == 0) return DIG_OK;
+    DIG_REQUIRE(keys_sorted && counts, "non-null keys, counts");
+    DIG_REQUIRE(slots == 0 || n_valid, "non-null n_valid");
+    if (int rc = check_ascending(__func__, keys_sorted, n)) return rc;
+    Staging st(device);
+    return st.call(dig_sparse_window_count, st.in(keys_sorted, n), n, st.in(n_valid, R), C, R, T, width, st.out(counts, n), nullptr);
+}
+
+int dig_sparse_window_test_host(const uint32_t* genome_words, int64_t n_words, const int64_t* chrom_off, const int64_t* chrom_len,
+                                int n_chrom, const int32_t* reg_chrom, const int64_t* reg_start, const int64_t* reg_end, int64_t R,
+                                const double* s_prob, int64_t C, int n_up, int binsize, int64_t n_tiles, const double* denom,
+                                const double* mu, const double* sigma, const int64_t* keys_sorted, int64_t n, const int64_t* offsets,
+                                int32_t width, int64_t w_begin, int64_t w_count, int32_t* out_cohort, int32_t* out_region,
+                                int32_t* out_window, int32_t* out_k, double* out_pt, double* out_exp, double* out_pval, int device)
+{
+    const TileArgs a{{genome_words, n_words, chrom_off, chrom_len, n_chrom, reg_chrom, reg_start, reg_end, R}, s_prob, C, n_up, binsize,
+                     n_tiles, nullptr, nullptr, nullptr, nullptr};
+    if (int rc = check_tile_tables_host(__func__, a, false)) return rc;
+    int64_t slots = 0;
+    if (int rc = sparse_window_sizes(__func__, C, R, n_tiles, width, &slots)) return rc;
+    DIG_REQUIRE(n >= 0 && w_begin >= 0 && w_count >= 0 && w_count <= INT32_MAX, "n, w_begin >= 0, 0 <= w_count < 2^31");
+    if (w_count == 0) return DIG_OK;
+    DIG_REQUIRE(offsets && out_cohort && out_region && out_window && out_k && out_pt && out_exp && out_pval, "non-null offsets and outputs");
+    DIG_REQUIRE(n == 0 || keys_sorted, "non-null keys");
+    DIG_REQUIRE(slots == 0 || n == 0 || (s_prob && denom && mu && sigma), "non-null s_prob, denom, mu, sigma");
+    if (int rc = check_ascending(__func__, keys_sorted, n)) return rc;
+    DIG_REQUIRE(offsets[0] == 0, "offsets: the exclusive prefix sum of the counts (0 first)");
+    for (int64_t i = 0; i < n; ++i) DIG_REQUIRE(offsets[i] <= offsets[i + 1], "offsets: the exclusive prefix sum of the counts (non-decreasing)");
+    const size_t rows = (size_t)C * R;
+    Staging st(device);
+    return call_tile_genome(st, dig_sparse_window_test, a, n_up, binsize, n_tiles, st.in(denom, rows), st.in(mu, rows), st.in(sigma, rows),
+                            st.in(keys_sorted, n), n, st.in(offsets, n + 1), width, w_begin, w_count, st.out(out_cohort, w_count),
+                            st.out(out_region, w_count), st.out(out_window, w_count), st.out(out_k, w_count), st.out(out_pt, w_count),
+                            st.out(out_exp, w_count), st.out(out_pval, w_count), nullptr);
+}
+
 int dig_overlap_join_count_host(const int64_t* blk_start_key, const int64_t* blk_runmax_key, const int64_t* blk_end, int64_t n_blk,
                                 const int64_t* mut_chrom, const int64_t* mut_start, const int64_t* mut_end, int64_t n_mut,
                                 int32_t* counts, int device)

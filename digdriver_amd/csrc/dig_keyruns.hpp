@@ -1,4 +1,4 @@
-// dig_keyruns.hpp -- what the counting routes (dig_genecounts.hip, dig_objectives.hip, dig_panelcounts.hip, dig_seqcounts.hip, dig_sitematch.hip, dig_tilehits.hip, dig_rowhits.hip, dig_tilesamples.hip, dig_tilesparse.hip, dig_tilewindows.hip, dig_tilewindowsamples.hip, dig_cnvwindows.hip) and their host twins share:
+// dig_keyruns.hpp -- what the counting routes (dig_genecounts.hip, dig_objectives.hip, dig_panelcounts.hip, dig_seqcounts.hip, dig_sitematch.hip, dig_tilehits.hip, dig_rowhits.hip, dig_tilesamples.hip, dig_tilesparse.hip, dig_tilesparsewindows.hip, dig_tilewindows.hip, dig_tilewindowsamples.hip, dig_cnvwindows.hip) and their host twins share:
 // rows encoded as 63-bit keys, sorted by the caller, counted as runs with one integer atomic per wave segment.
 #pragma once
 #include "dig_common.hpp"
@@ -59,6 +59,9 @@ int tile_sample_key_layout(const char* fn, int64_t C, int64_t R, int64_t T, int6
 // unless C, R, T < 2^31 and the product fits 62 bits.  tile_census_workspace_bytes: what dig_tile_census_workspace returns
 int sparse_tile_slots(const char* fn, int64_t C, int64_t R, int64_t T, int64_t* slots);
 int64_t tile_census_workspace_bytes(int64_t C, int n_up);
+
+// dig_tilesparsewindows.hip: tile_window_sizes and sparse_tile_slots, for the three sparse-window entry points and their host twins
+int sparse_window_sizes(const char* fn, int64_t C, int64_t R, int64_t T, int32_t width, int64_t* slots);
 
 // dig_cnvwindows.hip: the rows (3 C) and chunks (of DIG_CNV_SCAN_CHUNK windows) of the copy-number difference array i64 [C, 3, N + 1], its
 // bytes (dig_cnv_segment_deltas_size) and those of the chunk carries i64 [3 C, chunks] (dig_cnv_window_means_size); DIG_EINVAL (in the

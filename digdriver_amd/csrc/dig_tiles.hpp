@@ -1,4 +1,4 @@
-// dig_tiles.hpp -- what the kernels of the per-base route (dig_tiles.hip, dig_tiles_rows.hip, dig_tilesamples.hip, dig_tilesparse.hip)
+// dig_tiles.hpp -- what the kernels of the per-base route (dig_tiles.hip, dig_tiles_rows.hip, dig_tilesamples.hip, dig_tilesparse.hip, dig_tilesparsewindows.hip)
 // and their host twins (dig_host.hip) share: the view of the 4-bit genome and the region table (TileGenome) with a region's positions,
 // the packed-word window of a base range and its staging, the two nibble squeezes, the cohort operands of the matrix kernels, the
 // tile a mutation row counts in (tile_slot), and on the host the argument block of the entry points that take the genome (TileArgs:
@@ -158,6 +158,51 @@ __device__ __forceinline__ uint32_t nonacgt_flags(uint32_t w)       // base n is
     f = (f | (f >> 6)) & 0x000F000Fu;
     return (f | (f >> 12)) & 0xFFu;
 }
+
+// ---- the sparse routes (dig_tilesparse.hip, dig_tilesparsewindows.hip) ----
+constexpr int kSparseBlock = 256;
+constexpr int64_t kSparseNoKey = INT64_MAX;          // a pair that counts nowhere: sorts behind every real key
+
+// The windows of consecutive positions, one base at a time: ref is the table index of the last W bases (the leftmost base counts
+// highest, as itertools.product orders the contexts), good the bases since the last letter other than ACGT.
+template <int U>
+struct WindowWalk {
+    static constexpr int W = 2 * U + 1, K = 1 << (2 * W);
+    const uint32_t* words;
+    int64_t n_words, cw;
+    uint32_t word;
+    unsigned ref;
+    int good;
+
+    __device__ __forceinline__ WindowWalk(const uint32_t* w, int64_t nw) : words(w), n_words(nw), cw(-1), word(0), ref(0), good(0) {}
+    __device__ __forceinline__ void push(int64_t g)
+    {
+        int64_t w = word_of_base(g);
+        w = w < 0 ? 0 : (w < n_words ? w : n_words - 1);           // (never outside the array, whatever the region table holds)
+        if (w != cw) {
+            cw = w;
+            word = words[w];
+        }
+        const unsigned b = (word >> (4 * (int)(g & 7))) & 15u;
+        ref = ((ref << 2) | (b & 3u)) & (unsigned)(K - 1);
+        good = b < 4u ? good + 1 : 0;
+    }
+    // in front of the first position p (global base g): the W - 1 bases to the left of its window's last one
+    __device__ __forceinline__ void start(int64_t g)
+    {
+        for (int i = -U; i < U; ++i) push(g + i);
+    }
+    // position at global base g: true when its window is all ACGT (ref is then its context)
+    __device__ __forceinline__ bool step(int64_t g)
+    {
+        push(g + U);
+        return good >= W;
+    }
+};
+
+// dig_tilesparse.hip: the cohort masks of the census, [ceil(C / 64)][4^W] words (tile_census_workspace_bytes, dig_keyruns.hpp) into
+// `mask`: per context the cohorts of a pass whose table entry is positive
+void launch_tile_census_mask(const double* s_prob, int64_t C, int n_up, uint64_t* mask, hipStream_t stream);
 
 // ---- the cohort operands of the matrix kernels ----
 // A[m][ks]: lane 16 k + i holds S[c0 + 16 m + i][context of histogram row 4 ks + k] (v_mfma_f64_16x16x4); Aq[q][ks]: A[i][k] of

@@ -22,16 +22,13 @@
 //                             the arithmetic of tiled_nb_generic_kernel through the same device functions.  Every other entry is
 //                             written as "no tile" (k = 0).  Neighbouring lanes hold neighbouring tiles of one cohort: neighbouring
 //                             genome words and one table.
-// Both genome walkers read the tile kernels' 4-bit layout through its view (TileGenome, sparse_region: dig_tiles.hpp), every word
-// index clamped into the array.
+// Both genome walkers read the tile kernels' 4-bit layout through its view (TileGenome, sparse_region, WindowWalk: dig_tiles.hpp),
+// every word index clamped into the array; dig_tilesparsewindows.hip walks the same way.
 #include "dig_keyruns.hpp"
 #include "dig_math.hpp"
 #include "dig_tiles.hpp"
 
 namespace dig {
-
-constexpr int kSparseBlock = 256;
-constexpr int64_t kSparseNoKey = INT64_MAX;          // a pair that counts nowhere: sorts behind every real key
 
 // the sizes of the key (cohort R + region) T + tile: each below 2^31, the product within 62 bits
 int sparse_tile_slots(const char* fn, int64_t C, int64_t R, int64_t T, int64_t* slots)
@@ -53,43 +50,6 @@ int64_t tile_census_workspace_bytes(int64_t C, int n_up)
     return (passes > 0 ? passes : 1) * K * (int64_t)sizeof(uint64_t);
 }
 
-// The windows of consecutive positions, one base at a time: ref is the table index of the last W bases (the leftmost base counts
-// highest, as itertools.product orders the contexts), good the bases since the last letter other than ACGT.
-template <int U>
-struct WindowWalk {
-    static constexpr int W = 2 * U + 1, K = 1 << (2 * W);
-    const uint32_t* words;
-    int64_t n_words, cw;
-    uint32_t word;
-    unsigned ref;
-    int good;
-
-    __device__ __forceinline__ WindowWalk(const uint32_t* w, int64_t nw) : words(w), n_words(nw), cw(-1), word(0), ref(0), good(0) {}
-    __device__ __forceinline__ void push(int64_t g)
-    {
-        int64_t w = word_of_base(g);
-        w = w < 0 ? 0 : (w < n_words ? w : n_words - 1);           // (never outside the array, whatever the region table holds)
-        if (w != cw) {
-            cw = w;
-            word = words[w];
-        }
-        const unsigned b = (word >> (4 * (int)(g & 7))) & 15u;
-        ref = ((ref << 2) | (b & 3u)) & (unsigned)(K - 1);
-        good = b < 4u ? good + 1 : 0;
-    }
-    // in front of the first position p (global base g): the W - 1 bases to the left of its window's last one
-    __device__ __forceinline__ void start(int64_t g)
-    {
-        for (int i = -U; i < U; ++i) push(g + i);
-    }
-    // position at global base g: true when its window is all ACGT (ref is then its context)
-    __device__ __forceinline__ bool step(int64_t g)
-    {
-        push(g + U);
-        return good >= W;
-    }
-};
-
 // ---- census ----
 __global__ __launch_bounds__(kSparseBlock) void tile_census_mask_kernel(const double* __restrict__ s_prob, int64_t C, int K,
                                                                         uint64_t* __restrict__ mask, int64_t n)
@@ -103,6 +63,14 @@ __global__ __launch_bounds__(kSparseBlock) void tile_census_mask_kernel(const do
         if (c < C && s_prob[c * K + ctx] > 0.0) m |= 1ull << b;
     }
     mask[i] = m;
+}
+
+void launch_tile_census_mask(const double* s_prob, int64_t C, int n_up, uint64_t* mask, hipStream_t stream)
+{
+    const int K = tile_contexts(n_up);
+    const int64_t n_mask = tile_census_workspace_bytes(C, n_up) / (int64_t)sizeof(uint64_t);
+    hipLaunchKernelGGL(tile_census_mask_kernel, dim3((unsigned)((n_mask + kSparseBlock - 1) / kSparseBlock)), dim3(kSparseBlock), 0, stream,
+                       s_prob, C, K, mask, n_mask);
 }
 
 struct CensusArgs {
@@ -298,11 +266,8 @@ int dig_tile_census(const uint32_t* genome_words, int64_t n_words, const int64_t
     const int64_t need = tile_census_workspace_bytes(C, n_up);
     DIG_REQUIRE(workspace && workspace_bytes >= need, "workspace of dig_tile_census_workspace(C, n_up) bytes");
     DIG_REQUIRE(((uintptr_t)workspace & 7) == 0, "workspace aligned to 8 bytes");
-    const int K = tile_contexts(n_up);
     uint64_t* mask = static_cast<uint64_t*>(workspace);
-    const int64_t n_mask = need / (int64_t)sizeof(uint64_t);
-    hipLaunchKernelGGL(tile_census_mask_kernel, dim3((unsigned)((n_mask + kSparseBlock - 1) / kSparseBlock)), dim3(kSparseBlock), 0, s,
-                       s_prob, C, K, mask, n_mask);
+    launch_tile_census_mask(s_prob, C, n_up, mask, s);
     const CensusArgs a{t.g, s_prob, C, binsize, n_tiles, mask, first_pos, n_valid, denom, n_positive};
     if (n_up == 1) hipLaunchKernelGGL(tile_census_kernel<1>, dim3((unsigned)R), dim3(kSparseBlock), 0, s, a);
     else hipLaunchKernelGGL(tile_census_kernel<2>, dim3((unsigned)R), dim3(kSparseBlock), 0, s, a);

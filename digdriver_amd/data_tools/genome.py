@@ -88,8 +88,11 @@ class PackedGenome:
         g = cls.from_sequences(seqs)
         if cache:
             try:
-                np.savez(f_cache, names=np.array(g.names), offsets=g.offsets, lengths=g.lengths, words=g.words,
+                # (written beside its place and moved there: a second process that packs the same FASTA never reads half a cache)
+                tmp = "%s.%d.tmp.npz" % (f_cache, os.getpid())
+                np.savez(tmp, names=np.array(g.names), offsets=g.offsets, lengths=g.lengths, words=g.words,
                          other_pos=g.other_pos, other_letter=g.other_letter)
+                os.replace(tmp, f_cache)
                 g._cache2 = f_fasta + ".dig2.npz"
                 if os.path.exists(g._cache2):
                     os.remove(g._cache2)                  # (a 2-bit cache of an older FASTA)

@@ -1471,6 +1471,106 @@ def sparse_tile_test(genome, chroms, starts, ends, s_prob, binsize, n_tiles, fir
     return {k: v[head] for k, v in out.items()}
 
 
+# ---------------------------------------------------------------------------
+# sliding windows over the mutated tiles only (dig_tilesparsewindows.hip): nothing here is [C, R, T] either
+# ---------------------------------------------------------------------------
+SPARSE_WINDOW_CHUNK = 1 << 24       # candidate windows per call of dig_sparse_window_test: 40 bytes of outputs each
+
+
+def _window_width(width):
+    if isinstance(width, (bool, np.bool_)) or int(width) != width:
+        raise ValueError("width: an integer >= 1")
+    return int(width)
+
+
+def tile_window_census(genome, chroms, starts, ends, s_prob, binsize, width, n_tiles=None, n_positive=None, device=0, on_device=True):
+    """What the sparse window scan knows of the windows of `width` consecutive tiles without a [C, R, T] plane (dig_tile_window_census):
+    n_windows i32 [R], the bits of tile_window_test, and n_positive_w i32 [C, R], the windows below n_windows that cover a tile whose
+    dense pt is > 0 -- the windows whose dense pt is > 0.  Arguments as tile_census; n_positive: what tile_census returned for the same
+    binsize and n_tiles, or None -- with it a region whose tiles are all positive, or all not, is answered without a walk (a device
+    tensor there keeps the call on the device, an array sends it through the host twin).  Returns (n_windows, n_positive_w), device
+    tensors or (on_device=False) arrays.  ValueError for what the library refuses: a width outside [1, TILE_WINDOW_MAX_WIDTH], C R at or
+    above 2^31."""
+    width = _window_width(width)
+    be = backend_on(device, on_device) if n_positive is None else backend_of(n_positive, device=device)
+    args, held, C, R, _, n_up, _ = _tile_genome(be, genome, chroms, starts, ends, s_prob, binsize, n_tiles)
+    npos = be.arr(n_positive, "i32", (C, R))
+    nwin, npw = be.empty(R, "i32"), be.empty((C, R), "i32")
+    wsb = int(_lib.load().dig_tile_census_workspace(C, n_up))
+    p = be.ptr
+    with _requirements_as_value_errors():
+        be.call("dig_tile_window_census", *args, width, p(npos), p(nwin), p(npw), workspace=(be.empty(wsb, "u8"), wsb) if be.is_device else None)
+    return nwin, npw
+
+
+class SparseWindows:
+    """The sorted keys of one sparse scan, from which the windows of every width are served (sparse_window_test makes it)."""
+    NAMES = ("cohort", "region", "window", "k", "pt", "exp", "pval")
+
+    def __init__(self, be, args, held, C, R, T, n_valid, denom, mu, sigma, keys, chunk_windows):
+        self.be, self.args, self.held, self.C, self.R, self.T = be, args, held, C, R, T
+        self.n_valid, self.denom, self.mu, self.sigma, self.keys = n_valid, denom, mu, sigma, keys
+        self.chunk_windows = SPARSE_WINDOW_CHUNK if chunk_windows is None else int(chunk_windows)
+        if self.chunk_windows < 1 or self.chunk_windows > 2 ** 31 - 1:
+            raise ValueError("chunk_windows: an integer within [1, 2^31)")
+
+    def offsets(self, width):
+        """(offsets i64 [n + 1], total): where the candidate windows of every key start in the flat list of this width (the windows
+        whose first mutated tile is the key's; only a run's head has any), and how many there are -- the total may exceed 2^31."""
+        be, p, n = self.be, self.be.ptr, self.keys.shape[0]
+        counts = be.empty(n, "i64")
+        with _requirements_as_value_errors():
+            be.call("dig_sparse_window_count", p(self.keys), n, p(self.n_valid), self.C, self.R, self.T, _window_width(width), p(counts))
+        excl, total = _scan(be, counts)
+        return be.cat([excl, be.arr(np.array([total], np.int64))], "i64"), total
+
+    def chunks(self, width, chunk_windows=None):
+        """The mutated windows of `width` tiles, dig_sparse_window_test on at most chunk_windows candidates at a time: yields
+        dict(cohort, region, window, k i32, pt, exp, pval f64), one entry per mutated window, cohort-major, then by region, then by
+        window, each window once; the chunks one after the other are the whole list."""
+        be, p = self.be, self.be.ptr
+        width = _window_width(width)
+        step = self.chunk_windows if chunk_windows is None else int(chunk_windows)
+        if step < 1 or step > 2 ** 31 - 1:
+            raise ValueError("chunk_windows: an integer within [1, 2^31)")
+        offsets, total = self.offsets(width)
+        for begin in range(0, total, step):
+            count = min(step, total - begin)
+            out = {k: be.empty(count, "i32" if i < 4 else "f64") for i, k in enumerate(self.NAMES)}
+            with _requirements_as_value_errors():
+                be.call("dig_sparse_window_test", *self.args, p(self.denom), p(self.mu), p(self.sigma), p(self.keys), self.keys.shape[0],
+                        p(offsets), width, begin, count, *[p(out[k]) for k in self.NAMES])
+            yield out
+
+    def windows(self, width, chunk_windows=None):
+        """All chunks of `width` as one dict."""
+        got = list(self.chunks(width, chunk_windows))
+        return {k: self.be.cat([g[k] for g in got], "i32" if i < 4 else "f64") for i, k in enumerate(self.NAMES)}
+
+
+def sparse_window_test(genome, chroms, starts, ends, s_prob, binsize, n_tiles, first_pos, n_valid, denom, mu, sigma, mut_chrom, mut_start,
+                       mut_end, mut_cohort, chunk_windows=None):
+    """The NB test of the windows of consecutive tiles that hold a row, and of no other: the join, dig_sparse_tile_keys and the key sort
+    of sparse_tile_test, once; the SparseWindows it returns then serves every width -- per width dig_sparse_window_count, a prefix sum,
+    and dig_sparse_window_test in chunks of at most chunk_windows candidate windows (default SPARSE_WINDOW_CHUNK).  Arguments as
+    sparse_tile_test (device tensors -> device tensors, arrays -> the host twins).  .windows(width) is dict(cohort, region, window, k
+    i32, pt, exp, pval f64): one entry per mutated window, in the order of the dense window frame; width 1 is sparse_tile_test bit for
+    bit (with `window` for `tile`); against tile_window_test k is exact, pt and exp agree to rounding (one division here, a sum of
+    quotients there).  ValueError for what the library refuses."""
+    be = backend_of(first_pos, n_valid, denom)
+    args, held, C, R, T, _, binsize = _tile_genome(be, genome, chroms, starts, ends, s_prob, binsize, n_tiles)
+    denom, mu, sigma = (be.arr(x, "f64", (C, R)) for x in (denom, mu, sigma))
+    first_pos, n_valid, pm, pr, ms, co = _tile_rows(be, genome, chroms, starts, ends, first_pos, n_valid, mut_chrom, mut_start, mut_end,
+                                                    mut_cohort, R)
+    p = be.ptr
+    n = pm.shape[0]
+    keys = be.empty(n, "i64")
+    with _requirements_as_value_errors():
+        be.call("dig_sparse_tile_keys", p(pm), p(pr), n, p(ms), ms.shape[0], p(co), p(first_pos), p(n_valid), binsize, T, R, C, p(keys))
+        keys = _sorted(be, keys)
+    return SparseWindows(be, args, held, C, R, T, n_valid, denom, mu, sigma, keys, chunk_windows)
+
+
 def _tile_counts(be, score, n_valid, cut):
     """dig_tile_select_count on the backend's arrays: (the six leading arguments both entry points take, counts i32 [C R], C, R, T)."""
     score = be.arr(score, "f64")

@@ -698,6 +698,147 @@ def nb_model_hits_sparse(d_prs, idx, mu, sigma, f_muts, f_fasta, n_up=2, n_down=
     return frames
 
 
+def nb_model_window_hits_sparse(d_prs, idx, mu, sigma, f_muts, f_fasta, n_up=2, n_down=2, binsize=1, widths=(2,), collapse=False,
+                                pval_max=None, fdr=None, bonferroni=None, device=0, chunk_windows=None):
+    """nb_model_window_hits over the windows that hold a mutation row, and no other (DESIGN.md "Sparse sliding windows"): memory and
+    work follow the rows, the chunk and the hits kept -- no [C, R, T] array is allocated.  Exactly one of pval_max / fdr / bonferroni
+    (cut = bonferroni / n_testable of the cohort at that width).  One engine.tile_census and one engine.sparse_window_test (the join,
+    the keys and their sort) for every width; per width, in the order given: engine.tile_window_census, zero_tile_floor at
+    binsize * width (an empty window's pt is at most min(1, width binsize smax / denom)), then the candidate windows in chunks of at
+    most chunk_windows (default engine.SPARSE_WINDOW_CHUNK).  Of a chunk only what can still be a hit is kept -- pval_max: p <= it;
+    bonferroni: p <= level / max(the census' testable windows, 1), an upper bound of the final cut, filtered again with the final
+    n_testable; fdr: p <= fdr (every Benjamini-Hochberg hit is, and holds its rank among them) -- and, per cohort, the windows with a
+    p-value that the census does not count are counted.  With fdr the route keeps every window with p <= fdr (16 bytes each on the
+    device beside the host copy): pval_max and bonferroni are the genome-scale cuts.
+    Frames as nb_model_window_hits makes them (the nine columns, WIDTH, PEAK, QVAL with fdr per cohort and width; the index is the row
+    number in the full frame of that width; attrs n_testable and n_windows, one entry per width), with two more attrs, one entry per
+    width each: zero_floor, a lower bound of the p-value of every empty testable window, and complete, zero_floor (1 - 4e-6) > cut --
+    no empty window can be a hit.  Where it is false the frame is the dense hits with OBS >= 1.  Pi and EXP agree with the dense window
+    route to rounding (one division of the window's sum here, a sum of the tiles' quotients there), not in bits.
+    fdr needs every cohort complete at every width, else ValueError (naming cohorts, widths and floors) before any window is tested.
+    ValueError before a genome is packed: no cut or more than one, a bonferroni outside (0, 1], what _check_widths refuses, a width above
+    engine.TILE_WINDOW_MAX_WIDTH, a negative S_prob entry, n_up != n_down or n_up not 1 or 2.  The sample options are no parameters."""
+    _one_cut(pval_max, fdr, bonferroni)
+    widths = _check_widths(widths)
+    from .. import engine
+    if max(widths) > engine.TILE_WINDOW_MAX_WIDTH:
+        raise ValueError("widths: at most %d tiles" % engine.TILE_WINDOW_MAX_WIDTH)
+    if n_up != n_down or n_up not in (1, 2):
+        raise ValueError("the tile kernels take n_up = n_down = 1 or 2")
+    if isinstance(binsize, (bool, np.bool_)) or int(binsize) != binsize or binsize < 1:
+        raise ValueError("binsize: an integer >= 1")
+    binsize = int(binsize)
+    import pandas as pd
+    import torch
+    from ..data_tools import cohort_rows, genome as genome_mod
+    C = len(d_prs)
+    f_muts = list(f_muts)
+    idx = np.asarray(idx)
+    R = len(idx)
+    mu, sigma = np.asarray(mu, float).reshape(C, R), np.asarray(sigma, float).reshape(C, R)
+    if len(f_muts) != C:
+        raise ValueError("one mutation file per cohort: %d files for %d cohorts" % (len(f_muts), C))
+    s_prob = np.stack([_s_prob_table(d, n_up, collapse) for d in d_prs]) if C else np.zeros((0, 4 ** (2 * n_up + 1)))
+    if (s_prob < 0).any():
+        raise ValueError("S_prob: a negative entry (cohort %d)" % int(np.argwhere(s_prob < 0)[0][0]))
+    starts, ends = (idx[:, 1].astype(np.int64), idx[:, 2].astype(np.int64)) if R else (np.zeros(0, np.int64),) * 2
+    engine.check_tile_regions(starts, ends, n_up)
+    g = f_fasta if isinstance(f_fasta, genome_mod.PackedGenome) else genome_mod.PackedGenome.from_fasta(f_fasta)
+    chroms = [str(c) for c in idx[:, 0]] if R else []
+    known = set(n.replace("chr", "") for n in g.names)
+    rows = _cohort_rows(f_muts, known, False)
+    mc, ms, me = cohort_rows.column(rows, "chrom"), cohort_rows.column(rows, "start", "i64"), cohort_rows.column(rows, "end", "i64")
+    co = cohort_rows.cohort_column(rows, "start")
+    n_tiles = int(max(1, -(-int((ends - starts).max() if R else 1) // binsize)))
+    first_d, nval_d, denom_d, npos_d = engine.tile_census(g, chroms, starts, ends, s_prob, binsize, n_tiles=n_tiles, device=device)
+    first, nval = first_d.cpu().numpy(), np.clip(nval_d.cpu().numpy().astype(np.int64), 0, n_tiles)
+    smax = s_prob.max(axis=1) if C else np.zeros(0)
+    smin = np.where(s_prob > 0, s_prob, np.inf).min(axis=1) if C else np.zeros(0)
+    # per width: the windows, the testable ones the census knows, the floor -- and the certificates of fdr before any window is tested
+    census = []
+    for m in widths:
+        nwin_d, npw_d = engine.tile_window_census(g, chroms, starts, ends, s_prob, binsize, m, n_tiles=n_tiles, n_positive=npos_d)
+        floor, testable_d = zero_tile_floor(denom_d, smax, smin, mu, sigma, binsize * m, npos_d)
+        n_census = (npw_d.long() * testable_d).sum(dim=1).cpu().numpy() if R else np.zeros(C, np.int64)
+        census.append((nwin_d.cpu().numpy().astype(np.int64), n_census, floor))
+    if fdr is not None:
+        bad = [(c, m) for m, (_, _, floor) in zip(widths, census) for c in range(C) if not floor[c] * (1.0 - ZERO_FLOOR_MARGIN) > fdr]
+        if bad:
+            raise ValueError("fdr = %g: no certificate that an empty window is no hit for cohorts %s at widths %s (zero-window floors %s): "
+                             "a smaller fdr, a smaller binsize or width, or nb_model_window_hits"
+                             % (fdr, sorted(set(c for c, _ in bad)), sorted(set(m for _, m in bad)),
+                                ["%.3g" % census[widths.index(m)][2][c] for c, m in bad]))
+    scan = engine.sparse_window_test(g, chroms, starts, ends, s_prob, binsize, n_tiles, first_d, nval_d, denom_d, mu, sigma, mc, ms, me, co,
+                                     chunk_windows=chunk_windows)
+    dev = denom_d.device
+    n_pos = _region_positions(g, chroms, ends, first, n_up) if R else np.zeros(0, np.int64)
+    last = first + n_pos                                       # one past a region's last position
+    per_width = []                     # (m, the kept windows as host arrays, their cohort_ptr, cuts [C], n_testable [C], n_windows [R], floor, level)
+    for m, (nwin, n_census, floor) in zip(widths, census):
+        if pval_max is not None:
+            bound = np.full(C, float(pval_max))
+        elif fdr is not None:
+            bound = np.full(C, float(fdr))
+        else:
+            bound = float(bonferroni) / np.maximum(n_census, 1)
+        bound_d = torch.as_tensor(bound, device=dev)
+        extra = torch.zeros(C, dtype=torch.int64, device=dev)
+        kept, kept_p = [], []
+        for ch in scan.chunks(m):
+            c, p = ch["cohort"].long(), ch["pval"]
+            counted = testable_d[c, ch["region"].long()] & (ch["pt"] > 0)        # (the window census has these windows already)
+            extra += torch.bincount(c[~torch.isnan(p) & ~counted], minlength=C)[:C]
+            keep = p <= bound_d[c]                                             # (a NaN never passes)
+            kept.append({name: v[keep].cpu().numpy() for name, v in ch.items()})
+            if fdr is not None:
+                kept_p.append(p[keep])
+        win = {name: np.concatenate([k[name] for k in kept]) if kept else np.zeros(0, np.int32 if i < 4 else np.float64)
+               for i, name in enumerate(engine.SparseWindows.NAMES)}
+        n_test = n_census + extra.cpu().numpy()
+        wc = win["cohort"].astype(np.int64)
+        ptr = np.searchsorted(wc, np.arange(C + 1))                            # (the windows lie cohort-major)
+        if fdr is not None:
+            cuts = np.full(C, -1.0)
+            if len(wc):
+                # the mutated windows with p <= fdr, ranked in a list of n_testable: every rank up to the pivot is theirs
+                lists = torch.cat(kept_p).contiguous()
+                q, _ = bh_ragged(lists, ptr.astype(np.int64), n_global=np.maximum(n_test, 1).astype(np.float64))
+                for c in range(C):
+                    cuts[c] = bh_cut(lists[ptr[c]:ptr[c + 1]], q[ptr[c]:ptr[c + 1]], fdr)
+            level = np.full(C, float(fdr))
+        elif bonferroni is not None:
+            cuts = level = float(bonferroni) / np.maximum(n_test, 1)
+        else:
+            cuts = level = np.full(C, float(pval_max))
+        per_width.append((m, win, ptr, cuts, n_test, nwin, floor, level))
+    frames = []
+    for c in range(C):
+        cols = {name: [] for name in ("reg", "t", "k", "exp", "pval", "pt", "lo", "hi", "peak", "q", "row")}
+        for m, win, ptr, cuts, n_test, nwin, _, _ in per_width:
+            sel = np.arange(ptr[c], ptr[c + 1])
+            sel = sel[win["pval"][sel] <= cuts[c]]
+            reg, t, score = win["region"][sel].astype(np.int64), win["window"][sel].astype(np.int64), win["pval"][sel]
+            lo = first[reg] + t * binsize
+            hi = np.minimum(lo + np.minimum(m, nval[reg] - t) * binsize, last[reg]) - 1
+            cols["reg"].append(reg), cols["t"].append(t), cols["lo"].append(lo), cols["hi"].append(hi)
+            cols["k"].append(win["k"][sel]), cols["exp"].append(win["exp"][sel]), cols["pt"].append(win["pt"][sel]), cols["pval"].append(score)
+            cols["peak"].append(window_peaks(reg, t, score, m))
+            cols["q"].append(hits_q_values(score, int(n_test[c])) if fdr is not None else score)
+            cols["row"].append((np.cumsum(nwin) - nwin)[reg] + t)
+        cat = {name: np.concatenate(v) for name, v in cols.items()}
+        df = _tile_frame(idx, mu[c], sigma[c], first, n_pos, binsize, cat["reg"], cat["t"], cat["k"], cat["exp"], cat["pval"], cat["pt"])
+        df["POS"] = (cat["lo"] + cat["hi"]) / 2.0
+        df["WIDTH"], df["PEAK"] = (cat["hi"] - cat["lo"] + 1).astype(float), cat["peak"].astype(bool)
+        if fdr is not None:
+            df["QVAL"] = cat["q"]
+        df.index = pd.Index(cat["row"], dtype=np.int64)
+        df.attrs.update(n_testable=[int(w[4][c]) for w in per_width], n_windows=[int(w[5].sum()) for w in per_width],
+                        zero_floor=[float(w[6][c]) for w in per_width],
+                        complete=[bool(w[6][c] * (1.0 - ZERO_FLOOR_MARGIN) > w[7][c]) for w in per_width])
+        frames.append(df)
+    return frames
+
+
 def bh_ragged(p, row_ptr, n_global=None, rank0=None, carry=None, want_q=True, want_row_min=False, sorted_out=False):
     """dig_bh_qvalues_ragged (csrc/dig_sort.hip): Benjamini-Hochberg q-values of ragged rows of one float64 device tensor -- the
     library's own batched radix sort (63-bit keys, 32-bit payload, one kernel per pass), the Benjamini-Hochberg pass and the

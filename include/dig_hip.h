@@ -44,7 +44,8 @@ extern "C" {
                              * their _host twins (additions); + dig_tile_census(_workspace), dig_sparse_tile_keys, dig_sparse_tile_test
                              * and their _host twins (additions); + dig_tile_window_test and its _host twin (additions);
                              * + dig_tile_window_sample_keys, dig_tile_window_samples and their _host twins (additions);
-                             * + dig_cnv_segment_deltas, dig_cnv_window_means, their size queries and _host twins (additions) */
+                             * + dig_cnv_segment_deltas, dig_cnv_window_means, their size queries and _host twins (additions);
+                             * + dig_tile_window_census, dig_sparse_window_count, dig_sparse_window_test and their _host twins (additions) */
 
 /* dtype codes for dig_gather_bins */
 #define DIG_F32 0
@@ -727,6 +728,66 @@ int dig_tile_window_samples(const int64_t *keys_sorted, int64_t n, const int32_t
                             int64_t n_samples, int32_t width, int32_t *s_w, void *stream);
 int dig_tile_window_samples_host(const int64_t *keys_sorted, int64_t n, const int32_t *n_valid, int64_t C, int64_t R, int64_t T,
                                  int64_t n_samples, int32_t width, int32_t *s_w, int device);
+
+/* ---- sliding windows over the mutated tiles only (additive: the ABI version stays) --------------------------------- *
+ * dig_tile_window_test for the windows that hold a mutation row, and for no other, without a [C, R, T] plane.  Genome, chromosome
+ * and region arguments, s_prob, n_up, binsize and n_tiles = T as dig_tile_census takes them; keys_sorted i64 [n]: the keys of
+ * dig_sparse_tile_keys, (cohort R + region) T + tile, sorted ascending (a run of equal keys: a mutated tile); nv = min(n_valid[r], T)
+ * and n_windows, "window w covers the tiles w .. min(w + width, nv) - 1" as dig_tile_window_test defines them.  A MUTATED WINDOW of
+ * row (c, r) is a window w < n_windows[r] that covers a mutated tile of the row.  With t_prev the mutated tile in front of t in its
+ * row (-1: none), tile t is the FIRST mutated tile of exactly the windows [lo, hi), lo = max(t_prev + 1, t - width + 1, 0),
+ * hi = min(t + 1, n_windows[r]): every mutated window has one such tile and is named once, through it.
+ *   dig_tile_window_census: n_windows i32 [R] (the bits of dig_tile_window_test) and n_positive_w i32 [C, R], the windows
+ *     w < n_windows[r] that cover a tile with pt > 0 by the rule of dig_tile_census' n_positive -- the windows whose dense pt_w is > 0:
+ *     for nv >= width, n_windows[r] minus the sum over the maximal runs of Z consecutive tiles without a positive position of
+ *     max(Z - width + 1, 0); for 0 < nv < width, 1 when any tile is positive.  One workgroup per region, a pass per 64 cohorts;
+ *     integers only, no atomics, the LDS use does not depend on T.  n_positive i32 [C, R] or NULL: the n_positive of dig_tile_census
+ *     for the same binsize and n_tiles; a (region, pass of 64 cohorts) whose cohorts all have n_positive 0 or nv is then answered
+ *     without walking the genome.  workspace: dig_tile_census_workspace(C, n_up) bytes, aligned to 8 bytes (the call fills it).
+ *   dig_sparse_window_count: counts i64 [n]: at the head of a run max(hi - lo, 0), at every other index 0.  The head reads t_prev
+ *     from its left neighbour (the same row iff prev / T == key / T).  Keys that are negative, INT64_MAX, of a row >= C R or of a tile
+ *     >= nv get 0 before anything is dereferenced.  n_valid i32 [R].  One lane per key.
+ *   The caller forms offsets i64 [n + 1], the exclusive prefix sum of counts with the total last (it may exceed 2^31).
+ *   dig_sparse_window_test: the candidate windows j in [w_begin, w_begin + w_count) of the flat list, w_count < 2^31, one lane each.
+ *     The owner is the last index i with offsets[i] <= j < offsets[i + 1]; the window is w = lo(i) + j - offsets[i]; out_k = (the
+ *     first index at or behind i whose key is >= row T + min(w + width, nv)) - i; out_pt = (the sum of s_prob[c] over the window's
+ *     positions in ascending order, valid contexts only, started at 0.0) / denom[c, r] -- ONE division: width 1 gives the seven
+ *     outputs of dig_sparse_tile_test bit for bit, an aligned full window at (binsize, width) the pt bits of the sparse tile at
+ *     binsize width; dig_tile_window_test adds the tiles' quotients instead and agrees to rounding (1e-12 relative), not in bits.
+ *     out_exp = pt mu, out_pval: the device functions of dig_tiled_nb_test.  out_cohort, out_region, out_window, out_k i32, out_pt,
+ *     out_exp, out_pval f64 [w_count], in the order of the list: cohort-major, then by region, then by window.  nv comes from the
+ *     region table (what dig_tile_census writes as n_valid).  An index j that no head owns (offsets of another key list, a key
+ *     outside [0, C R T)) gets cohort = region = window = -1, k = 0 and NaN: every element of the chunk is written.  denom, mu,
+ *     sigma f64 [C, R].  Both genome walkers clamp every word index into [0, n_words).
+ * DIG_EINVAL, before anything is read or launched, for a width outside [1, DIG_TILE_WINDOW_MAX_WIDTH], C R >= 2^31, C, R or T at or
+ * above 2^31 and C R T beyond 62 bits.  Nothing is launched for R = 0 (census), n = 0 (count) or w_count = 0 (test).  Every typed
+ * pointer needs the alignment of its element and no more.  The host twins refuse what the twins of dig_tile_census refuse of the
+ * tables, keys that are not ascending and offsets that are not those of a prefix sum (0 first, non-decreasing). */
+int dig_tile_window_census(const uint32_t *genome_words, int64_t n_words, const int64_t *chrom_off, const int64_t *chrom_len,
+                           int n_chrom, const int32_t *reg_chrom, const int64_t *reg_start, const int64_t *reg_end, int64_t R,
+                           const double *s_prob, int64_t C, int n_up, int binsize, int64_t n_tiles, int32_t width,
+                           const int32_t *n_positive, int32_t *n_windows, int32_t *n_positive_w, void *workspace,
+                           int64_t workspace_bytes, void *stream);
+int dig_tile_window_census_host(const uint32_t *genome_words, int64_t n_words, const int64_t *chrom_off, const int64_t *chrom_len,
+                                int n_chrom, const int32_t *reg_chrom, const int64_t *reg_start, const int64_t *reg_end, int64_t R,
+                                const double *s_prob, int64_t C, int n_up, int binsize, int64_t n_tiles, int32_t width,
+                                const int32_t *n_positive, int32_t *n_windows, int32_t *n_positive_w, int device);
+int dig_sparse_window_count(const int64_t *keys_sorted, int64_t n, const int32_t *n_valid, int64_t C, int64_t R, int64_t T,
+                            int32_t width, int64_t *counts, void *stream);
+int dig_sparse_window_count_host(const int64_t *keys_sorted, int64_t n, const int32_t *n_valid, int64_t C, int64_t R, int64_t T,
+                                 int32_t width, int64_t *counts, int device);
+int dig_sparse_window_test(const uint32_t *genome_words, int64_t n_words, const int64_t *chrom_off, const int64_t *chrom_len,
+                           int n_chrom, const int32_t *reg_chrom, const int64_t *reg_start, const int64_t *reg_end, int64_t R,
+                           const double *s_prob, int64_t C, int n_up, int binsize, int64_t n_tiles, const double *denom,
+                           const double *mu, const double *sigma, const int64_t *keys_sorted, int64_t n, const int64_t *offsets,
+                           int32_t width, int64_t w_begin, int64_t w_count, int32_t *out_cohort, int32_t *out_region,
+                           int32_t *out_window, int32_t *out_k, double *out_pt, double *out_exp, double *out_pval, void *stream);
+int dig_sparse_window_test_host(const uint32_t *genome_words, int64_t n_words, const int64_t *chrom_off, const int64_t *chrom_len,
+                                int n_chrom, const int32_t *reg_chrom, const int64_t *reg_start, const int64_t *reg_end, int64_t R,
+                                const double *s_prob, int64_t C, int n_up, int binsize, int64_t n_tiles, const double *denom,
+                                const double *mu, const double *sigma, const int64_t *keys_sorted, int64_t n, const int64_t *offsets,
+                                int32_t width, int64_t w_begin, int64_t w_count, int32_t *out_cohort, int32_t *out_region,
+                                int32_t *out_window, int32_t *out_k, double *out_pt, double *out_exp, double *out_pval, int device);
 
 /* ---- sufficient statistics in canonical chunks (bin-sharded runs) --------------------------- *
  * Same quantity as dig_scale_suffstats / dig_scale_factors, defined so that it does not depend on the sharding: the bins

@@ -281,13 +281,28 @@ def cmd_tile(args):
     the mutation files; --by-sample adds OBS_SAMPLES and PVAL_SAMPLE behind REGION.  --window-tiles M [M ...] tests every window of M
     consecutive tiles instead (nb_model_window_hits: WIDTH and PEAK behind REGION; not with --sparse, --by-sample, --cut-on PVAL_SAMPLE).
     --window-samples (with --window-tiles) counts the distinct samples of every window: OBS_SAMPLES and PVAL_SAMPLE behind REGION, and
-    --cut-on PVAL_SAMPLE selects on them."""
+    --cut-on PVAL_SAMPLE selects on them.  --sparse --sparse-windows M [M ...] tests the windows of M consecutive tiles that hold a
+    mutation row, and no other (nb_model_window_hits_sparse: the frames of --window-tiles, the three cuts of --sparse, a zero-window
+    floor per cohort and width; not with --window-tiles, --window-samples or the sample options)."""
     n = _cohort_lists(args, manual=False)
+    if args.sparse_windows is not None:
+        if not args.sparse:
+            raise SystemExit("ERROR: --sparse-windows needs --sparse (every window of the dense planes: --window-tiles).")
+        if args.window_tiles is not None:
+            raise SystemExit("ERROR: --sparse-windows does not go with --window-tiles (the windows of the sparse scan or those of the dense planes).")
+        if args.window_samples:
+            raise SystemExit("ERROR: --sparse-windows does not take --window-samples (the sparse scan counts rows, not samples).")
+        if args.max_muts_per_sample is not None or args.max_muts_per_tile_per_sample is not None or args.by_sample or args.cut_on != 'PVAL':
+            raise SystemExit("ERROR: --sparse-windows does not take the sample options (--max-muts-per-sample, --max-muts-per-tile-per-sample, "
+                             "--by-sample, --cut-on).")
+        if min(args.sparse_windows) < 1 or len(set(args.sparse_windows)) != len(args.sparse_windows):
+            raise SystemExit("ERROR: --sparse-windows takes distinct integers >= 1.")
     if args.window_samples and args.window_tiles is None:
         raise SystemExit("ERROR: --window-samples needs --window-tiles (the tiles' own samples: --by-sample).")
     if args.window_tiles is not None:
         if args.sparse:
-            raise SystemExit("ERROR: --window-tiles is not part of --sparse (the sparse scan tests single tiles).")
+            raise SystemExit("ERROR: --window-tiles is not part of --sparse (the sparse scan tests single tiles); "
+                             "--sparse --sparse-windows M tests the windows that hold a mutation row.")
         if args.by_sample:
             raise SystemExit("ERROR: --window-tiles does not take --by-sample (the samples of a window are not the sum of its tiles' samples); "
                              "--window-samples counts a window's distinct samples.")
@@ -346,6 +361,25 @@ def cmd_tile(args):
         by_sample=args.by_sample, cut_on=args.cut_on)
     if args.window_samples:
         sample_opts['window_samples'] = True
+    if args.sparse and args.sparse_windows is not None:
+        try:
+            frames = nb_model.nb_model_window_hits_sparse(d_prs, idx[keep], np.array(mu)[:, keep], np.array(sigma)[:, keep], args.mutation_files,
+                                                          args.f_fasta, n_up=args.up, n_down=args.down, binsize=args.binsize,
+                                                          widths=args.sparse_windows, pval_max=args.pval_max, fdr=args.fdr,
+                                                          bonferroni=args.bonferroni)
+        except ValueError as exc:
+            if 'no certificate' not in str(exc):
+                raise
+            raise SystemExit("ERROR: {}".format(exc))
+        os.makedirs(args.outdir, exist_ok=True)
+        for pfx, frame in zip(args.outpfx, frames):
+            target = os.path.join(args.outdir, pfx + '.hits.txt')
+            floors = ', '.join('{:.3g}{}'.format(f, '' if done else ' (mutated windows only)')
+                               for f, done in zip(frame.attrs['zero_floor'], frame.attrs['complete']))
+            print('\t{}: {} hits of {} testable windows (widths {}), zero-window floors {}; saving to {}'.format(
+                pfx, len(frame), frame.attrs['n_testable'], args.sparse_windows, floors, target))
+            mapfile.write_results_tsv(frame, target)
+        return
     if args.sparse:
         try:
             frames = nb_model.nb_model_hits_sparse(d_prs, idx[keep], np.array(mu)[:, keep], np.array(sigma)[:, keep], args.mutation_files,
@@ -483,6 +517,10 @@ def parse_args(text=None):
     d.add_argument('--window-samples', action='store_true', default=False,
                    help="with --window-tiles: count every window's distinct samples (adds OBS_SAMPLES and PVAL_SAMPLE; --cut-on PVAL_SAMPLE "
                         "then selects on them)")
+    # the windows of --window-tiles that hold a mutation row, without the dense planes (DESIGN.md "Sparse sliding windows")
+    d.add_argument('--sparse-windows', type=int, nargs='+', default=None, metavar='M',
+                   help='with --sparse: test the windows of M consecutive tiles that hold a mutation row, for each M given (adds WIDTH and '
+                        'PEAK; not with --window-tiles, --window-samples or the sample options)')
     d.set_defaults(func=cmd_tile)
 
     # not a reference sub-command: quickDriver for many cohorts at once (driver_model/cohort_batch.py run_quick_cohorts)
