@@ -630,6 +630,8 @@ __global__ __launch_bounds__(kMfmaWaves * 64, kMfmaMinBlocks) void acc_dot_mfma_
 // them to the matrix pipe; the '-' strand permutation (sequence_tools.py:633-634) is a register choice: the lane reads
 // slice 4 t' + (3 - k) instead and takes component 3 - t of slice 3 - u where the '+' strand takes component u of slice t
 // (revcomp(16 t + 4 k + u) = 16 (3 - u) + 4 (3 - k) + (3 - t)).  No context rows cross HBM between two kernels any more.
+// That is the LIVE form (one-shot calls, the host twin).  A plan sums the rows once instead (element_contexts_kernel: they
+// depend on the bins and the element set only) and runs the PLANNED form, which streams that table like Lc.
 // =======================================================================================
 constexpr int kCtxWaves = 12;
 constexpr int kCtxSteps = 16;                 // 64 context rows / 4
@@ -648,9 +650,43 @@ __global__ __launch_bounds__(256) void compact_L_kernel(const int32_t* __restric
     if (__any(bad) && (threadIdx.x & 63) == 0) atomicOr(mismatch, 1);
 }
 
+// Plan-time: the region counts of every element as one [E, 64] table (dig_element_contexts_prepare) -- the sums the live form
+// of acc_dot_ctx_kernel gathers per call, which depend on the bins and the element set only.  16 lanes x int4 per row, as
+// phase B of acc_region_kernel forms and permutes them (same table); persistent over the elements, so any grid is enough.
+__global__ __launch_bounds__(256) void element_contexts_kernel(const int32_t* __restrict__ bin_ctx, const int64_t* __restrict__ ov_ptr,
+                                                               const int32_t* __restrict__ ov_idx, const uint8_t* __restrict__ strand_minus,
+                                                               int64_t E, int32_t* __restrict__ elt_ctx)
+{
+    const int l16 = threadIdx.x & 15;
+    const int4* ctx4 = reinterpret_cast<const int4*>(bin_ctx);
+    const int64_t stride = ((int64_t)gridDim.x * 256) >> 4;
+    for (int64_t e = ((int64_t)blockIdx.x * 256 + threadIdx.x) >> 4; e < E; e += stride) {
+        const int64_t q0 = ov_ptr[e], q1 = ov_ptr[e + 1];
+        int4 acc = make_int4(0, 0, 0, 0);
+        for (int64_t q = q0; q < q1; ++q) {                               // sequence_tools.py:630-631
+            const int4 v = ctx4[(int64_t)ov_idx[q] * 16 + l16];
+            acc.x += v.x; acc.y += v.y; acc.z += v.z; acc.w += v.w;
+        }
+        if (!strand_minus[e]) {
+            reinterpret_cast<int4*>(elt_ctx)[e * 16 + l16] = acc;
+        } else {                                                          // sequence_tools.py:633-634
+            int32_t* row = elt_ctx + e * 64;
+            const int c0 = 4 * l16;
+            row[revcomp_ctx(c0 + 0)] = acc.x;
+            row[revcomp_ctx(c0 + 1)] = acc.y;
+            row[revcomp_ctx(c0 + 2)] = acc.z;
+            row[revcomp_ctx(c0 + 3)] = acc.w;
+        }
+    }
+}
+
 // At most 160 vector registers (amdgpu_num_vgpr counts in units of two on the unified register file of gfx90a and later: 80 -> 160),
 // no scratch in any instantiation: three waves per SIMD leave room for one 32-register wave of the scale factors' background kernels.
-template <int NT, int NQ>
+// PLANNED (DIG_PIPE_ELEMENT_CTX): `bin_ctx` is the [E, 64] table of element_contexts_kernel, read slice for slice like Lc: every
+// address follows from the tile number, so there are no CSR bounds, no bin indices, no > 2 bins loop, no masks and no strand
+// selects (the table is stored permuted), and ov_ptr / ov_idx / strand_minus are not read.  The values that reach the matrix
+// steps, the sums and the stores are those of the live form in the same order: same bits.
+template <int NT, int NQ, bool PLANNED>
 __global__ __launch_bounds__(kCtxWaves * 64) __attribute__((amdgpu_waves_per_eu(3, 3), amdgpu_num_vgpr(80))) void acc_dot_ctx_kernel(
     const int32_t* __restrict__ bin_ctx, const int64_t* __restrict__ ov_ptr, const int32_t* __restrict__ ov_idx,
     const uint8_t* __restrict__ strand_minus, const int32_t* __restrict__ Lc, const double* __restrict__ d_pr,
@@ -686,7 +722,7 @@ __global__ __launch_bounds__(kCtxWaves * 64) __attribute__((amdgpu_waves_per_eu(
     const int4* ctx4 = reinterpret_cast<const int4*>(bin_ctx);
     const int4* L4 = reinterpret_cast<const int4*>(Lc);
     // every element's CSR range lies inside [0, nnz); with an empty CSR the index loads replay ov_ptr[0] (= 0: row 0)
-    const int64_t nnz = ov_ptr[E];
+    const int64_t nnz = PLANNED ? 0 : ov_ptr[E];
     const int32_t* oi_base = nnz > 0 ? ov_idx : reinterpret_cast<const int32_t*>(ov_ptr);
     const int64_t oi_last = nnz > 0 ? nnz - 1 : 0;
 
@@ -694,11 +730,12 @@ __global__ __launch_bounds__(kCtxWaves * 64) __attribute__((amdgpu_waves_per_eu(
     //  row is the tile's scalar first row + a lane offset formed again where it is needed)
     struct Bounds { int64_t q0; int cm; };
     struct Idx { int i0, i1; };
-    struct Rows { int4 a[4], b[4], l[4]; };
+    struct Rows { int4 a[4], b[PLANNED ? 1 : 4], l[4]; };   // (PLANNED: a = the element's row of the table; b is not used)
     auto first_row = [&](int64_t tile_) { return min(tile_, n_tiles - 1) * 16; };             // scalar; <= E - 1
     auto row_off = [&](int64_t row0) { return (unsigned)min(i, (int)min(E - 1 - row0, (int64_t)15)); };
     auto load_bounds = [&](int64_t tile_) {          // tiles / rows past the end replay the last row (never stored)
-        Bounds r;
+        Bounds r{0, 0};
+        if constexpr (PLANNED) return r;
         const int64_t row0 = first_row(tile_);
         const unsigned ro = row_off(row0);
         const int64_t* op = ov_ptr + row0;
@@ -708,23 +745,31 @@ __global__ __launch_bounds__(kCtxWaves * 64) __attribute__((amdgpu_waves_per_eu(
         return r;
     };
     auto load_idx = [&](const Bounds& b) {           // unconditional: bins an element does not have replay a valid entry
-        Idx x;
+        Idx x{0, 0};
+        if constexpr (PLANNED) return x;
         x.i0 = oi_base[min(b.q0, oi_last)];
         x.i1 = oi_base[min(b.q0 + 1, oi_last)];
         return x;
     };
     auto load_rows = [&](int64_t tile_, const Bounds& b, const Idx& x) {
         Rows r;
-        const int kk = b.cm < 0 ? 3 - kq : kq;
-        const int4* r0 = ctx4 + (int64_t)x.i0 * 16 + kk;
-        const int4* r1 = ctx4 + (int64_t)x.i1 * 16 + kk;
         const int64_t row0 = first_row(tile_);
         const int4* rl = L4 + row0 * 16;
         const unsigned lo = row_off(row0) * 16u + (unsigned)kq;
+        if constexpr (PLANNED) {
+            const int4* rr = ctx4 + row0 * 16;
+            r.b[0] = make_int4(0, 0, 0, 0);
 #pragma unroll
-        for (int t = 0; t < 4; ++t) r.a[t] = r0[4 * t];
+            for (int t = 0; t < 4; ++t) r.a[t] = rr[lo + 4u * t];
+        } else {
+            const int kk = b.cm < 0 ? 3 - kq : kq;
+            const int4* r0 = ctx4 + (int64_t)x.i0 * 16 + kk;
+            const int4* r1 = ctx4 + (int64_t)x.i1 * 16 + kk;
 #pragma unroll
-        for (int t = 0; t < 4; ++t) r.b[t] = r1[4 * t];
+            for (int t = 0; t < 4; ++t) r.a[t] = r0[4 * t];
+#pragma unroll
+            for (int t = 0; t < 4; ++t) r.b[t] = r1[4 * t];
+        }
 #pragma unroll
         for (int t = 0; t < 4; ++t) r.l[t] = rl[lo + 4u * t];
         return r;
@@ -778,7 +823,13 @@ __global__ __launch_bounds__(kCtxWaves * 64) __attribute__((amdgpu_waves_per_eu(
         const bool minus = b_c.cm < 0;
         // region counts of the element: sum of its bins' context rows (sequence_tools.py:630-631), integers
         int rcv[4][4], lv[4][4];
-        {
+        if constexpr (PLANNED) {
+#pragma unroll
+            for (int t = 0; t < 4; ++t) {
+                rcv[t][0] = r_c.a[t].x; rcv[t][1] = r_c.a[t].y; rcv[t][2] = r_c.a[t].z; rcv[t][3] = r_c.a[t].w;
+                lv[t][0] = r_c.l[t].x; lv[t][1] = r_c.l[t].y; lv[t][2] = r_c.l[t].z; lv[t][3] = r_c.l[t].w;
+            }
+        } else {
             const int m0 = cnt > 0 ? -1 : 0, m1 = cnt > 1 ? -1 : 0;
 #pragma unroll
             for (int t = 0; t < 4; ++t) {
@@ -789,7 +840,7 @@ __global__ __launch_bounds__(kCtxWaves * 64) __attribute__((amdgpu_waves_per_eu(
                 lv[t][0] = r_c.l[t].x; lv[t][1] = r_c.l[t].y; lv[t][2] = r_c.l[t].z; lv[t][3] = r_c.l[t].w;
             }
         }
-        if (__any(cnt > 2)) {                                    // elements over more than two bins (multi-block, gene-sized)
+        if (!PLANNED && __any(cnt > 2)) {                                    // elements over more than two bins (multi-block, gene-sized)
             const int kk = minus ? 3 - kq : kq;
             for (int j = 2; j < cnt; ++j) {
                 const int4* r = ctx4 + (int64_t)ov_idx[b_c.q0 + j] * 16 + kk;
@@ -840,7 +891,7 @@ __global__ __launch_bounds__(kCtxWaves * 64) __attribute__((amdgpu_waves_per_eu(
             for (int t = t0; t < t0 + 2; ++t) {
 #pragma unroll
                 for (int u = 0; u < 4; ++u) {
-                    const int vr = minus ? rcv[3 - u][3 - t] : rcv[t][u];
+                    const int vr = !PLANNED && minus ? rcv[3 - u][3 - t] : rcv[t][u];   // (the table is stored permuted)
                     const double Ar = (double)vr, Al = (double)lv[t][u];
                     const double* b = tabw + ((4 * t + u) * SL) * 64 + lane;
 #pragma unroll
@@ -1003,13 +1054,15 @@ int accumulate_launch(const double* bin_mu, const double* bin_std, const int32_t
 }
 
 // Compact form of the dot + context stages (dig_element_pipeline with DIG_PIPE_COMPACT_L): one kernel per 48-cohort chunk.
+// planned (DIG_PIPE_ELEMENT_CTX): `bin_ctx` is the [E, 64] table of element_contexts_launch; ov_ptr / ov_idx / strand_minus are not read.
 int accumulate_compact_launch(const int32_t* bin_ctx, const int64_t* ov_ptr, const int32_t* ov_idx, const uint8_t* strand_minus,
                               const int32_t* Lc, const int32_t* gene_length, const double* d_pr, double* P, int32_t* R_SIZE,
                               int32_t* ELT_SIZE, double* P_INDEL, int64_t E, int64_t C, void* stream, unsigned* zero_dwords,
-                              int n_zero)
+                              int n_zero, int planned)
 {
     if (E == 0 || C == 0) return DIG_OK;
-    DIG_REQUIRE(bin_ctx && ov_ptr && ov_idx && strand_minus && Lc && d_pr, "non-null inputs");
+    DIG_REQUIRE(bin_ctx && Lc && d_pr && (planned || (ov_ptr && ov_idx && strand_minus)), "non-null inputs");
+    DIG_REQUIRE(!planned || ((uintptr_t)bin_ctx & 255u) == 0, "element context table (DIG_PIPE_ELEMENT_CTX) 256-byte aligned");
     DIG_REQUIRE(P && R_SIZE && ELT_SIZE && P_INDEL, "non-null outputs");
     const int64_t n_tiles = (E + 15) / 16;
     int grid = (int)std::max<int64_t>(1, std::min<int64_t>(cu_count(), (n_tiles + kCtxWaves - 1) / kCtxWaves));
@@ -1020,7 +1073,7 @@ int accumulate_compact_launch(const int32_t* bin_ctx, const int64_t* ov_ptr, con
         const int rc = dispatch_cut(cut, [&](auto nt, auto nq) -> int {
             // register budget of a SIMD while this kernel runs: 3 waves x 160 (every instantiation; amdgpu_num_vgpr on the kernel) + one
             // 32-register wave of the scale factors' background kernels (dig_suffstats.hip) = 512
-            auto kern = acc_dot_ctx_kernel<nt.value, nq.value>;
+            auto kern = planned ? acc_dot_ctx_kernel<nt.value, nq.value, true> : acc_dot_ctx_kernel<nt.value, nq.value, false>;
             DIG_LAUNCH_STAGE(DIG_PIPE_DOT, kern, dim3(grid), dim3(kCtxWaves * 64), 0, (hipStream_t)stream, bin_ctx, ov_ptr, ov_idx, strand_minus,
                                Lc, d_pr, gene_length, P, R_SIZE, ELT_SIZE, P_INDEL, E, (int)C, ch * kMfmaChunk, (int)(ch == 0),
                                ch == 0 ? zero_dwords : nullptr, n_zero);
@@ -1029,6 +1082,16 @@ int accumulate_compact_launch(const int32_t* bin_ctx, const int64_t* ov_ptr, con
         });
         if (rc) return rc;
     }
+    return DIG_OK;
+}
+
+// Plan-time: the [E, 64] table of the elements' region counts (checked by dig_element_contexts_prepare).
+int element_contexts_launch(const int32_t* bin_ctx, const int64_t* ov_ptr, const int32_t* ov_idx, const uint8_t* strand_minus, int64_t E,
+                            int32_t* elt_ctx, void* stream)
+{
+    hipLaunchKernelGGL(element_contexts_kernel, dim3(grid_for(E * 16, 256)), dim3(256), 0, (hipStream_t)stream, bin_ctx, ov_ptr, ov_idx,
+                       strand_minus, E, elt_ctx);
+    DIG_HIP_TRY(hipGetLastError());
     return DIG_OK;
 }
 

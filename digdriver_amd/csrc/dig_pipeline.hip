@@ -11,7 +11,9 @@
 // Kernel sequence per call: acc_dot_ctx_kernel (contexts + dot, the compact form: DIG_PIPE_COMPACT_L after
 // dig_element_pipeline_prepare) or acc_region_kernel -> acc_dot_mfma_kernel (general form), then
 // element_stats_stream_fused_kernel (which finishes its own slow pairs).  Plan-time helpers live here too:
-// dig_element_pipeline_prepare (compact L) and dig_bin_records_pack (the bin tables as 20-byte records).
+// dig_element_pipeline_prepare (compact L), dig_element_contexts_prepare (the elements' context rows summed once: with
+// DIG_PIPE_ELEMENT_CTX the dot kernel streams that table instead of gathering bin rows) and dig_bin_records_pack (the
+// bin tables as 20-byte records).
 #include <algorithm>
 #include <vector>
 
@@ -47,7 +49,9 @@ int element_stats_launch(const double* mu, const double* sigma, const double* mu
 int accumulate_compact_launch(const int32_t* bin_ctx, const int64_t* ov_ptr, const int32_t* ov_idx, const uint8_t* strand_minus,
                               const int32_t* Lc, const int32_t* gene_length, const double* d_pr, double* P, int32_t* R_SIZE,
                               int32_t* ELT_SIZE, double* P_INDEL, int64_t E, int64_t C, void* stream, unsigned* zero_dwords,
-                              int n_zero);
+                              int n_zero, int planned);
+int element_contexts_launch(const int32_t* bin_ctx, const int64_t* ov_ptr, const int32_t* ov_idx, const uint8_t* strand_minus, int64_t E,
+                            int32_t* elt_ctx, void* stream);
 int compact_L_launch(const int32_t* L, int64_t E, int32_t* Lc, int* mismatch, void* stream);
 
 // workspace of dig_element_pipeline: [accumulate: context rows + parameter table][statistics: worklist][compact L + flag]
@@ -162,6 +166,17 @@ int dig_element_pipeline_prepare(const int32_t* L, int64_t E, int64_t C, void* w
     return DIG_OK;
 }
 
+int dig_element_contexts_prepare(const int32_t* bin_ctx, const int64_t* ov_ptr, const int32_t* ov_idx, const uint8_t* strand_minus,
+                                 int64_t N, int64_t E, int32_t* elt_ctx, void* stream)
+{
+    DIG_REQUIRE(N >= 0 && E >= 0, "N, E >= 0");
+    if (E == 0) return DIG_OK;
+    DIG_REQUIRE(ov_ptr && strand_minus && elt_ctx, "ov_ptr, strand_minus, elt_ctx non-null");
+    DIG_REQUIRE(N == 0 || (bin_ctx && ov_idx), "bin_ctx, ov_idx non-null");     // (N = 0: the CSR is empty, neither is read)
+    DIG_REQUIRE(((uintptr_t)elt_ctx & 255u) == 0, "elt_ctx 256-byte aligned");
+    return element_contexts_launch(bin_ctx, ov_ptr, ov_idx, strand_minus, E, elt_ctx, stream);
+}
+
 int64_t dig_element_records_bytes(int64_t E, int64_t C)
 {
     if (E <= 0 || C <= 0) return 0;
@@ -245,7 +260,11 @@ static int element_pipeline_run(const double* bin_mu, const double* bin_std, con
     const int worklist_clean = (stages & DIG_PIPE_WORKLIST_CLEAN) != 0;
     const int compact = (stages & DIG_PIPE_COMPACT_L) != 0 && N >= 1;
     const int records = (stages & DIG_PIPE_RECORDS) != 0;
-    stages &= ~(DIG_PIPE_WORKLIST_CLEAN | DIG_PIPE_COMPACT_L | DIG_PIPE_RECORDS);
+    const int planned = (stages & DIG_PIPE_ELEMENT_CTX) != 0;       // `bin_ctx` is dig_element_contexts_prepare's [E, 64] table
+    DIG_REQUIRE(!planned || (stages & DIG_PIPE_COMPACT_L), "DIG_PIPE_ELEMENT_CTX is valid only together with DIG_PIPE_COMPACT_L");
+    DIG_REQUIRE(!planned || N >= 1, "DIG_PIPE_ELEMENT_CTX needs N >= 1 (the compact form)");
+    DIG_REQUIRE(!planned || ((uintptr_t)bin_ctx & 255u) == 0, "element context table (DIG_PIPE_ELEMENT_CTX) 256-byte aligned");
+    stages &= ~(DIG_PIPE_WORKLIST_CLEAN | DIG_PIPE_COMPACT_L | DIG_PIPE_RECORDS | DIG_PIPE_ELEMENT_CTX);
     DIG_REQUIRE(stages >= 1 && stages <= 7, "stages: bit mask of DIG_PIPE_CONTEXTS, DIG_PIPE_DOT, DIG_PIPE_STATISTICS");
     DIG_REQUIRE(N >= 0 && E >= 0 && C >= 0, "N, E, C >= 0");
     if (E == 0 || C == 0) return DIG_OK;
@@ -265,7 +284,7 @@ static int element_pipeline_run(const double* bin_mu, const double* bin_std, con
             DIG_REQUIRE(bin_ctx && ov_ptr && ov_idx && strand_minus && d_pr && P && R_SIZE && ELT_SIZE && P_INDEL,
                         "non-null accumulation arguments");
             int rc = accumulate_compact_launch(bin_ctx, ov_ptr, ov_idx, strand_minus, (const int32_t*)((char*)workspace + lay.lc_off),
-                                               gene_length, d_pr, P, R_SIZE, ELT_SIZE, P_INDEL, E, C, stream, wl, 64);
+                                               gene_length, d_pr, P, R_SIZE, ELT_SIZE, P_INDEL, E, C, stream, wl, 64, planned);
             if (rc) return rc;
         }
     } else if (stages & 3) {

@@ -650,7 +650,8 @@ def element_pipeline(bin_mu, bin_std, bin_y, bin_flag, bin_ctx, ov_ptr, ov_idx, 
     if compact:
         plan = PipelinePlan(bin_mu, bin_std, bin_y, bin_flag, bin_ctx, ov_ptr, ov_idx, L, strand_minus, d_pr, obs_snv, obs_samples,
                             obs_indel, out_acc=out_acc, out_stats=out_stats, gene_length=gene_length, compact=compact,
-                            pack_bins=False)               # (one call: packing the tables would cost more than it saves)
+                            pack_bins=False, element_contexts=False)   # (one call: packing the tables, or summing the context rows
+                                                                       #  in a kernel of their own, would cost more than it saves)
         return plan.run(_t(cj, "f64", plan.dev), _t(cj_indel, "f64", plan.dev), stages=stages)
     be = device_backend(bin_mu.device)
     tabs, (N, E, C, n_class) = _bin_tables(be, bin_mu, bin_std, bin_y, bin_flag, bin_ctx, ov_ptr, ov_idx, L, strand_minus,
@@ -712,7 +713,7 @@ class PipelinePlan:
 
     def __init__(self, bin_mu, bin_std, bin_y, bin_flag, bin_ctx, ov_ptr, ov_idx, L, strand_minus, d_pr, obs_snv,
                  obs_samples, obs_indel, out_acc=None, out_stats=None, gene_length=None, compact="auto", workspace=None,
-                 pack_bins=True, records_out=False):
+                 pack_bins=True, records_out=False, element_contexts=True):
         """compact: "auto" (default) checks ONCE, here, on the device whether L repeats every context count three times
         (sequence_tools.py:560-564: true for every elementModel / tiledModel / quickDriver set) and, if so, runs the
         64-context form of the accumulation (contexts + dot in one kernel, half the matrix work); False forces the
@@ -724,7 +725,13 @@ class PipelinePlan:
         records_out: the statistics stage writes tile-blocked records (DIG_PIPE_RECORDS: the ten outputs of a pair -- seven
         statistics, MU, SIGMA, R_OBS | FLAG -- as field f of block i / 64 at [f / 2, i % 64, f % 2]: one aligned 5 120-byte run
         per 64-pair tile instead of eleven store streams) into `self.out_records` [ceil(E C / 64), 5, 64, 2]; `self.stats` and
-        MU / SIGMA / R_OBS / FLAG of `self.acc` are filled by `unpack()` (same bits).  Needs the packed bin records (pack_bins)."""
+        MU / SIGMA / R_OBS / FLAG of `self.acc` are filled by `unpack()` (same bits).  Needs the packed bin records (pack_bins).
+        element_contexts: a compact plan sums the context rows of every element's bins ONCE, here (dig_element_contexts_prepare:
+        a plan-owned [E, 64] int32 table, `self.elt_ctx`, outside the workspace), and its dot kernel streams that table instead
+        of walking the overlaps and gathering bin rows every call (DIG_PIPE_ELEMENT_CTX; integer sums: same bits).  The plan then
+        reads the table, not bin_ctx / ov_ptr / ov_idx / strand_minus (the statistics stage still reads the overlaps): call
+        `recontext()` after changing one of them in place.  Another PipelinePlan over the same tables and element set may be
+        given instead of True: its table is shared.  A plan that is not compact ignores the option."""
         import ctypes
         import torch
         dev = bin_mu.device
@@ -787,6 +794,19 @@ class PipelinePlan:
                           _lib.stream_ptr())
             self.compact = bool(ok.value)
         self._flags = (_lib.DIG_PIPE_COMPACT_L if self.compact else 0) | (_lib.DIG_PIPE_RECORDS if self.records_out else 0)
+        self.elt_ctx = None
+        if self.compact and element_contexts:
+            if isinstance(element_contexts, PipelinePlan):    # several plans over the SAME bins and element set share one table
+                other = element_contexts
+                assert other.elt_ctx is not None and (other.N, other.E) == (self.N, self.E)
+                assert all(other.keep[i].data_ptr() == self.keep[i].data_ptr() for i in (4, 5, 6, 8))
+                self.elt_ctx = other.elt_ctx
+            else:
+                self.elt_ctx = torch.empty((self.E, 64), dtype=torch.int32, device=dev)
+                assert self.elt_ctx.data_ptr() % 256 == 0
+                self.recontext()
+            self._head[4] = p(self.elt_ctx)                   # the `bin_ctx` slot (self.keep still holds the bin table)
+            self._flags |= _lib.DIG_PIPE_ELEMENT_CTX
 
     def unpack(self, cohort_major=False, stream=None, stats=None, rates=None):
         """records_out plans: out_records -> the plane form (self.stats [7, E, C] and MU, SIGMA, R_OBS, FLAG of self.acc) on
@@ -820,6 +840,17 @@ class PipelinePlan:
         with torch.cuda.device(self.dev):
             _lib.call("dig_bin_records_pack", _lib.dev_ptr(k[0]), _lib.dev_ptr(k[1]), _lib.dev_ptr(k[2]), _lib.dev_ptr(k[3]),
                       self.N, self.C, _lib.dev_ptr(self.records), self.records.numel(), _lib.stream_ptr())
+
+    def recontext(self):
+        """(Re)build the table of the elements' summed context rows from the plan's bin_ctx, overlaps and strands on torch's
+        current stream (enqueued, not waited for)."""
+        import torch
+        if self.elt_ctx is None:
+            return
+        k = self.keep
+        with torch.cuda.device(self.dev):
+            _lib.call("dig_element_contexts_prepare", _lib.dev_ptr(k[4]), _lib.dev_ptr(k[5]), _lib.dev_ptr(k[6]), _lib.dev_ptr(k[8]),
+                      self.N, self.E, _lib.dev_ptr(self.elt_ctx), _lib.stream_ptr())
 
     def run(self, cj, cj_indel, stages=7, stream=None):
         """Enqueue the pipeline (or one of its stages) on `stream` (default: torch's current stream)."""

@@ -45,7 +45,8 @@ extern "C" {
                              * and their _host twins (additions); + dig_tile_window_test and its _host twin (additions);
                              * + dig_tile_window_sample_keys, dig_tile_window_samples and their _host twins (additions);
                              * + dig_cnv_segment_deltas, dig_cnv_window_means, their size queries and _host twins (additions);
-                             * + dig_tile_window_census, dig_sparse_window_count, dig_sparse_window_test and their _host twins (additions) */
+                             * + dig_tile_window_census, dig_sparse_window_count, dig_sparse_window_test and their _host twins (additions);
+                             * + dig_element_contexts_prepare / DIG_PIPE_ELEMENT_CTX (additions) */
 
 /* dtype codes for dig_gather_bins */
 #define DIG_F32 0
@@ -197,6 +198,21 @@ int dig_accumulate_elements_host(const double *bin_mu, const double *bin_std, co
  *       Denominators are bit-identical to the general form, numerators differ by the rounding of a regrouped sum (P within
  *       a few ulp; tests/test_gpu_parity.py).  Without the flag the general K = 256 form runs, as before. */
 #define DIG_PIPE_COMPACT_L 16
+/* Element context rows as a plan-time product (compact form only).  The region counts of an element,
+ *     elt_ctx[e, j] = sum over the element's bins of bin_ctx[bin, j]            ('+' strand)
+ *                   = sum over the element's bins of bin_ctx[bin, revcomp(j)]   ('-' strand),
+ *     revcomp(16 t + 4 k + u) = 16 (3 - u) + 4 (3 - k) + (3 - t)                (sequence_tools.py:630-634),
+ * depend on bin_ctx, ov_ptr, ov_idx and strand_minus only -- the genome's bins and the element set, the same for every cohort
+ * and every call -- and are integers, so forming them once changes no bit of any output.
+ *   dig_element_contexts_prepare  PLAN TIME, once per element set (again after bin_ctx / ov_* / strand_minus changed): writes
+ *       the [E, 64] int32 table (caller-owned, 256-byte aligned; the table the general form's CONTEXTS stage leaves at the
+ *       start of its workspace).  An element without bins gets zeros.  Enqueued on `stream`; nothing is waited for.
+ *   DIG_PIPE_ELEMENT_CTX  OR into `stages` together with DIG_PIPE_COMPACT_L (alone: DIG_EINVAL): the `bin_ctx` argument of
+ *       dig_element_pipeline is then that table, and the DOT stage streams it like the compact L (no CSR walk, no gather,
+ *       no strand selects in acc_dot_ctx_kernel); the STATISTICS stage still reads ov_ptr / ov_idx.  Same bits as without. */
+#define DIG_PIPE_ELEMENT_CTX 64
+int dig_element_contexts_prepare(const int32_t *bin_ctx, const int64_t *ov_ptr, const int32_t *ov_idx,
+                                 const uint8_t *strand_minus, int64_t N, int64_t E, int32_t *elt_ctx, void *stream);
 /* Record-major outputs of the statistics stage (ABI 9).  The stage has eleven outputs per (element, cohort) pair -- the seven
  * planes of dig_element_stats and MU, SIGMA, R_OBS, FLAG of the accumulation (transfer_tools.py:343-344,473-482,594-615,
  * 731-747,1086-1087; genic_driver_tools.py:404-417) -- i.e. eleven store streams whose tile starts fall on odd 8-byte
