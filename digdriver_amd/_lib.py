@@ -121,6 +121,8 @@ _SIGNATURES = {
     "dig_group_fisher_host": [_vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _int],
     "dig_group_sums": [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp],
     "dig_group_sums_host": [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp, _int],
+    "dig_nb_power": [_vp] * 5 + [_i64, _i64, _vp, _int, ctypes.c_int32, _vp, _vp, _vp],
+    "dig_nb_power_host": [_vp] * 5 + [_i64, _i64, _vp, _int, ctypes.c_int32, _vp, _vp, _int],
     "dig_tile_sample_keys": [_vp, _vp, _i64, _vp, _i64] + [_vp] * 5 + [_int] + [_i64] * 4 + [_vp, _vp],
     "dig_tile_sample_keys_host": [_vp, _vp, _i64, _vp, _i64] + [_vp] * 5 + [_int] + [_i64] * 4 + [_vp, _int],
     "dig_tile_sample_counts": [_vp] + [_i64] * 6 + [_vp, _vp, _vp],

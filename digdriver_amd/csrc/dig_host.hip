@@ -705,6 +705,20 @@ int dig_group_sums_host(const double* x, const double* gate, const uint8_t* memb
                    nullptr);
 }
 
+int dig_nb_power_host(const double* alpha, const double* theta, const double* pi, const double* scale, const double* level, int64_t rows,
+                      int64_t n, const double* folds, int n_folds, int32_t k_max, int32_t* k_crit, double* power, int device)
+{
+    int64_t chunks = 0;
+    if (int rc = nb_power_sizes(__func__, rows, n, folds, n_folds, k_max, power, &chunks)) return rc;
+    for (int j = 0; j < n_folds; ++j) DIG_REQUIRE(folds[j] > 0.0 && folds[j] < HUGE_VAL, "folds finite and > 0");
+    const size_t m = (size_t)rows * n;
+    if (m == 0) return DIG_OK;
+    DIG_REQUIRE(alpha && theta && pi && level && k_crit, "non-null alpha, theta, pi, level, k_crit");
+    Staging st(device);
+    return st.call(dig_nb_power, st.in(alpha, m), st.in(theta, m), st.in(pi, m), st.in(scale, rows), st.in(level, rows), rows, n,
+                   st.in(folds, n_folds), n_folds, k_max, st.out(k_crit, m), n_folds ? st.out(power, m * n_folds) : nullptr, nullptr);
+}
+
 int dig_scale_suffstats_host(const double* bin_mu, const uint8_t* bin_flag, int64_t N, int64_t C, double* out_sum, int device)
 {
     DIG_REQUIRE(N >= 0 && C >= 0, "N, C >= 0");

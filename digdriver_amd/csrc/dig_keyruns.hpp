@@ -47,6 +47,11 @@ int row_select_sizes(const char* fn, int64_t rows, int64_t n, int64_t* chunks);
 // R * chunks < 2^31
 int group_sizes(const char* fn, int64_t R, int64_t C, int64_t E, int64_t M, int64_t* chunks);
 
+// dig_nbpower.hip: what dig_nb_power and its host twin check without looking at an array (include/dig_hip.h lists it), and the chunks
+// (one per workgroup) of a row
+int nb_power_sizes(const char* fn, int64_t rows, int64_t n, const double* folds, int n_folds, int32_t k_max, const double* power,
+                   int64_t* chunks);
+
 // dig_tilewindows.hip: tile_select_sizes and 1 <= width <= DIG_TILE_WINDOW_MAX_WIDTH, for dig_tile_window_test and its host twin
 int tile_window_sizes(const char* fn, int64_t C, int64_t R, int64_t T, int32_t width);
 

@@ -32,11 +32,11 @@ attributes of `DigPretrain.py countMutations` for C maps from one such call over
 (tests/test_gpu_target_cohorts.py).
 
 What the routes share, each written once:
-    _element_planes   overlaps, tabulation, scale callback, plan, unpack, gamma -> planes()     element_pass (element, calls, meta), quick
+    _element_planes   overlaps, tabulation, scale callback, plan, unpack, gamma -> planes()     element_pass (element, calls, meta, power), quick
     _select_hits, _hit_frames, _check_cut   q-values, cut, row_select, gather, hit frames       run_element_calls, run_element_meta_calls
     _gene_row_counts, _gene_frame_columns, _gene_frame_done   rows -> gene_counts -> columns    gene, target
     _run_and_write    files written while the frames behind them are assembled                  the five run_and_write_*_cohorts
-    _write_frames     finished frames to files, several at a time                               write_results, the calls' and the groups' files
+    _write_frames     finished frames to files, several at a time                               write_results, the calls', the groups' and the power files
     _writer_threads, _usable_cores   every pool's size, from the cores the process may use      all of the above, _encode_all_mutations
 """
 import numpy as np
@@ -595,6 +595,141 @@ def run_and_write_element_meta(f_muts, f_pretrained, f_element_data, save_key, g
     frames = run(f_muts, f_pretrained, f_element_data, save_key, groups, labels=labels, **kw)
     sfx = '.meta.hits.txt' if cut else '.meta.results.txt'
     return frames, _write_frames(frames, [os.path.join(outdir, f.attrs['group'] + sfx) for f in frames], write_threads)
+
+
+# ---------------------------------------------------------------------------------------------
+# power of the element route: could an element that was not called have been called at all?
+# ---------------------------------------------------------------------------------------------
+_POWER_CUTS = {'PVAL_SNV_BURDEN': ('EXP_SNV', 0, 'OBS_SNV'), 'PVAL_SAMPLE_BURDEN': ('EXP_SNV', 0, 'OBS_SAMPLES'),
+               'PVAL_INDEL_BURDEN': ('EXP_INDEL', 4, 'OBS_INDEL')}      # cut_on -> the EXP column, its plane of S, the OBS plane
+
+
+def _check_power(pval_max, fdr, bonferroni, cut_on, folds, power_min, labels, C):
+    """The arguments of run_element_power, checked before a file is read; returns (the folds as floats, their column labels)."""
+    if sum(v is not None for v in (pval_max, fdr, bonferroni)) != 1:
+        raise ValueError("exactly one of pval_max, fdr and bonferroni must be given")
+    if cut_on == 'PVAL_MUT_BURDEN':
+        raise ValueError("cut_on = PVAL_MUT_BURDEN has no critical count (Fisher's method over two tests): one of %s" % ", ".join(_POWER_CUTS))
+    if cut_on not in _POWER_CUTS:
+        raise ValueError("cut_on: one of %s" % ", ".join(_POWER_CUTS))
+    folds = [float(f) for f in folds]
+    tags = ['%g' % f for f in folds]
+    if not 1 <= len(folds) <= engine.NB_POWER_MAX_FOLDS or not all(0.0 < f < float("inf") for f in folds) or len(set(tags)) != len(tags):
+        raise ValueError("folds: one to %d different folds, each finite and > 0" % engine.NB_POWER_MAX_FOLDS)
+    if not 0.0 < power_min <= 1.0:
+        raise ValueError("power_min: a power within (0, 1]")
+    if labels is not None and len(labels) != C:
+        raise ValueError("labels: one label per cohort (%d)" % C)
+    return folds, tags
+
+
+def power_levels(P, pval_max=None, fdr=None, bonferroni=None):
+    """The level of run_element_power per row of the p-value plane P f64 [C, E] on the device, by the one of the three rules that is
+    given: (level f64 [C], n_testable [C]: the row's non-NaN values, n_hits [C]: its values <= the level; under fdr the row's hits at
+    that FDR, from nb_model.bh_cut and engine.row_select_counts), host arrays.  A row without a testable value gets a NaN level."""
+    C = int(P.shape[0])
+    n_testable = (~P.isnan()).sum(dim=1).cpu().numpy()
+    with np.errstate(all="ignore"):
+        if fdr is not None:
+            lists, q = _ragged_qvalues(P)
+            ptr = lists["row_ptr"]
+            cuts = np.array([nb_model.bh_cut(lists["score"][ptr[c]:ptr[c + 1]], q[ptr[c]:ptr[c + 1]], fdr) for c in range(C)])
+            n_hits = engine.row_select_counts(P, cuts).sum(dim=1).cpu().numpy()
+            level = float(fdr) * np.maximum(n_hits, 1) / n_testable
+        else:
+            level = np.full(C, float(pval_max)) if pval_max is not None else float(bonferroni) / n_testable
+        level = np.where(n_testable > 0, level, np.nan)
+    if fdr is None:
+        n_hits = engine.row_select_counts(P, level).sum(dim=1).cpu().numpy()
+    return level, n_testable, n_hits
+
+
+def run_element_power(f_muts, f_pretrained, f_element_data, save_key, pval_max=None, fdr=None, bonferroni=None,
+                      cut_on='PVAL_SNV_BURDEN', folds=(2.0, 5.0, 10.0), power_min=0.8, k_max=1 << 20, labels=None, scale_factors=None,
+                      max_muts_per_sample=3e9, max_muts_per_elt_per_sample=3e9, device=0, timings=None, read_workers=None,
+                      output_form="records", element_pass=None):
+    """For every (cohort, element): the CRITICAL COUNT of the burden test `cut_on` at the cohort's level -- the smallest count at which
+    the element would pass the cut -- and the POWER at it, the probability of reaching that count were the element under selection of
+    fold f (the reference's alternative, selection_coefficient: the same ALPHA, THETA Pi times f); engine.nb_power over the planes of
+    element_pass.  Returns (one frame per cohort, the per-element summary frame).
+    Exactly one of the three levels; with n_c the non-NaN values of cut_on in cohort c:
+        pval_max     the level is pval_max in every cohort
+        bonferroni   bonferroni / n_c
+        fdr          fdr max(h_c, 1) / n_c, h_c the cohort's hits at that FDR (nb_model.bh_cut, engine.row_select_counts): the
+                     Benjamini-Hochberg line at the last rejected rank -- an element whose p-value fell below it would be called; a
+                     cohort without hits gets the first step, fdr / n_c
+    (n_c = 0: a NaN level, hence K_CRIT = -1 and NaN powers in that cohort).  cut_on: PVAL_SNV_BURDEN, PVAL_SAMPLE_BURDEN or
+    PVAL_INDEL_BURDEN (PVAL_MUT_BURDEN has no critical count; an indel column that a cohort lacks is the ValueError of
+    run_element_calls).  folds: one to eight different folds, finite and > 0.
+    Frame c: index ELT; ELT_SIZE, EXP_<X>, OBS_<X>, the cut_on column, K_CRIT (-1: out of reach within k_max, or not defined),
+    POWER_F<fold> per fold (the fold printed with %g; 0.0 where the level is out of reach, NaN where K is not defined), POWERED (bool:
+    the power at the LARGEST fold >= power_min); attrs level, n_testable (n_c), n_hits (the elements with cut_on <= the level; h_c
+    under fdr).
+    Summary frame: index ELT; N_COHORTS_TESTED (the cohorts whose cut_on is a number), N_COHORTS_POWERED_F<fold> per fold (the cohorts
+    with that power >= power_min, summed on the device), MIN_K_CRIT (the smallest K_CRIT >= 0 over the cohorts, -1 if none),
+    BEST_COHORT (the cohort with the largest power at the largest fold, ties to the lowest cohort: its label from `labels`, without
+    labels its index; '' (-1) where no cohort's power is a number).  The other options as run_element_cohorts takes them."""
+    import torch
+    folds, tags = _check_power(pval_max, fdr, bonferroni, cut_on, folds, power_min, labels, len(f_muts))
+    D, names, st_ = _planes_of(element_pass, f_muts, f_pretrained, f_element_data, save_key, scale_factors, max_muts_per_sample,
+                               max_muts_per_elt_per_sample, device, timings, read_workers, output_form)
+    S = D['S']
+    C, E = D['MU'].shape
+    exp_name, exp_plane, obs_name = _POWER_CUTS[cut_on]
+    indel = cut_on == 'PVAL_INDEL_BURDEN'
+    if indel:
+        have_indel = (D['OBS_INDEL'].sum(dim=1) != 0).cpu().numpy()
+        if not have_indel.all():
+            raise ValueError("cut_on = %s: cohorts %s have no indel columns" % (cut_on, [c for c in range(C) if not have_indel[c]]))
+    P = S[_PVAL_PLANES[cut_on]]                                                       # [C, E]
+    level, n_testable, n_hits = power_levels(P, pval_max, fdr, bonferroni)
+    if indel:
+        got = engine.nb_power(D['ALPHA'], S[3], D['P_INDEL'].expand(C, E).contiguous(), level, folds=folds, k_max=k_max)
+    else:
+        got = engine.nb_power(D['ALPHA'], D['THETA'], D['P0'], level, scale=D['CJ'], folds=folds, k_max=k_max)
+    K, power = got["k_crit"], got["power"]                                            # [C, E], [F, C, E]
+    # the summary over the cohort axis, on the device
+    top = int(np.argmax(folds))
+    n_powered = (power >= power_min).sum(dim=1)                                       # [F, E] (a NaN power is not >=)
+    min_k = torch.where(K >= 0, K, torch.iinfo(torch.int32).max).min(dim=0).values
+    min_k = torch.where((K >= 0).any(dim=0), min_k, -1)
+    pw = torch.where(power[top].isnan(), float("-inf"), power[top])                   # [C, E]
+    cohort = torch.arange(C, device=pw.device)[:, None]
+    best = torch.where(pw == pw.max(dim=0).values, cohort, C).min(dim=0).values      # the lowest cohort among the largest powers
+    best = torch.where(power[top].isnan().all(dim=0), -1, best)
+    n_tested = (~P.isnan()).sum(dim=0)
+    st_.mark("power")
+    X = {k: v.cpu().numpy() for k, v in dict(ELT_SIZE=D['ELT_SIZE'], EXP=S[exp_plane], OBS=D[obs_name], P=P, K=K, POWER=power,
+                                             N_POWERED=n_powered, MIN_K=min_k, BEST=best, N_TESTED=n_tested).items()}
+    st_.mark("d2h")
+    index = pd.Index(names, name='ELT')
+    frames = []
+    for c in range(C):
+        d = {'ELT_SIZE': X['ELT_SIZE'], exp_name: X['EXP'][c], obs_name: X['OBS'][c].astype(float), cut_on: X['P'][c],
+             'K_CRIT': X['K'][c].astype(np.int64)}
+        d.update({'POWER_F' + t: X['POWER'][j, c] for j, t in enumerate(tags)})
+        d['POWERED'] = X['POWER'][top, c] >= power_min
+        frames.append(pd.DataFrame(d, index=index))
+        frames[-1].attrs.update(level=float(level[c]), n_testable=int(n_testable[c]), n_hits=int(n_hits[c]))
+    d = {'N_COHORTS_TESTED': X['N_TESTED'].astype(np.int64)}
+    d.update({'N_COHORTS_POWERED_F' + t: X['N_POWERED'][j].astype(np.int64) for j, t in enumerate(tags)})
+    d['MIN_K_CRIT'] = X['MIN_K'].astype(np.int64)
+    best = X['BEST'].astype(np.int64)
+    d['BEST_COHORT'] = best if labels is None else np.array([str(v) for v in labels] + [''], dtype=object)[best]
+    st_.mark("frames")
+    return frames, pd.DataFrame(d, index=index)
+
+
+def run_and_write_element_power(f_muts, f_pretrained, f_element_data, save_key, outdir, prefixes, write_threads=None, **kw):
+    """run_element_power (labels: the prefixes, unless given) with cohort c's frame written to <outdir>/<prefix>.power.txt and the
+    summary frame to <outdir>/elements.power.txt, as the calls' files are written (_write_frames).  Returns (frames, summary, paths:
+    the cohorts' files, then the summary's)."""
+    import os
+    kw.setdefault('labels', list(prefixes))
+    frames, summary = run_element_power(f_muts, f_pretrained, f_element_data, save_key, **kw)
+    assert len(prefixes) == len(frames)
+    paths = [os.path.join(outdir, pfx + '.power.txt') for pfx in prefixes] + [os.path.join(outdir, 'elements.power.txt')]
+    return frames, summary, _write_frames(frames + [summary], paths, write_threads)
 
 
 def _writer_threads(n, write_threads=None):

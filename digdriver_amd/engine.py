@@ -1784,6 +1784,42 @@ def group_sums(x, member, gate=None, device=0):
     return _group_launches(be, M, R, E, flat, ("f64",), call)[0]
 
 
+NB_POWER_MAX_FOLDS = 8                                   # DIG_NB_POWER_MAX_FOLDS (include/dig_hip.h)
+
+
+def nb_power(alpha, theta, pi, level, scale=None, folds=(), k_max=1 << 20, device=0):
+    """Critical counts of the upper mid-p burden test and the power at them (dig_nb_power): alpha, theta, pi f64 [R, n] (R rows =
+    cohorts; a [n] input is R = 1), level f64 [R] and scale f64 [R] or None (a single value stands for every row), folds: at most 8
+    finite numbers > 0.  With theta' = theta * scale and p(f) = 1 / ((theta' * pi) * f + 1), k_crit is the smallest k in [0, k_max]
+    with nb_pvalue_greater_midp(k, alpha, p(1)) <= level -- -1 where none reaches it, the statistic is NaN or the level is not inside
+    (0, 1) -- and power[j] = nb_pvalue_greater(k_crit, alpha, p(folds[j])): 0.0 where the level is out of reach, NaN for the other
+    two.  Returns dict(k_crit i32 [R, n], power f64 [F, R, n], None without folds) -- [n] and [F, n] for 1-D planes.  ValueError for
+    a refused requirement.  CUDA tensors in -> CUDA tensors out."""
+    be = backend_of(alpha, theta, pi, level, scale, device=device)
+    alpha = be.arr(alpha, "f64")
+    if alpha.ndim not in (1, 2):
+        raise ValueError("alpha must be [n] or [R, n]")
+    flat = alpha.ndim == 1
+    R, n = (1, int(alpha.shape[0])) if flat else (int(s) for s in alpha.shape)
+    alpha, theta, pi = (be.arr(x, "f64").reshape((R, n)) for x in (alpha, theta, pi))
+    folds = np.ascontiguousarray(np.atleast_1d(np.asarray(folds, np.float64)))
+    if folds.ndim != 1 or folds.shape[0] > NB_POWER_MAX_FOLDS or not (np.isfinite(folds) & (folds > 0)).all():
+        raise ValueError("folds: at most %d finite numbers > 0, not %r" % (NB_POWER_MAX_FOLDS, folds.tolist()))
+    if int(k_max) != k_max or not 0 <= k_max <= 1 << 30:
+        raise ValueError("k_max must be an integer in [0, 2^30], not %r" % (k_max,))
+    F = int(folds.shape[0])
+    # (a Python number is made a float64 array first: as a tensor it would be rounded to float32)
+    level, scale = (_per_cohort(be, x if x is None or is_cuda(x) else np.asarray(x, np.float64), R) for x in (level, scale))
+    k_crit, power, folds = be.empty((R, n), "i32"), be.empty((F, R, n), "f64") if F else None, be.arr(folds, "f64") if F else None
+    with _requirements_as_value_errors():
+        if R * n:                                            # (an empty tensor has no address, and a NULL power with folds is refused)
+            be.call("dig_nb_power", be.ptr(alpha), be.ptr(theta), be.ptr(pi), be.ptr(scale), be.ptr(level), R, n, be.ptr(folds), F,
+                    int(k_max), be.ptr(k_crit), be.ptr(power))
+    if flat:
+        k_crit, power = k_crit.reshape(n), power.reshape(F, n) if F else None
+    return dict(k_crit=k_crit, power=power)
+
+
 # ---------------------------------------------------------------------------
 # scale factors in canonical chunks: identical bits for any sharding of the bins (dig_scale_suffstats_chunked)
 # ---------------------------------------------------------------------------

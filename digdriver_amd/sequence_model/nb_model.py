@@ -92,6 +92,20 @@ def fisher_combine_groups(p, member, device=0):
     return got
 
 
+def nb_critical_count(alpha, p, level, k_max=1 << 20, device=0):
+    """The smallest count k in [0, k_max] at which nb_pvalue_greater_midp(k, alpha, p) <= level (one number), per entry of the broadcast
+    of alpha and p; -1 where no k <= k_max reaches the level, the statistic is NaN or the level is not inside (0, 1).  The one-array
+    convenience of engine.nb_power, called with theta = (1 - p) / p and pi = 1: the kernel's own p = 1 / (theta + 1) then reproduces p
+    only to rounding (an ulp or two), so a count whose statistic lies within that of the level may differ; a caller that needs the
+    route's bits hands engine.nb_power the route's planes.  i32 of the inputs' shape; device tensors in -> a device tensor out."""
+    from .. import engine
+    be = backend_of(alpha, p, device=device)
+    alpha, p = be.broadcast((alpha, p), "f64")
+    got = engine.nb_power(alpha.reshape(-1), ((1.0 - p) / p).reshape(-1), be.broadcast((1.0, alpha), "f64")[0].reshape(-1), level,
+                          k_max=k_max, device=device)["k_crit"]
+    return got.reshape(tuple(alpha.shape))
+
+
 # ---------------------------------------------------------------------------------------------
 # per-base / tiled route (nb_model.py:126-234, 340-342)
 # ---------------------------------------------------------------------------------------------

@@ -602,6 +602,34 @@ int dig_group_sums(const double *x, const double *gate, const uint8_t *member, i
 int dig_group_sums_host(const double *x, const double *gate, const uint8_t *member, int64_t R, int64_t C, int64_t E, int64_t M,
                         double *out, int device);
 
+/* ---- the power of the element route's burden test: critical counts and the chance of reaching them (additive: the ABI version
+ * stays) ---------------------------------------------------------------------------------------------------------------------- *
+ * Planes alpha, theta, pi are f64 [rows, n] (rows = cohorts, n elements, n contiguous); scale f64 [rows] (NULL: 1), level f64
+ * [rows]; folds f64 [n_folds], in device memory for dig_nb_power.  Per pair (r, e), every product ONE IEEE multiplication, left to
+ * right, without contraction:
+ *   theta' = theta[r, e] * scale[r];   p(f) = 1 / ((theta' * pi[r, e]) * f + 1)      (f = 1: the p of the statistics block)
+ *   k_crit[r, e] = K = the smallest integer k in [0, k_max] with nb_pvalue_greater_midp(k, alpha, p(1)) <= level[r]
+ *     (nb_model.py:271-278, the statistic of dig_nb_midp_upper; it falls strictly in k, M(k) - M(k + 1) = (pmf(k) + pmf(k + 1)) / 2,
+ *     so K is well defined).  K = -1 where (a) no k <= k_max reaches the level, (b) the statistic is NaN (alpha or p outside what
+ *     dig_nb_midp_upper accepts, a NaN input), (c) level[r] is not inside (0, 1) (a NaN level included).
+ *   power[j, r, e] = nb_pvalue_greater(K, alpha, p(folds[j])) (nb_model.py:243-256, what dig_nb_greater gives: P(X >= K) under the
+ *     reference's alternative of a fold f of selection, transfer_tools.py:1290-1291, with its k == 0 -> 1 clause and its pmf
+ *     fallback); 0.0 where K = -1 by (a), NaN where K = -1 by (b) or (c).
+ * k_crit i32 [rows, n], power f64 [n_folds, rows, n]; each is written once by its owner: no atomics, no workspace, outputs need not
+ * be zeroed.  The statistic is the project's own (1e-6 relative down to 1e-250, README): where neither M(K - 1) nor M(K) lies within
+ * that of the level, K is the reference's count exactly.
+ * DIG_EINVAL, before anything is read or launched: negative rows or n; n_folds outside [0, DIG_NB_POWER_MAX_FOLDS]; k_max outside
+ * [0, 2^30]; n_folds > 0 with folds NULL; power NULL with n_folds > 0 or non-NULL with n_folds = 0; n >= 2^31 or rows *
+ * ceil(n / 256) >= 2^31 (a chunk per workgroup); with rows * n > 0 a NULL alpha, theta, pi, level or k_crit.  The host twin also
+ * refuses a fold that is not finite and > 0 (the device form cannot look: such a fold gives what the formulas give).  Nothing is
+ * launched when rows * n = 0. */
+#define DIG_NB_POWER_MAX_FOLDS 8
+int dig_nb_power(const double *alpha, const double *theta, const double *pi, const double *scale, const double *level, int64_t rows,
+                 int64_t n, const double *folds, int n_folds, int32_t k_max, int32_t *k_crit, double *power, void *stream);
+int dig_nb_power_host(const double *alpha, const double *theta, const double *pi, const double *scale, const double *level,
+                      int64_t rows, int64_t n, const double *folds, int n_folds, int32_t k_max, int32_t *k_crit, double *power,
+                      int device);
+
 /* ---- the per-base route's counts by sample for many cohorts (additive: the ABI version stays) ------------------- *
  * dig_tile_mut_counts counts rows, whoever they belong to.  These two entry points count them per sample: with n(c, r, t, s) the
  * rows of GLOBAL sample s that dig_tile_mut_counts would count in tile (c, r, t) -- the same pairs, the same skip rules --

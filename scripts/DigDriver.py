@@ -137,7 +137,10 @@ def cmd_element_cohorts(args):
     <outdir>/<outpfx>.results.txt (--qvalues: with the QVAL_* columns behind the others); with --fdr or --pval-max (on --cut-on,
     default PVAL_SNV_BURDEN) only the elements that pass, as <outdir>/<outpfx>.hits.txt, QVAL_* columns included.  With --groups FILE
     also per group of cohorts <outdir>/<group>.meta.results.txt, or under the cut <outdir>/<group>.meta.hits.txt: the members'
-    p-values combined per element by Fisher's method (cohort_batch.run_element_meta / run_element_meta_calls)."""
+    p-values combined per element by Fisher's method (cohort_batch.run_element_meta / run_element_meta_calls).  With --power also,
+    behind the same pass, per cohort <outdir>/<outpfx>.power.txt and <outdir>/elements.power.txt: the critical count of --cut-on at the
+    level of the run's own cut (--pval-max, --fdr, or --bonferroni, which cuts nothing itself) and the power at it under --power-folds
+    (cohort_batch.run_element_power)."""
     n = _cohort_lists(args, manual=False)
     factors = None
     if args.scale_factor_manual or args.scale_factor_indel_manual:
@@ -149,16 +152,17 @@ def cmd_element_cohorts(args):
     if args.fdr is not None and args.pval_max is not None:
         raise SystemExit("ERROR: you must provide at most one of --pval-max and --fdr.")
     cut = args.fdr if args.fdr is not None else args.pval_max
-    if cut is None and args.cut_on is not None:
+    if cut is None and args.cut_on is not None and not args.power:
         raise SystemExit("ERROR: --cut-on needs --fdr or --pval-max.")
     if cut is not None and not 0.0 < cut <= 1.0:
         raise SystemExit("ERROR: --fdr and --pval-max take a level within (0, 1].")
+    power_kw = _power_options(args)
     groups = _read_groups(args.groups, args.outpfx) if args.groups else None
     from digdriver_amd.driver_model import cohort_batch
     print('Running user-defined element driver detection for {} cohorts'.format(n))
     common = dict(scale_factors=factors, max_muts_per_sample=args.max_muts_per_sample,
                   max_muts_per_elt_per_sample=args.max_muts_per_elt_per_sample)
-    if groups is not None:                        # the cohorts' files and the groups' behind ONE pass over the inputs
+    if groups is not None or power_kw is not None:   # the cohorts' files, the groups' and the power behind ONE pass over the inputs
         common['element_pass'] = cohort_batch.element_pass(args.mutation_files, args.maps, args.f_element_data, args.save_key, **common)
 
     def meta(**cut_kw):
@@ -174,12 +178,24 @@ def cmd_element_cohorts(args):
             else:
                 print('\tSaved results to {}'.format(path))
 
+    def power():
+        if power_kw is None:
+            return
+        frames, summary, paths = _without_indel_columns_exit(cohort_batch.run_and_write_element_power, args.mutation_files, args.maps,
+                                                             args.f_element_data, args.save_key, args.outdir, args.outpfx, **power_kw,
+                                                             **common)
+        for pfx, frame, path in zip(args.outpfx, frames, paths):
+            print('\t{}: level {:g}, {} of {} testable elements powered at fold {:g}; saved to {}'.format(
+                pfx, frame.attrs['level'], int(frame['POWERED'].sum()), frame.attrs['n_testable'], max(power_kw['folds']), path))
+        print('\tSaved the per-element summary to {}'.format(paths[-1]))
+
     if cut is None:
         _, paths = cohort_batch.run_and_write_element_cohorts(args.mutation_files, args.maps, args.f_element_data, args.save_key,
                                                               args.outdir, args.outpfx, qvalues=args.qvalues, **common)
         for path in paths:
             print('\tSaved results to {}'.format(path))
         meta()
+        power()
         return
     cut_kw = dict(pval_max=args.pval_max, fdr=args.fdr, cut_on=args.cut_on or 'PVAL_SNV_BURDEN')
     frames, paths = _without_indel_columns_exit(cohort_batch.run_and_write_element_calls, args.mutation_files, args.maps,
@@ -187,6 +203,30 @@ def cmd_element_cohorts(args):
     for pfx, frame, path in zip(args.outpfx, frames, paths):
         print('\t{}: {} hits of {} testable elements; saved to {}'.format(pfx, len(frame), frame.attrs['n_testable'], path))
     _without_indel_columns_exit(meta, **cut_kw)
+    power()
+
+
+def _power_options(args):
+    """--power of elementCohorts and what goes with it, checked before a file is read: None without --power, else the keywords of
+    cohort_batch.run_element_power (the level of the run's own cut, --cut-on, the folds, --power-min)."""
+    if not args.power:
+        if args.bonferroni is not None or args.power_folds is not None or args.power_min is not None:
+            raise SystemExit("ERROR: --bonferroni, --power-folds and --power-min need --power.")
+        return None
+    if sum(v is not None for v in (args.pval_max, args.fdr, args.bonferroni)) != 1:
+        raise SystemExit("ERROR: --power needs exactly one of --pval-max, --fdr and --bonferroni: the level of the critical counts.")
+    if args.bonferroni is not None and not 0.0 < args.bonferroni <= 1.0:
+        raise SystemExit("ERROR: --bonferroni takes a level within (0, 1].")
+    if args.cut_on == 'PVAL_MUT_BURDEN':
+        raise SystemExit("ERROR: --power has no critical count for --cut-on PVAL_MUT_BURDEN (Fisher's method over two tests).")
+    folds = args.power_folds if args.power_folds is not None else [2.0, 5.0, 10.0]
+    if not 1 <= len(folds) <= 8 or not all(0.0 < f < float('inf') for f in folds) or len(set('%g' % f for f in folds)) != len(folds):
+        raise SystemExit("ERROR: --power-folds takes one to eight different folds, each finite and > 0.")
+    power_min = 0.8 if args.power_min is None else args.power_min
+    if not 0.0 < power_min <= 1.0:
+        raise SystemExit("ERROR: --power-min takes a power within (0, 1].")
+    return dict(pval_max=args.pval_max, fdr=args.fdr, bonferroni=args.bonferroni, cut_on=args.cut_on or 'PVAL_SNV_BURDEN',
+                folds=tuple(folds), power_min=power_min)
 
 
 def _without_indel_columns_exit(run, *args, **kw):
@@ -560,6 +600,14 @@ def parse_args(text=None):
     ec.add_argument('--pval-max', type=float, default=None, help='write only the elements with p <= this, as <outpfx>.hits.txt')
     ec.add_argument('--cut-on', default=None, choices=['PVAL_SNV_BURDEN', 'PVAL_SAMPLE_BURDEN', 'PVAL_INDEL_BURDEN', 'PVAL_MUT_BURDEN'],
                     help='the column --fdr / --pval-max select on (default PVAL_SNV_BURDEN)')
+    ec.add_argument('--power', action='store_true', default=False,
+                    help="also write <outpfx>.power.txt and elements.power.txt: per element the critical count of --cut-on at the level "
+                         "of the run's cut and the power at it under a fold of selection")
+    ec.add_argument('--bonferroni', type=float, default=None,
+                    help="with --power: the level is this over the cohort's testable elements (cuts nothing itself)")
+    ec.add_argument('--power-folds', type=float, nargs='+', default=None, help='with --power: the folds of selection (default 2 5 10; at most 8)')
+    ec.add_argument('--power-min', type=float, default=None,
+                    help='with --power: POWERED is the power at the largest fold >= this (default 0.8)')
     ec.add_argument('--groups', type=str, default=None,
                     help='file of two tab-separated columns, group name and cohort prefix (one of --outpfx): per group the cohorts\' '
                          'p-values combined by Fisher\'s method, as <group>.meta.results.txt (under a cut: <group>.meta.hits.txt)')
