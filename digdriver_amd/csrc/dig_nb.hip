@@ -90,7 +90,14 @@ struct ElementStatsArgs {
     const double2* bin_pack;   // dig_bin_records_pack: {Y_PRED, STD^2} per (bin, cohort), or NULL
     const int32_t* bin_yf;     //                       Y_TRUE | (FLAG != 0) << 31
     int rec;              // DIG_PIPE_RECORDS: out is [ceil(n / 64) * 64][kRecOut] doubles (one record per pair) instead of seven planes
+    const char* rates;    // DIG_PIPE_ELEMENT_RATES: dig_element_rates_prepare's table (kRateTile bytes per 64-pair tile), or NULL
 };
+
+// dig_element_rates_prepare's table: per 64-pair tile 64 x {mu, sigma} (16 bytes a lane: one 1 KB run) and then
+// 64 x {R_OBS, FLAG} (8 bytes a lane: one 512-byte run) -- two load instructions of whole lines from one base address.
+constexpr int kRateTile = 64 * 24;
+constexpr int kRateInts = 64 * 16;      // where the {R_OBS, FLAG} run of a tile starts
+typedef int v2i __attribute__((ext_vector_type(2)));
 
 constexpr int kRecOut = 10;       // DIG_REC_DOUBLES: seven statistics, MU, SIGMA, {R_OBS, FLAG}
 // DIG_PIPE_RECORDS: field f of pair i lives in block i / 64 of 5 rows x 64 lanes x 2 doubles, at row f / 2, lane i % 64
@@ -312,10 +319,12 @@ struct StagePtr {            // tile t+2
     int64_t q0, q1;
     uint32_t i, e, c;
     uint32_t ok;             // (one-kernel form) the tile exists: its chunk will be produced
+    int64_t t;               // (planned rates) the tile, clamped to the last one: wave-uniform
 };
 struct StageIn {             // tile t+1
     int32_t idx[kPre];
-    double mu, sg, mu_i, sg_i;   // (GIVEN form only: the pair's parameters as handed in)
+    double mu, sg, mu_i, sg_i;   // (GIVEN form, planned rates: the pair's parameters as handed in)
+    int robs, flag;              // (planned rates only)
     double pi_s, pi_i, cj, cji;
     int k_snv, k_smp, k_ind;
     int64_t q0;
@@ -362,18 +371,24 @@ __device__ __forceinline__ void slow_round(const ElementStatsArgs& a, const unsi
 // from the packed bin records of dig_bin_records_pack (two gathers per bin instead of four);
 // GIVEN = 1 / 2: dig_element_stats (mu / sigma handed in per pair; 2: separate indel parameters) -- the same pipeline,
 // tickets and in-kernel second pass without the CSR and bin stages.
+// RATES (DIG_PIPE_ELEMENT_RATES, with GIVEN = 3): the rate sums were formed ONCE, by element_rates_kernel below (they depend on
+// the packed bin records and the overlaps only), and a tile's {mu, sigma} and {R_OBS, FLAG} arrive with its other streamed
+// inputs, as mu / sigma do in the GIVEN = 1 / 2 forms: no CSR stage, no index loads, no gathers, no loop over further bins and
+// no sqrt.  The four rate outputs are still written, from the streamed values; everything behind the sums is unchanged.
 // (TB and TICKETS stay in the parameter list so that the kernel keeps its name: one 1024-thread workgroup with tickets
 //  is the only form)
-template <int TB, bool TICKETS, int GIVEN = 0, bool REC = false>
+template <int TB, bool TICKETS, int GIVEN = 0, bool REC = false, bool RATES = false>
 __global__ __launch_bounds__(TB) void element_stats_stream_fused_kernel(ElementStatsArgs a)
 {
     static_assert(TB == 1024 && TICKETS, "one 1024-thread workgroup per CU drawing tile tickets");
     static_assert(!REC || GIVEN == 0 || GIVEN == 3, "record outputs: the pipeline's kernel only");
+    static_assert(!RATES || GIVEN == 3, "planned rates: the pipeline's kernel over packed bin records only");
     double* const queue = g_queue;
     unsigned* const tests = g_tests;
     constexpr int QCAP = kQueueCap;
     constexpr bool FUSED = GIVEN == 0 || GIVEN == 3;      // rate sums formed here (3: from the packed bin records)
     constexpr bool PACKED = GIVEN == 3;
+    constexpr bool SUMS = FUSED && !RATES;                // ... from the overlaps and the bin tables, every call
     __shared__ unsigned park_all[TB / 64][kParkCap];
     __shared__ unsigned s_ticket;
     if (threadIdx.x == 0) s_ticket = 0;
@@ -411,7 +426,8 @@ __global__ __launch_bounds__(TB) void element_stats_stream_fused_kernel(ElementS
         s.i = (uint32_t)(past ? n - 1 : iu);
         s.e = (uint32_t)(past ? a.E - 1 : eu);
         s.c = past ? C32 - 1 : cu;
-        if (FUSED) {
+        s.t = min(tile_ptr, n_tiles - 1);
+        if (SUMS) {
             s.q0 = a.ov_ptr[s.e];
             s.q1 = a.ov_ptr[s.e + 1];
         } else
@@ -419,7 +435,7 @@ __global__ __launch_bounds__(TB) void element_stats_stream_fused_kernel(ElementS
         return s;
     };
     // every element's CSR range lies inside [0, nnz); with an empty CSR the index loads replay ov_ptr[0] (= 0: row 0)
-    const int64_t nnz = FUSED ? a.ov_ptr[a.E] : 0;
+    const int64_t nnz = SUMS ? a.ov_ptr[a.E] : 0;
     const int32_t* oi_base = nnz > 0 ? a.ov_idx : reinterpret_cast<const int32_t*>(a.ov_ptr);
     const int64_t oi_last = nnz > 0 ? nnz - 1 : 0;
     auto fetch_in = [&](const StagePtr& s) {
@@ -428,7 +444,17 @@ __global__ __launch_bounds__(TB) void element_stats_stream_fused_kernel(ElementS
         r.nb = (uint32_t)(s.q1 - s.q0);
         r.i = s.i;
         r.c = s.c;
-        if (FUSED) {
+        if constexpr (RATES) {
+            // one base address per tile (scalar), two runs of whole lines; the lanes past n of the last tile read the table's
+            // padding, which holds the last pair's values -- what the replayed last pair gives the live form
+            const char* tb = a.rates + s.t * kRateTile;
+            const v2d ms = __builtin_nontemporal_load(reinterpret_cast<const v2d*>(tb) + lane);
+            const v2i rf = __builtin_nontemporal_load(reinterpret_cast<const v2i*>(tb + kRateInts) + lane);
+            r.mu = ms.x;
+            r.sg = ms.y;
+            r.robs = rf.x;
+            r.flag = rf.y;
+        } else if (FUSED) {
 #pragma unroll
             for (int j = 0; j < kPre; ++j)      // unconditional (the memory counter stays exact): bins past the pair's last replay a valid entry
                 r.idx[j] = oi_base[min(s.q0 + j, oi_last)];
@@ -453,7 +479,7 @@ __global__ __launch_bounds__(TB) void element_stats_stream_fused_kernel(ElementS
     };
     auto fetch_bin = [&](const StageIn& r) {
         StageBin b;
-        if (!FUSED) return b;
+        if (!SUMS) return b;
 #pragma unroll
         for (int j = 0; j < kPre; ++j) {
             const int64_t o = a.small_index ? (int64_t)(__umul24((uint32_t)r.idx[j], C32) + r.c)
@@ -505,7 +531,11 @@ __global__ __launch_bounds__(TB) void element_stats_stream_fused_kernel(ElementS
         // rate sums (genic_driver_tools.py:262-271)
         double mu = 0.0, var = 0.0;
         int robs = 0, flag = 0;
-        if (FUSED) {
+        if constexpr (RATES) {
+            robs = cur.robs;
+            flag = cur.flag;
+        }
+        if (SUMS) {
 #pragma unroll
         for (int j = 0; j < kPre; ++j) {      // (bins past the pair's last were fetched from a replayed row: skipped here)
             if ((uint32_t)j < cur.nb) {
@@ -537,7 +567,7 @@ __global__ __launch_bounds__(TB) void element_stats_stream_fused_kernel(ElementS
         }
         }
         PairRaw w;
-        if (FUSED) {
+        if (SUMS) {
             w.mu = w.mu_i = mu;
             w.sigma = w.sigma_i = sqrt(var);
         } else {
@@ -679,6 +709,38 @@ __global__ __launch_bounds__(TB) void element_stats_stream_fused_kernel(ElementS
             if (b >= ovf) break;
             slow_round(a, segment, b, ovf, false, 0u, sp, g_queue_list[threadIdx.x >> 6], n);
         }
+    }
+}
+
+// Plan-time: the rate sums of every pair as one table (dig_element_rates_prepare) -- what the live form above sums per call from
+// the packed bin records, which depend on the records and the overlaps only.  The additions of the live form in its order
+// (genic_driver_tools.py:262-271: from 0.0, the element's bins first to last; STD^2 is in the records) and the sqrt of this
+// compilation unit: same bits.  One thread per slot of the table, whole tiles: the slots past n repeat the last pair, as
+// the lanes past n of the live form's last tile do.  Persistent over the slots, so any grid is enough.
+__global__ __launch_bounds__(kBlock) void element_rates_kernel(const double2* __restrict__ bin_pack, const int32_t* __restrict__ bin_yf,
+                                                               const int64_t* __restrict__ ov_ptr, const int32_t* __restrict__ ov_idx,
+                                                               int64_t n, int64_t C, char* __restrict__ table)
+{
+    const int64_t slots = ((n + 63) >> 6) << 6;
+    const int64_t stride = (int64_t)gridDim.x * kBlock;
+    for (int64_t s = (int64_t)blockIdx.x * kBlock + threadIdx.x; s < slots; s += stride) {
+        const int64_t i = min(s, n - 1);
+        const int64_t e = i / C, c = i - e * C;
+        double mu = 0.0, var = 0.0;
+        int robs = 0, flag = 0;
+        const int64_t q1 = ov_ptr[e + 1];
+        for (int64_t q = ov_ptr[e]; q < q1; ++q) {
+            const int64_t o = (int64_t)ov_idx[q] * C + c;
+            const double2 mv = bin_pack[o];
+            const int32_t yf = bin_yf[o];
+            mu += mv.x;
+            var += mv.y;
+            robs += yf & 0x7fffffff;
+            flag |= (int)((uint32_t)yf >> 31);
+        }
+        char* tb = table + (s >> 6) * kRateTile;
+        reinterpret_cast<v2d*>(tb)[s & 63] = v2d{mu, sqrt(var)};
+        reinterpret_cast<v2i*>(tb + kRateInts)[s & 63] = v2i{robs, flag};
     }
 }
 
@@ -931,7 +993,20 @@ struct FusedRates {
     const double2* bin_pack;   // dig_bin_records_pack's records, or NULL: {Y_PRED, STD^2} ...
     const int32_t* bin_yf;     // ... and Y_TRUE | (FLAG != 0) << 31 per (bin, cohort)
     int records;               // DIG_PIPE_RECORDS: `out` holds one record of kRecOut doubles per pair
+    const void* rates;         // DIG_PIPE_ELEMENT_RATES: dig_element_rates_prepare's table, or NULL
 };
+
+int64_t element_rates_bytes(int64_t E, int64_t C) { return (E * C + 63) / 64 * kRateTile; }
+
+// Plan-time: the table of the pairs' rate sums (checked by dig_element_rates_prepare).
+int element_rates_launch(const double2* bin_pack, const int32_t* bin_yf, const int64_t* ov_ptr, const int32_t* ov_idx, int64_t E,
+                         int64_t C, void* table, void* stream)
+{
+    hipLaunchKernelGGL(element_rates_kernel, dim3(grid_for(E * C + 63, kBlock)), dim3(kBlock), 0, (hipStream_t)stream, bin_pack, bin_yf,
+                       ov_ptr, ov_idx, E * C, C, (char*)table);
+    DIG_HIP_TRY(hipGetLastError());
+    return DIG_OK;
+}
 
 int element_stats_launch(const double* mu, const double* sigma, const double* mu_indel, const double* sigma_indel,
                          const double* pi_sum, const double* pi_indel, int pi_indel_per_cohort, const int32_t* obs_snv,
@@ -951,7 +1026,7 @@ int element_stats_launch(const double* mu, const double* sigma, const double* mu
     const int use_fd = (C >= 2);   // exact: E * C * C < 2^64 for any problem that fits in memory
     ElementStatsArgs a{mu, sigma, mu_indel, sigma_indel, pi_sum, pi_indel, obs_snv, obs_samples, obs_indel,
                        cj, cj_indel, out, E, C, pi_indel_per_cohort, wl, make_fastdiv(C), use_fd,
-                       nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr, 0};
+                       nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr, 0, nullptr};
     if (fused) {
         a.bin_mu = fused->bin_mu; a.bin_std = fused->bin_std; a.bin_y = fused->bin_y; a.bin_flag = fused->bin_flag;
         a.ov_ptr = fused->ov_ptr; a.ov_idx = fused->ov_idx;
@@ -959,6 +1034,7 @@ int element_stats_launch(const double* mu, const double* sigma, const double* mu
         a.small_index = fused->small_index;
         a.bin_pack = fused->bin_pack; a.bin_yf = fused->bin_yf;
         a.rec = fused->records;
+        a.rates = (const char*)fused->rates;
     }
     if (wl && !worklist_already_zero) DIG_HIP_TRY(hipMemsetAsync(wl, 0, sizeof(unsigned) * kWorkHeader, s));
     bool finished_in_wave = false;
@@ -992,10 +1068,14 @@ int element_stats_launch(const double* mu, const double* sigma, const double* mu
         if (which == 2) {
             // one 1024-thread workgroup per CU drawing tiles from an LDS counter
             int rc;
+            DIG_REQUIRE(!a.rates || a.bin_pack, "DIG_PIPE_ELEMENT_RATES needs the packed bin records (dig_bin_records_pack)");
             if (a.rec) {
                 DIG_REQUIRE(a.bin_pack, "DIG_PIPE_RECORDS needs the packed bin records (dig_bin_records_pack)");
-                rc = launch_fused(element_stats_stream_fused_kernel<1024, true, 3, true>);
-            } else if (a.bin_pack)
+                rc = a.rates ? launch_fused(element_stats_stream_fused_kernel<1024, true, 3, true, true>)
+                             : launch_fused(element_stats_stream_fused_kernel<1024, true, 3, true>);
+            } else if (a.rates)
+                rc = launch_fused(element_stats_stream_fused_kernel<1024, true, 3, false, true>);
+            else if (a.bin_pack)
                 rc = launch_fused(element_stats_stream_fused_kernel<1024, true, 3>);
             else
                 rc = launch_fused(element_stats_stream_fused_kernel<1024, true>);

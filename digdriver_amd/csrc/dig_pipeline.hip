@@ -12,8 +12,9 @@
 // dig_element_pipeline_prepare) or acc_region_kernel -> acc_dot_mfma_kernel (general form), then
 // element_stats_stream_fused_kernel (which finishes its own slow pairs).  Plan-time helpers live here too:
 // dig_element_pipeline_prepare (compact L), dig_element_contexts_prepare (the elements' context rows summed once: with
-// DIG_PIPE_ELEMENT_CTX the dot kernel streams that table instead of gathering bin rows) and dig_bin_records_pack (the
-// bin tables as 20-byte records).
+// DIG_PIPE_ELEMENT_CTX the dot kernel streams that table instead of gathering bin rows), dig_bin_records_pack (the
+// bin tables as 20-byte records) and dig_element_rates_prepare (the pairs' rate sums formed once from those records: with
+// DIG_PIPE_ELEMENT_RATES the statistics kernel streams that table instead of walking the overlaps and gathering records).
 #include <algorithm>
 #include <vector>
 
@@ -33,7 +34,11 @@ struct FusedRates {
     const double2* bin_pack;   // dig_bin_records_pack's records, or NULL: {Y_PRED, STD^2} ...
     const int32_t* bin_yf;     // ... and Y_TRUE | (FLAG != 0) << 31 per (bin, cohort)
     int records;               // DIG_PIPE_RECORDS: `out` holds one record of DIG_REC_DOUBLES doubles per pair
+    const void* rates;         // DIG_PIPE_ELEMENT_RATES: dig_element_rates_prepare's table, or NULL
 };
+int64_t element_rates_bytes(int64_t E, int64_t C);
+int element_rates_launch(const double2* bin_pack, const int32_t* bin_yf, const int64_t* ov_ptr, const int32_t* ov_idx, int64_t E,
+                         int64_t C, void* table, void* stream);
 
 int accumulate_launch(const double* bin_mu, const double* bin_std, const int32_t* bin_y, const uint8_t* bin_flag,
                       const int32_t* bin_ctx, const int64_t* ov_ptr, const int32_t* ov_idx, const int32_t* L, int n_class,
@@ -222,6 +227,28 @@ int dig_bin_records_pack(const double* bin_mu, const double* bin_std, const int3
     return DIG_OK;
 }
 
+int64_t dig_element_rates_bytes(int64_t E, int64_t C)
+{
+    if (E <= 0 || C <= 0) return 0;
+    return element_rates_bytes(E, C);
+}
+
+int dig_element_rates_prepare(const void* bin_records, const int64_t* ov_ptr, const int32_t* ov_idx, int64_t N, int64_t E, int64_t C,
+                              void* rates, int64_t rates_bytes, void* stream)
+{
+    DIG_REQUIRE(N >= 0 && E >= 0 && C >= 0, "N, E, C >= 0");
+    if (E == 0 || C == 0) return DIG_OK;
+    DIG_REQUIRE(ov_ptr && rates, "ov_ptr, rates non-null");
+    DIG_REQUIRE(N == 0 || (bin_records && ov_idx), "bin_records, ov_idx non-null");     // (N = 0: the CSR is empty, neither is read)
+    DIG_REQUIRE(E * C < (int64_t)0xffffffffu, "E * C below 2^32 - 1 (the pipeline's own limit)");
+    DIG_REQUIRE(rates_bytes >= element_rates_bytes(E, C), "rates of at least dig_element_rates_bytes(E, C) bytes");
+    DIG_REQUIRE(((uintptr_t)rates & 255u) == 0, "rates 256-byte aligned");
+    DIG_REQUIRE(((uintptr_t)bin_records & 255u) == 0, "bin_records 256-byte aligned");
+    const BinRecords lay = bin_records_layout(N, C);
+    return element_rates_launch((const double2*)bin_records, (const int32_t*)((const char*)bin_records + lay.yf_off), ov_ptr, ov_idx, E, C,
+                                rates, stream);
+}
+
 static int element_pipeline_run(const double* bin_mu, const double* bin_std, const int32_t* bin_y, const uint8_t* bin_flag,
                          const int32_t* bin_ctx, const int64_t* ov_ptr, const int32_t* ov_idx, const int32_t* L,
                          const uint8_t* strand_minus, const int32_t* gene_length, const double* d_pr,
@@ -264,7 +291,11 @@ static int element_pipeline_run(const double* bin_mu, const double* bin_std, con
     DIG_REQUIRE(!planned || (stages & DIG_PIPE_COMPACT_L), "DIG_PIPE_ELEMENT_CTX is valid only together with DIG_PIPE_COMPACT_L");
     DIG_REQUIRE(!planned || N >= 1, "DIG_PIPE_ELEMENT_CTX needs N >= 1 (the compact form)");
     DIG_REQUIRE(!planned || ((uintptr_t)bin_ctx & 255u) == 0, "element context table (DIG_PIPE_ELEMENT_CTX) 256-byte aligned");
-    stages &= ~(DIG_PIPE_WORKLIST_CLEAN | DIG_PIPE_COMPACT_L | DIG_PIPE_RECORDS | DIG_PIPE_ELEMENT_CTX);
+    const int rates = (stages & DIG_PIPE_ELEMENT_RATES) != 0;       // `bin_mu` is dig_element_rates_prepare's table
+    DIG_REQUIRE(!rates || bin_records, "DIG_PIPE_ELEMENT_RATES needs the packed bin records (dig_bin_records_pack)");
+    DIG_REQUIRE(!rates || bin_mu, "DIG_PIPE_ELEMENT_RATES needs the rate table (dig_element_rates_prepare) as bin_mu");
+    DIG_REQUIRE(!rates || ((uintptr_t)bin_mu & 255u) == 0, "element rate table (DIG_PIPE_ELEMENT_RATES) 256-byte aligned");
+    stages &= ~(DIG_PIPE_WORKLIST_CLEAN | DIG_PIPE_COMPACT_L | DIG_PIPE_RECORDS | DIG_PIPE_ELEMENT_CTX | DIG_PIPE_ELEMENT_RATES);
     DIG_REQUIRE(stages >= 1 && stages <= 7, "stages: bit mask of DIG_PIPE_CONTEXTS, DIG_PIPE_DOT, DIG_PIPE_STATISTICS");
     DIG_REQUIRE(N >= 0 && E >= 0 && C >= 0, "N, E, C >= 0");
     if (E == 0 || C == 0) return DIG_OK;
@@ -295,7 +326,8 @@ static int element_pipeline_run(const double* bin_mu, const double* bin_std, con
     }
     if (!(stages & 4)) return DIG_OK;
     const int small_index = N < ((int64_t)1 << 24) && C < ((int64_t)1 << 24) && N * C < ((int64_t)1 << 32);
-    FusedRates f{bin_mu, bin_std, bin_y, bin_flag, ov_ptr, ov_idx, MU, SIGMA, R_OBS, FLAG, small_index, nullptr, nullptr, records};
+    FusedRates f{bin_mu, bin_std, bin_y, bin_flag, ov_ptr, ov_idx, MU, SIGMA, R_OBS, FLAG, small_index, nullptr, nullptr, records,
+                 rates ? (const void*)bin_mu : nullptr};
     if (records) {
         DIG_REQUIRE(bin_records, "DIG_PIPE_RECORDS needs bin_records (dig_bin_records_pack)");
         DIG_REQUIRE(((uintptr_t)out & 255u) == 0, "record-major `out` 256-byte aligned");

@@ -650,8 +650,8 @@ def element_pipeline(bin_mu, bin_std, bin_y, bin_flag, bin_ctx, ov_ptr, ov_idx, 
     if compact:
         plan = PipelinePlan(bin_mu, bin_std, bin_y, bin_flag, bin_ctx, ov_ptr, ov_idx, L, strand_minus, d_pr, obs_snv, obs_samples,
                             obs_indel, out_acc=out_acc, out_stats=out_stats, gene_length=gene_length, compact=compact,
-                            pack_bins=False, element_contexts=False)   # (one call: packing the tables, or summing the context rows
-                                                                       #  in a kernel of their own, would cost more than it saves)
+                            pack_bins=False, element_contexts=False,   # (one call: packing the tables, or summing the context rows
+                            element_rates=False)                       #  or the rates in a kernel of their own, would cost more than it saves)
         return plan.run(_t(cj, "f64", plan.dev), _t(cj_indel, "f64", plan.dev), stages=stages)
     be = device_backend(bin_mu.device)
     tabs, (N, E, C, n_class) = _bin_tables(be, bin_mu, bin_std, bin_y, bin_flag, bin_ctx, ov_ptr, ov_idx, L, strand_minus,
@@ -713,7 +713,7 @@ class PipelinePlan:
 
     def __init__(self, bin_mu, bin_std, bin_y, bin_flag, bin_ctx, ov_ptr, ov_idx, L, strand_minus, d_pr, obs_snv,
                  obs_samples, obs_indel, out_acc=None, out_stats=None, gene_length=None, compact="auto", workspace=None,
-                 pack_bins=True, records_out=False, element_contexts=True):
+                 pack_bins=True, records_out=False, element_contexts=True, element_rates=True):
         """compact: "auto" (default) checks ONCE, here, on the device whether L repeats every context count three times
         (sequence_tools.py:560-564: true for every elementModel / tiledModel / quickDriver set) and, if so, runs the
         64-context form of the accumulation (contexts + dot in one kernel, half the matrix work); False forces the
@@ -729,9 +729,18 @@ class PipelinePlan:
         element_contexts: a compact plan sums the context rows of every element's bins ONCE, here (dig_element_contexts_prepare:
         a plan-owned [E, 64] int32 table, `self.elt_ctx`, outside the workspace), and its dot kernel streams that table instead
         of walking the overlaps and gathering bin rows every call (DIG_PIPE_ELEMENT_CTX; integer sums: same bits).  The plan then
-        reads the table, not bin_ctx / ov_ptr / ov_idx / strand_minus (the statistics stage still reads the overlaps): call
+        reads the table, not bin_ctx / ov_ptr / ov_idx / strand_minus (the statistics stage reads the overlaps in its live form only: element_rates): call
         `recontext()` after changing one of them in place.  Another PipelinePlan over the same tables and element set may be
-        given instead of True: its table is shared.  A plan that is not compact ignores the option."""
+        given instead of True: its table is shared.  A plan that is not compact ignores the option.
+        element_rates: a plan with packed bin records forms the rate sums of every (element, cohort) pair -- MU, SIGMA, R_OBS, FLAG --
+        ONCE, here (dig_element_rates_prepare: a plan-owned table of 24 bytes per pair, `self.elt_rates`, outside the workspace),
+        and its statistics kernel streams that table instead of walking the overlaps and gathering bin records every call
+        (DIG_PIPE_ELEMENT_RATES; the live form's additions in its order: same bits).  The statistics stage then reads the table, not
+        the records or ov_ptr / ov_idx: `repack_bins()` and `recontext()` both rebuild it, since the tables and the overlaps both
+        feed it.  Another PipelinePlan over the same records and overlaps may be given instead of True: its table is shared.  A plan
+        without packed records ignores the option and sums per call.  A caller that builds a plan and runs it ONCE passes False
+        (engine.element_pipeline, cohort_batch._element_planes): for it the table is an extra write and read of 24 bytes per pair
+        and saves nothing."""
         import ctypes
         import torch
         dev = bin_mu.device
@@ -807,6 +816,20 @@ class PipelinePlan:
                 self.recontext()
             self._head[4] = p(self.elt_ctx)                   # the `bin_ctx` slot (self.keep still holds the bin table)
             self._flags |= _lib.DIG_PIPE_ELEMENT_CTX
+        self.elt_rates = None
+        if self.records is not None and element_rates:
+            if isinstance(element_rates, PipelinePlan):       # several plans over the SAME records and overlaps share one table
+                other = element_rates
+                assert other.elt_rates is not None and (other.N, other.E, other.C) == (self.N, self.E, self.C)
+                assert other.records.data_ptr() == self.records.data_ptr()
+                assert all(other.keep[i].data_ptr() == self.keep[i].data_ptr() for i in (5, 6))
+                self.elt_rates = other.elt_rates
+            else:
+                self.elt_rates = torch.empty(int(_lib.load().dig_element_rates_bytes(self.E, self.C)), dtype=torch.uint8, device=dev)
+                assert self.elt_rates.data_ptr() % 256 == 0
+                self._rerate()
+            self._head[0] = p(self.elt_rates)                 # the `bin_mu` slot (self.keep still holds the bin table)
+            self._flags |= _lib.DIG_PIPE_ELEMENT_RATES
 
     def unpack(self, cohort_major=False, stream=None, stats=None, rates=None):
         """records_out plans: out_records -> the plane form (self.stats [7, E, C] and MU, SIGMA, R_OBS, FLAG of self.acc) on
@@ -832,7 +855,8 @@ class PipelinePlan:
         return o, st
 
     def repack_bins(self):
-        """(Re)build the packed bin records from the plan's bin tables on torch's current stream (waits for it)."""
+        """(Re)build the packed bin records from the plan's bin tables on torch's current stream (waits for it), and the table of
+        the pairs' rate sums from them (enqueued behind it)."""
         import torch
         if self.records is None:
             return
@@ -840,11 +864,25 @@ class PipelinePlan:
         with torch.cuda.device(self.dev):
             _lib.call("dig_bin_records_pack", _lib.dev_ptr(k[0]), _lib.dev_ptr(k[1]), _lib.dev_ptr(k[2]), _lib.dev_ptr(k[3]),
                       self.N, self.C, _lib.dev_ptr(self.records), self.records.numel(), _lib.stream_ptr())
+        self._rerate()
+
+    def _rerate(self):
+        """(Re)build the table of the pairs' rate sums from the packed bin records and the overlaps on torch's current stream
+        (enqueued, not waited for)."""
+        import torch
+        if getattr(self, "elt_rates", None) is None:
+            return
+        k = self.keep
+        with torch.cuda.device(self.dev):
+            _lib.call("dig_element_rates_prepare", _lib.dev_ptr(self.records), _lib.dev_ptr(k[5]), _lib.dev_ptr(k[6]), self.N, self.E,
+                      self.C, _lib.dev_ptr(self.elt_rates), self.elt_rates.numel(), _lib.stream_ptr())
 
     def recontext(self):
         """(Re)build the table of the elements' summed context rows from the plan's bin_ctx, overlaps and strands on torch's
-        current stream (enqueued, not waited for)."""
+        current stream, and the table of the pairs' rate sums from the packed bin records and the overlaps (both enqueued, not
+        waited for)."""
         import torch
+        self._rerate()
         if self.elt_ctx is None:
             return
         k = self.keep

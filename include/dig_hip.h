@@ -46,7 +46,8 @@ extern "C" {
                              * + dig_tile_window_sample_keys, dig_tile_window_samples and their _host twins (additions);
                              * + dig_cnv_segment_deltas, dig_cnv_window_means, their size queries and _host twins (additions);
                              * + dig_tile_window_census, dig_sparse_window_count, dig_sparse_window_test and their _host twins (additions);
-                             * + dig_element_contexts_prepare / DIG_PIPE_ELEMENT_CTX (additions) */
+                             * + dig_element_contexts_prepare / DIG_PIPE_ELEMENT_CTX (additions);
+                             * + dig_element_rates_prepare, dig_element_rates_bytes / DIG_PIPE_ELEMENT_RATES (additions) */
 
 /* dtype codes for dig_gather_bins */
 #define DIG_F32 0
@@ -209,7 +210,7 @@ int dig_accumulate_elements_host(const double *bin_mu, const double *bin_std, co
  *       start of its workspace).  An element without bins gets zeros.  Enqueued on `stream`; nothing is waited for.
  *   DIG_PIPE_ELEMENT_CTX  OR into `stages` together with DIG_PIPE_COMPACT_L (alone: DIG_EINVAL): the `bin_ctx` argument of
  *       dig_element_pipeline is then that table, and the DOT stage streams it like the compact L (no CSR walk, no gather,
- *       no strand selects in acc_dot_ctx_kernel); the STATISTICS stage still reads ov_ptr / ov_idx.  Same bits as without. */
+ *       no strand selects in acc_dot_ctx_kernel); the STATISTICS stage still reads ov_ptr / ov_idx (unless DIG_PIPE_ELEMENT_RATES).  Same bits as without. */
 #define DIG_PIPE_ELEMENT_CTX 64
 int dig_element_contexts_prepare(const int32_t *bin_ctx, const int64_t *ov_ptr, const int32_t *ov_idx,
                                  const uint8_t *strand_minus, int64_t N, int64_t E, int32_t *elt_ctx, void *stream);
@@ -267,6 +268,26 @@ int dig_element_pipeline_host(const double *bin_mu, const double *bin_std, const
 int64_t dig_bin_records_bytes(int64_t N, int64_t C);
 int dig_bin_records_pack(const double *bin_mu, const double *bin_std, const int32_t *bin_y, const uint8_t *bin_flag, int64_t N,
                          int64_t C, void *records, int64_t records_bytes, void *stream);
+/* Element rate sums as a plan-time product (packed bin records only).  MU = sum Y_PRED, SIGMA = sqrt(sum STD^2), R_OBS = sum
+ * Y_TRUE and FLAG = OR of FLAG over a pair's bins (get_region_params_direct, genic_driver_tools.py:258-272) depend on the bin
+ * records and on ov_ptr / ov_idx only -- not on the scale factors, the observed counts or P -- so a caller that runs the
+ * same tables many times forms them once.  The additions are those of the statistics kernel in its order (from 0.0, the
+ * element's bins first to last) and the square root is the same code: the four outputs keep their bits.
+ *   dig_element_rates_prepare  PLAN TIME, once per set of records and overlaps (again after dig_bin_records_pack or a change
+ *       of ov_ptr / ov_idx): writes the table -- per 64-pair tile 64 x {double MU, SIGMA} then 64 x {int32 R_OBS, FLAG}, 1 536
+ *       bytes a tile, pair i = e * C + c in tile i / 64 at lane i % 64; the lanes past E * C of the last tile repeat the last
+ *       pair -- into `rates` (caller-owned, 256-byte aligned, at least dig_element_rates_bytes(E, C) bytes).  An element
+ *       without bins gives 0, 0, 0, 0.  Enqueued on `stream`; nothing is waited for.
+ *   DIG_PIPE_ELEMENT_RATES  OR into `stages` of dig_element_pipeline calls that pass `bin_records` (without: DIG_EINVAL): the
+ *       `bin_mu` argument is then that table, and the STATISTICS stage streams it with its other per-pair inputs (no CSR
+ *       walk, no index loads, no gathers, no loop over further bins, no sqrt in element_stats_stream_fused_kernel); it reads
+ *       neither the bin tables nor the records nor ov_ptr / ov_idx.  MU / SIGMA / R_OBS / FLAG are still written by every
+ *       call.  Same bits as without.  A caller that runs its tables ONCE gains nothing: the table is an extra write and read
+ *       of 24 bytes per pair. */
+#define DIG_PIPE_ELEMENT_RATES 128
+int64_t dig_element_rates_bytes(int64_t E, int64_t C);
+int dig_element_rates_prepare(const void *bin_records, const int64_t *ov_ptr, const int32_t *ov_idx, int64_t N, int64_t E,
+                              int64_t C, void *rates, int64_t rates_bytes, void *stream);
 int dig_element_pipeline(const double *bin_mu, const double *bin_std, const int32_t *bin_y, const uint8_t *bin_flag,
                          const int32_t *bin_ctx, const int64_t *ov_ptr, const int32_t *ov_idx, const int32_t *L,
                          const uint8_t *strand_minus, const int32_t *gene_length, const double *d_pr,
