@@ -18,6 +18,7 @@ DIG_F32, DIG_F64, DIG_I16, DIG_BF16 = 0, 1, 2, 3
 DIG_PIPE_CONTEXTS, DIG_PIPE_DOT, DIG_PIPE_STATISTICS, DIG_PIPE_WORKLIST_CLEAN, DIG_PIPE_COMPACT_L, DIG_PIPE_RECORDS = 1, 2, 4, 8, 16, 32
 DIG_PIPE_ELEMENT_CTX = 64          # `bin_ctx` of dig_element_pipeline is dig_element_contexts_prepare's [E, 64] table (with DIG_PIPE_COMPACT_L)
 DIG_PIPE_ELEMENT_RATES = 128       # `bin_mu` of dig_element_pipeline is dig_element_rates_prepare's table (with `bin_records`)
+DIG_PIPE_ELEMENT_P = 256           # `d_pr` of dig_element_pipeline is dig_element_p_prepare's table (P, P_INDEL, R_SIZE, ELT_SIZE)
 DIG_REC_DOUBLES, DIG_REC_MU, DIG_REC_SIGMA, DIG_REC_ROBS_FLAG = 10, 7, 8, 9
 DIG_CNV_SCAN_CHUNK = 2048          # windows per chunk of dig_cnv_window_means' scan
 GENE_CLASSES = ("SYN", "MIS", "NONS", "SPL", "TRUNC", "NONSYN")
@@ -78,6 +79,7 @@ _SIGNATURES = {
     "dig_element_pipeline_prepare": [_vp, _i64, _i64, _vp, _i64, _vp, _vp],
     "dig_element_contexts_prepare": [_vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp],
     "dig_element_rates_prepare": [_vp, _vp, _vp, _i64, _i64, _i64, _vp, _i64, _vp],
+    "dig_element_p_prepare": [_vp, _vp, _vp, _vp, _i64, _i64, _vp, _i64, _vp],
     "dig_element_pipeline_host": [_vp] * 25 + [_i64, _i64, _i64, _int],
     "dig_gene_stats": [_vp, _vp, _vp, _vp, _vp, _int, _vp, _int, _vp, _vp, _vp, _vp, _int, _vp, _i64, _i64, _vp],
     "dig_gene_stats_host": [_vp, _vp, _vp, _vp, _vp, _int, _vp, _int, _vp, _vp, _vp, _vp, _int, _vp, _i64, _i64, _int],
@@ -213,6 +215,7 @@ _SIZE_QUERIES = {
     "dig_bin_records_bytes": [_i64, _i64],
     "dig_element_records_bytes": [_i64, _i64],
     "dig_element_rates_bytes": [_i64, _i64],
+    "dig_element_p_bytes": [_i64, _i64],
     "dig_bh_workspace": [_i64, _i64],
     "dig_bh_ragged_workspace": [_vp, _i64],
     "dig_mutation_contexts_workspace": [_i64],

@@ -948,6 +948,90 @@ __global__ __launch_bounds__(kCtxWaves * 64) __attribute__((amdgpu_waves_per_eu(
     }
 }
 
+// =======================================================================================
+// P as a plan-time product (DIG_PIPE_ELEMENT_P).  Every input of the accumulation stages -- L, the context rows, gene_length,
+// d_pr -- belongs to the plan, so P, P_INDEL, R_SIZE and ELT_SIZE come out the same call after call.  A plan runs its own
+// accumulation form once, keeps bit copies of the four outputs in one table (element_p_pack_kernel) and every later call
+// streams them back into the caller's outputs (element_p_stream_kernel): 8 bytes in and 8 bytes out per pair instead of the
+// matrix work.  Whatever the form that ran wrote -- NaN / inf of zero denominators included -- is what the table holds.
+// Table: P [E C] f64 | P_INDEL [E] f64 | R_SIZE [E] i32 | ELT_SIZE [E] i32, every section 256-byte aligned.
+// =======================================================================================
+typedef double p_v2d __attribute__((ext_vector_type(2)));
+
+// n pieces of 8 or 16 bytes, four per thread and step of the grid, every load issued before the first store.
+// NT: the source is read once (the table, per call): non-temporal loads.  Stores are ordinary: the statistics kernel reads P next.
+template <typename V, bool NT>
+__device__ __forceinline__ void element_p_pieces(const V* __restrict__ src, V* __restrict__ dst, int64_t n)
+{
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += 4 * stride) {
+        V v[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+            if (i + u * stride < n) v[u] = NT ? __builtin_nontemporal_load(src + i + u * stride) : src[i + u * stride];
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+            if (i + u * stride < n) dst[i + u * stride] = v[u];
+    }
+}
+
+// 16-byte pieces where both sides allow them (the table always does; a caller's P is only promised 8-byte alignment), else 8-byte ones
+template <bool NT>
+__device__ __forceinline__ void element_p_copy(const double* __restrict__ sP, const double* __restrict__ sPI, const int32_t* __restrict__ sRS,
+                                               const int32_t* __restrict__ sES, double* __restrict__ dP, double* __restrict__ dPI,
+                                               int32_t* __restrict__ dRS, int32_t* __restrict__ dES, int64_t n, int64_t E)
+{
+    if ((((uintptr_t)sP | (uintptr_t)dP) & 15u) == 0) {
+        element_p_pieces<p_v2d, NT>(reinterpret_cast<const p_v2d*>(sP), reinterpret_cast<p_v2d*>(dP), n >> 1);
+        if ((n & 1) && blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) dP[n - 1] = sP[n - 1];
+    } else {
+        element_p_pieces<double, NT>(sP, dP, n);
+    }
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < E; e += stride) {
+        dPI[e] = sPI[e];
+        dRS[e] = sRS[e];
+        dES[e] = sES[e];
+    }
+}
+
+// Plan time: the four outputs of an accumulation call -> the table.
+__global__ __launch_bounds__(256) void element_p_pack_kernel(const double* __restrict__ P, const double* __restrict__ P_INDEL,
+                                                             const int32_t* __restrict__ R_SIZE, const int32_t* __restrict__ ELT_SIZE,
+                                                             double* __restrict__ tP, double* __restrict__ tPI, int32_t* __restrict__ tRS,
+                                                             int32_t* __restrict__ tES, int64_t n, int64_t E)
+{
+    element_p_copy<false>(P, P_INDEL, R_SIZE, ELT_SIZE, tP, tPI, tRS, tES, n, E);
+}
+
+// Per call (the DOT stage under DIG_PIPE_ELEMENT_P): the table -> the caller's four outputs; one launch whatever C is.
+__global__ __launch_bounds__(256) void element_p_stream_kernel(const double* __restrict__ tP, const double* __restrict__ tPI,
+                                                               const int32_t* __restrict__ tRS, const int32_t* __restrict__ tES,
+                                                               double* __restrict__ P, double* __restrict__ P_INDEL, int32_t* __restrict__ R_SIZE,
+                                                               int32_t* __restrict__ ELT_SIZE, int64_t n, int64_t E,
+                                                               unsigned* __restrict__ zero_dwords, int n_zero)
+{
+    // (pipeline only) clear the worklist header of the statistics stage that follows on the stream, as the dot kernels do
+    if (zero_dwords && blockIdx.x == 0 && (int)threadIdx.x < n_zero) zero_dwords[threadIdx.x] = 0u;
+    element_p_copy<true>(tP, tPI, tRS, tES, P, P_INDEL, R_SIZE, ELT_SIZE, n, E);
+}
+
+struct EltP {
+    int64_t pindel_off, rsize_off, eltsize_off, bytes;      // (P at 0)
+};
+static EltP element_p_layout(int64_t E, int64_t C)
+{
+    auto up = [](int64_t v) { return (v + 255) / 256 * 256; };
+    EltP t{};
+    t.pindel_off = up(E * C * (int64_t)sizeof(double));
+    t.rsize_off = t.pindel_off + up(E * (int64_t)sizeof(double));
+    t.eltsize_off = t.rsize_off + up(E * (int64_t)sizeof(int32_t));
+    t.bytes = t.eltsize_off + up(E * (int64_t)sizeof(int32_t));
+    return t;
+}
+// four pieces per thread and step: a grid of (n / 2) / 4 threads covers P in one step below the cap
+static int element_p_grid(int64_t E, int64_t C) { return grid_for(std::max<int64_t>((E * C / 2 + 3) / 4, E), 256); }
+
 struct AccWorkspace {
     int32_t* rcp;    // strand-permuted context counts of the elements, [E][64]
     double* tab;     // pre-swizzled MFMA parameter table, [n48][64 steps][3][64]
@@ -1101,6 +1185,36 @@ int compact_L_launch(const int32_t* L, int64_t E, int32_t* Lc, int* mismatch, vo
     DIG_HIP_TRY(hipMemsetAsync(mismatch, 0, sizeof(int), (hipStream_t)stream));
     if (E == 0) return DIG_OK;
     hipLaunchKernelGGL(compact_L_kernel, dim3(grid_for(E * 64, 256)), dim3(256), 0, (hipStream_t)stream, L, E * 64, Lc, mismatch);
+    DIG_HIP_TRY(hipGetLastError());
+    return DIG_OK;
+}
+
+int64_t element_p_bytes(int64_t E, int64_t C) { return element_p_layout(E, C).bytes; }
+
+// Plan-time: bit copies of an accumulation call's P, R_SIZE, ELT_SIZE, P_INDEL in one table (checked by dig_element_p_prepare).
+int element_p_pack_launch(const double* P, const int32_t* R_SIZE, const int32_t* ELT_SIZE, const double* P_INDEL, int64_t E, int64_t C,
+                          void* table, void* stream)
+{
+    const EltP t = element_p_layout(E, C);
+    char* b = (char*)table;
+    hipLaunchKernelGGL(element_p_pack_kernel, dim3(element_p_grid(E, C)), dim3(256), 0, (hipStream_t)stream, P, P_INDEL, R_SIZE, ELT_SIZE,
+                       (double*)b, (double*)(b + t.pindel_off), (int32_t*)(b + t.rsize_off), (int32_t*)(b + t.eltsize_off), E * C, E);
+    DIG_HIP_TRY(hipGetLastError());
+    return DIG_OK;
+}
+
+// The DOT stage of dig_element_pipeline with DIG_PIPE_ELEMENT_P: that table back into the caller's four outputs.
+int element_p_stream_launch(const void* table, double* P, int32_t* R_SIZE, int32_t* ELT_SIZE, double* P_INDEL, int64_t E, int64_t C,
+                            void* stream, unsigned* zero_dwords, int n_zero)
+{
+    if (E == 0 || C == 0) return DIG_OK;
+    DIG_REQUIRE(table && ((uintptr_t)table & 255u) == 0, "element P table (DIG_PIPE_ELEMENT_P) non-null and 256-byte aligned");
+    DIG_REQUIRE(P && R_SIZE && ELT_SIZE && P_INDEL, "non-null outputs");
+    const EltP t = element_p_layout(E, C);
+    const char* b = (const char*)table;
+    DIG_LAUNCH_STAGE(DIG_PIPE_DOT, element_p_stream_kernel, dim3(element_p_grid(E, C)), dim3(256), 0, (hipStream_t)stream, (const double*)b,
+                     (const double*)(b + t.pindel_off), (const int32_t*)(b + t.rsize_off), (const int32_t*)(b + t.eltsize_off), P, P_INDEL,
+                     R_SIZE, ELT_SIZE, E * C, E, zero_dwords, n_zero);
     DIG_HIP_TRY(hipGetLastError());
     return DIG_OK;
 }

@@ -15,6 +15,9 @@
 // DIG_PIPE_ELEMENT_CTX the dot kernel streams that table instead of gathering bin rows), dig_bin_records_pack (the
 // bin tables as 20-byte records) and dig_element_rates_prepare (the pairs' rate sums formed once from those records: with
 // DIG_PIPE_ELEMENT_RATES the statistics kernel streams that table instead of walking the overlaps and gathering records).
+// dig_element_p_prepare keeps bit copies of an accumulation call's P, R_SIZE, ELT_SIZE and P_INDEL -- whose inputs all belong
+// to the plan -- in one table: with DIG_PIPE_ELEMENT_P the DOT stage is element_p_stream_kernel, which writes them back into the
+// caller's outputs instead of forming them again.
 #include <algorithm>
 #include <vector>
 
@@ -58,6 +61,11 @@ int accumulate_compact_launch(const int32_t* bin_ctx, const int64_t* ov_ptr, con
 int element_contexts_launch(const int32_t* bin_ctx, const int64_t* ov_ptr, const int32_t* ov_idx, const uint8_t* strand_minus, int64_t E,
                             int32_t* elt_ctx, void* stream);
 int compact_L_launch(const int32_t* L, int64_t E, int32_t* Lc, int* mismatch, void* stream);
+int64_t element_p_bytes(int64_t E, int64_t C);
+int element_p_pack_launch(const double* P, const int32_t* R_SIZE, const int32_t* ELT_SIZE, const double* P_INDEL, int64_t E, int64_t C,
+                          void* table, void* stream);
+int element_p_stream_launch(const void* table, double* P, int32_t* R_SIZE, int32_t* ELT_SIZE, double* P_INDEL, int64_t E, int64_t C,
+                            void* stream, unsigned* zero_dwords, int n_zero);
 
 // workspace of dig_element_pipeline: [accumulate: context rows + parameter table][statistics: worklist][compact L + flag]
 struct PipeLayout {
@@ -249,6 +257,26 @@ int dig_element_rates_prepare(const void* bin_records, const int64_t* ov_ptr, co
                                 rates, stream);
 }
 
+int64_t dig_element_p_bytes(int64_t E, int64_t C)
+{
+    if (E <= 0 || C <= 0) return 0;
+    return element_p_bytes(E, C);
+}
+
+int dig_element_p_prepare(const double* P, const int32_t* R_SIZE, const int32_t* ELT_SIZE, const double* P_INDEL, int64_t E, int64_t C,
+                          void* table, int64_t table_bytes, void* stream)
+{
+    DIG_REQUIRE(E >= 0 && C >= 0, "E, C >= 0");
+    if (E == 0 || C == 0) return DIG_OK;
+    DIG_REQUIRE(P && R_SIZE && ELT_SIZE && P_INDEL && table, "P, R_SIZE, ELT_SIZE, P_INDEL, table non-null");
+    DIG_REQUIRE(E * C < (int64_t)0xffffffffu, "E * C below 2^32 - 1 (the pipeline's own limit)");
+    DIG_REQUIRE(table_bytes >= element_p_bytes(E, C), "table of at least dig_element_p_bytes(E, C) bytes");
+    DIG_REQUIRE(((uintptr_t)table & 255u) == 0, "table 256-byte aligned");
+    DIG_REQUIRE((((uintptr_t)P | (uintptr_t)P_INDEL) & 7u) == 0 && (((uintptr_t)R_SIZE | (uintptr_t)ELT_SIZE) & 3u) == 0,
+                "P, P_INDEL 8-byte and R_SIZE, ELT_SIZE 4-byte aligned");
+    return element_p_pack_launch(P, R_SIZE, ELT_SIZE, P_INDEL, E, C, table, stream);
+}
+
 static int element_pipeline_run(const double* bin_mu, const double* bin_std, const int32_t* bin_y, const uint8_t* bin_flag,
                          const int32_t* bin_ctx, const int64_t* ov_ptr, const int32_t* ov_idx, const int32_t* L,
                          const uint8_t* strand_minus, const int32_t* gene_length, const double* d_pr,
@@ -295,7 +323,11 @@ static int element_pipeline_run(const double* bin_mu, const double* bin_std, con
     DIG_REQUIRE(!rates || bin_records, "DIG_PIPE_ELEMENT_RATES needs the packed bin records (dig_bin_records_pack)");
     DIG_REQUIRE(!rates || bin_mu, "DIG_PIPE_ELEMENT_RATES needs the rate table (dig_element_rates_prepare) as bin_mu");
     DIG_REQUIRE(!rates || ((uintptr_t)bin_mu & 255u) == 0, "element rate table (DIG_PIPE_ELEMENT_RATES) 256-byte aligned");
-    stages &= ~(DIG_PIPE_WORKLIST_CLEAN | DIG_PIPE_COMPACT_L | DIG_PIPE_RECORDS | DIG_PIPE_ELEMENT_CTX | DIG_PIPE_ELEMENT_RATES);
+    const int p_table = (stages & DIG_PIPE_ELEMENT_P) != 0;         // `d_pr` is dig_element_p_prepare's table
+    DIG_REQUIRE(!p_table || d_pr, "DIG_PIPE_ELEMENT_P needs the P table (dig_element_p_prepare) as d_pr");
+    DIG_REQUIRE(!p_table || ((uintptr_t)d_pr & 255u) == 0, "element P table (DIG_PIPE_ELEMENT_P) 256-byte aligned");
+    stages &= ~(DIG_PIPE_WORKLIST_CLEAN | DIG_PIPE_COMPACT_L | DIG_PIPE_RECORDS | DIG_PIPE_ELEMENT_CTX | DIG_PIPE_ELEMENT_RATES |
+                DIG_PIPE_ELEMENT_P);
     DIG_REQUIRE(stages >= 1 && stages <= 7, "stages: bit mask of DIG_PIPE_CONTEXTS, DIG_PIPE_DOT, DIG_PIPE_STATISTICS");
     DIG_REQUIRE(N >= 0 && E >= 0 && C >= 0, "N, E, C >= 0");
     if (E == 0 || C == 0) return DIG_OK;
@@ -308,7 +340,16 @@ static int element_pipeline_run(const double* bin_mu, const double* bin_std, con
     const int64_t acc_bytes = lay.acc_bytes;
     // the first kernel also clears the worklist header of the statistics stage (64 dwords): no separate memset node
     unsigned* wl = (unsigned*)((char*)workspace + acc_bytes);
-    if (compact) {
+    if (p_table) {
+        // P, R_SIZE, ELT_SIZE, P_INDEL kept by dig_element_p_prepare: the DOT stage streams them into the outputs, in the compact
+        // and the general form alike (a CONTEXTS-only call has nothing to enqueue); bin_ctx, ov_*, L, strand_minus are not read
+        if (stages & DIG_PIPE_DOT) {
+            DIG_REQUIRE(P && R_SIZE && ELT_SIZE && P_INDEL, "non-null accumulation outputs");
+            DIG_REQUIRE(((uintptr_t)P & 7u) == 0 && ((uintptr_t)P_INDEL & 7u) == 0, "P, P_INDEL 8-byte aligned");
+            int rc = element_p_stream_launch(d_pr, P, R_SIZE, ELT_SIZE, P_INDEL, E, C, stream, wl, 64);
+            if (rc) return rc;
+        }
+    } else if (compact) {
         // context-repeated L, compacted by dig_element_pipeline_prepare: contexts + dot are ONE kernel (the DOT stage; a
         // CONTEXTS-only call has nothing to enqueue)
         if (stages & DIG_PIPE_DOT) {
@@ -339,7 +380,8 @@ static int element_pipeline_run(const double* bin_mu, const double* bin_std, con
     }
     return element_stats_launch(MU, SIGMA, nullptr, nullptr, P, P_INDEL, 0, obs_snv, obs_samples, obs_indel, cj, cj_indel,
                                 out, E, C, (char*)workspace + acc_bytes, lay.stats_bytes, stream, &f,
-                                /* worklist header cleared by the context kernel of THIS call; a statistics-only call
+                                /* worklist header cleared by the first accumulation kernel of THIS call (the DOT stage's in the
+                                   compact form and with DIG_PIPE_ELEMENT_P, else the context kernel); a statistics-only call
                                    (new scale factors on an existing accumulation) clears it itself */
-                                (compact ? (stages & DIG_PIPE_DOT) != 0 : (stages & 1) != 0) || worklist_clean);
+                                (compact || p_table ? (stages & DIG_PIPE_DOT) != 0 : (stages & 1) != 0) || worklist_clean);
 }

@@ -240,9 +240,9 @@ def _element_planes(elts, tables, d_pr, ctx, cohorts, scale, max_muts_per_sample
     # plane behind the pass.  Same bits.  The general (192-substitution) form of the accumulation, as the per-cohort route runs it:
     # the same P to the last bit.
     by_cohort = lambda x: x.transpose(-1, -2).contiguous()
-    # (element_rates=False: the plan runs ONCE -- a table of the rate sums would be written and read for nothing)
+    # (element_rates=False, element_p=False: the plan runs ONCE -- a table of the rate sums, or of P, would be written and read for nothing)
     plan = engine.PipelinePlan(*args, obs_snv, obs_smp, obs_ind, compact=False, pack_bins=True, records_out=(output_form == "records"),
-                               element_rates=False)
+                               element_rates=False, element_p=False)
     if plan.records_out:
         acc, _ = plan.run(cj, cji)
         st_cm = torch.empty((len(engine.ES_PLANES), plan.C, plan.E), dtype=torch.float64, device=dev)

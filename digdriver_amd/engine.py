@@ -651,7 +651,7 @@ def element_pipeline(bin_mu, bin_std, bin_y, bin_flag, bin_ctx, ov_ptr, ov_idx, 
         plan = PipelinePlan(bin_mu, bin_std, bin_y, bin_flag, bin_ctx, ov_ptr, ov_idx, L, strand_minus, d_pr, obs_snv, obs_samples,
                             obs_indel, out_acc=out_acc, out_stats=out_stats, gene_length=gene_length, compact=compact,
                             pack_bins=False, element_contexts=False,   # (one call: packing the tables, or summing the context rows
-                            element_rates=False)                       #  or the rates in a kernel of their own, would cost more than it saves)
+                            element_rates=False, element_p=False)      #  or the rates, or keeping P, in kernels of their own, would cost more than it saves)
         return plan.run(_t(cj, "f64", plan.dev), _t(cj_indel, "f64", plan.dev), stages=stages)
     be = device_backend(bin_mu.device)
     tabs, (N, E, C, n_class) = _bin_tables(be, bin_mu, bin_std, bin_y, bin_flag, bin_ctx, ov_ptr, ov_idx, L, strand_minus,
@@ -713,7 +713,7 @@ class PipelinePlan:
 
     def __init__(self, bin_mu, bin_std, bin_y, bin_flag, bin_ctx, ov_ptr, ov_idx, L, strand_minus, d_pr, obs_snv,
                  obs_samples, obs_indel, out_acc=None, out_stats=None, gene_length=None, compact="auto", workspace=None,
-                 pack_bins=True, records_out=False, element_contexts=True, element_rates=True):
+                 pack_bins=True, records_out=False, element_contexts=True, element_rates=True, element_p=True):
         """compact: "auto" (default) checks ONCE, here, on the device whether L repeats every context count three times
         (sequence_tools.py:560-564: true for every elementModel / tiledModel / quickDriver set) and, if so, runs the
         64-context form of the accumulation (contexts + dot in one kernel, half the matrix work); False forces the
@@ -740,7 +740,15 @@ class PipelinePlan:
         feed it.  Another PipelinePlan over the same records and overlaps may be given instead of True: its table is shared.  A plan
         without packed records ignores the option and sums per call.  A caller that builds a plan and runs it ONCE passes False
         (engine.element_pipeline, cohort_batch._element_planes): for it the table is an extra write and read of 24 bytes per pair
-        and saves nothing."""
+        and saves nothing.
+        element_p: P, R_SIZE, ELT_SIZE and P_INDEL depend on nothing a run() is given (L, the context rows, gene_length and d_pr
+        all belong to the plan).  The plan runs its own accumulation stages ONCE, here, in whichever form it has (compact, planned
+        contexts, general), keeps bit copies of the four outputs in a plan-owned table (dig_element_p_prepare: `self.elt_p`,
+        8 bytes per pair + 16 per element, outside the workspace), and the DOT stage of every run() streams them back into the
+        plan's outputs instead of forming them again (DIG_PIPE_ELEMENT_P; copies: same bits).  All four outputs are still written
+        by every run.  The plan then snapshots L, d_pr, gene_length, bin_ctx, the overlaps and the strands: call `recontext()`
+        after changing one of them in place.  Another PipelinePlan over the same inputs may be given instead of True: its table
+        is shared.  A caller that builds a plan and runs it ONCE passes False (as for element_rates)."""
         import ctypes
         import torch
         dev = bin_mu.device
@@ -830,6 +838,22 @@ class PipelinePlan:
                 self._rerate()
             self._head[0] = p(self.elt_rates)                 # the `bin_mu` slot (self.keep still holds the bin table)
             self._flags |= _lib.DIG_PIPE_ELEMENT_RATES
+        self.elt_p = None
+        self._live_flags, self._live_d_pr = self._flags, self._head[10]     # the accumulation form that fills the table
+        if element_p:
+            if isinstance(element_p, PipelinePlan):           # several plans over the SAME accumulation inputs share one table
+                other = element_p
+                assert other.elt_p is not None and (other.N, other.E, other.C, other.compact) == (self.N, self.E, self.C, self.compact)
+                assert all(other.keep[i].data_ptr() == self.keep[i].data_ptr() for i in (4, 5, 6, 7, 8, 10))
+                assert (other.keep[9] is None) == (self.keep[9] is None)
+                assert self.keep[9] is None or other.keep[9].data_ptr() == self.keep[9].data_ptr()
+                self.elt_p = other.elt_p
+            else:
+                self.elt_p = torch.empty(int(_lib.load().dig_element_p_bytes(self.E, self.C)), dtype=torch.uint8, device=dev)
+                assert self.elt_p.data_ptr() % 256 == 0
+                self._reform_p(recompact=False)               # (L was compacted just above)
+            self._head[10] = p(self.elt_p)                    # the `d_pr` slot (self.keep still holds the parameters)
+            self._flags |= _lib.DIG_PIPE_ELEMENT_P
 
     def unpack(self, cohort_major=False, stream=None, stats=None, rates=None):
         """records_out plans: out_records -> the plane form (self.stats [7, E, C] and MU, SIGMA, R_OBS, FLAG of self.acc) on
@@ -877,18 +901,45 @@ class PipelinePlan:
             _lib.call("dig_element_rates_prepare", _lib.dev_ptr(self.records), _lib.dev_ptr(k[5]), _lib.dev_ptr(k[6]), self.N, self.E,
                       self.C, _lib.dev_ptr(self.elt_rates), self.elt_rates.numel(), _lib.stream_ptr())
 
+    def _reform_p(self, recompact=True):
+        """(Re)build the table of P, P_INDEL, R_SIZE and ELT_SIZE on torch's current stream (enqueued, not waited for): the plan's
+        own accumulation stages (CONTEXTS | DOT in its live form, with its context table when it has one) into its outputs, then
+        bit copies of the four into the table.  recompact: a compact plan compacts L into its workspace again first (L may have
+        changed in place; checks the repetition and waits for the stream)."""
+        import torch
+        if getattr(self, "elt_p", None) is None:
+            return
+        o = self.acc
+        head = list(self._head)
+        head[10] = self._live_d_pr
+        with torch.cuda.device(self.dev):
+            if self.compact and recompact:
+                import ctypes
+                ok = ctypes.c_int(0)
+                _lib.call("dig_element_pipeline_prepare", _lib.dev_ptr(self.keep[7]), self.E, self.C, self._ws, self.wsb, ctypes.byref(ok),
+                          _lib.stream_ptr())
+                if not ok.value:
+                    raise ValueError("L no longer repeats every context count three times: a compact plan cannot take it (build a new plan)")
+            # (cj / cj_indel are statistics arguments: checked for NULL, not read by these stages -- any device pointer serves)
+            rc = self._fn(*head, self._tail[8], self._tail[8], *self._tail, _lib.DIG_PIPE_CONTEXTS | _lib.DIG_PIPE_DOT | self._live_flags,
+                          self._ws, self.wsb, _lib.stream_ptr())
+            _lib.check("dig_element_pipeline", rc)
+            _lib.call("dig_element_p_prepare", _lib.dev_ptr(o["P"]), _lib.dev_ptr(o["R_SIZE"]), _lib.dev_ptr(o["ELT_SIZE"]),
+                      _lib.dev_ptr(o["P_INDEL"]), self.E, self.C, _lib.dev_ptr(self.elt_p), self.elt_p.numel(), _lib.stream_ptr())
+
     def recontext(self):
-        """(Re)build the table of the elements' summed context rows from the plan's bin_ctx, overlaps and strands on torch's
-        current stream, and the table of the pairs' rate sums from the packed bin records and the overlaps (both enqueued, not
-        waited for)."""
+        """(Re)build what the plan snapshots of L, d_pr, gene_length, bin_ctx, the overlaps (ov_ptr, ov_idx) and the strands, on
+        torch's current stream: the table of the elements' summed context rows (bin_ctx, overlaps, strands), the table of the
+        pairs' rate sums (packed bin records, overlaps) and, after the context table, the table of P, P_INDEL, R_SIZE and ELT_SIZE
+        (all six; a compact plan compacts L again, which waits for the stream).  The tables are enqueued, not waited for."""
         import torch
         self._rerate()
-        if self.elt_ctx is None:
-            return
-        k = self.keep
-        with torch.cuda.device(self.dev):
-            _lib.call("dig_element_contexts_prepare", _lib.dev_ptr(k[4]), _lib.dev_ptr(k[5]), _lib.dev_ptr(k[6]), _lib.dev_ptr(k[8]),
-                      self.N, self.E, _lib.dev_ptr(self.elt_ctx), _lib.stream_ptr())
+        if self.elt_ctx is not None:
+            k = self.keep
+            with torch.cuda.device(self.dev):
+                _lib.call("dig_element_contexts_prepare", _lib.dev_ptr(k[4]), _lib.dev_ptr(k[5]), _lib.dev_ptr(k[6]), _lib.dev_ptr(k[8]),
+                          self.N, self.E, _lib.dev_ptr(self.elt_ctx), _lib.stream_ptr())
+        self._reform_p()
 
     def run(self, cj, cj_indel, stages=7, stream=None):
         """Enqueue the pipeline (or one of its stages) on `stream` (default: torch's current stream)."""

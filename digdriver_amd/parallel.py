@@ -97,6 +97,7 @@ class ShardedPipeline:
         self.out_acc = engine.alloc_accumulate_outputs(E, C, 1, device)
         self.out_stats = torch.empty((len(engine.ES_PLANES), E, C), dtype=torch.float64, device=device)
         td = self.td
+        # (a rank steps many times over one shard: the plan keeps its defaults and forms its tables -- context rows, rate sums, P -- once)
         self.pipe = engine.PipelinePlan(td["bin_mu"], td["bin_std"], td["bin_y"], td["bin_flag"], td["bin_ctx"], td["ov_ptr"],
                                         td["ov_idx"], td["L"], td["strand_minus"], td["d_pr"], td["obs_snv"], td["obs_samples"],
                                         td["obs_indel"], out_acc=self.out_acc, out_stats=self.out_stats) if E else None

@@ -47,7 +47,8 @@ extern "C" {
                              * + dig_cnv_segment_deltas, dig_cnv_window_means, their size queries and _host twins (additions);
                              * + dig_tile_window_census, dig_sparse_window_count, dig_sparse_window_test and their _host twins (additions);
                              * + dig_element_contexts_prepare / DIG_PIPE_ELEMENT_CTX (additions);
-                             * + dig_element_rates_prepare, dig_element_rates_bytes / DIG_PIPE_ELEMENT_RATES (additions) */
+                             * + dig_element_rates_prepare, dig_element_rates_bytes / DIG_PIPE_ELEMENT_RATES (additions);
+                             * + dig_element_p_prepare, dig_element_p_bytes / DIG_PIPE_ELEMENT_P (additions) */
 
 /* dtype codes for dig_gather_bins */
 #define DIG_F32 0
@@ -288,6 +289,28 @@ int dig_bin_records_pack(const double *bin_mu, const double *bin_std, const int3
 int64_t dig_element_rates_bytes(int64_t E, int64_t C);
 int dig_element_rates_prepare(const void *bin_records, const int64_t *ov_ptr, const int32_t *ov_idx, int64_t N, int64_t E,
                               int64_t C, void *rates, int64_t rates_bytes, void *stream);
+/* P as a plan-time product (either form of the accumulation).  P = sum L d_pr / sum region_counts d_pr, R_SIZE, ELT_SIZE and
+ * P_INDEL (genic_driver_tools.py:404-417: the reference stores P_SUM with MU and SIGMA in the pretrained element table, and
+ * the driver, transfer_tools.py:281-344, only reads it) depend on L, the context rows, gene_length and d_pr only -- not on
+ * the scale factors or the observed counts -- so a caller that runs the same element set and cohorts many times forms them
+ * once and has every later call copy them.
+ *   dig_element_p_prepare  PLAN TIME, after ONE accumulation call of whatever form (compact, planned contexts, general K =
+ *       256, C > 48 in chunks): bit copies of that call's four outputs go into `table` (caller-owned, 256-byte aligned, at
+ *       least dig_element_p_bytes(E, C) bytes): P [E C] f64 | P_INDEL [E] f64 | R_SIZE [E] int32 | ELT_SIZE [E] int32, every
+ *       section starting on a 256-byte boundary.  The table holds that form's bits, the NaN / inf of zero denominators
+ *       included.  Enqueued on `stream`; nothing is waited for.  Again after L, d_pr, gene_length, bin_ctx, ov_* or
+ *       strand_minus changed.
+ *   DIG_PIPE_ELEMENT_P  OR into `stages` of dig_element_pipeline calls: the `d_pr` argument is then that table (NULL or
+ *       misaligned: DIG_EINVAL).  The CONTEXTS stage enqueues nothing; the DOT stage is ONE launch of element_p_stream_kernel
+ *       whatever C is, which writes P, R_SIZE, ELT_SIZE and P_INDEL from the table into the caller's outputs (8 bytes in and
+ *       out per pair, no matrix work) and clears the worklist header; a DIG_PIPE_DOT stage timer reads that kernel.  The
+ *       accumulation stages read neither bin_ctx, ov_ptr / ov_idx, L, strand_minus nor gene_length; the STATISTICS stage is
+ *       unchanged and reads the caller's P / P_INDEL.  All four outputs are still written by every call.  The host twin and a
+ *       caller that runs its tables ONCE keep the live form: for them the table is an extra write and read. */
+#define DIG_PIPE_ELEMENT_P 256
+int64_t dig_element_p_bytes(int64_t E, int64_t C);
+int dig_element_p_prepare(const double *P, const int32_t *R_SIZE, const int32_t *ELT_SIZE, const double *P_INDEL, int64_t E,
+                          int64_t C, void *table, int64_t table_bytes, void *stream);
 int dig_element_pipeline(const double *bin_mu, const double *bin_std, const int32_t *bin_y, const uint8_t *bin_flag,
                          const int32_t *bin_ctx, const int64_t *ov_ptr, const int32_t *ov_idx, const int32_t *L,
                          const uint8_t *strand_minus, const int32_t *gene_length, const double *d_pr,
