@@ -127,6 +127,10 @@ _SIGNATURES = {
     "dig_group_sums_host": [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp, _int],
     "dig_nb_power": [_vp] * 5 + [_i64, _i64, _vp, _int, ctypes.c_int32, _vp, _vp, _vp],
     "dig_nb_power_host": [_vp] * 5 + [_i64, _i64, _vp, _int, ctypes.c_int32, _vp, _vp, _int],
+    "dig_map_windows": [_vp] * 4 + [_i64, _i64, _vp, _i64, _int, _int] + [_vp] * 5 + [_vp],
+    "dig_map_windows_host": [_vp] * 4 + [_i64, _i64, _vp, _i64, _int, _int] + [_vp] * 5 + [_int],
+    "dig_map_scores": [_vp] * 4 + [_i64, _i64, _vp, _vp, _vp, _i64, _vp],
+    "dig_map_scores_host": [_vp] * 4 + [_i64, _i64, _vp, _vp, _int],
     "dig_tile_sample_keys": [_vp, _vp, _i64, _vp, _i64] + [_vp] * 5 + [_int] + [_i64] * 4 + [_vp, _vp],
     "dig_tile_sample_keys_host": [_vp, _vp, _i64, _vp, _i64] + [_vp] * 5 + [_int] + [_i64] * 4 + [_vp, _int],
     "dig_tile_sample_counts": [_vp] + [_i64] * 6 + [_vp, _vp, _vp],
@@ -225,6 +229,7 @@ _SIZE_QUERIES = {
     "dig_cnv_window_means_size": [_i64, _i64],
     "dig_row_select_chunk": [],
     "dig_row_select_counts_size": [_i64, _i64],
+    "dig_map_scores_workspace": [_i64, _i64],
 }
 
 ABI_VERSION = 12         # include/dig_hip.h: DIG_ABI_VERSION
@@ -308,7 +313,8 @@ def workspace_bytes(kind, E, C):
     """Scratch bytes needed by dig_element_stats ("element_stats") / dig_accumulate_elements ("accumulate")."""
     lib = load()
     fn = {"element_stats": lib.dig_element_stats_workspace, "accumulate": lib.dig_accumulate_workspace,
-          "suffstats": lib.dig_scale_suffstats_workspace, "pipeline": lib.dig_element_pipeline_workspace}[kind]
+          "suffstats": lib.dig_scale_suffstats_workspace, "pipeline": lib.dig_element_pipeline_workspace,
+          "map_scores": lib.dig_map_scores_workspace}[kind]
     return int(fn(int(E), int(C)))
 
 

@@ -719,6 +719,39 @@ int dig_nb_power_host(const double* alpha, const double* theta, const double* pi
                    st.in(folds, n_folds), n_folds, k_max, st.out(k_crit, m), n_folds ? st.out(power, m * n_folds) : nullptr, nullptr);
 }
 
+int dig_map_windows_host(const double* mu_cm, const double* std_cm, const int32_t* y_cm, const uint8_t* flag_cm, int64_t C, int64_t N,
+                         const int64_t* run_ptr, int64_t M, int drop_flagged, int tail, int32_t* n_bins, int64_t* y_true, double* y_pred,
+                         double* std, double* pval, int device)
+{
+    MapWindowPlan plan{};
+    if (int rc = map_windows_sizes(__func__, C, N, M, drop_flagged, tail, flag_cm, &plan)) return rc;
+    if (C * M == 0) return DIG_OK;
+    DIG_REQUIRE(run_ptr && n_bins && y_true && y_pred && std && pval, "non-null run_ptr, n_bins, y_true, y_pred, std, pval");
+    DIG_REQUIRE(N == 0 || (mu_cm && std_cm && y_cm), "non-null mu_cm, std_cm, y_cm");
+    DIG_REQUIRE(run_ptr[0] >= 0 && run_ptr[M] == N, "run_ptr: non-negative first, N last");
+    for (int64_t m = 0; m < M; ++m) DIG_REQUIRE(run_ptr[m] <= run_ptr[m + 1], "run_ptr non-decreasing");
+    const size_t n_in = (size_t)C * N, n_out = (size_t)C * M;
+    Staging st(device);
+    return st.call(dig_map_windows, st.in(mu_cm, n_in), st.in(std_cm, n_in), st.in(y_cm, n_in), st.in(flag_cm, n_in), C, N,
+                   st.in(run_ptr, M + 1), M, drop_flagged, tail, st.out(n_bins, n_out), st.out(y_true, n_out), st.out(y_pred, n_out),
+                   st.out(std, n_out), st.out(pval, n_out), nullptr);
+}
+
+int dig_map_scores_host(const int32_t* n_bins, const int64_t* y_true, const double* y_pred, const double* pval, int64_t C, int64_t M,
+                        int64_t* counts, double* sums, int device)
+{
+    int64_t chunks = 0;
+    if (int rc = map_scores_sizes(__func__, C, M, &chunks)) return rc;
+    if (C == 0) return DIG_OK;
+    DIG_REQUIRE(counts && sums, "non-null counts, sums");
+    const size_t n = (size_t)C * M;
+    DIG_REQUIRE(n == 0 || (n_bins && y_true && y_pred && pval), "non-null n_bins, y_true, y_pred, pval");
+    const int64_t wsb = dig_map_scores_workspace(C, M);
+    Staging st(device);
+    return st.call(dig_map_scores, st.in(n_bins, n), st.in(y_true, n), st.in(y_pred, n), st.in(pval, n), C, M, st.out(counts, (size_t)C * 7),
+                   st.out(sums, (size_t)C * 4), st.scratch((size_t)wsb), wsb, nullptr);
+}
+
 int dig_scale_suffstats_host(const double* bin_mu, const uint8_t* bin_flag, int64_t N, int64_t C, double* out_sum, int device)
 {
     DIG_REQUIRE(N >= 0 && C >= 0, "N, C >= 0");

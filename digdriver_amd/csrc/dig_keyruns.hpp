@@ -52,6 +52,16 @@ int group_sizes(const char* fn, int64_t R, int64_t C, int64_t E, int64_t M, int6
 int nb_power_sizes(const char* fn, int64_t rows, int64_t n, const double* folds, int n_folds, int32_t k_max, const double* power,
                    int64_t* chunks);
 
+// dig_mapreport.hip: what dig_map_windows / dig_map_scores and their host twins check without looking at an array (include/dig_hip.h
+// lists it); the windows of a group (one group of neighbouring windows of a cohort at a time per workgroup) and the groups of a
+// cohort; the chunks (one per workgroup) of a cohort's windows
+struct MapWindowPlan {
+    int wpb;
+    int64_t groups;
+};
+int map_windows_sizes(const char* fn, int64_t C, int64_t N, int64_t M, int drop_flagged, int tail, const void* flag_cm, MapWindowPlan* plan);
+int map_scores_sizes(const char* fn, int64_t C, int64_t M, int64_t* chunks);
+
 // dig_tilewindows.hip: tile_select_sizes and 1 <= width <= DIG_TILE_WINDOW_MAX_WIDTH, for dig_tile_window_test and its host twin
 int tile_window_sizes(const char* fn, int64_t C, int64_t R, int64_t T, int32_t width);
 

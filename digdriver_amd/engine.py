@@ -1909,6 +1909,64 @@ def nb_power(alpha, theta, pi, level, scale=None, folds=(), k_max=1 << 20, devic
     return dict(k_crit=k_crit, power=power)
 
 
+MAP_TAILS = {"upper": 0, "side": 1}                      # `tail` of dig_map_windows (include/dig_hip.h)
+MAP_LEVELS = (0.05, 0.01, 0.001, 0.0001)                 # the levels of N_BELOW (gp_tools.py:117-121)
+MAP_COUNTS = ("N_WINDOWS", "N_TESTED", "OBS_TOTAL") + tuple("N_BELOW_%g" % a for a in MAP_LEVELS)
+MAP_SUMS = ("EXP_TOTAL", "SXX", "SYY", "SXY")
+
+
+def map_windows(mu_cm, std_cm, y_cm, flag_cm, run_ptr, drop_flagged=False, tail="upper", device=0):
+    """A map's bins merged into larger windows with the region test per window (dig_map_windows; gp_tools.merge_windows,
+    gp_tools.py:125-160): mu_cm, std_cm f64, y_cm i32, flag_cm u8 (None without drop_flagged) [C, N] cohort-major (a [N] input is
+    C = 1), run_ptr i64 [M + 1]: window m = bins run_ptr[m] .. run_ptr[m + 1] - 1.  tail: 'upper' (nb_pvalue_greater_midp, the burden
+    test) or 'side' (nb_pvalue_midp).  Returns dict(n_bins i32, y_true i64, y_pred f64, std f64, pval f64), each [C, M]: the sums of
+    the bins that are not gated out (a flagged bin with drop_flagged), the float sums sequential in ascending bin order, pval NaN for
+    a window without a bin left.  ValueError for a refused requirement.  CUDA tensors in -> CUDA tensors out."""
+    if tail not in MAP_TAILS:
+        raise ValueError("tail must be 'upper' or 'side', not %r" % (tail,))
+    be = backend_of(mu_cm, std_cm, y_cm, flag_cm, run_ptr, device=device)
+    mu_cm = be.arr(mu_cm, "f64")
+    if mu_cm.ndim not in (1, 2):
+        raise ValueError("mu_cm must be [N] or [C, N]")
+    C, N = (1, int(mu_cm.shape[0])) if mu_cm.ndim == 1 else (int(s) for s in mu_cm.shape)
+    std_cm, y_cm, flag_cm = be.arr(std_cm, "f64", (C, N)), be.arr(y_cm, "i32", (C, N)), be.arr(flag_cm, "u8", (C, N))
+    if drop_flagged and flag_cm is None:
+        raise ValueError("drop_flagged needs flag_cm")
+    run_ptr = be.arr(run_ptr, "i64", (-1,))
+    M = int(run_ptr.shape[0]) - 1
+    if M < 0:
+        raise ValueError("run_ptr must hold at least one offset")
+    out = dict(n_bins=be.empty((C, M), "i32"), y_true=be.empty((C, M), "i64"), y_pred=be.empty((C, M), "f64"),
+               std=be.empty((C, M), "f64"), pval=be.empty((C, M), "f64"))
+    p = be.ptr
+    with _requirements_as_value_errors():
+        if C * M:                                            # (an empty tensor has no address)
+            be.call("dig_map_windows", p(mu_cm), p(std_cm), p(y_cm), p(flag_cm) if drop_flagged else None, C, N, p(run_ptr), M,
+                    int(bool(drop_flagged)), MAP_TAILS[tail], p(out["n_bins"]), p(out["y_true"]), p(out["y_pred"]), p(out["std"]),
+                    p(out["pval"]))
+    return out
+
+
+def map_scores(n_bins, y_true, y_pred, pval, device=0):
+    """The per-cohort scores of merged planes [C, M] (dig_map_scores), over the windows with n_bins > 0: dict(counts i64 [C, 7]:
+    MAP_COUNTS -- N_WINDOWS, N_TESTED (pval not NaN), OBS_TOTAL, the windows with pval < 0.05, 0.01, 0.001, 0.0001 --, sums f64
+    [C, 4]: MAP_SUMS -- EXP_TOTAL and the sums of squares and products centred on the two means).  The float sums are taken in an
+    order fixed by (M, C): the same bits on any stream and through the host twin.  CUDA tensors in -> CUDA tensors out."""
+    be = backend_of(n_bins, y_true, y_pred, pval, device=device)
+    n_bins = be.arr(n_bins, "i32")
+    if n_bins.ndim != 2:
+        raise ValueError("n_bins must be [C, M]")
+    C, M = (int(s) for s in n_bins.shape)
+    y_true, y_pred, pval = be.arr(y_true, "i64", (C, M)), be.arr(y_pred, "f64", (C, M)), be.arr(pval, "f64", (C, M))
+    out = dict(counts=be.empty((C, len(MAP_COUNTS)), "i64"), sums=be.empty((C, len(MAP_SUMS)), "f64"))
+    p = be.ptr
+    with _requirements_as_value_errors():
+        if C:
+            be.call("dig_map_scores", p(n_bins), p(y_true), p(y_pred), p(pval), C, M, p(out["counts"]), p(out["sums"]),
+                    workspace=_shared_workspace(be, "map_scores", C, M))
+    return out
+
+
 # ---------------------------------------------------------------------------
 # scale factors in canonical chunks: identical bits for any sharding of the bins (dig_scale_suffstats_chunked)
 # ---------------------------------------------------------------------------

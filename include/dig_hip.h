@@ -674,6 +674,54 @@ int dig_nb_power_host(const double *alpha, const double *theta, const double *pi
                       int64_t rows, int64_t n, const double *folds, int n_folds, int32_t k_max, int32_t *k_crit, double *power,
                       int device);
 
+/* ---- the map report: a map's bins merged into larger windows, the region test per window, the scores of a cohort (additive: the
+ * ABI version stays) ------------------------------------------------------------------------------------------------------------- *
+ * Reference: gp_tools.merge_windows (sequence_model/gp_tools.py:125-160) and calibration_score_by_pvals (:117-121).
+ * Inputs: C maps on one (CHROM, START)-sorted grid of N bins, cohort-major: mu_cm (Y_PRED), std_cm (STD) f64 [C, N], y_cm (Y_TRUE) i32
+ * [C, N], flag_cm (FLAG) u8 [C, N] (may be NULL with drop_flagged = 0, when it is not read).  Merged windows: with W the grid's window
+ * and s >= 1 the scale, the key of bin i is (chrom[i], start[i] / (s W)); the M merged windows are the runs of equal key in grid
+ * order, run_ptr i64 [M + 1] (window m = bins run_ptr[m] .. run_ptr[m + 1] - 1; the caller builds it once per scale; device memory
+ * for dig_map_windows).  Bins missing from the grid add nothing; a window without a bin does not exist.
+ *   dig_map_windows, per cohort c and window m, with the gate g = 1, and g = 0 for a bin with flag != 0 when drop_flagged = 1:
+ *     n_bins i32 = sum g;   y_true i64 = sum g y;   y_pred f64 = sum g mu;   std f64 = sqrt(sum g std^2)
+ *     -- the two float sums are SEQUENTIAL IEEE double additions in ascending bin order from +0.0 (a gated-out bin adds +0.0), std * std
+ *     rounded before it is added (no fused multiply-add), the square root correctly rounded: np.cumsum over the run gives the same bits.
+ *     pval f64: NaN for n_bins = 0; otherwise (alpha, theta) = normal_params_to_gamma(y_pred, std), p = 1 / (theta + 1) and
+ *       tail = 0: nb_pvalue_greater_midp(y_true, alpha, p) (nb_model.py:271-278, what dig_nb_midp_upper gives: the burden test);
+ *       tail = 1: nb_pvalue_midp(y_true, alpha, p) (nb_model.py:316-337, what dig_nb_midp_twosided gives);
+ *     NaN where the reference's expression is NaN (y_pred <= 0, std = 0, a NaN input).
+ *     The five outputs are cohort-major [C, M] (M contiguous), each element written once by its owner: no atomics, no workspace, one
+ *     launch.
+ *   dig_map_scores, per cohort over the windows with n_bins > 0:
+ *     counts i64 [C, 7]: N_WINDOWS; N_TESTED (pval not NaN); OBS_TOTAL = sum y_true; N_BELOW[a] = the windows with pval < a, strict,
+ *       for a = 0.05, 0.01, 0.001, 0.0001;
+ *     sums f64 [C, 4]: EXP_TOTAL = sum y_pred; and, with mx = (double)OBS_TOTAL / (double)N_WINDOWS, my = EXP_TOTAL / (double)N_WINDOWS,
+ *       dx = (double)y_true - mx, dy = y_pred - my:  Sxx = sum dx dx, Syy = sum dy dy, Sxy = sum dx dy (every product rounded before it
+ *       is added).  The caller forms R2 = Sxy^2 / (Sxx Syy), the fractions and the calibration score.
+ *     The order of the four float sums is fixed by (M, C) alone: the windows of a cohort in chunks of 1024 (the last one shorter); in a
+ *     chunk, lane t of 256 adds the terms of windows t, t + 256, t + 512, t + 768 in that order from +0.0 (a window with n_bins = 0 or
+ *     past M adds +0.0), the lane sums are folded by halves (t += t + 128, then + 64, ... + 1), and the chunk sums are added first to last
+ *     from +0.0.  Any stream, any run, and the host twins: the same bits.
+ *     workspace: at least dig_map_scores_workspace(C, M) bytes, 8-byte aligned; it need not be zeroed.  C > 0 with M = 0: all zero.
+ * DIG_EINVAL, before anything is read or launched: negative C, N or M; tail or drop_flagged outside {0, 1}; drop_flagged with a NULL
+ * flag_cm (and C N > 0); C >= 2^31, N or M >= 2^40; C * window groups >= 2^31 (dig_map_windows: a group is 4096 / (N / M), at least 1
+ * and at most 256, neighbouring windows) or C * ceil(M / 1024) >= 2^31 (dig_map_scores); with C M > 0 a NULL run_ptr or output, with
+ * N > 0 too a NULL mu_cm, std_cm or y_cm; for dig_map_scores with C > 0 a NULL counts or sums, with M > 0 a NULL plane or workspace, a
+ * workspace that is too small or not 8-byte aligned.  dig_map_windows_host also refuses a run_ptr that begins below 0, does not end at
+ * N or decreases anywhere (the device form cannot look: it clamps every value into [its left neighbour, N], so a bad run_ptr reads
+ * nothing outside the tables).  Nothing is launched when C M = 0 (dig_map_windows) or C = 0 (dig_map_scores). */
+int dig_map_windows(const double *mu_cm, const double *std_cm, const int32_t *y_cm, const uint8_t *flag_cm, int64_t C, int64_t N,
+                    const int64_t *run_ptr, int64_t M, int drop_flagged, int tail, int32_t *n_bins, int64_t *y_true, double *y_pred,
+                    double *std, double *pval, void *stream);
+int dig_map_windows_host(const double *mu_cm, const double *std_cm, const int32_t *y_cm, const uint8_t *flag_cm, int64_t C, int64_t N,
+                         const int64_t *run_ptr, int64_t M, int drop_flagged, int tail, int32_t *n_bins, int64_t *y_true,
+                         double *y_pred, double *std, double *pval, int device);
+int64_t dig_map_scores_workspace(int64_t C, int64_t M);
+int dig_map_scores(const int32_t *n_bins, const int64_t *y_true, const double *y_pred, const double *pval, int64_t C, int64_t M,
+                   int64_t *counts, double *sums, void *workspace, int64_t workspace_bytes, void *stream);
+int dig_map_scores_host(const int32_t *n_bins, const int64_t *y_true, const double *y_pred, const double *pval, int64_t C, int64_t M,
+                        int64_t *counts, double *sums, int device);
+
 /* ---- the per-base route's counts by sample for many cohorts (additive: the ABI version stays) ------------------- *
  * dig_tile_mut_counts counts rows, whoever they belong to.  These two entry points count them per sample: with n(c, r, t, s) the
  * rows of GLOBAL sample s that dig_tile_mut_counts would count in tile (c, r, t) -- the same pairs, the same skip rules --

@@ -11,6 +11,8 @@ Drop-in for the sub-commands of the reference's scripts/DigPretrain.py (:280-477
     genicModel      genic_model frame                                                               (:226-237)
     elementModel    <save_key> element frame                                                        (:239-268)
     tiledModel      <save_key> tile frame                                                           (:271-278)
+    evaluateMaps    accuracy across scales and calibration of finished maps (not a reference sub-command; its arithmetic is
+                    sequence_model/gp_tools.py:117-160)
 
 Same positional arguments and option names.  `countNonc_context` is the reference's own deprecated
 sub-command (it calls a function that does not exist, DigPretrain.py:222) and is not provided.
@@ -165,6 +167,20 @@ def pretrain_tiled(args):
     mapfile.write_frame(args.output_h5 or args.f_pretrained, args.save_key, frame)
 
 
+def evaluate_maps(args):
+    """evaluateMaps: map_report.txt (one row per cohort and scale), and with --write-windows / --outliers-fdr the merged windows and
+    the outlier windows of every cohort and scale (region_model/map_report.py)."""
+    from digdriver_amd.region_model import map_report
+    try:
+        map_report.check_options(len(args.maps), args.labels, args.tail, args.outliers_fdr, args.scales_bp)
+        res = map_report.evaluate_maps(args.maps, args.scales_bp, key=args.key, labels=args.labels, drop_flagged=args.drop_flagged,
+                                       tail=args.tail, outliers_fdr=args.outliers_fdr)
+    except ValueError as exc:
+        raise SystemExit(str(exc))
+    for path in map_report.write_report(res, args.outdir, write_windows=args.write_windows):
+        print('wrote {}'.format(path))
+
+
 def parse_args(text=None):
     parser = argparse.ArgumentParser(description='Build a pretrained DIG mutation map (MI355X build).')
     sub = parser.add_subparsers()
@@ -227,6 +243,19 @@ def parse_args(text=None):
             e.add_argument('--indels-direct', action='store_true', default=False, help='use a separate indel region model')
         e.add_argument('--n-procs', default=get_cpus(), type=int, dest='N_procs', help='accepted for compatibility')
         e.set_defaults(func=func)
+
+    # not a reference sub-command: how good finished maps are (region_model/map_report.py)
+    f = sub.add_parser('evaluateMaps', help='accuracy across scales and calibration of finished maps')
+    f.add_argument('--maps', required=True, nargs='+', help='mutation maps on one bin grid')
+    f.add_argument('--outdir', required=True, help='directory for map_report.txt and the window files')
+    f.add_argument('--labels', nargs='+', default=None, help='one label per map (default: its cohort_name attribute, else the file stem)')
+    f.add_argument('--key', default='region_params', help='frame with the region parameters')
+    f.add_argument('--scales-bp', nargs='+', type=int, default=[10000, 50000, 100000, 1000000], help='window sizes, multiples of the maps\' window')
+    f.add_argument('--drop-flagged', action='store_true', default=False, help='leave flagged bins out of every window')
+    f.add_argument('--tail', choices=['upper', 'side'], default='upper', help='upper mid-p (the burden test) or two-sided mid-p')
+    f.add_argument('--write-windows', action='store_true', default=False, help='write <label>.windows_<bp>.txt per cohort and scale')
+    f.add_argument('--outliers-fdr', type=float, default=None, help='write the windows with Benjamini-Hochberg q <= this level')
+    f.set_defaults(func=evaluate_maps)
 
     return parser.parse_args(text.split()) if text else parser.parse_args()
 
