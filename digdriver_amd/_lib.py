@@ -131,6 +131,12 @@ _SIGNATURES = {
     "dig_map_windows_host": [_vp] * 4 + [_i64, _i64, _vp, _i64, _int, _int] + [_vp] * 5 + [_int],
     "dig_map_scores": [_vp] * 4 + [_i64, _i64, _vp, _vp, _vp, _i64, _vp],
     "dig_map_scores_host": [_vp] * 4 + [_i64, _i64, _vp, _vp, _int],
+    "dig_pair_bits": [_vp, _vp, _i64, _i64, _i64, _vp, _vp],
+    "dig_pair_bits_host": [_vp, _vp, _i64, _i64, _i64, _vp, _int],
+    "dig_pair_fisher": [_vp, _i64, _i64, _vp, _vp, _vp, _i64, _vp, _i64, _i64, ctypes.c_int32, ctypes.c_int32] + [_vp] * 5 + [_vp],
+    "dig_pair_fisher_host": [_vp, _i64, _i64, _vp, _vp, _vp, _i64, _vp, _i64, _i64, ctypes.c_int32, ctypes.c_int32] + [_vp] * 5 + [_int],
+    "dig_pair_counts": [_vp, _i64, _i64, _vp, _vp, _vp, _i64, _vp, _i64, _i64, ctypes.c_int32, ctypes.c_int32] + [_vp] * 2 + [_vp],
+    "dig_pair_counts_host": [_vp, _i64, _i64, _vp, _vp, _vp, _i64, _vp, _i64, _i64, ctypes.c_int32, ctypes.c_int32] + [_vp] * 2 + [_int],
     "dig_tile_sample_keys": [_vp, _vp, _i64, _vp, _i64] + [_vp] * 5 + [_int] + [_i64] * 4 + [_vp, _vp],
     "dig_tile_sample_keys_host": [_vp, _vp, _i64, _vp, _i64] + [_vp] * 5 + [_int] + [_i64] * 4 + [_vp, _int],
     "dig_tile_sample_counts": [_vp] + [_i64] * 6 + [_vp, _vp, _vp],

@@ -752,6 +752,73 @@ int dig_map_scores_host(const int32_t* n_bins, const int64_t* y_true, const doub
                    st.out(sums, (size_t)C * 4), st.scratch((size_t)wsb), wsb, nullptr);
 }
 
+// what the twins of dig_pair_fisher / dig_pair_counts require of the plan arrays, which the device forms cannot look at
+static int check_pair_plan(const char* fn, int64_t H_total, const int64_t* row_ptr, const int32_t* n_samples, const int64_t* pair_ptr,
+                           int64_t C, const int32_t* tiles, int64_t n_tiles, int64_t n_pairs, int32_t n_max, int32_t h_max)
+{
+    DIG_REQUIRE_IN(fn, C == 0 || (row_ptr && n_samples && pair_ptr), "non-null row_ptr, n_samples, pair_ptr");
+    DIG_REQUIRE_IN(fn, n_tiles == 0 || (tiles && C > 0), "non-null tiles");
+    if (C == 0) {
+        DIG_REQUIRE_IN(fn, H_total == 0 && n_pairs == 0, "no row and no pair without a cohort");
+        return DIG_OK;
+    }
+    DIG_REQUIRE_IN(fn, row_ptr[0] == 0 && row_ptr[C] == H_total, "row_ptr: 0 first, H_total last");
+    DIG_REQUIRE_IN(fn, pair_ptr[0] == 0 && pair_ptr[C] == n_pairs, "pair_ptr: 0 first, n_pairs last");
+    for (int64_t c = 0; c < C; ++c) {
+        const int64_t H = row_ptr[c + 1] - row_ptr[c];
+        DIG_REQUIRE_IN(fn, H >= 0 && H <= h_max, "0 <= rows of a cohort <= h_max");
+        DIG_REQUIRE_IN(fn, n_samples[c] >= 0 && n_samples[c] <= n_max, "0 <= n_samples <= n_max");
+        DIG_REQUIRE_IN(fn, pair_ptr[c + 1] - pair_ptr[c] == H * (H - 1) / 2, "pair_ptr: H (H - 1) / 2 pairs per cohort");
+    }
+    for (int64_t t = 0; t < n_tiles; ++t) {
+        const int32_t c = tiles[3 * t], bi = tiles[3 * t + 1], bj = tiles[3 * t + 2];
+        DIG_REQUIRE_IN(fn, c >= 0 && c < C && bi >= 0 && bi <= bj && (int64_t)bj * DIG_PAIR_TILE < row_ptr[c + 1] - row_ptr[c],
+                       "tiles: (cohort, block i <= block j) inside the cohort's rows");
+    }
+    return DIG_OK;
+}
+
+int dig_pair_bits_host(const int32_t* row, const int32_t* sample, int64_t n_keys, int64_t H_total, int64_t W, uint64_t* bits, int device)
+{
+    unsigned blocks = 0;
+    if (int rc = pair_bits_sizes(__func__, n_keys, H_total, W, bits, &blocks)) return rc;
+    if (H_total == 0) return DIG_OK;
+    DIG_REQUIRE(n_keys == 0 || (row && sample), "non-null row, sample");
+    Staging st(device);
+    return st.call(dig_pair_bits, st.in(row, n_keys), st.in(sample, n_keys), n_keys, H_total, W, st.out(bits, (size_t)H_total * W), nullptr);
+}
+
+int dig_pair_fisher_host(const uint64_t* bits, int64_t H_total, int64_t W, const int64_t* row_ptr, const int32_t* n_samples,
+                         const int64_t* pair_ptr, int64_t C, const int32_t* tiles, int64_t n_tiles, int64_t n_pairs, int32_t n_max,
+                         int32_t h_max, double* lnfact, int32_t* n_row, int32_t* n_both, double* pval_cooccur, double* pval_exclusive,
+                         int device)
+{
+    if (int rc = pair_fisher_sizes(__func__, bits, H_total, W, C, n_tiles, n_pairs, n_max, h_max)) return rc;
+    DIG_REQUIRE(lnfact, "non-null lnfact");
+    DIG_REQUIRE(H_total == 0 || n_row, "non-null n_row");
+    DIG_REQUIRE(n_pairs == 0 || (n_both && pval_cooccur && pval_exclusive), "non-null n_both, pval_cooccur, pval_exclusive");
+    if (int rc = check_pair_plan(__func__, H_total, row_ptr, n_samples, pair_ptr, C, tiles, n_tiles, n_pairs, n_max, h_max)) return rc;
+    Staging st(device);
+    return st.call(dig_pair_fisher, st.in(bits, (size_t)H_total * W), H_total, W, st.in(row_ptr, C + 1), st.in(n_samples, C),
+                   st.in(pair_ptr, C + 1), C, st.in(tiles, 3 * n_tiles), n_tiles, n_pairs, n_max, h_max, st.out(lnfact, (size_t)n_max + 1),
+                   st.out(n_row, H_total), st.out(n_both, n_pairs), st.out(pval_cooccur, n_pairs), st.out(pval_exclusive, n_pairs),
+                   nullptr);
+}
+
+int dig_pair_counts_host(const uint64_t* bits, int64_t H_total, int64_t W, const int64_t* row_ptr, const int32_t* n_samples,
+                         const int64_t* pair_ptr, int64_t C, const int32_t* tiles, int64_t n_tiles, int64_t n_pairs, int32_t n_max,
+                         int32_t h_max, int32_t* n_row, int32_t* n_both, int device)
+{
+    if (int rc = pair_fisher_sizes(__func__, bits, H_total, W, C, n_tiles, n_pairs, n_max, h_max)) return rc;
+    DIG_REQUIRE(H_total == 0 || n_row, "non-null n_row");
+    DIG_REQUIRE(n_pairs == 0 || n_both, "non-null n_both");
+    if (int rc = check_pair_plan(__func__, H_total, row_ptr, n_samples, pair_ptr, C, tiles, n_tiles, n_pairs, n_max, h_max)) return rc;
+    Staging st(device);
+    return st.call(dig_pair_counts, st.in(bits, (size_t)H_total * W), H_total, W, st.in(row_ptr, C + 1), st.in(n_samples, C),
+                   st.in(pair_ptr, C + 1), C, st.in(tiles, 3 * n_tiles), n_tiles, n_pairs, n_max, h_max, st.out(n_row, H_total),
+                   st.out(n_both, n_pairs), nullptr);
+}
+
 int dig_scale_suffstats_host(const double* bin_mu, const uint8_t* bin_flag, int64_t N, int64_t C, double* out_sum, int device)
 {
     DIG_REQUIRE(N >= 0 && C >= 0, "N, C >= 0");

@@ -52,6 +52,12 @@ int group_sizes(const char* fn, int64_t R, int64_t C, int64_t E, int64_t M, int6
 int nb_power_sizes(const char* fn, int64_t rows, int64_t n, const double* folds, int n_folds, int32_t k_max, const double* power,
                    int64_t* chunks);
 
+// dig_pairs.hip: what dig_pair_bits, dig_pair_fisher / dig_pair_counts and their host twins check without looking at an array
+// (include/dig_hip.h lists it); the workgroups of dig_pair_bits
+int pair_bits_sizes(const char* fn, int64_t n_keys, int64_t H_total, int64_t W, const void* bits, unsigned* blocks);
+int pair_fisher_sizes(const char* fn, const void* bits, int64_t H_total, int64_t W, int64_t C, int64_t n_tiles, int64_t n_pairs,
+                      int32_t n_max, int32_t h_max);
+
 // dig_mapreport.hip: what dig_map_windows / dig_map_scores and their host twins check without looking at an array (include/dig_hip.h
 // lists it); the windows of a group (one group of neighbouring windows of a cohort at a time per workgroup) and the groups of a
 // cohort; the chunks (one per workgroup) of a cohort's windows

@@ -343,9 +343,13 @@ def encode_mutations(df_mut, device, cohort_id=0, chrom_ids=None):
     return to_device(encode_mutations_host(df_mut, cohort_id, chrom_ids), device)
 
 
-def tabulate_cohorts(blocks, cohorts, drop_duplicates=True, max_muts_per_sample=1e9, max_muts_per_elt_per_sample=3e9):
+def tabulate_cohorts(blocks, cohorts, drop_duplicates=True, max_muts_per_sample=1e9, max_muts_per_elt_per_sample=3e9,
+                     return_sample_keys=False):
     """`cohorts`: list of encode_mutations() dicts (one per cohort).  Returns (OBS_SNV, OBS_SAMPLES, OBS_INDEL) int32
-    [E, C] device tensors and the per-cohort lists of blacklisted sample names."""
+    [E, C] device tensors and the per-cohort lists of blacklisted sample names.
+    return_sample_keys: a fifth value, dict(keys: int64 [K, 3] device tensor, one distinct (cohort, element, sample) row per kept
+    sample of an element -- the rows OBS_SAMPLES counts --, the sample numbered 0 .. n - 1 within its cohort over the samples that
+    were not blacklisted; n_samples: host int64 [C], that n per cohort)."""
     import torch
     dev = blocks.device
     C, E = len(cohorts), blocks.n_elements
@@ -381,6 +385,12 @@ def tabulate_cohorts(blocks, cohorts, drop_duplicates=True, max_muts_per_sample=
     obs_smp = z().index_add_(0, flat, torch.ones_like(snv)).view(E, C).to(torch.int32)
     black_np = black.cpu().numpy()
     blacklists = [[n for j, n in enumerate(c["sample_names"]) if black_np[int(o) + j]] for c, o in zip(cohorts, offs[:-1])]
+    if return_sample_keys:
+        kept = np.concatenate([[0], np.cumsum(~black_np[:n_samp_tot])])                  # kept samples in front of every global sample
+        first = torch.as_tensor(kept[np.asarray(offs[:-1], np.int64)], device=dev)      # ... in front of every cohort
+        local = torch.as_tensor(kept[:-1], device=dev)[key3[:, 2]] - first[key3[:, 0]] if n3 else key3[:, 2]
+        keys = torch.stack([key3[:, 0], key3[:, 1], local], dim=1)
+        return obs_snv, obs_smp, obs_ind, blacklists, dict(keys=keys, n_samples=np.diff(kept[np.asarray(offs, np.int64)]))
     return obs_snv, obs_smp, obs_ind, blacklists
 
 

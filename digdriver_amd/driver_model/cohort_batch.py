@@ -142,7 +142,8 @@ _QVAL_COLUMNS = ['QVAL_' + k[5:] for k in _PVAL_PLANES]                 # in the
 
 
 def element_pass(f_muts, f_pretrained, f_element_data, save_key, scale_factors=None, max_muts_per_sample=3e9,
-                 max_muts_per_elt_per_sample=3e9, device=0, timings=None, read_workers=None, output_form="records"):
+                 max_muts_per_elt_per_sample=3e9, device=0, timings=None, read_workers=None, output_form="records",
+                 keep_sample_keys=False):
     """The front half the four element routes share, and what their `element_pass=` argument takes: the three inputs read side by
     side, then _element_planes (the tabulation, the scale factors, the plan's pass and its unpacking).  Returns (planes, names,
     stages): `planes()` gives every plane a frame is built from as a device tensor, a cohort's column one contiguous row -- ELT_SIZE,
@@ -150,7 +151,10 @@ def element_pass(f_muts, f_pretrained, f_element_data, save_key, scale_factors=N
     (engine.ES_PLANES); CJ [C] -- `names` the element names and `stages` the _Stages of `timings`, marked up to "kernels".
     The three inputs are independent until the kernels need them, so they are read SIDE BY SIDE (round 5; one after the other
     they were 0.8 of the 1.5 s of a 37-cohort run): the maps (a thread per map), the element container, and the mutation
-    files -- each parsed by the library's own parser and uploaded by its own thread as soon as it is parsed."""
+    files -- each parsed by the library's own parser and uploaded by its own thread as soon as it is parsed.
+    keep_sample_keys: the tabulation's (cohort, element, sample) keys stay on the device beside the planes, as `planes.sample_keys`
+    (tabulate_gpu.tabulate_cohorts, return_sample_keys), with the elements' blocks as `planes.elements`: what run_element_pairs
+    needs.  Without it nothing is kept."""
     import time
     from concurrent.futures import ThreadPoolExecutor
     dev = resolve_device(device)
@@ -202,11 +206,14 @@ def element_pass(f_muts, f_pretrained, f_element_data, save_key, scale_factors=N
         print('Calculating scale factor')
         return genome_scale_factors(tables, cohorts, dev, dev_tables)
     return _element_planes(elts, tables, d_pr, ctx, cohorts, scale, max_muts_per_sample, max_muts_per_elt_per_sample, dev, st_,
-                           output_form), elts['names'], st_
+                           output_form, keep_sample_keys), elts['names'], st_
+
+
+_run_element_pass = element_pass                         # (the routes below take an argument of this name)
 
 
 def _element_planes(elts, tables, d_pr, ctx, cohorts, scale, max_muts_per_sample, max_muts_per_elt_per_sample, dev, st_,
-                    output_form="records"):
+                    output_form="records", keep_sample_keys=False):
     """What the element and the quick route do alike once both hold the elements (elts: chrom, blk_ptr, blk_start, blk_end,
     strand_minus, L -- host arrays or device tensors), the maps' tables and d_pr, the grid's window contexts ctx and the encoded
     cohorts: the bin overlaps, the join and tabulation, the scale factors, the plan's pass, its unpacking and the Gamma parameters.
@@ -221,9 +228,9 @@ def _element_planes(elts, tables, d_pr, ctx, cohorts, scale, max_muts_per_sample
     print('Tabulating mutations')
     owner = np.repeat(np.arange(E), np.diff(elts['blk_ptr']))
     blocks = tabulate_gpu.ElementBlocks(elts['chrom'][owner], elts['blk_start'], elts['blk_end'], owner, E, dev)
-    obs_snv, obs_smp, obs_ind, blacklists = tabulate_gpu.tabulate_cohorts(blocks, cohorts, drop_duplicates=True,
-                                                                          max_muts_per_sample=max_muts_per_sample,
-                                                                          max_muts_per_elt_per_sample=max_muts_per_elt_per_sample)
+    obs_snv, obs_smp, obs_ind, blacklists, *sample_keys = tabulate_gpu.tabulate_cohorts(
+        blocks, cohorts, drop_duplicates=True, max_muts_per_sample=max_muts_per_sample,
+        max_muts_per_elt_per_sample=max_muts_per_elt_per_sample, **(dict(return_sample_keys=True) if keep_sample_keys else {}))
     st_.mark("join_tabulate")
     dev_tables = tables.on_device(dev)                      # [N, C] on the device (uploaded cohort-major, transposed there)
     cj, cji = (x if torch.is_tensor(x) else torch.as_tensor(np.asarray(x, float), device=dev).reshape(C)
@@ -271,6 +278,10 @@ def _element_planes(elts, tables, d_pr, ctx, cohorts, scale, max_muts_per_sample
         D.update(P0=acc['P'][:, 0, :].transpose(0, 1).contiguous(), CJ=cj, OBS_SNV=by_cohort(obs_snv), OBS_SAMPLES=by_cohort(obs_smp),
                  OBS_INDEL=by_cohort(obs_ind))
         return D
+    if keep_sample_keys:
+        host = lambda a: a.cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
+        all_planes.sample_keys = sample_keys[0]
+        all_planes.elements = {k: host(elts[k]) for k in ('chrom', 'blk_ptr', 'blk_start', 'blk_end')}
     return all_planes
 
 
@@ -732,6 +743,164 @@ def run_and_write_element_power(f_muts, f_pretrained, f_element_data, save_key, 
     assert len(prefixes) == len(frames)
     paths = [os.path.join(outdir, pfx + '.power.txt') for pfx in prefixes] + [os.path.join(outdir, 'elements.power.txt')]
     return frames, summary, _write_frames(frames + [summary], paths, write_threads)
+
+
+# ---------------------------------------------------------------------------------------------
+# pairs of the element route: co-occurrence and exclusivity of the called elements across a cohort's samples
+# ---------------------------------------------------------------------------------------------
+PAIR_COLUMNS = ['ELT_B', 'N_SAMPLES', 'N_A', 'N_B', 'N_BOTH', 'N_A_ONLY', 'N_B_ONLY', 'N_NEITHER', 'LOG2_ODDS', 'PVAL_COOCCUR',
+                'PVAL_EXCLUSIVE', 'QVAL_COOCCUR', 'QVAL_EXCLUSIVE', 'TENDENCY']              # behind the index, ELT_A
+
+
+def _check_pairs(pair_pval_max, pair_fdr, min_samples, n_samples, C):
+    """run_element_pairs' own arguments, checked before a file is read."""
+    if (pair_pval_max is None) == (pair_fdr is None):
+        raise ValueError("exactly one of pair_pval_max and pair_fdr must be given")
+    if int(min_samples) != min_samples or min_samples < 1:
+        raise ValueError("min_samples: an integer >= 1, not %r" % (min_samples,))
+    if n_samples is not None and (len(n_samples) != C or any(int(n) != n or n < 1 for n in n_samples)):
+        raise ValueError("n_samples: one integer >= 1 per cohort (%d)" % C)
+
+
+def overlapping_pairs(chrom, blk_ptr, blk_start, blk_end, elements):
+    """The pairs (i < j) of positions in `elements` whose elements share a base: a block of one intersects a block of the other on one
+    chromosome (blocks half-open).  A sweep on the host over the blocks of the listed elements in (chromosome, start) order, each
+    against the blocks before it that are still open.  int64 [n, 2], ascending, without repeats."""
+    elements = np.asarray(elements, np.int64)
+    if len(elements) < 2:
+        return np.zeros((0, 2), np.int64)
+    n_blk = blk_ptr[elements + 1] - blk_ptr[elements]
+    pos = np.repeat(np.arange(len(elements)), n_blk)
+    blk = np.concatenate([np.arange(blk_ptr[e], blk_ptr[e + 1]) for e in elements]) if len(pos) else np.zeros(0, np.int64)
+    ch, lo, hi = np.asarray(chrom)[elements][pos], np.asarray(blk_start)[blk], np.asarray(blk_end)[blk]
+    order = np.lexsort((lo, ch))
+    found, active = set(), []                                # active: (end, position) of the blocks that may still reach a later start
+    last = None
+    for b in order:
+        if ch[b] != last:
+            active, last = [], ch[b]
+        active = [(e, q) for e, q in active if e > lo[b]]
+        if hi[b] > lo[b]:
+            found.update((min(q, pos[b]), max(q, pos[b])) for e, q in active if q != pos[b])
+            active.append((hi[b], pos[b]))
+    return np.array(sorted(found), np.int64).reshape(-1, 2)
+
+
+def _pair_rows_of(slot, H):
+    """(i, j) of the slots of one cohort's row-major upper triangle (engine.pair_index inverted), int64 arrays."""
+    slot = np.asarray(slot, np.int64)
+    i = np.floor(((2 * H - 1) - np.sqrt((2.0 * H - 1) ** 2 - 8.0 * slot)) / 2).astype(np.int64)
+    i = np.clip(i, 0, max(H - 2, 0))
+    for _ in range(2):                                       # (the square root may be off by one either way)
+        i = np.where(engine.pair_index(i, i + 1, H) > slot, i - 1, i)
+        i = np.where((i + 1 <= H - 2) & (engine.pair_index(i + 1, i + 2, H) <= slot), i + 1, i)
+    return i, slot - engine.pair_index(i, i + 1, H) + i + 1
+
+
+def run_element_pairs(f_muts, f_pretrained, f_element_data, save_key, pval_max=None, fdr=None, cut_on='PVAL_SNV_BURDEN',
+                      pair_pval_max=None, pair_fdr=None, min_samples=1, n_samples=None, scale_factors=None, max_muts_per_sample=3e9,
+                      max_muts_per_elt_per_sample=3e9, device=0, timings=None, read_workers=None, output_form="records",
+                      element_pass=None):
+    """How the calls of run_element_calls relate to each other across a cohort's samples: per cohort, for every pair of called elements,
+    the samples hit in both and the two one-sided Fisher exact tests -- co-occurrence and exclusivity -- with Benjamini-Hochberg over
+    the cohort's pairs (include/dig_hip.h and DESIGN, Pairs of the element route, state the rule; engine.pair_bits / engine.pair_fisher).
+    The element cut (pval_max / fdr, cut_on) is run_element_calls'; the hits with OBS_SAMPLES >= min_samples enter, in the order of
+    the hits frame (more than 8 192 of them in a cohort: ValueError).  Row h is the set of samples with a kept row in element h: the
+    tabulation's own (cohort, element, sample) keys, so its size is OBS_SAMPLES.  The universe is the cohort's samples that the
+    tabulation did not blacklist, or n_samples[c] >= that number (samples without a mutation are not in the file).
+    Pairs whose elements share a base would co-occur through one mutation: their p-values are NaN (not testable, outside the
+    Benjamini-Hochberg family), TENDENCY 'overlap', counts reported.  Exactly one of pair_pval_max / pair_fdr: a pair is reported when
+    either p-value (q-value) passes; only the reported pairs and the overlapping ones cross to the host.
+    One frame per cohort in pair order, index ELT_A, columns PAIR_COLUMNS; LOG2_ODDS = log2((N_BOTH + 1/2)(N_NEITHER + 1/2) /
+    ((N_A_ONLY + 1/2)(N_B_ONLY + 1/2))), TENDENCY 'co-occurrence' where it is above 0, else 'exclusivity'.  attrs: n_elements,
+    n_pairs, n_testable.  element_pass: what element_pass(..., keep_sample_keys=True) returned for the same inputs."""
+    import torch
+    j = _check_cut(pval_max, fdr, cut_on)
+    C = len(f_muts)
+    _check_pairs(pair_pval_max, pair_fdr, min_samples, n_samples, C)
+    given = element_pass or _run_element_pass(f_muts, f_pretrained, f_element_data, save_key, scale_factors, max_muts_per_sample,
+                                              max_muts_per_elt_per_sample, device, timings, read_workers, output_form, True)
+    planes, names, st_ = given
+    if not hasattr(planes, 'sample_keys'):
+        raise ValueError("element_pass: made without keep_sample_keys=True")
+    D = planes()
+    dev = D['S'].device
+    E = D['S'].shape[-1]
+    have_indel = (D['OBS_INDEL'].sum(dim=1) != 0).cpu().numpy()
+    if j >= 2 and not have_indel.all():
+        raise ValueError("cut_on = %s: cohorts %s have no indel columns" % (cut_on, [c for c in range(C) if not have_indel[c]]))
+    _, hit_ptr, row, elt, _ = _select_hits(D['S'][list(_PVAL_PLANES.values())], j, pval_max, fdr)
+    st_.mark("qvalues_select")
+    enters = D['OBS_SAMPLES'][row, elt] >= int(min_samples)
+    row, elt = row[enters], elt[enters]
+    rows = torch.bincount(row, minlength=C).cpu().numpy().astype(np.int64)              # H per cohort
+    if rows.max(initial=0) > engine.PAIR_MAX_ROWS:
+        raise ValueError("cohorts %s have more than %d entering elements (%s): raise min_samples (%d) or make the cut on %s stricter"
+                         % ([c for c in range(C) if rows[c] > engine.PAIR_MAX_ROWS], engine.PAIR_MAX_ROWS, rows.max(), min_samples, cut_on))
+    observed = np.asarray(planes.sample_keys['n_samples'], np.int64)
+    n = observed if n_samples is None else np.asarray(n_samples, np.int64)
+    if (n < observed).any():
+        raise ValueError("n_samples: below the samples of the mutation file that were not blacklisted (%s) in cohorts %s"
+                         % (observed.tolist(), np.nonzero(n < observed)[0].tolist()))
+    H_total = int(rows.sum())
+    # the bit matrix: the hit's place in the stacked matrix per (cohort, element), -1 elsewhere; one key per kept sample of an element
+    place = torch.full((C * E,), -1, dtype=torch.int32, device=dev)
+    place[row * E + elt] = torch.arange(H_total, dtype=torch.int32, device=dev)
+    keys = planes.sample_keys['keys']
+    bits = engine.pair_bits(place[keys[:, 0] * E + keys[:, 1]], keys[:, 2].to(torch.int32), H_total, engine.pair_words(int(n.max(initial=0))))
+    got = engine.pair_fisher(bits, rows, n)
+    st_.mark("pair_tests")
+    row_ptr, pair_ptr = got['plan']['row_ptr'], got['pair_ptr']
+    p = torch.stack([got['pval_cooccur'], got['pval_exclusive']])                      # [2, n_pairs]
+    # the pairs that share a base: found on the host among the entering elements' blocks, set to NaN on the device
+    elt_host, B = elt.cpu().numpy(), planes.elements
+    shared = [overlapping_pairs(B['chrom'], B['blk_ptr'], B['blk_start'], B['blk_end'], elt_host[row_ptr[c]:row_ptr[c + 1]]) for c in range(C)]
+    shared_slot = np.concatenate([pair_ptr[c] + engine.pair_index(s[:, 0], s[:, 1], int(rows[c])) for c, s in enumerate(shared)]
+                                 or [np.zeros(0, np.int64)]).astype(np.int64)
+    overlap = torch.zeros(p.shape[1], dtype=torch.bool, device=dev)
+    overlap[torch.as_tensor(shared_slot, device=dev)] = True
+    p[:, overlap] = float("nan")
+    # Benjamini-Hochberg per cohort and column over the testable pairs: the ragged lists of the non-NaN values
+    testable = ~p[0].isnan()
+    before = torch.cat([torch.zeros(1, dtype=torch.int64, device=dev), testable.cumsum(0)])
+    t_ptr = before[torch.as_tensor(pair_ptr, device=dev)].cpu().numpy()
+    q = torch.full_like(p, float("nan"))
+    if int(t_ptr[-1]):
+        for k in range(2):
+            q[k, testable] = nb_model.bh_ragged(p[k, testable], t_ptr)[0]
+    st_.mark("pair_qvalues")
+    level, by = (pair_fdr, q) if pair_fdr is not None else (pair_pval_max, p)
+    at = torch.nonzero(((by <= level).any(dim=0)) | overlap)[:, 0]
+    X = {k: v[..., at].cpu().numpy() for k, v in dict(P=p, Q=q, BOTH=got['n_both'], OVERLAP=overlap).items()}
+    slot, n_row = at.cpu().numpy(), got['n_row'].cpu().numpy().astype(np.int64)
+    st_.mark("d2h")
+    frames = []
+    names = np.asarray(names, dtype=object)
+    for c in range(C):
+        lo, hi = np.searchsorted(slot, [pair_ptr[c], pair_ptr[c + 1]])
+        i, k = _pair_rows_of(slot[lo:hi] - pair_ptr[c], int(rows[c]))
+        n_a, n_b, both = n_row[row_ptr[c] + i], n_row[row_ptr[c] + k], X['BOTH'][lo:hi].astype(np.int64)
+        a_only, b_only = n_a - both, n_b - both
+        neither = int(n[c]) - n_a - n_b + both
+        odds = np.log2((both + 0.5) * (neither + 0.5) / ((a_only + 0.5) * (b_only + 0.5)))
+        tendency = np.where(X['OVERLAP'][lo:hi], 'overlap', np.where(odds > 0, 'co-occurrence', 'exclusivity')).astype(object)
+        d = {'ELT_B': names[elt_host[row_ptr[c] + k]], 'N_SAMPLES': np.full(hi - lo, int(n[c]), np.int64), 'N_A': n_a, 'N_B': n_b,
+             'N_BOTH': both, 'N_A_ONLY': a_only, 'N_B_ONLY': b_only, 'N_NEITHER': neither, 'LOG2_ODDS': odds,
+             'PVAL_COOCCUR': X['P'][0, lo:hi], 'PVAL_EXCLUSIVE': X['P'][1, lo:hi], 'QVAL_COOCCUR': X['Q'][0, lo:hi],
+             'QVAL_EXCLUSIVE': X['Q'][1, lo:hi], 'TENDENCY': tendency}
+        frames.append(pd.DataFrame(d, index=pd.Index(names[elt_host[row_ptr[c] + i]], name='ELT_A'), columns=PAIR_COLUMNS))
+        frames[-1].attrs.update(n_elements=int(rows[c]), n_pairs=int(pair_ptr[c + 1] - pair_ptr[c]), n_testable=int(t_ptr[c + 1] - t_ptr[c]))
+    st_.mark("frames")
+    return frames
+
+
+def run_and_write_element_pairs(f_muts, f_pretrained, f_element_data, save_key, outdir, prefixes, write_threads=None, **kw):
+    """run_element_pairs with cohort c's frame written to <outdir>/<prefix>.pairs.txt (mapfile.write_results_tsv: the counts are
+    integers), as the calls' files are written (_write_frames).  Returns (frames, paths)."""
+    import os
+    frames = run_element_pairs(f_muts, f_pretrained, f_element_data, save_key, **kw)
+    assert len(prefixes) == len(frames)
+    return frames, _write_frames(frames, [os.path.join(outdir, pfx + '.pairs.txt') for pfx in prefixes], write_threads)
 
 
 def _writer_threads(n, write_threads=None):

@@ -1909,7 +1909,104 @@ def nb_power(alpha, theta, pi, level, scale=None, folds=(), k_max=1 << 20, devic
     return dict(k_crit=k_crit, power=power)
 
 
-MAP_TAILS = {"upper": 0, "side": 1}                      # `tail` of dig_map_windows (include/dig_hip.h)
+# ---------------------------------------------------------------------------
+# pairs of rows of a bit matrix: intersection counts and the two one-sided Fisher exact tests (dig_pair_bits, dig_pair_fisher)
+# ---------------------------------------------------------------------------
+PAIR_MAX_SAMPLES, PAIR_MAX_ROWS, PAIR_TILE, PAIR_CHUNK_BITS = 65536, 8192, 64, 2048      # DIG_PAIR_* (include/dig_hip.h)
+
+
+def pair_words(n_max):
+    """The u64 words of a bit row that holds n_max samples: even (16-byte rows), at least 2."""
+    return max(2, 2 * ((int(n_max) + 127) // 128))
+
+
+def pair_index(i, j, H):
+    """The slot of pair (i, j), i < j < H, in the row-major upper triangle of one cohort (numbers or arrays)."""
+    return i * (2 * H - i - 1) // 2 + (j - i - 1)
+
+
+def pair_plan(rows, n_samples):
+    """The plan-time arrays of dig_pair_fisher, on the host: rows[c] entering rows and n_samples[c] samples per cohort ->
+    dict(C, H_total, n_pairs, n_max, h_max, W, row_ptr i64 [C + 1], pair_ptr i64 [C + 1], n_samples i32 [C], tiles i32 [n_tiles, 3]).
+    ValueError for what the library would refuse: more than 65 536 samples or 8 192 rows in a cohort, 2^31 pairs or more."""
+    rows, n_samples = np.atleast_1d(np.asarray(rows, np.int64)), np.atleast_1d(np.asarray(n_samples, np.int64))
+    if rows.ndim != 1 or rows.shape != n_samples.shape or (rows < 0).any() or (n_samples < 0).any():
+        raise ValueError("rows and n_samples: one number >= 0 per cohort")
+    C = int(rows.shape[0])
+    n_max, h_max = (int(x.max()) if C else 0 for x in (n_samples, rows))
+    if n_max > PAIR_MAX_SAMPLES:
+        raise ValueError("pair_fisher: requirement failed: n_max <= 65 536 samples per cohort (got %d)" % n_max)
+    if h_max > PAIR_MAX_ROWS:
+        raise ValueError("pair_fisher: requirement failed: h_max <= 8 192 rows per cohort: a higher min_samples or a stricter cut "
+                         "(got %d)" % h_max)
+    row_ptr, pair_ptr = (np.concatenate([[0], np.cumsum(x)]).astype(np.int64) for x in (rows, rows * (rows - 1) // 2))
+    if pair_ptr[-1] >= 1 << 31:
+        raise ValueError("pair_fisher: requirement failed: fewer than 2^31 pairs per call: fewer cohorts per call (got %d)" % pair_ptr[-1])
+    tiles = [np.zeros((0, 3), np.int32)]
+    for c in range(C):
+        bi, bj = np.triu_indices((int(rows[c]) + PAIR_TILE - 1) // PAIR_TILE if rows[c] > 1 else 0)
+        tiles.append(np.stack([np.full(bi.shape, c), bi, bj], 1).astype(np.int32))
+    return dict(C=C, H_total=int(row_ptr[-1]), n_pairs=int(pair_ptr[-1]), n_max=n_max, h_max=h_max, W=pair_words(n_max), row_ptr=row_ptr,
+                pair_ptr=pair_ptr, n_samples=n_samples.astype(np.int32), tiles=np.ascontiguousarray(np.concatenate(tiles)))
+
+
+def _pair_bits_arg(be, bits, H_total, W):
+    """bits as the backend's i64 [H_total, W] (a numpy uint64 array is viewed, not converted)."""
+    if isinstance(bits, np.ndarray) and bits.dtype == np.uint64:
+        bits = np.ascontiguousarray(bits).view(np.int64)
+    bits = be.arr(bits, "i64")
+    if tuple(bits.shape) != (H_total, W):
+        raise ValueError("bits must be [%d, %d] (rows, pair_words(max n_samples)), not %r" % (H_total, W, tuple(bits.shape)))
+    return bits
+
+
+def pair_bits(row, sample, H_total, W, device=0):
+    """The stacked bit matrix of distinct (row, sample) keys (dig_pair_bits): row i32 [K] -- a row of the matrix, -1 where the key's
+    element does not enter --, sample i32 [K] the cohort-local sample index.  Returns bits i64 [H_total, W] (the bytes of u64 words:
+    sample s is bit s % 64 of word s / 64), W = pair_words(the largest n_samples).  Repeated keys are harmless.  ValueError for a
+    refused requirement.  CUDA tensors in -> a CUDA tensor out."""
+    be = backend_of(row, sample, device=device)
+    row, sample = be.arr(row, "i32", (-1,)), be.arr(sample, "i32", (-1,))
+    if row.shape != sample.shape:
+        raise ValueError("row and sample: one of each per key")
+    H_total, W, K = int(H_total), int(W), int(row.shape[0])
+    if H_total < 0 or W < 2 or W % 2 or W > PAIR_MAX_SAMPLES // 64:
+        raise ValueError("pair_bits: requirement failed: H_total >= 0, W even, 2 <= W <= 1024 (got %d, %d)" % (H_total, W))
+    bits = be.empty((H_total, W), "i64")
+    with _requirements_as_value_errors():
+        if H_total:
+            be.call("dig_pair_bits", be.ptr(row) if K else None, be.ptr(sample) if K else None, K, H_total, W, be.ptr(bits))
+    return bits
+
+
+def pair_fisher(bits, rows, n_samples, device=0, tails=True):
+    """Per pair of rows of each cohort the size of the intersection and the two one-sided Fisher exact p-values (dig_pair_fisher;
+    include/dig_hip.h states the rule): bits i64 / u64 [H_total, W] from pair_bits, rows[c] the rows of cohort c (stacked in cohort
+    order), n_samples[c] its samples -- host numbers, the plan (pair_plan).  Returns dict(n_row i32 [H_total], n_both i32 [n_pairs],
+    pval_cooccur, pval_exclusive f64 [n_pairs] (None with tails=False: dig_pair_counts), pair_ptr: host i64 [C + 1], plan); pair
+    (i, j) of cohort c is at pair_ptr[c] + pair_index(i, j, rows[c]).  ValueError for a refused requirement.  CUDA tensors in -> CUDA
+    tensors out."""
+    be = backend_of(bits, device=device)
+    plan = pair_plan(rows, n_samples)
+    H_total, P, W = plan["H_total"], plan["n_pairs"], plan["W"]
+    bits = _pair_bits_arg(be, bits, H_total, W)
+    n_row, n_both = be.empty(H_total, "i32"), be.empty(P, "i32")
+    p_co, p_ex = (be.empty(P, "f64"), be.empty(P, "f64")) if tails else (None, None)
+    if H_total:
+        dev = {k: be.arr(plan[k]) for k in ("row_ptr", "n_samples", "pair_ptr", "tiles")}
+        head = (be.ptr(bits), H_total, W, be.ptr(dev["row_ptr"]), be.ptr(dev["n_samples"]), be.ptr(dev["pair_ptr"]), plan["C"],
+                be.ptr(dev["tiles"]) if len(plan["tiles"]) else None, len(plan["tiles"]), P, plan["n_max"], plan["h_max"])
+        ptr = lambda x: be.ptr(x) if x is not None and P else None                 # (an empty tensor has no address)
+        with _requirements_as_value_errors():
+            if tails:
+                lnfact = be.empty(plan["n_max"] + 1, "f64")
+                be.call("dig_pair_fisher", *head, be.ptr(lnfact), be.ptr(n_row), ptr(n_both), ptr(p_co), ptr(p_ex))
+            else:
+                be.call("dig_pair_counts", *head, be.ptr(n_row), ptr(n_both))
+    return dict(n_row=n_row, n_both=n_both, pval_cooccur=p_co, pval_exclusive=p_ex, pair_ptr=plan["pair_ptr"], plan=plan)
+
+
+MAP_TAILS ={"upper": 0, "side": 1}                      # `tail` of dig_map_windows (include/dig_hip.h)
 MAP_LEVELS = (0.05, 0.01, 0.001, 0.0001)                 # the levels of N_BELOW (gp_tools.py:117-121)
 MAP_COUNTS = ("N_WINDOWS", "N_TESTED", "OBS_TOTAL") + tuple("N_BELOW_%g" % a for a in MAP_LEVELS)
 MAP_SUMS = ("EXP_TOTAL", "SXX", "SYY", "SXY")

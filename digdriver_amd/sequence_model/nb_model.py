@@ -106,6 +106,57 @@ def nb_critical_count(alpha, p, level, k_max=1 << 20, device=0):
     return got.reshape(tuple(alpha.shape))
 
 
+class PairTests:
+    """What pair_fisher_exact returns for one cohort of H rows: n_row i32 [H] and, per pair i < j at slot pair_index(i, j), n_both
+    i32, pval_cooccur and pval_exclusive f64 [H (H - 1) / 2] (row-major upper triangle; arrays or device tensors)."""
+
+    def __init__(self, H, n_samples, got):
+        self.H, self.n_samples = H, n_samples
+        self.n_row, self.n_both = got["n_row"], got["n_both"]
+        self.pval_cooccur, self.pval_exclusive = got["pval_cooccur"], got["pval_exclusive"]
+
+    def pair_index(self, i, j):
+        """The slot of the pair of rows i != j (numbers or arrays)."""
+        from .. import engine
+        i, j = np.minimum(i, j), np.maximum(i, j)
+        if np.any(i == j) or np.any(i < 0) or np.any(j >= self.H):
+            raise IndexError("a pair is two different rows of 0 .. %d" % (self.H - 1))
+        return engine.pair_index(i, j, self.H)
+
+
+def pair_fisher_exact(rows, n_samples=None, device=0):
+    """One-sided Fisher exact tests of co-occurrence and exclusivity for every pair of rows of one cohort's incidence matrix
+    (engine.pair_fisher; include/dig_hip.h states the rule).  rows: a bool [H, n] array, DataFrame or tensor (non-zero: the sample
+    is in the row) -- or the bit matrix of engine.pair_bits (int64 / uint64 [H, W]) with n_samples given.  n_samples: the universe,
+    at least n (samples that no row holds; default n).  pval_cooccur is scipy's fisher_exact(alternative='greater') of the pair's
+    2 x 2 table, pval_exclusive its alternative='less'.  Returns PairTests; device tensors in -> device tensors out."""
+    from .. import engine
+    if type(rows).__name__ == "DataFrame":
+        rows = rows.values
+    be = backend_of(rows, device=device)
+    if getattr(rows, "ndim", None) != 2:
+        rows = np.asarray(rows)
+    if rows.ndim != 2:
+        raise ValueError("rows must be a [H, n] matrix")
+    H = int(rows.shape[0])
+    if str(rows.dtype).split(".")[-1] in ("int64", "uint64"):
+        if n_samples is None:
+            raise ValueError("a bit matrix needs n_samples")
+        bits = rows
+    else:
+        n = int(rows.shape[1])
+        n_samples = n if n_samples is None else int(n_samples)
+        if n_samples < n:
+            raise ValueError("n_samples must be at least the matrix's %d columns" % n)
+        if be.is_device:
+            at = be.torch.nonzero(rows)
+            r, s = at[:, 0], at[:, 1]
+        else:
+            r, s = np.nonzero(rows)
+        bits = engine.pair_bits(r, s, H, engine.pair_words(n_samples), device=device)
+    return PairTests(H, int(n_samples), engine.pair_fisher(bits, [H], [int(n_samples)], device=device))
+
+
 # ---------------------------------------------------------------------------------------------
 # per-base / tiled route (nb_model.py:126-234, 340-342)
 # ---------------------------------------------------------------------------------------------

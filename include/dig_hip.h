@@ -674,6 +674,71 @@ int dig_nb_power_host(const double *alpha, const double *theta, const double *pi
                       int64_t rows, int64_t n, const double *folds, int n_folds, int32_t k_max, int32_t *k_crit, double *power,
                       int device);
 
+/* ---- pairs of the element route: co-occurrence and exclusivity of called elements across a cohort's samples (additive: the ABI
+ * version stays) ----------------------------------------------------------------------------------------------------------------- *
+ * The rule, for one cohort of n samples and H entering elements h = 0 .. H - 1 (nothing in the reference does this; it is pinned to
+ * exact integer arithmetic and to scipy):
+ *   row h    the set of samples with at least one kept mutation in element h, as n bits of W u64 words: sample s is bit s % 64 of word
+ *            s / 64; the bits behind sample n - 1 are zero.
+ *   counts   for every pair i < j: r = |row i|, k = |row j|, a = |row i AND row j| (N_BOTH), lo = max(0, r + k - n), hi = min(r, k).
+ *   density  pmf(x) = C(k, x) C(n - k, r - x) / C(n, r).
+ *   PVAL_COOCCUR  = sum_{x = a .. hi} pmf(x)   (scipy hypergeom.sf(a - 1, n, k, r); fisher_exact(alternative='greater'))
+ *   PVAL_EXCLUSIVE = sum_{x = lo .. a} pmf(x)  (hypergeom.cdf(a, n, k, r); alternative='less')
+ *            A pair with r = 0, k = 0, r = n or k = n has both equal to 1.
+ *   order    pairs are listed per cohort in row-major upper-triangle order, idx(i, j) = i (2 H - i - 1) / 2 + (j - i - 1);
+ *            pair_ptr[c] is the sum of H_c (H_c - 1) / 2 over the earlier cohorts.
+ *   tails    pmf(a) = exp of a sum of table entries ln(x!) (lnfact, x = 0 .. n_max, lgamma(x + 1), filled once per call).  With
+ *            mode = floor((r + 1)(k + 1) / (n + 2)): for a >= mode the upper tail, otherwise the lower one, is summed outward from
+ *            a by the ratio recurrence pmf(x + 1) / pmf(x) = (k - x)(r - x) / ((x + 1)(n - k - r + x + 1)); its terms fall, and it
+ *            stops when a term is no more than 2^-56 of the sum or the support ends.  The other tail is 1 - that + pmf(a).  Both are
+ *            capped at 1.  The small tail is a sum of positive terms, the large one is at least about a half.
+ *   limits   n <= DIG_PAIR_MAX_SAMPLES = 65 536, H <= DIG_PAIR_MAX_ROWS = 8 192 per cohort, fewer than 2^31 pairs per call.
+ *
+ * dig_pair_bits: (row, sample) keys -> the stacked bit matrix bits u64 [H_total, W], which the entry point zeroes first.  row i32
+ * [n_keys]: a row of the matrix, -1 (any value outside [0, H_total)) where the key's element does not enter; sample i32 [n_keys]:
+ * the cohort-local sample index (a value outside [0, 64 W) sets nothing).  One thread per key and one 32-bit atomic OR; a repeated
+ * key is harmless.  W: the call's words per row, even (16-byte rows), 2 <= W <= 1024.
+ * DIG_EINVAL before anything is launched: negative n_keys or H_total; W odd or outside [2, 1024]; H_total >= 2^31; n_keys >= 2^39;
+ * with H_total > 0 a NULL bits or one that is not 16-byte aligned; with n_keys > 0 a NULL row or sample.
+ *
+ * dig_pair_fisher: bits -> per row its popcount n_row i32 [H_total], per pair n_both i32, pval_cooccur f64 and pval_exclusive f64 at
+ * the pair's slot pair_ptr[c] + idx(i, j) ([n_pairs]); lnfact f64 [n_max + 1] is the table, an output the caller provides room for
+ * (the only workspace).  row_ptr i64 [C + 1] (cohort c owns the rows row_ptr[c] .. row_ptr[c + 1] - 1), n_samples i32 [C], pair_ptr
+ * i64 [C + 1]; tiles i32 [n_tiles, 3] = (cohort, block i, block j), one per DIG_PAIR_TILE x DIG_PAIR_TILE = 64 x 64 tile of a
+ * cohort's pair matrix with block i <= block j and 64 block j < H_c, in any order (engine.pair_tiles builds it: a few KB); a
+ * workgroup per tile, a diagonal tile does its upper triangle.  n_max >= every n_samples[c] and h_max >= every H_c are what the
+ * caller declares of the device arrays: the limits are checked on them, the table is sized by n_max, and the kernel clips a cohort
+ * to them and writes no slot outside [0, n_pairs).  A pair whose counts cannot belong to n samples (a bit set behind sample
+ * n - 1) gets NaN p-values.  The panels go through LDS DIG_PAIR_CHUNK_BITS = 2 048 samples at a time.
+ * dig_pair_counts: the same without the tail rule and the table: n_row and n_both only.
+ * DIG_EINVAL before anything is launched: a negative size; n_max > 65 536; h_max > 8 192; n_pairs >= 2^31; n_tiles, C or H_total >=
+ * 2^31; W odd, outside [2, 1024] or below n_max / 64; with H_total > 0 a NULL bits or one that is not 16-byte aligned, or a NULL
+ * n_row; a NULL lnfact; with n_pairs > 0 a NULL n_both, pval_cooccur or pval_exclusive; with n_tiles > 0 a NULL row_ptr, n_samples,
+ * pair_ptr or tiles.  The host twins also check the plan arrays themselves: row_ptr from 0 to H_total with 0 <= H_c <= h_max,
+ * 0 <= n_samples[c] <= n_max, pair_ptr[c + 1] - pair_ptr[c] = H_c (H_c - 1) / 2 up to n_pairs, every tile inside its cohort.  Device
+ * form and twin run the same kernels: their outputs are equal bit for bit. */
+#define DIG_PAIR_MAX_SAMPLES 65536
+#define DIG_PAIR_MAX_ROWS 8192
+#define DIG_PAIR_TILE 64
+#define DIG_PAIR_CHUNK_BITS 2048
+int dig_pair_bits(const int32_t *row, const int32_t *sample, int64_t n_keys, int64_t H_total, int64_t W, uint64_t *bits, void *stream);
+int dig_pair_bits_host(const int32_t *row, const int32_t *sample, int64_t n_keys, int64_t H_total, int64_t W, uint64_t *bits,
+                       int device);
+int dig_pair_fisher(const uint64_t *bits, int64_t H_total, int64_t W, const int64_t *row_ptr, const int32_t *n_samples,
+                    const int64_t *pair_ptr, int64_t C, const int32_t *tiles, int64_t n_tiles, int64_t n_pairs, int32_t n_max,
+                    int32_t h_max, double *lnfact, int32_t *n_row, int32_t *n_both, double *pval_cooccur, double *pval_exclusive,
+                    void *stream);
+int dig_pair_fisher_host(const uint64_t *bits, int64_t H_total, int64_t W, const int64_t *row_ptr, const int32_t *n_samples,
+                         const int64_t *pair_ptr, int64_t C, const int32_t *tiles, int64_t n_tiles, int64_t n_pairs, int32_t n_max,
+                         int32_t h_max, double *lnfact, int32_t *n_row, int32_t *n_both, double *pval_cooccur,
+                         double *pval_exclusive, int device);
+int dig_pair_counts(const uint64_t *bits, int64_t H_total, int64_t W, const int64_t *row_ptr, const int32_t *n_samples,
+                    const int64_t *pair_ptr, int64_t C, const int32_t *tiles, int64_t n_tiles, int64_t n_pairs, int32_t n_max,
+                    int32_t h_max, int32_t *n_row, int32_t *n_both, void *stream);
+int dig_pair_counts_host(const uint64_t *bits, int64_t H_total, int64_t W, const int64_t *row_ptr, const int32_t *n_samples,
+                         const int64_t *pair_ptr, int64_t C, const int32_t *tiles, int64_t n_tiles, int64_t n_pairs, int32_t n_max,
+                         int32_t h_max, int32_t *n_row, int32_t *n_both, int device);
+
 /* ---- the map report: a map's bins merged into larger windows, the region test per window, the scores of a cohort (additive: the
  * ABI version stays) ------------------------------------------------------------------------------------------------------------- *
  * Reference: gp_tools.merge_windows (sequence_model/gp_tools.py:125-160) and calibration_score_by_pvals (:117-121).

@@ -140,7 +140,9 @@ def cmd_element_cohorts(args):
     p-values combined per element by Fisher's method (cohort_batch.run_element_meta / run_element_meta_calls).  With --power also,
     behind the same pass, per cohort <outdir>/<outpfx>.power.txt and <outdir>/elements.power.txt: the critical count of --cut-on at the
     level of the run's own cut (--pval-max, --fdr, or --bonferroni, which cuts nothing itself) and the power at it under --power-folds
-    (cohort_batch.run_element_power)."""
+    (cohort_batch.run_element_power).  With --pairs (and --fdr or --pval-max: the pairs are pairs of calls) also per cohort
+    <outdir>/<outpfx>.pairs.txt: for every pair of called elements the samples hit in both and the one-sided Fisher exact tests of
+    co-occurrence and exclusivity, the pairs that pass --pairs-fdr (default 0.1) or --pairs-pval-max (cohort_batch.run_element_pairs)."""
     n = _cohort_lists(args, manual=False)
     factors = None
     if args.scale_factor_manual or args.scale_factor_indel_manual:
@@ -157,13 +159,16 @@ def cmd_element_cohorts(args):
     if cut is not None and not 0.0 < cut <= 1.0:
         raise SystemExit("ERROR: --fdr and --pval-max take a level within (0, 1].")
     power_kw = _power_options(args)
+    pairs_kw = _pairs_options(args, n)
     groups = _read_groups(args.groups, args.outpfx) if args.groups else None
     from digdriver_amd.driver_model import cohort_batch
     print('Running user-defined element driver detection for {} cohorts'.format(n))
     common = dict(scale_factors=factors, max_muts_per_sample=args.max_muts_per_sample,
                   max_muts_per_elt_per_sample=args.max_muts_per_elt_per_sample)
-    if groups is not None or power_kw is not None:   # the cohorts' files, the groups' and the power behind ONE pass over the inputs
-        common['element_pass'] = cohort_batch.element_pass(args.mutation_files, args.maps, args.f_element_data, args.save_key, **common)
+    if groups is not None or power_kw is not None or pairs_kw is not None:      # every route's files behind ONE pass over the inputs
+        keep = dict(keep_sample_keys=True) if pairs_kw is not None else {}
+        common['element_pass'] = cohort_batch.element_pass(args.mutation_files, args.maps, args.f_element_data, args.save_key, **common,
+                                                           **keep)
 
     def meta(**cut_kw):
         # (the groups' files beside the cohorts': <group>.meta.results.txt, or <group>.meta.hits.txt under the same cut)
@@ -189,6 +194,21 @@ def cmd_element_cohorts(args):
                 pfx, frame.attrs['level'], int(frame['POWERED'].sum()), frame.attrs['n_testable'], max(power_kw['folds']), path))
         print('\tSaved the per-element summary to {}'.format(paths[-1]))
 
+    def pairs():
+        if pairs_kw is None:
+            return
+        try:
+            frames, paths = _without_indel_columns_exit(cohort_batch.run_and_write_element_pairs, args.mutation_files, args.maps,
+                                                        args.f_element_data, args.save_key, args.outdir, args.outpfx, **cut_kw,
+                                                        **pairs_kw, **common)
+        except ValueError as exc:                        # (too many called elements for the pair matrix, --pairs-n-samples too small)
+            if 'entering elements' not in str(exc) and 'n_samples' not in str(exc):
+                raise
+            raise SystemExit("ERROR: --pairs: {}".format(exc))
+        for pfx, frame, path in zip(args.outpfx, frames, paths):
+            print('\t{}: {} pairs reported of {} testable among {} elements; saved to {}'.format(
+                pfx, len(frame), frame.attrs['n_testable'], frame.attrs['n_elements'], path))
+
     if cut is None:
         _, paths = cohort_batch.run_and_write_element_cohorts(args.mutation_files, args.maps, args.f_element_data, args.save_key,
                                                               args.outdir, args.outpfx, qvalues=args.qvalues, **common)
@@ -204,6 +224,7 @@ def cmd_element_cohorts(args):
         print('\t{}: {} hits of {} testable elements; saved to {}'.format(pfx, len(frame), frame.attrs['n_testable'], path))
     _without_indel_columns_exit(meta, **cut_kw)
     power()
+    pairs()
 
 
 def _power_options(args):
@@ -227,6 +248,30 @@ def _power_options(args):
         raise SystemExit("ERROR: --power-min takes a power within (0, 1].")
     return dict(pval_max=args.pval_max, fdr=args.fdr, bonferroni=args.bonferroni, cut_on=args.cut_on or 'PVAL_SNV_BURDEN',
                 folds=tuple(folds), power_min=power_min)
+
+
+def _pairs_options(args, n):
+    """--pairs of elementCohorts and what goes with it, checked before a file is read: None without --pairs, else the keywords of
+    cohort_batch.run_element_pairs that are its own (the level of the pairs, --pairs-min-samples, --pairs-n-samples)."""
+    own = (args.pairs_fdr, args.pairs_pval_max, args.pairs_min_samples, args.pairs_n_samples)
+    if not args.pairs:
+        if any(v is not None for v in own):
+            raise SystemExit("ERROR: --pairs-fdr, --pairs-pval-max, --pairs-min-samples and --pairs-n-samples need --pairs.")
+        return None
+    if (args.fdr is None) == (args.pval_max is None):
+        raise SystemExit("ERROR: --pairs needs exactly one of --fdr and --pval-max: the pairs are pairs of called elements.")
+    if args.pairs_fdr is not None and args.pairs_pval_max is not None:
+        raise SystemExit("ERROR: you must provide at most one of --pairs-fdr and --pairs-pval-max.")
+    level = args.pairs_pval_max if args.pairs_pval_max is not None else 0.1 if args.pairs_fdr is None else args.pairs_fdr
+    if not 0.0 < level <= 1.0:
+        raise SystemExit("ERROR: --pairs-fdr and --pairs-pval-max take a level within (0, 1].")
+    min_samples = 1 if args.pairs_min_samples is None else args.pairs_min_samples
+    if min_samples < 1:
+        raise SystemExit("ERROR: --pairs-min-samples takes a count of at least 1.")
+    if args.pairs_n_samples is not None and (len(args.pairs_n_samples) != n or min(args.pairs_n_samples) < 1):
+        raise SystemExit("ERROR: --pairs-n-samples takes one sample count >= 1 per cohort.")
+    return dict(pair_pval_max=args.pairs_pval_max, pair_fdr=None if args.pairs_pval_max is not None else level, min_samples=min_samples,
+                n_samples=args.pairs_n_samples)
 
 
 def _without_indel_columns_exit(run, *args, **kw):
@@ -608,6 +653,16 @@ def parse_args(text=None):
     ec.add_argument('--power-folds', type=float, nargs='+', default=None, help='with --power: the folds of selection (default 2 5 10; at most 8)')
     ec.add_argument('--power-min', type=float, default=None,
                     help='with --power: POWERED is the power at the largest fold >= this (default 0.8)')
+    ec.add_argument('--pairs', action='store_true', default=False,
+                    help='with --fdr or --pval-max, also write <outpfx>.pairs.txt: co-occurrence and exclusivity of the called elements '
+                         "across the cohort's samples (one-sided Fisher exact tests per pair, Benjamini-Hochberg over the pairs)")
+    ec.add_argument('--pairs-fdr', type=float, default=None, help='with --pairs: report the pairs with a q-value <= this (default 0.1)')
+    ec.add_argument('--pairs-pval-max', type=float, default=None, help='with --pairs: report the pairs with a p-value <= this instead')
+    ec.add_argument('--pairs-min-samples', type=int, default=None,
+                    help='with --pairs: only the called elements hit in at least this many samples enter (default 1)')
+    ec.add_argument('--pairs-n-samples', type=int, nargs='+', default=None,
+                    help="with --pairs: the cohorts' sample counts, one per cohort (default: the samples of the mutation file; samples "
+                         'without a mutation are not in it)')
     ec.add_argument('--groups', type=str, default=None,
                     help='file of two tab-separated columns, group name and cohort prefix (one of --outpfx): per group the cohorts\' '
                          'p-values combined by Fisher\'s method, as <group>.meta.results.txt (under a cut: <group>.meta.hits.txt)')
